@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/s of the rover step hot path (obs + reward + done + done compaction) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, pre-rolls, warms up, times exactly K steps in one pass and prints the result line; --dump-outputs DIR then
+also writes what the last timed step computed as DIR/<name>.npy.  Everything else it can measure (the roofline object, the cull
+statistics, the CPU baselines, the `also` workloads, repeated passes, the N > 1 alternate gather pass, the full record file) runs
+only with --full.
 
 A "step" is one fused RLTask.post_physics_step (rl_task.py:239-259) over one batch of synthetic sim states
 that are already resident in HBM: get_observations (P terrain rays + 26 rock rays per rover against the
@@ -22,7 +27,7 @@ N > 1 (weak scaling, 65 536 envs per GPU, one process per GPU over RCCL):
   serialised pass the headline one.  After each pass the root compares integer checksums of what it received with
   checksums every rank computed of what it sent (`gather_check`).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it carries two extra objects:
   roofline     — the ray-cast kernel: f32 VALU issue utilisation (instructions per launch from profiles/valu.json x 4
                  cycles / (1 024 SIMDs x 2.4 GHz x HIP-event time)), with the HBM side (PMC traffic, GB/s, fraction of
                  8 TB/s) and SURVEY §8(d)'s no-reuse byte model (`algorithmic_equiv_GBps`, `reuse_factor`) next to it
@@ -93,13 +98,22 @@ def parse(argv=None):
                          "and in the reference's as-shipped fp16 arithmetic, timed in the same process after the headline pass")
     ap.add_argument("--also-only", default="", help="comma-separated names of the `also` workloads to run (default: all)")
     ap.add_argument("--also-steps", type=int, default=50, help="timed steps per pass of each `also` workload (>= 20)")
-    ap.add_argument("--passes", type=int, default=30,
+    ap.add_argument("--passes", type=int, default=None,
                     help="back-to-back timed passes of --steps steps (each bracketed by barrier + device sync); value / ms_per_step are the MEDIAN "
-                         "pass, min / max in `passes`")
+                         "pass, min / max in `passes` (default: 1, with --full 30)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and cull objects, CPU baselines, the `also` workloads, "
+                         "30 passes, the N > 1 alternate gather pass, and the full record file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: a fixed, seeded sample of env rows beyond that)")
     ap.add_argument("--also-passes", type=int, default=5)
     ap.add_argument("--rank-timeout-s", type=float, default=900.0,
                     help="N > 1 self-launch: kill every rank and exit 124 when the run has not finished after this many seconds")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.passes is None:
+        args.passes = 30 if args.full else 1
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -477,10 +491,11 @@ def compact_line(full, full_path=None):
     ps = full.get("passes") or {}
     line["passes"] = {k: ps.get(k) for k in ("n", "min_ms_per_step", "max_ms_per_step")}
     line["passes"]["spread"] = _r(ps.get("spread"))
-    line["roofline"] = {k: _r(rf.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "avg_launch_ms",
-                                                   "stall_frac", "limited_by", "nearest_roof", "profile_key", "profile_stale")}
-    line["roofline"]["valu_frac"] = [_r(x) for x in rf["valu_frac_bracket"]] if rf.get("valu_frac_bracket") else None
-    line["roofline"]["algorithmic_equiv_GBps"] = _r(rf.get("algorithmic_equiv_GBps"))
+    if rf:
+        line["roofline"] = {k: _r(rf.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "avg_launch_ms",
+                                                       "stall_frac", "limited_by", "nearest_roof", "profile_key", "profile_stale")}
+        line["roofline"]["valu_frac"] = [_r(x) for x in rf["valu_frac_bracket"]] if rf.get("valu_frac_bracket") else None
+        line["roofline"]["algorithmic_equiv_GBps"] = _r(rf.get("algorithmic_equiv_GBps"))
     cb = full.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = {"value": _r(cb["value"]), "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
@@ -533,6 +548,36 @@ def write_full(full):
         except OSError:
             continue
     return None
+
+
+DUMP_LIMIT = 64 << 20        # bytes: --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, per_env, whole=None, seed=0):
+    """--dump-outputs: `per_env` maps names to tensors whose first dimension is the env, `whole` to tensors written as they are.
+    Floating tensors are written as float32, integer ones as float64 (exact), one DIR/<name>.npy each.  When the per-env arrays
+    would take the total past DUMP_LIMIT, the same fixed, seeded sample of env rows is taken from each, its indices in
+    env_index.npy.  -> the number of env rows written."""
+    import numpy as np
+    import torch
+
+    def host(t):
+        return t.detach().cpu().numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+
+    os.makedirs(out_dir, exist_ok=True)
+    whole = {k: host(v) for k, v in (whole or {}).items()}
+    n = next(iter(per_env.values())).shape[0]
+    row_bytes = sum((4 if t.is_floating_point() else 8) * (t.numel() // max(n, 1)) for t in per_env.values())
+    budget = DUMP_LIMIT - sum(a.nbytes for a in whole.values()) - 8 * n          # (env_index.npy, if a sample is taken)
+    m = min(n, max(1, budget // max(row_bytes, 1)))
+    if m < n:
+        idx = np.sort(np.random.default_rng(seed).choice(n, m, replace=False))
+        whole["env_index"] = idx.astype(np.float64)
+        sel = torch.from_numpy(idx)
+        per_env = {k: v[sel.to(v.device)] for k, v in per_env.items()}
+    for k, v in list(per_env.items()) + list(whole.items()):
+        np.save(os.path.join(out_dir, k + ".npy"), v if isinstance(v, np.ndarray) else host(v))
+    return m
 
 
 _SCENES = {}
@@ -927,7 +972,8 @@ def run_rank(args):
     def timed_passes(first_step, overlap, n):
         """n back-to-back passes of exactly --steps steps, each bracketed by barrier + device sync on both sides with the max over the
         ranks as its time; -> (median pass's time, min, max, gather check of the last pass, per-rank record of the median pass, steps run)"""
-        eng.set_profiling(True, every=args.event_every)      # resets the in-library ray-cast event counters
+        if args.full:
+            eng.set_profiling(True, every=args.event_every)  # resets the in-library ray-cast event counters
         recs = []
         for p in range(n):
             e, ok_p, pr = timed_pass(first_step + p * args.steps, overlap, check=(p == n - 1))
@@ -937,15 +983,22 @@ def run_rank(args):
         return med, t_min, t_max, recs[-1][1], pr_med, n * args.steps
 
     # Event timing is switched on BEFORE the warm-up: the first timed hipEventRecord on a stream makes the runtime
-    # enable queue profiling once (tens of ms); the warm-up absorbs that, then the counters are reset.
-    eng.set_profiling(True)
+    # enable queue profiling once (tens of ms); the warm-up absorbs that, then the counters are reset.  Only --full reads them.
+    if args.full:
+        eng.set_profiling(True)
     if args.preroll_ms > 0:                  # clock ramp: not part of the W warm-up steps or the K timed steps
+        # the pre-roll runs a time-dependent number of steps: the progress counters it advances are put back afterwards, so the
+        # warm-up and timed steps see the same inputs in every run with the same arguments (--dump-outputs compares runs)
+        progress0 = [b["progress"].clone() for b in batches]
         t_pre, i_pre = time.perf_counter(), 0
         while time.perf_counter() - t_pre < args.preroll_ms * 1e-3:      # local compute only: no collective, so the
             for _ in range(8):                                           # ranks need not agree on the iteration count
                 launch_step(i_pre % len(sins), 0)
                 i_pre += 1
             _sync()
+        for b, p0 in zip(batches, progress0):
+            b["progress"].copy_(p0)
+        _sync()
         if world > 1:
             dist.barrier()
     overlap = can_overlap and not args.sync_gather
@@ -953,13 +1006,30 @@ def run_rank(args):
         one_step(i, overlap)
     n_pass = max(1, args.passes)
     elapsed, t_min, t_max, ok, per_rank, ran = timed_passes(args.warmup, overlap, n_pass)
-    prof = eng.get_profile()
+    if args.dump_outputs and rank == 0:
+        last = args.warmup + ran - 1         # the outputs of the last timed step, before anything else runs on the engine
+        d = last % depth
+        if world == 1:
+            obs_d, rew_d, done_d = gather.local_views(d)
+            per_env = {"obs_buf": obs_d, "rew_buf": rew_d, "done": done_d, "reset_buf": reset, "progress_buf": batches[last % len(batches)]["progress"],
+                       "rock_collision": rock, "stone_collision": stone_mask, **{"extras_" + k: v for k, v in extras.items()}}
+            if args.validate_goals:          # reset_envs re-drew these for the envs the step flagged done
+                per_env.update({"state_" + k: batches[last % len(batches)][k] for k in ("pos", "quat", "joints", "target")})
+            whole = {"reset_ids": reset_ids[:int(n_reset.item())]}
+        else:                                # N > 1: what the learner rank received from every rank
+            og, rg, dg = gather.global_views(d)
+            per_env = {"obs_buf": og.reshape(-1, W), "rew_buf": rg.reshape(-1), "done": dg.reshape(-1)}
+            whole = None
+        n_rows = dump_outputs(args.dump_outputs, per_env, whole)
+        print(f"bench.py: wrote the outputs of timed step {last} ({n_rows} env rows) to {args.dump_outputs}", file=sys.stderr)
+    prof = eng.get_profile() if args.full else None
     alt = None
-    if world > 1 and can_overlap and not args.no_alt_pass:
+    if args.full and world > 1 and can_overlap and not args.no_alt_pass:
         e2, e2_min, e2_max, ok2, pr2, _ = timed_passes(args.warmup + ran, not overlap, min(5, n_pass))
         alt = {"mode": "overlapped" if not overlap else "sync_gather", "value": E_global * args.steps / e2,
                "ms_per_step": 1e3 * e2 / args.steps, "gather_check": ok2, "per_rank": pr2}
-    eng.set_profiling(False)
+    if args.full:
+        eng.set_profiling(False)
     if world > 1:            # every rank says who it was (a run that dies later still leaves this on stderr)
         print(f"bench.py: rank {rank}/{world} on cuda:{local_rank} ({torch.cuda.get_device_name(local_rank) if torch.cuda.is_available() else 'cpu'}), "
               f"backend {dist.get_backend()}, {1e3 * elapsed / args.steps:.4f} ms per step (median of {n_pass} passes)", file=sys.stderr, flush=True)
@@ -996,11 +1066,12 @@ def run_rank(args):
                        "table_bytes": int(info.table_bytes[0] + info.table_bytes[1])},
             "rccl_ranks": dist.get_world_size() if world > 1 else 1,
             "backend": dist.get_backend() if world > 1 else None,
-            "roofline": roofline(args, E, n_rays, prof, info, _lib_version()),
             "lib": _lib_version(),
             "lib_built_from_tree": _lib_matches_tree(),      # false: the .so was built from other sources than the ones next to it
         }
-        if info.raycast_variant >= 3:
+        if args.full:
+            line["roofline"] = roofline(args, E, n_rays, prof, info, _lib_version())
+        if args.full and info.raycast_variant >= 3:
             ci = eng.cull_info()
             line["cull"] = {"candidate_pairs_per_ray": ci["pairs_per_ray"], "rays_with_both_tests": ci["rays_both_tests"] / max(ci["rays"], 1),
                             "rays_per_bin": ci["rays"] / max(ci["bins"], 1), "max_pairs_per_run": ci["max_pairs_per_run"],
@@ -1021,11 +1092,11 @@ def run_rank(args):
                 line["alt_" + alt.pop("mode")] = alt
             if ok is False or (alt is not None and alt.get("gather_check") is False):
                 rc = 3
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(args, scene, distn, batches[0])
         default_workload = (world == 1 and args.mesh == "grid" and args.ray_precision == "fp32" and args.rays == "37"
                             and not args.validate_goals and not args.graph and E == 65536)
-        if default_workload and not args.no_also:
+        if args.full and default_workload and not args.no_also:
             # the representative workloads under the same clock: the geometry the reference's real terrain has (a decimated mesh,
             # utils/terrain_utils/terrain_generation.py:217-243) and its real arithmetic (fp16, camera.py:55) — headline fields unchanged
             eng.close()
@@ -1033,7 +1104,7 @@ def run_rank(args):
             torch.cuda.empty_cache()
             _SCENES[(args.mesh, args.cells, args.k, args.stones)] = (scene, zf)
             line["also"] = also_workloads(args, device, local_rank)
-        out_line = json.dumps(compact_line(line, write_full(line)), allow_nan=False, separators=(",", ":"))
+        out_line = json.dumps(compact_line(line, write_full(line) if args.full else None), allow_nan=False, separators=(",", ":"))
         if len(out_line) > COMPACT_LIMIT:
             print(f"bench.py: the record line is {len(out_line)} bytes (> {COMPACT_LIMIT}): a driver that keeps a bounded tail may lose it",
                   file=sys.stderr)

@@ -306,15 +306,17 @@ class FakeEngine:
 
 bench._device = lambda local_rank: torch.device("cpu")
 bench._init_process_group = lambda dist, device: dist.init_process_group("gloo")
-bench._make_engine = lambda n, local_rank, n_global, off: FakeEngine(n, off)
+engines = []
+bench._make_engine = lambda n, local_rank, n_global, off: engines.append(FakeEngine(n, off)) or engines[-1]
 bench._sync = lambda: None
 bench.load_scene = lambda args, device, local_rank=0: (None, None)
 rc = bench.main(sys.argv[1:])
-print("rank", os.environ["RANK"], "done", file=sys.stderr)
+print("engine steps", [e.steps for e in engines], file=sys.stderr)
+print("rank", os.environ.get("RANK", "0"), "done", file=sys.stderr)
 sys.exit(rc)
 """
 
-_BENCH_ARGS = ["--steps", "7", "--warmup", "3", "--envs-per-gpu", "64", "--preroll-ms", "20", "--passes", "3"]
+_BENCH_ARGS = ["--steps", "7", "--warmup", "3", "--envs-per-gpu", "64", "--preroll-ms", "20", "--passes", "3", "--full"]
 
 
 def _check_bench_line(out, extra):
@@ -415,6 +417,58 @@ def test_bench_self_launch_gloo(tmp_path, extra):
     assert p.returncode == 0, p.stderr[-3000:]
     assert "rank 0 done" in p.stderr and "rank 1 done" in p.stderr
     _check_bench_line(p.stdout, extra)
+
+
+def test_bench_plain_run_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: W + K engine steps and nothing else (no
+    pre-roll here, one pass, no roofline / cull / CPU baseline / `also` / full record); DIR holds the last timed step's outputs as
+    float32 / float64 arrays."""
+    import json
+    script = tmp_path / "bench_worker.py"
+    script.write_text(_BENCH_WORKER)
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(ROVER_ROOT=ROOT)
+    out = tmp_path / "out"
+    p = subprocess.run([sys.executable, str(script), "--gpus", "1", "--steps", "7", "--warmup", "3", "--envs-per-gpu", "64",
+                        "--preroll-ms", "0", "--dump-outputs", str(out)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert "engine steps [10]" in p.stderr
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["passes"]["n"] == 1 and d["ms_per_step"] > 0
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert k in d
+    assert not {"roofline", "cull", "cpu_baseline", "also", "full_record"} & set(d)
+    obs, rew, done = (np.load(out / f"{k}.npy") for k in ("obs_buf", "rew_buf", "done"))
+    assert obs.dtype == np.float32 and obs.shape == (64, 41) and done.dtype == np.float64
+    np.testing.assert_array_equal(obs, np.broadcast_to((torch.arange(64, dtype=torch.float32)[:, None] + 0.001 * 10).numpy(), (64, 41)))
+    np.testing.assert_array_equal(rew, np.arange(64))
+    np.testing.assert_array_equal(done, (np.arange(64) + 10) % 2)
+    assert np.load(out / "reset_ids.npy").shape == (0,) and not (out / "env_index.npy").exists()
+
+
+def test_bench_dump_outputs_stays_under_its_limit_with_a_seeded_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: past DUMP_LIMIT the same seeded env rows are taken from every per-env array (indices in env_index.npy),
+    and two dumps of the same arrays are identical."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 20_000)
+    n = 1000
+    per_env = {"obs_buf": torch.arange(n * 5, dtype=torch.float32).reshape(n, 5), "reset_buf": torch.arange(n) % 3}
+    whole = {"reset_ids": torch.arange(0, n, 3)}
+    for d in ("a", "b"):
+        m = bench.dump_outputs(str(tmp_path / d), per_env, whole)
+        assert 0 < m < n
+    sizes = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    assert sizes <= 20_000 + 4 * 128                                # + the .npy headers
+    for f in ("obs_buf", "reset_buf", "reset_ids", "env_index"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"{f}.npy"), np.load(tmp_path / "b" / f"{f}.npy"))
+    idx = np.load(tmp_path / "a" / "env_index.npy").astype(np.int64)
+    assert len(idx) == m and (np.diff(idx) > 0).all()
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "obs_buf.npy"), per_env["obs_buf"].numpy()[idx])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "reset_buf.npy"), idx % 3)
+    assert np.load(tmp_path / "a" / "reset_ids.npy").dtype == np.float64
 
 
 def test_bench_self_launch_reports_a_failed_rank(tmp_path):

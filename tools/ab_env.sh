@@ -8,7 +8,7 @@ for rep in 1 2; do
 for ev in "${envs[@]}"; do
   tag=$(echo "$ev" | tr -c 'A-Za-z0-9=' '_')
   P=/tmp/abe_$tag; rm -rf $P; mkdir -p $P
-  ( export $ev; rocprofv3 --kernel-trace --stats --output-format csv -d $P -- python3 bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-also --no-torch-ref "$@" > $P/bench.json 2> $P/err )
+  ( export $ev; rocprofv3 --kernel-trace --stats --output-format csv -d $P -- python3 bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-also --no-torch-ref "$@" > $P/bench.json 2> $P/err )
   python3 - "$ev" "$P" <<'PY'
 import csv, glob, json, sys
 v, P = sys.argv[1], sys.argv[2]

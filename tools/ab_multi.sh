@@ -8,7 +8,7 @@ for so in ab_tmp/*.so; do
   v=$(basename $so .so)
   cp $so isaac_rover_2.0_amd/csrc/librover_step.so
   P=/tmp/abm_$v; rm -rf $P; mkdir -p $P
-  rocprofv3 --kernel-trace --stats --output-format csv -d $P -- python3 bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-also --no-torch-ref "$@" > $P/bench.json 2> $P/err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $P -- python3 bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-also --no-torch-ref "$@" > $P/bench.json 2> $P/err
   python3 - "$v" "$P" <<'PY'
 import csv, glob, json, sys
 v, P = sys.argv[1], sys.argv[2]

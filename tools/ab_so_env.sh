@@ -11,7 +11,7 @@ for arm in "${arms[@]}"; do
   cp "$so" isaac_rover_2.0_amd/csrc/librover_step.so
   tag=$(echo "$arm" | tr -c 'A-Za-z0-9=' '_')
   P=/tmp/abs_$tag; rm -rf $P; mkdir -p $P
-  ( export $ev; rocprofv3 --kernel-trace --stats --output-format csv -d $P -- python3 bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-also --no-torch-ref "$@" > $P/bench.json 2> $P/err )
+  ( export $ev; rocprofv3 --kernel-trace --stats --output-format csv -d $P -- python3 bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-also --no-torch-ref "$@" > $P/bench.json 2> $P/err )
   python3 - "$arm" "$P" <<'PY'
 import csv, glob, json, sys
 v, P = sys.argv[1], sys.argv[2]

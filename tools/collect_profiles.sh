@@ -19,7 +19,7 @@ echo "profiling $LIB"
 python3 -c "import sys; sys.path.insert(0, '.'); from isaac_rover_amd import _lib; sys.exit(0 if _lib.version().endswith('src-' + _lib.source_hash()) else 1)" \
   || { echo "librover_step.so was not built from the sources in the tree: run csrc/build.sh first"; exit 1; }
 python3 bench.py --steps 5 --warmup 2 --passes 1 --no-cpu-baseline --no-also > /dev/null 2>&1       # builds the scene cache
-rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -- python3 bench.py --steps 200 --warmup 10 --passes 3 --no-cpu-baseline --no-also > "$OUT/${TAG}_bench_under_rocprof.json" 2> $P/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -- python3 bench.py --full --steps 200 --warmup 10 --passes 3 --no-cpu-baseline --no-also > "$OUT/${TAG}_bench_under_rocprof.json" 2> $P/stats.err
 
 pmc_passes() {   # $1 = workload key, $2 = file tag, rest = bench arguments
   local key=$1 ftag=$2; shift 2
@@ -43,15 +43,15 @@ pmc_passes E65536_P37_K200_C600_irregular "${TAG}_irregular" --mesh irregular
 cp "$OUT"/valu.json "$OUT"/traffic.json profiles/
 # (bench.py prints the compact record line on stdout and writes everything it measured to gpurun_out/bench_full.json: both are kept)
 b() { local name=$1; shift; python3 bench.py "$@" > "$OUT/${name}.json" 2> /dev/null; cp gpurun_out/bench_full.json "$OUT/${name}_full.json" 2> /dev/null; }
-b "${TAG}_bench"                                                  # the driver's command: headline + also{} + cpu_baseline
-b "${TAG}_bench_4096envs" --envs-per-gpu 4096 --steps 200 --warmup 100 --no-cpu-baseline --no-also
-b "${TAG}_bench_32768envs" --envs-per-gpu 32768 --no-cpu-baseline --no-also
-b "${TAG}_bench_cfg5_120rays_goalvalidation" --rays 120 --validate-goals --no-cpu-baseline --no-also
-b "${TAG}_bench_fp16_as_shipped" --ray-precision fp16_as_shipped --no-cpu-baseline --no-also
-b "${TAG}_bench_mesh_shuffled" --mesh shuffled --no-cpu-baseline --no-also
-b "${TAG}_bench_mesh_irregular" --mesh irregular --no-cpu-baseline --no-also
-b "${TAG}_bench_native_4096envs" --rays native --envs-per-gpu 4096 --no-cpu-baseline --no-also
+b "${TAG}_bench" --full                                           # the whole record: headline + also{} + cpu_baseline
+b "${TAG}_bench_4096envs" --full --envs-per-gpu 4096 --steps 200 --warmup 100 --no-cpu-baseline --no-also
+b "${TAG}_bench_32768envs" --full --envs-per-gpu 32768 --no-cpu-baseline --no-also
+b "${TAG}_bench_cfg5_120rays_goalvalidation" --full --rays 120 --validate-goals --no-cpu-baseline --no-also
+b "${TAG}_bench_fp16_as_shipped" --full --ray-precision fp16_as_shipped --no-cpu-baseline --no-also
+b "${TAG}_bench_mesh_shuffled" --full --mesh shuffled --no-cpu-baseline --no-also
+b "${TAG}_bench_mesh_irregular" --full --mesh irregular --no-cpu-baseline --no-also
+b "${TAG}_bench_native_4096envs" --full --rays native --envs-per-gpu 4096 --no-cpu-baseline --no-also
 # the reference's own operating point: numEnvs 512 (cfg/task/Rover.yaml:11) x its native 1 634 + 26 rays, on the decimated-style mesh
-b "${TAG}_bench_native_512envs_irregular" --rays native --envs-per-gpu 512 --mesh irregular --steps 200 --warmup 100 --no-cpu-baseline --no-also
-b "${TAG}_bench_native_512envs_irregular_fp16" --rays native --envs-per-gpu 512 --mesh irregular --ray-precision fp16_as_shipped --steps 200 --warmup 100 --no-cpu-baseline --no-also
+b "${TAG}_bench_native_512envs_irregular" --full --rays native --envs-per-gpu 512 --mesh irregular --steps 200 --warmup 100 --no-cpu-baseline --no-also
+b "${TAG}_bench_native_512envs_irregular_fp16" --full --rays native --envs-per-gpu 512 --mesh irregular --ray-precision fp16_as_shipped --steps 200 --warmup 100 --no-cpu-baseline --no-also
 ls -la "$OUT"

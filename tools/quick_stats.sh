@@ -3,7 +3,7 @@
 set -u
 export TMPDIR=/tmp
 P=/tmp/quick_stats; rm -rf $P; mkdir -p $P
-rocprofv3 --kernel-trace --stats --output-format csv -d $P -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline "$@" > $P/bench.json 2> $P/err
+rocprofv3 --kernel-trace --stats --output-format csv -d $P -- python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline "$@" > $P/bench.json 2> $P/err
 python3 - <<'PY'
 import csv, glob, json
 f = sorted(glob.glob("/tmp/quick_stats/**/*kernel_stats.csv", recursive=True))[-1]
