@@ -15,43 +15,76 @@
 
 using namespace rover;
 
+// One hipMalloc allocation, owned: freed when the owner is reset, replaced or destroyed (on the ctx's device: every entry point that can
+// free holds a DeviceGuard).  Move-only.
+template <typename T>
+class DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    // n elements in place of what the buffer held; on failure it holds nothing and the runtime's sticky error is cleared
+    hipError_t alloc(size_t n) {
+        reset();
+        const hipError_t e = hipMalloc((void**)&p_, n * sizeof(T));
+        if (e != hipSuccess) { (void)hipGetLastError(); p_ = nullptr; return e; }
+        n_ = n;
+        return e;
+    }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }
+    T* get() const { return p_; }
+    uint64_t bytes() const { return (uint64_t)n_ * sizeof(T); }
+
+  private:
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// The tables of one map for one rejection proof: proof 0 is the f32 one (ray_precision 0 / 1), proof 1 the as-shipped fp16 arithmetic's
+// (ray_precision 2).  The culled ray cast (variant 3) reads ctab and far; the staged one (variant 4) lvl / lrec / lid, which are optional.
+struct ProofTables {
+    DevBuf<uint4> ctab;                 // [T_int] bounding-sphere centre + scaled unit normal per triangle (16 B)
+    DevBuf<float4> far;                 // [cell][2] far-pair bounds, then [cell] near-pair bounds
+    DevBuf<float4> lvl;                 // staged: [cell][lane_lvl_stride()] header, suffix bounds, the suffixes' cones
+    DevBuf<uint4> lrec;                 // staged: [cell][2][pp] pair records of tests (A) and (B) in group-bound order
+    DevBuf<uint2> lid;                  // staged: [cell][pp] the pairs' triangle ids
+    int64_t always = 0, nocone = 0;     // always-candidate triangles, cells without a cone (counted when the tables were built)
+    LaneTables view() const { return LaneTables{lvl.get(), lrec.get(), lid.get()}; }
+};
+
+// Everything rover_set_knn_map builds for one map; built whole, then moved into the ctx in one assignment
+struct MapTables {
+    DevBuf<uint16_t> table;             // re-packed map, per-cell contiguous fp16 block [X*Y][9][K8]
+    KnnDev knn{};                       // its geometry; knn.table = table.get()
+    DevBuf<int32_t> cull_idx;           // culled / staged ray cast: [cell][K8] the cell's triangles in the internal numbering (null: not built)
+    DevBuf<uint16_t> rtab;              // [T_int] the nine fp16 vertex components of a triangle (20 B)
+    ProofTables proof[2];
+    uint32_t lane_pp = 0;               // pairs per row of the staged kernel's records
+    int64_t tris = 0, farok = 0, cells = 0;   // triangles; cells whose far bound can hold for a usual ray (far_build_kernel); cells
+    uint64_t bytes() const {
+        uint64_t b = table.bytes() + cull_idx.bytes() + rtab.bytes();
+        for (const ProofTables& p : proof) b += p.ctab.bytes() + p.far.bytes() + p.lvl.bytes() + p.lrec.bytes() + p.lid.bytes();
+        return b;
+    }
+};
+
 struct rover_ctx {
     rover_cfg cfg{};
     std::string err;
-    // re-packed maps
-    KnnDev map[2]{};
-    uint64_t table_bytes[2]{0, 0};
-    bool have_map[2]{false, false};
-    // tables of the culled ray cast (variant 3): the cell's triangle ids, and per triangle a bounding-sphere centre + scaled
-    // unit normal (16 B) and the nine fp16 vertex components (20 B)
-    int32_t* cull_idx[2]{nullptr, nullptr};
-    uint4* cull_ctab[2]{nullptr, nullptr};
-    uint4* cull_ctab_h[2]{nullptr, nullptr};    // the same for the as-shipped fp16 arithmetic's rejection proof (ray_precision 2)
-    uint32_t* cull_qrow_h[2]{nullptr, nullptr};
-    float4* cull_far[2]{nullptr, nullptr};      // [cell][2] far-pair bounds (f32 proof / fp16 proof)
-    float4* cull_far_h[2]{nullptr, nullptr};
-    uint16_t* cull_rtab[2]{nullptr, nullptr};
-    uint32_t* cull_qrow[2]{nullptr, nullptr};
-    uint64_t cull_bytes[2]{0, 0};
-    // tables of the staged ray cast (variant 4; f32 proof): per cell the pair records in group-bound order, their ids, the suffix bounds
-    LaneTables lane[2]{}, lane_h[2]{};  // per map: f32 proof / as-shipped fp16 proof
-    uint32_t lane_pp[2]{0, 0};
-    hipStream_t side = nullptr;         // variant 4: the rocks part's launch runs beside the terrain part's, on this stream, between two events
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int lane_side_stream = 0;           // ROVER_LANE_SIDE_STREAM=1: side by side (measured: 125 against 127 M env-steps/s one after the other — the two launches
-                                        // slow each other down by more than the rocks launch's ramp and tail cost; kept as a switch)
+    MapTables maps[2];                  // terrain, rocks
     int lane_env_order = -1;            // variant 4 without the sort (the ray slots in env order): -1 auto (mid-size batches), 0 / 1 (option "lane_env_order")
     int staged_tables = 3;              // which proofs' staged-kernel tables rover_set_knn_map builds: bit 0 the f32 proof, bit 1 the as-shipped fp16 one (option
                                         // "staged_tables", before the maps are set; ~4.3 KB per cell, K = 200, map and proof)
     int lane_rocks = -1;                // variant 4: the rocks part of the sorted list through the staged kernel too: -1 auto, 0 / 1 (option "lane_rocks", ROVER_LANE_ROCKS)
-    uint2* d_cull_queue = nullptr;      // candidate queue of the culled ray cast: one region of 1 024 entries per wave of a launch
+    DevBuf<uint2> d_cull_queue;         // candidate queue of the culled ray cast: one region of 1 024 entries per wave of a launch
     uint64_t cull_entries = 0;
-    uint4* d_cull_stats = nullptr;      // per-wave counters of the last culled launch (rover_get_cull_info)
+    DevBuf<uint4> d_cull_stats;         // per-wave counters of the last culled launch (rover_get_cull_info)
     uint32_t cull_stat_slots = 0;
     uint64_t stats_sig = 0;             // how the last launch that wrote the counters cast its rays (run_raycast)
-    int64_t cull_always[2]{0, 0}, cull_nocone[2]{0, 0}, cull_tris[2]{0, 0};      // per map, counted when its tables were built
-    int64_t cull_always_h[2]{0, 0}, cull_nocone_h[2]{0, 0};
-    int64_t cull_farok[2]{0, 0}, cull_cells[2]{0, 0};      // cells whose far bound can hold for a usual ray (far_build_kernel) / cells
     double cull_eta_h = 0.08;           // free parameter of the fp16 proof (rover_cull.hip, cull_proof_h); ROVER_CULLH_ETA for experiments
     double cull_split_h = 8.0;          // how test (A)'s cross term is split between its |h|^2 and rho^2 parts (cull_proof_h); ROVER_CULLH_SPLIT
     uint64_t cull_budget = 1536ull << 20;  // option "cull_queue_mb": most bytes the queue may take (a step is cast in several launches beyond it)
@@ -59,37 +92,39 @@ struct rover_ctx {
     int cull_lazy = -1;                 // ROVER_CULL_LAZY: -1 auto, 0 / 1 force (experiments)
     uint32_t cull_run = 0;              // run length the queue was sized for
     // distribution
-    double* d_dist = nullptr;       // [P][3]
-    int32_t* d_obs_idx = nullptr;   // [Ns+Nd]
+    DevBuf<double> d_dist;          // [P][3]
+    DevBuf<int32_t> d_obs_idx;      // [Ns+Nd]
     int32_t P = 0, Ns = 0, Nd = 0;
     bool have_dist = false;
-    // heightfield / stones
+    // heightfield / stones (hf and sgrid: the kernels' views of the owners beside them)
+    DevBuf<float> d_hm;
     HeightDev hf{};
     bool have_hf = false;
-    float* d_stones = nullptr;
+    DevBuf<float> d_stones;         // [S][7]
     int32_t S = 0;
+    DevBuf<uint32_t> d_grid_start;
+    DevBuf<float4> d_grid_xyr;
     StoneGridDev sgrid{};
     bool have_stones = false;
     // per-step workspace
     uint32_t R8 = 0;
-    RayRec* d_rays = nullptr;
-    float* d_dist_out = nullptr;    // [E*R8]
-    float* d_euler = nullptr;       // [E,3]
-    float* d_heading = nullptr;     // [E]
-    int64_t* d_ids_work = nullptr;  // [E]
-    uint32_t* d_goal_work = nullptr;// [2][E] work lists of generate_goals
-    uint32_t* d_block_cnt = nullptr;// [ceil(E/256)]
+    DevBuf<RayRec> d_rays;
+    DevBuf<float> d_dist_out;       // [E*R8]
+    DevBuf<float> d_euler;          // [E,3]
+    DevBuf<float> d_heading;        // [E]
+    DevBuf<int64_t> d_ids_work;     // [E]
+    DevBuf<uint32_t> d_goal_work;   // [2][E] work lists of generate_goals
+    DevBuf<uint32_t> d_block_cnt;   // [ceil(E/256)] + a spare word
     // ray binning (raycast variant 2)
-    uint32_t* d_bins = nullptr;         // [E*R8] bin key per slot
-    uint32_t* d_bkt_table = nullptr;    // [n_buckets * n_blocks] counts -> offsets
-    size_t bkt_table_bytes = 0;
+    DevBuf<uint32_t> d_bins;            // [E*R8] bin key per slot
+    DevBuf<uint32_t> d_bkt_table;       // [n_buckets * n_blocks] counts -> offsets
     bool bkt_table_dirty = true;        // not known to be all zero (what prep_rays_kernel's fused histogram starts from): a step failed half way
-    uint2* d_pairs = nullptr;           // [E*R8] (bin, slot) after the coarse partition
+    DevBuf<uint2> d_pairs;              // [E*R8] (bin, slot) after the coarse partition
     uint32_t low_bits = 10;             // bins per sort bucket = 2^low_bits, in force (alloc_bins)
     uint32_t low_bits_opt = 0;          // option "bin_low_bits": 0 = chosen by the library, else 8..12
     int precision = 0;                  // option "ray_precision": 0 fp32 mode, 1 fp16 sources, 2 as shipped (fp16 maths)
-    uint32_t* d_block_sums = nullptr;   // [4096] bucket totals + [4097] bucket starts
-    uint32_t* d_sorted = nullptr;       // [E*R8] ray slots sorted by (map, cell)
+    DevBuf<uint32_t> d_block_sums;      // [4096] bucket totals + [4097] bucket starts
+    DevBuf<uint32_t> d_sorted;          // [E*R8] ray slots sorted by (map, cell)
     bool defer_obs = false, obs_pending = false;   // rover_step: assemble_obs waits for do_metrics and shares its launch
     ObsArgs pending_obs{};
     uint32_t n_bins = 0;
@@ -99,8 +134,7 @@ struct rover_ctx {
     uint32_t run = 0;                   // option "raycast_run": 0 = auto (effective_run)
     uint32_t early_out = 1;             // option "raycast_early_out": conservative whole-pair rejection (bit-identical results)
     int32_t cell_rcp = 0;               // option "cell_index_mode": 0 cpu_div (x / 0.1), 1 cuda_rcp (x * (1 / 0.1))
-    float* d_mlp_scratch = nullptr;     // partial sums of the split-k small-batch encoder path (rover_mlp_chain_forward)
-    size_t mlp_scratch_floats = 0;
+    DevBuf<float> d_mlp_scratch;        // partial sums of the split-k small-batch encoder path (rover_mlp_chain_forward)
     uint64_t workspace_bytes = 0;
     bool ws_ok = false, bins_ok = false;   // false after a failed (re)allocation: the step entry points refuse to run
     bool rays_valid = false;            // the ray workspace holds a finished ray cast (rover_replay_raycast)
@@ -170,12 +204,9 @@ struct DeviceGuard {
     if (device_guard__.err != hipSuccess)                                                                      \
         return fail((c), ROVER_E_HIP, "hipSetDevice(%d): %s", (c)->cfg.device, hipGetErrorString(device_guard__.err))
 
-template <typename T>
-static void dfree(T*& p) {
-    if (p) { (void)hipFree((void*)p); p = nullptr; }
-}
-
 static uint64_t valid_rays(const rover_ctx* c) { return (uint64_t)c->cfg.num_envs * (26u + (uint64_t)c->P); }
+static bool have_maps(const rover_ctx* c) { return c->maps[0].table.get() && c->maps[1].table.get(); }
+static int proof_in_force(const rover_ctx* c) { return c->precision == 2 ? 1 : 0; }      // ProofTables: the as-shipped fp16 arithmetic has its own
 
 // Auto choice, measured on MI355X at K = 200, 37 + 26 rays (round 4, one call per size, whole step): the culled ray cast passes the
 // env-order kernel between 512 and 1 024 envs (32 k / 64 k rays: 9.8 vs 11.0 M env-steps/s at 512 — the four sort launches cost more than
@@ -193,17 +224,17 @@ static uint64_t valid_rays(const rover_ctx* c) { return (uint64_t)c->cfg.num_env
 #define ROVER_AUTO_LANE_RAYS 24576u
 #define ROVER_AUTO_LANE_ENV_RAYS_F16 98304u   // as shipped: below this many rays the staged kernel in env order (lane_env_order) is ahead of the culled one
 static bool lane_tables_ok(const rover_ctx* c) {
-    const LaneTables* t = c->precision == 2 ? c->lane_h : c->lane;
-    return t[0].lrec && t[1].lrec;
+    const int k = proof_in_force(c);
+    return c->maps[0].proof[k].lrec.get() && c->maps[1].proof[k].lrec.get();
 }
 static int effective_variant(const rover_ctx* c) {
-    const bool v2_ok = c->map[0].K8 <= 256 && c->map[1].K8 <= 256;      // 64 lanes x 4 triangles
+    const bool v2_ok = c->maps[0].knn.K8 <= 256 && c->maps[1].knn.K8 <= 256;      // 64 lanes x 4 triangles
     if (c->variant == 1 || !v2_ok) return 1;
     const bool v4_ok = lane_tables_ok(c);     // the staged kernel's tables of the proof in force, on both maps
     if (c->variant == 0 && c->precision != 2 && c->have_dist && valid_rays(c) < (v4_ok ? ROVER_AUTO_LANE_RAYS : ROVER_AUTO_CULL_RAYS_F32 + 1u)) return 1;
     if (c->variant == 0 && c->precision == 2 && c->have_dist && valid_rays(c) <= ROVER_AUTO_CULL_RAYS_F16) return 2;      // small batches, as shipped: binned
     // variant 3 (culled): its exact phase runs either arithmetic (f32 / as shipped), each with its own proof tables
-    const bool v3_ok = c->cull_idx[0] && c->cull_idx[1];
+    const bool v3_ok = c->maps[0].cull_idx.get() && c->maps[1].cull_idx.get();
     if (c->variant == 2 || !v3_ok) return 2;
     // variant 4 (staged, rover_cull.hip: lane = (ray, chunk of 8 pairs) over per-cell record rows): either arithmetic, each with its
     // proof's tables.  Auto: the table above; the native 1 634 + 26 rays at 512 envs on an irregular mesh 2.13 / 2.98 (culled / staged), the
@@ -223,8 +254,8 @@ static int effective_variant(const rover_ctx* c) {
         //  2.46, at 512 envs 1.56 / 2.24 / 2.44 / 2.10: on a regular terrain mesh the staged kernel from the binned kernel's range on.  Irregular terrain
         //  mesh: 4 096 envs 22.1 / 25.4 / 21.6 / 21.3; 16 384: 39.7 / 35.8 / 35.9 / 23.8; 65 536: 49.7 / 47.9 / 59.9 / 25.2; native rays at 512 envs 1.52 / 1.41 / 1.62 /
         //  1.42: staged from two heightmap rays per terrain cell, as before.)
-        else if (valid_rays(c) < ROVER_AUTO_LANE_ENV_RAYS_F16 || 2 * c->cull_farok[0] >= c->cull_cells[0] ||
-                 (uint64_t)c->cfg.num_envs * (uint64_t)c->P >= 2ull * (uint64_t)c->cull_cells[0]) return 4;
+        else if (valid_rays(c) < ROVER_AUTO_LANE_ENV_RAYS_F16 || 2 * c->maps[0].farok >= c->maps[0].cells ||
+                 (uint64_t)c->cfg.num_envs * (uint64_t)c->P >= 2ull * (uint64_t)c->maps[0].cells) return 4;
     }
     return 3;
 }
@@ -251,7 +282,7 @@ static uint32_t effective_run(const rover_ctx* c) {
     //  65 536: 91.9 / 111.8 / 133.0; 120 + 26 rays 38.5 / 53.9 / 65.0; irregular mesh 67.8 / 92.4 / 104.7)
     if (effective_variant(c) == 4) return r < 12 ? 32u : 64u;
     if (effective_variant(c) >= 3) {
-        const bool quick_rays = c->precision != 2 && 2 * c->cull_farok[0] >= c->cull_cells[0];      // regular mesh (most cells have a far bound), f32 arithmetic
+        const bool quick_rays = c->precision != 2 && 2 * c->maps[0].farok >= c->maps[0].cells;      // regular mesh (most cells have a far bound), f32 arithmetic
         if (quick_rays) return r < 3 ? 8u : (r < 6 ? 16u : (r < 20 ? 32u : 64u));                   // powers of two: 63 instead of 64 cost 6 %
         return r < 12 ? 8u : (r < 24 ? 16u : (r < 48 ? 32u : 64u));
     }
@@ -264,8 +295,8 @@ static int alloc_cull_queue(rover_ctx* c);
 
 static int alloc_bins(rover_ctx* c) {
     c->bins_ok = false;
-    if (!c->have_map[0] || !c->have_map[1]) return ROVER_OK;
-    const uint64_t nb = (uint64_t)c->map[0].X * c->map[0].Y + (uint64_t)c->map[1].X * c->map[1].Y;
+    if (!have_maps(c)) return ROVER_OK;
+    const uint64_t nb = (uint64_t)c->maps[0].knn.X * c->maps[0].knn.Y + (uint64_t)c->maps[1].knn.X * c->maps[1].knn.Y;
     if (nb > 0xfffffffeull) return fail(c, ROVER_E_INVALID, "too many map cells for ray binning");
     c->n_bins = (uint32_t)nb;
     c->low_bits = c->low_bits_opt ? c->low_bits_opt : 10u;
@@ -279,15 +310,13 @@ static int alloc_bins(rover_ctx* c) {
         while (lb > 8u && n_slots > (1ull << (32u - lb)) && ((c->n_bins + (1u << (lb - 1u)) - 1u) >> (lb - 1u)) <= 4096u) --lb;
         if (n_slots <= (1ull << (32u - lb))) c->low_bits = lb;
     }
-    if (!c->d_block_sums) HIP_TRY(c, hipMalloc((void**)&c->d_block_sums, (2 * 4096 + 8) * sizeof(uint32_t)));   // bucket totals + bucket starts
+    if (!c->d_block_sums.get()) HIP_TRY(c, c->d_block_sums.alloc(2 * 4096 + 8));   // bucket totals + bucket starts
     if (c->have_dist) {                                   // table size depends on E*R8 too
-        dfree(c->d_bkt_table);
         const uint64_t n_blocks = ((uint64_t)c->cfg.num_envs * c->R8 + 4095) / 4096;
-        c->bkt_table_bytes = ((uint64_t)bucket_count(c) * n_blocks + 1) * sizeof(uint32_t);
-        HIP_TRY(c, hipMalloc((void**)&c->d_bkt_table, c->bkt_table_bytes));
+        HIP_TRY(c, c->d_bkt_table.alloc((uint64_t)bucket_count(c) * n_blocks + 1));
         // zero from the start, here and not in the first step: a first step that is only CAPTURED (hipGraph) would record the clearing
         // without running it, and an eager step after it would count into whatever the allocation held
-        HIP_TRY(c, hipMemset(c->d_bkt_table, 0, c->bkt_table_bytes));
+        HIP_TRY(c, hipMemset(c->d_bkt_table.get(), 0, c->d_bkt_table.bytes()));
         c->bkt_table_dirty = false;
         c->bins_ok = true;
     }
@@ -296,49 +325,45 @@ static int alloc_bins(rover_ctx* c) {
 
 // candidate queue of the culled ray cast (one bounded region per resident wave) + its per-wave counters, for the options in force
 static int alloc_cull_queue(rover_ctx* c) {
-    if (!c->ws_ok || !c->have_dist || !c->have_map[0] || !c->have_map[1] || effective_variant(c) < 3) return ROVER_OK;
+    if (!c->ws_ok || !c->have_dist || !have_maps(c) || effective_variant(c) < 3) return ROVER_OK;
     const uint32_t run = effective_run(c);
     const uint64_t entries = cull_queue_entries(valid_rays(c), (uint32_t)c->cfg.num_envs * (uint32_t)c->P, run, c->cull_budget, &c->cull_launches);
     // (the per-wave counters are sized by the RAY count, the queue — once capped by the budget — is not: a second
     //  rover_set_distribution with more rays must grow the counters even when the queue keeps its size)
     // (by the PADDED slot count: in env order the staged kernel walks every slot of every env, and its runs are never shorter than `run`)
     const uint32_t slots = rover::cull_stat_slots((uint64_t)c->cfg.num_envs * c->R8, run < 16u ? run : 16u);
-    if (c->d_cull_queue && c->d_cull_stats && entries == c->cull_entries && run == c->cull_run && slots == c->cull_stat_slots) return ROVER_OK;
-    dfree(c->d_cull_queue); dfree(c->d_cull_stats);
+    if (c->d_cull_queue.get() && c->d_cull_stats.get() && entries == c->cull_entries && run == c->cull_run && slots == c->cull_stat_slots) return ROVER_OK;
+    c->d_cull_queue.reset(); c->d_cull_stats.reset();
     c->cull_stat_slots = 0;
     c->cull_entries = 0;
     // no fallback to another kernel: a queue that cannot be allocated is an error the caller sees
-    hipError_t e = hipMalloc((void**)&c->d_cull_queue, entries * sizeof(uint2));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        c->d_cull_queue = nullptr;
+    if (hipError_t e = c->d_cull_queue.alloc(entries))
         return fail(c, ROVER_E_NOMEM, "culled ray cast: candidate queue of %llu bytes: %s", (unsigned long long)(entries * sizeof(uint2)), hipGetErrorString(e));
-    }
     c->cull_entries = entries; c->cull_run = run;
-    HIP_TRY(c, hipMalloc((void**)&c->d_cull_stats, (size_t)slots * sizeof(uint4)));
+    HIP_TRY(c, c->d_cull_stats.alloc(slots));
     c->cull_stat_slots = slots;
     c->stats_sig = 0;
-    HIP_TRY(c, hipMemset(c->d_cull_stats, 0, (size_t)c->cull_stat_slots * sizeof(uint4)));
+    HIP_TRY(c, hipMemset(c->d_cull_stats.get(), 0, c->d_cull_stats.bytes()));
     return ROVER_OK;
 }
 
 static int alloc_workspace(rover_ctx* c) {
     c->ws_ok = false;
-    dfree(c->d_rays); dfree(c->d_dist_out); dfree(c->d_euler); dfree(c->d_heading); dfree(c->d_sorted);
-    dfree(c->d_bins); dfree(c->d_pairs);
+    c->d_rays.reset(); c->d_dist_out.reset(); c->d_euler.reset(); c->d_heading.reset(); c->d_sorted.reset();
+    c->d_bins.reset(); c->d_pairs.reset();
     const uint64_t E = (uint64_t)c->cfg.num_envs;
     c->R8 = (uint32_t)(((26 + c->P) + 7) / 8 * 8);
     const uint64_t n = E * c->R8;
     if (n > 0xffffffffull) return fail(c, ROVER_E_INVALID, "num_envs * rays_per_env = %llu exceeds 2^32", (unsigned long long)n);
-    HIP_TRY(c, hipMalloc((void**)&c->d_rays, n * sizeof(RayRec)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_dist_out, n * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_euler, E * 3 * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_heading, E * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_sorted, n * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_bins, n * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_pairs, n * sizeof(uint2)));
-    HIP_TRY(c, hipMemset(c->d_euler, 0, E * 3 * sizeof(float)));
-    HIP_TRY(c, hipMemset(c->d_heading, 0, E * sizeof(float)));
+    HIP_TRY(c, c->d_rays.alloc(n));
+    HIP_TRY(c, c->d_dist_out.alloc(n));
+    HIP_TRY(c, c->d_euler.alloc(E * 3));
+    HIP_TRY(c, c->d_heading.alloc(E));
+    HIP_TRY(c, c->d_sorted.alloc(n));
+    HIP_TRY(c, c->d_bins.alloc(n));
+    HIP_TRY(c, c->d_pairs.alloc(n));
+    HIP_TRY(c, hipMemset(c->d_euler.get(), 0, c->d_euler.bytes()));
+    HIP_TRY(c, hipMemset(c->d_heading.get(), 0, c->d_heading.bytes()));
     c->workspace_bytes = n * (sizeof(RayRec) + sizeof(float) + 2 * sizeof(uint32_t) + sizeof(uint2)) + E * (4 * sizeof(float) + sizeof(int64_t));
     c->rays_valid = false;
     c->obs_valid = false;
@@ -440,6 +465,85 @@ static void cull_numbering(const std::vector<float2>& cen, std::vector<uint32_t>
     }
 }
 
+// rover_set_knn_map's work, into `m` alone: the re-packed map, then — where the culled ray cast can serve the map (64 lanes x 4 triangles;
+// triangle ids and the map bit share 32 bits of a queue entry) — its tables, then the staged kernel's.  The build's own buffers go on return.
+static int build_map_tables(rover_ctx* c, MapTables& m, const int32_t* map_idx, int32_t X, int32_t Y, int32_t K, const int32_t* tris,
+                            int32_t T, const uint16_t* verts, int32_t V, float cell, float shift_x, float shift_y) {
+    const uint64_t n_cells = (uint64_t)X * Y;
+    const uint32_t K8 = (uint32_t)((K + 7) / 8 * 8);
+    DevBuf<int32_t> d_idx, d_tris;
+    DevBuf<uint16_t> d_verts;
+    hipError_t e;
+    if ((e = d_idx.alloc(n_cells * K)) != hipSuccess || (e = d_tris.alloc((uint64_t)T * 3)) != hipSuccess ||
+        (e = d_verts.alloc((uint64_t)V * 3)) != hipSuccess || (e = m.table.alloc(n_cells * 9ull * K8)) != hipSuccess)
+        return fail(c, ROVER_E_NOMEM, "set_knn_map: hipMalloc (%llu B table): %s", (unsigned long long)(n_cells * 9ull * K8 * sizeof(uint16_t)),
+                    hipGetErrorString(e));
+    if ((e = hipMemcpy(d_idx.get(), map_idx, d_idx.bytes(), hipMemcpyDefault)) != hipSuccess ||
+        (e = hipMemcpy(d_tris.get(), tris, d_tris.bytes(), hipMemcpyDefault)) != hipSuccess ||
+        (e = hipMemcpy(d_verts.get(), verts, d_verts.bytes(), hipMemcpyDefault)) != hipSuccess ||
+        (e = launch_repack(d_idx.get(), d_tris.get(), d_verts.get(), n_cells, (uint32_t)K, K8, (uint32_t)T, (uint32_t)V, m.table.get(), nullptr)) != hipSuccess ||
+        (e = hipDeviceSynchronize()) != hipSuccess)
+        return fail(c, ROVER_E_HIP, "set_knn_map: %s", hipGetErrorString(e));
+    m.knn = KnnDev{m.table.get(), X, Y, K, (int32_t)K8, cell, shift_x, shift_y, 1.0f / cell};
+    m.lane_pp = lane_pairs_per_row(K8);
+    m.tris = T; m.cells = (int64_t)n_cells;
+    if (K8 > 256 || (uint32_t)T >= 0x1ffffffu) return ROVER_OK;
+    // internal triangle numbering (spatial partners get ids 2p, 2p + 1, pairs ordered along a Morton curve): cull_numbering()
+    std::vector<uint32_t> order, newid((size_t)T);
+    {
+        DevBuf<float2> d_cen;
+        std::vector<float2> cen((size_t)T);
+        if ((e = d_cen.alloc(T)) != hipSuccess ||
+            (e = launch_tri_centroids(d_tris.get(), d_verts.get(), (uint32_t)T, (uint32_t)V, d_cen.get(), nullptr)) != hipSuccess ||
+            (e = hipMemcpy(cen.data(), d_cen.get(), d_cen.bytes(), hipMemcpyDeviceToHost)) != hipSuccess)
+            return fail(c, ROVER_E_HIP, "set_knn_map: triangle centroids: %s", hipGetErrorString(e));
+        cull_numbering(cen, order, newid);
+    }
+    const uint32_t T_int = (uint32_t)order.size();
+    if (T_int >= 0x3ffffffu) return fail(c, ROVER_E_INVALID, "set_knn_map: too many triangles for the culled ray cast's 26-bit ids");
+    // the culled ray cast's tables and the build's buffers (qrow: per cell and proof, read only by the build kernels)
+    DevBuf<uint32_t> d_qrow[2], d_order, d_newid, d_cnt;
+    DevBuf<float> d_nz;
+    if ((e = m.cull_idx.alloc(n_cells * K8)) != hipSuccess || (e = m.rtab.alloc((uint64_t)T_int * 10u)) != hipSuccess ||
+        (e = m.proof[0].ctab.alloc(T_int)) != hipSuccess || (e = m.proof[1].ctab.alloc(T_int)) != hipSuccess ||
+        (e = m.proof[0].far.alloc(3 * n_cells)) != hipSuccess || (e = m.proof[1].far.alloc(3 * n_cells)) != hipSuccess ||
+        (e = d_qrow[0].alloc(n_cells)) != hipSuccess || (e = d_qrow[1].alloc(n_cells)) != hipSuccess || (e = d_nz.alloc(T_int)) != hipSuccess ||
+        (e = d_cnt.alloc(8)) != hipSuccess || (e = d_order.alloc(T_int)) != hipSuccess || (e = d_newid.alloc(T)) != hipSuccess)
+        return fail(c, ROVER_E_HIP, "set_knn_map: cull tables: %s", hipGetErrorString(e));
+    // The staged kernel's tables are optional, each proof's on its own: which proofs get them is the "staged_tables" option, and an allocation
+    // that fails drops that proof's (the culled kernel then runs for it, effective_variant) — unless variant 4 was asked for by name.
+    for (int k = 0; k < 2; ++k) {
+        if (!((c->staged_tables >> k) & 1)) continue;
+        ProofTables& p = m.proof[k];
+        if ((e = p.lvl.alloc(n_cells * lane_lvl_stride())) != hipSuccess || (e = p.lrec.alloc(n_cells * 2ull * m.lane_pp)) != hipSuccess ||
+            (e = p.lid.alloc(n_cells * m.lane_pp)) != hipSuccess) {
+            p.lvl.reset(); p.lrec.reset(); p.lid.reset();
+            if (c->variant == 4)
+                return fail(c, ROVER_E_NOMEM, "set_knn_map: the staged ray cast's tables (%llu B per proof) do not fit and raycast_variant 4 was requested: %s",
+                            (unsigned long long)(n_cells * ((uint64_t)lane_lvl_stride() * sizeof(float4) + (uint64_t)m.lane_pp * (2 * sizeof(uint4) + sizeof(uint2)))),
+                            hipGetErrorString(e));
+        }
+    }
+    CullBuildArgs a{};
+    a.map_idx = d_idx.get(); a.tris = d_tris.get(); a.verts = d_verts.get();
+    a.n_cells = n_cells; a.K = (uint32_t)K; a.K8 = K8; a.T = (uint32_t)T; a.T_int = T_int; a.V = (uint32_t)V;
+    a.order = d_order.get(); a.newid = d_newid.get(); a.idx4 = m.cull_idx.get(); a.rtab = m.rtab.get();
+    a.ctab = m.proof[0].ctab.get(); a.ctab_h = m.proof[1].ctab.get(); a.qrow = d_qrow[0].get(); a.qrow_h = d_qrow[1].get();
+    a.far = m.proof[0].far.get(); a.far_h = m.proof[1].far.get(); a.nz_scratch = d_nz.get(); a.counts = d_cnt.get();
+    a.ph = cull_proof_h(c->cull_eta_h, c->cull_split_h); a.Y = (uint32_t)Y; a.cell_size = cell; a.shift_x = shift_x; a.shift_y = shift_y;
+    a.lane = m.proof[0].view(); a.lane_h = m.proof[1].view();
+    uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if ((e = hipMemcpy(d_order.get(), order.data(), d_order.bytes(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(d_newid.get(), newid.data(), d_newid.bytes(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemset(d_cnt.get(), 0, d_cnt.bytes())) != hipSuccess || (e = launch_cull_build(a, nullptr)) != hipSuccess ||
+        (e = hipDeviceSynchronize()) != hipSuccess || (e = hipMemcpy(h_cnt, d_cnt.get(), sizeof h_cnt, hipMemcpyDeviceToHost)) != hipSuccess)
+        return fail(c, ROVER_E_HIP, "set_knn_map: cull tables (%llu B): %s", (unsigned long long)m.bytes(), hipGetErrorString(e));
+    m.proof[0].always = h_cnt[0]; m.proof[0].nocone = h_cnt[1];
+    m.proof[1].always = h_cnt[2]; m.proof[1].nocone = h_cnt[3];
+    m.farok = h_cnt[4];
+    return ROVER_OK;
+}
+
 extern "C" {
 
 #ifndef ROVER_SRC_HASH
@@ -463,7 +567,6 @@ int rover_create(const rover_cfg* cfg, rover_ctx** out) {
     c->cfg = *cfg;
     if (c->cfg.num_envs_global <= 0) c->cfg.num_envs_global = c->cfg.num_envs;
     if (c->cfg.max_episode_length <= 0) c->cfg.max_episode_length = 3000;
-    if (const char* v = getenv("ROVER_LANE_SIDE_STREAM")) c->lane_side_stream = atoi(v) != 0 ? 1 : 0;
     if (const char* v = getenv("ROVER_LANE_ENV_ORDER")) c->lane_env_order = atoi(v) != 0 ? 1 : 0;
     if (const char* v = getenv("ROVER_LANE_ROCKS")) c->lane_rocks = atoi(v) != 0 ? 1 : 0;
     if (const char* v = getenv("ROVER_RAYCAST_VARIANT")) { int x = atoi(v); c->variant = (x >= 1 && x <= 4) ? x : 0; }
@@ -475,39 +578,17 @@ int rover_create(const rover_cfg* cfg, rover_ctx** out) {
     if (const char* v = getenv("ROVER_RAYCAST_RUN")) { int r = atoi(v); if (r >= 1 && r <= 4096) c->run = (uint32_t)r; }
     DeviceGuard guard(cfg->device);
     e = guard.err;
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_block_cnt, ((size_t)cfg->num_envs / 256 + 2) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_goal_work, 2 * (size_t)cfg->num_envs * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_ids_work, (size_t)cfg->num_envs * sizeof(int64_t));
+    if (e == hipSuccess) e = c->d_block_cnt.alloc((size_t)cfg->num_envs / 256 + 2);
+    if (e == hipSuccess) e = c->d_goal_work.alloc(2 * (size_t)cfg->num_envs);
+    if (e == hipSuccess) e = c->d_ids_work.alloc((size_t)cfg->num_envs);
     if (e != hipSuccess) { delete c; return fail(nullptr, ROVER_E_HIP, "rover_create: %s", hipGetErrorString(e)); }
-    if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        if (c->side) (void)hipStreamDestroy(c->side);
-        if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-        if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-        c->side = nullptr; c->ev_fork = nullptr; c->ev_join = nullptr;      // (no side stream: the launches run one after the other)
-    }
     *out = c;
     return ROVER_OK;
 }
 
 void rover_destroy(rover_ctx* c) {
     if (!c) return;
-    DeviceGuard guard(c->cfg.device);
-    for (int w = 0; w < 2; ++w) { uint16_t* t = const_cast<uint16_t*>(c->map[w].table); dfree(t); dfree(c->cull_idx[w]); dfree(c->cull_ctab[w]); dfree(c->cull_rtab[w]); dfree(c->cull_qrow[w]); dfree(c->cull_ctab_h[w]); dfree(c->cull_qrow_h[w]); dfree(c->cull_far[w]); dfree(c->cull_far_h[w]);
-                                  dfree(c->lane[w].lvl); dfree(c->lane[w].lrec); dfree(c->lane[w].lid); dfree(c->lane_h[w].lvl); dfree(c->lane_h[w].lrec); dfree(c->lane_h[w].lid); }
-    dfree(c->d_dist); dfree(c->d_obs_idx);
-    { float* h = const_cast<float*>(c->hf.hm); dfree(h); }
-    dfree(c->d_stones);
-    { uint32_t* p = const_cast<uint32_t*>(c->sgrid.cell_start); dfree(p); float4* q = const_cast<float4*>(c->sgrid.stone_xyr); dfree(q); }
-    dfree(c->d_rays); dfree(c->d_dist_out); dfree(c->d_euler); dfree(c->d_heading); dfree(c->d_ids_work);
-    dfree(c->d_bins); dfree(c->d_bkt_table); dfree(c->d_pairs); dfree(c->d_block_sums); dfree(c->d_sorted);
-    dfree(c->d_block_cnt);
-    dfree(c->d_goal_work);
-    dfree(c->d_cull_queue); dfree(c->d_cull_stats); dfree(c->d_mlp_scratch);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+    DeviceGuard guard(c->cfg.device);         // the owners free their device memory on the ctx's device
     for (auto& e : c->ev0) (void)hipEventDestroy(e);
     for (auto& e : c->ev1) (void)hipEventDestroy(e);
     delete c;
@@ -522,128 +603,9 @@ int rover_set_knn_map(rover_ctx* c, int which, const int32_t* map_idx, int32_t X
         return fail(c, ROVER_E_INVALID, "set_knn_map: bad shape X=%d Y=%d K=%d T=%d V=%d cell=%g", X, Y, K, T, V, (double)cell);
     if ((uint64_t)X * (uint64_t)Y > 0xffffffffull) return fail(c, ROVER_E_INVALID, "set_knn_map: X*Y exceeds 2^32 cells");
     USE_DEVICE(c);
-    const uint64_t n_cells = (uint64_t)X * Y;
-    const uint32_t K8 = (uint32_t)((K + 7) / 8 * 8);
-    const uint64_t bytes = n_cells * 9ull * K8 * sizeof(uint16_t);
-    int32_t *d_idx = nullptr, *d_tris = nullptr;
-    uint16_t *d_verts = nullptr, *d_table = nullptr;
-    auto cleanup = [&]() { dfree(d_idx); dfree(d_tris); dfree(d_verts); };
-    hipError_t e;
-    if ((e = hipMalloc((void**)&d_idx, n_cells * K * sizeof(int32_t))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_tris, (uint64_t)T * 3 * sizeof(int32_t))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_verts, (uint64_t)V * 3 * sizeof(uint16_t))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_table, bytes)) != hipSuccess) {
-        cleanup(); dfree(d_table);
-        return fail(c, ROVER_E_NOMEM, "set_knn_map: hipMalloc (%llu B table): %s", (unsigned long long)bytes, hipGetErrorString(e));
-    }
-    if ((e = hipMemcpy(d_idx, map_idx, n_cells * K * sizeof(int32_t), hipMemcpyDefault)) != hipSuccess ||
-        (e = hipMemcpy(d_tris, tris, (uint64_t)T * 3 * sizeof(int32_t), hipMemcpyDefault)) != hipSuccess ||
-        (e = hipMemcpy(d_verts, verts, (uint64_t)V * 3 * sizeof(uint16_t), hipMemcpyDefault)) != hipSuccess ||
-        (e = launch_repack(d_idx, d_tris, d_verts, n_cells, (uint32_t)K, K8, (uint32_t)T, (uint32_t)V, d_table, nullptr)) != hipSuccess ||
-        (e = hipDeviceSynchronize()) != hipSuccess) {
-        cleanup(); dfree(d_table);
-        return fail(c, ROVER_E_HIP, "set_knn_map: %s", hipGetErrorString(e));
-    }
-    // tables of the culled ray cast (64 lanes x 4 triangles; triangle ids and the map bit share 32 bits of a queue entry)
-    int32_t* d_cidx = nullptr;
-    uint4 *d_ctab = nullptr, *d_ctab_h = nullptr;
-    uint16_t* d_rtab = nullptr;
-    uint32_t *d_qrow = nullptr, *d_qrow_h = nullptr;
-    float4 *d_far = nullptr, *d_far_h = nullptr;
-    float* d_nz = nullptr;
-    LaneTables lt{}, lth{};
-    const uint32_t lane_pp = lane_pairs_per_row(K8);
-    uint32_t* d_cnt = nullptr;
-    uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t cull_bytes = 0;
-    uint32_t *d_order = nullptr, *d_newid = nullptr;
-    if (K8 <= 256 && (uint32_t)T < 0x1ffffffu) {
-        const uint64_t b_idx = n_cells * K8 * sizeof(int32_t);
-        uint32_t T_int = 0;
-        auto drop = [&]() { cleanup(); dfree(d_cidx); dfree(d_ctab); dfree(d_ctab_h); dfree(d_rtab); dfree(d_qrow); dfree(d_qrow_h); dfree(d_far); dfree(d_far_h); dfree(d_nz); dfree(d_cnt);
-                            dfree(d_order); dfree(d_newid); dfree(d_table); dfree(lt.lvl); dfree(lt.lrec); dfree(lt.lid); dfree(lth.lvl); dfree(lth.lrec); dfree(lth.lid); };
-        // internal triangle numbering (spatial partners get ids 2p, 2p + 1, pairs ordered along a Morton curve): cull_numbering()
-        std::vector<uint32_t> order, newid((size_t)T);
-        {
-            float2* d_cen = nullptr;
-            std::vector<float2> cen((size_t)T);
-            if ((e = hipMalloc((void**)&d_cen, (uint64_t)T * sizeof(float2))) != hipSuccess ||
-                (e = launch_tri_centroids(d_tris, d_verts, (uint32_t)T, (uint32_t)V, d_cen, nullptr)) != hipSuccess ||
-                (e = hipMemcpy(cen.data(), d_cen, (uint64_t)T * sizeof(float2), hipMemcpyDeviceToHost)) != hipSuccess) {
-                dfree(d_cen); drop();
-                return fail(c, ROVER_E_HIP, "set_knn_map: triangle centroids: %s", hipGetErrorString(e));
-            }
-            dfree(d_cen);
-            cull_numbering(cen, order, newid);
-        }
-        T_int = (uint32_t)order.size();
-        if (T_int >= 0x3ffffffu) { drop(); return fail(c, ROVER_E_INVALID, "set_knn_map: too many triangles for the culled ray cast's 26-bit ids"); }
-        const uint64_t b_ct = (uint64_t)T_int * sizeof(uint4), b_rt = (uint64_t)T_int * 20u;
-        const uint64_t b_lane = n_cells * ((uint64_t)lane_lvl_stride() * sizeof(float4) + (uint64_t)lane_pp * (2 * sizeof(uint4) + sizeof(uint2)));
-        // The staged kernel's tables are optional: which proofs get them is the "staged_tables" option, and an allocation that fails drops them
-        // (the culled kernel then runs, effective_variant) — unless variant 4 was asked for by name.
-        const bool want_f = (c->staged_tables & 1) != 0, want_h = (c->staged_tables & 2) != 0;
-        auto lane_alloc = [&](LaneTables& t) -> hipError_t {
-            hipError_t le;
-            if ((le = hipMalloc((void**)&t.lvl, n_cells * (uint64_t)lane_lvl_stride() * sizeof(float4))) != hipSuccess ||
-                (le = hipMalloc((void**)&t.lrec, n_cells * 2ull * lane_pp * sizeof(uint4))) != hipSuccess ||
-                (le = hipMalloc((void**)&t.lid, n_cells * (uint64_t)lane_pp * sizeof(uint2))) != hipSuccess) {
-                dfree(t.lvl); dfree(t.lrec); dfree(t.lid);
-                t = LaneTables{};
-                (void)hipGetLastError();
-            }
-            return le;
-        };
-        hipError_t le = hipSuccess;
-        if (want_f) le = lane_alloc(lt);
-        if (want_h && le == hipSuccess) le = lane_alloc(lth);
-        if (le != hipSuccess) {
-            dfree(lt.lvl); dfree(lt.lrec); dfree(lt.lid); lt = LaneTables{};
-            if (c->variant == 4) {
-                drop();
-                return fail(c, ROVER_E_NOMEM, "set_knn_map: the staged ray cast's tables (%llu B per proof) do not fit and raycast_variant 4 was requested: %s",
-                            (unsigned long long)b_lane, hipGetErrorString(le));
-            }
-        }
-        cull_bytes = b_idx + 2 * b_ct + b_rt + 2 * n_cells * sizeof(uint32_t) + 2 * n_cells * 48u + ((lt.lrec ? 1 : 0) + (lth.lrec ? 1 : 0)) * b_lane;
-        if ((e = hipMalloc((void**)&d_cidx, b_idx)) != hipSuccess || (e = hipMalloc((void**)&d_ctab, b_ct)) != hipSuccess ||
-            (e = hipMalloc((void**)&d_ctab_h, b_ct)) != hipSuccess || (e = hipMalloc((void**)&d_qrow_h, n_cells * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMalloc((void**)&d_rtab, b_rt)) != hipSuccess || (e = hipMalloc((void**)&d_qrow, n_cells * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMalloc((void**)&d_far, n_cells * 48u)) != hipSuccess || (e = hipMalloc((void**)&d_far_h, n_cells * 48u)) != hipSuccess ||
-            (e = hipMalloc((void**)&d_nz, (uint64_t)T_int * sizeof(float))) != hipSuccess ||
-            (e = hipMalloc((void**)&d_cnt, 8 * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMalloc((void**)&d_order, (uint64_t)T_int * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMalloc((void**)&d_newid, (uint64_t)T * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMemcpy(d_order, order.data(), (uint64_t)T_int * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy(d_newid, newid.data(), (uint64_t)T * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemset(d_cnt, 0, 8 * sizeof(uint32_t))) != hipSuccess ||
-            (e = launch_cull_build(d_idx, d_tris, d_verts, n_cells, (uint32_t)K, K8, (uint32_t)T, T_int, (uint32_t)V, d_order, d_newid, d_cidx,
-                                   d_ctab, d_ctab_h, d_rtab, d_qrow, d_qrow_h, d_far, d_far_h, d_nz, d_cnt, cull_proof_h(c->cull_eta_h, c->cull_split_h), (uint32_t)Y, cell,
-                                   shift_x, shift_y, lt, lth, nullptr)) != hipSuccess ||
-            (e = hipDeviceSynchronize()) != hipSuccess ||
-            (e = hipMemcpy(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost)) != hipSuccess) {
-            drop();
-            return fail(c, ROVER_E_HIP, "set_knn_map: cull tables (%llu B): %s", (unsigned long long)cull_bytes, hipGetErrorString(e));
-        }
-    }
-    cleanup();
-    dfree(d_nz); dfree(d_cnt); dfree(d_order); dfree(d_newid);
-    c->cull_always[which] = h_cnt[0]; c->cull_nocone[which] = h_cnt[1]; c->cull_tris[which] = T;
-    c->cull_always_h[which] = h_cnt[2]; c->cull_nocone_h[which] = h_cnt[3];
-    c->cull_farok[which] = h_cnt[4]; c->cull_cells[which] = (int64_t)n_cells;
-    uint16_t* old = const_cast<uint16_t*>(c->map[which].table);
-    dfree(old);
-    dfree(c->cull_idx[which]); dfree(c->cull_ctab[which]); dfree(c->cull_rtab[which]); dfree(c->cull_qrow[which]);
-    dfree(c->cull_ctab_h[which]); dfree(c->cull_qrow_h[which]); dfree(c->cull_far[which]); dfree(c->cull_far_h[which]);
-    dfree(c->lane[which].lvl); dfree(c->lane[which].lrec); dfree(c->lane[which].lid);
-    dfree(c->lane_h[which].lvl); dfree(c->lane_h[which].lrec); dfree(c->lane_h[which].lid);
-    c->lane[which] = lt; c->lane_h[which] = lth; c->lane_pp[which] = lane_pp;
-    c->cull_far[which] = d_far; c->cull_far_h[which] = d_far_h;
-    c->cull_idx[which] = d_cidx; c->cull_ctab[which] = d_ctab; c->cull_rtab[which] = d_rtab; c->cull_qrow[which] = d_qrow; c->cull_bytes[which] = cull_bytes;
-    c->cull_ctab_h[which] = d_ctab_h; c->cull_qrow_h[which] = d_qrow_h;
-    c->map[which] = KnnDev{d_table, X, Y, K, (int32_t)K8, cell, shift_x, shift_y, 1.0f / cell};
-    c->table_bytes[which] = bytes + cull_bytes;
-    c->have_map[which] = true;
+    MapTables m;
+    if (int r = build_map_tables(c, m, map_idx, X, Y, K, tris, T, verts, V, cell, shift_x, shift_y)) return r;      // (the previous map stays)
+    c->maps[which] = std::move(m);
     c->rays_valid = false;
     return alloc_bins(c);
 }
@@ -666,12 +628,12 @@ int rover_set_distribution(rover_ctx* c, const double* pts, int32_t P, const int
     for (int32_t v : idx)
         if (v < 0 || v >= P) return fail(c, ROVER_E_INVALID, "set_distribution: index %d outside [0,%d)", v, P);
     c->have_dist = false;
-    dfree(c->d_dist); dfree(c->d_obs_idx);
-    HIP_TRY(c, hipMalloc((void**)&c->d_dist, hp.size() * sizeof(double)));
-    HIP_TRY(c, hipMemcpy(c->d_dist, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMalloc((void**)&c->d_obs_idx, (idx.size() + 1) * sizeof(int32_t)));
-    HIP_TRY(c, hipMemset(c->d_obs_idx, 0, (idx.size() + 1) * sizeof(int32_t)));      // assemble_obs_kernel reads entry 0 from every lane
-    if (!idx.empty()) HIP_TRY(c, hipMemcpy(c->d_obs_idx, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    c->d_dist.reset(); c->d_obs_idx.reset();
+    HIP_TRY(c, c->d_dist.alloc(hp.size()));
+    HIP_TRY(c, hipMemcpy(c->d_dist.get(), hp.data(), c->d_dist.bytes(), hipMemcpyHostToDevice));
+    HIP_TRY(c, c->d_obs_idx.alloc(idx.size() + 1));
+    HIP_TRY(c, hipMemset(c->d_obs_idx.get(), 0, c->d_obs_idx.bytes()));      // assemble_obs_kernel reads entry 0 from every lane
+    if (!idx.empty()) HIP_TRY(c, hipMemcpy(c->d_obs_idx.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     c->P = P; c->Ns = Ns; c->Nd = Nd;
     c->have_dist = true;
     return alloc_workspace(c);
@@ -681,13 +643,11 @@ int rover_set_heightfield(rover_ctx* c, const float* hm, int32_t N0, int32_t N1,
     if (!c) return ROVER_E_INVALID;
     if (!hm || N0 <= 0 || N1 <= 0 || !(hscale > 0.0f)) return fail(c, ROVER_E_INVALID, "set_heightfield: bad arguments");
     USE_DEVICE(c);
-    float* d = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&d, (uint64_t)N0 * N1 * sizeof(float)));
-    hipError_t e = hipMemcpy(d, hm, (uint64_t)N0 * N1 * sizeof(float), hipMemcpyDefault);
-    if (e != hipSuccess) { dfree(d); return fail(c, ROVER_E_HIP, "set_heightfield: %s", hipGetErrorString(e)); }
-    float* old = const_cast<float*>(c->hf.hm);
-    dfree(old);
-    c->hf = HeightDev{d, N0, N1, hscale, vscale, sx, sy, 1.0f / hscale, c->cell_rcp};
+    DevBuf<float> d;
+    HIP_TRY(c, d.alloc((uint64_t)N0 * N1));
+    HIP_TRY(c, hipMemcpy(d.get(), hm, d.bytes(), hipMemcpyDefault));       // (the previous heightfield stays in place)
+    c->d_hm = std::move(d);
+    c->hf = HeightDev{c->d_hm.get(), N0, N1, hscale, vscale, sx, sy, 1.0f / hscale, c->cell_rcp};
     c->have_hf = true;
     return ROVER_OK;
 }
@@ -736,23 +696,18 @@ int rover_set_stones(rover_ctx* c, const float* info7, int32_t S) {
         float fid; memcpy(&fid, &sidx, sizeof fid);
         xyr[k] = float4{h[7 * (size_t)sidx], h[7 * (size_t)sidx + 1], h[7 * (size_t)sidx + 6], fid};
     }
-    uint32_t* d_start = nullptr;
-    float4* d_idx = nullptr;
-    float* d_info = nullptr;
+    DevBuf<uint32_t> d_start;
+    DevBuf<float4> d_xyr;
+    DevBuf<float> d_info;
     hipError_t e;
-    if ((e = hipMalloc((void**)&d_start, start.size() * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_idx, xyr.size() * sizeof(float4))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_info, ((uint64_t)S * 7 + 1) * sizeof(float))) != hipSuccess ||
-        (e = hipMemcpy(d_start, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(d_idx, xyr.data(), xyr.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess ||
-        (S && (e = hipMemcpy(d_info, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)) {
-        dfree(d_start); dfree(d_idx); dfree(d_info);
+    if ((e = d_start.alloc(start.size())) != hipSuccess || (e = d_xyr.alloc(xyr.size())) != hipSuccess ||
+        (e = d_info.alloc((uint64_t)S * 7 + 1)) != hipSuccess ||
+        (e = hipMemcpy(d_start.get(), start.data(), d_start.bytes(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(d_xyr.get(), xyr.data(), d_xyr.bytes(), hipMemcpyHostToDevice)) != hipSuccess ||
+        (S && (e = hipMemcpy(d_info.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess))
         return fail(c, ROVER_E_HIP, "set_stones: %s", hipGetErrorString(e));        // the previous stone tables stay in place
-    }
-    dfree(c->d_stones);
-    { uint32_t* p = const_cast<uint32_t*>(c->sgrid.cell_start); dfree(p); float4* q = const_cast<float4*>(c->sgrid.stone_xyr); dfree(q); }
-    c->d_stones = d_info;
-    c->sgrid = StoneGridDev{d_start, d_idx, x0, y0, 1.0f / cell, nx, ny};
+    c->d_stones = std::move(d_info); c->d_grid_start = std::move(d_start); c->d_grid_xyr = std::move(d_xyr);
+    c->sgrid = StoneGridDev{c->d_grid_start.get(), c->d_grid_xyr.get(), x0, y0, 1.0f / cell, nx, ny};
     c->S = S;
     c->have_stones = true;
     return ROVER_OK;
@@ -772,14 +727,14 @@ static int check_precision(rover_ctx* c) {
         return fail(c, ROVER_E_STATE, "ray_precision 2 (as shipped, fp16 maths) needs ray-cast variant 2 or 3 (K <= 256 on both maps)");
     // a variant asked for by name is the one that runs, or the call fails: the staged kernel needs the tables of the arithmetic in force
     // (K > 256 on a map is the documented exception: every variant then runs as the streaming kernel 1, and rover_get_info says so)
-    if (c->variant == 4 && c->map[0].K8 <= 256 && c->map[1].K8 <= 256 && !lane_tables_ok(c))
+    if (c->variant == 4 && c->maps[0].knn.K8 <= 256 && c->maps[1].knn.K8 <= 256 && !lane_tables_ok(c))
         return fail(c, ROVER_E_STATE, "raycast_variant 4 (staged) was requested but its tables for ray_precision %d are not there (option "
                                       "staged_tables, or they did not fit when the maps were set)", c->precision);
     return ROVER_OK;
 }
 
 static int check_ready(rover_ctx* c) {
-    if (!c->have_map[0] || !c->have_map[1]) return fail(c, ROVER_E_STATE, "terrain and rocks maps must be set (rover_set_knn_map)");
+    if (!have_maps(c)) return fail(c, ROVER_E_STATE, "terrain and rocks maps must be set (rover_set_knn_map)");
     if (!c->have_dist) return fail(c, ROVER_E_STATE, "ray distribution must be set (rover_set_distribution)");
     if (!c->ws_ok || !c->bins_ok) return fail(c, ROVER_E_STATE, "the step workspace is not allocated (an earlier rover_set_* call failed)");
     return check_precision(c);
@@ -787,17 +742,19 @@ static int check_ready(rover_ctx* c) {
 
 static CullArgs cull_args(const rover_ctx* c, uint32_t n_valid) {
     CullArgs a{};
-    a.rays = c->d_rays; a.sorted = c->d_sorted; a.n_sorted = n_valid;
+    a.rays = c->d_rays.get(); a.sorted = c->d_sorted.get(); a.n_sorted = n_valid;
     a.n_terrain = (uint32_t)c->cfg.num_envs * (uint32_t)c->P;
     const bool h = c->precision == 2;     // the as-shipped fp16 arithmetic: its own proof tables, the fp16 exact phase
-    a.idx0 = c->cull_idx[0]; a.idx1 = c->cull_idx[1];
-    a.ctab0 = h ? c->cull_ctab_h[0] : c->cull_ctab[0]; a.ctab1 = h ? c->cull_ctab_h[1] : c->cull_ctab[1];
-    a.rtab0 = c->cull_rtab[0]; a.rtab1 = c->cull_rtab[1];
+    const MapTables &m0 = c->maps[0], &m1 = c->maps[1];
+    const int k = proof_in_force(c);
+    a.idx0 = m0.cull_idx.get(); a.idx1 = m1.cull_idx.get();
+    a.ctab0 = m0.proof[k].ctab.get(); a.ctab1 = m1.proof[k].ctab.get();
+    a.rtab0 = m0.rtab.get(); a.rtab1 = m1.rtab.get();
     a.half = h ? 1 : 0;
     const CullProofH ph = cull_proof_h(c->cull_eta_h, c->cull_split_h);
     a.c_a_h = ph.c_a; a.tau2_h = ph.tau2;
-    a.far0 = h ? c->cull_far_h[0] : c->cull_far[0]; a.far1 = h ? c->cull_far_h[1] : c->cull_far[1];
-    a.near0 = a.far0 + 2ull * (uint64_t)c->cull_cells[0]; a.near1 = a.far1 + 2ull * (uint64_t)c->cull_cells[1];
+    a.far0 = m0.proof[k].far.get(); a.far1 = m1.proof[k].far.get();
+    a.near0 = a.far0 + 2ull * (uint64_t)m0.cells; a.near1 = a.far1 + 2ull * (uint64_t)m1.cells;
     a.k2_far = cull_far_k2(a.half, ph);
     // few rays per (map, cell) bin: most bins have no ray that tests the far pairs, and setting them up lazily halves a bin's set-up
     // (32 768 envs x 63 rays 69.7 -> 76 M env-steps/s, 4 096 envs 26.9 -> 30 M; with 146 rays per env a bin holds 14 rays, nearly every
@@ -808,21 +765,21 @@ static CullArgs cull_args(const rover_ctx* c, uint32_t n_valid) {
     // (round 4: what decides is the rays per bin, not the size of the ray set — 120 + 26 rays at 16 384 / 4 096 envs hold 5.8 / 2.1 rays per
     //  bin and gain 2.8 / 3.7 % from the on-demand kernel; the estimate is heightmap rays per terrain cell for rovers spread over the map.
     //  The native 1 634-point set is dense — 3.2 rays per bin already at 512 envs — and keeps the eager kernel: -1 ... -5 % otherwise.)
-    const bool few_per_bin = c->P <= 260 && (uint64_t)c->cfg.num_envs * (uint64_t)c->P < 8ull * (uint64_t)c->cull_cells[0];
-    const bool lazy_auto = (26 + c->P < 100 || few_per_bin) && 2 * c->cull_farok[0] >= c->cull_cells[0];
+    const bool few_per_bin = c->P <= 260 && (uint64_t)c->cfg.num_envs * (uint64_t)c->P < 8ull * (uint64_t)c->maps[0].cells;
+    const bool lazy_auto = (26 + c->P < 100 || few_per_bin) && 2 * c->maps[0].farok >= c->maps[0].cells;
     a.lazy_far = (c->cull_lazy < 0 ? lazy_auto : c->cull_lazy != 0) ? 1 : 0;
     // rays that clear their whole cell are left out of the scan where some do: a mesh whose cells mostly have a usable bound, and rock
     // rays (the ones that qualify) at least a tenth of the ray set (120 + 26 rays: 12 % of the rays, +3.8 %; the native 1 634 + 26: none)
-    a.skip_clear = (2 * c->cull_farok[0] >= c->cull_cells[0] && 26 + c->P <= 260) ? 1 : 0;
+    a.skip_clear = (2 * c->maps[0].farok >= c->maps[0].cells && 26 + c->P <= 260) ? 1 : 0;
     // The as-shipped fp16 arithmetic takes the same two choices since round 4 (its proof's group bound holds less often — 39 % of the rays
     // skip the far pairs, 13 % are not scanned at all, against 84 % / 25 % — but what holds is free: 65 536 envs 85.4 -> 88.3 M
     // env-steps/s, 16 384 envs 50.0 -> 53.3 M, alternating in one call); without the whole-cell skip its kernel stays the eager one.
     if (h && !a.skip_clear) a.lazy_far = 0;
-    a.kp0 = (uint32_t)c->map[0].K8; a.kp1 = (uint32_t)c->map[1].K8;
+    a.kp0 = (uint32_t)c->maps[0].knn.K8; a.kp1 = (uint32_t)c->maps[1].knn.K8;
     a.run = effective_run(c);
-    a.out = c->d_dist_out;
-    a.queue = c->d_cull_queue;
-    a.stats = c->d_cull_stats;
+    a.out = c->d_dist_out.get();
+    a.queue = c->d_cull_queue.get();
+    a.stats = c->d_cull_stats.get();
     a.queue_entries = c->cull_entries;
     return a;
 }
@@ -840,8 +797,8 @@ static bool lane_env_order(const rover_ctx* c, int variant) {
     //  4 096 envs 35.3 / 36.4 — the sort pays from one rover per ~64 cells)
     // (as shipped the staged kernel is the auto choice for small batches in env order and for dense ray sets behind the sort: effective_variant)
     if (c->precision == 2) return c->have_dist && valid_rays(c) < ROVER_AUTO_LANE_ENV_RAYS_F16;
-    return c->have_dist && 2ull * (uint64_t)c->cfg.num_envs * (uint64_t)c->P < 3ull * (uint64_t)c->cull_cells[0] &&
-           64ull * (uint64_t)c->cfg.num_envs < (uint64_t)c->cull_cells[0];
+    return c->have_dist && 2ull * (uint64_t)c->cfg.num_envs * (uint64_t)c->P < 3ull * (uint64_t)c->maps[0].cells &&
+           64ull * (uint64_t)c->cfg.num_envs < (uint64_t)c->maps[0].cells;
 }
 
 // variant 4 behind the sort: the rocks part of the sorted list through the staged kernel too?  Yes, since round 6, in either arithmetic: f32 — 4-byte
@@ -851,29 +808,29 @@ static bool lane_rocks_too(const rover_ctx* c) { return c->lane_rocks < 0 ? true
 // the ray-cast launch(es) of a step for the variant in force, on the ray records / sorted list in the workspace
 static int run_raycast(rover_ctx* c, int variant, uint32_t n_valid, hipStream_t s) {
     const uint32_t E = (uint32_t)c->cfg.num_envs;
-    if (variant >= 3 && c->d_cull_stats) {
+    if (variant >= 3 && c->d_cull_stats.get()) {
         // the per-wave counters of rover_get_cull_info: a launch writes the slots of its own waves; when the way the rays are cast changed
         // since the last launch (another kernel, order or run length: another number of waves) the slots are cleared first
         const uint64_t sig = (uint64_t)variant | ((uint64_t)lane_env_order(c, variant) << 8) | ((uint64_t)lane_rocks_too(c) << 9) | ((uint64_t)effective_run(c) << 16) |
                              ((uint64_t)c->precision << 32);
         if (sig != c->stats_sig) {
-            HIP_TRY(c, hipMemsetAsync(c->d_cull_stats, 0, (size_t)c->cull_stat_slots * sizeof(uint4), s));
+            HIP_TRY(c, hipMemsetAsync(c->d_cull_stats.get(), 0, c->d_cull_stats.bytes(), s));
             c->stats_sig = sig;
         }
     }
     if (variant == 4) {
         LaneArgs l{};
-        l.rays = c->d_rays; l.sorted = c->d_sorted; l.n_sorted = n_valid; l.n_terrain = E * (uint32_t)c->P;
+        l.rays = c->d_rays.get(); l.sorted = c->d_sorted.get(); l.n_sorted = n_valid; l.n_terrain = E * (uint32_t)c->P;
         const bool lh = c->precision == 2;
         for (int w = 0; w < 2; ++w) {
-            const LaneTables& t = lh ? c->lane_h[w] : c->lane[w];
-            l.lvl[w] = t.lvl; l.lrec[w] = t.lrec; l.lid[w] = t.lid; l.rtab[w] = c->cull_rtab[w]; l.pp[w] = c->lane_pp[w];
+            const LaneTables t = c->maps[w].proof[proof_in_force(c)].view();
+            l.lvl[w] = t.lvl; l.lrec[w] = t.lrec; l.lid[w] = t.lid; l.rtab[w] = c->maps[w].rtab.get(); l.pp[w] = c->maps[w].lane_pp;
         }
         {
             const CullProofH ph = cull_proof_h(c->cull_eta_h, c->cull_split_h);
             l.half = lh ? 1 : 0; l.c_a_h = ph.c_a; l.k2_far = cull_far_k2(l.half, ph);
         }
-        l.run = effective_run(c); l.out = c->d_dist_out; l.stats = c->d_cull_stats;
+        l.run = effective_run(c); l.out = c->d_dist_out.get(); l.stats = c->d_cull_stats.get();
         if (lane_env_order(c, variant)) {      // every slot (padding included), in env order, one launch
             l.sorted = nullptr; l.n_sorted = E * c->R8; l.n_terrain = l.n_sorted;
             // slots per wave: enough waves to fill 1 024 SIMDs (4 096 envs x 64 slots in runs of 64 are one wave per SIMD).  Whole step, M
@@ -897,27 +854,19 @@ static int run_raycast(rover_ctx* c, int variant, uint32_t n_valid, hipStream_t 
             l.n_sorted = l.n_terrain < n_valid ? l.n_terrain : n_valid;
             a.sorted += l.n_sorted; a.n_sorted -= l.n_sorted; a.n_terrain = 0;
             a.stats += lane_waves(l.n_sorted, l.run);
-            // the two launches touch disjoint rays, results and counters and could run side by side (fork / join by events); measured, that is
-            // no faster than one after the other (lane_side_stream)
-            const bool beside = c->lane_side_stream && c->side && a.n_sorted;
-            if (beside) {
-                HIP_TRY(c, hipEventRecord(c->ev_fork, s));
-                HIP_TRY(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-                HIP_TRY(c, launch_raycast_culled(a, c->side));
-                HIP_TRY(c, hipEventRecord(c->ev_join, c->side));
-            }
+            // (the two launches touch disjoint rays, results and counters; side by side on a second stream they measured slower: 125 against
+            //  127 M env-steps/s)
             HIP_TRY(c, launch_raycast_lane(l, s));
-            if (beside) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_join, 0));
-            else if (a.n_sorted) HIP_TRY(c, launch_raycast_culled(a, s));
+            if (a.n_sorted) HIP_TRY(c, launch_raycast_culled(a, s));
         }
     } else if (variant == 3)
         HIP_TRY(c, launch_raycast_culled(cull_args(c, n_valid), s));
     else if (variant == 2)
-        HIP_TRY(c, launch_raycast_binned(c->d_rays, c->d_sorted, n_valid, c->map[0].table, c->map[1].table,
-                                         (uint32_t)c->map[0].K8, (uint32_t)c->map[1].K8, effective_run(c), c->precision == 2, c->early_out, c->d_dist_out, s));
+        HIP_TRY(c, launch_raycast_binned(c->d_rays.get(), c->d_sorted.get(), n_valid, c->maps[0].knn.table, c->maps[1].knn.table,
+                                         (uint32_t)c->maps[0].knn.K8, (uint32_t)c->maps[1].knn.K8, effective_run(c), c->precision == 2, c->early_out, c->d_dist_out.get(), s));
     else
-        HIP_TRY(c, launch_raycast(c->d_rays, E * c->R8, c->map[0].table, c->map[1].table, (uint32_t)c->map[0].K8,
-                                  (uint32_t)c->map[1].K8, c->d_dist_out, s));
+        HIP_TRY(c, launch_raycast(c->d_rays.get(), E * c->R8, c->maps[0].knn.table, c->maps[1].knn.table, (uint32_t)c->maps[0].knn.K8,
+                                  (uint32_t)c->maps[1].knn.K8, c->d_dist_out.get(), s));
     return ROVER_OK;
 }
 
@@ -930,16 +879,16 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
     PrepArgs p{};
     p.E = E; p.P = (uint32_t)c->P; p.R8 = c->R8;
     p.pos = pos; p.quat = quat; p.joints = joints; p.target = target; p.euler_in = euler_in;
-    p.dist = c->d_dist; p.terrain = c->map[0]; p.rocks = c->map[1];
-    p.rays = c->d_rays; p.euler = euler_in ? nullptr : c->d_euler; p.heading = euler_in ? nullptr : c->d_heading;
+    p.dist = c->d_dist.get(); p.terrain = c->maps[0].knn; p.rocks = c->maps[1].knn;
+    p.rays = c->d_rays.get(); p.euler = euler_in ? nullptr : c->d_euler.get(); p.heading = euler_in ? nullptr : c->d_heading.get();
     const int variant = effective_variant(c);
     // (the queue is sized by every call that changes its size — never here: no hipMalloc inside a step / a stream capture)
-    if (variant >= 3 && (!c->d_cull_queue || !c->d_cull_stats || c->cull_run != effective_run(c)))
+    if (variant >= 3 && (!c->d_cull_queue.get() || !c->d_cull_stats.get() || c->cull_run != effective_run(c)))
         return fail(c, ROVER_E_STATE, "the culled ray cast's candidate queue is not allocated for the options in force");
     const uint32_t n_valid = E * (26u + (uint32_t)c->P);
-    p.rocks_bin_offset = (uint32_t)((uint64_t)c->map[0].X * c->map[0].Y);
+    p.rocks_bin_offset = (uint32_t)((uint64_t)c->maps[0].knn.X * c->maps[0].knn.Y);
     const bool sorts = variant >= 2 && !lane_env_order(c, variant);
-    if (sorts) p.bin_out = c->d_bins;
+    if (sorts) p.bin_out = c->d_bins.get();
     p.precision = c->precision;
     p.cell_rcp = c->cell_rcp;
     // the sort's first pass (keys per coarse bucket and tile) inside prep_rays_kernel where a 64-env block's keys lie in one tile: the
@@ -947,16 +896,16 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
     // (caller-supplied rays, rover_cast_rays: import_rays_kernel writes the records and keys, the sort counts its keys itself)
     const bool hist_fused = !import_src && sorts && bin_hist_fused(E * c->R8, c->R8, c->n_bins, c->low_bits, &p.hist_blocks_per_tile);
     if (hist_fused) {
-        if (c->bkt_table_dirty) HIP_TRY(c, hipMemsetAsync(c->d_bkt_table, 0, c->bkt_table_bytes, s));
+        if (c->bkt_table_dirty) HIP_TRY(c, hipMemsetAsync(c->d_bkt_table.get(), 0, c->d_bkt_table.bytes(), s));
         c->bkt_table_dirty = true;
-        p.hist = c->d_bkt_table; p.hist_low_bits = c->low_bits; p.hist_buckets = bucket_count(c);
+        p.hist = c->d_bkt_table.get(); p.hist_low_bits = c->low_bits; p.hist_buckets = bucket_count(c);
     }
     if (import_src) {
         // caller-supplied directions: the culled / staged ray cast's proofs need them of unit length (what -normalize() gives)
-        uint32_t* const not_unit = variant >= 3 ? c->d_block_cnt + (size_t)c->cfg.num_envs / 256 + 1 : nullptr;      // (the spare word behind the block counts)
+        uint32_t* const not_unit = variant >= 3 ? c->d_block_cnt.get() + (size_t)c->cfg.num_envs / 256 + 1 : nullptr;      // (the spare word behind the block counts)
         if (not_unit) HIP_TRY(c, hipMemsetAsync(not_unit, 0, sizeof(uint32_t), s));
-        HIP_TRY(c, launch_import_rays(import_src, import_dir, E, c->R8, (uint32_t)c->P, c->map[0], c->map[1], p.rocks_bin_offset, c->precision,
-                                      c->cell_rcp, c->d_rays, sorts ? c->d_bins : nullptr, s, not_unit));
+        HIP_TRY(c, launch_import_rays(import_src, import_dir, E, c->R8, (uint32_t)c->P, c->maps[0].knn, c->maps[1].knn, p.rocks_bin_offset, c->precision,
+                                      c->cell_rcp, c->d_rays.get(), sorts ? c->d_bins.get() : nullptr, s, not_unit));
         if (not_unit) {
             uint32_t bad = 0;
             HIP_TRY(c, hipMemcpyAsync(&bad, not_unit, sizeof bad, hipMemcpyDeviceToHost, s));
@@ -971,8 +920,8 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
         HIP_TRY(c, launch_prep(p, s));
     }
     if (sorts)
-        HIP_TRY(c, launch_bin_rays(c->d_bins, E * c->R8, n_valid, c->n_bins, c->low_bits, c->d_bkt_table, c->d_pairs,
-                                   c->d_block_sums, c->d_sorted, hist_fused, s));
+        HIP_TRY(c, launch_bin_rays(c->d_bins.get(), E * c->R8, n_valid, c->n_bins, c->low_bits, c->d_bkt_table.get(), c->d_pairs.get(),
+                                   c->d_block_sums.get(), c->d_sorted.get(), hist_fused, s));
     // fused histogram: bucket_sort_kernel has cleared the table again; otherwise the table (if the sort ran) holds this step's offsets
     if (sorts) c->bkt_table_dirty = !hist_fused;        // (variant 1 does not touch the table)
     const bool timed = c->profiling && (c->prof_seen++ % c->prof_every) == 0;
@@ -1003,15 +952,15 @@ static int do_observations(rover_ctx* c, const rover_step_in* in, const rover_st
     c->obs_valid = true;
     ObsArgs o{};
     o.E = E; o.W = W; o.R8 = c->R8; o.obs_stride = stride;
-    o.pos = in->pos; o.target = in->target; o.heading = c->d_heading; o.lin_hist = in->lin_hist; o.ang_hist = in->ang_hist;
-    o.dist = c->d_dist_out; o.obs_idx = c->d_obs_idx; o.obs = out->obs; o.fp16_div = c->precision == 2;
+    o.pos = in->pos; o.target = in->target; o.heading = c->d_heading.get(); o.lin_hist = in->lin_hist; o.ang_hist = in->ang_hist;
+    o.dist = c->d_dist_out.get(); o.obs_idx = c->d_obs_idx.get(); o.obs = out->obs; o.fp16_div = c->precision == 2;
     if (c->defer_obs) { c->pending_obs = o; c->obs_pending = true; }
     else HIP_TRY(c, launch_assemble_obs(o, s));
     if (out->ray_dist || out->wheel_dist || out->body_dist || out->ray_src || out->hit_pt)
-        HIP_TRY(c, launch_export_dist(c->d_dist_out, c->d_rays, E, c->R8, (uint32_t)c->P, c->precision, out->ray_dist, out->wheel_dist,
+        HIP_TRY(c, launch_export_dist(c->d_dist_out.get(), c->d_rays.get(), E, c->R8, (uint32_t)c->P, c->precision, out->ray_dist, out->wheel_dist,
                                       out->body_dist, out->ray_src, out->hit_pt, s));
-    if (out->euler) HIP_TRY(c, hipMemcpyAsync(out->euler, c->d_euler, (uint64_t)E * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (out->heading_diff) HIP_TRY(c, hipMemcpyAsync(out->heading_diff, c->d_heading, (uint64_t)E * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (out->euler) HIP_TRY(c, hipMemcpyAsync(out->euler, c->d_euler.get(), (uint64_t)E * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (out->heading_diff) HIP_TRY(c, hipMemcpyAsync(out->heading_diff, c->d_heading.get(), (uint64_t)E * sizeof(float), hipMemcpyDeviceToDevice, s));
     return ROVER_OK;
 }
 
@@ -1038,14 +987,14 @@ static int do_metrics(rover_ctx* c, const rover_step_in* in, const rover_step_ou
     m.wheel_thr = c->precision == 2 ? 0.7998046875f : 0.8f;                // fp16(0.8), fp16(0.45): Python scalars compared
     m.body_thr = c->precision == 2 ? 0.449951171875f : 0.45f;              // against fp16 tensors (rover.py:667-668)
     m.pos = in->pos; m.target = in->target; m.joints = in->joints; m.lin_hist = in->lin_hist; m.ang_hist = in->ang_hist;
-    m.euler_pre = in->euler_pre; m.heading = c->d_heading; m.dist = c->d_dist_out;
+    m.euler_pre = in->euler_pre; m.heading = c->d_heading.get(); m.dist = c->d_dist_out.get();
     m.progress = in->progress; m.rock_collision = out->rock_collision; m.rew = out->rew; m.reset = out->reset;
     m.ex_pos_reward = out->ex_pos_reward; m.ex_collision = out->ex_collision_penalty; m.ex_upright = out->ex_uprightness_penalty;
     m.ex_heading = out->ex_heading_contraint_penalty; m.ex_motion = out->ex_motion_contraint_penalty;
-    m.block_cnt = count_done ? c->d_block_cnt : nullptr;
+    m.block_cnt = count_done ? c->d_block_cnt.get() : nullptr;
     m.stone_collision = coll ? out->stone_collision : nullptr; m.stone_margin = out->stone_margin;
     m.done_u8 = done ? out->done_u8 : nullptr;
-    m.sgrid = c->sgrid; m.info7 = c->d_stones;
+    m.sgrid = c->sgrid; m.info7 = c->d_stones.get();
     m.ex_goal_angle = out->ex_goal_angle_penalty; m.ex_lin = out->ex_torque_penalty_driving; m.ex_ang = out->ex_torque_penalty_steering;
     if (c->obs_pending) {
         c->obs_pending = false;
@@ -1094,7 +1043,7 @@ int rover_get_depths(rover_ctx* c, const float* positions, const float* rotation
     hipStream_t s = (hipStream_t)stream;
     if (int r = cast_rays(c, positions, nullptr, nullptr, nullptr, rotations_euler, s)) return r;
     if (distances || points || sources)
-        HIP_TRY(c, launch_export_dist(c->d_dist_out, c->d_rays, (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, c->precision, distances,
+        HIP_TRY(c, launch_export_dist(c->d_dist_out.get(), c->d_rays.get(), (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, c->precision, distances,
                                       nullptr, nullptr, sources, points, s));
     return ROVER_OK;
 }
@@ -1108,7 +1057,7 @@ int rover_get_collisions(rover_ctx* c, const float* positions, const float* rota
     hipStream_t s = (hipStream_t)stream;
     if (int r = cast_rays(c, positions, nullptr, joints, nullptr, rotations_euler, s)) return r;
     if (wheel_dist || body_dist)
-        HIP_TRY(c, launch_export_dist(c->d_dist_out, c->d_rays, (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, c->precision, nullptr,
+        HIP_TRY(c, launch_export_dist(c->d_dist_out.get(), c->d_rays.get(), (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, c->precision, nullptr,
                                       wheel_dist, body_dist, nullptr, nullptr, s));
     return ROVER_OK;
 }
@@ -1118,7 +1067,7 @@ int rover_export_rays(rover_ctx* c, float* src, float* dir, int32_t* cell, float
     if (int r = check_ready(c)) return r;
     if (!c->rays_valid) return fail(c, ROVER_E_STATE, "export_rays: no ray records yet (run a step first)");
     USE_DEVICE(c);
-    HIP_TRY(c, launch_export_rays(c->d_rays, c->d_dist_out, (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, src, dir, cell, dist,
+    HIP_TRY(c, launch_export_rays(c->d_rays.get(), c->d_dist_out.get(), (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, src, dir, cell, dist,
                                   (hipStream_t)stream));
     return ROVER_OK;
 }
@@ -1130,7 +1079,7 @@ int rover_cast_rays(rover_ctx* c, const float* src, const float* dir, float* dis
     USE_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     if (int r = cast_rays(c, nullptr, nullptr, nullptr, nullptr, nullptr, s, src, dir)) return r;
-    HIP_TRY(c, launch_export_rays(c->d_rays, c->d_dist_out, (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, nullptr, nullptr, nullptr, dist, s));
+    HIP_TRY(c, launch_export_rays(c->d_rays.get(), c->d_dist_out.get(), (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, nullptr, nullptr, nullptr, dist, s));
     return ROVER_OK;
 }
 
@@ -1138,7 +1087,7 @@ int rover_compact_resets(rover_ctx* c, const int64_t* reset, int64_t* ids, int32
     if (!c) return ROVER_E_INVALID;
     if (!reset || !ids || !n_reset) return fail(c, ROVER_E_INVALID, "compact_resets: null pointer");
     USE_DEVICE(c);
-    HIP_TRY(c, launch_compact(reset, (uint32_t)c->cfg.num_envs, (int64_t)c->cfg.env_offset, c->d_block_cnt, false, ids, n_reset,
+    HIP_TRY(c, launch_compact(reset, (uint32_t)c->cfg.num_envs, (int64_t)c->cfg.env_offset, c->d_block_cnt.get(), false, ids, n_reset,
                               (hipStream_t)stream));
     return ROVER_OK;
 }
@@ -1162,7 +1111,7 @@ int rover_step(rover_ctx* c, const rover_step_in* in, const rover_step_out* out,
         return r;
     }
     if (compact)
-        HIP_TRY(c, launch_compact(out->reset, (uint32_t)c->cfg.num_envs, (int64_t)c->cfg.env_offset, c->d_block_cnt, true,
+        HIP_TRY(c, launch_compact(out->reset, (uint32_t)c->cfg.num_envs, (int64_t)c->cfg.env_offset, c->d_block_cnt.get(), true,
                                   out->reset_ids, out->n_reset, s));
     return ROVER_OK;
 }
@@ -1183,7 +1132,7 @@ int rover_clearance(rover_ctx* c, const float* xy, int32_t n, float* out, void* 
     if (n < 0 || (n > 0 && (!xy || !out))) return fail(c, ROVER_E_INVALID, "clearance: bad arguments");
     if (n == 0) return ROVER_OK;
     USE_DEVICE(c);
-    HIP_TRY(c, launch_clearance(c->d_stones, (uint32_t)c->S, xy, (uint32_t)n, out, (hipStream_t)stream));
+    HIP_TRY(c, launch_clearance(c->d_stones.get(), (uint32_t)c->S, xy, (uint32_t)n, out, (hipStream_t)stream));
     return ROVER_OK;
 }
 
@@ -1193,7 +1142,7 @@ int rover_shift_spawns(rover_ctx* c, float* pos3, int32_t n, int32_t max_iter, v
     if (n < 0 || (n > 0 && !pos3) || max_iter < 0) return fail(c, ROVER_E_INVALID, "shift_spawns: bad arguments");
     if (n == 0) return ROVER_OK;
     USE_DEVICE(c);
-    HIP_TRY(c, launch_shift_spawns(c->sgrid, c->d_stones, pos3, (uint32_t)n, max_iter, (hipStream_t)stream));
+    HIP_TRY(c, launch_shift_spawns(c->sgrid, c->d_stones.get(), pos3, (uint32_t)n, max_iter, (hipStream_t)stream));
     return ROVER_OK;
 }
 
@@ -1215,8 +1164,8 @@ int rover_generate_goals(rover_ctx* c, const int64_t* env_ids, int32_t n, const 
         return fail(c, ROVER_E_INVALID, "generate_goals: bad arguments (n=%d, max_draws=%d)", n, max_draws);
     if (n == 0) return ROVER_OK;
     USE_DEVICE(c);
-    GoalArgs g{c->d_stones, (uint32_t)c->S, c->hf, c->sgrid, env_ids, 0, (uint32_t)n, nullptr, initial_pos3, target3, radius, draws,
-               max_draws, seed, nullptr, (int32_t*)c->d_goal_work, n_draws_used};
+    GoalArgs g{c->d_stones.get(), (uint32_t)c->S, c->hf, c->sgrid, env_ids, 0, (uint32_t)n, nullptr, initial_pos3, target3, radius, draws,
+               max_draws, seed, nullptr, (int32_t*)c->d_goal_work.get(), n_draws_used};
     HIP_TRY(c, launch_generate_goals(g, (uint32_t)n, (hipStream_t)stream));
     return ROVER_OK;
 }
@@ -1246,9 +1195,9 @@ int rover_reset_envs(rover_ctx* c, const rover_reset_io* io, void* stream) {
     const uint32_t n_max = io->n_reset_dev ? (uint32_t)c->cfg.num_envs : (uint32_t)io->n_reset_host;
     HIP_TRY(c, launch_reset_envs(a, n_max, s));
     if (io->target3) {
-        GoalArgs g{c->d_stones, (uint32_t)c->S, c->hf, c->sgrid, io->reset_ids, (int64_t)c->cfg.env_offset, (uint32_t)io->n_reset_host,
+        GoalArgs g{c->d_stones.get(), (uint32_t)c->S, c->hf, c->sgrid, io->reset_ids, (int64_t)c->cfg.env_offset, (uint32_t)io->n_reset_host,
                    io->n_reset_dev, io->initial_pos3, io->target3, io->radius > 0.f ? io->radius : 8.0f, io->draws,
-                   io->max_draws > 0 ? io->max_draws : 256, io->seed, io->seed_dev, (int32_t*)c->d_goal_work, io->n_draws_used};
+                   io->max_draws > 0 ? io->max_draws : 256, io->seed, io->seed_dev, (int32_t*)c->d_goal_work.get(), io->n_draws_used};
         HIP_TRY(c, launch_generate_goals(g, n_max, s));
     }
     return ROVER_OK;
@@ -1279,13 +1228,12 @@ int rover_get_info(const rover_ctx* c, rover_info* info) {
     memset(info, 0, sizeof *info);
     info->P = c->P; info->Ns = c->Ns; info->Nd = c->Nd; info->rays_per_env_padded = (int32_t)c->R8;
     for (int w = 0; w < 2; ++w) {
-        info->K[w] = c->map[w].K; info->K8[w] = c->map[w].K8; info->X[w] = c->map[w].X; info->Y[w] = c->map[w].Y;
-        info->table_bytes[w] = c->table_bytes[w];
+        info->K[w] = c->maps[w].knn.K; info->K8[w] = c->maps[w].knn.K8; info->X[w] = c->maps[w].knn.X; info->Y[w] = c->maps[w].knn.Y;
+        info->table_bytes[w] = c->maps[w].bytes();
     }
     // the per-step workspace: ray records, distances, sort buffers, env records, and the culled ray cast's queue + counters
-    info->workspace_bytes = c->workspace_bytes + (c->d_cull_queue ? c->cull_entries * sizeof(uint2) : 0) +
-                            (c->d_cull_stats ? (uint64_t)c->cull_stat_slots * sizeof(uint4) : 0);
-    info->raycast_variant = (c->have_map[0] && c->have_map[1]) ? effective_variant(c) : 0;
+    info->workspace_bytes = c->workspace_bytes + c->d_cull_queue.bytes() + c->d_cull_stats.bytes();
+    info->raycast_variant = have_maps(c) ? effective_variant(c) : 0;
     info->cell_index_mode = c->cell_rcp; info->ray_precision = c->precision;
     info->raycast_sorted = info->raycast_variant >= 2 && !lane_env_order(c, info->raycast_variant);
     info->raycast_rocks_staged = info->raycast_variant == 4 && (!info->raycast_sorted || lane_rocks_too(c)) ? 1 : 0;
@@ -1296,19 +1244,20 @@ int rover_get_cull_info(rover_ctx* c, rover_cull_info* out) {
     if (!c || !out) return ROVER_E_INVALID;
     memset(out, 0, sizeof *out);
     for (int w = 0; w < 2; ++w) {             // (of the proof tables the precision in force uses)
-        out->triangles[w] = c->cull_tris[w];
-        out->always_candidate_triangles[w] = c->precision == 2 ? c->cull_always_h[w] : c->cull_always[w];
-        out->cells_without_cone[w] = c->precision == 2 ? c->cull_nocone_h[w] : c->cull_nocone[w];
+        const MapTables& m = c->maps[w];
+        out->triangles[w] = m.tris;
+        out->always_candidate_triangles[w] = m.proof[proof_in_force(c)].always;
+        out->cells_without_cone[w] = m.proof[proof_in_force(c)].nocone;
+        out->cells_with_far_bound[w] = m.farok;
     }
-    for (int w = 0; w < 2; ++w) out->cells_with_far_bound[w] = c->cull_farok[w];
-    out->far_records_on_demand = (c->have_dist && c->have_map[0]) ? (uint64_t)cull_args(c, 0).lazy_far : 0;
-    out->queue_bytes = c->d_cull_queue ? c->cull_entries * sizeof(uint2) : 0;
-    out->launches_per_step = c->d_cull_queue ? c->cull_launches : 0;
-    if (!c->d_cull_stats || c->last_variant < 3) return ROVER_OK;
+    out->far_records_on_demand = (c->have_dist && c->maps[0].table.get()) ? (uint64_t)cull_args(c, 0).lazy_far : 0;
+    out->queue_bytes = c->d_cull_queue.bytes();
+    out->launches_per_step = c->d_cull_queue.get() ? c->cull_launches : 0;
+    if (!c->d_cull_stats.get() || c->last_variant < 3) return ROVER_OK;
     USE_DEVICE(c);
     HIP_TRY(c, hipDeviceSynchronize());
     std::vector<uint4> h(c->cull_stat_slots);
-    HIP_TRY(c, hipMemcpy(h.data(), c->d_cull_stats, h.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(h.data(), c->d_cull_stats.get(), h.size() * sizeof(uint4), hipMemcpyDeviceToHost));
     for (const uint4& v : h) {
         out->candidate_pairs += v.x; out->rays += v.y & 0xffu; out->rays_far_skipped += v.y >> 8; out->rays_both_tests += v.z & 0xffu; out->rays_not_scanned += v.z >> 8; out->bins += v.w & 0xffu;
         out->lane_items += (v.w >> 8) & 0x3ffffu; out->lane_flushes += v.w >> 26;      // (zero in the words the culled kernel's waves write)
@@ -1372,26 +1321,25 @@ static int build_knn_map_impl(rover_ctx* c, const float* vertices, int32_t V, co
     if (T < K) return fail(c, ROVER_E_INVALID, "build_knn_map: the mesh has %d triangles, fewer than K=%d", T, K);
     if (K > 4096) return fail(c, ROVER_E_INVALID, "build_knn_map: K=%d exceeds the builder's limit of 4096", K);
     USE_DEVICE(c);
-    float *d_v = nullptr, *d_cx = nullptr, *d_cy = nullptr, *d_cell = nullptr;
-    int32_t *d_t = nullptr, *d_over = nullptr;
-    uint32_t *d_cur = nullptr, *d_items = nullptr, *d_bs = nullptr, *d_start = nullptr;
-    auto cleanup = [&]() { dfree(d_v); dfree(d_cx); dfree(d_cy); dfree(d_t); dfree(d_over); dfree(d_cur); dfree(d_items); dfree(d_bs); dfree(d_cell); dfree(d_start); };
+    DevBuf<float> d_v, d_cx, d_cy, d_cell;
+    DevBuf<int32_t> d_t, d_over;
+    DevBuf<uint32_t> d_cur, d_items, d_bs, d_start;
 #define KNN_TRY(expr)                                                                                     \
     do {                                                                                                  \
         hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess) { cleanup(); return fail(c, ROVER_E_HIP, "build_knn_map: %s: %s", #expr, hipGetErrorString(e__)); } \
+        if (e__ != hipSuccess) return fail(c, ROVER_E_HIP, "build_knn_map: %s: %s", #expr, hipGetErrorString(e__)); \
     } while (0)
-    KNN_TRY(hipMalloc((void**)&d_v, (size_t)V * 3 * sizeof(float)));
-    KNN_TRY(hipMalloc((void**)&d_t, (size_t)T * 3 * sizeof(int32_t)));
-    KNN_TRY(hipMalloc((void**)&d_cx, (size_t)T * sizeof(float)));
-    KNN_TRY(hipMalloc((void**)&d_cy, (size_t)T * sizeof(float)));
-    KNN_TRY(hipMalloc((void**)&d_items, (size_t)T * sizeof(uint32_t)));
-    KNN_TRY(hipMalloc((void**)&d_over, sizeof(int32_t)));
-    KNN_TRY(hipMalloc((void**)&d_bs, 8192 * sizeof(uint32_t)));
-    KNN_TRY(hipMemcpy(d_v, vertices, (size_t)V * 3 * sizeof(float), hipMemcpyDefault));
-    KNN_TRY(hipMemcpy(d_t, triangles, (size_t)T * 3 * sizeof(int32_t), hipMemcpyDefault));
-    KNN_TRY(hipMemset(d_over, 0, sizeof(int32_t)));
-    KNN_TRY(launch_knn_centroids(d_v, d_t, (uint32_t)T, (uint32_t)V, ref, d_cx, d_cy, nullptr));
+    KNN_TRY(d_v.alloc((size_t)V * 3));
+    KNN_TRY(d_t.alloc((size_t)T * 3));
+    KNN_TRY(d_cx.alloc(T));
+    KNN_TRY(d_cy.alloc(T));
+    KNN_TRY(d_items.alloc(T));
+    KNN_TRY(d_over.alloc(1));
+    KNN_TRY(d_bs.alloc(8192));
+    KNN_TRY(hipMemcpy(d_v.get(), vertices, d_v.bytes(), hipMemcpyDefault));
+    KNN_TRY(hipMemcpy(d_t.get(), triangles, d_t.bytes(), hipMemcpyDefault));
+    KNN_TRY(hipMemset(d_over.get(), 0, sizeof(int32_t)));
+    KNN_TRY(launch_knn_centroids(d_v.get(), d_t.get(), (uint32_t)T, (uint32_t)V, ref, d_cx.get(), d_cy.get(), nullptr));
     if (ref) {
         // cell coordinates as fp16 values: the caller's tables (what the reference's torch.arange(0, X res, res, dtype=float16)
         // gave on the host that built the map), or fp16(float(i) * res) — ATen's CUDA arange kernel, the reference's own device
@@ -1401,13 +1349,13 @@ static int build_knn_map_impl(rover_ctx* c, const float* vertices, int32_t V, co
         if (cell_y_f16) KNN_TRY(hipMemcpy(hy.data(), cell_y_f16, hy.size() * sizeof(uint16_t), hipMemcpyDefault));
         for (int32_t i = 0; i < X; ++i) cell[(size_t)i] = half_bits_to_float(cell_x_f16 ? hx[(size_t)i] : float_to_half_bits((float)i * res));
         for (int32_t j = 0; j < Y; ++j) cell[(size_t)X + j] = half_bits_to_float(cell_y_f16 ? hy[(size_t)j] : float_to_half_bits((float)j * res));
-        KNN_TRY(hipMalloc((void**)&d_cell, cell.size() * sizeof(float)));
-        KNN_TRY(hipMemcpy(d_cell, cell.data(), cell.size() * sizeof(float), hipMemcpyHostToDevice));
+        KNN_TRY(d_cell.alloc(cell.size()));
+        KNN_TRY(hipMemcpy(d_cell.get(), cell.data(), d_cell.bytes(), hipMemcpyHostToDevice));
     }
     // bucket grid over the centroids' bounding box; bucket edge ~ the radius that holds K/4 centroids at mean density
     std::vector<float> hx((size_t)T), hy((size_t)T);
-    KNN_TRY(hipMemcpy(hx.data(), d_cx, (size_t)T * sizeof(float), hipMemcpyDeviceToHost));
-    KNN_TRY(hipMemcpy(hy.data(), d_cy, (size_t)T * sizeof(float), hipMemcpyDeviceToHost));
+    KNN_TRY(hipMemcpy(hx.data(), d_cx.get(), d_cx.bytes(), hipMemcpyDeviceToHost));
+    KNN_TRY(hipMemcpy(hy.data(), d_cy.get(), d_cy.bytes(), hipMemcpyDeviceToHost));
     float x0 = hx[0], x1 = hx[0], y0 = hy[0], y1 = hy[0];
     for (int32_t t = 0; t < T; ++t) {
         if (hx[t] == hx[t]) { x0 = hx[t] < x0 ? hx[t] : x0; x1 = hx[t] > x1 ? hx[t] : x1; }
@@ -1427,23 +1375,22 @@ static int build_knn_map_impl(rover_ctx* c, const float* vertices, int32_t V, co
         while ((uint64_t)nbx * nby > (1u << 22)) { gsz *= 2.0; nbx = (uint32_t)(((double)x1 - x0) / gsz) + 1; nby = (uint32_t)(((double)y1 - y0) / gsz) + 1; attempt = 99; }
         const float g = (float)gsz, inv_g = 1.0f / g;
         const uint32_t nb = nbx * nby;
-        dfree(d_cur); dfree(d_start);
-        KNN_TRY(hipMalloc((void**)&d_cur, ((size_t)nb + 1) * sizeof(uint32_t)));
-        KNN_TRY(hipMemset(d_cur, 0, ((size_t)nb + 1) * sizeof(uint32_t)));
-        KNN_TRY(hipMemset(d_over, 0, sizeof(int32_t)));
-        KNN_TRY(launch_knn_bucket(d_cx, d_cy, (uint32_t)T, x0, y0, inv_g, nbx, nby, d_cur, d_items, 1, nullptr));
-        KNN_TRY(launch_scan_exclusive(d_cur, nb + 1, d_bs, nullptr));
-        e2 = hipMalloc((void**)&d_start, ((size_t)nb + 1) * sizeof(uint32_t));
-        if (e2 == hipSuccess) e2 = hipMemcpy(d_start, d_cur, ((size_t)nb + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice);
-        if (e2 == hipSuccess) e2 = launch_knn_bucket(d_cx, d_cy, (uint32_t)T, x0, y0, inv_g, nbx, nby, d_cur, d_items, 0, nullptr);
-        if (e2 == hipSuccess) e2 = launch_knn_select(d_cx, d_cy, d_start, d_items, x0, y0, g, nbx, nby, (uint32_t)X, (uint32_t)Y, res,
-                                                     (uint32_t)K, d_cell, d_cell ? d_cell + X : nullptr, map_idx_out, d_over, nullptr);
+        d_start.reset();
+        KNN_TRY(d_cur.alloc((size_t)nb + 1));
+        KNN_TRY(hipMemset(d_cur.get(), 0, d_cur.bytes()));
+        KNN_TRY(hipMemset(d_over.get(), 0, sizeof(int32_t)));
+        KNN_TRY(launch_knn_bucket(d_cx.get(), d_cy.get(), (uint32_t)T, x0, y0, inv_g, nbx, nby, d_cur.get(), d_items.get(), 1, nullptr));
+        KNN_TRY(launch_scan_exclusive(d_cur.get(), nb + 1, d_bs.get(), nullptr));
+        e2 = d_start.alloc((size_t)nb + 1);
+        if (e2 == hipSuccess) e2 = hipMemcpy(d_start.get(), d_cur.get(), d_cur.bytes(), hipMemcpyDeviceToDevice);
+        if (e2 == hipSuccess) e2 = launch_knn_bucket(d_cx.get(), d_cy.get(), (uint32_t)T, x0, y0, inv_g, nbx, nby, d_cur.get(), d_items.get(), 0, nullptr);
+        if (e2 == hipSuccess) e2 = launch_knn_select(d_cx.get(), d_cy.get(), d_start.get(), d_items.get(), x0, y0, g, nbx, nby, (uint32_t)X, (uint32_t)Y, res,
+                                                     (uint32_t)K, d_cell.get(), d_cell.get() ? d_cell.get() + X : nullptr, map_idx_out, d_over.get(), nullptr);
         if (e2 == hipSuccess) e2 = hipDeviceSynchronize();
         over = 0;
-        if (e2 == hipSuccess) e2 = hipMemcpy(&over, d_over, sizeof over, hipMemcpyDeviceToHost);
+        if (e2 == hipSuccess) e2 = hipMemcpy(&over, d_over.get(), sizeof over, hipMemcpyDeviceToHost);
         if (e2 != hipSuccess || !over) break;
     }
-    cleanup();
 #undef KNN_TRY
     if (e2 != hipSuccess) return fail(c, ROVER_E_HIP, "build_knn_map: %s", hipGetErrorString(e2));
     if (over) return fail(c, ROVER_E_INVALID, "build_knn_map: a search ring held more than 8192 candidate triangles (mesh too dense for K=%d)", K);
@@ -1482,12 +1429,9 @@ static int chain_args_of(rover_ctx* c, const float* x, int64_t x_stride, int32_t
 
 // the split-k scratch buffer, grown when a larger batch comes (not inside a stream capture — size the first call before capturing)
 static int mlp_scratch_reserve(rover_ctx* c, size_t need, hipStream_t s) {
-    if (need <= c->mlp_scratch_floats) return ROVER_OK;
+    if (need * sizeof(float) <= c->d_mlp_scratch.bytes()) return ROVER_OK;
     HIP_TRY(c, hipStreamSynchronize(s));          // kernels still reading the old buffer
-    dfree(c->d_mlp_scratch);
-    c->mlp_scratch_floats = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_mlp_scratch, need * sizeof(float)));
-    c->mlp_scratch_floats = need;
+    HIP_TRY(c, c->d_mlp_scratch.alloc(need));
     return ROVER_OK;
 }
 
@@ -1495,7 +1439,7 @@ static int chain_run(rover_ctx* c, const ChainArgs& a, hipStream_t s) {
     if (a.M == 0) return ROVER_OK;
     if (chain_wants_splitk(a)) {          // small batches: first layer split along k through a scratch buffer
         if (int r = mlp_scratch_reserve(c, chain_splitk_scratch_floats(a.M, a.K0, a.n[0]), s)) return r;
-        HIP_TRY(c, launch_chain_splitk(a, c->d_mlp_scratch, s));
+        HIP_TRY(c, launch_chain_splitk(a, c->d_mlp_scratch.get(), s));
         return ROVER_OK;
     }
     hipError_t e = launch_chain(a, s);
@@ -1528,7 +1472,7 @@ int rover_mlp_chain_pair_forward(rover_ctx* c, int32_t M, const rover_chain_desc
     if (chain_pair_fits(a, b)) {
         const size_t fa = chain_splitk_scratch_floats(a.M, a.K0, a.n[0]), fb = chain_splitk_scratch_floats(b.M, b.K0, b.n[0]);
         if (int r = mlp_scratch_reserve(c, fa + fb, s)) return r;
-        HIP_TRY(c, launch_chain_splitk_pair(a, b, c->d_mlp_scratch, c->d_mlp_scratch + fa, copy_src, copy_src_stride, copy_dst, copy_dst_stride, copy_cols, s));
+        HIP_TRY(c, launch_chain_splitk_pair(a, b, c->d_mlp_scratch.get(), c->d_mlp_scratch.get() + fa, copy_src, copy_src_stride, copy_dst, copy_dst_stride, copy_cols, s));
         return ROVER_OK;
     }
     if (copy_cols > 0)
@@ -1543,7 +1487,7 @@ int rover_set_option(rover_ctx* c, const char* name, int64_t value) {
     USE_DEVICE(c);                                 // some options (re)allocate device workspace
     if (!strcmp(name, "raycast_variant")) {
         if (value < 0 || value > 4) return fail(c, ROVER_E_INVALID, "raycast_variant must be 0 (auto), 1 (env order), 2 (binned), 3 (culled) or 4 (staged)");
-        if (value == 4 && c->have_map[0] && c->have_map[1] && c->map[0].K8 <= 256 && c->map[1].K8 <= 256 && !lane_tables_ok(c))
+        if (value == 4 && have_maps(c) && c->maps[0].knn.K8 <= 256 && c->maps[1].knn.K8 <= 256 && !lane_tables_ok(c))
             return fail(c, ROVER_E_STATE, "raycast_variant 4 (staged) needs its tables for the arithmetic in force: they were not built (option "
                                           "staged_tables, or they did not fit when the maps were set)");
         c->variant = (int)value;
@@ -1634,7 +1578,7 @@ int rover_get_profile(rover_ctx* c, rover_profile* out) {
     if (prof_drain(c)) return fail(c, ROVER_E_HIP, "get_profile: event drain failed");
     out->raycast_ms = c->prof_ms;
     out->launches = c->prof_launches;
-    out->pairs_per_launch = (uint64_t)c->cfg.num_envs * ((uint64_t)c->P * (uint64_t)c->map[0].K + 26ull * (uint64_t)c->map[1].K);
+    out->pairs_per_launch = (uint64_t)c->cfg.num_envs * ((uint64_t)c->P * (uint64_t)c->maps[0].knn.K + 26ull * (uint64_t)c->maps[1].knn.K);
     return ROVER_OK;
 }
 
@@ -1647,7 +1591,7 @@ int rover_replay_raycast(rover_ctx* c, void* stream) {
     if (v >= 2 && !c->sorted_valid && !lane_env_order(c, v)) v = 1;       // no sorted list from the last step: only an env-order kernel can replay
     const uint32_t n_valid = (uint32_t)c->cfg.num_envs * (26u + (uint32_t)c->P);
     hipStream_t s = (hipStream_t)stream;
-    if (v >= 3 && (!c->d_cull_queue || !c->d_cull_stats || c->cull_run != effective_run(c)))
+    if (v >= 3 && (!c->d_cull_queue.get() || !c->d_cull_stats.get() || c->cull_run != effective_run(c)))
         return fail(c, ROVER_E_STATE, "the culled ray cast's candidate queue is not allocated for the options in force");
     if (int r = run_raycast(c, v, n_valid, s)) return r;
     return ROVER_OK;

@@ -1614,30 +1614,24 @@ float cull_far_k2(int half, CullProofH ph) {
 uint32_t lane_pairs_per_row(uint32_t K8);
 static void lane_build(const int32_t* idx4, const uint4* ctab, uint64_t n_cells, uint32_t K8, uint32_t Y, float cell_size, float shift_x, float shift_y,
                        const uint32_t* qrow, const float* nz_abs, LaneTables t, int half, CullProofH ph, hipStream_t s);
-// T: the caller's triangle count (ids in map_idx); T_int: slots of the internal numbering (order [T_int], newid [T]).
 // ctab / qrow / far: the f32 proof's tables; ctab_h / qrow_h / far_h: the as-shipped fp16 arithmetic's (CullK<1>); idx4 and rtab serve both.
-hipError_t launch_cull_build(const int32_t* map_idx, const int32_t* tris, const uint16_t* verts, uint64_t n_cells, uint32_t K,
-                             uint32_t K8, uint32_t T, uint32_t T_int, uint32_t V, const uint32_t* order, const uint32_t* newid,
-                             int32_t* idx4, uint4* ctab, uint4* ctab_h, uint16_t* rtab, uint32_t* qrow, uint32_t* qrow_h, float4* far,
-                             float4* far_h, float* nz_scratch,
-                             uint32_t* counts /* [5], zeroed: always-candidate triangles, cells without a cone; the same for fp16; cells with a useful far bound */,
-                             CullProofH ph, uint32_t Y, float cell_size, float shift_x, float shift_y, LaneTables lane, LaneTables lane_h, hipStream_t s) {
-    hipLaunchKernelGGL(rtab_build_kernel, dim3(blocks_for(T_int, 256)), dim3(256), 0, s, tris, verts, T_int, V, order, rtab);
-    hipLaunchKernelGGL(ctab_build_kernel<1>, dim3(blocks_for(T_int, 256)), dim3(256), 0, s, rtab, T_int, order, ctab_h, nz_scratch, counts + 2, ph);
-    hipLaunchKernelGGL(idx4_build_kernel, dim3((uint32_t)n_cells), dim3(256), 0, s, map_idx, K, K8, T, newid, nz_scratch, rtab, Y, cell_size,
-                       shift_x, shift_y, idx4, qrow_h, counts + 2);
-    lane_build(idx4, ctab_h, n_cells, K8, Y, cell_size, shift_x, shift_y, qrow_h, nz_scratch, lane_h, 1, ph, s);      // (nz_scratch holds the fp16 proof's cone values here)
-    hipLaunchKernelGGL(ctab_build_kernel<0>, dim3(blocks_for(T_int, 256)), dim3(256), 0, s, rtab, T_int, order, ctab, nz_scratch, counts, ph);
-    hipLaunchKernelGGL(idx4_build_kernel, dim3((uint32_t)n_cells), dim3(256), 0, s, map_idx, K, K8, T, newid, nz_scratch, rtab, Y, cell_size,
-                       shift_x, shift_y, idx4, qrow, counts);
-    lane_build(idx4, ctab, n_cells, K8, Y, cell_size, shift_x, shift_y, qrow, nz_scratch, lane, 0, ph, s);
+hipError_t launch_cull_build(const CullBuildArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(rtab_build_kernel, dim3(blocks_for(a.T_int, 256)), dim3(256), 0, s, a.tris, a.verts, a.T_int, a.V, a.order, a.rtab);
+    hipLaunchKernelGGL(ctab_build_kernel<1>, dim3(blocks_for(a.T_int, 256)), dim3(256), 0, s, a.rtab, a.T_int, a.order, a.ctab_h, a.nz_scratch, a.counts + 2, a.ph);
+    hipLaunchKernelGGL(idx4_build_kernel, dim3((uint32_t)a.n_cells), dim3(256), 0, s, a.map_idx, a.K, a.K8, a.T, a.newid, a.nz_scratch, a.rtab, a.Y, a.cell_size,
+                       a.shift_x, a.shift_y, a.idx4, a.qrow_h, a.counts + 2);
+    lane_build(a.idx4, a.ctab_h, a.n_cells, a.K8, a.Y, a.cell_size, a.shift_x, a.shift_y, a.qrow_h, a.nz_scratch, a.lane_h, 1, a.ph, s);      // (nz_scratch holds the fp16 proof's cone values here)
+    hipLaunchKernelGGL(ctab_build_kernel<0>, dim3(blocks_for(a.T_int, 256)), dim3(256), 0, s, a.rtab, a.T_int, a.order, a.ctab, a.nz_scratch, a.counts, a.ph);
+    hipLaunchKernelGGL(idx4_build_kernel, dim3((uint32_t)a.n_cells), dim3(256), 0, s, a.map_idx, a.K, a.K8, a.T, a.newid, a.nz_scratch, a.rtab, a.Y, a.cell_size,
+                       a.shift_x, a.shift_y, a.idx4, a.qrow, a.counts);
+    lane_build(a.idx4, a.ctab, a.n_cells, a.K8, a.Y, a.cell_size, a.shift_x, a.shift_y, a.qrow, a.nz_scratch, a.lane, 0, a.ph, s);
     float k1, k2;
     cull_far_consts(CullK<0>::c_a, 1.00001, &k1, &k2);
-    hipLaunchKernelGGL(far_build_kernel, dim3(blocks_for(n_cells, 4)), dim3(256), 0, s, reinterpret_cast<const int4*>(idx4), ctab, n_cells, K8, Y,
-                       cell_size, shift_x, shift_y, k1, CullK<0>::tau2, qrow, reinterpret_cast<FarRec*>(far), far + 2ull * n_cells, counts + 4);
-    cull_far_consts(ph.c_a, 1.004, &k1, &k2);
-    hipLaunchKernelGGL(far_build_kernel, dim3(blocks_for(n_cells, 4)), dim3(256), 0, s, reinterpret_cast<const int4*>(idx4), ctab_h, n_cells, K8, Y,
-                       cell_size, shift_x, shift_y, k1, ph.tau2, qrow_h, reinterpret_cast<FarRec*>(far_h), far_h + 2ull * n_cells, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(far_build_kernel, dim3(blocks_for(a.n_cells, 4)), dim3(256), 0, s, reinterpret_cast<const int4*>(a.idx4), a.ctab, a.n_cells, a.K8, a.Y,
+                       a.cell_size, a.shift_x, a.shift_y, k1, CullK<0>::tau2, a.qrow, reinterpret_cast<FarRec*>(a.far), a.far + 2ull * a.n_cells, a.counts + 4);
+    cull_far_consts(a.ph.c_a, 1.004, &k1, &k2);
+    hipLaunchKernelGGL(far_build_kernel, dim3(blocks_for(a.n_cells, 4)), dim3(256), 0, s, reinterpret_cast<const int4*>(a.idx4), a.ctab_h, a.n_cells, a.K8, a.Y,
+                       a.cell_size, a.shift_x, a.shift_y, k1, a.ph.tau2, a.qrow_h, reinterpret_cast<FarRec*>(a.far_h), a.far_h + 2ull * a.n_cells, (uint32_t*)nullptr);
     return hipGetLastError();
 }
 

@@ -230,11 +230,28 @@ hipError_t launch_raycast_binned(const RayRec* rays, const uint32_t* sorted, uin
                                  const uint16_t* tab1, uint32_t kp0, uint32_t kp1, uint32_t run, bool fp16_math, uint32_t early_out, float* out,
                                  hipStream_t s);
 hipError_t launch_tri_centroids(const int32_t* tris, const uint16_t* verts, uint32_t T, uint32_t V, float2* out, hipStream_t s);
-hipError_t launch_cull_build(const int32_t* map_idx, const int32_t* tris, const uint16_t* verts, uint64_t n_cells, uint32_t K,
-                             uint32_t K8, uint32_t T, uint32_t T_int, uint32_t V, const uint32_t* order, const uint32_t* newid,
-                             int32_t* idx4, uint4* ctab, uint4* ctab_h, uint16_t* rtab, uint32_t* qrow, uint32_t* qrow_h, float4* far,
-                             float4* far_h, float* nz_scratch, uint32_t* counts, CullProofH ph, uint32_t Y, float cell_size, float shift_x,
-                             float shift_y, LaneTables lane, LaneTables lane_h, hipStream_t s);
+// the tables of the culled and staged ray casts for one map (launch_cull_build, rover_cull.hip)
+struct CullBuildArgs {
+    const int32_t* map_idx;      // [cell][K] the caller's triangle ids
+    const int32_t* tris;         // [T][3]
+    const uint16_t* verts;       // [V][3] fp16
+    uint64_t n_cells;
+    uint32_t K, K8;
+    uint32_t T, T_int, V;        // T: the caller's triangle count (ids in map_idx); T_int: slots of the internal numbering
+    const uint32_t *order, *newid;   // [T_int] internal id -> caller's (0xffffffff = hole), [T] caller's id -> internal
+    int32_t* idx4;               // [cell][K8/4][4] internal triangle ids (both proofs)
+    uint16_t* rtab;              // [T_int] 20 B: nine fp16 vertex components (both proofs)
+    uint4 *ctab, *ctab_h;        // [T_int] per proof: f32 / as-shipped fp16 (CullK<1>)
+    uint32_t *qrow, *qrow_h;     // [cell] per proof, read only by the build kernels
+    float4 *far, *far_h;         // [cell][2] far-pair bounds, then [cell] near-pair bounds, per proof
+    float* nz_scratch;           // [T_int]
+    uint32_t* counts;            // [5], zeroed: always-candidate triangles, cells without a cone; the same for fp16; cells with a useful far bound
+    CullProofH ph;
+    uint32_t Y;
+    float cell_size, shift_x, shift_y;
+    LaneTables lane, lane_h;     // the staged kernel's tables per proof (null: not built)
+};
+hipError_t launch_cull_build(const CullBuildArgs& a, hipStream_t s);
 float cull_far_k2(int half, CullProofH ph);
 hipError_t launch_raycast_culled(CullArgs a, hipStream_t s);
 hipError_t launch_knn_centroids(const float* verts, const int32_t* tris, uint32_t T, uint32_t V, int ref, float* cx, float* cy,

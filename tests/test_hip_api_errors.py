@@ -191,6 +191,17 @@ def test_obs_row_stride_and_create_destroy_loop():
         e2, _ = _engine(64)
         e2.close()
     assert torch.cuda.mem_get_info()[0] >= free0 - (64 << 20)
+    # re-setting a scene frees the tables it replaces: one leaked set of these maps' tables exceeds the tolerance
+    big = synth.make_scene(n_cells=300, k=100, n_stones=16, device="cuda")
+    torch.cuda.empty_cache()
+    free0 = torch.cuda.mem_get_info()[0]
+    e3 = _lib.Engine(64, device=0)
+    for _ in range(20):
+        e3.set_scene(big, synth.ray_distribution("9"))
+    assert e3.info().table_bytes[0] > (64 << 20)
+    e3.close()
+    torch.cuda.empty_cache()
+    assert torch.cuda.mem_get_info()[0] >= free0 - (64 << 20)
 
 
 def test_mlp_chain_forward_shapes_and_errors():
