@@ -240,6 +240,33 @@ ROVER_API int rover_pre_physics_step(rover_ctx *ctx, const float *actions, const
 ROVER_API int rover_ackermann(rover_ctx *ctx, const float *lin, const float *ang, int32_t n, float *steering,
                               float *velocities, void *stream);
 
+/* ---- evaluation mode: per-rover outcome codes (rover.py:122-137 buffers, :620-641 is_done, :670-672 check_collision) ------- */
+/* The reference's is_evaluation branch.  Per env a code, 0 until the env's FIRST outcome, then never changed and never cleared by a
+ * reset (only the first outcome of each rover counts, rover.py:124-129):
+ *   1  collided (check_collision, :670-672 — run by get_observations only at curriculum level >= 2, :292-293), or out of area:
+ *      target distance >= 9.5 (:622-624; no reset below 11),
+ *   2  reached the goal: target distance <= 0.18 (:627-628),
+ *   3  timed out: progress >= max_episode_length (:630-631),
+ * checked in that order (a collision of the same step beats everything, then out of area, goal, timeout).  A tilt reset or the
+ * d >= 11 reset gives no code of its own.  ADDITIONAL output (not in the reference): eval_step, the env's progress at the step its code
+ * latched (the steps to the outcome).  The latch runs inside the metrics pass of rover_step (both stages, reference order),
+ * rover_get_observations (collision, level >= 2) and rover_is_done (the other three); rover_calculate_metrics, rover_get_depths,
+ * rover_get_collisions and rover_cast_rays never latch.  While evaluation is on, those calls need in->progress.
+ * The file dump of :632-640 (torch.save at global_step % max_episode_length == 0) is the caller's: RoverTask(eval_save_dir=...).
+ *
+ * rover_set_evaluation: init-time.  enable != 0 allocates the ctx's two [E] int64 arrays (eval_res, eval_step), zeroes them and
+ *   synchronises the device; enable = 0 frees them and turns the latch off.  With evaluation off the step's outputs and kernels are
+ *   those of a ctx that never had it. */
+ROVER_API int rover_set_evaluation(rover_ctx *ctx, int32_t enable);
+/* Resets env_ids [n] (LOCAL ids, a device pointer) to code 0 and step 0, or every env when env_ids is NULL (n is then ignored): a new
+ * evaluation window, or chosen envs re-armed.  The ids are checked on the host (the call synchronises `stream` when env_ids is given):
+ * an id outside [0, num_envs) or n outside [0, num_envs] is ROVER_E_INVALID.  ROVER_E_STATE while evaluation is off. */
+ROVER_API int rover_eval_clear(rover_ctx *ctx, const int64_t *env_ids, int32_t n, void *stream);
+/* Copies the state out on `stream`, enqueue only (no synchronisation); every pointer is an optional DEVICE pointer:
+ * eval_res [E] int64 (self.rover_eval_res, rover.py:130), eval_step [E] int64, summary8 [8] int64 = count of codes 0..3, then the sum of
+ * eval_step over the envs of codes 0..3 (exact integer sums).  ROVER_E_STATE while evaluation is off. */
+ROVER_API int rover_eval_read(rover_ctx *ctx, int64_t *eval_res, int64_t *eval_step, int64_t *summary8, void *stream);
+
 /* ---- KNN map builder ("next" row f-3): tasks/utils/rover_utils.py:48-123 ------------------------------------ */
 /* For every cell (x, y) of an X x Y map at `res` metres per cell (cell position = (x res, y res), rover_utils.py:75-81)
  * the K triangles whose centroid ((v0+v1+v2)/3, :68-70) is nearest in xy, ascending.  vertices [V,3] float32,

@@ -124,6 +124,9 @@ SYMBOLS = {
     "rover_linear_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "rover_mlp_chain_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rover_mlp_chain_pair_forward": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
+    "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
+    "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
     "rover_set_option": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "rover_set_profiling": (C.c_int, [_P, C.c_int32]),
     "rover_get_profile": (C.c_int, [_P, C.POINTER(Profile)]),
@@ -553,6 +556,29 @@ class Engine:
             self._h, xa.shape[0], C.byref(da), C.byref(db), _ptr(copy_src) if copy_cols else None, copy_src.stride(0) if copy_cols else 0,
             _ptr(copy_dst) if copy_cols else None, copy_dst.stride(0) if copy_cols else 0, int(copy_cols), _stream(self._dev_index)),
             "rover_mlp_chain_pair_forward")
+
+    # ---- evaluation mode (rover.py:122-137, 620-641, 670-672) -------------------------------------
+    def set_evaluation(self, enable=True):
+        """Turns the per-env outcome latch on (fresh zeroed codes and steps, synchronises) or off (frees them)."""
+        self._check(self.lib.rover_set_evaluation(self._h, 1 if enable else 0), "rover_set_evaluation")
+
+    def eval_clear(self, env_ids=None):
+        """Re-arms the given LOCAL env ids (int64 device tensor), or every env: code 0, step 0.  With ids the call synchronises."""
+        n = 0
+        if env_ids is not None:
+            n = env_ids.shape[0]
+            self._chk(env_ids, (n,), torch.int64, "env_ids")
+        self._check(self.lib.rover_eval_clear(self._h, _ptr(env_ids), n, _stream(self._dev_index)), "rover_eval_clear")
+
+    def eval_read(self, eval_res=None, eval_step=None, summary8=None):
+        """Enqueues copies of the codes [E], the latch steps [E] and / or the summary [8] (counts of codes 0..3, sums of the steps
+        over codes 0..3) into the given int64 device tensors; no host sync."""
+        e = self.num_envs
+        self._chk(eval_res, (e,), torch.int64, "eval_res")
+        self._chk(eval_step, (e,), torch.int64, "eval_step")
+        self._chk(summary8, (8,), torch.int64, "summary8")
+        self._check(self.lib.rover_eval_read(self._h, _ptr(eval_res), _ptr(eval_step), _ptr(summary8), _stream(self._dev_index)),
+                    "rover_eval_read")
 
     def set_option(self, name, value):
         self._check(self.lib.rover_set_option(self._h, name.encode(), int(value)), "rover_set_option")

@@ -139,6 +139,10 @@ struct rover_ctx {
     bool ws_ok = false, bins_ok = false;   // false after a failed (re)allocation: the step entry points refuse to run
     bool rays_valid = false;            // the ray workspace holds a finished ray cast (rover_replay_raycast)
     bool obs_valid = false;             // ... and euler / heading hold the state of a rover_get_observations (rover_calculate_metrics reads them)
+    // evaluation mode (rover_set_evaluation): per-env outcome code and the progress at which it latched
+    DevBuf<int64_t> d_eval_res;         // [E] 0 pending, 1 collided / out of area, 2 reached goal, 3 timed out
+    DevBuf<int64_t> d_eval_step;        // [E]
+    bool eval_on = false;
     // in-situ ray-cast timing (rover_set_profiling)
     bool profiling = false;
     int32_t prof_every = 1;             // time every prof_every-th ray-cast launch (an event pair costs ~12 us of stream time)
@@ -996,6 +1000,11 @@ static int do_metrics(rover_ctx* c, const rover_step_in* in, const rover_step_ou
     m.done_u8 = done ? out->done_u8 : nullptr;
     m.sgrid = c->sgrid; m.info7 = c->d_stones.get();
     m.ex_goal_angle = out->ex_goal_angle_penalty; m.ex_lin = out->ex_torque_penalty_driving; m.ex_ang = out->ex_torque_penalty_steering;
+    // the evaluation latch: check_collision's update (rover.py:670-672, level >= 2 only) and is_done's (:620-631); never metrics alone
+    if (c->eval_on && ((coll && c->cfg.curriculum_level >= 2) || done)) {
+        if (!in->progress) return fail(c, ROVER_E_INVALID, "evaluation: progress is required (the latch records it)");
+        m.eval_res = c->d_eval_res.get(); m.eval_step = c->d_eval_step.get();
+    }
     if (c->obs_pending) {
         c->obs_pending = false;
         HIP_TRY(c, launch_obs_metrics(c->pending_obs, m, s));
@@ -1113,6 +1122,53 @@ int rover_step(rover_ctx* c, const rover_step_in* in, const rover_step_out* out,
     if (compact)
         HIP_TRY(c, launch_compact(out->reset, (uint32_t)c->cfg.num_envs, (int64_t)c->cfg.env_offset, c->d_block_cnt.get(), true,
                                   out->reset_ids, out->n_reset, s));
+    return ROVER_OK;
+}
+
+// ---- evaluation mode -------------------------------------------------------------------------------
+int rover_set_evaluation(rover_ctx* c, int32_t enable) {
+    if (!c) return ROVER_E_INVALID;
+    USE_DEVICE(c);
+    c->eval_on = false;
+    c->d_eval_res.reset(); c->d_eval_step.reset();
+    if (!enable) return ROVER_OK;
+    const size_t E = (size_t)c->cfg.num_envs;
+    HIP_TRY(c, c->d_eval_res.alloc(E));
+    HIP_TRY(c, c->d_eval_step.alloc(E));
+    HIP_TRY(c, hipMemset(c->d_eval_res.get(), 0, c->d_eval_res.bytes()));
+    HIP_TRY(c, hipMemset(c->d_eval_step.get(), 0, c->d_eval_step.bytes()));
+    HIP_TRY(c, hipDeviceSynchronize());
+    c->eval_on = true;
+    return ROVER_OK;
+}
+
+int rover_eval_clear(rover_ctx* c, const int64_t* env_ids, int32_t n, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    if (!c->eval_on) return fail(c, ROVER_E_STATE, "eval_clear: evaluation is off (rover_set_evaluation(ctx, 1) first)");
+    const int32_t E = c->cfg.num_envs;
+    if (env_ids && (n < 0 || n > E)) return fail(c, ROVER_E_INVALID, "eval_clear: n = %d outside [0, %d]", n, E);
+    USE_DEVICE(c);
+    hipStream_t s = (hipStream_t)stream;
+    if (env_ids && n > 0) {                 // the ids are checked on the host: the call waits for the stream that wrote them
+        std::vector<int64_t> h((size_t)n);
+        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, hipMemcpy(h.data(), env_ids, h.size() * sizeof(int64_t), hipMemcpyDefault));
+        for (int32_t i = 0; i < n; ++i)
+            if (h[i] < 0 || h[i] >= E) return fail(c, ROVER_E_INVALID, "eval_clear: env id %lld outside [0, %d)", (long long)h[i], E);
+    }
+    HIP_TRY(c, launch_eval_clear(c->d_eval_res.get(), c->d_eval_step.get(), (uint32_t)E, env_ids, env_ids ? (uint32_t)n : (uint32_t)E, s));
+    return ROVER_OK;
+}
+
+int rover_eval_read(rover_ctx* c, int64_t* eval_res, int64_t* eval_step, int64_t* summary8, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    if (!c->eval_on) return fail(c, ROVER_E_STATE, "eval_read: evaluation is off (rover_set_evaluation(ctx, 1) first)");
+    USE_DEVICE(c);
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t bytes = (uint64_t)c->cfg.num_envs * sizeof(int64_t);
+    if (eval_res) HIP_TRY(c, hipMemcpyAsync(eval_res, c->d_eval_res.get(), bytes, hipMemcpyDeviceToDevice, s));
+    if (eval_step) HIP_TRY(c, hipMemcpyAsync(eval_step, c->d_eval_step.get(), bytes, hipMemcpyDeviceToDevice, s));
+    if (summary8) HIP_TRY(c, launch_eval_summary(c->d_eval_res.get(), c->d_eval_step.get(), (uint32_t)c->cfg.num_envs, summary8, s));
     return ROVER_OK;
 }
 

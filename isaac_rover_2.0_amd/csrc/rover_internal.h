@@ -157,6 +157,10 @@ struct MetricsArgs {
     float stone_margin;
     StoneGridDev sgrid;
     const float* info7;
+    // optional evaluation latch (rover_set_evaluation, rover.py:620-641,670-672): the host passes it to the collision stage at
+    // curriculum level >= 2 and to the done stage only; null = off.  eval_step: progress at the step the code latched.
+    int64_t* eval_res;
+    int64_t* eval_step;
 };
 
 struct ResetArgs {
@@ -274,6 +278,8 @@ hipError_t launch_obs_metrics(const ObsArgs& o, const MetricsArgs& m, hipStream_
 hipError_t launch_metrics_done(const MetricsArgs& a, hipStream_t s);
 hipError_t launch_compact(const int64_t* reset, uint32_t n, int64_t offset, uint32_t* block_cnt, bool counted, int64_t* ids,
                           int32_t* count, hipStream_t s);
+hipError_t launch_eval_summary(const int64_t* eval_res, const int64_t* eval_step, uint32_t E, int64_t* summary8, hipStream_t s);
+hipError_t launch_eval_clear(int64_t* eval_res, int64_t* eval_step, uint32_t E, const int64_t* ids, uint32_t n, hipStream_t s);
 hipError_t launch_quat_to_euler(const float* q, float* eul, uint32_t n, hipStream_t s);
 hipError_t launch_clearance(const float* info7, uint32_t S, const float* xy, uint32_t n, float* out, hipStream_t s);
 hipError_t launch_shift_spawns(const StoneGridDev& g, const float* info7, float* pos3, uint32_t n, int32_t max_iter, hipStream_t s);

@@ -615,8 +615,11 @@ __device__ __forceinline__ void metrics_done_env(const MetricsArgs& a, uint32_t 
     // Every load of the env first, every store after: the compiler may not move a load above a store it cannot prove
     // disjoint, so loads placed where they are used made the thread wait for memory five or six times in a row (one env per
     // thread: 1 024 waves, nothing else to run meanwhile).
-    const bool need_progress = a.do_increment | a.do_metrics | a.do_done;
+    const bool eval = a.eval_res != nullptr;                               // evaluation latch (rover.py:620-641,670-672)
+    const bool need_progress = a.do_increment | a.do_metrics | a.do_done | eval;
     int64_t progress = need_progress ? a.progress[e] : 0;
+    const int64_t code0 = eval ? a.eval_res[e] : 0;                         // once set, a code never changes
+    int64_t code = code0;
     const bool cast = a.do_collision && a.curriculum_level >= 2;
     float4 dw[6];
     float2 db = make_float2(0.0f, 0.0f);
@@ -660,6 +663,7 @@ __device__ __forceinline__ void metrics_done_env(const MetricsArgs& a, uint32_t 
         }
         a.rock_collision[e] = coll;
         if (a.stone_collision) a.stone_collision[e] = stone ? 1 : 0;
+        if (eval && cast && code == 0) code = coll;                         // :670-672 (check_collision runs at level >= 2 only)
     }
     float td = sqrtf(tx * tx + ty * ty);                                    // :482 / :617
     if (a.do_metrics) {
@@ -698,7 +702,13 @@ __device__ __forceinline__ void metrics_done_env(const MetricsArgs& a, uint32_t 
         a.reset[e] = reset;
         if (a.done_u8) a.done_u8[e] = (uint8_t)reset;
         done_flag = reset != 0;
+        if (eval) {                                                         // :620-631, each only while the code is still 0
+            if (code == 0 && td >= 9.5f) code = 1;                          // out of area counts as a collision (no reset below 11)
+            if (code == 0 && td <= 0.18f) code = 2;                         // reached the goal
+            if (code == 0 && progress >= (int64_t)a.max_episode_length) code = 3;   // timed out
+        }
     }
+    if (eval && code != code0) { a.eval_res[e] = code; a.eval_step[e] = progress; }
 }
 
 __device__ __forceinline__ void metrics_done_block(const MetricsArgs& a, uint32_t bid) {
@@ -750,6 +760,51 @@ __global__ void __launch_bounds__(256) compact_write_kernel(const int64_t* __res
     for (uint32_t v = 0; v < 4u; ++v) woff += (v < w) ? wcnt[v] : 0u;
     if (flag) ids[base + woff + __popcll(ballot & ((1ull << lane) - 1ull))] = offset + (int64_t)i;
     if (blockIdx.x == gridDim.x - 1 && tid == 0) *count = (int32_t)(base + wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3]);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// evaluation bookkeeping (rover_eval_read / rover_eval_clear): summary = [count of codes 0..3 | sum of eval_step over codes 0..3]
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) eval_summary_kernel(const int64_t* __restrict__ eval_res, const int64_t* __restrict__ eval_step,
+                                                           uint32_t E, unsigned long long* __restrict__ summary8) {
+    __shared__ unsigned long long part[8];
+    if (threadIdx.x < 8u) part[threadIdx.x] = 0ull;
+    __syncthreads();
+    unsigned long long cnt[4] = {0ull, 0ull, 0ull, 0ull}, sum[4] = {0ull, 0ull, 0ull, 0ull};
+    for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < E; e += gridDim.x * 256u) {
+        const int64_t c = eval_res[e];
+        const unsigned long long st = (unsigned long long)eval_step[e];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            cnt[k] += (c == k) ? 1ull : 0ull;
+            sum[k] += (c == k) ? st : 0ull;
+        }
+    }
+    // integer sums (two's complement, mod 2^64): exact and independent of the order of the atomics
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            cnt[k] += __shfl_xor(cnt[k], off, 64);
+            sum[k] += __shfl_xor(sum[k], off, 64);
+        }
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { atomicAdd(&part[k], cnt[k]); atomicAdd(&part[4 + k], sum[k]); }
+    }
+    __syncthreads();
+    if (threadIdx.x < 8u) atomicAdd(&summary8[threadIdx.x], part[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(256) eval_clear_kernel(int64_t* __restrict__ eval_res, int64_t* __restrict__ eval_step, uint32_t E,
+                                                         const int64_t* __restrict__ ids, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const int64_t e = ids ? ids[i] : (int64_t)i;
+    if (e < 0 || e >= (int64_t)E) return;                                   // (the host validated the ids; never write outside)
+    eval_res[e] = 0;
+    eval_step[e] = 0;
 }
 
 __global__ void __launch_bounds__(256) quat_to_euler_kernel(const float* __restrict__ q, float* __restrict__ eul, uint32_t n) {
@@ -1874,6 +1929,22 @@ hipError_t launch_compact(const int64_t* reset, uint32_t n, int64_t offset, uint
     const uint32_t nb = blocks_for(n, 256);
     if (!counted) hipLaunchKernelGGL(compact_count_kernel, dim3(nb), dim3(256), 0, s, reset, n, block_cnt);
     hipLaunchKernelGGL(compact_write_kernel, dim3(nb), dim3(256), 0, s, reset, n, offset, block_cnt, ids, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_eval_summary(const int64_t* eval_res, const int64_t* eval_step, uint32_t E, int64_t* summary8, hipStream_t s) {
+    hipError_t err = hipMemsetAsync(summary8, 0, 8 * sizeof(int64_t), s);
+    if (err != hipSuccess) return err;
+    uint32_t nb = blocks_for(E, 256);
+    if (nb > 1024u) nb = 1024u;                                             // grid-stride: at most 1 024 x 8 atomics on the result
+    hipLaunchKernelGGL(eval_summary_kernel, dim3(nb), dim3(256), 0, s, eval_res, eval_step, E,
+                       reinterpret_cast<unsigned long long*>(summary8));
+    return hipGetLastError();
+}
+
+hipError_t launch_eval_clear(int64_t* eval_res, int64_t* eval_step, uint32_t E, const int64_t* ids, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(eval_clear_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, eval_res, eval_step, E, ids, n);
     return hipGetLastError();
 }
 

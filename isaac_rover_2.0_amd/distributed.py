@@ -135,3 +135,13 @@ class StepGather:
         if wait:
             self.wait(d)
         return self.global_views(d)
+
+
+def reduce_eval_summary(summary: torch.Tensor, group=None) -> torch.Tensor:
+    """Evaluation mode across env shards: SUM all-reduce, in place, of a rank's int64 [8] summary (``rover_eval_read``: counts of the
+    codes 0..3, then the sums of the latch steps over codes 0..3), so that every rank holds the whole run's totals.  Integer sums:
+    exact and independent of the rank order.  The per-env codes themselves stay on their shard, in local env order."""
+    if summary.dtype != torch.int64 or tuple(summary.shape) != (8,):
+        raise ValueError(f"reduce_eval_summary: expected an int64 [8] summary, got {summary.dtype} {tuple(summary.shape)}")
+    dist.all_reduce(summary, op=dist.ReduceOp.SUM, group=group)
+    return summary

@@ -8,7 +8,13 @@ task.  Every tensor computation of ``get_observations`` / ``calculate_metrics`` 
 class is host-side bookkeeping only and raises if the library or a GPU is missing (no CPU fallback).
 
 What is NOT here: USD stage building (:187-270), the dead teacher/student loaders (:169-172),
-teacher-data dumps (:298-317), evaluation bookkeeping (:620-641).
+teacher-data dumps (:298-317), the evaluation branch's prints and its unread ``is_evaluation_with_noise`` / ``max_noise_dev``.
+
+Evaluation mode (``is_evaluation=True``; :122-137, :620-641, :670-672) is the reference's: one outcome code per rover in
+``self.rover_eval_res`` (1 collided or out of area, 2 reached the goal, 3 timed out; the first outcome counts), latched on the
+device inside the step's metrics pass (``rover_set_evaluation``), so it needs no host sync and is part of a captured graph.  Added
+on top: ``self.rover_eval_steps`` (progress at the latch), ``evaluation_summary()`` and ``eval_clear()``.  The reference's two
+``torch.save`` files (:632-640) are written only when ``eval_save_dir`` is given.
 
 Deviations from the reference, all deliberate and tested:
   * ``post_physics_step`` is ONE fused ``rover_step`` launch sequence (``fused=True``, default); with
@@ -26,7 +32,10 @@ Deviations from the reference, all deliberate and tested:
 from __future__ import annotations
 
 import math
+import os
+import random
 
+import numpy as np
 import torch
 
 from .. import _lib, synth
@@ -101,7 +110,7 @@ class _RockDetector:
 class RoverTask(RLTask):
     def __init__(self, name, sim_config, env, offset=None, *, scene=None, distribution=None, fused=True,
                  device_reset=True, ray_precision="fp32", num_envs_global=None, env_offset=0, stone_mask_margin=None,
-                 cell_index_mode="cuda_rcp", graph=False) -> None:
+                 cell_index_mode="cuda_rcp", graph=False, is_evaluation=False, eval_save_dir=None) -> None:
         """``scene``: a ``synth.Scene`` (or ``assets.load_reference_assets(root)``) with the terrain / rocks KNN maps,
         stone list and heightfield the reference loads from disk (:92-94,:144,:210).  ``distribution``: optional
         (points [P,3] f64, sparse_idx, dense_idx); default = the reference's native 1634-point set.
@@ -110,7 +119,9 @@ class RoverTask(RLTask):
         the reference's step does not have and that never feeds reward or done.
         ``cell_index_mode``: how the cell lookup ``(xy - shift) / 0.1`` (camera.py:241, rock_detect.py:381, rover.py:590) is
         rounded.  Default "cuda_rcp" = the reference AS DEPLOYED (rover.py:90 pins cuda:0, where ATen multiplies by the
-        reciprocal); "cpu_div" = ATen's CPU division, what the golden vectors (captured on the CPU) pin."""
+        reciprocal); "cpu_div" = ATen's CPU division, what the golden vectors (captured on the CPU) pin.
+        ``is_evaluation``: the reference's evaluation mode (:122-137), fixed for the task's lifetime (assigning to
+        ``self.is_evaluation`` later raises).  ``eval_save_dir``: where the two files of :632-640 go (None: nothing is written)."""
         if scene is None:
             raise ValueError("RoverTask needs the terrain assets: pass scene=assets.load_reference_assets(root) "
                              "or a synth.Scene")
@@ -142,7 +153,15 @@ class RoverTask(RLTask):
         self._reset_dist = self._task_cfg["env"]["resetDist"]
         self.max_episode_length = 3000                                                    # :119
         self.curriculum = self._task_cfg["env"]["terrain"]["curriculum"]
-        self.is_evaluation = False
+        self._is_evaluation = bool(is_evaluation)
+        self._eval_save_dir = eval_save_dir
+        if eval_save_dir is not None and not self._is_evaluation:
+            raise ValueError("eval_save_dir needs is_evaluation=True")
+        if self._is_evaluation:                                                           # :133-137
+            seed = self._seed
+            torch.manual_seed(seed)
+            random.seed(seed)
+            np.random.seed(seed)
         self.target_positions = torch.zeros((self._num_envs, 3), device=self._device, dtype=torch.float32)   # :142
         self.stone_info = torch.from_numpy(synth.read_stone_info_array(scene.stone_info_raw)).to(self._device)  # :144
         self.save_teacher_data = self._task_cfg["collect_data"]
@@ -172,6 +191,12 @@ class RoverTask(RLTask):
         self.Camera._engine = self._engine
         self.Rock_detector._engine = self._engine
         self._env_offset = int(env_offset)
+        self._eval_name = ""                            # the reference's self._name of the dump, set by pre_physics_step (:376)
+        if self._is_evaluation:                         # :130: rover_eval_res, one int64 code per env; the latch state lives in the ctx
+            self._engine.set_evaluation(True)
+            self._eval_res = torch.zeros(self._num_envs, dtype=torch.long, device=self._device)
+            self._eval_steps = torch.zeros(self._num_envs, dtype=torch.long, device=self._device)
+            self._eval_sum = torch.zeros(8, dtype=torch.long, device=self._device)
 
         # persistent side-state the three methods hand to each other (:274-283, :343, :667)
         e, dev = self._num_envs, self._device
@@ -261,9 +286,69 @@ class RoverTask(RLTask):
         self._engine.calculate_metrics(self._sin, self._sout)
 
     def is_done(self) -> None:
-        """rover.py:610-647 → rover_is_done (tilt from the PRE-physics euler ``self.rover_rot``)."""
+        """rover.py:610-647 → rover_is_done (tilt from the PRE-physics euler ``self.rover_rot``; with evaluation on, also the
+        outcome codes of :620-631 and the dump of :632-640)."""
         self._engine.is_done(self._sin, self._sout)
         self._compaction_fresh = False
+        self._eval_dump()
+
+    # ------------------------------------------------------------------------------------------------
+    # evaluation mode (rover.py:122-137, 620-641, 670-672)
+    # ------------------------------------------------------------------------------------------------
+    @property
+    def is_evaluation(self) -> bool:
+        return self._is_evaluation
+
+    @is_evaluation.setter
+    def is_evaluation(self, value):
+        raise AttributeError("is_evaluation is fixed at construction: RoverTask(..., is_evaluation=True)")
+
+    def _eval_check(self):
+        if not self._is_evaluation:
+            raise AttributeError("evaluation mode is off: RoverTask(..., is_evaluation=True)")
+
+    @property
+    def rover_eval_res(self) -> torch.Tensor:
+        """[E] int64 outcome codes (0 pending, 1 collided / out of area, 2 reached goal, 3 timed out): a persistent tensor the
+        read is enqueued into on the current stream (no host sync)."""
+        self._eval_check()
+        self._engine.eval_read(eval_res=self._eval_res)
+        return self._eval_res
+
+    @property
+    def rover_eval_steps(self) -> torch.Tensor:
+        """[E] int64 progress at the step each code latched (0 while pending); enqueued like ``rover_eval_res``."""
+        self._eval_check()
+        self._engine.eval_read(eval_step=self._eval_steps)
+        return self._eval_steps
+
+    def evaluation_summary(self) -> dict:
+        """Counts of the four codes over this task's envs, the success rate (reached goal / envs) and the mean progress at
+        which the goal was reached (nan before the first one).  One host sync."""
+        self._eval_check()
+        self._engine.eval_read(summary8=self._eval_sum)
+        s = self._eval_sum.tolist()
+        return dict(pending=s[0], collided=s[1], reached_goal=s[2], timed_out=s[3], num_envs=self._num_envs,
+                    success_rate=s[2] / self._num_envs, mean_steps_to_goal=(s[6] / s[2]) if s[2] else float("nan"),
+                    summary8=s)
+
+    def eval_clear(self, env_ids=None):
+        """Re-arms every env (None) or the given local env ids: code 0, step 0.  Captured graphs are dropped (recaptured)."""
+        self._eval_check()
+        if env_ids is not None:
+            env_ids = torch.as_tensor(env_ids, device=self._device).long().contiguous()
+        self._engine.eval_clear(env_ids)
+        self._pre_graph = self._post_graph = None
+
+    def _eval_dump(self):
+        """:632-640: at global_step % max_episode_length == 0 the progress of the envs whose code is 2 — of their CURRENT episode,
+        [n, 1] (the reference's quirk) — and the codes, under the reference's file names, into ``eval_save_dir``."""
+        if self._eval_save_dir is None or self.global_step % self.max_episode_length != 0:
+            return
+        res = self.rover_eval_res
+        indexes = (res == 2).nonzero(as_tuple=False)
+        torch.save(self.progress_buf[indexes].cpu(), os.path.join(self._eval_save_dir, self._eval_name + "episode_length.pt"))
+        torch.save(res.cpu().clone(), os.path.join(self._eval_save_dir, self._eval_name + ".pt"))
 
     def post_physics_step(self):
         if not self._fused:
@@ -275,6 +360,7 @@ class RoverTask(RLTask):
             else:
                 self._engine.step(self._sin, self._sout, increment_progress=True, compact=True)
             self._compaction_fresh = True
+            self._eval_dump()
         else:
             self.progress_buf[:] += 1
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
@@ -297,6 +383,7 @@ class RoverTask(RLTask):
         ``device_reset=False`` keeps the reference's control flow (host ``len()`` of the id list, then the methods)."""
         self.global_step += 1
         self.rover_loc = self._rover.get_world_poses()[0]
+        self._eval_name = "rover_eval_no_noise_teacher_rocks_small_area_removedv5"                # :376
         if self.global_step == 10:                                                               # :344-353
             self.curriculum_level = 2
             self._engine.set_curriculum_level(2)

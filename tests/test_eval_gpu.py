@@ -1,0 +1,314 @@
+"""GPU (-m gpu): evaluation mode (rover.py:122-137, 620-641, 670-672) — the device latch of the metrics pass against the reference's
+own evaluation branch (tests/golden/eval_seq_*) and the numpy restatement of tests/eval_helpers.py."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden, scene_for
+from eval_helpers import EVAL_FIXTURES, restate_sequence, restate_step, target_dist
+
+pytestmark = pytest.mark.gpu
+
+NAME = "rover_eval_no_noise_teacher_rocks_small_area_removedv5"
+OUT_KEYS = ("obs_buf", "rew_buf", "reset_buf", "rock_collision", "progress_buf", "done_u8", "reset_ids", "euler", "heading_diff",
+            "ray_dist", "wheel_dist", "body_dist")
+
+
+def _engine(fx, variant, evaluation=True, num_envs=None):
+    from hip_helpers import make_engine
+    scene = scene_for(fx)
+    e = num_envs or fx["out_eval_res"].shape[1]
+    eng = make_engine(scene, (fx["distribution"], fx["sparse_idx"], fx["dense_idx"]), e, variant=variant,
+                      curriculum_level=int(fx["curriculum_level"][0]), num_envs_global=e)
+    if not bool(fx["fp32"]):
+        eng.set_option("ray_precision", 2)
+    if evaluation:
+        eng.set_evaluation(True)
+    return eng
+
+
+def _states(fx, k):
+    return {key[3:]: torch.from_numpy(np.ascontiguousarray(v[k])) for key, v in fx.items() if key.startswith("in_")}
+
+
+def _run_fixture(eng, fx, fused, evaluation=True):
+    from hip_helpers import hip_step
+    e = fx["out_eval_res"].shape[1]
+    res = torch.zeros(e, dtype=torch.int64, device=eng.device)
+    stp = torch.zeros(e, dtype=torch.int64, device=eng.device)
+    outs, codes, steps = [], [], []
+    for k in range(fx["out_eval_res"].shape[0]):
+        eng.set_curriculum_level(int(fx["curriculum_level"][k]))
+        outs.append(hip_step(eng, _states(fx, k), fused=fused))
+        if evaluation:
+            eng.eval_read(res, stp)
+            torch.cuda.synchronize()
+            codes.append(res.cpu().numpy())
+            steps.append(stp.cpu().numpy())
+    return outs, (np.stack(codes) if codes else None), (np.stack(steps) if steps else None)
+
+
+@pytest.mark.parametrize("name", EVAL_FIXTURES)
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("variant", [None, 3])
+def test_eval_codes_match_reference(name, fused, variant):
+    """Per step, the codes equal the reference's rover_eval_res exactly; the latch steps equal the restatement."""
+    fx = load_golden(name)
+    eng = _engine(fx, variant)
+    outs, codes, steps = _run_fixture(eng, fx, fused)
+    np.testing.assert_array_equal(np.stack([o["rock_collision"] for o in outs]), fx["out_rock_collision"])
+    np.testing.assert_array_equal(np.stack([o["progress_buf"] for o in outs]), fx["out_progress_buf"])
+    for k in range(codes.shape[0]):
+        np.testing.assert_array_equal(codes[k], fx["out_eval_res"][k], err_msg=f"step {k}")
+    _, want_steps, _ = restate_sequence(fx)
+    np.testing.assert_array_equal(steps, want_steps)
+    eng.close()
+
+
+@pytest.mark.parametrize("name", EVAL_FIXTURES)
+@pytest.mark.parametrize("fused", [True, False])
+def test_eval_on_changes_no_other_output(name, fused):
+    """Every existing output of the step is bit-identical with evaluation on and off."""
+    fx = load_golden(name)
+    on, off = _engine(fx, 3, evaluation=True), _engine(fx, 3, evaluation=False)
+    a, _, _ = _run_fixture(on, fx, fused)
+    b, _, _ = _run_fixture(off, fx, fused, evaluation=False)
+    for k, (x, y) in enumerate(zip(a, b)):
+        assert set(x) == set(y)
+        for key in x:
+            np.testing.assert_array_equal(x[key], y[key], err_msg=f"step {k}: {key}")
+    for key in OUT_KEYS:
+        assert key in a[0]
+    on.close()
+    off.close()
+
+
+def test_eval_full_size_summary():
+    """65 536 envs, 37 + 26 rays (BASELINE configs[2]), random states moved between steps: the per-env codes equal the restatement
+    applied to the step's own outputs, and summary8 equals bincount / the sums of eval_read."""
+    from hip_helpers import hip_step, make_engine
+    from isaac_rover_amd import synth
+    e = 65536
+    scene = synth.make_scene(n_cells=128, k=24, n_stones=48)
+    eng = make_engine(scene, synth.ray_distribution("37"), e, variant=None)
+    eng.set_evaluation(True)
+    st = synth.make_states(e, 12.8, seed=41)
+    g = torch.Generator().manual_seed(5)
+    drift = 0.2 * (torch.rand(e, 2, generator=g) - 0.5)
+    st["target"][::97, 0:2] = st["pos"][::97, 0:2] + torch.tensor([0.1, 0.05])     # goals
+    st["target"][5::89, 0] += 3.0                                                     # out of area for some
+    code, step = np.zeros(e, np.int64), np.zeros(e, np.int64)
+    dev = eng.device
+    res, stp, summ = (torch.zeros(n, dtype=torch.int64, device=dev) for n in (e, e, 8))
+    for k in range(4):
+        out = hip_step(eng, st, fused=True)
+        code, step = restate_step(code, step, out["rock_collision"], target_dist(st["pos"].numpy(), st["target"].numpy()),
+                                  out["progress_buf"], 2)
+        eng.eval_read(res, stp, summ)
+        torch.cuda.synchronize()
+        r, s, sm = res.cpu().numpy(), stp.cpu().numpy(), summ.cpu().numpy()
+        np.testing.assert_array_equal(r, code, err_msg=f"step {k}")
+        np.testing.assert_array_equal(s, step, err_msg=f"step {k}")
+        np.testing.assert_array_equal(sm[0:4], np.bincount(r, minlength=4))
+        np.testing.assert_array_equal(sm[4:8], [int(s[r == c].sum()) for c in range(4)])
+        st["pos"][:, 0:2] += drift
+        st["progress"] = torch.from_numpy(out["progress_buf"])
+    assert (np.bincount(code, minlength=4) > 0).all(), np.bincount(code, minlength=4)
+    eng.close()
+
+
+def test_eval_clear_and_state_errors():
+    from isaac_rover_amd import _lib
+    fx = load_golden(EVAL_FIXTURES[0])
+    eng = _engine(fx, 3, evaluation=False)
+    h, lib = eng._h, eng.lib
+    buf = torch.zeros(8, dtype=torch.int64, device=eng.device)
+    assert lib.rover_eval_read(h, None, None, _lib._ptr(buf), None) == -2             # ROVER_E_STATE before rover_set_evaluation
+    assert lib.rover_eval_clear(h, None, 0, None) == -2
+    with pytest.raises(_lib.RoverError):
+        eng.eval_read(summary8=buf)
+    eng.set_evaluation(True)
+    _, codes, _ = _run_fixture(eng, fx, True)
+    e = codes.shape[1]
+    ids = torch.tensor([0, 2, 4, 6, 9], dtype=torch.int64, device=eng.device)
+    eng.eval_clear(ids)
+    res, stp = torch.zeros(e, dtype=torch.int64, device=eng.device), torch.zeros(e, dtype=torch.int64, device=eng.device)
+    eng.eval_read(res, stp)
+    torch.cuda.synchronize()
+    want = codes[-1].copy()
+    want[ids.cpu().numpy()] = 0
+    np.testing.assert_array_equal(res.cpu().numpy(), want)
+    assert (stp.cpu().numpy()[ids.cpu().numpy()] == 0).all()
+    # re-armed envs latch again on the next step (the last scripted state: e4 sits at td = 10, e9 on a stone at level 2)
+    from hip_helpers import hip_step
+    hip_step(eng, _states(fx, fx["out_eval_res"].shape[0] - 1))
+    eng.eval_read(res)
+    torch.cuda.synchronize()
+    r = res.cpu().numpy()
+    assert r[4] == 1 and r[9] == 1
+    np.testing.assert_array_equal(np.delete(r, ids.cpu().numpy()), np.delete(want, ids.cpu().numpy()))
+    # bad ids / sizes
+    bad = torch.tensor([e], dtype=torch.int64, device=eng.device)
+    assert lib.rover_eval_clear(h, _lib._ptr(bad), 1, None) == -1
+    assert lib.rover_eval_clear(h, _lib._ptr(ids), e + 1, None) == -1
+    assert lib.rover_eval_clear(h, _lib._ptr(ids), -1, None) == -1
+    eng.eval_clear()
+    eng.eval_read(res, stp)
+    torch.cuda.synchronize()
+    assert not res.any() and not stp.any()
+    eng.set_evaluation(False)
+    assert lib.rover_eval_read(h, None, None, _lib._ptr(buf), None) == -2
+    eng.close()
+
+
+# ---- RoverTask ---------------------------------------------------------------------------------------------------------------
+def _fixture_task(fx, fused, save_dir):
+    from isaac_rover_amd.config import SimConfig
+    from isaac_rover_amd.tasks.rover import RoverTask
+    from isaac_rover_amd.vec_env import VecEnv
+    st = _states(fx, 0)
+    e = st["pos"].shape[0]
+    env = VecEnv(headless=True)
+    task = RoverTask("Rover", SimConfig(num_envs=e, device="cuda:0"), env, scene=scene_for(fx),
+                     distribution=(fx["distribution"], fx["sparse_idx"], fx["dense_idx"]), fused=fused, cell_index_mode="cpu_div",
+                     ray_precision="fp32" if bool(fx["fp32"]) else "fp16_as_shipped", is_evaluation=True, eval_save_dir=save_dir)
+    env.set_task(task, sim_params={"dt": 0.05}, spawn_positions=st["pos"].clone())
+    task._eval_name = NAME            # what the task's first pre_physics_step sets (rover.py:376); the fixture feeds states instead
+    return task, env
+
+
+@pytest.mark.parametrize("name", EVAL_FIXTURES)
+@pytest.mark.parametrize("fused", [True, False])
+def test_task_eval_matches_reference_and_saves(name, fused, tmp_path):
+    """RoverTask(is_evaluation=True) fed the fixture's states step by step: the reference's codes at every step, and at the save step
+    (global_step % 3000 == 0) the reference's two files, names and contents."""
+    fx = load_golden(name)
+    task, env = _fixture_task(fx, fused, str(tmp_path))
+    dev = task.device
+    for k in range(fx["out_eval_res"].shape[0]):
+        st = _states(fx, k)
+        task._rover.feed(st["pos"].to(dev), st["quat"].to(dev), st["joints"].to(dev))
+        task.target_positions.copy_(st["target"].to(dev))
+        task.linear_velocity.tracker.copy_(st["lin_hist"].to(dev))
+        task.angular_velocity.tracker.copy_(st["ang_hist"].to(dev))
+        task.rover_rot.copy_(st["euler_pre"].to(dev))
+        task.progress_buf.copy_(st["progress"].to(dev))
+        task.curriculum_level = int(fx["curriculum_level"][k])
+        task._engine.set_curriculum_level(task.curriculum_level)
+        task.global_step = int(fx["global_step"][k])
+        task.post_physics_step()
+        np.testing.assert_array_equal(task.rover_eval_res.cpu().numpy(), fx["out_eval_res"][k], err_msg=f"step {k}")
+        files = sorted(os.listdir(tmp_path))
+        if k < int(fx["save_step"]):
+            assert files == []
+    assert files == sorted([str(fx["save_name_episode_length"]), str(fx["save_name_eval_res"])])
+    ep = torch.load(os.path.join(tmp_path, str(fx["save_name_episode_length"])))
+    res = torch.load(os.path.join(tmp_path, str(fx["save_name_eval_res"])))
+    assert ep.dtype == torch.int64 and tuple(ep.shape) == fx["save_episode_length"].shape
+    np.testing.assert_array_equal(ep.numpy(), fx["save_episode_length"])
+    np.testing.assert_array_equal(res.numpy(), fx["save_eval_res"])
+    s = task.evaluation_summary()
+    final = fx["out_eval_res"][-1]
+    assert [s["pending"], s["collided"], s["reached_goal"], s["timed_out"]] == np.bincount(final, minlength=4).tolist()
+    assert s["success_rate"] == np.mean(final == 2)
+    env.close()
+
+
+def _drive(task_kw, steps=30, yaw=False, save_dir=None, set_step=None):
+    """A VecEnv run of `steps` steps on the kinematic pose feeder, with goals, out-of-area targets and timeouts scripted in; returns the
+    task's codes after every step (and checks them against the restatement of each step's own outputs)."""
+    from isaac_rover_amd import synth
+    from isaac_rover_amd.config import SimConfig
+    from isaac_rover_amd.vec_env import VecEnv, initialize_task
+    e = 256
+    scene = synth.make_scene(n_cells=128, k=16, n_stones=24)
+    env = VecEnv(headless=True)
+    task = initialize_task(SimConfig(num_envs=e, device="cuda:0"), env, scene, distribution=synth.ray_distribution("37"),
+                           is_evaluation=True, eval_save_dir=save_dir, **task_kw)
+    g = torch.Generator().manual_seed(3)
+    yaws = torch.randint(0, 361, (steps + 1, e), generator=g, dtype=torch.int32).cuda()
+    if yaw:
+        task.reset()                      # every env flagged: the first step below re-spawns them with the given yaws
+    else:
+        env.reset()
+    code = task.rover_eval_res.cpu().numpy()
+    step = task.rover_eval_steps.cpu().numpy()
+    history = []
+    for i in range(steps):
+        actions = (2 * torch.rand(e, 2, generator=g) - 1).cuda()
+        if i == 12:
+            task.progress_buf[::5] = 2997
+        if i == 15:
+            task.target_positions[1::7, 0:2] = task._rover.get_world_poses()[0][1::7, 0:2] + 0.05
+            task.target_positions[3::11, 0] += 10.0
+        if set_step is not None and i == set_step:
+            task.global_step = 2999
+        if yaw:
+            task.pre_physics_step(actions, reset_yaw_deg=yaws[i])
+            env._world.step()
+            task.post_physics_step()
+        else:
+            env.step(actions)
+        pos = task._rover.get_world_poses()[0].cpu().numpy()
+        code, step = restate_step(code, step, task.rock_collison.cpu().numpy(), target_dist(pos, task.target_positions.cpu().numpy()),
+                                  task.progress_buf.cpu().numpy(), task.curriculum_level)
+        got = task.rover_eval_res.cpu().numpy()
+        np.testing.assert_array_equal(got, code, err_msg=f"step {i}")
+        np.testing.assert_array_equal(task.rover_eval_steps.cpu().numpy(), step, err_msg=f"step {i}")
+        history.append(got)
+    assert (np.bincount(history[-1], minlength=4)[1:] > 0).all(), np.bincount(history[-1], minlength=4)
+    return task, env, np.stack(history)
+
+
+def test_task_eval_same_codes_on_every_path():
+    """fused / unfused / graph=True (and a second task with the same seed) on the device-reset path; fused vs device_reset=False with
+    the reset yaws given (the two paths draw their yaws from different generators otherwise)."""
+    runs = {}
+    for label, kw in (("fused", dict(fused=True)), ("fused_again", dict(fused=True)), ("unfused", dict(fused=False)),
+                      ("graph", dict(graph=True))):
+        task, env, h = _drive(kw)
+        if label == "graph":
+            assert task._post_graph is not None          # the latch ran inside the replayed post-physics graph
+        runs[label] = h
+        env.close()
+    for label in ("fused_again", "unfused", "graph"):
+        np.testing.assert_array_equal(runs[label], runs["fused"], err_msg=label)
+    a = _drive(dict(fused=True), yaw=True)
+    b = _drive(dict(fused=False, device_reset=False), yaw=True)
+    np.testing.assert_array_equal(a[2], b[2])
+    for t in (a, b):
+        t[1].close()
+
+
+def test_task_eval_save_dir(tmp_path, monkeypatch):
+    """eval_save_dir: the two files at the step whose global_step % 3000 == 0; no dir: nothing is written anywhere."""
+    monkeypatch.chdir(tmp_path)
+    out = tmp_path / "eval"
+    out.mkdir()
+    task, env, h = _drive(dict(fused=True), steps=16, save_dir=str(out), set_step=14)
+    assert sorted(os.listdir(out)) == sorted([NAME + "episode_length.pt", NAME + ".pt"])
+    res = torch.load(str(out / (NAME + ".pt")))
+    np.testing.assert_array_equal(res.numpy(), h[14])
+    ep = torch.load(str(out / (NAME + "episode_length.pt")))
+    assert ep.dim() == 2 and ep.shape[1] == 1 and ep.shape[0] == int((h[14] == 2).sum())
+    env.close()
+    task2, env2, _ = _drive(dict(fused=True), steps=16, set_step=14)
+    assert sorted(os.listdir(tmp_path)) == ["eval"]
+    env2.close()
+
+
+def test_task_eval_flag_is_fixed():
+    from isaac_rover_amd import synth
+    from isaac_rover_amd.config import SimConfig
+    from isaac_rover_amd.vec_env import VecEnv, initialize_task
+    env = VecEnv(headless=True)
+    task = initialize_task(SimConfig(num_envs=64, device="cuda:0"), env, synth.make_scene(n_cells=64, k=16, n_stones=8),
+                           distribution=synth.ray_distribution("9"))
+    assert task.is_evaluation is False
+    with pytest.raises(AttributeError):
+        task.is_evaluation = True
+    with pytest.raises(AttributeError):
+        task.rover_eval_res
+    env.close()
