@@ -72,6 +72,25 @@ struct MapTables {
     }
 };
 
+// The ray cast of a step, decided in one place (plan_raycast) from the maps, the distribution, the options and the ROVER_* knobs read at
+// rover_create.  replan() recomputes it whenever one of them changes; steps, replays and reports read it and derive nothing themselves.
+struct RayPlan {
+    int variant = 0;                    // 0: a map is missing; 1 env-order kernel, 2 binned, 3 culled, 4 staged
+    int proof = 0;                      // the ProofTables in force: 1 for the as-shipped fp16 arithmetic (ray_precision 2), else 0
+    bool sorted = false;                // the bucket sort by (map, cell) runs before the ray cast
+    bool env_order = false;             // variant 4 over the ray slots in env order, one launch
+    bool rocks_staged = false;          // variant 4: the rocks part through the staged kernel too (else the culled kernel casts it)
+    uint32_t run = 0;                   // rays per wave of the sorted launches
+    uint32_t env_run = 0;               // slots per wave of the staged kernel in env order
+    bool lazy_far = false;              // culled kernel: a bin's far records fetched only when a ray needs them
+    bool skip_clear = false;            // culled kernel: rays that clear their whole cell left out of the scan
+    bool operator==(const RayPlan& o) const {
+        return variant == o.variant && proof == o.proof && sorted == o.sorted && env_order == o.env_order && rocks_staged == o.rocks_staged &&
+               run == o.run && env_run == o.env_run && lazy_far == o.lazy_far && skip_clear == o.skip_clear;
+    }
+    bool operator!=(const RayPlan& o) const { return !(*this == o); }
+};
+
 struct rover_ctx {
     rover_cfg cfg{};
     std::string err;
@@ -84,13 +103,13 @@ struct rover_ctx {
     uint64_t cull_entries = 0;
     DevBuf<uint4> d_cull_stats;         // per-wave counters of the last culled launch (rover_get_cull_info)
     uint32_t cull_stat_slots = 0;
-    uint64_t stats_sig = 0;             // how the last launch that wrote the counters cast its rays (run_raycast)
+    RayPlan queue_plan{};               // the plan the queue and counters were sized for (alloc_cull_queue)
+    RayPlan stats_plan{};               // the plan the counters were last written under (run_raycast)
     double cull_eta_h = 0.08;           // free parameter of the fp16 proof (rover_cull.hip, cull_proof_h); ROVER_CULLH_ETA for experiments
     double cull_split_h = 8.0;          // how test (A)'s cross term is split between its |h|^2 and rho^2 parts (cull_proof_h); ROVER_CULLH_SPLIT
     uint64_t cull_budget = 1536ull << 20;  // option "cull_queue_mb": most bytes the queue may take (a step is cast in several launches beyond it)
     uint32_t cull_launches = 1;
     int cull_lazy = -1;                 // ROVER_CULL_LAZY: -1 auto, 0 / 1 force (experiments)
-    uint32_t cull_run = 0;              // run length the queue was sized for
     // distribution
     DevBuf<double> d_dist;          // [P][3]
     DevBuf<int32_t> d_obs_idx;      // [Ns+Nd]
@@ -128,10 +147,10 @@ struct rover_ctx {
     bool defer_obs = false, obs_pending = false;   // rover_step: assemble_obs waits for do_metrics and shares its launch
     ObsArgs pending_obs{};
     uint32_t n_bins = 0;
-    int variant = 0;                    // 0 = auto
-    int last_variant = 1;
-    bool sorted_valid = false;
-    uint32_t run = 0;                   // option "raycast_run": 0 = auto (effective_run)
+    int variant = 0;                    // option "raycast_variant": 0 = auto (plan_raycast)
+    uint32_t run = 0;                   // option "raycast_run": 0 = auto (plan_run)
+    RayPlan plan{};                     // the ray cast in force (replan)
+    RayPlan ws_plan{};                  // the plan the ray workspace was produced with (cast_rays): the sorted list, rover_get_cull_info
     uint32_t early_out = 1;             // option "raycast_early_out": conservative whole-pair rejection (bit-identical results)
     int32_t cell_rcp = 0;               // option "cell_index_mode": 0 cpu_div (x / 0.1), 1 cuda_rcp (x * (1 / 0.1))
     DevBuf<float> d_mlp_scratch;        // partial sums of the split-k small-batch encoder path (rover_mlp_chain_forward)
@@ -220,18 +239,23 @@ static int proof_in_force(const rover_ctx* c) { return c->precision == 2 ? 1 : 0
 #define ROVER_AUTO_CULL_RAYS_F32 49152u
 #define ROVER_AUTO_CULL_RAYS_F16 24576u
 // The staged ray cast: from 24 576 rays (f32 arithmetic), in env order — no sort — while a terrain cell holds fewer than 1.5 heightmap rays
-// and 48 cells or more hold one rover (lane_env_order).  Whole step, M env-steps/s, 37 + 26 rays, one call (tools/sweep_small.sh,
+// and 48 cells or more hold one rover (plan_env_order).  Whole step, M env-steps/s, 37 + 26 rays, one call (tools/sweep_small.sh,
 // profiles/r05_final_sweep.log), env-order kernel / culled / staged behind the sort / staged in env order: 512 envs 11.4 / 10.5 / 8.2 / 17.0,
 // 1 024: 14.7 / 17.6 / 15.4 / 29.3, 2 048: 17.4 / 27.3 / 26.5 / 37.7, 4 096: 18.3 / 39.9 / 41.1 / 49.1, 8 192: 18.9 / 54.9 / 59.2 / 57.7,
 // 16 384: 19.2 / 72.2 / 79.7 / 66.9, 32 768: 19.3 / 98.4 / 113.6 / 71.1, 65 536: 19.2 / 121.7 / 142.1 / 73.5; 120 + 26 rays at 4 096 envs
 // 8.4 / 26.1 / 30.8 / 35.0, at 65 536 envs 8.5 / 56.2 / 69.9 / 45.4.
 #define ROVER_AUTO_LANE_RAYS 24576u
-#define ROVER_AUTO_LANE_ENV_RAYS_F16 98304u   // as shipped: below this many rays the staged kernel in env order (lane_env_order) is ahead of the culled one
+#define ROVER_AUTO_LANE_ENV_RAYS_F16 98304u   // as shipped: below this many rays the staged kernel in env order (plan_env_order) is ahead of the culled one
 static bool lane_tables_ok(const rover_ctx* c) {
     const int k = proof_in_force(c);
     return c->maps[0].proof[k].lrec.get() && c->maps[1].proof[k].lrec.get();
 }
-static int effective_variant(const rover_ctx* c) {
+// raycast_variant 4 asked for by name cannot run: the staged kernel's tables of the arithmetic in force are not there (K > 256 on a map is the
+// documented exception: every variant then runs as the streaming kernel 1, and rover_get_info says so).  rover_set_option and check_precision.
+static bool staged_tables_missing(const rover_ctx* c) {
+    return have_maps(c) && c->maps[0].knn.K8 <= 256 && c->maps[1].knn.K8 <= 256 && !lane_tables_ok(c);
+}
+static int plan_variant(const rover_ctx* c) {
     const bool v2_ok = c->maps[0].knn.K8 <= 256 && c->maps[1].knn.K8 <= 256;      // 64 lanes x 4 triangles
     if (c->variant == 1 || !v2_ok) return 1;
     const bool v4_ok = lane_tables_ok(c);     // the staged kernel's tables of the proof in force, on both maps
@@ -267,7 +291,7 @@ static int effective_variant(const rover_ctx* c) {
 // Sorted rays per wave.  Long runs amortise a cell's set-up (65 536 envs, ray cast only: run 12 -> 1.183 ms, 16 -> 1.171,
 // 24 -> 1.153, 32 -> 1.144, 64 -> 1.150); small batches need more, shorter waves to fill 256 CUs (4 096 envs: run 4 ->
 // 0.2145 ms per step, run 16 -> 0.2264 ms).
-static uint32_t effective_run(const rover_ctx* c) {
+static uint32_t plan_run(const rover_ctx* c, int variant) {
     if (c->run) return c->run;
     const uint64_t r = valid_rays(c) / 65536u;
     // the culled ray cast (round 3, one call each: 4 096 envs run 4 / 8 / 16 / 32 -> 0.155 / 0.151 / 0.161 / 0.173 ms per step;
@@ -284,8 +308,8 @@ static uint32_t effective_run(const rover_ctx* c) {
     // the staged kernel behind the sort wants long runs — a chunk read is shared by the run's rays that test it, a round is fuller —
     // (whole step, M env-steps/s, runs of 16 / 32 / 64: 8 192 envs 54.5 / 57.6 / 56.0; 16 384: 68.5 / 77.0 / 79.3; 32 768: 82.8 / 98.1 / 110.5;
     //  65 536: 91.9 / 111.8 / 133.0; 120 + 26 rays 38.5 / 53.9 / 65.0; irregular mesh 67.8 / 92.4 / 104.7)
-    if (effective_variant(c) == 4) return r < 12 ? 32u : 64u;
-    if (effective_variant(c) >= 3) {
+    if (variant == 4) return r < 12 ? 32u : 64u;
+    if (variant >= 3) {
         const bool quick_rays = c->precision != 2 && 2 * c->maps[0].farok >= c->maps[0].cells;      // regular mesh (most cells have a far bound), f32 arithmetic
         if (quick_rays) return r < 3 ? 8u : (r < 6 ? 16u : (r < 20 ? 32u : 64u));                   // powers of two: 63 instead of 64 cost 6 %
         return r < 12 ? 8u : (r < 24 ? 16u : (r < 48 ? 32u : 64u));
@@ -293,9 +317,66 @@ static uint32_t effective_run(const rover_ctx* c) {
     return (uint32_t)(r < 4 ? 4 : (r > 32 ? 32 : r));
 }
 
-static uint32_t bucket_count(const rover_ctx* c) { return (c->n_bins + (1u << c->low_bits) - 1u) >> c->low_bits; }
+// The staged ray cast needs no bins: where a (map, cell) bin holds a ray or none — small and mid-size batches — the sort's three launches
+// (18 us) buy it nothing and it walks the ray slots in env order (a run = 64 consecutive slots: a rover's 37 heightmap rays still share cells).
+// Measured (MI355X, 37 + 26 rays, whole step, one call per size): see ROVER_AUTO_ENVORDER_* below.
+static bool plan_env_order(const rover_ctx* c, int variant) {
+    if (variant != 4) return false;
+    if (c->lane_env_order >= 0) return c->lane_env_order != 0;
+    // what decides is the heightmap rays per terrain cell (rovers spread over the map): below ~1.5 the sort buys no sharing (4 096 envs x 120
+    // rays: 1.37, env order 35.3 against 30.9 M env-steps/s behind the sort; 16 384 x 37: 1.68, 67.1 / 80.1) — and the rovers per cell: from one per
+    // 48 cells a cell's rays come from several rovers and only the sort brings them together (8 192 x 37: 57.8 / 59.3; 4 096 x 37: 49.2 / 41.1)
+    // (round 6, the rocks part in the staged launch too: behind the sort / env order 4 096 envs 48.9 / 49.9, 8 192 envs 68.6 / 58.3, 120 + 26 rays at
+    //  4 096 envs 35.3 / 36.4 — the sort pays from one rover per ~64 cells)
+    // (as shipped the staged kernel is the auto choice for small batches in env order and for dense ray sets behind the sort: plan_variant)
+    if (c->precision == 2) return c->have_dist && valid_rays(c) < ROVER_AUTO_LANE_ENV_RAYS_F16;
+    return c->have_dist && 2ull * (uint64_t)c->cfg.num_envs * (uint64_t)c->P < 3ull * (uint64_t)c->maps[0].cells &&
+           64ull * (uint64_t)c->cfg.num_envs < (uint64_t)c->maps[0].cells;
+}
 
-static int alloc_cull_queue(rover_ctx* c);
+// The whole decision, for the inputs in force
+static RayPlan plan_raycast(const rover_ctx* c) {
+    RayPlan p{};
+    p.proof = proof_in_force(c);
+    // few rays per (map, cell) bin: most bins have no ray that tests the far pairs, and setting them up lazily halves a bin's set-up
+    // (32 768 envs x 63 rays 69.7 -> 76 M env-steps/s, 4 096 envs 26.9 -> 30 M; with 146 rays per env a bin holds 14 rays, nearly every
+    // bin needs its far pairs and the second, dependent gather costs 3 %: eager there)
+    // The kernel that fetches a bin's far records only when a ray needs them pays where most bins skip them: small ray sets (few rays
+    // per bin) on a terrain map whose cells mostly have a useful far bound (a regular grid: all of them; an irregular mesh with
+    // triangles that span many cells: few — there the second, dependent round of gathers cost 3 %).
+    // (round 4: what decides is the rays per bin, not the size of the ray set — 120 + 26 rays at 16 384 / 4 096 envs hold 5.8 / 2.1 rays per
+    //  bin and gain 2.8 / 3.7 % from the on-demand kernel; the estimate is heightmap rays per terrain cell for rovers spread over the map.
+    //  The native 1 634-point set is dense — 3.2 rays per bin already at 512 envs — and keeps the eager kernel: -1 ... -5 % otherwise.)
+    const bool few_per_bin = c->P <= 260 && (uint64_t)c->cfg.num_envs * (uint64_t)c->P < 8ull * (uint64_t)c->maps[0].cells;
+    const bool lazy_auto = (26 + c->P < 100 || few_per_bin) && 2 * c->maps[0].farok >= c->maps[0].cells;
+    p.lazy_far = c->cull_lazy < 0 ? lazy_auto : c->cull_lazy != 0;
+    // rays that clear their whole cell are left out of the scan where some do: a mesh whose cells mostly have a usable bound, and rock
+    // rays (the ones that qualify) at least a tenth of the ray set (120 + 26 rays: 12 % of the rays, +3.8 %; the native 1 634 + 26: none)
+    p.skip_clear = 2 * c->maps[0].farok >= c->maps[0].cells && 26 + c->P <= 260;
+    // The as-shipped fp16 arithmetic takes the same two choices since round 4 (its proof's group bound holds less often — 39 % of the rays
+    // skip the far pairs, 13 % are not scanned at all, against 84 % / 25 % — but what holds is free: 65 536 envs 85.4 -> 88.3 M
+    // env-steps/s, 16 384 envs 50.0 -> 53.3 M, alternating in one call); without the whole-cell skip its kernel stays the eager one.
+    if (p.proof && !p.skip_clear) p.lazy_far = false;
+    if (!have_maps(c)) return p;
+    p.variant = plan_variant(c);
+    p.env_order = plan_env_order(c, p.variant);
+    p.sorted = p.variant >= 2 && !p.env_order;
+    // variant 4 behind the sort: the rocks part of the sorted list through the staged kernel too?  Yes (lane_rocks -1, auto), since round 6, in either
+    // arithmetic: f32 — 4-byte test-(B) records, one launch 0.31 ms against 0.23 + 0.14; as shipped 91.0 against 87.2 M env-steps/s (and 96.9 with the
+    // round's proof constants).  In env order the one launch casts every slot.
+    p.rocks_staged = p.variant == 4 && (p.env_order || c->lane_rocks != 0);
+    p.run = plan_run(c, p.variant);
+    // slots per wave: enough waves to fill 1 024 SIMDs (4 096 envs x 64 slots in runs of 64 are one wave per SIMD).  Whole step, M
+    // env-steps/s, runs of 8 / 16 / 32 / 64: 512 envs 15.0 / 16.3 / 14.9 / 12.7; 1 024: 21.2 / 26.7 / 26.3 / 22.1; 2 048: 27.5 / 35.3 / 37.1 /
+    // 36.6; 4 096: - / 45.0 / 49.8 / 47.2; 8 192: - / 52.6 / 60.1 / 59.2; 120 + 26 rays at 4 096 envs: 19.9 / - / 35.5 / 33.2
+    if (p.env_order) {
+        const uint64_t slots = (uint64_t)c->cfg.num_envs * c->R8;
+        p.env_run = c->run ? (c->run > 64u ? 64u : c->run) : (slots >= (1ull << 20) ? 64u : (slots >= (1ull << 17) ? 32u : 16u));
+    }
+    return p;
+}
+
+static uint32_t bucket_count(const rover_ctx* c) { return (c->n_bins + (1u << c->low_bits) - 1u) >> c->low_bits; }
 
 static int alloc_bins(rover_ctx* c) {
     c->bins_ok = false;
@@ -324,31 +405,39 @@ static int alloc_bins(rover_ctx* c) {
         c->bkt_table_dirty = false;
         c->bins_ok = true;
     }
-    return alloc_cull_queue(c);       // sized here, not in the step: hipMalloc is not allowed while a stream is capturing
+    return ROVER_OK;
 }
 
-// candidate queue of the culled ray cast (one bounded region per resident wave) + its per-wave counters, for the options in force
-static int alloc_cull_queue(rover_ctx* c) {
-    if (!c->ws_ok || !c->have_dist || !have_maps(c) || effective_variant(c) < 3) return ROVER_OK;
-    const uint32_t run = effective_run(c);
-    const uint64_t entries = cull_queue_entries(valid_rays(c), (uint32_t)c->cfg.num_envs * (uint32_t)c->P, run, c->cull_budget, &c->cull_launches);
+// candidate queue of the culled ray cast (one bounded region per resident wave) + its per-wave counters, for plan p
+static int alloc_cull_queue(rover_ctx* c, const RayPlan& p) {
+    if (!c->ws_ok || !c->have_dist || p.variant < 3) return ROVER_OK;
+    const uint64_t entries = cull_queue_entries(valid_rays(c), (uint32_t)c->cfg.num_envs * (uint32_t)c->P, p.run, c->cull_budget, &c->cull_launches);
     // (the per-wave counters are sized by the RAY count, the queue — once capped by the budget — is not: a second
     //  rover_set_distribution with more rays must grow the counters even when the queue keeps its size)
-    // (by the PADDED slot count: in env order the staged kernel walks every slot of every env, and its runs are never shorter than `run`)
-    const uint32_t slots = rover::cull_stat_slots((uint64_t)c->cfg.num_envs * c->R8, run < 16u ? run : 16u);
-    if (c->d_cull_queue.get() && c->d_cull_stats.get() && entries == c->cull_entries && run == c->cull_run && slots == c->cull_stat_slots) return ROVER_OK;
+    // (by the PADDED slot count: in env order the staged kernel walks every slot of every env)
+    const uint32_t slots = rover::cull_stat_slots((uint64_t)c->cfg.num_envs * c->R8, p.env_order ? p.env_run : p.run);
+    c->queue_plan = p;
+    if (c->d_cull_queue.get() && c->d_cull_stats.get() && entries == c->cull_entries && slots == c->cull_stat_slots) return ROVER_OK;
     c->d_cull_queue.reset(); c->d_cull_stats.reset();
     c->cull_stat_slots = 0;
     c->cull_entries = 0;
     // no fallback to another kernel: a queue that cannot be allocated is an error the caller sees
     if (hipError_t e = c->d_cull_queue.alloc(entries))
         return fail(c, ROVER_E_NOMEM, "culled ray cast: candidate queue of %llu bytes: %s", (unsigned long long)(entries * sizeof(uint2)), hipGetErrorString(e));
-    c->cull_entries = entries; c->cull_run = run;
+    c->cull_entries = entries;
     HIP_TRY(c, c->d_cull_stats.alloc(slots));
     c->cull_stat_slots = slots;
-    c->stats_sig = 0;
+    c->stats_plan = RayPlan{};
     HIP_TRY(c, hipMemset(c->d_cull_stats.get(), 0, c->d_cull_stats.bytes()));
     return ROVER_OK;
+}
+
+// Every change of a plan input, and of what sizes the queue, ends here: the plan, then the queue and counters sized for it — here, never in
+// a step (hipMalloc is not allowed while a stream is capturing).  r: the caller's own result; after an error the plan is still brought up
+// to date (rover_get_info reports it), and the queue is left as it is.
+static int replan(rover_ctx* c, int r = ROVER_OK) {
+    c->plan = plan_raycast(c);
+    return r ? r : alloc_cull_queue(c, c->plan);
 }
 
 static int alloc_workspace(rover_ctx* c) {
@@ -515,7 +604,7 @@ static int build_map_tables(rover_ctx* c, MapTables& m, const int32_t* map_idx, 
         (e = d_cnt.alloc(8)) != hipSuccess || (e = d_order.alloc(T_int)) != hipSuccess || (e = d_newid.alloc(T)) != hipSuccess)
         return fail(c, ROVER_E_HIP, "set_knn_map: cull tables: %s", hipGetErrorString(e));
     // The staged kernel's tables are optional, each proof's on its own: which proofs get them is the "staged_tables" option, and an allocation
-    // that fails drops that proof's (the culled kernel then runs for it, effective_variant) — unless variant 4 was asked for by name.
+    // that fails drops that proof's (the culled kernel then runs for it, plan_variant) — unless variant 4 was asked for by name.
     for (int k = 0; k < 2; ++k) {
         if (!((c->staged_tables >> k) & 1)) continue;
         ProofTables& p = m.proof[k];
@@ -580,6 +669,7 @@ int rover_create(const rover_cfg* cfg, rover_ctx** out) {
     if (const char* v = getenv("ROVER_CULL_QUEUE_MB")) { const long mb = atol(v); if (mb >= 1) c->cull_budget = (uint64_t)mb << 20; }
     if (const char* v = getenv("ROVER_BIN_LOW_BITS")) { int b = atoi(v); if (b >= 8 && b <= 12) c->low_bits_opt = (uint32_t)b; }
     if (const char* v = getenv("ROVER_RAYCAST_RUN")) { int r = atoi(v); if (r >= 1 && r <= 4096) c->run = (uint32_t)r; }
+    (void)replan(c);                 // (no maps, no distribution yet: nothing to size)
     DeviceGuard guard(cfg->device);
     e = guard.err;
     if (e == hipSuccess) e = c->d_block_cnt.alloc((size_t)cfg->num_envs / 256 + 2);
@@ -611,7 +701,7 @@ int rover_set_knn_map(rover_ctx* c, int which, const int32_t* map_idx, int32_t X
     if (int r = build_map_tables(c, m, map_idx, X, Y, K, tris, T, verts, V, cell, shift_x, shift_y)) return r;      // (the previous map stays)
     c->maps[which] = std::move(m);
     c->rays_valid = false;
-    return alloc_bins(c);
+    return replan(c, alloc_bins(c));
 }
 
 int rover_set_distribution(rover_ctx* c, const double* pts, int32_t P, const int64_t* sparse_idx, int32_t Ns,
@@ -633,14 +723,17 @@ int rover_set_distribution(rover_ctx* c, const double* pts, int32_t P, const int
         if (v < 0 || v >= P) return fail(c, ROVER_E_INVALID, "set_distribution: index %d outside [0,%d)", v, P);
     c->have_dist = false;
     c->d_dist.reset(); c->d_obs_idx.reset();
-    HIP_TRY(c, c->d_dist.alloc(hp.size()));
-    HIP_TRY(c, hipMemcpy(c->d_dist.get(), hp.data(), c->d_dist.bytes(), hipMemcpyHostToDevice));
-    HIP_TRY(c, c->d_obs_idx.alloc(idx.size() + 1));
-    HIP_TRY(c, hipMemset(c->d_obs_idx.get(), 0, c->d_obs_idx.bytes()));      // assemble_obs_kernel reads entry 0 from every lane
-    if (!idx.empty()) HIP_TRY(c, hipMemcpy(c->d_obs_idx.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    c->P = P; c->Ns = Ns; c->Nd = Nd;
-    c->have_dist = true;
-    return alloc_workspace(c);
+    const int r = [&]() -> int {
+        HIP_TRY(c, c->d_dist.alloc(hp.size()));
+        HIP_TRY(c, hipMemcpy(c->d_dist.get(), hp.data(), c->d_dist.bytes(), hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_obs_idx.alloc(idx.size() + 1));
+        HIP_TRY(c, hipMemset(c->d_obs_idx.get(), 0, c->d_obs_idx.bytes()));      // assemble_obs_kernel reads entry 0 from every lane
+        if (!idx.empty()) HIP_TRY(c, hipMemcpy(c->d_obs_idx.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        c->P = P; c->Ns = Ns; c->Nd = Nd;
+        c->have_dist = true;
+        return alloc_workspace(c);
+    }();
+    return replan(c, r);         // (a failure half way leaves no distribution: the plan says so too)
 }
 
 int rover_set_heightfield(rover_ctx* c, const float* hm, int32_t N0, int32_t N1, float hscale, float vscale, float sx, float sy) {
@@ -724,14 +817,11 @@ int rover_set_curriculum_level(rover_ctx* c, int32_t level) {
 }
 
 // ---- step ------------------------------------------------------------------------------------------
-static int check_ready(rover_ctx* c);
-static int effective_variant(const rover_ctx* c);
 static int check_precision(rover_ctx* c) {
-    if (c->precision == 2 && effective_variant(c) < 2)
+    if (c->precision == 2 && c->plan.variant < 2)
         return fail(c, ROVER_E_STATE, "ray_precision 2 (as shipped, fp16 maths) needs ray-cast variant 2 or 3 (K <= 256 on both maps)");
     // a variant asked for by name is the one that runs, or the call fails: the staged kernel needs the tables of the arithmetic in force
-    // (K > 256 on a map is the documented exception: every variant then runs as the streaming kernel 1, and rover_get_info says so)
-    if (c->variant == 4 && c->maps[0].knn.K8 <= 256 && c->maps[1].knn.K8 <= 256 && !lane_tables_ok(c))
+    if (c->variant == 4 && staged_tables_missing(c))
         return fail(c, ROVER_E_STATE, "raycast_variant 4 (staged) was requested but its tables for ray_precision %d are not there (option "
                                       "staged_tables, or they did not fit when the maps were set)", c->precision);
     return ROVER_OK;
@@ -744,43 +834,25 @@ static int check_ready(rover_ctx* c) {
     return check_precision(c);
 }
 
-static CullArgs cull_args(const rover_ctx* c, uint32_t n_valid) {
+static CullArgs cull_args(const rover_ctx* c, const RayPlan& p, uint32_t n_valid) {
     CullArgs a{};
     a.rays = c->d_rays.get(); a.sorted = c->d_sorted.get(); a.n_sorted = n_valid;
     a.n_terrain = (uint32_t)c->cfg.num_envs * (uint32_t)c->P;
-    const bool h = c->precision == 2;     // the as-shipped fp16 arithmetic: its own proof tables, the fp16 exact phase
     const MapTables &m0 = c->maps[0], &m1 = c->maps[1];
-    const int k = proof_in_force(c);
+    const int k = p.proof;                // the as-shipped fp16 arithmetic: its own proof tables, the fp16 exact phase
     a.idx0 = m0.cull_idx.get(); a.idx1 = m1.cull_idx.get();
     a.ctab0 = m0.proof[k].ctab.get(); a.ctab1 = m1.proof[k].ctab.get();
     a.rtab0 = m0.rtab.get(); a.rtab1 = m1.rtab.get();
-    a.half = h ? 1 : 0;
+    a.half = k;
     const CullProofH ph = cull_proof_h(c->cull_eta_h, c->cull_split_h);
     a.c_a_h = ph.c_a; a.tau2_h = ph.tau2;
     a.far0 = m0.proof[k].far.get(); a.far1 = m1.proof[k].far.get();
     a.near0 = a.far0 + 2ull * (uint64_t)m0.cells; a.near1 = a.far1 + 2ull * (uint64_t)m1.cells;
     a.k2_far = cull_far_k2(a.half, ph);
-    // few rays per (map, cell) bin: most bins have no ray that tests the far pairs, and setting them up lazily halves a bin's set-up
-    // (32 768 envs x 63 rays 69.7 -> 76 M env-steps/s, 4 096 envs 26.9 -> 30 M; with 146 rays per env a bin holds 14 rays, nearly every
-    // bin needs its far pairs and the second, dependent gather costs 3 %: eager there)
-    // The kernel that fetches a bin's far records only when a ray needs them pays where most bins skip them: small ray sets (few rays
-    // per bin) on a terrain map whose cells mostly have a useful far bound (a regular grid: all of them; an irregular mesh with
-    // triangles that span many cells: few — there the second, dependent round of gathers cost 3 %).
-    // (round 4: what decides is the rays per bin, not the size of the ray set — 120 + 26 rays at 16 384 / 4 096 envs hold 5.8 / 2.1 rays per
-    //  bin and gain 2.8 / 3.7 % from the on-demand kernel; the estimate is heightmap rays per terrain cell for rovers spread over the map.
-    //  The native 1 634-point set is dense — 3.2 rays per bin already at 512 envs — and keeps the eager kernel: -1 ... -5 % otherwise.)
-    const bool few_per_bin = c->P <= 260 && (uint64_t)c->cfg.num_envs * (uint64_t)c->P < 8ull * (uint64_t)c->maps[0].cells;
-    const bool lazy_auto = (26 + c->P < 100 || few_per_bin) && 2 * c->maps[0].farok >= c->maps[0].cells;
-    a.lazy_far = (c->cull_lazy < 0 ? lazy_auto : c->cull_lazy != 0) ? 1 : 0;
-    // rays that clear their whole cell are left out of the scan where some do: a mesh whose cells mostly have a usable bound, and rock
-    // rays (the ones that qualify) at least a tenth of the ray set (120 + 26 rays: 12 % of the rays, +3.8 %; the native 1 634 + 26: none)
-    a.skip_clear = (2 * c->maps[0].farok >= c->maps[0].cells && 26 + c->P <= 260) ? 1 : 0;
-    // The as-shipped fp16 arithmetic takes the same two choices since round 4 (its proof's group bound holds less often — 39 % of the rays
-    // skip the far pairs, 13 % are not scanned at all, against 84 % / 25 % — but what holds is free: 65 536 envs 85.4 -> 88.3 M
-    // env-steps/s, 16 384 envs 50.0 -> 53.3 M, alternating in one call); without the whole-cell skip its kernel stays the eager one.
-    if (h && !a.skip_clear) a.lazy_far = 0;
+    a.lazy_far = p.lazy_far ? 1 : 0;
+    a.skip_clear = p.skip_clear ? 1 : 0;
     a.kp0 = (uint32_t)c->maps[0].knn.K8; a.kp1 = (uint32_t)c->maps[1].knn.K8;
-    a.run = effective_run(c);
+    a.run = p.run;
     a.out = c->d_dist_out.get();
     a.queue = c->d_cull_queue.get();
     a.stats = c->d_cull_stats.get();
@@ -788,59 +860,36 @@ static CullArgs cull_args(const rover_ctx* c, uint32_t n_valid) {
     return a;
 }
 
-// The staged ray cast needs no bins: where a (map, cell) bin holds a ray or none — small and mid-size batches — the sort's three launches
-// (18 us) buy it nothing and it walks the ray slots in env order (a run = 64 consecutive slots: a rover's 37 heightmap rays still share cells).
-// Measured (MI355X, 37 + 26 rays, whole step, one call per size): see ROVER_AUTO_ENVORDER_* below.
-static bool lane_env_order(const rover_ctx* c, int variant) {
-    if (variant != 4) return false;
-    if (c->lane_env_order >= 0) return c->lane_env_order != 0;
-    // what decides is the heightmap rays per terrain cell (rovers spread over the map): below ~1.5 the sort buys no sharing (4 096 envs x 120
-    // rays: 1.37, env order 35.3 against 30.9 M env-steps/s behind the sort; 16 384 x 37: 1.68, 67.1 / 80.1) — and the rovers per cell: from one per
-    // 48 cells a cell's rays come from several rovers and only the sort brings them together (8 192 x 37: 57.8 / 59.3; 4 096 x 37: 49.2 / 41.1)
-    // (round 6, the rocks part in the staged launch too: behind the sort / env order 4 096 envs 48.9 / 49.9, 8 192 envs 68.6 / 58.3, 120 + 26 rays at
-    //  4 096 envs 35.3 / 36.4 — the sort pays from one rover per ~64 cells)
-    // (as shipped the staged kernel is the auto choice for small batches in env order and for dense ray sets behind the sort: effective_variant)
-    if (c->precision == 2) return c->have_dist && valid_rays(c) < ROVER_AUTO_LANE_ENV_RAYS_F16;
-    return c->have_dist && 2ull * (uint64_t)c->cfg.num_envs * (uint64_t)c->P < 3ull * (uint64_t)c->maps[0].cells &&
-           64ull * (uint64_t)c->cfg.num_envs < (uint64_t)c->maps[0].cells;
+// the culled / staged ray cast's candidate queue and counters were sized for plan p (replan; never in a step: no hipMalloc inside a stream capture)
+static int check_queue(rover_ctx* c, const RayPlan& p) {
+    if (p.variant >= 3 && (!c->d_cull_queue.get() || !c->d_cull_stats.get() || c->queue_plan != p))
+        return fail(c, ROVER_E_STATE, "the culled ray cast's candidate queue is not allocated for the options in force");
+    return ROVER_OK;
 }
 
-// variant 4 behind the sort: the rocks part of the sorted list through the staged kernel too?  Yes, since round 6, in either arithmetic: f32 — 4-byte
-// test-(B) records, one launch 0.31 ms against 0.23 + 0.14; as shipped 91.0 against 87.2 M env-steps/s (and 96.9 with the round's proof constants).
-static bool lane_rocks_too(const rover_ctx* c) { return c->lane_rocks < 0 ? true : c->lane_rocks != 0; }
-
-// the ray-cast launch(es) of a step for the variant in force, on the ray records / sorted list in the workspace
-static int run_raycast(rover_ctx* c, int variant, uint32_t n_valid, hipStream_t s) {
+// the ray-cast launch(es) of plan p, on the ray records / sorted list in the workspace
+static int run_raycast(rover_ctx* c, const RayPlan& p, uint32_t n_valid, hipStream_t s) {
     const uint32_t E = (uint32_t)c->cfg.num_envs;
-    if (variant >= 3 && c->d_cull_stats.get()) {
+    if (p.variant >= 3 && c->d_cull_stats.get() && p != c->stats_plan) {
         // the per-wave counters of rover_get_cull_info: a launch writes the slots of its own waves; when the way the rays are cast changed
         // since the last launch (another kernel, order or run length: another number of waves) the slots are cleared first
-        const uint64_t sig = (uint64_t)variant | ((uint64_t)lane_env_order(c, variant) << 8) | ((uint64_t)lane_rocks_too(c) << 9) | ((uint64_t)effective_run(c) << 16) |
-                             ((uint64_t)c->precision << 32);
-        if (sig != c->stats_sig) {
-            HIP_TRY(c, hipMemsetAsync(c->d_cull_stats.get(), 0, c->d_cull_stats.bytes(), s));
-            c->stats_sig = sig;
-        }
+        HIP_TRY(c, hipMemsetAsync(c->d_cull_stats.get(), 0, c->d_cull_stats.bytes(), s));
+        c->stats_plan = p;
     }
-    if (variant == 4) {
+    if (p.variant == 4) {
         LaneArgs l{};
         l.rays = c->d_rays.get(); l.sorted = c->d_sorted.get(); l.n_sorted = n_valid; l.n_terrain = E * (uint32_t)c->P;
-        const bool lh = c->precision == 2;
         for (int w = 0; w < 2; ++w) {
-            const LaneTables t = c->maps[w].proof[proof_in_force(c)].view();
+            const LaneTables t = c->maps[w].proof[p.proof].view();
             l.lvl[w] = t.lvl; l.lrec[w] = t.lrec; l.lid[w] = t.lid; l.rtab[w] = c->maps[w].rtab.get(); l.pp[w] = c->maps[w].lane_pp;
         }
         {
             const CullProofH ph = cull_proof_h(c->cull_eta_h, c->cull_split_h);
-            l.half = lh ? 1 : 0; l.c_a_h = ph.c_a; l.k2_far = cull_far_k2(l.half, ph);
+            l.half = p.proof; l.c_a_h = ph.c_a; l.k2_far = cull_far_k2(l.half, ph);
         }
-        l.run = effective_run(c); l.out = c->d_dist_out.get(); l.stats = c->d_cull_stats.get();
-        if (lane_env_order(c, variant)) {      // every slot (padding included), in env order, one launch
-            l.sorted = nullptr; l.n_sorted = E * c->R8; l.n_terrain = l.n_sorted;
-            // slots per wave: enough waves to fill 1 024 SIMDs (4 096 envs x 64 slots in runs of 64 are one wave per SIMD).  Whole step, M
-            // env-steps/s, runs of 8 / 16 / 32 / 64: 512 envs 15.0 / 16.3 / 14.9 / 12.7; 1 024: 21.2 / 26.7 / 26.3 / 22.1; 2 048: 27.5 / 35.3 / 37.1 /
-            // 36.6; 4 096: - / 45.0 / 49.8 / 47.2; 8 192: - / 52.6 / 60.1 / 59.2; 120 + 26 rays at 4 096 envs: 19.9 / - / 35.5 / 33.2
-            l.run = c->run ? (c->run > 64u ? 64u : c->run) : ((uint64_t)E * c->R8 >= (1ull << 20) ? 64u : ((uint64_t)E * c->R8 >= (1ull << 17) ? 32u : 16u));
+        l.run = p.run; l.out = c->d_dist_out.get(); l.stats = c->d_cull_stats.get();
+        if (p.env_order) {      // every slot (padding included), in env order, one launch
+            l.sorted = nullptr; l.n_sorted = E * c->R8; l.n_terrain = l.n_sorted; l.run = p.env_run;
             HIP_TRY(c, launch_raycast_lane(l, s));
             return ROVER_OK;
         }
@@ -848,13 +897,13 @@ static int run_raycast(rover_ctx* c, int variant, uint32_t n_valid, hipStream_t 
         // rays, which test every pair of their cell both ways) — the staged kernel reads a cell's whole 6.6 KB of (A) and (B) rows for one such
         // ray where the culled kernel reads 800 bytes of ids and gathers: a tie at 65 536 envs (363-372 us in one launch against 226-233 +
         // 137-140).  On an irregular rocks mesh — most cells without a usable far bound — yes (465 us against 327 + 270 with the first version).
-        if (lane_rocks_too(c)) {
+        if (p.rocks_staged) {
             HIP_TRY(c, launch_raycast_lane(l, s));
         } else {
             // the terrain rays (the first E x P of the sorted list: terrain bins sort first) through the staged kernel, the rock rays — few per
             // bin, a tenth of them off every cone (the horizontal body rays) — through the culled one, which reads 800 bytes of ids per bin
             // where the staged kernel reads the 3.5 KB of a cell's whole row for one such ray
-            CullArgs a = cull_args(c, n_valid);
+            CullArgs a = cull_args(c, p, n_valid);
             l.n_sorted = l.n_terrain < n_valid ? l.n_terrain : n_valid;
             a.sorted += l.n_sorted; a.n_sorted -= l.n_sorted; a.n_terrain = 0;
             a.stats += lane_waves(l.n_sorted, l.run);
@@ -863,11 +912,11 @@ static int run_raycast(rover_ctx* c, int variant, uint32_t n_valid, hipStream_t 
             HIP_TRY(c, launch_raycast_lane(l, s));
             if (a.n_sorted) HIP_TRY(c, launch_raycast_culled(a, s));
         }
-    } else if (variant == 3)
-        HIP_TRY(c, launch_raycast_culled(cull_args(c, n_valid), s));
-    else if (variant == 2)
+    } else if (p.variant == 3)
+        HIP_TRY(c, launch_raycast_culled(cull_args(c, p, n_valid), s));
+    else if (p.variant == 2)
         HIP_TRY(c, launch_raycast_binned(c->d_rays.get(), c->d_sorted.get(), n_valid, c->maps[0].knn.table, c->maps[1].knn.table,
-                                         (uint32_t)c->maps[0].knn.K8, (uint32_t)c->maps[1].knn.K8, effective_run(c), c->precision == 2, c->early_out, c->d_dist_out.get(), s));
+                                         (uint32_t)c->maps[0].knn.K8, (uint32_t)c->maps[1].knn.K8, p.run, p.proof != 0, c->early_out, c->d_dist_out.get(), s));
     else
         HIP_TRY(c, launch_raycast(c->d_rays.get(), E * c->R8, c->maps[0].knn.table, c->maps[1].knn.table, (uint32_t)c->maps[0].knn.K8,
                                   (uint32_t)c->maps[1].knn.K8, c->d_dist_out.get(), s));
@@ -885,13 +934,11 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
     p.pos = pos; p.quat = quat; p.joints = joints; p.target = target; p.euler_in = euler_in;
     p.dist = c->d_dist.get(); p.terrain = c->maps[0].knn; p.rocks = c->maps[1].knn;
     p.rays = c->d_rays.get(); p.euler = euler_in ? nullptr : c->d_euler.get(); p.heading = euler_in ? nullptr : c->d_heading.get();
-    const int variant = effective_variant(c);
-    // (the queue is sized by every call that changes its size — never here: no hipMalloc inside a step / a stream capture)
-    if (variant >= 3 && (!c->d_cull_queue.get() || !c->d_cull_stats.get() || c->cull_run != effective_run(c)))
-        return fail(c, ROVER_E_STATE, "the culled ray cast's candidate queue is not allocated for the options in force");
+    const RayPlan& plan = c->plan;
+    if (int r = check_queue(c, plan)) return r;
     const uint32_t n_valid = E * (26u + (uint32_t)c->P);
     p.rocks_bin_offset = (uint32_t)((uint64_t)c->maps[0].knn.X * c->maps[0].knn.Y);
-    const bool sorts = variant >= 2 && !lane_env_order(c, variant);
+    const bool sorts = plan.sorted;
     if (sorts) p.bin_out = c->d_bins.get();
     p.precision = c->precision;
     p.cell_rcp = c->cell_rcp;
@@ -906,7 +953,7 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
     }
     if (import_src) {
         // caller-supplied directions: the culled / staged ray cast's proofs need them of unit length (what -normalize() gives)
-        uint32_t* const not_unit = variant >= 3 ? c->d_block_cnt.get() + (size_t)c->cfg.num_envs / 256 + 1 : nullptr;      // (the spare word behind the block counts)
+        uint32_t* const not_unit = plan.variant >= 3 ? c->d_block_cnt.get() + (size_t)c->cfg.num_envs / 256 + 1 : nullptr;      // (the spare word behind the block counts)
         if (not_unit) HIP_TRY(c, hipMemsetAsync(not_unit, 0, sizeof(uint32_t), s));
         HIP_TRY(c, launch_import_rays(import_src, import_dir, E, c->R8, (uint32_t)c->P, c->maps[0].knn, c->maps[1].knn, p.rocks_bin_offset, c->precision,
                                       c->cell_rcp, c->d_rays.get(), sorts ? c->d_bins.get() : nullptr, s, not_unit));
@@ -933,14 +980,13 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
         if (c->prof_pending == kProfRing && prof_drain(c)) return fail(c, ROVER_E_HIP, "profiling: event drain failed");
         HIP_TRY(c, hipEventRecord(c->ev0[c->prof_pending], s));
     }
-    if (int r = run_raycast(c, variant, n_valid, s)) return r;
+    if (int r = run_raycast(c, plan, n_valid, s)) return r;
     if (timed) {
         HIP_TRY(c, hipEventRecord(c->ev1[c->prof_pending], s));
         ++c->prof_pending;
         ++c->prof_launches;
     }
-    c->last_variant = variant;
-    c->sorted_valid = sorts;
+    c->ws_plan = plan;
     c->rays_valid = true;
     return ROVER_OK;
 }
@@ -1289,10 +1335,10 @@ int rover_get_info(const rover_ctx* c, rover_info* info) {
     }
     // the per-step workspace: ray records, distances, sort buffers, env records, and the culled ray cast's queue + counters
     info->workspace_bytes = c->workspace_bytes + c->d_cull_queue.bytes() + c->d_cull_stats.bytes();
-    info->raycast_variant = have_maps(c) ? effective_variant(c) : 0;
+    info->raycast_variant = c->plan.variant;
     info->cell_index_mode = c->cell_rcp; info->ray_precision = c->precision;
-    info->raycast_sorted = info->raycast_variant >= 2 && !lane_env_order(c, info->raycast_variant);
-    info->raycast_rocks_staged = info->raycast_variant == 4 && (!info->raycast_sorted || lane_rocks_too(c)) ? 1 : 0;
+    info->raycast_sorted = c->plan.sorted ? 1 : 0;
+    info->raycast_rocks_staged = c->plan.rocks_staged ? 1 : 0;
     return ROVER_OK;
 }
 
@@ -1302,14 +1348,14 @@ int rover_get_cull_info(rover_ctx* c, rover_cull_info* out) {
     for (int w = 0; w < 2; ++w) {             // (of the proof tables the precision in force uses)
         const MapTables& m = c->maps[w];
         out->triangles[w] = m.tris;
-        out->always_candidate_triangles[w] = m.proof[proof_in_force(c)].always;
-        out->cells_without_cone[w] = m.proof[proof_in_force(c)].nocone;
+        out->always_candidate_triangles[w] = m.proof[c->plan.proof].always;
+        out->cells_without_cone[w] = m.proof[c->plan.proof].nocone;
         out->cells_with_far_bound[w] = m.farok;
     }
-    out->far_records_on_demand = (c->have_dist && c->maps[0].table.get()) ? (uint64_t)cull_args(c, 0).lazy_far : 0;
+    out->far_records_on_demand = (c->have_dist && c->maps[0].table.get()) ? (uint64_t)c->plan.lazy_far : 0;
     out->queue_bytes = c->d_cull_queue.bytes();
     out->launches_per_step = c->d_cull_queue.get() ? c->cull_launches : 0;
-    if (!c->d_cull_stats.get() || c->last_variant < 3) return ROVER_OK;
+    if (!c->d_cull_stats.get() || c->ws_plan.variant < 3) return ROVER_OK;
     USE_DEVICE(c);
     HIP_TRY(c, hipDeviceSynchronize());
     std::vector<uint4> h(c->cull_stat_slots);
@@ -1543,11 +1589,11 @@ int rover_set_option(rover_ctx* c, const char* name, int64_t value) {
     USE_DEVICE(c);                                 // some options (re)allocate device workspace
     if (!strcmp(name, "raycast_variant")) {
         if (value < 0 || value > 4) return fail(c, ROVER_E_INVALID, "raycast_variant must be 0 (auto), 1 (env order), 2 (binned), 3 (culled) or 4 (staged)");
-        if (value == 4 && have_maps(c) && c->maps[0].knn.K8 <= 256 && c->maps[1].knn.K8 <= 256 && !lane_tables_ok(c))
+        if (value == 4 && staged_tables_missing(c))
             return fail(c, ROVER_E_STATE, "raycast_variant 4 (staged) needs its tables for the arithmetic in force: they were not built (option "
                                           "staged_tables, or they did not fit when the maps were set)");
         c->variant = (int)value;
-        return alloc_cull_queue(c);
+        return replan(c);
     }
     if (!strcmp(name, "staged_tables")) {
         if (value < 0 || value > 3) return fail(c, ROVER_E_INVALID, "staged_tables must be 0 (none), 1 (f32 proof), 2 (as-shipped fp16 proof) or 3 (both)");
@@ -1557,24 +1603,24 @@ int rover_set_option(rover_ctx* c, const char* name, int64_t value) {
     if (!strcmp(name, "lane_env_order")) {
         if (value < -1 || value > 1) return fail(c, ROVER_E_INVALID, "lane_env_order must be -1 (auto), 0 or 1");
         c->lane_env_order = (int)value;
-        return ROVER_OK;
+        return replan(c);
     }
     if (!strcmp(name, "lane_rocks")) {
         if (value < -1 || value > 1) return fail(c, ROVER_E_INVALID, "lane_rocks must be -1 (auto), 0 or 1");
         c->lane_rocks = (int)value;
-        return ROVER_OK;
+        return replan(c);
     }
     if (!strcmp(name, "ray_precision")) {
         if (value < 0 || value > 2) return fail(c, ROVER_E_INVALID, "ray_precision must be 0 (fp32), 1 (fp16 sources) or 2 (as shipped)");
         c->precision = (int)value;
         c->rays_valid = false;
         c->obs_valid = false;           // (what an observation means changed: rover_calculate_metrics wants a fresh rover_get_observations)
-        return alloc_cull_queue(c);
+        return replan(c);
     }
     if (!strcmp(name, "bin_low_bits")) {
         if (value != 0 && (value < 8 || value > 12)) return fail(c, ROVER_E_INVALID, "bin_low_bits must be 0 (chosen by the library) or in [8, 12]");
         c->low_bits_opt = (uint32_t)value;
-        return alloc_bins(c);
+        return replan(c, alloc_bins(c));
     }
     if (!strcmp(name, "raycast_early_out")) {
         if (value < 0 || value > 1) return fail(c, ROVER_E_INVALID, "raycast_early_out must be 0 or 1");
@@ -1592,12 +1638,12 @@ int rover_set_option(rover_ctx* c, const char* name, int64_t value) {
     if (!strcmp(name, "cull_queue_mb")) {
         if (value < 1 || value > (1 << 20)) return fail(c, ROVER_E_INVALID, "cull_queue_mb must be in [1, 1048576]");
         c->cull_budget = (uint64_t)value << 20;
-        return alloc_cull_queue(c);
+        return replan(c);
     }
     if (!strcmp(name, "raycast_run")) {
         if (value < 0 || value > 4096) return fail(c, ROVER_E_INVALID, "raycast_run must be 0 (auto) or in [1, 4096]");
         c->run = (uint32_t)value;
-        return alloc_cull_queue(c);
+        return replan(c);
     }
     return fail(c, ROVER_E_INVALID, "unknown option '%s'", name);
 }
@@ -1643,14 +1689,10 @@ int rover_replay_raycast(rover_ctx* c, void* stream) {
     if (int r = check_ready(c)) return r;
     if (!c->rays_valid) return fail(c, ROVER_E_STATE, "replay_raycast: no ray records yet (run a step first)");
     USE_DEVICE(c);
-    int v = effective_variant(c);
-    if (v >= 2 && !c->sorted_valid && !lane_env_order(c, v)) v = 1;       // no sorted list from the last step: only an env-order kernel can replay
-    const uint32_t n_valid = (uint32_t)c->cfg.num_envs * (26u + (uint32_t)c->P);
-    hipStream_t s = (hipStream_t)stream;
-    if (v >= 3 && (!c->d_cull_queue.get() || !c->d_cull_stats.get() || c->cull_run != effective_run(c)))
-        return fail(c, ROVER_E_STATE, "the culled ray cast's candidate queue is not allocated for the options in force");
-    if (int r = run_raycast(c, v, n_valid, s)) return r;
-    return ROVER_OK;
+    RayPlan p = c->plan;
+    if (p.sorted && !c->ws_plan.sorted) { p = RayPlan{}; p.variant = 1; }     // no sorted list from the last step: only an env-order kernel can replay
+    if (int r = check_queue(c, p)) return r;
+    return run_raycast(c, p, (uint32_t)c->cfg.num_envs * (26u + (uint32_t)c->P), (hipStream_t)stream);
 }
 
 }  // extern "C"

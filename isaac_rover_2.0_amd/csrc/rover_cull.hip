@@ -42,9 +42,6 @@
 // ray record, the id row carries q (rounded down): where q wins, phase 1 runs test (A) only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <stdio.h>
-#include <vector>
 #include <type_traits>
 #include "rover_internal.h"
 #include "rover_raymath.h"
@@ -522,7 +519,7 @@ __device__ __forceinline__ void cull_exact(const RayRec* __restrict__ rays, cons
         if (base + 64u < n) en_next = entry(min(base + 64u + lane, n - 1u));
         float best;
         if (H) {
-            // the reference's as-shipped fp16 arithmetic (cast_pairs_h: what raycast_binned_h_kernel runs on every triangle); the
+            // the reference's as-shipped fp16 arithmetic (cast_pairs_h: what raycast_binned_kernel<1> runs on every triangle); the
             // ray record holds fp16 values widened to f32 (prep_rays_kernel, precision 2), so the casts below are exact
             h2 v[9];
 #pragma unroll
@@ -974,9 +971,7 @@ __global__ void __launch_bounds__(64 * CULL_WPB) cull_scan_kernel(CULL_SCAN_ARGS
 #define LN_PAD 5.0e-5                // added to a triangle's radius: what pays for the relative coordinates' rounding (header comment: >= 1e-6 would do)
 #define LN_AB 8u                     // pairs an item keeps in flight: test (A) only (a record per pair) ...
 #define LN_ABB 4u                    // ... tests (A) and (B) (two records per pair)
-#ifndef LN_ABB4
 #define LN_ABB4 4u                   // ... tests (A) and (B4) (f32 proof: 16 + 8 bytes per pair)
-#endif
 // Test (B) of the f32 proof on 4-byte records ("B4", the second half of a cell's row: 8 B per pair instead of 16).  A record holds the
 // triangle's unit normal as three signed 10-bit integers n4 = round(511 n^) (bits 0-9, 10-19, 20-29), n^ the direction of the ctab record's
 // fp16 normal (within 5e-4 of N / |N|: fp16 components of a vector of length r / tau >= 1); the builder decodes its own code and keeps it only
@@ -1285,20 +1280,9 @@ __device__ __forceinline__ void lane_exact(const RayRec* __restrict__ rays, cons
         const float4 *__restrict__ lvl1, const uint4 *__restrict__ lrec0, const uint4 *__restrict__ lrec1, const uint2 *__restrict__ lid0,    \
         const uint2 *__restrict__ lid1, const RawTri *__restrict__ rtab0, const RawTri *__restrict__ rtab1, uint32_t pp01, uint32_t run,      \
         uint32_t n_blocks, uint32_t split, uint32_t t8, uint32_t r8, uint32_t chsr, uint32_t run_r, float *__restrict__ out,                  \
-        uint4 *__restrict__ stats, float k2_far, float c_a, uint32_t *__restrict__ diag
+        uint4 *__restrict__ stats, float k2_far, float c_a
 
-#ifdef ROVER_DIAG_SORTED_RECS       // diagnostic builds only: the ray records copied into sorted order first (not timed with the kernel), read coalesced
-__device__ const RayRec* g_diag_recs = nullptr;
-__global__ void diag_gather_recs(const RayRec* __restrict__ rays, const uint32_t* __restrict__ sorted, uint32_t n, RayRec* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4* src = reinterpret_cast<const float4*>(rays + sorted[i]);
-    float4* dst = reinterpret_cast<float4*>(out + i);
-    dst[0] = src[0]; dst[1] = src[1];
-}
-#endif
-
-template <int H, int DIAG>
+template <int H>
 __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bounds__(64) lane_scan_kernel(LANE_SCAN_ARGS) {
     __shared__ float4 s_ray[128];                         // per ray {s'x, s'y, s'z, dx}, {dy, dz, the cell's record row (64-bit address)}
     __shared__ uint16_t s_q[LN_QCAP];                     // the queue of the exact phase: ray | pair position << 6; before it, while the tests run:
@@ -1326,15 +1310,10 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     if (i0 >= n_sorted) return;
     const uint32_t n_run = min(my_run, n_sorted - i0);
     const bool in_run = lane < n_run;
-    const uint64_t t_start = DIAG ? __builtin_amdgcn_s_memtime() : 0ull;
     // sorted == NULL: the ray slots in env order (small batches: a bin holds a ray or none, the sort's three launches buy nothing; a run is
     // then `run` consecutive slots — 16, 32 or 64: run_raycast —, padding slots — flags bit 1 clear — take no part)
     const uint32_t gid = sorted ? sorted[i0 + (in_run ? lane : n_run - 1u)] : i0 + (in_run ? lane : n_run - 1u);
-#ifdef ROVER_DIAG_SORTED_RECS
-    const RayRec* const rrec = (sorted && g_diag_recs) ? g_diag_recs + (i0 + (in_run ? lane : n_run - 1u)) : rays + gid;
-#else
     const RayRec* const rrec = rays + gid;
-#endif
     const float4 rsa = reinterpret_cast<const float4*>(rrec)[0], rsb = reinterpret_cast<const float4*>(rrec)[1];
     const uint32_t cell = __float_as_uint(rsa.w), rflags = __float_as_uint(rsb.w), map = rflags & 1u;
     const bool act = in_run && (rflags & 2u) != 0u;
@@ -1382,28 +1361,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     const bool ab = act && tame && !cone;                     // off the cell's cone: the prefix runs tests (A) and (B)
     if (allc) L = nch;
     if (!act) L = 0u;
-#ifdef ROVER_DIAG_AB_MAXCH      // diagnostic builds only (wrong results, right timing): the (A) + (B) items of a ray stop after this many chunks
-    const uint32_t n_a = (act && !allc && !ab) ? L : 0u, n_b = ab ? min(L, (uint32_t)(ROVER_DIAG_AB_MAXCH)) : 0u;
-#else
     const uint32_t n_a = (act && !allc && !ab) ? L : 0u, n_b = ab ? L : 0u;
-#endif
-    // (diagnostic of the library's own: ROVER_LANE_DIAG=1 prints where a wave's time goes — launch_raycast_lane)
-    uint64_t tq = 0;
-    uint32_t dg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto lap = [&](int k) { if (DIAG) { const uint64_t n = __builtin_amdgcn_s_memtime(); dg[k] += (uint32_t)(n - tq); tq = n; } };
-    if (DIAG) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tq = __builtin_amdgcn_s_memtime();
-        dg[5] = (uint32_t)(tq - t_start);
-        for (uint32_t v = 0; v < (diag[(size_t)n_blocks * 4u * 8u + 39u] ? 19u : 0u); ++v) {    // (ROVER_LANE_DIAG=2) histogram of the rays' levels behind the per-wave rows: its atomics distort the times
-            const uint32_t cnt = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(act && !map && (allc ? 17u : (ab ? 18u : L)) == v));
-            const uint32_t cnt1 = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(act && map && (allc ? 17u : (ab ? 18u : L)) == v));
-            if (lane == 0u && cnt) atomicAdd(diag + (size_t)n_blocks * 4u * 8u + v, cnt);
-            if (lane == 0u && cnt1) atomicAdd(diag + (size_t)n_blocks * 4u * 8u + 20u + v, cnt1);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tq = __builtin_amdgcn_s_memtime();
-    }
     // The items, in the order bin by bin, chunk by chunk, the bin's rays that test the chunk: lanes that read the same 128-byte line of a
     // record row sit next to each other.  Position of item (ray, k) = items of the bins before + items of the bin's chunks before k + the
     // ray's rank among the bin's rays with more than k items.  Two lists: the (A) items, behind them the (A) + (B) items.
@@ -1436,7 +1394,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     }
     uint32_t cused = 0, ctot = 0, n_flush = 0;
     wave_lds_sync();
-    lap(0);
     // the tests: 64 items per round, the records straight from the cell's row (L1 / L2: a chunk is read by the bin's rays side by side)
     auto rounds = [&](uint32_t it0, uint32_t it1, auto AB) {
         constexpr bool kAB = decltype(AB)::value;
@@ -1514,17 +1471,14 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     rounds(0u, ia_tot, std::false_type{});
     if (ib_tot) rounds(ia_tot, ia_tot + ib_tot, std::true_type{});
     wave_lds_sync();
-    lap(2);
     // candidates -> queue entries; the exact phase whenever the queue could not take the next ray's entries (rare) and at the end
     auto flush = [&]() {
         wave_lds_sync();
-        lap(3);
         lane_exact<H>(rays, rtab0, rtab1, lid0, lid1, pp01, s_q, cused, s_abs, key, lane, s_bk);
         ctot += cused;
         cused = 0;
         ++n_flush;
         wave_lds_sync();
-        lap(4);
     };
     {
         uint32_t cm[LN_MAXCH / 4u], cnt = 0;                      // the ray's masks, four chunks per register (chunk k in byte k % 4 of word k / 4)
@@ -1567,7 +1521,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
             if (r_lo < r_end) flush();
         }
     }
-    lap(3);
     if (cused) flush();
     wave_lds_sync();
     if (act) out[gid] = funkey(s_bk[lane]);
@@ -1579,18 +1532,12 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
         const uint32_t n_bins = (uint32_t)__builtin_popcountll(heads);
         const uint32_t n_rays = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(act));          // (env order: without the padding slots)
         if (lane == 0u) stats[wave] = make_uint4(ctot, n_rays | (n_fskip << 8), n_both | (n_askip << 8), n_bins | (min(ia_tot + ib_tot, 0x3ffffu) << 8) | (min(n_flush, 63u) << 26));
-        if (DIAG && lane == 0u) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) diag[(size_t)wave * 8u + k] = dg[k];
-        }
     }
 }
 
 // ---------------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------------
-static inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
-
 hipError_t launch_tri_centroids(const int32_t* tris, const uint16_t* verts, uint32_t T, uint32_t V, float2* out, hipStream_t s) {
     hipLaunchKernelGGL(tri_centroid_kernel, dim3(blocks_for(T, 256)), dim3(256), 0, s, tris, verts, T, V, out);
     return hipGetLastError();
@@ -1738,50 +1685,10 @@ hipError_t launch_raycast_lane(LaneArgs a, hipStream_t s) {
         g.chr = 31u; g.r8 = blocks_for(g.n_blocks - g.split, 8);
     }
     const float k2 = a.k2_far, c_a = a.half ? a.c_a_h : CullK<0>::c_a;
-    static const bool want_diag = getenv("ROVER_LANE_DIAG") != nullptr;
-    static uint32_t* d_diag = nullptr; static uint32_t diag_waves = 0; static int diag_left = 2;
-    const uint32_t waves = g.n_blocks * 4u;
-    if (want_diag && diag_waves < waves) { if (d_diag) (void)hipFree(d_diag); (void)hipMalloc((void**)&d_diag, ((size_t)waves * 8u + 40u) * sizeof(uint32_t)); diag_waves = waves; }
-    if (want_diag && d_diag) {
-        (void)hipMemsetAsync(d_diag, 0, ((size_t)waves * 8u + 40u) * sizeof(uint32_t), s);
-        static const bool want_hist = atoi(getenv("ROVER_LANE_DIAG")) >= 2;      // the level histogram too
-        if (want_hist) (void)hipMemsetAsync(d_diag + (size_t)waves * 8u + 39u, 1, 1, s);
-    }
-#ifdef ROVER_DIAG_SORTED_RECS
-    if (a.sorted) {
-        static RayRec* d_recs = nullptr; static uint32_t cap = 0;
-        if (cap < a.n_sorted) { if (d_recs) (void)hipFree(d_recs); (void)hipMalloc((void**)&d_recs, (size_t)a.n_sorted * sizeof(RayRec)); cap = a.n_sorted;
-                                const RayRec* p = d_recs; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_diag_recs), &p, sizeof p); }
-        hipLaunchKernelGGL(diag_gather_recs, dim3((a.n_sorted + 255u) / 256u), dim3(256), 0, s, a.rays, a.sorted, a.n_sorted, d_recs);
-    }
-#endif
-    auto kern = a.half ? lane_scan_kernel<1, 0> : (want_diag && d_diag ? lane_scan_kernel<0, 1> : lane_scan_kernel<0, 0>);
-    hipLaunchKernelGGL(kern, dim3((g.t8 + g.r8) * 8u * 4u), dim3(64), 0, s, a.rays, a.sorted,
+    hipLaunchKernelGGL(a.half ? lane_scan_kernel<1> : lane_scan_kernel<0>, dim3((g.t8 + g.r8) * 8u * 4u), dim3(64), 0, s, a.rays, a.sorted,
                        a.n_sorted, a.lvl[0], a.lvl[1], a.lrec[0], a.lrec[1], a.lid[0], a.lid[1], reinterpret_cast<const RawTri*>(a.rtab[0]),
                        reinterpret_cast<const RawTri*>(a.rtab[1]), a.pp[0] | (a.pp[1] << 16), g.run, g.n_blocks, g.split, g.t8, g.r8, g.chs | (g.chr << 8),
-                       g.run_r, a.out, a.stats, k2, c_a, (want_diag && !a.half) ? d_diag : nullptr);
-    static int diag_seen = 0;
-    if (want_diag && d_diag && ++diag_seen > 8 && diag_left > 0) {       // (not the first launches: cold caches)      // where a wave's time goes: mean shader-clock cycles per wave and phase (synchronises: a diagnostic)
-        --diag_left;
-        std::vector<uint32_t> h((size_t)waves * 8u + 40u);
-        if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(h.data(), d_diag, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess) {
-            const uint32_t* hg = h.data() + (size_t)waves * 8u;
-            for (int part = 0; part < 2; ++part) {           // the waves of the terrain part, then of the rocks part of the sorted list
-                const size_t w0 = part ? (size_t)g.split * 4u : 0u, w1 = part ? waves : std::min<size_t>(waves, (size_t)g.split * 4u);
-                if (w1 <= w0) continue;
-                double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (size_t i = w0 * 8u; i < w1 * 8u; ++i) sum[i & 7u] += h[i];
-                const double nw = (double)(w1 - w0);
-                fprintf(stderr, "lane_scan_kernel, %s part, %zu waves, mean ticks per wave: prologue loads %.0f | bins/scans %.0f | items %.0f | entries %.0f | exact %.0f\n",
-                        part ? "rocks" : "terrain", w1 - w0, sum[5] / nw, sum[0] / nw, sum[2] / nw, sum[3] / nw, sum[4] / nw);
-            }
-            for (int m = 0; m < (hg[39] ? 2 : 0); ++m) {
-                fprintf(stderr, "  %s rays by level 0..16:", m ? "rock" : "terrain");
-                for (int v = 0; v < 17; ++v) fprintf(stderr, " %u", hg[20 * m + v]);
-                fprintf(stderr, ", wild (all pairs candidates): %u, off the cone (tests A and B): %u\n", hg[20 * m + 17], hg[20 * m + 18]);
-            }
-        }
-    }
+                       g.run_r, a.out, a.stats, k2, c_a);
     return hipGetLastError();
 }
 

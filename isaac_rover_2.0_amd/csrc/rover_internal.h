@@ -221,6 +221,9 @@ bool chain_pair_fits(const ChainArgs& a, const ChainArgs& b);
 hipError_t launch_chain_splitk_pair(const ChainArgs& a, const ChainArgs& b, float* scratch_a, float* scratch_b, const float* copy_src,
                                     int64_t copy_src_stride, float* copy_dst, int64_t copy_dst_stride, int copy_cols, hipStream_t s);
 
+// blocks of bs threads (or items) that cover n: the launchers' grid sizes
+static inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
+
 hipError_t launch_repack(const int32_t* map_idx, const int32_t* tris, const uint16_t* verts, uint64_t n_cells, uint32_t K,
                          uint32_t K8, uint32_t T, uint32_t V, uint16_t* table, hipStream_t s);
 hipError_t launch_prep(const PrepArgs& a, hipStream_t s);

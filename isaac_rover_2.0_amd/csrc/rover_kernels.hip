@@ -19,8 +19,8 @@
 // * bucket_hist / rowscan / scatter / sort   bucket sort of the ray slots by (map, cell), LDS atomics only (3 - 4 launches)
 // * cull_scan_kernel         (rover_cull.hip) the culled ray cast: 1 wave / run of sorted rays                      (A4, A5) <- roofline kernel
 //   raycast_binned_kernel    variant 2: 1 wave / run of sorted rays, 4 triangles per lane in registers, every triangle evaluated,
-//                            conservative early out (round 1's roofline kernel; the bit-for-bit reference of the culled one)
-//   raycast_binned_h_kernel  the same in the reference's as-shipped fp16 arithmetic (ray_precision 2)
+//                            conservative early out (round 1's roofline kernel; the bit-for-bit reference of the culled one);
+//                            <1>: the same in the reference's as-shipped fp16 arithmetic (ray_precision 2)
 //   raycast_kernel           variant 1: env order, half-wave per ray, streams the cell blocks (small batches, K8 > 256)
 // * obs_metrics_kernel       assemble_obs (1 thread / 4 obs elements, coalesced rows) + metrics_done (1 thread / env: collision mask,
 //                            stone mask, reward, extras, done, done count) in one launch                            (A1, A7, A8, A10)
@@ -31,6 +31,7 @@
 //   knn_centroid / knn_bucket / knn_select kernels                                                                   (f-3)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "rover_internal.h"
 #include "rover_raymath.h"
 
@@ -324,11 +325,7 @@ __global__ void __launch_bounds__(64 * PREP_SLOTS) prep_rays_kernel(PrepArgs a, 
         RayRec rec;
         rec.sx = rec.sy = rec.sz = 0.0f; rec.cell = 0u; rec.dx = rec.dy = 0.0f; rec.dz = 1.0f; rec.flags = 0u;
         uint32_t bin = 0xffffffffu;
-#ifdef ROVER_DIAG_SKIP_LO       // diagnostic builds only (wrong results, right timing): ray slots [LO, HI) are left out of the cast
-        const bool real = live && slot < n_real && !(slot >= (ROVER_DIAG_SKIP_LO) && slot < (ROVER_DIAG_SKIP_HI));
-#else
         const bool real = live && slot < n_real;
-#endif
         uint32_t kind = 0u;
         if (real) {
             float sx, sy, sz;                  // origin
@@ -1487,7 +1484,14 @@ __global__ void __launch_bounds__(NT) bucket_sort_kernel(const uint2* __restrict
 // The three quotients share one reciprocal refinement: the exact instruction sequence of the IEEE f32
 // division expansion without its range scaling (den and quotients here are far from the f32 range ends),
 // so results stay bit-identical to n = N/det, m = M/det, k = K/det.
+// H = 1: the reference's AS-SHIPPED arithmetic (option ray_precision = 2): Camera.dtype = float16, so every elementwise ATen op
+// of ray_casting.py:31-59 rounds to fp16.  The per-pair maths in packed fp16 (v_pk_mul_f16 / v_pk_add_f16, one rounding per op,
+// no contraction); the three quotients are taken in f32 (IEEE, shared reciprocal) and rounded to fp16, which equals the fp16
+// quotient (24 >= 2*11 + 2 bits).  Bit-identical to the oracle's fp16 mode, which the as-shipped golden fixture pins bit for bit.
+// (the fp16 (ray, triangle) arithmetic — CellRegsH, set_pair_h, cast_pairs_h — lives in rover_raymath.h: one definition for this
+// kernel and the culled ray cast's exact phase)
 // ---------------------------------------------------------------------------------------------------
+template <int H>
 __global__ void __launch_bounds__(256) raycast_binned_kernel(const RayRec* __restrict__ rays, const uint32_t* __restrict__ sorted,
                                                              uint32_t n_sorted, const _Float16* __restrict__ tab0,
                                                              const _Float16* __restrict__ tab1, uint32_t kp0, uint32_t kp1,
@@ -1503,7 +1507,7 @@ __global__ void __launch_bounds__(256) raycast_binned_kernel(const RayRec* __res
     if (i >= n_sorted) return;
     const uint32_t i_end = min(i + run, n_sorted);
     uint32_t cur_cell = 0xffffffffu, cur_map = 0xffffffffu;
-    CellRegs<2> t;                    // per lane: 4 triangles as 2 packed pairs
+    std::conditional_t<H != 0, CellRegsH<2>, CellRegs<2>> t;      // per lane: 4 triangles as 2 packed pairs
     t.poison();
     uint64_t vmask[2][2] = {{0, 0}, {0, 0}};
     for (; i < i_end; ++i) {
@@ -1524,10 +1528,17 @@ __global__ void __launch_bounds__(256) raycast_binned_kernel(const RayRec* __res
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
                     const int t0 = 2 * p, t1 = 2 * p + 1;
-                    f2 w[9];
+                    if constexpr (H) {
+                        h2 vv[9];
 #pragma unroll
-                    for (int q = 0; q < 9; ++q) w[q] = f2{(float)v[q][t0], (float)v[q][t1]};
-                    set_pair(t, p, w);
+                        for (int q = 0; q < 9; ++q) vv[q] = h2{v[q][t0], v[q][t1]};
+                        set_pair_h(t, p, vv);
+                    } else {
+                        f2 w[9];
+#pragma unroll
+                        for (int q = 0; q < 9; ++q) w[q] = f2{(float)v[q][t0], (float)v[q][t1]};
+                        set_pair(t, p, w);
+                    }
                 }
             }
 #pragma unroll
@@ -1536,9 +1547,18 @@ __global__ void __launch_bounds__(256) raycast_binned_kernel(const RayRec* __res
                 vmask[p][1] = __builtin_amdgcn_ballot_w64(t.ax[p].y == t.ax[p].y);
             }
         }
-        const f2 sx = {ra.x, ra.x}, sy = {ra.y, ra.y}, sz = {ra.z, ra.z};
-        const f2 dx = {rb.x, rb.x}, dy = {rb.y, rb.y}, dz = {rb.z, rb.z};
-        float best = cast_pairs<2>(t, sx, sy, sz, dx, dy, dz, vmask, map ? pre_rocks : pre_terrain);
+        float best;
+        if constexpr (H) {
+            // the record holds fp16 values widened to f32 (prep_rays_kernel, precision 2): the casts are exact
+            const _Float16 hsx = (_Float16)ra.x, hsy = (_Float16)ra.y, hsz = (_Float16)ra.z;
+            const _Float16 hdx = (_Float16)rb.x, hdy = (_Float16)rb.y, hdz = (_Float16)rb.z;
+            best = cast_pairs_h<2>(t, h2{hsx, hsx}, h2{hsy, hsy}, h2{hsz, hsz}, h2{hdx, hdx}, h2{hdy, hdy}, h2{hdz, hdz}, vmask,
+                                   map ? pre_rocks : pre_terrain);
+        } else {
+            const f2 sx = {ra.x, ra.x}, sy = {ra.y, ra.y}, sz = {ra.z, ra.z};
+            const f2 dx = {rb.x, rb.x}, dy = {rb.y, rb.y}, dz = {rb.z, rb.z};
+            best = cast_pairs<2>(t, sx, sy, sz, dx, dy, dz, vmask, map ? pre_rocks : pre_terrain);
+        }
         best = wave_min_to_lane63(best);
         if (lane == 63u) out[gid] = best;
     }
@@ -1669,76 +1689,8 @@ __global__ void __launch_bounds__(256) knn_select_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------
-// ray cast in the reference's AS-SHIPPED arithmetic (option ray_precision = 2): Camera.dtype = float16, so every
-// elementwise ATen op of ray_casting.py:31-59 rounds to fp16.  Same structure as raycast_binned_kernel, the per-pair
-// maths in packed fp16 (v_pk_mul_f16 / v_pk_add_f16, one rounding per op, no contraction); the three quotients are
-// taken in f32 (IEEE, shared reciprocal) and rounded to fp16, which equals the fp16 quotient (24 >= 2*11 + 2 bits).
-// Bit-identical to the oracle's fp16 mode, which the as-shipped golden fixture pins bit for bit.
-// ---------------------------------------------------------------------------------------------------
-// (the fp16 (ray, triangle) arithmetic — CellRegsH, set_pair_h, cast_pairs_h — lives in rover_raymath.h: one definition for this
-// kernel and the culled ray cast's exact phase)
-
-__global__ void __launch_bounds__(256) raycast_binned_h_kernel(const RayRec* __restrict__ rays, const uint32_t* __restrict__ sorted,
-                                                               uint32_t n_sorted, const _Float16* __restrict__ tab0,
-                                                               const _Float16* __restrict__ tab1, uint32_t kp0, uint32_t kp1,
-                                                               uint32_t run, uint32_t n_blocks, uint32_t nb8,
-                                                               uint32_t pre_terrain, uint32_t pre_rocks, float* __restrict__ out) {
-    const uint32_t lb = (blockIdx.x & 7u) * nb8 + (blockIdx.x >> 3);
-    if (lb >= n_blocks) return;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(lb * 4u + (threadIdx.x >> 6));
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t i = wave * run;
-    if (i >= n_sorted) return;
-    const uint32_t i_end = min(i + run, n_sorted);
-    uint32_t cur_cell = 0xffffffffu, cur_map = 0xffffffffu;
-    CellRegsH<2> t;
-    t.poison();
-    uint64_t vmask[2][2] = {{0, 0}, {0, 0}};
-    for (; i < i_end; ++i) {
-        const uint32_t gid = __builtin_amdgcn_readfirstlane(sorted[i]);
-        const float4* rp = reinterpret_cast<const float4*>(rays + gid);
-        const float4 ra = rp[0], rb = rp[1];
-        const uint32_t cell = __builtin_amdgcn_readfirstlane(__float_as_uint(ra.w));
-        const uint32_t map = __builtin_amdgcn_readfirstlane(__float_as_uint(rb.w)) & 1u;
-        if (cell != cur_cell || map != cur_map) {
-            if (map != cur_map && cur_map != 0xffffffffu && kp0 != kp1) t.poison();
-            cur_cell = cell; cur_map = map;
-            const uint32_t kp = map ? kp1 : kp0;
-            const _Float16* base = (map ? tab1 : tab0) + (size_t)cell * 9u * kp + lane * 4u;
-            if (lane * 4u < kp) {
-                half4 v[9];
-#pragma unroll
-                for (int q = 0; q < 9; ++q) v[q] = *reinterpret_cast<const half4*>(base + (size_t)q * kp);
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    const int t0 = 2 * p, t1 = 2 * p + 1;
-                    h2 vv[9];
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) vv[q] = h2{v[q][t0], v[q][t1]};
-                    set_pair_h(t, p, vv);
-                }
-            }
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                vmask[p][0] = __builtin_amdgcn_ballot_w64(t.ax[p].x == t.ax[p].x);
-                vmask[p][1] = __builtin_amdgcn_ballot_w64(t.ax[p].y == t.ax[p].y);
-            }
-        }
-        // the record holds fp16 values widened to f32 (prep_rays_kernel, precision 2): the casts are exact
-        const _Float16 hsx = (_Float16)ra.x, hsy = (_Float16)ra.y, hsz = (_Float16)ra.z;
-        const _Float16 hdx = (_Float16)rb.x, hdy = (_Float16)rb.y, hdz = (_Float16)rb.z;
-        float best = cast_pairs_h<2>(t, h2{hsx, hsx}, h2{hsy, hsy}, h2{hsz, hsz}, h2{hdx, hdx}, h2{hdy, hdy}, h2{hdz, hdz}, vmask,
-                                  map ? pre_rocks : pre_terrain);
-        best = wave_min_to_lane63(best);
-        if (lane == 63u) out[gid] = best;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
 // launchers (host)
 // ---------------------------------------------------------------------------------------------------
-static inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
-
 hipError_t launch_repack(const int32_t* map_idx, const int32_t* tris, const uint16_t* verts, uint64_t n_cells, uint32_t K,
                          uint32_t K8, uint32_t T, uint32_t V, uint16_t* table, hipStream_t s) {
     uint64_t n = n_cells * K8;
@@ -1844,10 +1796,10 @@ hipError_t launch_raycast_binned(const RayRec* rays, const uint32_t* sorted, uin
     // (A/B in one process, 65 536 envs, f32 kernel: none 1.424 ms, far pair only 1.228, every pair 1.249, this choice 1.169)
     const uint32_t pre_terrain = early_out ? 2u : 0u, pre_rocks = early_out ? 3u : 0u;
     if (fp16_math)
-        hipLaunchKernelGGL(raycast_binned_h_kernel, dim3(nb8 * 8u), dim3(256), 0, s, rays, sorted, n_sorted, t0, t1, kp0, kp1, run,
+        hipLaunchKernelGGL(raycast_binned_kernel<1>, dim3(nb8 * 8u), dim3(256), 0, s, rays, sorted, n_sorted, t0, t1, kp0, kp1, run,
                            n_blocks, nb8, pre_terrain, pre_rocks, out);
     else
-        hipLaunchKernelGGL(raycast_binned_kernel, dim3(nb8 * 8u), dim3(256), 0, s, rays, sorted, n_sorted, t0, t1, kp0, kp1, run,
+        hipLaunchKernelGGL(raycast_binned_kernel<0>, dim3(nb8 * 8u), dim3(256), 0, s, rays, sorted, n_sorted, t0, t1, kp0, kp1, run,
                            n_blocks, nb8, pre_terrain, pre_rocks, out);
     return hipGetLastError();
 }
