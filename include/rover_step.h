@@ -332,6 +332,21 @@ ROVER_API int rover_mlp_chain_pair_forward(rover_ctx *ctx, int32_t M, const rove
                                            const float *copy_src, int64_t copy_src_stride, float *copy_dst, int64_t copy_dst_stride,
                                            int32_t copy_cols, void *stream);
 
+/* Which kernel instantiation the three calls above would launch for these shapes — host only: no ctx, no launch, no pointer read
+ * but widths / activations (and, for the pair, those of the two descriptors).  Returns the instantiation's name:
+ *   rover_linear_route: "linear_act<1,1>" (one 32-column tile per workgroup) below 65 536 rows, else "linear_act<NT,4>" with
+ *     NT = 1..5 output tiles, "x2" appended when the columns are split in two halves ("linear_act<3,4>x2", "linear_act<4,4>x2");
+ *   rover_mlp_chain_route: "splitk<TN,RT>" (TN in {5, 6}, RT in {1, 2}: the two kernels of the split-k path), "mlp_small",
+ *     "chain16<5,4,0,0>", "chain16<6,4,0,0>" or "chain16<16,10,8,1>";
+ *   rover_mlp_chain_pair_route: "pair(splitk<TN,RT>)" when both chains run side by side, else "seq(<a>;<b>)" (one after the other,
+ *     the copy as a hipMemcpy2DAsync).
+ * "none" where the call launches nothing (M = 0); NULL where it would be refused with ROVER_E_INVALID for its shapes.  Strings are
+ * static, except rover_mlp_chain_pair_route's, which stays valid until the calling thread's next call of it. */
+ROVER_API const char *rover_linear_route(int32_t M, int32_t K, int32_t N);
+ROVER_API const char *rover_mlp_chain_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t *widths,
+                                            const int32_t *activations);
+ROVER_API const char *rover_mlp_chain_pair_route(int32_t M, const rover_chain_desc *a, const rover_chain_desc *b);
+
 /* ---- tuning knobs ------------------------------------------------------------------------------------- */
 /* name = "raycast_variant": 0 = auto; 1 = one half-wave per ray in env order, every cell block streamed from HBM;
  *        2 = rays counting-sorted by (map, cell), one wave per run of sorted rays, the cell's triangles held in registers

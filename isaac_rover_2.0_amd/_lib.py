@@ -124,6 +124,9 @@ SYMBOLS = {
     "rover_linear_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "rover_mlp_chain_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rover_mlp_chain_pair_forward": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
+    "rover_linear_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
+    "rover_mlp_chain_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "rover_mlp_chain_pair_route": (C.c_char_p, [C.c_int32, C.POINTER(ChainDesc), C.POINTER(ChainDesc)]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
     "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
     "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -556,6 +559,40 @@ class Engine:
             self._h, xa.shape[0], C.byref(da), C.byref(db), _ptr(copy_src) if copy_cols else None, copy_src.stride(0) if copy_cols else 0,
             _ptr(copy_dst) if copy_cols else None, copy_dst.stride(0) if copy_cols else 0, int(copy_cols), _stream(self._dev_index)),
             "rover_mlp_chain_pair_forward")
+
+    # ---- which kernel a forward call runs (host only: no ctx, no launch) ----------------------------
+    @staticmethod
+    def _route(name):
+        return None if name is None else name.decode()
+
+    @classmethod
+    def _chain_shape(cls, k0, widths, activations):
+        n = len(widths)
+        if len(activations) != n:
+            raise RoverError("chain route: one activation per layer")
+        return (int(k0), n, (C.c_int32 * n)(*[int(w) for w in widths]),
+                (C.c_int32 * n)(*[a if isinstance(a, int) else cls.ACTIVATIONS[a] for a in activations]))
+
+    @classmethod
+    def linear_route(cls, m, k, n):
+        """The instantiation linear_forward runs for an [m, k] x [n, k]^T layer ("linear_act<3,4>x2", ...); "none" for m = 0,
+        None where the call would be refused."""
+        return cls._route(load().rover_linear_route(int(m), int(k), int(n)))
+
+    @classmethod
+    def chain_route(cls, m, k0, widths, activations):
+        """The kernel chain_forward runs ("splitk<6,2>", "mlp_small", "chain16<16,10,8,1>", ...); activations: names or codes."""
+        k0, n, w, a = cls._chain_shape(k0, widths, activations)
+        return cls._route(load().rover_mlp_chain_route(int(m), k0, n, w, a))
+
+    @classmethod
+    def chain_pair_route(cls, m, a, b):
+        """The launches of chain_pair_forward: "pair(splitk<TN,RT>)" or "seq(<a>;<b>)"; a, b = (k0, widths, activations)."""
+        descs = []
+        for k0, widths, acts in (a, b):
+            k0, n, w, ac = cls._chain_shape(k0, widths, acts)
+            descs.append((ChainDesc(None, k0, k0, n, None, None, C.addressof(w), C.addressof(ac), None, 0), w, ac))
+        return cls._route(load().rover_mlp_chain_pair_route(int(m), C.byref(descs[0][0]), C.byref(descs[1][0])))
 
     # ---- evaluation mode (rover.py:122-137, 620-641, 670-672) -------------------------------------
     def set_evaluation(self, enable=True):

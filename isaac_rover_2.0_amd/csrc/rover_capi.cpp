@@ -1537,16 +1537,15 @@ static int mlp_scratch_reserve(rover_ctx* c, size_t need, hipStream_t s) {
     return ROVER_OK;
 }
 
-static int chain_run(rover_ctx* c, const ChainArgs& a, hipStream_t s) {
-    if (a.M == 0) return ROVER_OK;
-    if (chain_wants_splitk(a)) {          // small batches: first layer split along k through a scratch buffer
-        if (int r = mlp_scratch_reserve(c, chain_splitk_scratch_floats(a.M, a.K0, a.n[0]), s)) return r;
-        HIP_TRY(c, launch_chain_splitk(a, c->d_mlp_scratch.get(), s));
-        return ROVER_OK;
-    }
-    hipError_t e = launch_chain(a, s);
-    if (e == hipErrorInvalidValue) return fail(c, ROVER_E_INVALID, "mlp_chain_forward: net outside the built tile shapes (<= 96 -> <= 64, or <= 256 -> <= 160 -> <= 128 -> <= 16 with hidden activations none / LeakyReLU / ReLU)");
-    HIP_TRY(c, e);
+static int chain_refused(rover_ctx* c) {
+    return fail(c, ROVER_E_INVALID, "mlp_chain_forward: net outside the built tile shapes (<= 96 -> <= 64, or <= 256 -> <= 160 -> <= 128 -> <= 16 with hidden activations none / LeakyReLU / ReLU)");
+}
+
+// launches what chain_route() chose (never ChainKernel::None)
+static int chain_run(rover_ctx* c, const ChainArgs& a, const ChainRoute& r, hipStream_t s) {
+    if (r.kernel == ChainKernel::SplitK)
+        if (int e = mlp_scratch_reserve(c, chain_splitk_scratch_floats(a.M, a.K0, a.n[0]), s)) return e;
+    HIP_TRY(c, launch_chain(a, r, c->d_mlp_scratch.get(), s));
     return ROVER_OK;
 }
 
@@ -1556,8 +1555,11 @@ int rover_mlp_chain_forward(rover_ctx* c, const float* x, int64_t x_stride, int3
     if (!c) return ROVER_E_INVALID;
     ChainArgs a{};
     if (int r = chain_args_of(c, x, x_stride, M, K0, n_layers, weights, biases, widths, activations, y, y_stride, &a)) return r;
+    if (M == 0) return ROVER_OK;
+    const ChainRoute r = chain_route(a);
+    if (r.kernel == ChainKernel::None) return chain_refused(c);
     USE_DEVICE(c);
-    return chain_run(c, a, (hipStream_t)stream);
+    return chain_run(c, a, r, (hipStream_t)stream);
 }
 
 int rover_mlp_chain_pair_forward(rover_ctx* c, int32_t M, const rover_chain_desc* da, const rover_chain_desc* db, const float* copy_src,
@@ -1569,19 +1571,62 @@ int rover_mlp_chain_pair_forward(rover_ctx* c, int32_t M, const rover_chain_desc
     if (int r = chain_args_of(c, da->x, da->x_stride, M, da->K0, da->n_layers, da->weights, da->biases, da->widths, da->activations, da->y, da->y_stride, &a)) return r;
     if (int r = chain_args_of(c, db->x, db->x_stride, M, db->K0, db->n_layers, db->weights, db->biases, db->widths, db->activations, db->y, db->y_stride, &b)) return r;
     if (M == 0) return ROVER_OK;
+    const ChainRoute ra = chain_route(a), rb = chain_route(b);
+    if (ra.kernel == ChainKernel::None || rb.kernel == ChainKernel::None) return chain_refused(c);
     USE_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
-    if (chain_pair_fits(a, b)) {
+    if (chain_pair_side_by_side(ra, rb)) {
         const size_t fa = chain_splitk_scratch_floats(a.M, a.K0, a.n[0]), fb = chain_splitk_scratch_floats(b.M, b.K0, b.n[0]);
         if (int r = mlp_scratch_reserve(c, fa + fb, s)) return r;
-        HIP_TRY(c, launch_chain_splitk_pair(a, b, c->d_mlp_scratch.get(), c->d_mlp_scratch.get() + fa, copy_src, copy_src_stride, copy_dst, copy_dst_stride, copy_cols, s));
+        HIP_TRY(c, launch_chain_splitk_pair(a, b, ra, c->d_mlp_scratch.get(), c->d_mlp_scratch.get() + fa, copy_src, copy_src_stride, copy_dst,
+                                            copy_dst_stride, copy_cols, s));
         return ROVER_OK;
     }
     if (copy_cols > 0)
         HIP_TRY(c, hipMemcpy2DAsync(copy_dst, (size_t)copy_dst_stride * sizeof(float), copy_src, (size_t)copy_src_stride * sizeof(float),
                                     (size_t)copy_cols * sizeof(float), (size_t)M, hipMemcpyDeviceToDevice, s));
-    if (int r = chain_run(c, a, s)) return r;
-    return chain_run(c, b, s);
+    if (int r = chain_run(c, a, ra, s)) return r;
+    return chain_run(c, b, rb, s);
+}
+
+// ---- route queries: what the forward calls above would launch, from the shapes alone (host only) ----
+const char* rover_linear_route(int32_t M, int32_t K, int32_t N) {
+    const LinearRoute r = linear_route(M, N);
+    if (K < 0 || !r.nw) return nullptr;
+    return M == 0 ? "none" : linear_route_name(r);
+}
+
+// the part of chain_args_of() that chain_route() reads; false where chain_args_of() refuses the shapes
+static bool chain_shape_of(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations, ChainArgs* a) {
+    if (!widths || !activations || M < 0 || K0 <= 0 || (n_layers != 2 && n_layers != 4)) return false;
+    *a = ChainArgs{};
+    a->M = M; a->K0 = K0; a->n_layers = n_layers;
+    for (int i = 0; i < n_layers; ++i) {
+        if (widths[i] <= 0 || widths[i] > 256 || activations[i] < 0 || activations[i] > 4) return false;
+        a->n[i] = widths[i]; a->act[i] = activations[i];
+    }
+    return true;
+}
+
+const char* rover_mlp_chain_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations) {
+    ChainArgs a;
+    if (!chain_shape_of(M, K0, n_layers, widths, activations, &a)) return nullptr;
+    return M == 0 ? "none" : chain_route_name(chain_route(a));
+}
+
+const char* rover_mlp_chain_pair_route(int32_t M, const rover_chain_desc* da, const rover_chain_desc* db) {
+    ChainArgs a, b;
+    if (!da || !db || !chain_shape_of(M, da->K0, da->n_layers, da->widths, da->activations, &a) ||
+        !chain_shape_of(M, db->K0, db->n_layers, db->widths, db->activations, &b))
+        return nullptr;
+    if (M == 0) return "none";
+    const ChainRoute ra = chain_route(a), rb = chain_route(b);
+    const char *na = chain_route_name(ra), *nb = chain_route_name(rb);
+    if (!na || !nb) return nullptr;
+    static thread_local char name[64];
+    if (chain_pair_side_by_side(ra, rb)) snprintf(name, sizeof name, "pair(%s)", na);
+    else snprintf(name, sizeof name, "seq(%s;%s)", na, nb);
+    return name;
 }
 
 int rover_set_option(rover_ctx* c, const char* name, int64_t value) {

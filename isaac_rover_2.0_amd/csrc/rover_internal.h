@@ -200,6 +200,10 @@ struct LinearArgs {
     float* y; int64_t y_stride;            // [M, N] rows at y_stride floats
     int32_t M, K, N, act;                  // act: 0 none, 1 leakyrelu(0.01), 2 tanh, 3 relu, 4 elu
 };
+// the instantiation a layer runs (rover_mlp.hip): linear_act_kernel<nt, nw> on ny column tiles (grid.y); nw = 0: refused
+struct LinearRoute { int nw, nt, ny; };
+LinearRoute linear_route(int M, int N);
+const char* linear_route_name(const LinearRoute& r);      // "linear_act<3,4>x2", or NULL
 hipError_t launch_linear_act(const LinearArgs& a, hipStream_t s);
 
 // a chain of 2 or 4 layers in one kernel (rover_mlp.hip): y = L_n(... L_1(x)), L_i(v) = act_i(W_i v + b_i)
@@ -211,15 +215,21 @@ struct ChainArgs {
     int32_t act[4];
     float* y; int64_t y_stride;            // [M, n_last] rows at y_stride floats
 };
-hipError_t launch_chain(const ChainArgs& a, hipStream_t s);
-// small batches: a 2-layer chain with its first layer split along k (rover_mlp.hip); scratch holds chain_splitk_scratch_floats() floats
-bool chain_wants_splitk(const ChainArgs& a);
+// which kernel runs a chain, decided once from M, K0, the widths and the activations (no pointer is read): split-k (a 2-layer chain
+// at small batches, first layer split along k through a scratch buffer; tn output tiles, rt row tiles per wave), mlp_small (a 4-layer
+// net at small batches) or chain16 with the tile shape the widths need; None: outside the built tile shapes
+enum class ChainKernel { None, SplitK, MlpSmall, Chain16_5, Chain16_6, Chain16Long };
+struct ChainRoute { ChainKernel kernel; int tn, rt; };
+ChainRoute chain_route(const ChainArgs& a);
+const char* chain_route_name(const ChainRoute& r);        // "splitk<6,2>", "chain16<16,10,8,1>", ..., or NULL
+// split-k: scratch holds chain_splitk_scratch_floats() floats
 size_t chain_splitk_scratch_floats(int M, int K0, int n0);
-hipError_t launch_chain_splitk(const ChainArgs& a, float* scratch, hipStream_t s);
-// two such chains over the same rows in one launch per stage (+ an optional column copy), when chain_pair_fits()
-bool chain_pair_fits(const ChainArgs& a, const ChainArgs& b);
-hipError_t launch_chain_splitk_pair(const ChainArgs& a, const ChainArgs& b, float* scratch_a, float* scratch_b, const float* copy_src,
-                                    int64_t copy_src_stride, float* copy_dst, int64_t copy_dst_stride, int copy_cols, hipStream_t s);
+hipError_t launch_chain(const ChainArgs& a, const ChainRoute& r, float* split_k_scratch, hipStream_t s);
+// two split-k chains over the same rows in one launch per stage (+ an optional column copy), when chain_pair_side_by_side()
+bool chain_pair_side_by_side(const ChainRoute& ra, const ChainRoute& rb);
+hipError_t launch_chain_splitk_pair(const ChainArgs& a, const ChainArgs& b, const ChainRoute& r, float* scratch_a, float* scratch_b,
+                                    const float* copy_src, int64_t copy_src_stride, float* copy_dst, int64_t copy_dst_stride, int copy_cols,
+                                    hipStream_t s);
 
 // blocks of bs threads (or items) that cover n: the launchers' grid sizes
 static inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }

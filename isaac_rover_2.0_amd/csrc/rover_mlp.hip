@@ -100,16 +100,24 @@ __global__ void __launch_bounds__(64 * NW) linear_act_kernel(LinearArgs a) {
     }
 }
 
+// 128-row workgroups holding all N columns need M >= 128 * 512 rows to put two of them on each of the 256 CUs; below that one wave per
+// workgroup and one 32-column tile per workgroup (grid.y), e.g. 4 096 x 80 -> 128 x 3 workgroups.
+// 6-8 accumulator tiles per wave (248-312 VGPRs) leave one wave per SIMD and nothing to overlap the staging with: those layers are split
+// into column halves over grid.y (the A tile is read twice, from L2): 124 -> 256 at 65 536 rows 134 -> 88 us (5 tiles as 3 + 2 was
+// slower: 78 -> 113 us)
+LinearRoute linear_route(int M, int N) {
+    if (M < 0 || N <= 0 || N > 256) return LinearRoute{0, 0, 0};
+    if (M >= 128 * 512) {
+        const int nt_all = (N + 31) / 32, ny = nt_all > 5 ? 2 : 1;
+        return LinearRoute{4, (nt_all + ny - 1) / ny, ny};
+    }
+    return LinearRoute{1, 1, (N + 31) / 32};
+}
+
 template <int NW>
-static hipError_t launch_linear_nw(const LinearArgs& a, hipStream_t s) {
-    const uint32_t nb = (uint32_t)((a.M + 32 * NW - 1) / (32 * NW));
-    const int nt_all = (a.N + 31) / 32;
-    // 6-8 accumulator tiles per wave (248-312 VGPRs) leave one wave per SIMD and nothing to overlap the staging with: those
-    // layers are split into column halves over grid.y (the A tile is read twice, from L2): 124 -> 256 at 65 536 rows 134 -> 88 us
-    // (5 tiles as 3 + 2 was slower: 78 -> 113 us)
-    const int ny = nt_all > 5 ? 2 : 1, nt = (nt_all + ny - 1) / ny;
-    const dim3 grid(nb, (uint32_t)ny);
-    switch (nt) {
+static hipError_t launch_linear_nw(const LinearArgs& a, const LinearRoute& r, hipStream_t s) {
+    const dim3 grid((uint32_t)((a.M + 32 * NW - 1) / (32 * NW)), (uint32_t)r.ny);
+    switch (r.nt) {
         case 1: hipLaunchKernelGGL((linear_act_kernel<1, NW>), grid, dim3(64 * NW), 0, s, a); break;
         case 2: hipLaunchKernelGGL((linear_act_kernel<2, NW>), grid, dim3(64 * NW), 0, s, a); break;
         case 3: hipLaunchKernelGGL((linear_act_kernel<3, NW>), grid, dim3(64 * NW), 0, s, a); break;
@@ -121,11 +129,10 @@ static hipError_t launch_linear_nw(const LinearArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_linear_act(const LinearArgs& a, hipStream_t s) {
-    // 128-row workgroups holding all N columns need M >= 128 * 512 rows to put two of them on each of the 256 CUs; below that
-    // one wave per workgroup and one 32-column tile per workgroup (grid.y), e.g. 4 096 x 80 -> 128 x 3 workgroups
-    if (a.M >= 128 * 512) return launch_linear_nw<4>(a, s);
-    if (a.N > 256) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((linear_act_kernel<1, 1>), dim3((uint32_t)((a.M + 31) / 32), (uint32_t)((a.N + 31) / 32)), dim3(64), 0, s, a);
+    const LinearRoute r = linear_route(a.M, a.N);
+    if (r.nw == 4) return launch_linear_nw<4>(a, r, s);
+    if (r.nw != 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((linear_act_kernel<1, 1>), dim3((uint32_t)((a.M + 31) / 32), (uint32_t)r.ny), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 
@@ -540,13 +547,9 @@ size_t chain_splitk_scratch_floats(int M, int K0, int n0) {
     const int S = splitk_chunks(M, K0, &chunk, &rt);
     return (size_t)S * (size_t)M * (size_t)(n0 <= 80 ? 80 : 96);
 }
-// (the same nets at every batch size: what the large-batch 2-layer kernel is built for, <= 96 -> <= 64)
-bool chain_wants_splitk(const ChainArgs& a) { return a.n_layers == 2 && a.M < 20480 && a.K0 >= 128 && a.n[0] <= 96 && a.n[1] <= 64; }
-
-static int splitk_tn(const ChainArgs& a) { return a.n[0] <= 80 ? 5 : 6; }
-static SplitkL1 splitk_l1_of(const ChainArgs& a, float* scratch, int* rt) {
-    int chunk;
-    const int S = splitk_chunks(a.M, a.K0, &chunk, rt);
+static SplitkL1 splitk_l1_of(const ChainArgs& a, float* scratch) {
+    int chunk, rt;
+    const int S = splitk_chunks(a.M, a.K0, &chunk, &rt);
     return SplitkL1{a.x, a.x_stride, a.K0, a.w[0], a.n[0], chunk, S, scratch};
 }
 static SplitkFin splitk_fin_of(const ChainArgs& a, const SplitkL1& l) {
@@ -560,31 +563,29 @@ static void launch_splitk_tn(const SplitkL1Pair& l, const SplitkFinPair& f, int 
     else hipLaunchKernelGGL((splitk_layer1_kernel<TN, 1>), g1, dim3(64), 0, s, l);
     hipLaunchKernelGGL((splitk_finish_kernel<TN>), g2, dim3(256), 0, s, f);
 }
-hipError_t launch_chain_splitk(const ChainArgs& a, float* scratch, hipStream_t s) {
-    int rt;
+static hipError_t launch_chain_splitk(const ChainArgs& a, const ChainRoute& r, float* scratch, hipStream_t s) {
     SplitkL1Pair l{}; SplitkFinPair f{};
     l.M = f.M = a.M;
-    l.c[0] = splitk_l1_of(a, scratch, &rt);
+    l.c[0] = splitk_l1_of(a, scratch);
     f.c[0] = splitk_fin_of(a, l.c[0]);
-    if (splitk_tn(a) == 5) launch_splitk_tn<5>(l, f, 1, rt, s); else launch_splitk_tn<6>(l, f, 1, rt, s);
+    if (r.tn == 5) launch_splitk_tn<5>(l, f, 1, r.rt, s); else launch_splitk_tn<6>(l, f, 1, r.rt, s);
     return hipGetLastError();
 }
-// two chains over the same rows side by side (both chain_wants_splitk, the same tile shape: the caller checks); scratch_b follows
-// chain a's part of the scratch buffer
-bool chain_pair_fits(const ChainArgs& a, const ChainArgs& b) {
-    return a.M == b.M && chain_wants_splitk(a) && chain_wants_splitk(b) && splitk_tn(a) == splitk_tn(b);
+// two chains over the same rows side by side (both split-k with the same tile shape); scratch_b follows chain a's part of the scratch buffer
+bool chain_pair_side_by_side(const ChainRoute& ra, const ChainRoute& rb) {
+    return ra.kernel == ChainKernel::SplitK && rb.kernel == ChainKernel::SplitK && ra.tn == rb.tn;      // (rt depends on M only)
 }
-hipError_t launch_chain_splitk_pair(const ChainArgs& a, const ChainArgs& b, float* scratch_a, float* scratch_b, const float* copy_src,
-                                    int64_t copy_src_stride, float* copy_dst, int64_t copy_dst_stride, int copy_cols, hipStream_t s) {
-    int rt, rt_b;
+hipError_t launch_chain_splitk_pair(const ChainArgs& a, const ChainArgs& b, const ChainRoute& r, float* scratch_a, float* scratch_b,
+                                    const float* copy_src, int64_t copy_src_stride, float* copy_dst, int64_t copy_dst_stride, int copy_cols,
+                                    hipStream_t s) {
     SplitkL1Pair l{}; SplitkFinPair f{};
     l.M = f.M = a.M;
-    l.c[0] = splitk_l1_of(a, scratch_a, &rt);
-    l.c[1] = splitk_l1_of(b, scratch_b, &rt_b);                       // (rt depends on M only)
+    l.c[0] = splitk_l1_of(a, scratch_a);
+    l.c[1] = splitk_l1_of(b, scratch_b);
     f.c[0] = splitk_fin_of(a, l.c[0]);
     f.c[1] = splitk_fin_of(b, l.c[1]);
     f.copy_src = copy_src; f.copy_src_stride = copy_src_stride; f.copy_dst = copy_dst; f.copy_dst_stride = copy_dst_stride; f.copy_cols = copy_cols;
-    if (splitk_tn(a) == 5) launch_splitk_tn<5>(l, f, 2, rt, s); else launch_splitk_tn<6>(l, f, 2, rt, s);
+    if (r.tn == 5) launch_splitk_tn<5>(l, f, 2, r.rt, s); else launch_splitk_tn<6>(l, f, 2, r.rt, s);
     return hipGetLastError();
 }
 
@@ -647,27 +648,58 @@ __global__ void __launch_bounds__(512) mlp_small_kernel(ChainArgs a) {
 }
 
 // tile shapes instantiated: the reference's encoder (<= 80 -> <= 64, or <= 96 -> <= 64) and MLP (<= 256 -> <= 160 -> <= 128 -> <= 16,
-// hidden activations none / LeakyReLU / ReLU); anything else: hipErrorInvalidValue (the caller runs layer by layer)
-hipError_t launch_chain(const ChainArgs& a, hipStream_t s) {
+// hidden activations none / LeakyReLU / ReLU); anything else: ChainKernel::None (the caller runs layer by layer).  The same nets go
+// to the same kernels at every batch size: split-k (2 layers) and mlp_small (4 layers) below 20 480 rows, chain16 from there on.
+ChainRoute chain_route(const ChainArgs& a) {
     auto cheap = [](int act) { return act == 0 || act == 1 || act == 3; };
-    // (the same nets at every batch size: what the large-batch kernel is built for)
     const bool mlp4 = a.n_layers == 4 && a.n[0] <= 256 && a.n[1] <= 160 && a.n[2] <= 128 && a.n[3] <= 16 && cheap(a.act[0]) && cheap(a.act[1]) &&
                       cheap(a.act[2]);
-    if (mlp4 && a.M < 20480 && a.K0 <= 256) {
-        hipLaunchKernelGGL(mlp_small_kernel, dim3((uint32_t)((a.M + 15) / 16)), dim3(512), 0, s, a);      // small batches: latency, not throughput
-        return hipGetLastError();
-    }
-    const dim3 grid((uint32_t)((a.M + 127) / 128));
-    if (a.n_layers == 2 && a.n[0] <= 80 && a.n[1] <= 64) {
-        hipLaunchKernelGGL((chain16_kernel<5, 4, 0, 0>), grid, dim3(512), 0, s, a);
-    } else if (a.n_layers == 2 && a.n[0] <= 96 && a.n[1] <= 64) {
-        hipLaunchKernelGGL((chain16_kernel<6, 4, 0, 0>), grid, dim3(512), 0, s, a);
+    ChainRoute r{ChainKernel::None, 0, 0};
+    if (a.n_layers == 2 && a.n[0] <= 96 && a.n[1] <= 64) {
+        r.tn = a.n[0] <= 80 ? 5 : 6;
+        if (a.M < 20480 && a.K0 >= 128) {                           // small batches: first layer split along k through a scratch buffer
+            int chunk;
+            splitk_chunks(a.M, a.K0, &chunk, &r.rt);
+            r.kernel = ChainKernel::SplitK;
+        } else {
+            r.kernel = r.tn == 5 ? ChainKernel::Chain16_5 : ChainKernel::Chain16_6;
+        }
     } else if (mlp4) {
-        hipLaunchKernelGGL((chain16_kernel<16, 10, 8, 1>), grid, dim3(512), 0, s, a);
-    } else {
-        return hipErrorInvalidValue;
+        r.kernel = a.M < 20480 && a.K0 <= 256 ? ChainKernel::MlpSmall : ChainKernel::Chain16Long;     // small batches: latency, not throughput
+    }
+    return r;
+}
+
+hipError_t launch_chain(const ChainArgs& a, const ChainRoute& r, float* scratch, hipStream_t s) {
+    const dim3 grid((uint32_t)((a.M + 127) / 128));
+    switch (r.kernel) {
+        case ChainKernel::SplitK: return launch_chain_splitk(a, r, scratch, s);
+        case ChainKernel::MlpSmall: hipLaunchKernelGGL(mlp_small_kernel, dim3((uint32_t)((a.M + 15) / 16)), dim3(512), 0, s, a); break;
+        case ChainKernel::Chain16_5: hipLaunchKernelGGL((chain16_kernel<5, 4, 0, 0>), grid, dim3(512), 0, s, a); break;
+        case ChainKernel::Chain16_6: hipLaunchKernelGGL((chain16_kernel<6, 4, 0, 0>), grid, dim3(512), 0, s, a); break;
+        case ChainKernel::Chain16Long: hipLaunchKernelGGL((chain16_kernel<16, 10, 8, 1>), grid, dim3(512), 0, s, a); break;
+        default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+// the instantiation a route launches, by name (rover_linear_route / rover_mlp_chain_route)
+const char* linear_route_name(const LinearRoute& r) {
+    static const char* const wide[2][5] = {{"linear_act<1,4>", "linear_act<2,4>", "linear_act<3,4>", "linear_act<4,4>", "linear_act<5,4>"},
+                                           {"linear_act<1,4>x2", "linear_act<2,4>x2", "linear_act<3,4>x2", "linear_act<4,4>x2", "linear_act<5,4>x2"}};
+    if (r.nw == 1) return "linear_act<1,1>";
+    if (r.nw == 4 && r.nt >= 1 && r.nt <= 5 && (r.ny == 1 || r.ny == 2)) return wide[r.ny - 1][r.nt - 1];
+    return nullptr;
+}
+const char* chain_route_name(const ChainRoute& r) {
+    switch (r.kernel) {
+        case ChainKernel::SplitK: return r.tn == 5 ? (r.rt == 2 ? "splitk<5,2>" : "splitk<5,1>") : (r.rt == 2 ? "splitk<6,2>" : "splitk<6,1>");
+        case ChainKernel::MlpSmall: return "mlp_small";
+        case ChainKernel::Chain16_5: return "chain16<5,4,0,0>";
+        case ChainKernel::Chain16_6: return "chain16<6,4,0,0>";
+        case ChainKernel::Chain16Long: return "chain16<16,10,8,1>";
+        default: return nullptr;
+    }
 }
 
 }  // namespace rover

@@ -121,6 +121,32 @@ def test_c_abi_exports_every_declared_symbol():
     assert not any(s.startswith("oracle_") for s in exported)      # the product never links the oracle
 
 
+def test_mlp_routes_at_switch_points():
+    """The policy-net dispatch rules on both sides of every switch point, from the route query alone (no GPU): rows 20 479 / 20 480
+    (split-k and mlp_small against chain16), 2 047 / 2 048 (split-k row tiles), 65 535 / 65 536 (linear_act workgroups), K0 127 / 128
+    and 256 / 257, first widths 80 / 81 and 96 / 97; refusals are NULL, empty batches "none"."""
+    from isaac_rover_amd._lib import Engine as E
+    enc = lambda n0=80, n1=60: ((n0, n1), ("leakyrelu", "leakyrelu"))
+    mlp = ((256, 160, 128, 2), ("leakyrelu", "leakyrelu", "leakyrelu", "tanh"))
+    assert [E.chain_route(m, 634, *enc()) for m in (1, 2047, 2048, 20479, 20480)] == \
+        ["splitk<5,1>", "splitk<5,1>", "splitk<5,2>", "splitk<5,2>", "chain16<5,4,0,0>"]
+    assert [E.chain_route(17, k, *enc(n0)) for k, n0 in ((127, 80), (128, 80), (128, 81), (128, 96))] == \
+        ["chain16<5,4,0,0>", "splitk<5,1>", "splitk<6,1>", "splitk<6,1>"]
+    assert E.chain_route(17, 128, *enc(97)) is None and E.chain_route(17, 128, *enc(96, 65)) is None
+    assert [E.chain_route(m, k, *mlp) for m, k in ((20479, 256), (20479, 257), (20480, 124), (1, 1))] == \
+        ["mlp_small", "chain16<16,10,8,1>", "chain16<16,10,8,1>", "mlp_small"]
+    assert E.chain_route(300, 124, (256, 160, 128, 2), ("tanh", "relu", "relu", "tanh")) is None        # tanh on a hidden layer
+    assert E.chain_route(300, 124, (257, 160, 128, 2), mlp[1]) is None and E.chain_route(300, 124, (256, 160, 128), ("relu",) * 3) is None
+    assert E.chain_route(0, 124, *mlp) == "none" and E.chain_route(-1, 124, *mlp) is None and E.chain_route(1, 0, *mlp) is None
+    assert [E.linear_route(m, 5, n) for m, n in ((65535, 256), (65536, 32), (65536, 33), (65536, 160), (65536, 161), (65536, 193))] == \
+        ["linear_act<1,1>", "linear_act<1,4>", "linear_act<2,4>", "linear_act<5,4>", "linear_act<3,4>x2", "linear_act<4,4>x2"]
+    assert E.linear_route(1, 5, 257) is None and E.linear_route(1, -1, 5) is None and E.linear_route(0, 0, 5) == "none"
+    a, b = (634,) + enc(), (1112,) + enc()
+    assert E.chain_pair_route(20479, a, b) == "pair(splitk<5,2>)" and E.chain_pair_route(20480, a, b) == "seq(chain16<5,4,0,0>;chain16<5,4,0,0>)"
+    assert E.chain_pair_route(17, a, (1112,) + enc(96)) == "seq(splitk<5,1>;splitk<6,1>)"
+    assert E.chain_pair_route(17, a, (1112,) + enc(97)) is None
+
+
 def test_product_never_imports_oracle():
     """The oracle is test infrastructure: no import, include, link or dlopen of it in the shipped package."""
     pkg = os.path.join(ROOT, "isaac_rover_2.0_amd")
