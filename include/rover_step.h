@@ -409,6 +409,26 @@ typedef struct {
     int32_t raycast_rocks_staged;  /* variant 4: 1 = the rocks part of the sorted list runs on the staged kernel too, 0 = on the culled one */
 } rover_info;
 ROVER_API int rover_get_info(const rover_ctx *ctx, rover_info *info);
+/* The whole ray-cast plan in force (what the next step's ray cast will run) and the other host-side values that select a code path of
+ * a step — host only: copies what the ctx already holds, launches nothing, does not synchronise.  Tests assert it field by field, so
+ * that they know which kernel instantiation and traversal they exercised. */
+typedef struct {
+    int32_t variant;               /* 0: a map is missing; 1 env-order kernel, 2 binned, 3 culled, 4 staged */
+    int32_t proof;                 /* the proof tables in force: 1 for the as-shipped fp16 arithmetic (ray_precision 2), else 0 */
+    int32_t sorted;                /* the bucket sort by (map, cell) runs before the ray cast */
+    int32_t env_order;             /* variant 4 over the ray slots in env order, one launch */
+    int32_t rocks_staged;          /* variant 4: the rocks part on the staged kernel too (0: the culled kernel casts it, a second launch) */
+    int32_t run;                   /* rays per wave of the sorted launches */
+    int32_t env_run;               /* slots per wave of the staged kernel in env order (0 unless env_order) */
+    int32_t lazy_far;              /* culled kernel: a bin's far records fetched only when a ray needs them */
+    int32_t skip_clear;            /* culled kernel: rays that clear their whole cell left out of the scan */
+    int32_t cull_launches;         /* launches the queue budget ("cull_queue_mb") cuts a culled ray cast over the whole ray set into
+                                      (rover_cull_info.launches_per_step); 0: no candidate queue (variants 1, 2, or nothing to plan yet) */
+    int32_t low_bits;              /* width of the low digit of the bucket sort in force ("bin_low_bits") */
+    int32_t sort_entry_dwords;     /* 1: a sort entry is low bin bits | slot id in one dword, 2: (bin, slot); 0: the step does not sort */
+    int32_t hist_fused;            /* 1: prep_rays_kernel counts the sort's coarse buckets itself (one launch less); 0 also when the step does not sort */
+} rover_raycast_plan;
+ROVER_API int rover_get_raycast_plan(const rover_ctx *ctx, rover_raycast_plan *out);
 /* Diagnostics of the culled ray cast (variant 3, csrc/rover_cull.hip).  Per map: how many triangles its conservative
  * rejection test can never reject (slivers, non-finite vertices: stored with a zero normal = "always a candidate") and how
  * many cells have no normal cone (their rays run both tests on every pair).  Of the LAST culled launch on this ctx: rays

@@ -68,6 +68,11 @@ class CullInfo(C.Structure):
                 ("lane_items", C.c_uint64), ("lane_flushes", C.c_uint64)]
 
 
+class RaycastPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("variant", "proof", "sorted", "env_order", "rocks_staged", "run", "env_run", "lazy_far",
+                                         "skip_clear", "cull_launches", "low_bits", "sort_entry_dwords", "hist_fused")]
+
+
 class ChainDesc(C.Structure):
     _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64), ("K0", C.c_int32), ("n_layers", C.c_int32), ("weights", C.c_void_p),
                 ("biases", C.c_void_p), ("widths", C.c_void_p), ("activations", C.c_void_p), ("y", C.c_void_p), ("y_stride", C.c_int64)]
@@ -118,6 +123,7 @@ SYMBOLS = {
     "rover_ackermann": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P]),
     "rover_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "rover_get_cull_info": (C.c_int, [_P, C.POINTER(CullInfo)]),
+    "rover_get_raycast_plan": (C.c_int, [_P, C.POINTER(RaycastPlan)]),
     "rover_replay_raycast": (C.c_int, [_P, _P]),
     "rover_build_knn_map": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
     "rover_build_knn_map_ref": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P]),
@@ -298,6 +304,13 @@ class Engine:
         i = Info()
         self._check(self.lib.rover_get_info(self._h, C.byref(i)), "rover_get_info")
         return i
+
+    def raycast_plan(self):
+        """The ray-cast plan in force and the other host-side values that select a step's code path (rover_get_raycast_plan) as a
+        plain dict of ints; host only, no launch, no synchronisation."""
+        p = RaycastPlan()
+        self._check(self.lib.rover_get_raycast_plan(self._h, C.byref(p)), "rover_get_raycast_plan")
+        return {k: int(getattr(p, k)) for k, _ in RaycastPlan._fields_}
 
     def cull_info(self):
         """Diagnostics of the culled ray cast (rover_get_cull_info) as a dict; synchronises the device."""

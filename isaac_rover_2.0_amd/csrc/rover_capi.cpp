@@ -867,6 +867,11 @@ static int check_queue(rover_ctx* c, const RayPlan& p) {
     return ROVER_OK;
 }
 
+// the sort of plan p's steps (its own rays, not caller-supplied ones) has its first pass inside prep_rays_kernel
+static bool hist_fused_for(const rover_ctx* c, const RayPlan& p, uint32_t* blocks_per_tile) {
+    return p.sorted && c->have_dist && bin_hist_fused((uint32_t)c->cfg.num_envs * c->R8, c->R8, c->n_bins, c->low_bits, blocks_per_tile);
+}
+
 // the ray-cast launch(es) of plan p, on the ray records / sorted list in the workspace
 static int run_raycast(rover_ctx* c, const RayPlan& p, uint32_t n_valid, hipStream_t s) {
     const uint32_t E = (uint32_t)c->cfg.num_envs;
@@ -945,7 +950,7 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
     // the sort's first pass (keys per coarse bucket and tile) inside prep_rays_kernel where a 64-env block's keys lie in one tile: the
     // table is zero between steps (allocation, then the sort's last kernel) — unless a step failed half way
     // (caller-supplied rays, rover_cast_rays: import_rays_kernel writes the records and keys, the sort counts its keys itself)
-    const bool hist_fused = !import_src && sorts && bin_hist_fused(E * c->R8, c->R8, c->n_bins, c->low_bits, &p.hist_blocks_per_tile);
+    const bool hist_fused = !import_src && hist_fused_for(c, plan, &p.hist_blocks_per_tile);
     if (hist_fused) {
         if (c->bkt_table_dirty) HIP_TRY(c, hipMemsetAsync(c->d_bkt_table.get(), 0, c->d_bkt_table.bytes(), s));
         c->bkt_table_dirty = true;
@@ -1339,6 +1344,21 @@ int rover_get_info(const rover_ctx* c, rover_info* info) {
     info->cell_index_mode = c->cell_rcp; info->ray_precision = c->precision;
     info->raycast_sorted = c->plan.sorted ? 1 : 0;
     info->raycast_rocks_staged = c->plan.rocks_staged ? 1 : 0;
+    return ROVER_OK;
+}
+
+int rover_get_raycast_plan(const rover_ctx* c, rover_raycast_plan* out) {
+    if (!c || !out) return ROVER_E_INVALID;
+    memset(out, 0, sizeof *out);
+    const RayPlan& p = c->plan;
+    out->variant = p.variant; out->proof = p.proof; out->sorted = p.sorted ? 1 : 0; out->env_order = p.env_order ? 1 : 0;
+    out->rocks_staged = p.rocks_staged ? 1 : 0; out->run = (int32_t)p.run; out->env_run = (int32_t)p.env_run;
+    out->lazy_far = p.lazy_far ? 1 : 0; out->skip_clear = p.skip_clear ? 1 : 0;
+    out->cull_launches = p.variant >= 3 && c->d_cull_queue.get() ? (int32_t)c->cull_launches : 0;      // (a queue of an earlier plan may still be there)
+    out->low_bits = (int32_t)c->low_bits;
+    uint32_t blocks_per_tile = 0;
+    out->sort_entry_dwords = p.sorted && c->have_dist ? (bin_entries_packed((uint32_t)c->cfg.num_envs * c->R8, c->low_bits) ? 1 : 2) : 0;
+    out->hist_fused = hist_fused_for(c, p, &blocks_per_tile) ? 1 : 0;
     return ROVER_OK;
 }
 

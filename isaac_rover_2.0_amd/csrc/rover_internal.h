@@ -241,6 +241,8 @@ hipError_t launch_raycast(const RayRec* rays, uint32_t n_rays, const uint16_t* t
                           uint32_t kp1, float* out, hipStream_t s);
 // true when prep_rays_kernel can count the sort's coarse buckets itself (PrepArgs::hist): a 64-env block's keys lie inside one tile of the sort
 bool bin_hist_fused(uint32_t n_slots, uint32_t R8, uint32_t n_bins, uint32_t low_bits, uint32_t* blocks_per_tile);
+// true when launch_bin_rays sorts one-dword entries (low bin bits | slot id) for this many slots, false for (bin, slot) pairs
+bool bin_entries_packed(uint32_t n_slots, uint32_t low_bits);
 hipError_t launch_bin_rays(const uint32_t* bins, uint32_t n_slots, uint32_t n_valid, uint32_t n_bins, uint32_t low_bits,
                            uint32_t* table, uint2* pairs, uint32_t* block_sums, uint32_t* sorted, bool hist_done, hipStream_t s);
 hipError_t launch_raycast_binned(const RayRec* rays, const uint32_t* sorted, uint32_t n_sorted, const uint16_t* tab0,

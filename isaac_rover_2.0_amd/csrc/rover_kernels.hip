@@ -1720,9 +1720,11 @@ hipError_t launch_scan_exclusive(uint32_t* data, uint32_t n, uint32_t* block_sum
 // tile of the sort's first two passes: 4 096 slots per 256-thread block; from 2 M slots 16 384 per 1 024-thread block — a (block, bucket)
 // run of the scatter is then ~23 entries instead of ~6 (its partial-line writes were 9 of its 21 us at 65 536 envs) and the count
 // table a quarter of the rows; small batches keep the small tile (more blocks than CUs matter more there)
+// a sort entry is one dword — slot ids leave room for the low bin bits — (else (bin, slot) as two): the one place that decides it
+bool bin_entries_packed(uint32_t n_slots, uint32_t low_bits) { return (uint64_t)n_slots <= (1ull << (32u - low_bits)); }
 static inline uint32_t bin_tile_threads(uint32_t n_slots, uint32_t low_bits, bool* packed_out) {
     const bool big = n_slots >= (2u << 20);
-    const bool packed = (uint64_t)n_slots <= (1ull << (32u - low_bits));          // slot ids leave room for the low bin bits: one dword per entry
+    const bool packed = bin_entries_packed(n_slots, low_bits);
     if (packed_out) *packed_out = packed;
     return big ? (packed ? 1024u : 512u) : 256u;                                  // (two-dword entries: 12 bytes of LDS per slot, 8 192 slots)
 }

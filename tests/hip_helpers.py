@@ -1,4 +1,5 @@
 """Helpers for the -m gpu parity tests: drive the HIP path through the C ABI (isaac_rover_amd._lib)."""
+import numpy as np
 import torch
 
 from isaac_rover_amd import _lib
@@ -62,3 +63,33 @@ def hip_step(eng, st, compact=True, fused=True, stone_margin=None):
     n = int(bufs["n_reset"].item())
     out["reset_ids"] = bufs["reset_ids"][:n].cpu().numpy()
     return out
+
+
+def _oracle_maps(scene):
+    from oracle import oracle as orc
+    return (orc.KnnMap(scene.terrain.map_indices, scene.terrain.triangles, scene.terrain.vertices),
+            orc.KnnMap(scene.rocks.map_indices, scene.rocks.triangles, scene.rocks.vertices))
+
+
+def _rays_vs_oracle(eng, maps, half, label):
+    """The ray phase on its own, free of the pose trigonometry: the device's OWN rays of the last step (origins and ray-record
+    directions as prep_rays_kernel made them, `rover_export_rays`) through the oracle's per-ray arithmetic (ray_casting.py:34-59 + the
+    cell lookup + min over K, `oracle.raycast_unit`) must give the device's distances bit for bit — every ray, both maps.
+    -> (origins, cells, the oracle's distances [E][26 + P])"""
+    from oracle import oracle as orc
+    src, dirs, cell, dist = (x.cpu().numpy() for x in eng.export_rays())
+    t, r = maps
+    want_rock = orc.raycast_unit(r, src[:, :26], dirs[:, :26], half=half).reshape(dist[:, :26].shape)
+    want_terr = orc.raycast_unit(t, src[:, 26:], dirs[:, 26:], half=half).reshape(dist[:, 26:].shape)
+    # equal as IEEE values (a distance of exactly zero may come out as +0 from one triangle and -0 from another: which of the two equal
+    # values a min returns is the reduction order's business — torch.min's too; 1 ray of 9.6 M at configs[4]), NaN where the oracle has NaN
+    want_all = np.concatenate((want_rock, want_terr), axis=1)
+    differ = ~((dist == want_all) | (np.isnan(dist) & np.isnan(want_all)))
+    n_bad = int(differ.sum())
+    n_bits = int((dist.view(np.uint32) != want_all.view(np.uint32)).sum())
+    print(f"[{label}] ray phase on the device's own rays vs the oracle: {n_bad} of {dist.size} distances differ ({n_bits} in their bits: +0 / -0)")
+    for e, sl in list(zip(*np.nonzero(differ)))[:8]:
+        print(f"   env {e} slot {sl}: src {src[e, sl].tolist()} ({src[e, sl].view(np.uint32).tolist()}) dir {dirs[e, sl].tolist()} "
+              f"({dirs[e, sl].view(np.uint32).tolist()}) cell {cell[e, sl]}: device {dist[e, sl]!r} oracle {want_all[e, sl]!r}")
+    assert n_bad == 0, f"{label}: {n_bad} of {dist.size} ray distances differ from the oracle on IDENTICAL rays"
+    return src, cell, want_all

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import assert_step_close
+from hip_helpers import _oracle_maps, _rays_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -205,35 +206,6 @@ def test_full_size_config4_dense_rays_and_goal_validation():
 # ALL envs against the oracle (round 4).  The C oracle (OpenMP) does ~0.3 M env-steps/s on the GPU box's host cores in fp32
 # and ~60 k in its fp16 mode, so a whole BASELINE-size batch costs it 0.2-3 s — no reason to sample.
 # ---------------------------------------------------------------------------------------------------------------------
-def _oracle_maps(scene):
-    from oracle import oracle as orc
-    return (orc.KnnMap(scene.terrain.map_indices, scene.terrain.triangles, scene.terrain.vertices),
-            orc.KnnMap(scene.rocks.map_indices, scene.rocks.triangles, scene.rocks.vertices))
-
-
-def _rays_vs_oracle(eng, maps, half, label):
-    """The ray phase on its own, free of the pose trigonometry: the device's OWN rays of the last step (origins and ray-record
-    directions as prep_rays_kernel made them, `rover_export_rays`) through the oracle's per-ray arithmetic (ray_casting.py:34-59 + the
-    cell lookup + min over K, `oracle.raycast_unit`) must give the device's distances bit for bit — every ray, both maps."""
-    from oracle import oracle as orc
-    src, dirs, cell, dist = (x.cpu().numpy() for x in eng.export_rays())
-    t, r = maps
-    want_rock = orc.raycast_unit(r, src[:, :26], dirs[:, :26], half=half).reshape(dist[:, :26].shape)
-    want_terr = orc.raycast_unit(t, src[:, 26:], dirs[:, 26:], half=half).reshape(dist[:, 26:].shape)
-    # equal as IEEE values (a distance of exactly zero may come out as +0 from one triangle and -0 from another: which of the two equal
-    # values a min returns is the reduction order's business — torch.min's too; 1 ray of 9.6 M at configs[4]), NaN where the oracle has NaN
-    want_all = np.concatenate((want_rock, want_terr), axis=1)
-    differ = ~((dist == want_all) | (np.isnan(dist) & np.isnan(want_all)))
-    n_bad = int(differ.sum())
-    n_bits = int((dist.view(np.uint32) != want_all.view(np.uint32)).sum())
-    print(f"[{label}] ray phase on the device's own rays vs the oracle: {n_bad} of {dist.size} distances differ ({n_bits} in their bits: +0 / -0)")
-    for e, sl in list(zip(*np.nonzero(differ)))[:8]:
-        print(f"   env {e} slot {sl}: src {src[e, sl].tolist()} ({src[e, sl].view(np.uint32).tolist()}) dir {dirs[e, sl].tolist()} "
-              f"({dirs[e, sl].view(np.uint32).tolist()}) cell {cell[e, sl]}: device {dist[e, sl]!r} oracle {want_all[e, sl]!r}")
-    assert n_bad == 0, f"{label}: {n_bad} of {dist.size} ray distances differ from the oracle on IDENTICAL rays"
-    return src, cell
-
-
 def _all_envs_vs_oracle(scene, distn, st, label, budget=None):
     """Two comparisons per arithmetic (fp32 parity mode, the reference's as-shipped fp16 arithmetic), each on every env:
       (a) the ray phase on identical rays (`_rays_vs_oracle`): ZERO differing distances;
@@ -255,7 +227,7 @@ def _all_envs_vs_oracle(scene, distn, st, label, budget=None):
     b.update(budget or {})
     eng = make_engine(scene, distn, n, variant=None)                 # the library's own choice of ray-cast kernel
     got = hip_step(eng, st)
-    src, cell = _rays_vs_oracle(eng, maps, False, f"{label} fp32")
+    src, cell, _ = _rays_vs_oracle(eng, maps, False, f"{label} fp32")
     eng.close()
     want = orc.step(t, r, st, *distn, num_envs_global=n, precision="fp32")
     g = dict(got)
@@ -283,7 +255,7 @@ def _all_envs_vs_oracle(scene, distn, st, label, budget=None):
         assert eng.info().raycast_variant == variant
         outs[variant] = hip_step(eng, st)
         if variant == 3:
-            src16, _ = _rays_vs_oracle(eng, maps, True, f"{label} as shipped")
+            src16, _, _ = _rays_vs_oracle(eng, maps, True, f"{label} as shipped")
         eng.close()
     for k in outs[3]:
         np.testing.assert_array_equal(outs[3][k], outs[2][k], err_msg=f"{label} as shipped: {k}, culled vs every-triangle kernel")

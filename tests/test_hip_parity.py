@@ -62,7 +62,9 @@ def test_exact_ties_follow_the_reference(name, precision, variant):
 
 @pytest.mark.parametrize("dist_name,num_envs,seed", [("37", 4096, 11), ("120", 1024, 12), ("9", 2048, 13)])
 def test_step_matches_oracle(dist_name, num_envs, seed):
-    """BASELINE.json configs[1] size (4096 envs, 37 rays) against the CPU oracle on the same seeded inputs."""
+    """Batches of BASELINE.json configs[1]'s env and ray counts (4096 envs, 37 rays) and two others against the CPU oracle on the same seeded
+    inputs — on a 128 x 128-cell, K = 24 scene through the culled kernel (make_engine's default); configs[1] itself (600 x 600 cells,
+    K = 200, the plan the library picks) is the first row of tests/test_raycast_plans_gpu.py."""
     from hip_helpers import hip_step, make_engine
     from isaac_rover_amd import synth
     from oracle import oracle as orc
