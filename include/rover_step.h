@@ -392,8 +392,14 @@ ROVER_API const char *rover_mlp_chain_pair_route(int32_t M, const rover_chain_de
  *        at K = 200 (1.56 GB at 600 x 600 cells).  Tables that are not asked for, or that do not fit (the allocation failure is absorbed:
  *        the culled kernel, variant 3, then runs), leave variant 4 unavailable for that arithmetic: the auto choice never picks it, and
  *        asking for it by name ("raycast_variant" 4) is an error (ROVER_E_STATE / ROVER_E_NOMEM), never a silent change of kernel.
- * name = "raycast_run": sorted rays per wave for variants 2 and 3 (default 0 = auto: 32 on full batches, down to 4 on small
- *        ones; variant 3 caps it at 64). */
+ * name = "raycast_run": rays per wave of the launches over the sorted list (variants 2, 3, 4) and — capped at 64 — slots per wave of
+ *        variant 4 in env order; 1..4096, variants 3 and 4 cap it at 64.  0 (default) = auto, from r = rays per step / 65 536: variant 2
+ *        r clamped to [4, 32]; variant 3 8 / 16 / 32 / 64 from r = 0 / 3 / 6 / 20 (regular terrain mesh, f32 arithmetic) or 0 / 12 /
+ *        24 / 48 (irregular mesh, or ray_precision 2); variant 4 behind the sort 32, 64 from r = 12; in env order 16, 32 from 2^17
+ *        padded ray slots, 64 from 2^20.  Results do not depend on it.
+ * Every name above but "ray_precision" and "cell_index_mode" that has a ROVER_<NAME> environment variable (ROVER_RAYCAST_VARIANT,
+ * ROVER_RAYCAST_RUN, ROVER_LANE_ENV_ORDER, ROVER_LANE_ROCKS, ROVER_BIN_LOW_BITS, ROVER_CULL_QUEUE_MB) takes its start value from it at
+ * rover_create; a value outside the option's range (and 0 = auto) is ignored there. */
 ROVER_API int rover_set_option(rover_ctx *ctx, const char *name, int64_t value);
 
 /* ---- introspection (bench / roofline) ---------------------------------------------------------------- */
@@ -429,6 +435,23 @@ typedef struct {
     int32_t hist_fused;            /* 1: prep_rays_kernel counts the sort's coarse buckets itself (one launch less); 0 also when the step does not sort */
 } rover_raycast_plan;
 ROVER_API int rover_get_raycast_plan(const rover_ctx *ctx, rover_raycast_plan *out);
+/* The same plan without a ctx and without a device, from the shapes and options alone (as rover_linear_route answers for a layer):
+ * what rover_get_raycast_plan reports on a ctx with these inputs.  The options are the fields below, named as rover_set_option names
+ * them and checked as it checks them — no environment variable is read; zero-initialise, then set lane_env_order = lane_rocks =
+ * cull_lazy = -1 and cull_queue_mb = 1536 for the defaults.  Per map (terrain, rocks): X, Y and K8 as rover_get_info reports them,
+ * cells_with_far_bound as rover_get_cull_info does, and which tables rover_set_knn_map built (the culled kernel's: K8 <= 256; the
+ * staged kernel's per proof: option "staged_tables").  ROVER_E_INVALID (rover_last_error(NULL)) for a value no ctx could hold. */
+typedef struct {
+    int32_t num_envs, P, have_dist;    /* P: heightmap rays per env (0 with have_dist = 0: no rover_set_distribution yet) */
+    int32_t ray_precision, raycast_variant, raycast_run, lane_env_order, lane_rocks, bin_low_bits;
+    int32_t cull_lazy;                 /* ROVER_CULL_LAZY: < 0 auto, 0 / else force the culled kernel's on-demand far records */
+    int64_t cull_queue_mb;
+    int32_t map_present[2], X[2], Y[2], K8[2];
+    int64_t cells_with_far_bound[2];
+    int32_t has_cull_tables[2];
+    int32_t has_staged_tables[2][2];   /* [map][proof]: 0 the f32 proof, 1 the as-shipped fp16 one */
+} rover_plan_query;
+ROVER_API int rover_plan_raycast(const rover_plan_query *query, rover_raycast_plan *out);
 /* Diagnostics of the culled ray cast (variant 3, csrc/rover_cull.hip).  Per map: how many triangles its conservative
  * rejection test can never reject (slivers, non-finite vertices: stored with a zero normal = "always a candidate") and how
  * many cells have no normal cone (their rays run both tests on every pair).  Of the LAST culled launch on this ctx: rays

@@ -73,6 +73,13 @@ class RaycastPlan(C.Structure):
                                          "skip_clear", "cull_launches", "low_bits", "sort_entry_dwords", "hist_fused")]
 
 
+class PlanQuery(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_envs", "P", "have_dist", "ray_precision", "raycast_variant", "raycast_run", "lane_env_order",
+                                         "lane_rocks", "bin_low_bits", "cull_lazy")]
+    _fields_ += [("cull_queue_mb", C.c_int64), ("map_present", C.c_int32 * 2), ("X", C.c_int32 * 2), ("Y", C.c_int32 * 2), ("K8", C.c_int32 * 2),
+                 ("cells_with_far_bound", C.c_int64 * 2), ("has_cull_tables", C.c_int32 * 2), ("has_staged_tables", (C.c_int32 * 2) * 2)]
+
+
 class ChainDesc(C.Structure):
     _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64), ("K0", C.c_int32), ("n_layers", C.c_int32), ("weights", C.c_void_p),
                 ("biases", C.c_void_p), ("widths", C.c_void_p), ("activations", C.c_void_p), ("y", C.c_void_p), ("y_stride", C.c_int64)]
@@ -124,6 +131,7 @@ SYMBOLS = {
     "rover_get_info": (C.c_int, [_P, C.POINTER(Info)]),
     "rover_get_cull_info": (C.c_int, [_P, C.POINTER(CullInfo)]),
     "rover_get_raycast_plan": (C.c_int, [_P, C.POINTER(RaycastPlan)]),
+    "rover_plan_raycast": (C.c_int, [C.POINTER(PlanQuery), C.POINTER(RaycastPlan)]),
     "rover_replay_raycast": (C.c_int, [_P, _P]),
     "rover_build_knn_map": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
     "rover_build_knn_map_ref": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P]),
@@ -144,11 +152,15 @@ SYMBOLS = {
 _lib = None
 
 
+def _sources():
+    """The files the library is built from (csrc/SOURCES, one per line, relative to csrc/): build.sh compiles and hashes the same list."""
+    with open(os.path.join(_CSRC, "SOURCES")) as f:
+        return [os.path.join(_CSRC, line.strip()) for line in f if line.strip()]
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library in-tree (hipcc cross-compiles gfx950 without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("rover_capi.cpp", "rover_kernels.hip", "rover_cull.hip", "rover_mlp.hip", "rover_internal.h",
-                                             "rover_raymath.h", "build.sh")]
-    srcs.append(os.path.join(os.path.dirname(_CSRC), "..", "include", "rover_step.h"))
+    srcs = _sources() + [os.path.join(_CSRC, "SOURCES"), os.path.join(_CSRC, "build.sh")]
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["bash", os.path.join(_CSRC, "build.sh")])
@@ -180,10 +192,32 @@ def source_hash() -> str:
     """The same hash computed from the source files in the tree (what a fresh build.sh would embed)."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("rover_capi.cpp", "rover_kernels.hip", "rover_cull.hip", "rover_mlp.hip", "rover_internal.h", "rover_raymath.h"):
-        h.update(open(os.path.join(_CSRC, f), "rb").read())
-    h.update(open(os.path.join(os.path.dirname(_CSRC), "..", "include", "rover_step.h"), "rb").read())
+    for f in _sources():
+        h.update(open(f, "rb").read())
     return h.hexdigest()[:12]
+
+
+def plan_raycast(num_envs, maps, P=0, have_dist=None, ray_precision=0, raycast_variant=0, raycast_run=0, lane_env_order=-1, lane_rocks=-1,
+                 bin_low_bits=0, cull_lazy=-1, cull_queue_mb=1536):
+    """rover_plan_raycast: the plan a ctx with these inputs reports (Engine.raycast_plan()), from shapes and options alone — no ctx, no
+    device, no environment variable.  ``maps``: (terrain, rocks), each None (not set) or a dict X, Y, K8, cells_with_far_bound,
+    has_cull_tables, has_staged_tables = (f32 proof, fp16 proof).  ``have_dist`` defaults to P > 0."""
+    q = PlanQuery(num_envs=int(num_envs), P=int(P), have_dist=int(P > 0 if have_dist is None else have_dist), ray_precision=int(ray_precision),
+                  raycast_variant=int(raycast_variant), raycast_run=int(raycast_run), lane_env_order=int(lane_env_order), lane_rocks=int(lane_rocks),
+                  bin_low_bits=int(bin_low_bits), cull_lazy=int(cull_lazy), cull_queue_mb=int(cull_queue_mb))
+    for w, m in enumerate(maps):
+        if m is None:
+            continue
+        q.map_present[w], q.X[w], q.Y[w], q.K8[w] = 1, int(m["X"]), int(m["Y"]), int(m["K8"])
+        q.cells_with_far_bound[w], q.has_cull_tables[w] = int(m["cells_with_far_bound"]), int(m["has_cull_tables"])
+        for k in range(2):
+            q.has_staged_tables[w][k] = int(m["has_staged_tables"][k])
+    out = RaycastPlan()
+    lib = load()
+    rc = lib.rover_plan_raycast(C.byref(q), C.byref(out))
+    if rc != 0:
+        raise RoverError(f"rover_plan_raycast failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return {k: int(getattr(out, k)) for k, _ in RaycastPlan._fields_}
 
 
 def _ptr(t):

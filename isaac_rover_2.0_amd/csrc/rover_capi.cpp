@@ -2,6 +2,7 @@
 // tables, argument checks, kernel sequencing.  No torch, no exceptions across the boundary.
 #include "../../include/rover_step.h"
 #include "rover_internal.h"
+#include "rover_plan.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -72,44 +73,22 @@ struct MapTables {
     }
 };
 
-// The ray cast of a step, decided in one place (plan_raycast) from the maps, the distribution, the options and the ROVER_* knobs read at
-// rover_create.  replan() recomputes it whenever one of them changes; steps, replays and reports read it and derive nothing themselves.
-struct RayPlan {
-    int variant = 0;                    // 0: a map is missing; 1 env-order kernel, 2 binned, 3 culled, 4 staged
-    int proof = 0;                      // the ProofTables in force: 1 for the as-shipped fp16 arithmetic (ray_precision 2), else 0
-    bool sorted = false;                // the bucket sort by (map, cell) runs before the ray cast
-    bool env_order = false;             // variant 4 over the ray slots in env order, one launch
-    bool rocks_staged = false;          // variant 4: the rocks part through the staged kernel too (else the culled kernel casts it)
-    uint32_t run = 0;                   // rays per wave of the sorted launches
-    uint32_t env_run = 0;               // slots per wave of the staged kernel in env order
-    bool lazy_far = false;              // culled kernel: a bin's far records fetched only when a ray needs them
-    bool skip_clear = false;            // culled kernel: rays that clear their whole cell left out of the scan
-    bool operator==(const RayPlan& o) const {
-        return variant == o.variant && proof == o.proof && sorted == o.sorted && env_order == o.env_order && rocks_staged == o.rocks_staged &&
-               run == o.run && env_run == o.env_run && lazy_far == o.lazy_far && skip_clear == o.skip_clear;
-    }
-    bool operator!=(const RayPlan& o) const { return !(*this == o); }
+// The candidate queue of the culled / staged ray cast and its per-wave counters, with the two facts the steps check about them
+struct CullQueue {
+    DevBuf<uint2> entries;              // one region of 1 024 entries per wave of a launch
+    DevBuf<uint4> stats;                // per-wave counters of the last culled launch (rover_get_cull_info)
+    StepPlan sized_for{};               // the plan both were sized for (alloc_cull_queue)
+    StepPlan counters_written_under{};  // the plan the counters were last written under (run_raycast)
 };
 
 struct rover_ctx {
     rover_cfg cfg{};
     std::string err;
     MapTables maps[2];                  // terrain, rocks
-    int lane_env_order = -1;            // variant 4 without the sort (the ray slots in env order): -1 auto (mid-size batches), 0 / 1 (option "lane_env_order")
-    int staged_tables = 3;              // which proofs' staged-kernel tables rover_set_knn_map builds: bit 0 the f32 proof, bit 1 the as-shipped fp16 one (option
-                                        // "staged_tables", before the maps are set; ~4.3 KB per cell, K = 200, map and proof)
-    int lane_rocks = -1;                // variant 4: the rocks part of the sorted list through the staged kernel too: -1 auto, 0 / 1 (option "lane_rocks", ROVER_LANE_ROCKS)
-    DevBuf<uint2> d_cull_queue;         // candidate queue of the culled ray cast: one region of 1 024 entries per wave of a launch
-    uint64_t cull_entries = 0;
-    DevBuf<uint4> d_cull_stats;         // per-wave counters of the last culled launch (rover_get_cull_info)
-    uint32_t cull_stat_slots = 0;
-    RayPlan queue_plan{};               // the plan the queue and counters were sized for (alloc_cull_queue)
-    RayPlan stats_plan{};               // the plan the counters were last written under (run_raycast)
-    double cull_eta_h = 0.08;           // free parameter of the fp16 proof (rover_cull.hip, cull_proof_h); ROVER_CULLH_ETA for experiments
-    double cull_split_h = 8.0;          // how test (A)'s cross term is split between its |h|^2 and rho^2 parts (cull_proof_h); ROVER_CULLH_SPLIT
-    uint64_t cull_budget = 1536ull << 20;  // option "cull_queue_mb": most bytes the queue may take (a step is cast in several launches beyond it)
-    uint32_t cull_launches = 1;
-    int cull_lazy = -1;                 // ROVER_CULL_LAZY: -1 auto, 0 / 1 force (experiments)
+    Knobs knobs{};                      // what rover_set_option / the ROVER_* environment set (the knob table below)
+    StepPlan plan{};                    // the step in force (replan): what runs and what the plan-dependent buffers are sized for
+    StepPlan ws_plan{};                 // the plan the ray workspace was produced with (cast_rays): the sorted list, rover_get_cull_info
+    CullQueue queue;
     // distribution
     DevBuf<double> d_dist;          // [P][3]
     DevBuf<int32_t> d_obs_idx;      // [Ns+Nd]
@@ -126,7 +105,6 @@ struct rover_ctx {
     StoneGridDev sgrid{};
     bool have_stones = false;
     // per-step workspace
-    uint32_t R8 = 0;
     DevBuf<RayRec> d_rays;
     DevBuf<float> d_dist_out;       // [E*R8]
     DevBuf<float> d_euler;          // [E,3]
@@ -139,19 +117,9 @@ struct rover_ctx {
     DevBuf<uint32_t> d_bkt_table;       // [n_buckets * n_blocks] counts -> offsets
     bool bkt_table_dirty = true;        // not known to be all zero (what prep_rays_kernel's fused histogram starts from): a step failed half way
     DevBuf<uint2> d_pairs;              // [E*R8] (bin, slot) after the coarse partition
-    uint32_t low_bits = 10;             // bins per sort bucket = 2^low_bits, in force (alloc_bins)
-    uint32_t low_bits_opt = 0;          // option "bin_low_bits": 0 = chosen by the library, else 8..12
     int precision = 0;                  // option "ray_precision": 0 fp32 mode, 1 fp16 sources, 2 as shipped (fp16 maths)
     DevBuf<uint32_t> d_block_sums;      // [4096] bucket totals + [4097] bucket starts
     DevBuf<uint32_t> d_sorted;          // [E*R8] ray slots sorted by (map, cell)
-    bool defer_obs = false, obs_pending = false;   // rover_step: assemble_obs waits for do_metrics and shares its launch
-    ObsArgs pending_obs{};
-    uint32_t n_bins = 0;
-    int variant = 0;                    // option "raycast_variant": 0 = auto (plan_raycast)
-    uint32_t run = 0;                   // option "raycast_run": 0 = auto (plan_run)
-    RayPlan plan{};                     // the ray cast in force (replan)
-    RayPlan ws_plan{};                  // the plan the ray workspace was produced with (cast_rays): the sorted list, rover_get_cull_info
-    uint32_t early_out = 1;             // option "raycast_early_out": conservative whole-pair rejection (bit-identical results)
     int32_t cell_rcp = 0;               // option "cell_index_mode": 0 cpu_div (x / 0.1), 1 cuda_rcp (x * (1 / 0.1))
     DevBuf<float> d_mlp_scratch;        // partial sums of the split-k small-batch encoder path (rover_mlp_chain_forward)
     uint64_t workspace_bytes = 0;
@@ -227,178 +195,35 @@ struct DeviceGuard {
     if (device_guard__.err != hipSuccess)                                                                      \
         return fail((c), ROVER_E_HIP, "hipSetDevice(%d): %s", (c)->cfg.device, hipGetErrorString(device_guard__.err))
 
-static uint64_t valid_rays(const rover_ctx* c) { return (uint64_t)c->cfg.num_envs * (26u + (uint64_t)c->P); }
 static bool have_maps(const rover_ctx* c) { return c->maps[0].table.get() && c->maps[1].table.get(); }
-static int proof_in_force(const rover_ctx* c) { return c->precision == 2 ? 1 : 0; }      // ProofTables: the as-shipped fp16 arithmetic has its own
 
-// Auto choice, measured on MI355X at K = 200, 37 + 26 rays (round 4, one call per size, whole step): the culled ray cast passes the
-// env-order kernel between 512 and 1 024 envs (32 k / 64 k rays: 9.8 vs 11.0 M env-steps/s at 512 — the four sort launches cost more than
-// the culling saves —, 16.5 vs 14.6 M at 1 024, 25.8 vs 17.0 M at 2 048); in the as-shipped fp16 arithmetic it is ahead of the binned
-// kernel from 512 envs on (9.1 vs 8.1, 14.0 vs 12.4, 20.6 vs 17.2 M).  (Until round 4 the switch sat at 131 072 rays: round 2's
-// measurement, when the ray cast behind the sort was the every-triangle kernel.)
-#define ROVER_AUTO_CULL_RAYS_F32 49152u
-#define ROVER_AUTO_CULL_RAYS_F16 24576u
-// The staged ray cast: from 24 576 rays (f32 arithmetic), in env order — no sort — while a terrain cell holds fewer than 1.5 heightmap rays
-// and 48 cells or more hold one rover (plan_env_order).  Whole step, M env-steps/s, 37 + 26 rays, one call (tools/sweep_small.sh,
-// profiles/r05_final_sweep.log), env-order kernel / culled / staged behind the sort / staged in env order: 512 envs 11.4 / 10.5 / 8.2 / 17.0,
-// 1 024: 14.7 / 17.6 / 15.4 / 29.3, 2 048: 17.4 / 27.3 / 26.5 / 37.7, 4 096: 18.3 / 39.9 / 41.1 / 49.1, 8 192: 18.9 / 54.9 / 59.2 / 57.7,
-// 16 384: 19.2 / 72.2 / 79.7 / 66.9, 32 768: 19.3 / 98.4 / 113.6 / 71.1, 65 536: 19.2 / 121.7 / 142.1 / 73.5; 120 + 26 rays at 4 096 envs
-// 8.4 / 26.1 / 30.8 / 35.0, at 65 536 envs 8.5 / 56.2 / 69.9 / 45.4.
-#define ROVER_AUTO_LANE_RAYS 24576u
-#define ROVER_AUTO_LANE_ENV_RAYS_F16 98304u   // as shipped: below this many rays the staged kernel in env order (plan_env_order) is ahead of the culled one
-static bool lane_tables_ok(const rover_ctx* c) {
-    const int k = proof_in_force(c);
-    return c->maps[0].proof[k].lrec.get() && c->maps[1].proof[k].lrec.get();
-}
-// raycast_variant 4 asked for by name cannot run: the staged kernel's tables of the arithmetic in force are not there (K > 256 on a map is the
-// documented exception: every variant then runs as the streaming kernel 1, and rover_get_info says so).  rover_set_option and check_precision.
-static bool staged_tables_missing(const rover_ctx* c) {
-    return have_maps(c) && c->maps[0].knn.K8 <= 256 && c->maps[1].knn.K8 <= 256 && !lane_tables_ok(c);
-}
-static int plan_variant(const rover_ctx* c) {
-    const bool v2_ok = c->maps[0].knn.K8 <= 256 && c->maps[1].knn.K8 <= 256;      // 64 lanes x 4 triangles
-    if (c->variant == 1 || !v2_ok) return 1;
-    const bool v4_ok = lane_tables_ok(c);     // the staged kernel's tables of the proof in force, on both maps
-    if (c->variant == 0 && c->precision != 2 && c->have_dist && valid_rays(c) < (v4_ok ? ROVER_AUTO_LANE_RAYS : ROVER_AUTO_CULL_RAYS_F32 + 1u)) return 1;
-    if (c->variant == 0 && c->precision == 2 && c->have_dist && valid_rays(c) <= ROVER_AUTO_CULL_RAYS_F16) return 2;      // small batches, as shipped: binned
-    // variant 3 (culled): its exact phase runs either arithmetic (f32 / as shipped), each with its own proof tables
-    const bool v3_ok = c->maps[0].cull_idx.get() && c->maps[1].cull_idx.get();
-    if (c->variant == 2 || !v3_ok) return 2;
-    // variant 4 (staged, rover_cull.hip: lane = (ray, chunk of 8 pairs) over per-cell record rows): either arithmetic, each with its
-    // proof's tables.  Auto: the table above; the native 1 634 + 26 rays at 512 envs on an irregular mesh 2.13 / 2.98 (culled / staged), the
-    // irregular mesh at 65 536 envs 83.5 / 113.8.  As shipped (fp16 proof: a third of the rays lie off their cell's narrow cone and test
-    // every pair both ways) the culled kernel stays ahead at 37 + 26 rays from 2 048 envs on (23.1 / 22.2 there, 31.7 / 27.1 at 4 096, 54.2 / 46.8 at
-    // 16 384, 91.2 / 87.1 at 65 536) but not below (env order, no sort: 512 envs 9.7 / 13.4, 1 024: 15.4 / 18.5, 1 536: 20.0 / 21.8) and not on dense ray
-    // sets — ten or more heightmap rays per terrain cell (behind the sort: 120 + 26 rays at 65 536 envs 47.1 / 51.6, the native 1 634 + 26 rays at
-    // 4 096 envs 3.65 / 3.86; below ten: native rays at 512 envs 2.25 / 1.95).  On an irregular terrain mesh — fewer than half of the cells
-    // with a usable far bound: the culled kernel then scans most cells whole — from two rays per cell: 37 + 26 rays at 4 096 / 16 384 / 65 536
-    // envs (0.4 / 1.7 / 6.7 rays per cell) 25.5 / 20.7, 36.1 / 34.3, 48.1 / 58.7; the native rays at 512 envs (2.3) 1.46 / 1.61.
-    if (v4_ok && c->variant == 4) return 4;
-    if (v4_ok && c->variant == 0 && c->have_dist) {
-        if (c->precision != 2) { if (valid_rays(c) >= ROVER_AUTO_LANE_RAYS) return 4; }
-        // (round 6 — the rocks part in the staged launch, eta = 0.08, cross-term split 8 —, binned / culled / staged behind the sort / staged in env order,
-        //  M env-steps/s at 37 + 26 rays: 512 envs 8.7 / 9.9 / 9.2 / 14.3; 1 536: 15.1 / 20.6 / 21.1 / 23.9; 2 048: 17.5 / 23.7 / 24.3 / 24.8; 4 096: 21.9 / 32.6 / 33.7 /
-        //  30.3; 16 384: 39.8 / 55.9 / 57.6 / 41.0; 65 536: 51.0 / 93.3 / 95.4 / 44.7; 120 + 26 rays 22.6 / 45.4 / 51.1 / 27.9; native rays at 4 096 envs 1.95 / 3.57 / 4.04 /
-        //  2.46, at 512 envs 1.56 / 2.24 / 2.44 / 2.10: on a regular terrain mesh the staged kernel from the binned kernel's range on.  Irregular terrain
-        //  mesh: 4 096 envs 22.1 / 25.4 / 21.6 / 21.3; 16 384: 39.7 / 35.8 / 35.9 / 23.8; 65 536: 49.7 / 47.9 / 59.9 / 25.2; native rays at 512 envs 1.52 / 1.41 / 1.62 /
-        //  1.42: staged from two heightmap rays per terrain cell, as before.)
-        else if (valid_rays(c) < ROVER_AUTO_LANE_ENV_RAYS_F16 || 2 * c->maps[0].farok >= c->maps[0].cells ||
-                 (uint64_t)c->cfg.num_envs * (uint64_t)c->P >= 2ull * (uint64_t)c->maps[0].cells) return 4;
+// What plan_step reads, from the ctx: the only place that reads it for planning
+static PlanInputs plan_inputs(const rover_ctx* c) {
+    PlanInputs in;
+    in.num_envs = c->cfg.num_envs; in.P = c->P; in.have_dist = c->have_dist; in.precision = c->precision; in.knobs = c->knobs;
+    for (int w = 0; w < 2; ++w) {
+        const MapTables& m = c->maps[w];
+        MapShape& s = in.map[w];
+        s.present = m.table.get() != nullptr;
+        s.X = m.knn.X; s.Y = m.knn.Y; s.K8 = m.knn.K8; s.cells = m.cells; s.farok = m.farok;
+        s.has_cull_tables = m.cull_idx.get() != nullptr;
+        for (int k = 0; k < 2; ++k) s.has_staged_tables[k] = m.proof[k].lrec.get() != nullptr;
     }
-    return 3;
+    return in;
 }
 
-// Sorted rays per wave.  Long runs amortise a cell's set-up (65 536 envs, ray cast only: run 12 -> 1.183 ms, 16 -> 1.171,
-// 24 -> 1.153, 32 -> 1.144, 64 -> 1.150); small batches need more, shorter waves to fill 256 CUs (4 096 envs: run 4 ->
-// 0.2145 ms per step, run 16 -> 0.2264 ms).
-static uint32_t plan_run(const rover_ctx* c, int variant) {
-    if (c->run) return c->run;
-    const uint64_t r = valid_rays(c) / 65536u;
-    // the culled ray cast (round 3, one call each: 4 096 envs run 4 / 8 / 16 / 32 -> 0.155 / 0.151 / 0.161 / 0.173 ms per step;
-    // 8 192 envs 0.246 / 0.227 / 0.236 / 0.249; 16 384 envs 0.407 / 0.335 / 0.331 / 0.343): small batches want many short-lived waves
-    // (round 4, on the final kernels, whole step in M env-steps/s at 37 + 26 rays, one call: 1 024 envs run 4 / 8 / 16 / 32 -> 16.0 / 16.5 / 16.2 /
-    //  13.4; 2 048: 23.9 / 25.9 / 25.7 / 24.0; 4 096 run 8 / 16 / 32: 37.0 / 37.9 / 36.5; 8 192 run 8 / 16 / 32 / 64: 49.0 / 52.4 / 52.8 / 51.4;
-    //  16 384 run 16 / 32 / 64: 68.8 / 71.9 / 72.3; 32 768 run 32 / 64: 96.0 / 97.9; 49 152: 109.1 / 112.5 — since the one-wave workgroups
-    //  and the LDS-first queue of round 3 longer runs win earlier than the table above, measured before them, said)
-    //  A wave's life is longer where a ray has more candidates — an irregular mesh (8.6 pairs per ray against 3.6), the as-shipped fp16
-    //  arithmetic (8.1) — and there shorter runs still balance better (irregular mesh, run 8 / 16 / 32 / 64: 4 096 envs 30.2 / 29.5 / 27.1 / 25.6;
-    //  8 192: 39.0 / 39.7 / 37.8 / 36.7; 16 384: 49.1 / 53.0 / 52.7 / 51.3; 32 768: 58.8 / 66.0 / 68.2 / 67.2; 65 536: 66.0 / 77.7 / 82.4 / 81.8;
-    //  fp16 at 8 192 envs: 36.3 / 36.0 / 34.8 / 34.1): they keep the older table.  The native ray set on the regular mesh: 512 envs run 16 / 32 /
-    //  64 -> 2.56 / 2.61 / 2.46, 1 024 envs 3.10 / 3.33 / 3.32.)
-    // the staged kernel behind the sort wants long runs — a chunk read is shared by the run's rays that test it, a round is fuller —
-    // (whole step, M env-steps/s, runs of 16 / 32 / 64: 8 192 envs 54.5 / 57.6 / 56.0; 16 384: 68.5 / 77.0 / 79.3; 32 768: 82.8 / 98.1 / 110.5;
-    //  65 536: 91.9 / 111.8 / 133.0; 120 + 26 rays 38.5 / 53.9 / 65.0; irregular mesh 67.8 / 92.4 / 104.7)
-    if (variant == 4) return r < 12 ? 32u : 64u;
-    if (variant >= 3) {
-        const bool quick_rays = c->precision != 2 && 2 * c->maps[0].farok >= c->maps[0].cells;      // regular mesh (most cells have a far bound), f32 arithmetic
-        if (quick_rays) return r < 3 ? 8u : (r < 6 ? 16u : (r < 20 ? 32u : 64u));                   // powers of two: 63 instead of 64 cost 6 %
-        return r < 12 ? 8u : (r < 24 ? 16u : (r < 48 ? 32u : 64u));
-    }
-    return (uint32_t)(r < 4 ? 4 : (r > 32 ? 32 : r));
-}
+static uint32_t bucket_count(const StepPlan& p) { return (uint32_t)((p.n_bins + (1u << p.low_bits) - 1u) >> p.low_bits); }
 
-// The staged ray cast needs no bins: where a (map, cell) bin holds a ray or none — small and mid-size batches — the sort's three launches
-// (18 us) buy it nothing and it walks the ray slots in env order (a run = 64 consecutive slots: a rover's 37 heightmap rays still share cells).
-// Measured (MI355X, 37 + 26 rays, whole step, one call per size): see ROVER_AUTO_ENVORDER_* below.
-static bool plan_env_order(const rover_ctx* c, int variant) {
-    if (variant != 4) return false;
-    if (c->lane_env_order >= 0) return c->lane_env_order != 0;
-    // what decides is the heightmap rays per terrain cell (rovers spread over the map): below ~1.5 the sort buys no sharing (4 096 envs x 120
-    // rays: 1.37, env order 35.3 against 30.9 M env-steps/s behind the sort; 16 384 x 37: 1.68, 67.1 / 80.1) — and the rovers per cell: from one per
-    // 48 cells a cell's rays come from several rovers and only the sort brings them together (8 192 x 37: 57.8 / 59.3; 4 096 x 37: 49.2 / 41.1)
-    // (round 6, the rocks part in the staged launch too: behind the sort / env order 4 096 envs 48.9 / 49.9, 8 192 envs 68.6 / 58.3, 120 + 26 rays at
-    //  4 096 envs 35.3 / 36.4 — the sort pays from one rover per ~64 cells)
-    // (as shipped the staged kernel is the auto choice for small batches in env order and for dense ray sets behind the sort: plan_variant)
-    if (c->precision == 2) return c->have_dist && valid_rays(c) < ROVER_AUTO_LANE_ENV_RAYS_F16;
-    return c->have_dist && 2ull * (uint64_t)c->cfg.num_envs * (uint64_t)c->P < 3ull * (uint64_t)c->maps[0].cells &&
-           64ull * (uint64_t)c->cfg.num_envs < (uint64_t)c->maps[0].cells;
-}
-
-// The whole decision, for the inputs in force
-static RayPlan plan_raycast(const rover_ctx* c) {
-    RayPlan p{};
-    p.proof = proof_in_force(c);
-    // few rays per (map, cell) bin: most bins have no ray that tests the far pairs, and setting them up lazily halves a bin's set-up
-    // (32 768 envs x 63 rays 69.7 -> 76 M env-steps/s, 4 096 envs 26.9 -> 30 M; with 146 rays per env a bin holds 14 rays, nearly every
-    // bin needs its far pairs and the second, dependent gather costs 3 %: eager there)
-    // The kernel that fetches a bin's far records only when a ray needs them pays where most bins skip them: small ray sets (few rays
-    // per bin) on a terrain map whose cells mostly have a useful far bound (a regular grid: all of them; an irregular mesh with
-    // triangles that span many cells: few — there the second, dependent round of gathers cost 3 %).
-    // (round 4: what decides is the rays per bin, not the size of the ray set — 120 + 26 rays at 16 384 / 4 096 envs hold 5.8 / 2.1 rays per
-    //  bin and gain 2.8 / 3.7 % from the on-demand kernel; the estimate is heightmap rays per terrain cell for rovers spread over the map.
-    //  The native 1 634-point set is dense — 3.2 rays per bin already at 512 envs — and keeps the eager kernel: -1 ... -5 % otherwise.)
-    const bool few_per_bin = c->P <= 260 && (uint64_t)c->cfg.num_envs * (uint64_t)c->P < 8ull * (uint64_t)c->maps[0].cells;
-    const bool lazy_auto = (26 + c->P < 100 || few_per_bin) && 2 * c->maps[0].farok >= c->maps[0].cells;
-    p.lazy_far = c->cull_lazy < 0 ? lazy_auto : c->cull_lazy != 0;
-    // rays that clear their whole cell are left out of the scan where some do: a mesh whose cells mostly have a usable bound, and rock
-    // rays (the ones that qualify) at least a tenth of the ray set (120 + 26 rays: 12 % of the rays, +3.8 %; the native 1 634 + 26: none)
-    p.skip_clear = 2 * c->maps[0].farok >= c->maps[0].cells && 26 + c->P <= 260;
-    // The as-shipped fp16 arithmetic takes the same two choices since round 4 (its proof's group bound holds less often — 39 % of the rays
-    // skip the far pairs, 13 % are not scanned at all, against 84 % / 25 % — but what holds is free: 65 536 envs 85.4 -> 88.3 M
-    // env-steps/s, 16 384 envs 50.0 -> 53.3 M, alternating in one call); without the whole-cell skip its kernel stays the eager one.
-    if (p.proof && !p.skip_clear) p.lazy_far = false;
-    if (!have_maps(c)) return p;
-    p.variant = plan_variant(c);
-    p.env_order = plan_env_order(c, p.variant);
-    p.sorted = p.variant >= 2 && !p.env_order;
-    // variant 4 behind the sort: the rocks part of the sorted list through the staged kernel too?  Yes (lane_rocks -1, auto), since round 6, in either
-    // arithmetic: f32 — 4-byte test-(B) records, one launch 0.31 ms against 0.23 + 0.14; as shipped 91.0 against 87.2 M env-steps/s (and 96.9 with the
-    // round's proof constants).  In env order the one launch casts every slot.
-    p.rocks_staged = p.variant == 4 && (p.env_order || c->lane_rocks != 0);
-    p.run = plan_run(c, p.variant);
-    // slots per wave: enough waves to fill 1 024 SIMDs (4 096 envs x 64 slots in runs of 64 are one wave per SIMD).  Whole step, M
-    // env-steps/s, runs of 8 / 16 / 32 / 64: 512 envs 15.0 / 16.3 / 14.9 / 12.7; 1 024: 21.2 / 26.7 / 26.3 / 22.1; 2 048: 27.5 / 35.3 / 37.1 /
-    // 36.6; 4 096: - / 45.0 / 49.8 / 47.2; 8 192: - / 52.6 / 60.1 / 59.2; 120 + 26 rays at 4 096 envs: 19.9 / - / 35.5 / 33.2
-    if (p.env_order) {
-        const uint64_t slots = (uint64_t)c->cfg.num_envs * c->R8;
-        p.env_run = c->run ? (c->run > 64u ? 64u : c->run) : (slots >= (1ull << 20) ? 64u : (slots >= (1ull << 17) ? 32u : 16u));
-    }
-    return p;
-}
-
-static uint32_t bucket_count(const rover_ctx* c) { return (c->n_bins + (1u << c->low_bits) - 1u) >> c->low_bits; }
-
+// the sort's tables, for the bins and the digit the plan says
 static int alloc_bins(rover_ctx* c) {
+    const StepPlan& p = c->plan;
     c->bins_ok = false;
     if (!have_maps(c)) return ROVER_OK;
-    const uint64_t nb = (uint64_t)c->maps[0].knn.X * c->maps[0].knn.Y + (uint64_t)c->maps[1].knn.X * c->maps[1].knn.Y;
-    if (nb > 0xfffffffeull) return fail(c, ROVER_E_INVALID, "too many map cells for ray binning");
-    c->n_bins = (uint32_t)nb;
-    c->low_bits = c->low_bits_opt ? c->low_bits_opt : 10u;
-    while (c->low_bits < 12u && bucket_count(c) > 4096u) ++c->low_bits;
-    if (!c->low_bits_opt && c->have_dist) {
-        // One-dword sort entries (low bin bits | slot id) need n_slots <= 2^(32 - low_bits).  A dense ray set that misses that at 1 024 bins
-        // per bucket (65 536 envs x 152 slots: 24 bits of slot id) sorts faster with fewer bins per bucket and packed entries than with
-        // two-dword entries (configs[4]: the four sort passes 158 -> 110 us) — as long as the buckets stay <= 4 096.
-        const uint64_t n_slots = (uint64_t)c->cfg.num_envs * c->R8;
-        uint32_t lb = c->low_bits;
-        while (lb > 8u && n_slots > (1ull << (32u - lb)) && ((c->n_bins + (1u << (lb - 1u)) - 1u) >> (lb - 1u)) <= 4096u) --lb;
-        if (n_slots <= (1ull << (32u - lb))) c->low_bits = lb;
-    }
+    if (p.n_bins > 0xfffffffeull) return fail(c, ROVER_E_INVALID, "too many map cells for ray binning");
     if (!c->d_block_sums.get()) HIP_TRY(c, c->d_block_sums.alloc(2 * 4096 + 8));   // bucket totals + bucket starts
     if (c->have_dist) {                                   // table size depends on E*R8 too
-        const uint64_t n_blocks = ((uint64_t)c->cfg.num_envs * c->R8 + 4095) / 4096;
-        HIP_TRY(c, c->d_bkt_table.alloc((uint64_t)bucket_count(c) * n_blocks + 1));
+        const uint64_t n_blocks = ((uint64_t)c->cfg.num_envs * p.R8 + 4095) / 4096;
+        HIP_TRY(c, c->d_bkt_table.alloc((uint64_t)bucket_count(p) * n_blocks + 1));
         // zero from the start, here and not in the first step: a first step that is only CAPTURED (hipGraph) would record the clearing
         // without running it, and an eager step after it would count into whatever the allocation held
         HIP_TRY(c, hipMemset(c->d_bkt_table.get(), 0, c->d_bkt_table.bytes()));
@@ -408,36 +233,37 @@ static int alloc_bins(rover_ctx* c) {
     return ROVER_OK;
 }
 
-// candidate queue of the culled ray cast (one bounded region per resident wave) + its per-wave counters, for plan p
-static int alloc_cull_queue(rover_ctx* c, const RayPlan& p) {
-    if (!c->ws_ok || !c->have_dist || p.variant < 3) return ROVER_OK;
-    const uint64_t entries = cull_queue_entries(valid_rays(c), (uint32_t)c->cfg.num_envs * (uint32_t)c->P, p.run, c->cull_budget, &c->cull_launches);
-    // (the per-wave counters are sized by the RAY count, the queue — once capped by the budget — is not: a second
-    //  rover_set_distribution with more rays must grow the counters even when the queue keeps its size)
-    // (by the PADDED slot count: in env order the staged kernel walks every slot of every env)
-    const uint32_t slots = rover::cull_stat_slots((uint64_t)c->cfg.num_envs * c->R8, p.env_order ? p.env_run : p.run);
-    c->queue_plan = p;
-    if (c->d_cull_queue.get() && c->d_cull_stats.get() && entries == c->cull_entries && slots == c->cull_stat_slots) return ROVER_OK;
-    c->d_cull_queue.reset(); c->d_cull_stats.reset();
-    c->cull_stat_slots = 0;
-    c->cull_entries = 0;
+// the candidate queue and its per-wave counters, as large as the plan says (nothing to do for a plan without a queue)
+static int alloc_cull_queue(rover_ctx* c) {
+    const StepPlan& p = c->plan;
+    CullQueue& q = c->queue;
+    if (!c->ws_ok || !p.queue_entries) return ROVER_OK;
+    // (the counters are sized by the ray count, the queue — once capped by the budget — is not: a second rover_set_distribution with more
+    //  rays must grow the counters even when the queue keeps its size)
+    const bool fits = q.entries.get() && q.stats.get() && p.queue_entries == q.sized_for.queue_entries && p.stat_slots == q.sized_for.stat_slots;
+    q.sized_for = p;
+    if (fits) return ROVER_OK;
+    q.entries.reset(); q.stats.reset();
     // no fallback to another kernel: a queue that cannot be allocated is an error the caller sees
-    if (hipError_t e = c->d_cull_queue.alloc(entries))
-        return fail(c, ROVER_E_NOMEM, "culled ray cast: candidate queue of %llu bytes: %s", (unsigned long long)(entries * sizeof(uint2)), hipGetErrorString(e));
-    c->cull_entries = entries;
-    HIP_TRY(c, c->d_cull_stats.alloc(slots));
-    c->cull_stat_slots = slots;
-    c->stats_plan = RayPlan{};
-    HIP_TRY(c, hipMemset(c->d_cull_stats.get(), 0, c->d_cull_stats.bytes()));
+    if (hipError_t e = q.entries.alloc(p.queue_entries))
+        return fail(c, ROVER_E_NOMEM, "culled ray cast: candidate queue of %llu bytes: %s", (unsigned long long)(p.queue_entries * sizeof(uint2)), hipGetErrorString(e));
+    HIP_TRY(c, q.stats.alloc(p.stat_slots));
+    q.counters_written_under = StepPlan{};
+    HIP_TRY(c, hipMemset(q.stats.get(), 0, q.stats.bytes()));
     return ROVER_OK;
 }
 
-// Every change of a plan input, and of what sizes the queue, ends here: the plan, then the queue and counters sized for it — here, never in
-// a step (hipMalloc is not allowed while a stream is capturing).  r: the caller's own result; after an error the plan is still brought up
-// to date (rover_get_info reports it), and the queue is left as it is.
-static int replan(rover_ctx* c, int r = ROVER_OK) {
-    c->plan = plan_raycast(c);
-    return r ? r : alloc_cull_queue(c, c->plan);
+static int alloc_workspace(rover_ctx* c);
+
+// Every change of a plan input ends here: the plan, then the buffers it sizes — `what` names those beyond the queue that the change can
+// resize — here, never in a step (hipMalloc is not allowed while a stream is capturing).  r: the caller's own result; after an error the
+// plan is still brought up to date (rover_get_info reports it), and the buffers are left as they are.
+enum Realloc { REALLOC_QUEUE, REALLOC_BINS, REALLOC_WORKSPACE };
+static int replan(rover_ctx* c, Realloc what = REALLOC_QUEUE, int r = ROVER_OK) {
+    c->plan = plan_step(plan_inputs(c));
+    if (!r && what == REALLOC_WORKSPACE) r = alloc_workspace(c);
+    if (!r && what == REALLOC_BINS) r = alloc_bins(c);
+    return r ? r : alloc_cull_queue(c);
 }
 
 static int alloc_workspace(rover_ctx* c) {
@@ -445,8 +271,7 @@ static int alloc_workspace(rover_ctx* c) {
     c->d_rays.reset(); c->d_dist_out.reset(); c->d_euler.reset(); c->d_heading.reset(); c->d_sorted.reset();
     c->d_bins.reset(); c->d_pairs.reset();
     const uint64_t E = (uint64_t)c->cfg.num_envs;
-    c->R8 = (uint32_t)(((26 + c->P) + 7) / 8 * 8);
-    const uint64_t n = E * c->R8;
+    const uint64_t n = E * c->plan.R8;
     if (n > 0xffffffffull) return fail(c, ROVER_E_INVALID, "num_envs * rays_per_env = %llu exceeds 2^32", (unsigned long long)n);
     HIP_TRY(c, c->d_rays.alloc(n));
     HIP_TRY(c, c->d_dist_out.alloc(n));
@@ -604,14 +429,14 @@ static int build_map_tables(rover_ctx* c, MapTables& m, const int32_t* map_idx, 
         (e = d_cnt.alloc(8)) != hipSuccess || (e = d_order.alloc(T_int)) != hipSuccess || (e = d_newid.alloc(T)) != hipSuccess)
         return fail(c, ROVER_E_HIP, "set_knn_map: cull tables: %s", hipGetErrorString(e));
     // The staged kernel's tables are optional, each proof's on its own: which proofs get them is the "staged_tables" option, and an allocation
-    // that fails drops that proof's (the culled kernel then runs for it, plan_variant) — unless variant 4 was asked for by name.
+    // that fails drops that proof's (the culled kernel then runs for it, plan_step) — unless variant 4 was asked for by name.
     for (int k = 0; k < 2; ++k) {
-        if (!((c->staged_tables >> k) & 1)) continue;
+        if (!((c->knobs.staged_tables >> k) & 1)) continue;
         ProofTables& p = m.proof[k];
         if ((e = p.lvl.alloc(n_cells * lane_lvl_stride())) != hipSuccess || (e = p.lrec.alloc(n_cells * 2ull * m.lane_pp)) != hipSuccess ||
             (e = p.lid.alloc(n_cells * m.lane_pp)) != hipSuccess) {
             p.lvl.reset(); p.lrec.reset(); p.lid.reset();
-            if (c->variant == 4)
+            if (c->knobs.variant == 4)
                 return fail(c, ROVER_E_NOMEM, "set_knn_map: the staged ray cast's tables (%llu B per proof) do not fit and raycast_variant 4 was requested: %s",
                             (unsigned long long)(n_cells * ((uint64_t)lane_lvl_stride() * sizeof(float4) + (uint64_t)m.lane_pp * (2 * sizeof(uint4) + sizeof(uint2)))),
                             hipGetErrorString(e));
@@ -623,7 +448,7 @@ static int build_map_tables(rover_ctx* c, MapTables& m, const int32_t* map_idx, 
     a.order = d_order.get(); a.newid = d_newid.get(); a.idx4 = m.cull_idx.get(); a.rtab = m.rtab.get();
     a.ctab = m.proof[0].ctab.get(); a.ctab_h = m.proof[1].ctab.get(); a.qrow = d_qrow[0].get(); a.qrow_h = d_qrow[1].get();
     a.far = m.proof[0].far.get(); a.far_h = m.proof[1].far.get(); a.nz_scratch = d_nz.get(); a.counts = d_cnt.get();
-    a.ph = cull_proof_h(c->cull_eta_h, c->cull_split_h); a.Y = (uint32_t)Y; a.cell_size = cell; a.shift_x = shift_x; a.shift_y = shift_y;
+    a.ph = cull_proof_h(c->knobs.cull_eta_h, c->knobs.cull_split_h); a.Y = (uint32_t)Y; a.cell_size = cell; a.shift_x = shift_x; a.shift_y = shift_y;
     a.lane = m.proof[0].view(); a.lane_h = m.proof[1].view();
     uint32_t h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if ((e = hipMemcpy(d_order.get(), order.data(), d_order.bytes(), hipMemcpyHostToDevice)) != hipSuccess ||
@@ -635,6 +460,66 @@ static int build_map_tables(rover_ctx* c, MapTables& m, const int32_t* map_idx, 
     m.proof[1].always = h_cnt[2]; m.proof[1].nocone = h_cnt[3];
     m.farok = h_cnt[4];
     return ROVER_OK;
+}
+
+// ---- knobs: one table for the ROVER_* environment (rover_create) and rover_set_option -------------------------------------------------
+// What a change invalidates, and how the two sides differ where they do, are data of the row.
+enum : unsigned { KNOB_REPLAN = 1, KNOB_BINS = 2, KNOB_RAYS_OBS = 4 };      // the plan; the sort's tables too; the ray workspace and the obs state
+enum : unsigned {
+    KNOB_OPT_ALSO_ZERO = 1,     // the option accepts 0 (the library's choice) beside its range; the environment only the range
+    KNOB_ENV_AS_BOOL = 2,       // the environment's value is read as v != 0
+    KNOB_REAL = 4,              // a real number (atof), else an integer (atol)
+    KNOB_MUST_RUN = 8,          // the option names a kernel: a variant that cannot run is refused (staged_tables_missing)
+};
+struct KnobRow {
+    const char* option;         // rover_set_option name, or NULL
+    const char* env;            // read at rover_create, or NULL
+    double opt_lo, opt_hi;      // accepted by the option; anything else is ROVER_E_INVALID
+    double env_lo, env_hi;      // accepted from the environment; anything else is ignored
+    unsigned flags;
+    void (*set)(rover_ctx*, double);
+    unsigned invalidates;
+    const char* values;         // the option's accepted values in words (its error message)
+};
+#define KNOB_SET(field, expr) [](rover_ctx* c, double v) { c->field = (expr); }
+static const double kIntMin = -2147483648.0, kIntMax = 2147483647.0, kLongMax = 9223372036854775807.0;
+static const KnobRow kKnobs[] = {
+    {"raycast_variant", "ROVER_RAYCAST_VARIANT", 0, 4, 1, 4, KNOB_MUST_RUN, KNOB_SET(knobs.variant, (int)v), KNOB_REPLAN,
+     "0 (auto), 1 (env order), 2 (binned), 3 (culled) or 4 (staged)"},
+    {"raycast_run", "ROVER_RAYCAST_RUN", 0, 4096, 1, 4096, 0, KNOB_SET(knobs.run, (uint32_t)v), KNOB_REPLAN, "0 (auto) or in [1, 4096]"},
+    {"lane_env_order", "ROVER_LANE_ENV_ORDER", -1, 1, kIntMin, kIntMax, KNOB_ENV_AS_BOOL, KNOB_SET(knobs.lane_env_order, (int)v), KNOB_REPLAN,
+     "-1 (auto), 0 or 1"},
+    {"lane_rocks", "ROVER_LANE_ROCKS", -1, 1, kIntMin, kIntMax, KNOB_ENV_AS_BOOL, KNOB_SET(knobs.lane_rocks, (int)v), KNOB_REPLAN, "-1 (auto), 0 or 1"},
+    {nullptr, "ROVER_CULL_LAZY", 1, 0, kIntMin, kIntMax, 0, KNOB_SET(knobs.cull_lazy, (int)v), KNOB_REPLAN, nullptr},
+    {"bin_low_bits", "ROVER_BIN_LOW_BITS", 8, 12, 8, 12, KNOB_OPT_ALSO_ZERO, KNOB_SET(knobs.low_bits_opt, (uint32_t)v), KNOB_REPLAN | KNOB_BINS,
+     "0 (chosen by the library) or in [8, 12]"},
+    {"cull_queue_mb", "ROVER_CULL_QUEUE_MB", 1, 1 << 20, 1, kLongMax, 0, KNOB_SET(knobs.cull_budget, (uint64_t)v << 20), KNOB_REPLAN, "in [1, 1048576]"},
+    {nullptr, "ROVER_CULLH_ETA", 1, 0, 0.02, 0.5, KNOB_REAL, KNOB_SET(knobs.cull_eta_h, v), 0, nullptr},
+    {nullptr, "ROVER_CULLH_SPLIT", 1, 0, 0.5, 64.0, KNOB_REAL, KNOB_SET(knobs.cull_split_h, v), 0, nullptr},
+    {"staged_tables", nullptr, 0, 3, 1, 0, 0, KNOB_SET(knobs.staged_tables, (int)v), 0,      // takes effect at the next rover_set_knn_map
+     "0 (none), 1 (f32 proof), 2 (as-shipped fp16 proof) or 3 (both)"},
+    {"raycast_early_out", nullptr, 0, 1, 1, 0, 0, KNOB_SET(knobs.early_out, (uint32_t)v), 0, "0 or 1"},
+    // (what an observation means changes with these two: rover_calculate_metrics wants a fresh rover_get_observations)
+    {"ray_precision", nullptr, 0, 2, 1, 0, 0, KNOB_SET(precision, (int)v), KNOB_REPLAN | KNOB_RAYS_OBS, "0 (fp32), 1 (fp16 sources) or 2 (as shipped)"},
+    {"cell_index_mode", nullptr, 0, 1, 1, 0, 0, KNOB_SET(cell_rcp, (int32_t)v), KNOB_RAYS_OBS, "0 (cpu_div) or 1 (cuda_rcp)"},
+};
+#undef KNOB_SET
+
+static const KnobRow* knob_by_option(const char* name) {
+    for (const KnobRow& k : kKnobs)
+        if (k.option && !strcmp(k.option, name)) return &k;
+    return nullptr;
+}
+static bool knob_option_accepts(const KnobRow& k, double v) {
+    return (v >= k.opt_lo && v <= k.opt_hi) || ((k.flags & KNOB_OPT_ALSO_ZERO) && v == 0);
+}
+
+static void plan_to_c(const StepPlan& p, rover_raycast_plan* out) {
+    out->variant = p.variant; out->proof = p.proof; out->sorted = p.sorted ? 1 : 0; out->env_order = p.env_order ? 1 : 0;
+    out->rocks_staged = p.rocks_staged ? 1 : 0; out->run = (int32_t)p.run; out->env_run = (int32_t)p.env_run;
+    out->lazy_far = p.lazy_far ? 1 : 0; out->skip_clear = p.skip_clear ? 1 : 0;
+    out->cull_launches = (int32_t)p.cull_launches; out->low_bits = (int32_t)p.low_bits;
+    out->sort_entry_dwords = (int32_t)p.sort_entry_dwords; out->hist_fused = p.hist_fused ? 1 : 0;
 }
 
 extern "C" {
@@ -660,15 +545,14 @@ int rover_create(const rover_cfg* cfg, rover_ctx** out) {
     c->cfg = *cfg;
     if (c->cfg.num_envs_global <= 0) c->cfg.num_envs_global = c->cfg.num_envs;
     if (c->cfg.max_episode_length <= 0) c->cfg.max_episode_length = 3000;
-    if (const char* v = getenv("ROVER_LANE_ENV_ORDER")) c->lane_env_order = atoi(v) != 0 ? 1 : 0;
-    if (const char* v = getenv("ROVER_LANE_ROCKS")) c->lane_rocks = atoi(v) != 0 ? 1 : 0;
-    if (const char* v = getenv("ROVER_RAYCAST_VARIANT")) { int x = atoi(v); c->variant = (x >= 1 && x <= 4) ? x : 0; }
-    if (const char* v = getenv("ROVER_CULL_LAZY")) c->cull_lazy = atoi(v);
-    if (const char* v = getenv("ROVER_CULLH_ETA")) { const double x = atof(v); if (x >= 0.02 && x <= 0.5) c->cull_eta_h = x; }
-    if (const char* v = getenv("ROVER_CULLH_SPLIT")) { const double x = atof(v); if (x >= 0.5 && x <= 64.0) c->cull_split_h = x; }
-    if (const char* v = getenv("ROVER_CULL_QUEUE_MB")) { const long mb = atol(v); if (mb >= 1) c->cull_budget = (uint64_t)mb << 20; }
-    if (const char* v = getenv("ROVER_BIN_LOW_BITS")) { int b = atoi(v); if (b >= 8 && b <= 12) c->low_bits_opt = (uint32_t)b; }
-    if (const char* v = getenv("ROVER_RAYCAST_RUN")) { int r = atoi(v); if (r >= 1 && r <= 4096) c->run = (uint32_t)r; }
+    for (const KnobRow& k : kKnobs) {
+        const char* text = k.env ? getenv(k.env) : nullptr;
+        if (!text) continue;
+        double v = (k.flags & KNOB_REAL) ? atof(text) : (double)atol(text);
+        if (v < k.env_lo || v > k.env_hi) continue;
+        if (k.flags & KNOB_ENV_AS_BOOL) v = v != 0 ? 1 : 0;
+        k.set(c, v);
+    }
     (void)replan(c);                 // (no maps, no distribution yet: nothing to size)
     DeviceGuard guard(cfg->device);
     e = guard.err;
@@ -701,7 +585,7 @@ int rover_set_knn_map(rover_ctx* c, int which, const int32_t* map_idx, int32_t X
     if (int r = build_map_tables(c, m, map_idx, X, Y, K, tris, T, verts, V, cell, shift_x, shift_y)) return r;      // (the previous map stays)
     c->maps[which] = std::move(m);
     c->rays_valid = false;
-    return replan(c, alloc_bins(c));
+    return replan(c, REALLOC_BINS);
 }
 
 int rover_set_distribution(rover_ctx* c, const double* pts, int32_t P, const int64_t* sparse_idx, int32_t Ns,
@@ -731,9 +615,9 @@ int rover_set_distribution(rover_ctx* c, const double* pts, int32_t P, const int
         if (!idx.empty()) HIP_TRY(c, hipMemcpy(c->d_obs_idx.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         c->P = P; c->Ns = Ns; c->Nd = Nd;
         c->have_dist = true;
-        return alloc_workspace(c);
+        return ROVER_OK;
     }();
-    return replan(c, r);         // (a failure half way leaves no distribution: the plan says so too)
+    return replan(c, REALLOC_WORKSPACE, r);         // (a failure half way leaves no distribution: the plan says so too)
 }
 
 int rover_set_heightfield(rover_ctx* c, const float* hm, int32_t N0, int32_t N1, float hscale, float vscale, float sx, float sy) {
@@ -821,7 +705,7 @@ static int check_precision(rover_ctx* c) {
     if (c->precision == 2 && c->plan.variant < 2)
         return fail(c, ROVER_E_STATE, "ray_precision 2 (as shipped, fp16 maths) needs ray-cast variant 2 or 3 (K <= 256 on both maps)");
     // a variant asked for by name is the one that runs, or the call fails: the staged kernel needs the tables of the arithmetic in force
-    if (c->variant == 4 && staged_tables_missing(c))
+    if (c->knobs.variant == 4 && staged_tables_missing(plan_inputs(c)))
         return fail(c, ROVER_E_STATE, "raycast_variant 4 (staged) was requested but its tables for ray_precision %d are not there (option "
                                       "staged_tables, or they did not fit when the maps were set)", c->precision);
     return ROVER_OK;
@@ -834,7 +718,7 @@ static int check_ready(rover_ctx* c) {
     return check_precision(c);
 }
 
-static CullArgs cull_args(const rover_ctx* c, const RayPlan& p, uint32_t n_valid) {
+static CullArgs cull_args(const rover_ctx* c, const StepPlan& p, uint32_t n_valid) {
     CullArgs a{};
     a.rays = c->d_rays.get(); a.sorted = c->d_sorted.get(); a.n_sorted = n_valid;
     a.n_terrain = (uint32_t)c->cfg.num_envs * (uint32_t)c->P;
@@ -844,7 +728,7 @@ static CullArgs cull_args(const rover_ctx* c, const RayPlan& p, uint32_t n_valid
     a.ctab0 = m0.proof[k].ctab.get(); a.ctab1 = m1.proof[k].ctab.get();
     a.rtab0 = m0.rtab.get(); a.rtab1 = m1.rtab.get();
     a.half = k;
-    const CullProofH ph = cull_proof_h(c->cull_eta_h, c->cull_split_h);
+    const CullProofH ph = cull_proof_h(c->knobs.cull_eta_h, c->knobs.cull_split_h);
     a.c_a_h = ph.c_a; a.tau2_h = ph.tau2;
     a.far0 = m0.proof[k].far.get(); a.far1 = m1.proof[k].far.get();
     a.near0 = a.far0 + 2ull * (uint64_t)m0.cells; a.near1 = a.far1 + 2ull * (uint64_t)m1.cells;
@@ -854,32 +738,29 @@ static CullArgs cull_args(const rover_ctx* c, const RayPlan& p, uint32_t n_valid
     a.kp0 = (uint32_t)c->maps[0].knn.K8; a.kp1 = (uint32_t)c->maps[1].knn.K8;
     a.run = p.run;
     a.out = c->d_dist_out.get();
-    a.queue = c->d_cull_queue.get();
-    a.stats = c->d_cull_stats.get();
-    a.queue_entries = c->cull_entries;
+    a.queue = c->queue.entries.get();
+    a.stats = c->queue.stats.get();
+    a.queue_entries = p.queue_entries;          // (check_queue: the queue was sized for p)
     return a;
 }
 
 // the culled / staged ray cast's candidate queue and counters were sized for plan p (replan; never in a step: no hipMalloc inside a stream capture)
-static int check_queue(rover_ctx* c, const RayPlan& p) {
-    if (p.variant >= 3 && (!c->d_cull_queue.get() || !c->d_cull_stats.get() || c->queue_plan != p))
+static int check_queue(rover_ctx* c, const StepPlan& p) {
+    const CullQueue& q = c->queue;
+    if (p.variant >= 3 && (!q.entries.get() || !q.stats.get() || q.sized_for != p))
         return fail(c, ROVER_E_STATE, "the culled ray cast's candidate queue is not allocated for the options in force");
     return ROVER_OK;
 }
 
-// the sort of plan p's steps (its own rays, not caller-supplied ones) has its first pass inside prep_rays_kernel
-static bool hist_fused_for(const rover_ctx* c, const RayPlan& p, uint32_t* blocks_per_tile) {
-    return p.sorted && c->have_dist && bin_hist_fused((uint32_t)c->cfg.num_envs * c->R8, c->R8, c->n_bins, c->low_bits, blocks_per_tile);
-}
-
 // the ray-cast launch(es) of plan p, on the ray records / sorted list in the workspace
-static int run_raycast(rover_ctx* c, const RayPlan& p, uint32_t n_valid, hipStream_t s) {
+static int run_raycast(rover_ctx* c, const StepPlan& p, uint32_t n_valid, hipStream_t s) {
     const uint32_t E = (uint32_t)c->cfg.num_envs;
-    if (p.variant >= 3 && c->d_cull_stats.get() && p != c->stats_plan) {
+    CullQueue& q = c->queue;
+    if (p.variant >= 3 && q.stats.get() && p != q.counters_written_under) {
         // the per-wave counters of rover_get_cull_info: a launch writes the slots of its own waves; when the way the rays are cast changed
         // since the last launch (another kernel, order or run length: another number of waves) the slots are cleared first
-        HIP_TRY(c, hipMemsetAsync(c->d_cull_stats.get(), 0, c->d_cull_stats.bytes(), s));
-        c->stats_plan = p;
+        HIP_TRY(c, hipMemsetAsync(q.stats.get(), 0, q.stats.bytes(), s));
+        q.counters_written_under = p;
     }
     if (p.variant == 4) {
         LaneArgs l{};
@@ -889,19 +770,15 @@ static int run_raycast(rover_ctx* c, const RayPlan& p, uint32_t n_valid, hipStre
             l.lvl[w] = t.lvl; l.lrec[w] = t.lrec; l.lid[w] = t.lid; l.rtab[w] = c->maps[w].rtab.get(); l.pp[w] = c->maps[w].lane_pp;
         }
         {
-            const CullProofH ph = cull_proof_h(c->cull_eta_h, c->cull_split_h);
+            const CullProofH ph = cull_proof_h(c->knobs.cull_eta_h, c->knobs.cull_split_h);
             l.half = p.proof; l.c_a_h = ph.c_a; l.k2_far = cull_far_k2(l.half, ph);
         }
-        l.run = p.run; l.out = c->d_dist_out.get(); l.stats = c->d_cull_stats.get();
+        l.run = p.run; l.out = c->d_dist_out.get(); l.stats = q.stats.get();
         if (p.env_order) {      // every slot (padding included), in env order, one launch
-            l.sorted = nullptr; l.n_sorted = E * c->R8; l.n_terrain = l.n_sorted; l.run = p.env_run;
+            l.sorted = nullptr; l.n_sorted = E * p.R8; l.n_terrain = l.n_sorted; l.run = p.env_run;
             HIP_TRY(c, launch_raycast_lane(l, s));
             return ROVER_OK;
         }
-        // The rocks part too?  On a regular rocks mesh no: its rays are few per bin and a tenth of them lie off every cone (the horizontal body
-        // rays, which test every pair of their cell both ways) — the staged kernel reads a cell's whole 6.6 KB of (A) and (B) rows for one such
-        // ray where the culled kernel reads 800 bytes of ids and gathers: a tie at 65 536 envs (363-372 us in one launch against 226-233 +
-        // 137-140).  On an irregular rocks mesh — most cells without a usable far bound — yes (465 us against 327 + 270 with the first version).
         if (p.rocks_staged) {
             HIP_TRY(c, launch_raycast_lane(l, s));
         } else {
@@ -921,9 +798,9 @@ static int run_raycast(rover_ctx* c, const RayPlan& p, uint32_t n_valid, hipStre
         HIP_TRY(c, launch_raycast_culled(cull_args(c, p, n_valid), s));
     else if (p.variant == 2)
         HIP_TRY(c, launch_raycast_binned(c->d_rays.get(), c->d_sorted.get(), n_valid, c->maps[0].knn.table, c->maps[1].knn.table,
-                                         (uint32_t)c->maps[0].knn.K8, (uint32_t)c->maps[1].knn.K8, p.run, p.proof != 0, c->early_out, c->d_dist_out.get(), s));
+                                         (uint32_t)c->maps[0].knn.K8, (uint32_t)c->maps[1].knn.K8, p.run, p.proof != 0, c->knobs.early_out, c->d_dist_out.get(), s));
     else
-        HIP_TRY(c, launch_raycast(c->d_rays.get(), E * c->R8, c->maps[0].knn.table, c->maps[1].knn.table, (uint32_t)c->maps[0].knn.K8,
+        HIP_TRY(c, launch_raycast(c->d_rays.get(), E * p.R8, c->maps[0].knn.table, c->maps[1].knn.table, (uint32_t)c->maps[0].knn.K8,
                                   (uint32_t)c->maps[1].knn.K8, c->d_dist_out.get(), s));
     return ROVER_OK;
 }
@@ -935,11 +812,11 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
                      hipStream_t s, const float* import_src = nullptr, const float* import_dir = nullptr) {
     const uint32_t E = (uint32_t)c->cfg.num_envs;
     PrepArgs p{};
-    p.E = E; p.P = (uint32_t)c->P; p.R8 = c->R8;
+    const StepPlan& plan = c->plan;
+    p.E = E; p.P = (uint32_t)c->P; p.R8 = plan.R8;
     p.pos = pos; p.quat = quat; p.joints = joints; p.target = target; p.euler_in = euler_in;
     p.dist = c->d_dist.get(); p.terrain = c->maps[0].knn; p.rocks = c->maps[1].knn;
     p.rays = c->d_rays.get(); p.euler = euler_in ? nullptr : c->d_euler.get(); p.heading = euler_in ? nullptr : c->d_heading.get();
-    const RayPlan& plan = c->plan;
     if (int r = check_queue(c, plan)) return r;
     const uint32_t n_valid = E * (26u + (uint32_t)c->P);
     p.rocks_bin_offset = (uint32_t)((uint64_t)c->maps[0].knn.X * c->maps[0].knn.Y);
@@ -950,17 +827,17 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
     // the sort's first pass (keys per coarse bucket and tile) inside prep_rays_kernel where a 64-env block's keys lie in one tile: the
     // table is zero between steps (allocation, then the sort's last kernel) — unless a step failed half way
     // (caller-supplied rays, rover_cast_rays: import_rays_kernel writes the records and keys, the sort counts its keys itself)
-    const bool hist_fused = !import_src && hist_fused_for(c, plan, &p.hist_blocks_per_tile);
+    const bool hist_fused = !import_src && plan.hist_fused;
     if (hist_fused) {
         if (c->bkt_table_dirty) HIP_TRY(c, hipMemsetAsync(c->d_bkt_table.get(), 0, c->d_bkt_table.bytes(), s));
         c->bkt_table_dirty = true;
-        p.hist = c->d_bkt_table.get(); p.hist_low_bits = c->low_bits; p.hist_buckets = bucket_count(c);
+        p.hist = c->d_bkt_table.get(); p.hist_low_bits = plan.low_bits; p.hist_buckets = bucket_count(plan); p.hist_blocks_per_tile = plan.hist_blocks_per_tile;
     }
     if (import_src) {
         // caller-supplied directions: the culled / staged ray cast's proofs need them of unit length (what -normalize() gives)
         uint32_t* const not_unit = plan.variant >= 3 ? c->d_block_cnt.get() + (size_t)c->cfg.num_envs / 256 + 1 : nullptr;      // (the spare word behind the block counts)
         if (not_unit) HIP_TRY(c, hipMemsetAsync(not_unit, 0, sizeof(uint32_t), s));
-        HIP_TRY(c, launch_import_rays(import_src, import_dir, E, c->R8, (uint32_t)c->P, c->maps[0].knn, c->maps[1].knn, p.rocks_bin_offset, c->precision,
+        HIP_TRY(c, launch_import_rays(import_src, import_dir, E, plan.R8, (uint32_t)c->P, c->maps[0].knn, c->maps[1].knn, p.rocks_bin_offset, c->precision,
                                       c->cell_rcp, c->d_rays.get(), sorts ? c->d_bins.get() : nullptr, s, not_unit));
         if (not_unit) {
             uint32_t bad = 0;
@@ -976,8 +853,8 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
         HIP_TRY(c, launch_prep(p, s));
     }
     if (sorts)
-        HIP_TRY(c, launch_bin_rays(c->d_bins.get(), E * c->R8, n_valid, c->n_bins, c->low_bits, c->d_bkt_table.get(), c->d_pairs.get(),
-                                   c->d_block_sums.get(), c->d_sorted.get(), hist_fused, s));
+        HIP_TRY(c, launch_bin_rays(c->d_bins.get(), E * plan.R8, n_valid, (uint32_t)plan.n_bins, plan.low_bits, plan.sort_entry_dwords == 1,
+                                   c->d_bkt_table.get(), c->d_pairs.get(), c->d_block_sums.get(), c->d_sorted.get(), hist_fused, s));
     // fused histogram: bucket_sort_kernel has cleared the table again; otherwise the table (if the sort ran) holds this step's offsets
     if (sorts) c->bkt_table_dirty = !hist_fused;        // (variant 1 does not touch the table)
     const bool timed = c->profiling && (c->prof_seen++ % c->prof_every) == 0;
@@ -996,7 +873,8 @@ static int cast_rays(rover_ctx* c, const float* pos, const float* quat, const fl
     return ROVER_OK;
 }
 
-static int do_observations(rover_ctx* c, const rover_step_in* in, const rover_step_out* out, hipStream_t s) {
+// launch_obs false (rover_step): the obs pass is left to the caller, which hands *obs_args to do_metrics — one grid for both passes
+static int do_observations(rover_ctx* c, const rover_step_in* in, const rover_step_out* out, hipStream_t s, bool launch_obs, ObsArgs* obs_args) {
     if (!in->pos || !in->quat || !in->joints || !in->target || !in->lin_hist || !in->ang_hist)
         return fail(c, ROVER_E_INVALID, "get_observations: null input pointer");
     if (!out->obs) return fail(c, ROVER_E_INVALID, "get_observations: obs is required");
@@ -1006,21 +884,22 @@ static int do_observations(rover_ctx* c, const rover_step_in* in, const rover_st
     if (int r = cast_rays(c, in->pos, in->quat, in->joints, in->target, nullptr, s)) return r;
     c->obs_valid = true;
     ObsArgs o{};
-    o.E = E; o.W = W; o.R8 = c->R8; o.obs_stride = stride;
+    o.E = E; o.W = W; o.R8 = c->plan.R8; o.obs_stride = stride;
     o.pos = in->pos; o.target = in->target; o.heading = c->d_heading.get(); o.lin_hist = in->lin_hist; o.ang_hist = in->ang_hist;
     o.dist = c->d_dist_out.get(); o.obs_idx = c->d_obs_idx.get(); o.obs = out->obs; o.fp16_div = c->precision == 2;
-    if (c->defer_obs) { c->pending_obs = o; c->obs_pending = true; }
-    else HIP_TRY(c, launch_assemble_obs(o, s));
+    if (launch_obs) HIP_TRY(c, launch_assemble_obs(o, s));
+    *obs_args = o;
     if (out->ray_dist || out->wheel_dist || out->body_dist || out->ray_src || out->hit_pt)
-        HIP_TRY(c, launch_export_dist(c->d_dist_out.get(), c->d_rays.get(), E, c->R8, (uint32_t)c->P, c->precision, out->ray_dist, out->wheel_dist,
+        HIP_TRY(c, launch_export_dist(c->d_dist_out.get(), c->d_rays.get(), E, c->plan.R8, (uint32_t)c->P, c->precision, out->ray_dist, out->wheel_dist,
                                       out->body_dist, out->ray_src, out->hit_pt, s));
     if (out->euler) HIP_TRY(c, hipMemcpyAsync(out->euler, c->d_euler.get(), (uint64_t)E * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (out->heading_diff) HIP_TRY(c, hipMemcpyAsync(out->heading_diff, c->d_heading.get(), (uint64_t)E * sizeof(float), hipMemcpyDeviceToDevice, s));
     return ROVER_OK;
 }
 
+// with_obs != NULL: the obs pass of a do_observations(launch_obs = false) runs in the same launch
 static int do_metrics(rover_ctx* c, const rover_step_in* in, const rover_step_out* out, int inc, int coll, int met, int done,
-                      hipStream_t s, bool count_done = false) {
+                      hipStream_t s, bool count_done = false, const ObsArgs* with_obs = nullptr) {
     if (!in->pos || !in->target) return fail(c, ROVER_E_INVALID, "metrics/done: null input pointer");
     if ((inc || met || done) && !in->progress) return fail(c, ROVER_E_INVALID, "metrics/done: progress is required");
     if (!out->rock_collision) return fail(c, ROVER_E_INVALID, "metrics/done: rock_collision is required");
@@ -1032,7 +911,7 @@ static int do_metrics(rover_ctx* c, const rover_step_in* in, const rover_step_ou
         if (!(out->stone_margin <= 1.4f)) return fail(c, ROVER_E_INVALID, "stone_margin %g exceeds the 1.4 m reach of the stone grid", (double)out->stone_margin);
     }
     MetricsArgs m{};
-    m.E = (uint32_t)c->cfg.num_envs; m.R8 = c->R8;
+    m.E = (uint32_t)c->cfg.num_envs; m.R8 = c->plan.R8;
     m.curriculum_level = c->cfg.curriculum_level; m.max_episode_length = c->cfg.max_episode_length;
     m.num_envs_global = c->cfg.num_envs_global;
     m.do_increment = inc; m.do_collision = coll; m.do_metrics = met; m.do_done = done;
@@ -1056,12 +935,8 @@ static int do_metrics(rover_ctx* c, const rover_step_in* in, const rover_step_ou
         if (!in->progress) return fail(c, ROVER_E_INVALID, "evaluation: progress is required (the latch records it)");
         m.eval_res = c->d_eval_res.get(); m.eval_step = c->d_eval_step.get();
     }
-    if (c->obs_pending) {
-        c->obs_pending = false;
-        HIP_TRY(c, launch_obs_metrics(c->pending_obs, m, s));
-    } else {
-        HIP_TRY(c, launch_metrics_done(m, s));
-    }
+    if (with_obs) HIP_TRY(c, launch_obs_metrics(*with_obs, m, s));
+    else HIP_TRY(c, launch_metrics_done(m, s));
     return ROVER_OK;
 }
 
@@ -1071,7 +946,8 @@ int rover_get_observations(rover_ctx* c, const rover_step_in* in, const rover_st
     if (int r = check_ready(c)) return r;
     USE_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
-    if (int r = do_observations(c, in, out, s)) return r;
+    ObsArgs o{};
+    if (int r = do_observations(c, in, out, s, true, &o)) return r;
     if (!out->rock_collision) return ROVER_OK;
     // check_collision (rover.py:292-293) is part of get_observations: run only the collision stage
     return do_metrics(c, in, out, 0, 1, 0, 0, s);
@@ -1103,7 +979,7 @@ int rover_get_depths(rover_ctx* c, const float* positions, const float* rotation
     hipStream_t s = (hipStream_t)stream;
     if (int r = cast_rays(c, positions, nullptr, nullptr, nullptr, rotations_euler, s)) return r;
     if (distances || points || sources)
-        HIP_TRY(c, launch_export_dist(c->d_dist_out.get(), c->d_rays.get(), (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, c->precision, distances,
+        HIP_TRY(c, launch_export_dist(c->d_dist_out.get(), c->d_rays.get(), (uint32_t)c->cfg.num_envs, c->plan.R8, (uint32_t)c->P, c->precision, distances,
                                       nullptr, nullptr, sources, points, s));
     return ROVER_OK;
 }
@@ -1117,7 +993,7 @@ int rover_get_collisions(rover_ctx* c, const float* positions, const float* rota
     hipStream_t s = (hipStream_t)stream;
     if (int r = cast_rays(c, positions, nullptr, joints, nullptr, rotations_euler, s)) return r;
     if (wheel_dist || body_dist)
-        HIP_TRY(c, launch_export_dist(c->d_dist_out.get(), c->d_rays.get(), (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, c->precision, nullptr,
+        HIP_TRY(c, launch_export_dist(c->d_dist_out.get(), c->d_rays.get(), (uint32_t)c->cfg.num_envs, c->plan.R8, (uint32_t)c->P, c->precision, nullptr,
                                       wheel_dist, body_dist, nullptr, nullptr, s));
     return ROVER_OK;
 }
@@ -1127,7 +1003,7 @@ int rover_export_rays(rover_ctx* c, float* src, float* dir, int32_t* cell, float
     if (int r = check_ready(c)) return r;
     if (!c->rays_valid) return fail(c, ROVER_E_STATE, "export_rays: no ray records yet (run a step first)");
     USE_DEVICE(c);
-    HIP_TRY(c, launch_export_rays(c->d_rays.get(), c->d_dist_out.get(), (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, src, dir, cell, dist,
+    HIP_TRY(c, launch_export_rays(c->d_rays.get(), c->d_dist_out.get(), (uint32_t)c->cfg.num_envs, c->plan.R8, (uint32_t)c->P, src, dir, cell, dist,
                                   (hipStream_t)stream));
     return ROVER_OK;
 }
@@ -1139,7 +1015,7 @@ int rover_cast_rays(rover_ctx* c, const float* src, const float* dir, float* dis
     USE_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     if (int r = cast_rays(c, nullptr, nullptr, nullptr, nullptr, nullptr, s, src, dir)) return r;
-    HIP_TRY(c, launch_export_rays(c->d_rays.get(), c->d_dist_out.get(), (uint32_t)c->cfg.num_envs, c->R8, (uint32_t)c->P, nullptr, nullptr, nullptr, dist, s));
+    HIP_TRY(c, launch_export_rays(c->d_rays.get(), c->d_dist_out.get(), (uint32_t)c->cfg.num_envs, c->plan.R8, (uint32_t)c->P, nullptr, nullptr, nullptr, dist, s));
     return ROVER_OK;
 }
 
@@ -1160,16 +1036,10 @@ int rover_step(rover_ctx* c, const rover_step_in* in, const rover_step_out* out,
     hipStream_t s = (hipStream_t)stream;
     if ((flags & ROVER_STEP_COMPACT) && (!out->reset_ids || !out->n_reset))
         return fail(c, ROVER_E_INVALID, "step: ROVER_STEP_COMPACT needs reset_ids and n_reset");
-    c->defer_obs = true;              // the obs pass is launched by do_metrics, in one grid with the metrics pass
-    c->obs_pending = false;
-    const int ro = do_observations(c, in, out, s);
-    c->defer_obs = false;
-    if (ro) { c->obs_pending = false; return ro; }
+    ObsArgs o{};                      // the obs pass is launched by do_metrics, in one grid with the metrics pass
+    if (int r = do_observations(c, in, out, s, false, &o)) return r;
     const bool compact = (flags & ROVER_STEP_COMPACT) != 0;
-    if (int r = do_metrics(c, in, out, (flags & ROVER_STEP_INCREMENT_PROGRESS) ? 1 : 0, 1, 1, 1, s, compact)) {
-        c->obs_pending = false;
-        return r;
-    }
+    if (int r = do_metrics(c, in, out, (flags & ROVER_STEP_INCREMENT_PROGRESS) ? 1 : 0, 1, 1, 1, s, compact, &o)) return r;
     if (compact)
         HIP_TRY(c, launch_compact(out->reset, (uint32_t)c->cfg.num_envs, (int64_t)c->cfg.env_offset, c->d_block_cnt.get(), true,
                                   out->reset_ids, out->n_reset, s));
@@ -1333,13 +1203,13 @@ int rover_ackermann(rover_ctx* c, const float* lin, const float* ang, int32_t n,
 int rover_get_info(const rover_ctx* c, rover_info* info) {
     if (!c || !info) return ROVER_E_INVALID;
     memset(info, 0, sizeof *info);
-    info->P = c->P; info->Ns = c->Ns; info->Nd = c->Nd; info->rays_per_env_padded = (int32_t)c->R8;
+    info->P = c->P; info->Ns = c->Ns; info->Nd = c->Nd; info->rays_per_env_padded = (int32_t)c->plan.R8;
     for (int w = 0; w < 2; ++w) {
         info->K[w] = c->maps[w].knn.K; info->K8[w] = c->maps[w].knn.K8; info->X[w] = c->maps[w].knn.X; info->Y[w] = c->maps[w].knn.Y;
         info->table_bytes[w] = c->maps[w].bytes();
     }
     // the per-step workspace: ray records, distances, sort buffers, env records, and the culled ray cast's queue + counters
-    info->workspace_bytes = c->workspace_bytes + c->d_cull_queue.bytes() + c->d_cull_stats.bytes();
+    info->workspace_bytes = c->workspace_bytes + c->queue.entries.bytes() + c->queue.stats.bytes();
     info->raycast_variant = c->plan.variant;
     info->cell_index_mode = c->cell_rcp; info->ray_precision = c->precision;
     info->raycast_sorted = c->plan.sorted ? 1 : 0;
@@ -1350,15 +1220,7 @@ int rover_get_info(const rover_ctx* c, rover_info* info) {
 int rover_get_raycast_plan(const rover_ctx* c, rover_raycast_plan* out) {
     if (!c || !out) return ROVER_E_INVALID;
     memset(out, 0, sizeof *out);
-    const RayPlan& p = c->plan;
-    out->variant = p.variant; out->proof = p.proof; out->sorted = p.sorted ? 1 : 0; out->env_order = p.env_order ? 1 : 0;
-    out->rocks_staged = p.rocks_staged ? 1 : 0; out->run = (int32_t)p.run; out->env_run = (int32_t)p.env_run;
-    out->lazy_far = p.lazy_far ? 1 : 0; out->skip_clear = p.skip_clear ? 1 : 0;
-    out->cull_launches = p.variant >= 3 && c->d_cull_queue.get() ? (int32_t)c->cull_launches : 0;      // (a queue of an earlier plan may still be there)
-    out->low_bits = (int32_t)c->low_bits;
-    uint32_t blocks_per_tile = 0;
-    out->sort_entry_dwords = p.sorted && c->have_dist ? (bin_entries_packed((uint32_t)c->cfg.num_envs * c->R8, c->low_bits) ? 1 : 2) : 0;
-    out->hist_fused = hist_fused_for(c, p, &blocks_per_tile) ? 1 : 0;
+    plan_to_c(c->plan, out);
     return ROVER_OK;
 }
 
@@ -1373,13 +1235,14 @@ int rover_get_cull_info(rover_ctx* c, rover_cull_info* out) {
         out->cells_with_far_bound[w] = m.farok;
     }
     out->far_records_on_demand = (c->have_dist && c->maps[0].table.get()) ? (uint64_t)c->plan.lazy_far : 0;
-    out->queue_bytes = c->d_cull_queue.bytes();
-    out->launches_per_step = c->d_cull_queue.get() ? c->cull_launches : 0;
-    if (!c->d_cull_stats.get() || c->ws_plan.variant < 3) return ROVER_OK;
+    const CullQueue& q = c->queue;
+    out->queue_bytes = q.entries.bytes();
+    out->launches_per_step = q.entries.get() ? q.sized_for.cull_launches : 0;
+    if (!q.stats.get() || c->ws_plan.variant < 3) return ROVER_OK;
     USE_DEVICE(c);
     HIP_TRY(c, hipDeviceSynchronize());
-    std::vector<uint4> h(c->cull_stat_slots);
-    HIP_TRY(c, hipMemcpy(h.data(), c->d_cull_stats.get(), h.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+    std::vector<uint4> h(q.stats.bytes() / sizeof(uint4));
+    HIP_TRY(c, hipMemcpy(h.data(), q.stats.get(), q.stats.bytes(), hipMemcpyDeviceToHost));
     for (const uint4& v : h) {
         out->candidate_pairs += v.x; out->rays += v.y & 0xffu; out->rays_far_skipped += v.y >> 8; out->rays_both_tests += v.z & 0xffu; out->rays_not_scanned += v.z >> 8; out->bins += v.w & 0xffu;
         out->lane_items += (v.w >> 8) & 0x3ffffu; out->lane_flushes += v.w >> 26;      // (zero in the words the culled kernel's waves write)
@@ -1652,65 +1515,50 @@ const char* rover_mlp_chain_pair_route(int32_t M, const rover_chain_desc* da, co
 int rover_set_option(rover_ctx* c, const char* name, int64_t value) {
     if (!c || !name) return ROVER_E_INVALID;
     USE_DEVICE(c);                                 // some options (re)allocate device workspace
-    if (!strcmp(name, "raycast_variant")) {
-        if (value < 0 || value > 4) return fail(c, ROVER_E_INVALID, "raycast_variant must be 0 (auto), 1 (env order), 2 (binned), 3 (culled) or 4 (staged)");
-        if (value == 4 && staged_tables_missing(c))
-            return fail(c, ROVER_E_STATE, "raycast_variant 4 (staged) needs its tables for the arithmetic in force: they were not built (option "
-                                          "staged_tables, or they did not fit when the maps were set)");
-        c->variant = (int)value;
-        return replan(c);
-    }
-    if (!strcmp(name, "staged_tables")) {
-        if (value < 0 || value > 3) return fail(c, ROVER_E_INVALID, "staged_tables must be 0 (none), 1 (f32 proof), 2 (as-shipped fp16 proof) or 3 (both)");
-        c->staged_tables = (int)value;       // takes effect at the next rover_set_knn_map
-        return ROVER_OK;
-    }
-    if (!strcmp(name, "lane_env_order")) {
-        if (value < -1 || value > 1) return fail(c, ROVER_E_INVALID, "lane_env_order must be -1 (auto), 0 or 1");
-        c->lane_env_order = (int)value;
-        return replan(c);
-    }
-    if (!strcmp(name, "lane_rocks")) {
-        if (value < -1 || value > 1) return fail(c, ROVER_E_INVALID, "lane_rocks must be -1 (auto), 0 or 1");
-        c->lane_rocks = (int)value;
-        return replan(c);
-    }
-    if (!strcmp(name, "ray_precision")) {
-        if (value < 0 || value > 2) return fail(c, ROVER_E_INVALID, "ray_precision must be 0 (fp32), 1 (fp16 sources) or 2 (as shipped)");
-        c->precision = (int)value;
-        c->rays_valid = false;
-        c->obs_valid = false;           // (what an observation means changed: rover_calculate_metrics wants a fresh rover_get_observations)
-        return replan(c);
-    }
-    if (!strcmp(name, "bin_low_bits")) {
-        if (value != 0 && (value < 8 || value > 12)) return fail(c, ROVER_E_INVALID, "bin_low_bits must be 0 (chosen by the library) or in [8, 12]");
-        c->low_bits_opt = (uint32_t)value;
-        return replan(c, alloc_bins(c));
-    }
-    if (!strcmp(name, "raycast_early_out")) {
-        if (value < 0 || value > 1) return fail(c, ROVER_E_INVALID, "raycast_early_out must be 0 or 1");
-        c->early_out = (uint32_t)value;
-        return ROVER_OK;
-    }
-    if (!strcmp(name, "cell_index_mode")) {
-        if (value < 0 || value > 1) return fail(c, ROVER_E_INVALID, "cell_index_mode must be 0 (cpu_div) or 1 (cuda_rcp)");
-        c->cell_rcp = (int32_t)value;
+    const KnobRow* k = knob_by_option(name);
+    if (!k) return fail(c, ROVER_E_INVALID, "unknown option '%s'", name);
+    if (!knob_option_accepts(*k, (double)value)) return fail(c, ROVER_E_INVALID, "%s must be %s", name, k->values);
+    if ((k->flags & KNOB_MUST_RUN) && value == 4 && staged_tables_missing(plan_inputs(c)))
+        return fail(c, ROVER_E_STATE, "raycast_variant 4 (staged) needs its tables for the arithmetic in force: they were not built (option "
+                                      "staged_tables, or they did not fit when the maps were set)");
+    k->set(c, (double)value);
+    if (k->invalidates & KNOB_RAYS_OBS) {
         c->hf.rcp = c->cell_rcp;
         c->rays_valid = false;
         c->obs_valid = false;
-        return ROVER_OK;
     }
-    if (!strcmp(name, "cull_queue_mb")) {
-        if (value < 1 || value > (1 << 20)) return fail(c, ROVER_E_INVALID, "cull_queue_mb must be in [1, 1048576]");
-        c->cull_budget = (uint64_t)value << 20;
-        return replan(c);
+    return (k->invalidates & KNOB_REPLAN) ? replan(c, (k->invalidates & KNOB_BINS) ? REALLOC_BINS : REALLOC_QUEUE) : ROVER_OK;
+}
+
+int rover_plan_raycast(const rover_plan_query* q, rover_raycast_plan* out) {
+    if (!q || !out) return fail(nullptr, ROVER_E_INVALID, "plan_raycast: null argument");
+    if (q->num_envs <= 0 || q->P < 0 || (q->have_dist && q->P == 0))
+        return fail(nullptr, ROVER_E_INVALID, "plan_raycast: num_envs=%d P=%d have_dist=%d", q->num_envs, q->P, q->have_dist);
+    const struct { const char* option; int64_t value; } given[] = {
+        {"raycast_variant", q->raycast_variant}, {"raycast_run", q->raycast_run}, {"lane_env_order", q->lane_env_order}, {"lane_rocks", q->lane_rocks},
+        {"bin_low_bits", q->bin_low_bits}, {"cull_queue_mb", q->cull_queue_mb}, {"ray_precision", q->ray_precision}};
+    for (const auto& g : given)
+        if (!knob_option_accepts(*knob_by_option(g.option), (double)g.value))
+            return fail(nullptr, ROVER_E_INVALID, "plan_raycast: %s must be %s", g.option, knob_by_option(g.option)->values);
+    PlanInputs in;
+    in.num_envs = q->num_envs; in.P = q->P; in.have_dist = q->have_dist != 0; in.precision = q->ray_precision;
+    in.knobs.variant = q->raycast_variant; in.knobs.run = (uint32_t)q->raycast_run; in.knobs.lane_env_order = q->lane_env_order;
+    in.knobs.lane_rocks = q->lane_rocks; in.knobs.cull_lazy = q->cull_lazy; in.knobs.low_bits_opt = (uint32_t)q->bin_low_bits;
+    in.knobs.cull_budget = (uint64_t)q->cull_queue_mb << 20;
+    for (int w = 0; w < 2; ++w) {
+        MapShape& m = in.map[w];
+        if (q->map_present[w] && (q->X[w] <= 0 || q->Y[w] <= 0 || q->K8[w] <= 0 || q->K8[w] % 8 || q->cells_with_far_bound[w] < 0 ||
+                                  q->cells_with_far_bound[w] > (int64_t)q->X[w] * q->Y[w]))
+            return fail(nullptr, ROVER_E_INVALID, "plan_raycast: map %d: X=%d Y=%d K8=%d cells_with_far_bound=%lld", w, q->X[w], q->Y[w], q->K8[w],
+                        (long long)q->cells_with_far_bound[w]);
+        if (!q->map_present[w]) continue;
+        m.present = true; m.X = q->X[w]; m.Y = q->Y[w]; m.K8 = q->K8[w]; m.cells = (int64_t)q->X[w] * q->Y[w]; m.farok = q->cells_with_far_bound[w];
+        m.has_cull_tables = q->has_cull_tables[w] != 0;
+        for (int k = 0; k < 2; ++k) m.has_staged_tables[k] = q->has_staged_tables[w][k] != 0;
     }
-    if (!strcmp(name, "raycast_run")) {
-        if (value < 0 || value > 4096) return fail(c, ROVER_E_INVALID, "raycast_run must be 0 (auto) or in [1, 4096]");
-        c->run = (uint32_t)value;
-        return replan(c);
-    }
-    return fail(c, ROVER_E_INVALID, "unknown option '%s'", name);
+    memset(out, 0, sizeof *out);
+    plan_to_c(plan_step(in), out);
+    return ROVER_OK;
 }
 
 int rover_set_profiling(rover_ctx* c, int32_t enable) {
@@ -1754,8 +1602,8 @@ int rover_replay_raycast(rover_ctx* c, void* stream) {
     if (int r = check_ready(c)) return r;
     if (!c->rays_valid) return fail(c, ROVER_E_STATE, "replay_raycast: no ray records yet (run a step first)");
     USE_DEVICE(c);
-    RayPlan p = c->plan;
-    if (p.sorted && !c->ws_plan.sorted) { p = RayPlan{}; p.variant = 1; }     // no sorted list from the last step: only an env-order kernel can replay
+    StepPlan p = c->plan;
+    if (p.sorted && !c->ws_plan.sorted) { p = StepPlan{}; p.variant = 1; p.R8 = c->plan.R8; }     // no sorted list from the last step: only an env-order kernel can replay
     if (int r = check_queue(c, p)) return r;
     return run_raycast(c, p, (uint32_t)c->cfg.num_envs * (26u + (uint32_t)c->P), (hipStream_t)stream);
 }

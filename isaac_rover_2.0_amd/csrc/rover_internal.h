@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rover_plan.h"      // the integer helpers plan_step shares with the launchers (bin_*, cull_queue_entries, cull_stat_slots, lane_*)
 
 // Test (B) for a whole set of triangles by its normal cone (rover_cull.hip, header comment): the ray-side constant of the f32 proof.
 #define ROVER_CONE_TAU 1.25e-2
@@ -86,7 +87,6 @@ struct CullArgs {
     int skip_clear;              // (eager kernel) do not scan rays that clear their whole cell — the on-demand kernel always does
     uint4* stats;                // [waves] per-wave counters of the last launch {queue entries, rays, rays with both tests, bins}
 };
-uint32_t cull_stat_slots(uint64_t n_rays, uint32_t run);
 // the staged ray cast (raycast variant 4, rover_cull.hip): lane = (ray, chunk of 8 pairs) over per-cell record rows in group-bound order
 struct LaneArgs {
     const RayRec* rays;
@@ -102,11 +102,8 @@ struct LaneArgs {
     int half;                    // the tables are the as-shipped fp16 arithmetic's, the exact phase runs it
     float c_a_h, k2_far;         // test (A)'s constant of that proof; the level bound's ray-side constant (cull_far_k2)
 };
-uint32_t lane_pairs_per_row(uint32_t K8);
 uint32_t lane_lvl_stride();
-uint32_t lane_waves(uint32_t n_rays, uint32_t run);
 hipError_t launch_raycast_lane(LaneArgs a, hipStream_t s);
-uint64_t cull_queue_entries(uint64_t n_rays, uint32_t n_terrain, uint32_t run, uint64_t budget_bytes, uint32_t* n_launches);
 
 // n / d for every 32-bit n with a multiply-high and two shifts (Granlund & Montgomery's round-up method): the compiler's own
 // expansion of a division by a run-time value is ~30 (32-bit) / ~110 (64-bit) dependent instructions per thread.
@@ -239,11 +236,8 @@ hipError_t launch_repack(const int32_t* map_idx, const int32_t* tris, const uint
 hipError_t launch_prep(const PrepArgs& a, hipStream_t s);
 hipError_t launch_raycast(const RayRec* rays, uint32_t n_rays, const uint16_t* tab0, const uint16_t* tab1, uint32_t kp0,
                           uint32_t kp1, float* out, hipStream_t s);
-// true when prep_rays_kernel can count the sort's coarse buckets itself (PrepArgs::hist): a 64-env block's keys lie inside one tile of the sort
-bool bin_hist_fused(uint32_t n_slots, uint32_t R8, uint32_t n_bins, uint32_t low_bits, uint32_t* blocks_per_tile);
-// true when launch_bin_rays sorts one-dword entries (low bin bits | slot id) for this many slots, false for (bin, slot) pairs
-bool bin_entries_packed(uint32_t n_slots, uint32_t low_bits);
-hipError_t launch_bin_rays(const uint32_t* bins, uint32_t n_slots, uint32_t n_valid, uint32_t n_bins, uint32_t low_bits,
+// packed: one-dword sort entries (bin_entries_packed(n_slots, low_bits): the plan's sort_entry_dwords == 1)
+hipError_t launch_bin_rays(const uint32_t* bins, uint32_t n_slots, uint32_t n_valid, uint32_t n_bins, uint32_t low_bits, bool packed,
                            uint32_t* table, uint2* pairs, uint32_t* block_sums, uint32_t* sorted, bool hist_done, hipStream_t s);
 hipError_t launch_raycast_binned(const RayRec* rays, const uint32_t* sorted, uint32_t n_sorted, const uint16_t* tab0,
                                  const uint16_t* tab1, uint32_t kp0, uint32_t kp1, uint32_t run, bool fp16_math, uint32_t early_out, float* out,

@@ -1722,10 +1722,8 @@ hipError_t launch_scan_exclusive(uint32_t* data, uint32_t n, uint32_t* block_sum
 // table a quarter of the rows; small batches keep the small tile (more blocks than CUs matter more there)
 // a sort entry is one dword — slot ids leave room for the low bin bits — (else (bin, slot) as two): the one place that decides it
 bool bin_entries_packed(uint32_t n_slots, uint32_t low_bits) { return (uint64_t)n_slots <= (1ull << (32u - low_bits)); }
-static inline uint32_t bin_tile_threads(uint32_t n_slots, uint32_t low_bits, bool* packed_out) {
+static inline uint32_t bin_tile_threads(uint32_t n_slots, bool packed) {
     const bool big = n_slots >= (2u << 20);
-    const bool packed = bin_entries_packed(n_slots, low_bits);
-    if (packed_out) *packed_out = packed;
     return big ? (packed ? 1024u : 512u) : 256u;                                  // (two-dword entries: 12 bytes of LDS per slot, 8 192 slots)
 }
 
@@ -1735,20 +1733,20 @@ static inline uint32_t bin_tile_threads(uint32_t n_slots, uint32_t low_bits, boo
 // the table again.  One launch less per step (6.1 us at 65 536 envs, 4.7 at 4 096); other ray counts keep bucket_hist_kernel.
 bool bin_hist_fused(uint32_t n_slots, uint32_t R8, uint32_t n_bins, uint32_t low_bits, uint32_t* blocks_per_tile) {
     const uint32_t n_buckets = (n_bins + (1u << low_bits) - 1u) >> low_bits;
-    const uint32_t tile = bin_tile_threads(n_slots, low_bits, nullptr) * BKT_ITEMS, keys = 64u * R8;      // keys of a prep_rays block's 64 envs
+    const uint32_t tile = bin_tile_threads(n_slots, bin_entries_packed(n_slots, low_bits)) * BKT_ITEMS, keys = 64u * R8;      // keys of a prep_rays block's 64 envs
     if (low_bits < 8u || low_bits > 12u || n_buckets > 1024u || keys > tile || tile % keys != 0u) return false;
     *blocks_per_tile = tile / keys;
     return true;
 }
 
 // sort the valid ray slots by bin; work = [counts/offsets table | pairs]; returns hipErrorInvalidValue when the bin space is too large
-hipError_t launch_bin_rays(const uint32_t* bins, uint32_t n_slots, uint32_t n_valid, uint32_t n_bins, uint32_t low_bits,
+hipError_t launch_bin_rays(const uint32_t* bins, uint32_t n_slots, uint32_t n_valid, uint32_t n_bins, uint32_t low_bits, bool packed,
                            uint32_t* table, uint2* pairs, uint32_t* block_sums, uint32_t* sorted, bool hist_done, hipStream_t s) {
     const uint32_t n_buckets = (n_bins + (1u << low_bits) - 1u) >> low_bits;
     if (low_bits < 8u || low_bits > 12u || n_buckets > BKT_MAX) return hipErrorInvalidValue;
     const bool big = n_slots >= (2u << 20);
-    bool packed;
-    const uint32_t nt = bin_tile_threads(n_slots, low_bits, &packed), tile = nt * BKT_ITEMS;
+    if (packed != bin_entries_packed(n_slots, low_bits)) return hipErrorInvalidValue;
+    const uint32_t nt = bin_tile_threads(n_slots, packed), tile = nt * BKT_ITEMS;
     const uint32_t n_blocks = blocks_for(n_slots, tile);
     uint32_t* bucket_tot = block_sums;                 // [BKT_MAX]
     uint32_t* const zero = hist_done ? table : nullptr;         // counted by prep_rays_kernel: the table has to be zero again after this sort
