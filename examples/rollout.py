@@ -2,10 +2,12 @@
 """train.py-shaped rollout on the MI355X rover step path (no Isaac Sim, no learner).
 
 Mirrors the loop of the reference's `omniisaacgymenvs/train.py:57-125` (env = load...("Rover"); trainer loop:
-actions = agent.act(obs); obs, rew, done, info = env.step(actions)) with a random policy standing in for the skrl PPO
-agent and `vec_env.KinematicSim` standing in for PhysX.
+actions = agent.act(obs); obs, rew, done, info = env.step(actions)) with `vec_env.KinematicSim` standing in for PhysX and, for
+the skrl PPO agent, either a random policy (`--policy random`, the default) or the actor itself (`--policy actor`:
+`StochasticActorHeightmap.act`, sampled on the GPU in the kernel that ends its forward; `--checkpoint` loads a `state_dict` saved
+from the reference's module).
 
-    python examples/rollout.py --envs 4096 --steps 200 [--assets /path/to/omniisaacgymenvs]
+    python examples/rollout.py --envs 4096 --steps 200 [--assets /path/to/omniisaacgymenvs] [--policy actor [--checkpoint actor.pt]]
 """
 import argparse
 import os
@@ -25,6 +27,8 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--assets", default="", help="directory holding the reference's tasks/utils/terrain/... files")
     ap.add_argument("--native-rays", action="store_true", help="the reference's 1634-point distribution (1750-float obs)")
+    ap.add_argument("--policy", choices=("random", "actor"), default="random", help="random actions, or StochasticActorHeightmap.act(obs)")
+    ap.add_argument("--checkpoint", default="", help="--policy actor: a state_dict of the reference's StochasticActorHeightmap (torch.save)")
     args = ap.parse_args()
 
     scene = assets.load_reference_assets(args.assets) if args.assets else synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
@@ -39,19 +43,31 @@ def main():
     env.set_task(task, sim_params={"dt": 0.05}, spawn_positions=spawn)          # utils/task_util.py:45
     obs = env.reset()
     print(f"obs {tuple(obs.shape)}  actions {task.num_actions}  device {task.device}")
+    agent = None
+    if args.policy == "actor":
+        from isaac_rover_amd.learning.model import StochasticActorHeightmap
+        agent = StochasticActorHeightmap(task._engine, task)
+        if args.checkpoint:
+            sd = torch.load(args.checkpoint, map_location="cpu")
+            agent.load_state_dict(sd.get("policy", sd) if isinstance(sd, dict) else sd)
+        print(f"policy: StochasticActorHeightmap, {sum(v.numel() for v in agent.state_dict().values()):,} parameters"
+              f"{' from ' + args.checkpoint if args.checkpoint else ' (fresh initialisation)'}")
     ret = torch.zeros(args.envs, device=task.device)
     episodes = 0
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        actions = 2 * torch.rand(args.envs, 2, device=task.device) - 1          # agent.act(obs) goes here
+        if agent is None:
+            actions = 2 * torch.rand(args.envs, 2, device=task.device) - 1
+        else:
+            actions, log_prob, outputs = agent.act(obs)                            # what a PPO rollout stores next to obs and rew
         obs, rew, done, info = env.step(actions)
         ret += rew
         episodes += int(done.sum())                                             # host sync, like a logger would do
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{args.steps} steps x {args.envs} envs in {dt:.2f} s = {args.steps * args.envs / dt:,.0f} env-steps/s "
-          f"(incl. random policy + toy pose feeder); episodes finished: {episodes}; mean return {float(ret.mean()):.4f}")
+          f"(incl. {args.policy} policy + toy pose feeder); episodes finished: {episodes}; mean return {float(ret.mean()):.4f}")
     env.close()
 
 

@@ -347,6 +347,75 @@ ROVER_API const char *rover_mlp_chain_route(int32_t M, int32_t K0, int32_t n_lay
                                             const int32_t *activations);
 ROVER_API const char *rover_mlp_chain_pair_route(int32_t M, const rover_chain_desc *a, const rover_chain_desc *b);
 
+/* ---- the actor's Gaussian head: act() = sampled action + log-probability (learning/model.py:152-195 under skrl's GaussianMixin) ---- */
+/* Semantics of torch.distributions.Normal.  With mean [M, A] (the Tanh head's output), ls = log_std [A]:
+ *   ls'      = clamp(ls, min_log_std, max_log_std) if clip_log_std, else ls;        sigma = exp(ls')
+ *   actions  = mean + sigma * eps  (deterministic: mean), then clamp(actions, low, high) if clip_actions
+ *   x        = taken_actions if given, else the returned (possibly clamped) f32 actions
+ *   log_prob = reduce_j [ -((x_j - mean_j) / sigma_j)^2 / 2 - ls'_j - 0.5 log(2 pi) ]   ([M, 1]; ROVER_REDUCE_NONE: the terms, [M, A])
+ * log_prob is computed from x - mean, never from eps, so a call with taken_actions = the actions an earlier call returned gives that
+ * call's log_prob bit for bit.
+ * Noise: Philox4x32-10 (the generator of the goal / reset-yaw draws), for global row g = row_offset + r, call counter t and
+ * component pair p = j / 2:
+ *   w = philox(counter = (g, t & 0xffffffff, t >> 32, 0x50000000 | p), key = (seed & 0xffffffff, seed >> 32))
+ *   u0 = ((w[0] >> 8) + 1) 2^-24 in (0, 1],  u1 = (w[1] >> 8) 2^-24 in [0, 1),  rad = sqrt(-2 ln u0)
+ *   eps[2 p] = rad cos(2 pi u1),  eps[2 p + 1] = rad sin(2 pi u1)                  (finite, |eps| <= sqrt(48 ln 2) = 5.7681)
+ * The fourth counter word is 0 in the goal / yaw draws: the streams are disjoint under one seed.  A draw depends on (seed, t, g, j)
+ * alone — not on M, not on the kernel that runs the head, not on how a batch is sharded (a shard passes its env_offset as row_offset).
+ * The call counter is t = step + *step_dev (mod 2^64; step_dev NULL: step alone), read by the kernels WHEN THEY RUN.  The library never
+ * writes it: the caller advances *step_dev, with work enqueued on the SAME stream after the call (one increment per act), inside the
+ * captured region when the call is captured — then an eager call and a graph replay read and advance the same word and cannot drift
+ * apart.  A caller that evaluates log_prob for taken_actions, or passes an explicit step, does not advance it. */
+#define ROVER_REDUCE_SUM  0     /* skrl's reduction="sum" (the reference's, model.py:153-156) */
+#define ROVER_REDUCE_MEAN 1
+#define ROVER_REDUCE_PROD 2
+#define ROVER_REDUCE_MAX  3
+#define ROVER_REDUCE_MIN  4
+#define ROVER_REDUCE_NONE 5     /* log_prob is [M, A] */
+typedef struct {
+    const float *log_std;         /* [A] device: log_std_parameter (model.py:183)                                              */
+    int32_t A;                    /* 1 .. 16 components                                                                         */
+    int32_t clip_log_std;         /* clamp log_std to [min_log_std, max_log_std] (needs min <= max)                             */
+    float min_log_std, max_log_std;
+    int32_t clip_actions;         /* clamp the sampled actions to [low, high] (needs low <= high)                               */
+    float low, high;
+    int32_t reduction;            /* ROVER_REDUCE_*                                                                             */
+    int32_t deterministic;        /* actions = mean                                                                             */
+    uint64_t seed, step;
+    const uint64_t *step_dev;     /* optional [1] device word added to step when the kernels run (see above)                    */
+    int64_t row_offset;           /* global row of row 0: >= 0, row_offset + M <= 2^32                                          */
+    const float *taken_actions;   /* optional [M, A] device: log_prob is evaluated at these                                     */
+    int64_t taken_stride;
+    float *actions;               /* [M, A] out */
+    int64_t actions_stride;
+    float *log_prob;              /* [M, 1] out, [M, A] with ROVER_REDUCE_NONE */
+    int64_t log_prob_stride;
+    const float *mean;            /* rover_gaussian_head: the given mean [M, A].  rover_mlp_chain_act: unused (NULL) — the mean is  */
+    int64_t mean_stride;          /*   the chain's output y ("mean_actions")                                                    */
+} rover_gauss_head;
+/* rover_mlp_chain_forward with the head on its last layer's output (widths[n_layers - 1] == head->A): y receives the mean, exactly as
+ * rover_mlp_chain_forward writes it.  For A <= 4 on the two kernels that end the actor's forward ("mlp_small", "chain16<16,10,8,1>")
+ * the head runs INSIDE that kernel (the whole head of a row sits in one lane's accumulator registers): as many launches as the forward.
+ * Every other chain runs its forward and then the head as one more launch.  Chains outside the built tile shapes are refused like
+ * rover_mlp_chain_forward refuses them (run the layers one by one, then rover_gaussian_head).  The chain entry points' rule carries
+ * over: one stream per ctx at a time, the first small-batch call of a size warmed up outside a stream capture. */
+ROVER_API int rover_mlp_chain_act(rover_ctx *ctx, const float *x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers,
+                                  const float *const *weights, const float *const *biases, const int32_t *widths,
+                                  const int32_t *activations, float *y, int64_t y_stride, const rover_gauss_head *head, void *stream);
+/* The head on a given mean (head->mean [M, A], A <= 16): one launch, one thread per row. */
+ROVER_API int rover_gaussian_head(rover_ctx *ctx, int32_t M, const rover_gauss_head *head, void *stream);
+/* eps [M, A] (A <= 16) alone, as the head draws it for (seed, step + *step_dev, row_offset). */
+ROVER_API int rover_policy_noise(rover_ctx *ctx, uint64_t seed, uint64_t step, const uint64_t *step_dev, int64_t row_offset, int32_t M,
+                                 int32_t A, float *eps, int64_t eps_stride, void *stream);
+/* Host only (no ctx, no device): out[4] = Philox4x32-10(counter[4], key[2]) — the round function the kernels run, on the CPU. */
+ROVER_API int rover_philox4x32(const uint32_t *counter, const uint32_t *key, uint32_t *out);
+/* What rover_mlp_chain_act would launch — host only, no pointer is read but widths / activations and the descriptor's own fields
+ * (its pointers are only tested for NULL): "mlp_small+gauss" / "chain16<16,10,8,1>+gauss" when the head is fused into the chain's last
+ * kernel, "<rover_mlp_chain_route's name>;gauss" when it is a launch of its own, "none" for M = 0, NULL where the call would be
+ * refused with ROVER_E_INVALID (rover_last_error(NULL) says why). */
+ROVER_API const char *rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t *widths,
+                                                const int32_t *activations, const rover_gauss_head *head);
+
 /* ---- tuning knobs ------------------------------------------------------------------------------------- */
 /* name = "raycast_variant": 0 = auto; 1 = one half-wave per ray in env order, every cell block streamed from HBM;
  *        2 = rays counting-sorted by (map, cell), one wave per run of sorted rays, the cell's triangles held in registers

@@ -85,6 +85,17 @@ class ChainDesc(C.Structure):
                 ("biases", C.c_void_p), ("widths", C.c_void_p), ("activations", C.c_void_p), ("y", C.c_void_p), ("y_stride", C.c_int64)]
 
 
+class GaussHead(C.Structure):
+    _fields_ = [("log_std", C.c_void_p), ("A", C.c_int32), ("clip_log_std", C.c_int32), ("min_log_std", C.c_float), ("max_log_std", C.c_float),
+                ("clip_actions", C.c_int32), ("low", C.c_float), ("high", C.c_float), ("reduction", C.c_int32), ("deterministic", C.c_int32),
+                ("seed", C.c_uint64), ("step", C.c_uint64), ("step_dev", C.c_void_p), ("row_offset", C.c_int64),
+                ("taken_actions", C.c_void_p), ("taken_stride", C.c_int64), ("actions", C.c_void_p), ("actions_stride", C.c_int64),
+                ("log_prob", C.c_void_p), ("log_prob_stride", C.c_int64), ("mean", C.c_void_p), ("mean_stride", C.c_int64)]
+
+
+REDUCTIONS = {"sum": 0, "mean": 1, "prod": 2, "max": 3, "min": 4, None: 5, "none": 5}
+
+
 class ResetIO(C.Structure):
     _fields_ = [("reset_ids", C.c_void_p), ("n_reset_dev", C.c_void_p), ("n_reset_host", C.c_int32),
                 ("initial_pos3", C.c_void_p), ("pos3", C.c_void_p), ("quat4", C.c_void_p), ("joint_pos13", C.c_void_p),
@@ -141,6 +152,11 @@ SYMBOLS = {
     "rover_linear_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
     "rover_mlp_chain_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rover_mlp_chain_pair_route": (C.c_char_p, [C.c_int32, C.POINTER(ChainDesc), C.POINTER(ChainDesc)]),
+    "rover_mlp_chain_act": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(GaussHead), _P]),
+    "rover_gaussian_head": (C.c_int, [_P, C.c_int32, C.POINTER(GaussHead), _P]),
+    "rover_policy_noise": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    "rover_philox4x32": (C.c_int, [_P, _P, _P]),
+    "rover_mlp_chain_act_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(GaussHead)]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
     "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
     "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -218,6 +234,46 @@ def plan_raycast(num_envs, maps, P=0, have_dist=None, ray_precision=0, raycast_v
     if rc != 0:
         raise RoverError(f"rover_plan_raycast failed ({rc}): {lib.rover_last_error(None).decode()}")
     return {k: int(getattr(out, k)) for k, _ in RaycastPlan._fields_}
+
+
+def philox4x32(counter, key):
+    """rover_philox4x32: the four Philox4x32-10 words for ``counter`` (4 uint32) and ``key`` (2 uint32), computed on the host by the
+    round function the kernels run.  No ctx, no device."""
+    c = (C.c_uint32 * 4)(*[int(v) & 0xffffffff for v in counter])
+    k = (C.c_uint32 * 2)(*[int(v) & 0xffffffff for v in key])
+    out = (C.c_uint32 * 4)()
+    lib = load()
+    rc = lib.rover_philox4x32(c, k, out)
+    if rc != 0:
+        raise RoverError(f"rover_philox4x32 failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return tuple(int(v) for v in out)
+
+
+_FAKE = 16          # a non-null address for the descriptor of a route query (never read)
+
+
+def gauss_head_desc(A, log_std=_FAKE, actions=_FAKE, log_prob=_FAKE, clip_log_std=True, min_log_std=-20.0, max_log_std=2.0, clip_actions=False,
+                    low=-1.0, high=1.0, reduction="sum", deterministic=False, seed=0, step=0, step_dev=None, row_offset=0, taken_actions=None,
+                    taken_stride=None, actions_stride=None, log_prob_stride=None, mean=None, mean_stride=None):
+    """A rover_gauss_head from plain values (pointers as integers; the defaults are skrl's as the reference sets them, model.py:153-156).
+    ``reduction``: a name of REDUCTIONS or a code."""
+    red = reduction if isinstance(reduction, int) and not isinstance(reduction, bool) else REDUCTIONS[reduction]
+    A = int(A)
+    return GaussHead(log_std, A, int(bool(clip_log_std)), float(min_log_std), float(max_log_std), int(bool(clip_actions)), float(low), float(high),
+                     int(red), int(bool(deterministic)), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), step_dev, int(row_offset),
+                     taken_actions, A if taken_stride is None else int(taken_stride), actions, A if actions_stride is None else int(actions_stride),
+                     log_prob, (A if red == 5 else 1) if log_prob_stride is None else int(log_prob_stride), mean,
+                     A if mean_stride is None else int(mean_stride))
+
+
+def chain_act_route(m, k0, widths, activations, head=None):
+    """rover_mlp_chain_act_route: "mlp_small+gauss" / "chain16<16,10,8,1>+gauss" (the head inside the chain's last kernel),
+    "<chain route>;gauss" (the head as a launch of its own), "none" for m = 0, None where rover_mlp_chain_act would refuse the call.
+    ``head``: a GaussHead (gauss_head_desc) — default: the reference's settings with A = widths[-1]."""
+    k0, n, w, a = Engine._chain_shape(k0, widths, activations)
+    if head is None:
+        head = gauss_head_desc(widths[-1])
+    return Engine._route(load().rover_mlp_chain_act_route(int(m), k0, n, w, a, C.byref(head)))
 
 
 def _ptr(t):
@@ -606,6 +662,76 @@ class Engine:
             self._h, xa.shape[0], C.byref(da), C.byref(db), _ptr(copy_src) if copy_cols else None, copy_src.stride(0) if copy_cols else 0,
             _ptr(copy_dst) if copy_cols else None, copy_dst.stride(0) if copy_cols else 0, int(copy_cols), _stream(self._dev_index)),
             "rover_mlp_chain_pair_forward")
+
+    # ---- the actor's Gaussian head (rover_gauss_head) --------------------------------------------------
+    def _f32_rows(self, t, m, cols, name, what):
+        if t is None or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or tuple(t.shape) != (m, cols):
+            raise RoverError(f"{what}: {name} must be a float32 GPU matrix [{m},{cols}] with unit column stride")
+        return t
+
+    def _gauss_head(self, what, m, log_std, actions, log_prob, mean=None, taken_actions=None, step_dev=None, reduction="sum", **kw):
+        """-> GaussHead over checked tensors (log_std [A]; actions [m, A]; log_prob [m, 1], or [m, A] with reduction None)."""
+        a = int(log_std.numel())
+        self._chk(log_std, (a,), torch.float32, "log_std")
+        if reduction not in REDUCTIONS:
+            raise RoverError(f"{what}: unknown reduction {reduction!r}")
+        self._f32_rows(actions, m, a, "actions", what)
+        self._f32_rows(log_prob, m, a if REDUCTIONS[reduction] == 5 else 1, "log_prob", what)
+        if taken_actions is not None:
+            self._f32_rows(taken_actions, m, a, "taken_actions", what)
+        if mean is not None:
+            self._f32_rows(mean, m, a, "mean", what)
+        if step_dev is not None and (not step_dev.is_cuda or step_dev.dtype != torch.int64 or step_dev.numel() != 1):
+            raise RoverError(f"{what}: step_dev must be one int64 word on the GPU (read as uint64)")
+        dp = lambda t: None if t is None else t.data_ptr()
+        st = lambda t: 0 if t is None else t.stride(0)
+        return gauss_head_desc(a, dp(log_std), dp(actions), dp(log_prob), reduction=reduction, step_dev=dp(step_dev), taken_actions=dp(taken_actions),
+                               taken_stride=st(taken_actions), actions_stride=st(actions), log_prob_stride=st(log_prob), mean=dp(mean),
+                               mean_stride=st(mean), **kw)
+
+    def chain_act(self, x, layers, mean_out, log_std, actions, log_prob, **head):
+        """chain_forward with the Gaussian head on its output (rover_mlp_chain_act): ``mean_out`` receives what chain_forward writes,
+        ``actions`` / ``log_prob`` the head's results.  ``head``: taken_actions, step_dev, reduction and the scalar fields of
+        gauss_head_desc (seed, step, row_offset, deterministic, clip_*, ...)."""
+        m, k0 = x.shape
+        for t, name in ((x, "x"), (mean_out, "mean_out")):
+            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+                raise RoverError(f"chain_act: {name} must be a float32 GPU matrix with unit column stride")
+        n = len(layers)
+        k = k0
+        for l in layers:
+            self._chk(l.weight, (l.weight.shape[0], k), torch.float32, "weight")
+            self._chk(l.bias, (l.weight.shape[0],), torch.float32, "bias")
+            k = l.weight.shape[0]
+        if mean_out.shape[0] != m or mean_out.shape[1] != k:
+            raise RoverError(f"chain_act: mean_out must be [{m},{k}]")
+        desc = self._gauss_head("chain_act", m, log_std, actions, log_prob, **head)
+        w = (C.c_void_p * n)(*[_ptr(l.weight) for l in layers])
+        b = (C.c_void_p * n)(*[_ptr(l.bias) for l in layers])
+        widths = (C.c_int32 * n)(*[l.weight.shape[0] for l in layers])
+        acts = (C.c_int32 * n)(*[self.ACTIVATIONS[l.activation] for l in layers])
+        self._check(self.lib.rover_mlp_chain_act(self._h, _ptr(x), x.stride(0), m, k0, n, w, b, widths, acts, _ptr(mean_out), mean_out.stride(0),
+                                                 C.byref(desc), _stream(self._dev_index)), "rover_mlp_chain_act")
+        return actions, log_prob
+
+    def gaussian_head(self, mean, log_std, actions, log_prob, **head):
+        """The head on a given ``mean`` [m, A], A <= 16 (rover_gaussian_head): one launch."""
+        if mean is None or mean.dim() != 2:
+            raise RoverError("gaussian_head: mean must be a float32 GPU matrix")
+        desc = self._gauss_head("gaussian_head", mean.shape[0], log_std, actions, log_prob, mean=mean, **head)
+        self._check(self.lib.rover_gaussian_head(self._h, mean.shape[0], C.byref(desc), _stream(self._dev_index)), "rover_gaussian_head")
+        return actions, log_prob
+
+    def policy_noise(self, m, a, seed=0, step=0, step_dev=None, row_offset=0, out=None):
+        """eps [m, a] as the head draws it for (seed, step + *step_dev, row_offset) (rover_policy_noise)."""
+        if out is None:
+            out = torch.empty(int(m), int(a), device=self.device)
+        self._f32_rows(out, int(m), int(a), "out", "policy_noise")
+        self._check(self.lib.rover_policy_noise(self._h, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), _ptr(step_dev), int(row_offset), int(m),
+                                                int(a), _ptr(out), out.stride(0), _stream(self._dev_index)), "rover_policy_noise")
+        return out
+
+    chain_act_route = staticmethod(chain_act_route)
 
     # ---- which kernel a forward call runs (host only: no ctx, no launch) ----------------------------
     @staticmethod

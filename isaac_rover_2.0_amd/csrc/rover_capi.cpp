@@ -2,6 +2,7 @@
 // tables, argument checks, kernel sequencing.  No torch, no exceptions across the boundary.
 #include "../../include/rover_step.h"
 #include "rover_internal.h"
+#include "rover_philox.h"
 #include "rover_plan.h"
 
 #include <algorithm>
@@ -1509,6 +1510,104 @@ const char* rover_mlp_chain_pair_route(int32_t M, const rover_chain_desc* da, co
     static thread_local char name[64];
     if (chain_pair_side_by_side(ra, rb)) snprintf(name, sizeof name, "pair(%s)", na);
     else snprintf(name, sizeof name, "seq(%s;%s)", na, nb);
+    return name;
+}
+
+// ---- the Gaussian head ----
+// the validated descriptor (0 = ok, else the error is recorded with c, or for rover_last_error(NULL) when c is null); no pointer is read
+static int gauss_head_of(rover_ctx* c, const rover_gauss_head* g, int32_t M, bool given_mean, GaussHead* out) {
+    if (!g) return fail(c, ROVER_E_INVALID, "gauss_head: null descriptor");
+    if (g->A < 1 || g->A > GAUSS_MAX_A) return fail(c, ROVER_E_INVALID, "gauss_head: A = %d outside 1 .. %d", g->A, GAUSS_MAX_A);
+    if (g->clip_log_std && !(g->min_log_std <= g->max_log_std))
+        return fail(c, ROVER_E_INVALID, "gauss_head: min_log_std %g > max_log_std %g", (double)g->min_log_std, (double)g->max_log_std);
+    if (g->clip_actions && !(g->low <= g->high)) return fail(c, ROVER_E_INVALID, "gauss_head: low %g > high %g", (double)g->low, (double)g->high);
+    if (g->reduction < ROVER_REDUCE_SUM || g->reduction > ROVER_REDUCE_NONE) return fail(c, ROVER_E_INVALID, "gauss_head: unknown reduction %d", g->reduction);
+    if (!g->log_std || !g->actions || !g->log_prob) return fail(c, ROVER_E_INVALID, "gauss_head: log_std, actions and log_prob must be given");
+    const int lp_cols = g->reduction == ROVER_REDUCE_NONE ? g->A : 1;
+    if (g->actions_stride < g->A || g->log_prob_stride < lp_cols || (g->taken_actions && g->taken_stride < g->A))
+        return fail(c, ROVER_E_INVALID, "gauss_head: a row stride is shorter than its row (A = %d)", g->A);
+    if (given_mean && (!g->mean || g->mean_stride < g->A)) return fail(c, ROVER_E_INVALID, "gauss_head: mean [M, A] must be given");
+    if (M < 0 || g->row_offset < 0 || g->row_offset + (int64_t)M > (int64_t)1 << 32)
+        return fail(c, ROVER_E_INVALID, "gauss_head: rows %lld .. + %d outside [0, 2^32)", (long long)g->row_offset, M);
+    GaussHead h{};
+    h.log_std = g->log_std; h.A = g->A; h.clip_log_std = g->clip_log_std != 0; h.clip_actions = g->clip_actions != 0;
+    h.reduction = g->reduction; h.deterministic = g->deterministic != 0;
+    h.min_log_std = g->min_log_std; h.max_log_std = g->max_log_std; h.low = g->low; h.high = g->high;
+    h.seed = g->seed; h.step = g->step; h.step_dev = g->step_dev; h.row_offset = g->row_offset;
+    h.taken = g->taken_actions; h.taken_stride = g->taken_stride;
+    h.actions = g->actions; h.actions_stride = g->actions_stride; h.log_prob = g->log_prob; h.log_prob_stride = g->log_prob_stride;
+    *out = h;
+    return ROVER_OK;
+}
+
+int rover_mlp_chain_act(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers, const float* const* weights,
+                        const float* const* biases, const int32_t* widths, const int32_t* activations, float* y, int64_t y_stride,
+                        const rover_gauss_head* head, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    ChainArgs a{};
+    GaussHead h{};
+    if (int r = chain_args_of(c, x, x_stride, M, K0, n_layers, weights, biases, widths, activations, y, y_stride, &a)) return r;
+    if (int r = gauss_head_of(c, head, M, false, &h)) return r;
+    if (a.n[n_layers - 1] != h.A) return fail(c, ROVER_E_INVALID, "mlp_chain_act: the last layer is %d wide, the head has A = %d", a.n[n_layers - 1], h.A);
+    if (M == 0) return ROVER_OK;
+    const ChainRoute r = chain_route(a);
+    if (r.kernel == ChainKernel::None) return chain_refused(c);
+    USE_DEVICE(c);
+    hipStream_t s = (hipStream_t)stream;
+    if (chain_head_fused(r, h.A)) {
+        HIP_TRY(c, launch_chain_head(a, r, h, s));
+        return ROVER_OK;
+    }
+    if (int e = chain_run(c, a, r, s)) return e;
+    HIP_TRY(c, launch_gaussian_head(a.y, a.y_stride, M, h, s));
+    return ROVER_OK;
+}
+
+int rover_gaussian_head(rover_ctx* c, int32_t M, const rover_gauss_head* head, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    GaussHead h{};
+    if (int r = gauss_head_of(c, head, M, true, &h)) return r;
+    if (M == 0) return ROVER_OK;
+    USE_DEVICE(c);
+    HIP_TRY(c, launch_gaussian_head(head->mean, head->mean_stride, M, h, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+int rover_policy_noise(rover_ctx* c, uint64_t seed, uint64_t step, const uint64_t* step_dev, int64_t row_offset, int32_t M, int32_t A, float* eps,
+                       int64_t eps_stride, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    if (!eps || M < 0 || A < 1 || A > GAUSS_MAX_A || eps_stride < A || row_offset < 0 || row_offset + (int64_t)M > (int64_t)1 << 32)
+        return fail(c, ROVER_E_INVALID, "policy_noise: bad arguments (M=%d A=%d row_offset=%lld)", M, A, (long long)row_offset);
+    if (M == 0) return ROVER_OK;
+    USE_DEVICE(c);
+    HIP_TRY(c, launch_policy_noise(seed, step, step_dev, row_offset, M, A, eps, eps_stride, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+int rover_philox4x32(const uint32_t* counter, const uint32_t* key, uint32_t* out) {
+    if (!counter || !key || !out) return fail(nullptr, ROVER_E_INVALID, "philox4x32: null argument");
+    uint32_t w[4] = {counter[0], counter[1], counter[2], counter[3]};
+    philox4x32_10(w, key[0], key[1]);
+    for (int i = 0; i < 4; ++i) out[i] = w[i];
+    return ROVER_OK;
+}
+
+const char* rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations,
+                                      const rover_gauss_head* head) {
+    ChainArgs a;
+    GaussHead h{};
+    if (!chain_shape_of(M, K0, n_layers, widths, activations, &a)) {
+        fail(nullptr, ROVER_E_INVALID, "mlp_chain_act_route: bad shapes (M=%d K0=%d layers=%d)", M, K0, n_layers);
+        return nullptr;
+    }
+    if (gauss_head_of(nullptr, head, M, false, &h)) return nullptr;
+    if (a.n[n_layers - 1] != h.A) {
+        fail(nullptr, ROVER_E_INVALID, "mlp_chain_act_route: the last layer is %d wide, the head has A = %d", a.n[n_layers - 1], h.A);
+        return nullptr;
+    }
+    if (M == 0) return "none";
+    const char* name = chain_act_route_name(chain_route(a), h.A);
+    if (!name) fail(nullptr, ROVER_E_INVALID, "mlp_chain_act_route: net outside the built tile shapes");
     return name;
 }
 

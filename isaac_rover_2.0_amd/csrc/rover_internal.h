@@ -228,6 +228,30 @@ hipError_t launch_chain_splitk_pair(const ChainArgs& a, const ChainArgs& b, cons
                                     const float* copy_src, int64_t copy_src_stride, float* copy_dst, int64_t copy_dst_stride, int copy_cols,
                                     hipStream_t s);
 
+// The Gaussian policy head (rover_gauss_head of the C ABI, validated): actions = mean + exp(log_std') eps with counter-based noise,
+// and the log-probability of the returned (or the taken) actions — one row per thread, in the last kernel of the actor's forward
+// (chain16 / mlp_small "+gauss", A <= 4) or as a kernel of its own on a given mean.
+#define GAUSS_MAX_A 16
+enum GaussReduction { GAUSS_SUM = 0, GAUSS_MEAN = 1, GAUSS_PROD = 2, GAUSS_MAX = 3, GAUSS_MIN = 4, GAUSS_NONE = 5 };
+struct GaussHead {
+    const float* log_std;                  // [A]
+    int32_t A, clip_log_std, clip_actions, reduction, deterministic;
+    float min_log_std, max_log_std, low, high;
+    uint64_t seed, step;
+    const uint64_t* step_dev;              // optional [1]: added to step on the device (a captured graph's call counter)
+    int64_t row_offset;                    // global row of local row 0 (a shard's env_offset)
+    const float* taken; int64_t taken_stride;      // optional [M, A]: log_prob is evaluated at these instead of the returned actions
+    float* actions; int64_t actions_stride;        // [M, A]
+    float* log_prob; int64_t log_prob_stride;      // [M, 1], or [M, A] with GAUSS_NONE
+};
+// fused: the chain's last kernel carries the head (A <= 4 on mlp_small / chain16<16,10,8,1>); else forward, then the head's own launch
+bool chain_head_fused(const ChainRoute& r, int A);
+const char* chain_act_route_name(const ChainRoute& r, int A);     // "mlp_small+gauss", "chain16<16,10,8,1>;gauss", ..., or NULL
+hipError_t launch_chain_head(const ChainArgs& a, const ChainRoute& r, const GaussHead& h, hipStream_t s);       // chain_head_fused() routes only
+hipError_t launch_gaussian_head(const float* mean, int64_t mean_stride, int M, const GaussHead& h, hipStream_t s);
+hipError_t launch_policy_noise(uint64_t seed, uint64_t step, const uint64_t* step_dev, int64_t row_offset, int M, int A, float* eps,
+                               int64_t eps_stride, hipStream_t s);
+
 // blocks of bs threads (or items) that cover n: the launchers' grid sizes
 static inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
 

@@ -33,6 +33,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "rover_internal.h"
+#include "rover_philox.h"
 #include "rover_raymath.h"
 
 namespace rover {
@@ -897,15 +898,9 @@ __global__ void __launch_bounds__(256) sample_height_kernel(HeightDev h, const f
 
 // Philox4x32-10 (Salmon et al. 2011), used when the caller supplies no uniforms
 __device__ __forceinline__ float philox_uniform(uint64_t seed, uint32_t draw, uint32_t idx) {
-    uint32_t c0 = idx, c1 = draw, c2 = 0u, c3 = 0u, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return (float)(c0 >> 8) * (1.0f / 16777216.0f);                        // [0,1) with 24 bits, like torch.rand f32
+    uint32_t c[4] = {idx, draw, 0u, 0u};                                   // word 3 = 0: the policy's action noise uses 0x50000000 | pair
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (float)(c[0] >> 8) * (1.0f / 16777216.0f);                      // [0,1) with 24 bits, like torch.rand f32
 }
 
 // generate_goals rover.py:544-549 (+ random_goals :554-564, check_goal_collision :533-542, goal z :581-583).

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rover_internal.h"
+#include "rover_philox.h"
 
 namespace rover {
 
@@ -277,6 +278,115 @@ __device__ __forceinline__ void c16_store(const f32x4 (&acc)[T], float* __restri
         }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The Gaussian policy head (skrl's GaussianMixin on learning/model.py:152-195, semantics of torch.distributions.Normal): ONE definition
+// of the noise and of the arithmetic, used by the fused epilogues of chain16 / mlp_small, by gaussian_head_kernel and by
+// policy_noise_kernel.
+//
+// Noise: Philox4x32-10 keyed by the seed, counter (global row, call counter lo, hi, 0x50000000 | component pair) -> two uniforms ->
+// Box-Muller.  A draw depends on (seed, call counter, global row, component) alone: not on the batch size, the kernel route or the
+// sharding.  u0 = (24 bits + 1) 2^-24 in (0, 1] keeps the logarithm finite: |eps| <= sqrt(48 ln 2).  sincospif takes the angle in
+// half turns, so 2 pi u1 is never rounded.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void gauss_eps_pair(uint64_t seed, uint64_t t, uint32_t g, uint32_t p, float& e0, float& e1) {
+    uint32_t c[4] = {g, (uint32_t)t, (uint32_t)(t >> 32), 0x50000000u | p};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float u0 = (float)((c[0] >> 8) + 1u) * (1.0f / 16777216.0f);
+    const float u1 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
+    const float rad = sqrtf(-2.0f * logf(u0));
+    float sn, cs;
+    sincospif(2.0f * u1, &sn, &cs);
+    e0 = rad * cs;
+    e1 = rad * sn;
+}
+
+__device__ __forceinline__ float gauss_clamp(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }     // a NaN stays a NaN (torch.clamp)
+
+// one row: mean[0 .. A) in registers -> actions and log_prob stored (row: the LOCAL row; the noise is drawn for row_offset + row).
+// log_prob comes from x - mean of the returned f32 action (or the taken one), never from eps: act(s) and act(s, taken = the
+// returned actions) run the same instructions on the same values.
+template <int AMAX>
+__device__ __forceinline__ void gaussian_head(const GaussHead& h, uint32_t row, const float (&mean)[AMAX]) {
+    const uint64_t t = h.step + (h.step_dev ? *h.step_dev : 0ull);
+    const uint32_t g = (uint32_t)((uint64_t)h.row_offset + row);
+    const int A = h.A < AMAX ? h.A : AMAX;
+    float* __restrict__ act_row = h.actions + (size_t)row * h.actions_stride;
+    float lp[AMAX];
+#pragma unroll
+    for (int p = 0; p < (AMAX + 1) / 2; ++p) {
+        float e[2] = {0.0f, 0.0f};
+        if (2 * p < A && !h.deterministic) gauss_eps_pair(h.seed, t, g, (uint32_t)p, e[0], e[1]);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int j = 2 * p + q;
+            if (j >= AMAX) continue;
+            lp[j] = 0.0f;
+            if (j >= A) continue;
+            float ls = h.log_std[j];
+            if (h.clip_log_std) ls = gauss_clamp(ls, h.min_log_std, h.max_log_std);
+            const float sigma = expf(ls);
+            float act = h.deterministic ? mean[j] : mean[j] + sigma * e[q];
+            if (h.clip_actions) act = gauss_clamp(act, h.low, h.high);
+            act_row[j] = act;
+            const float x = h.taken ? h.taken[(size_t)row * h.taken_stride + j] : act;
+            const float z = (x - mean[j]) / sigma;
+            lp[j] = (-0.5f * (z * z) - ls) - 0.91893853320467274f;          // 0.5 log(2 pi)
+        }
+    }
+    float* __restrict__ lp_row = h.log_prob + (size_t)row * h.log_prob_stride;
+    if (h.reduction == GAUSS_NONE) {
+#pragma unroll
+        for (int j = 0; j < AMAX; ++j) if (j < A) lp_row[j] = lp[j];
+        return;
+    }
+    float r = lp[0];
+#pragma unroll
+    for (int j = 1; j < AMAX; ++j) {
+        if (j >= A) continue;
+        const float v = lp[j];
+        switch (h.reduction) {
+            case GAUSS_PROD: r = r * v; break;
+            case GAUSS_MAX: r = (v > r || v != v) ? v : r; break;
+            case GAUSS_MIN: r = (v < r || v != v) ? v : r; break;
+            default: r = r + v; break;
+        }
+    }
+    if (h.reduction == GAUSS_MEAN) r = r / (float)A;
+    lp_row[0] = r;
+}
+
+// the head of a chain kernel's last accumulator tile: lane (m, g = 0) holds features 0 .. 3 of its batch row (A <= 4)
+__device__ __forceinline__ void c16_gauss(const f32x4& acc, const GaussHead& h, int M, uint32_t row, uint32_t g) {
+    if (g != 0u || row >= (uint32_t)M) return;
+    const float mean[4] = {acc[0], acc[1], acc[2], acc[3]};
+    gaussian_head<4>(h, row, mean);
+}
+
+// on a given mean [M, A], A <= 16: one thread per row (the per-layer route, chains outside the fused tile shapes, A > 4)
+__global__ void __launch_bounds__(256) gaussian_head_kernel(GaussHead h, const float* __restrict__ mean_in, int64_t mean_stride, int M) {
+    const uint32_t row = blockIdx.x * 256u + threadIdx.x;
+    if (row >= (uint32_t)M) return;
+    float mean[GAUSS_MAX_A];
+#pragma unroll
+    for (int j = 0; j < GAUSS_MAX_A; ++j) mean[j] = j < h.A ? mean_in[(size_t)row * mean_stride + j] : 0.0f;
+    gaussian_head<GAUSS_MAX_A>(h, row, mean);
+}
+
+// eps [M, A] alone: what gaussian_head draws for these (seed, call counter, row_offset)
+__global__ void __launch_bounds__(256) policy_noise_kernel(uint64_t seed, uint64_t step, const uint64_t* __restrict__ step_dev, int64_t row_offset,
+                                                           int M, int A, float* __restrict__ eps, int64_t eps_stride) {
+    const uint32_t row = blockIdx.x * 256u + threadIdx.x;
+    if (row >= (uint32_t)M) return;
+    const uint64_t t = step + (step_dev ? *step_dev : 0ull);
+    const uint32_t g = (uint32_t)((uint64_t)row_offset + row);
+    for (int p = 0; 2 * p < A; ++p) {
+        float e0, e1;
+        gauss_eps_pair(seed, t, g, (uint32_t)p, e0, e1);
+        eps[(size_t)row * eps_stride + 2 * p] = e0;
+        if (2 * p + 1 < A) eps[(size_t)row * eps_stride + 2 * p + 1] = e1;
+    }
+}
+
 // layer 1 for the TN output tiles that start at weight row n_off: both operands from LDS slabs of 32 k.  Staging is 16 bytes per
 // lane and instruction (global_load_dwordx4 at 4-byte alignment -> ds_write_b128): 2 + 2 loads and stores per thread and slab where
 // dword staging took 13 + 13 with a 64-bit address and two bounds tests each — measured, the staging instructions do not hide
@@ -340,8 +450,10 @@ __device__ __forceinline__ void c16_layer1(f32x4 (&a1)[TN], const ChainArgs& a, 
 // T1..T4: 16-wide output tiles of the layers (T3 = T4 = 0: a 2-layer chain).  The 4-layer chain computes layer 1 in two halves of
 // T1 / 2 tiles, each fed into layer 2's accumulators as soon as it is done (the input rows are staged twice: k = 124 is four
 // slabs): 32 + 40 live accumulator registers instead of 64 + 40, and the kernel stays under 128 VGPRs without spilling.
-template <int T1, int T2, int T3, int T4>
-__global__ void __launch_bounds__(512, 4) chain16_kernel(ChainArgs a) {       // four waves per SIMD (two workgroups per CU): <= 128 VGPRs
+// HEAD: the Gaussian head on the last layer's tile before it is stored (gauss: then non-null) — instantiations of their own
+// (chain16_head_kernel); the plain ones are what they were.
+template <int T1, int T2, int T3, int T4, bool HEAD>
+__device__ __forceinline__ void chain16_body(const ChainArgs& a, const GaussHead* gauss) {
     constexpr bool LONG = T3 != 0;
     constexpr int T1H = LONG ? T1 / 2 : T1;
     constexpr uint32_t L1 = (128u + T1H * 16u) * C16_XP;                                 // layer 1: input rows + weight rows, 32 k each
@@ -396,9 +508,19 @@ __global__ void __launch_bounds__(512, 4) chain16_kernel(ChainArgs a) {       //
             c16_zero(a4);
             c16_layer<T3, T4>(a3, a4, a.w[3], a.n[2], a.n[3], 0u, lds, tid, m, g);
             c16_bias_act(a4, a.b[3], a.n[3], a.act[3], g);
+            if constexpr (HEAD) c16_gauss(a4[0], *gauss, a.M, row, g);
             c16_store(a4, a.y, a.y_stride, a.n[3], a.M, row, g);
         }
     }
+}
+template <int T1, int T2, int T3, int T4>
+__global__ void __launch_bounds__(512, 4) chain16_kernel(ChainArgs a) {       // four waves per SIMD (two workgroups per CU): <= 128 VGPRs
+    chain16_body<T1, T2, T3, T4, false>(a, nullptr);
+}
+template <int T1, int T2, int T3, int T4>
+__global__ void __launch_bounds__(512, 4) chain16_head_kernel(ChainArgs a, GaussHead h) {
+    static_assert(T4 == 1, "the head sits on the 4-layer chain's last tile");
+    chain16_body<T1, T2, T3, T4, true>(a, &h);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -595,7 +717,8 @@ hipError_t launch_chain_splitk_pair(const ChainArgs& a, const ChainArgs& b, cons
 // ds_read_b128 per 16 k.  chain16_kernel walks ~42 barrier-synchronised slab steps per 128 rows (67 us whatever the batch); here a
 // layer is <= 2 tiles x 16 steps per wave (25 us at 512 rows, 30 us at 4 096).
 #define MS_PITCH 260
-__global__ void __launch_bounds__(512) mlp_small_kernel(ChainArgs a) {
+template <bool HEAD>
+__device__ __forceinline__ void mlp_small_body(const ChainArgs& a, const GaussHead* gauss) {
     __shared__ __attribute__((aligned(16))) float buf[2][16][MS_PITCH];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, m = lane & 15u, g = lane >> 4;
     const uint32_t row0 = blockIdx.x * 16u;
@@ -631,13 +754,16 @@ __global__ void __launch_bounds__(512) mlp_small_kernel(ChainArgs a) {
             }
             // lane (m, g) holds features 16 t + 4 g + r of batch row m; features past N are written as zeros: they are the padding
             // columns the next layer's 16-wide k steps read
+            f32x4 out;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const uint32_t f = 16u * t + 4u * g + (uint32_t)r;
                 const float v = f < N ? mlp_act(acc[r] + (a.b[l] ? a.b[l][f] : 0.0f), a.act[l]) : 0.0f;
                 if (last) { if (f < N && row0 + m < (uint32_t)a.M) a.y[(size_t)(row0 + m) * a.y_stride + f] = v; }
                 else buf[cur ^ 1u][m][f] = v;
+                out[r] = v;
             }
+            if constexpr (HEAD) { if (last && t == 0u) c16_gauss(out, *gauss, a.M, row0 + m, g); }      // features 0 .. 3: tile 0's g = 0 lanes
         }
         if (!last) {
             __syncthreads();
@@ -646,6 +772,8 @@ __global__ void __launch_bounds__(512) mlp_small_kernel(ChainArgs a) {
         }
     }
 }
+__global__ void __launch_bounds__(512) mlp_small_kernel(ChainArgs a) { mlp_small_body<false>(a, nullptr); }
+__global__ void __launch_bounds__(512) mlp_small_head_kernel(ChainArgs a, GaussHead h) { mlp_small_body<true>(a, &h); }
 
 // tile shapes instantiated: the reference's encoder (<= 80 -> <= 64, or <= 96 -> <= 64) and MLP (<= 256 -> <= 160 -> <= 128 -> <= 16,
 // hidden activations none / LeakyReLU / ReLU); anything else: ChainKernel::None (the caller runs layer by layer).  The same nets go
@@ -681,6 +809,41 @@ hipError_t launch_chain(const ChainArgs& a, const ChainRoute& r, float* scratch,
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+// ---- the Gaussian head's launches -------------------------------------------------------------------------------------------
+// Fused where the whole head of a row sits in one lane of the chain's last tile (A <= 4) on the two kernels that end the actor's
+// forward; every other chain runs its forward, then gaussian_head_kernel on the stored mean.
+bool chain_head_fused(const ChainRoute& r, int A) {
+    return A >= 1 && A <= 4 && (r.kernel == ChainKernel::MlpSmall || r.kernel == ChainKernel::Chain16Long);
+}
+hipError_t launch_chain_head(const ChainArgs& a, const ChainRoute& r, const GaussHead& h, hipStream_t s) {
+    if (!chain_head_fused(r, h.A) || a.n[a.n_layers - 1] != h.A) return hipErrorInvalidValue;
+    if (r.kernel == ChainKernel::MlpSmall) hipLaunchKernelGGL(mlp_small_head_kernel, dim3((uint32_t)((a.M + 15) / 16)), dim3(512), 0, s, a, h);
+    else hipLaunchKernelGGL((chain16_head_kernel<16, 10, 8, 1>), dim3((uint32_t)((a.M + 127) / 128)), dim3(512), 0, s, a, h);
+    return hipGetLastError();
+}
+hipError_t launch_gaussian_head(const float* mean, int64_t mean_stride, int M, const GaussHead& h, hipStream_t s) {
+    if (h.A < 1 || h.A > GAUSS_MAX_A) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gaussian_head_kernel, dim3(blocks_for((uint64_t)M, 256u)), dim3(256), 0, s, h, mean, mean_stride, M);
+    return hipGetLastError();
+}
+hipError_t launch_policy_noise(uint64_t seed, uint64_t step, const uint64_t* step_dev, int64_t row_offset, int M, int A, float* eps,
+                               int64_t eps_stride, hipStream_t s) {
+    hipLaunchKernelGGL(policy_noise_kernel, dim3(blocks_for((uint64_t)M, 256u)), dim3(256), 0, s, seed, step, step_dev, row_offset, M, A, eps, eps_stride);
+    return hipGetLastError();
+}
+const char* chain_act_route_name(const ChainRoute& r, int A) {
+    if (A < 1 || A > GAUSS_MAX_A) return nullptr;
+    const bool fused = chain_head_fused(r, A);
+    switch (r.kernel) {
+        case ChainKernel::SplitK: return r.tn == 5 ? (r.rt == 2 ? "splitk<5,2>;gauss" : "splitk<5,1>;gauss") : (r.rt == 2 ? "splitk<6,2>;gauss" : "splitk<6,1>;gauss");
+        case ChainKernel::MlpSmall: return fused ? "mlp_small+gauss" : "mlp_small;gauss";
+        case ChainKernel::Chain16_5: return "chain16<5,4,0,0>;gauss";
+        case ChainKernel::Chain16_6: return "chain16<6,4,0,0>;gauss";
+        case ChainKernel::Chain16Long: return fused ? "chain16<16,10,8,1>+gauss" : "chain16<16,10,8,1>;gauss";
+        default: return nullptr;
+    }
 }
 
 // the instantiation a route launches, by name (rover_linear_route / rover_mlp_chain_route)

@@ -6,6 +6,12 @@ Mirrors ``omniisaacgymenvs/learning/model.py``: ``Layer`` (:84-121, Linear + act
 ``cfg/trainSKRL/RoverPPOSKRL.yaml:7-9``), the results are concatenated with the proprioceptive values and fed to the
 MLP (256 → 160 → 128, yaml :3-5) with a Tanh head of 2 (actor) or a linear head of 1 (critic).
 
+``act()`` adds what a rollout asks of the actor (skrl's ``GaussianMixin``, built by the reference with ``clip_actions=False,
+clip_log_std=True, min_log_std=-20, max_log_std=2, reduction="sum"``, model.py:153-156): a sampled action, its log-probability and the
+log-probability of actions taken earlier — inside the kernel that ends the forward (``rover_mlp_chain_act``), with counter-based
+noise keyed by (seed, call counter, GLOBAL row), so a shard draws its slice of the whole batch's noise.  The critic's ``act()`` is
+``DeterministicMixin``'s (:198-201).
+
 Large batches run each encoder and the MLP + head as ONE fused kernel each (``rover_mlp_chain_forward``, f32 MFMA, activations
 kept in registers between the layers); otherwise every ``Layer`` is one ``rover_linear_forward`` launch.  The slices are read in
 place from ``obs_buf`` and the encoder outputs are written straight into the concat buffer, so there is no ``torch.cat``.  Training (skrl PPO,
@@ -31,8 +37,18 @@ class HeightmapNet:
     """Shared body of the reference's two model classes; ``head_activation`` 'tanh' = actor, None = critic."""
 
     def __init__(self, engine, num_observations, num_sparse, num_dense, num_outputs, head_activation, mlp_features=(256, 160, 128),
-                 encoder_features=(80, 60), activation_function="leakyrelu", device="cuda:0", seed=0):
+                 encoder_features=(80, 60), activation_function="leakyrelu", device="cuda:0", seed=0, clip_actions=False, clip_log_std=True,
+                 min_log_std=-20.0, max_log_std=2.0, reduction="sum", row_offset=0, action_low=-1.0, action_high=1.0):
+        """``seed`` initialises the weights and keys the action noise; ``row_offset``: the global row of this net's row 0 (a shard's
+        env_offset); ``clip_*`` / ``min_log_std`` / ``max_log_std`` / ``reduction``: skrl's mixin arguments (model.py:153-156,198-201);
+        ``action_low`` / ``action_high``: the action space's bounds, used only with ``clip_actions``."""
         g = torch.Generator().manual_seed(seed)
+        if reduction not in ("sum", "mean", "prod", "max", "min", None):
+            raise ValueError(f"reduction must be one of 'sum', 'mean', 'prod', 'max', 'min' or None, not {reduction!r}")
+        self.seed, self.row_offset, self.reduction = int(seed), int(row_offset), reduction
+        self.clip_actions, self.clip_log_std = bool(clip_actions), bool(clip_log_std)
+        self.min_log_std, self.max_log_std = float(min_log_std), float(max_log_std)
+        self.action_low, self.action_high = float(action_low), float(action_high)
         self.engine, self.device = engine, device
         self.num_sparse, self.num_dense = num_sparse, num_dense
         self.num_proprioception = num_observations - num_sparse - num_dense                # model.py:174
@@ -52,6 +68,10 @@ class HeightmapNet:
         # :183 — only the stochastic actor owns a log-std parameter (DeterministicHeightmap has none, :197-241)
         self.log_std_parameter = torch.zeros(num_outputs, device=device) if head_activation == "tanh" else None
         self._bufs = {}
+        # act()'s call counter, in device memory so that a captured graph draws fresh noise on every replay: read by the head's kernel,
+        # advanced by act() on the same stream right after it (eager and captured alike)
+        self._act_counter = torch.zeros(1, dtype=torch.int64, device=device)
+        self._last_rows = 0
 
     def _buf(self, key, rows, cols):
         b = self._bufs.get(key)
@@ -64,6 +84,20 @@ class HeightmapNet:
         ``fused``: run each encoder and the MLP + head as ONE kernel each (``rover_mlp_chain_forward``: activations stay in
         registers) — default for batches of >= 20 480 rows when the layer widths fit the built tile shapes; otherwise one
         ``rover_linear_forward`` launch per layer."""
+        cat, mlp_fused = self._encode(states, fused)
+        if mlp_fused:
+            e = states.shape[0]
+            return self.engine.chain_forward(cat, self.network, self._buf(("mlp", len(self.network) - 1), e, self.network[-1].weight.shape[0]))
+        return self._mlp_layers(cat)
+
+    def _mlp_layers(self, cat):
+        x = cat
+        for li, layer in enumerate(self.network):
+            x = self.engine.linear_forward(x, layer.weight, layer.bias, layer.activation, self._buf(("mlp", li), cat.shape[0], layer.weight.shape[0]))
+        return x
+
+    def _encode(self, states, fused):
+        """Both encoders and the proprioception columns into the concat buffer -> (cat, whether the MLP + head runs as one chain kernel)."""
         e = states.shape[0]
         p, ns, nd = self.num_proprioception, self.num_sparse, self.num_dense
         ef = self.encoder0[-1].weight.shape[0]
@@ -76,12 +110,7 @@ class HeightmapNet:
             self.engine.chain_pair_forward(states[:, p:p + ns], self.encoder0, cat[:, p:p + ef],
                                            states[:, p + ns:p + ns + nd], self.encoder1, cat[:, p + ef:p + 2 * ef],
                                            copy_src=states, copy_dst=cat, copy_cols=p)
-            if self.engine.chain_fits(self.network):
-                return self.engine.chain_forward(cat, self.network, self._buf(("mlp", len(self.network) - 1), e, self.network[-1].weight.shape[0]))
-            x = cat
-            for li, layer in enumerate(self.network):
-                x = self.engine.linear_forward(x, layer.weight, layer.bias, layer.activation, self._buf(("mlp", li), e, layer.weight.shape[0]))
-            return x
+            return cat, self.engine.chain_fits(self.network)
         cat[:, 0:p] = states[:, 0:p]
         for enc, lo, n, col in ((self.encoder0, p, ns, p), (self.encoder1, p + ns, nd, p + ef)):
             x = states[:, lo:lo + n]
@@ -92,12 +121,60 @@ class HeightmapNet:
                 last = li == len(enc) - 1
                 out = cat[:, col:col + ef] if last else self._buf(("enc", col, li), e, layer.weight.shape[0])
                 x = self.engine.linear_forward(x, layer.weight, layer.bias, layer.activation, out)
-        if fused and self.engine.chain_fits(self.network):
-            return self.engine.chain_forward(cat, self.network, self._buf(("mlp", len(self.network) - 1), e, self.network[-1].weight.shape[0]))
-        x = cat
-        for li, layer in enumerate(self.network):
-            x = self.engine.linear_forward(x, layer.weight, layer.bias, layer.activation, self._buf(("mlp", li), e, layer.weight.shape[0]))
-        return x
+        return cat, bool(fused and self.engine.chain_fits(self.network))
+
+    # ---- skrl's mixins: GaussianMixin.act (actor), DeterministicMixin.act (critic) --------------------------------
+    def act(self, states, taken_actions=None, deterministic=False, step=None, role="", fused=None):
+        """Actor: -> (actions [E, A], log_prob [E, 1] ([E, A] with reduction None), {"mean_actions": mean [E, A]}) with
+        mean = compute(states), actions = mean + exp(log_std') eps (``deterministic``: mean), clamped to the action bounds only with
+        ``clip_actions``, and log_prob that of ``taken_actions`` if given, else of the returned actions.  Also skrl's calling shape:
+        ``act({"states": s, "taken_actions": a}, role="policy")``.  ``actions`` and ``log_prob`` are new tensors; ``mean_actions`` is
+        compute()'s buffer (overwritten by the next compute() / act() of the same batch size).
+        The noise of row r is keyed by (seed, call counter, row_offset + r): it does not depend on the batch size or the kernel.  The
+        counter lives on the device and advances by one per act() — not when ``taken_actions`` is given (an evaluation of old actions)
+        and not when ``step`` (an explicit counter value) is passed.  Capturing act() in a graph: warm it up once first; every replay
+        then reads and advances the same counter an eager call does.
+        Critic (no log-std parameter): -> (value, None, {})."""
+        if isinstance(states, dict):
+            inputs = states
+            states, taken_actions = inputs["states"], inputs.get("taken_actions", taken_actions)
+        if self.log_std_parameter is None:
+            value = self.compute(states, fused)
+            if self.clip_actions:
+                value = torch.clamp(value, self.action_low, self.action_high)
+            return value, None, {}
+        e, a = states.shape[0], self.network[-1].weight.shape[0]
+        self._last_rows = e
+        actions = torch.empty(e, a, device=self.device)
+        log_prob = torch.empty(e, a if self.reduction is None else 1, device=self.device)
+        mean = self._buf(("mlp", len(self.network) - 1), e, a)
+        head = dict(taken_actions=taken_actions, reduction=self.reduction, deterministic=deterministic, seed=self.seed, row_offset=self.row_offset,
+                    clip_log_std=self.clip_log_std, min_log_std=self.min_log_std, max_log_std=self.max_log_std, clip_actions=self.clip_actions,
+                    low=self.action_low, high=self.action_high)
+        if step is None:
+            head["step_dev"] = self._act_counter
+        else:
+            head["step"] = int(step)
+        cat, mlp_fused = self._encode(states, fused)
+        if mlp_fused:
+            self.engine.chain_act(cat, self.network, mean, self.log_std_parameter, actions, log_prob, **head)
+        else:
+            self.engine.gaussian_head(self._mlp_layers(cat), self.log_std_parameter, actions, log_prob, **head)
+        if step is None and taken_actions is None:
+            self._act_counter += 1
+        return actions, log_prob, {"mean_actions": mean}
+
+    def _clipped_log_std(self):
+        ls = self.log_std_parameter
+        return torch.clamp(ls, self.min_log_std, self.max_log_std) if self.clip_log_std else ls
+
+    def get_log_std(self, role=""):
+        """log_std' (clamped if ``clip_log_std``) as [rows of the last act(), A]."""
+        return self._clipped_log_std().expand(max(self._last_rows, 1), -1)
+
+    def get_entropy(self, role=""):
+        """Normal's entropy per component, 0.5 + 0.5 log(2 pi) + log_std', as [rows of the last act(), A]."""
+        return 0.5 + 0.5 * math.log(2.0 * math.pi) + self.get_log_std(role)
 
     # ---- interop with the reference's nn.Module parameter names --------------------------------------------
     def state_dict(self):
@@ -122,6 +199,7 @@ class HeightmapNet:
 
 def StochasticActorHeightmap(engine, task, **kw):
     hm = task.Camera.heightmap
+    kw.setdefault("row_offset", int(engine.cfg.env_offset))       # a shard's actor draws its slice of the global batch's noise
     return HeightmapNet(engine, task.num_observations, hm.get_num_sparse_vector(), hm.get_num_dense_vector(), task.num_actions,
                         "tanh", device=task.device, **kw)
 
