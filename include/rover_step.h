@@ -307,8 +307,11 @@ ROVER_API int rover_linear_forward(rover_ctx *ctx, const float *x, int64_t x_str
  * last layer's output touch HBM: the activations stay in the MFMA accumulator registers, which are the next layer's B operand as
  * they are (csrc/rover_mlp.hip).  weights[i] is nn.Linear's [widths[i]][widths[i-1]] (K0 for i = 0), biases[i] may be NULL.
  * Built tile shapes: 2 layers with widths <= 96, <= 64; 4 layers with widths <= 256, <= 160, <= 128, <= 16 and activation 0, 1 or 3
- * (none / LeakyReLU / ReLU) on the three hidden layers (else ROVER_E_INVALID: use rover_linear_forward per layer).  Same numerics as
- * rover_linear_forward up to the summation order inside a layer.
+ * (none / LeakyReLU / ReLU) on the three hidden layers (else ROVER_E_INVALID: use rover_linear_forward per layer).  That rule, and
+ * which kernel a chain gets at which batch size, lives in ONE place, chain_route() of csrc/rover_mlp.hip; a caller that has to know
+ * beforehand asks rover_mlp_chain_route below (non-NULL: the chain fits) instead of restating widths or row counts, as the Python
+ * binding's chain_fits() and the policy nets' forward plan (learning/model.py) do.  Same numerics as rover_linear_forward up to the
+ * summation order inside a layer.
  * Small batches (M < 20 480 with a 2-layer chain) go through a split-k scratch buffer that the ctx owns and grows on demand: the
  * chain entry points of one ctx must therefore run on ONE stream at a time (two forwards overlapped on different streams need two
  * ctxs), and the first small-batch call of a given size must not happen inside a stream capture (it may hipMalloc and synchronise);
@@ -340,8 +343,9 @@ ROVER_API int rover_mlp_chain_pair_forward(rover_ctx *ctx, int32_t M, const rove
  *     "chain16<5,4,0,0>", "chain16<6,4,0,0>" or "chain16<16,10,8,1>";
  *   rover_mlp_chain_pair_route: "pair(splitk<TN,RT>)" when both chains run side by side, else "seq(<a>;<b>)" (one after the other,
  *     the copy as a hipMemcpy2DAsync).
- * "none" where the call launches nothing (M = 0); NULL where it would be refused with ROVER_E_INVALID for its shapes.  Strings are
- * static, except rover_mlp_chain_pair_route's, which stays valid until the calling thread's next call of it. */
+ * "none" where the call launches nothing (M = 0); NULL where it would be refused with ROVER_E_INVALID for its shapes.  Some names are
+ * composed in a buffer of the calling thread: a returned pointer is valid until that thread's next route query (any of these three or
+ * rover_mlp_chain_act_route). */
 ROVER_API const char *rover_linear_route(int32_t M, int32_t K, int32_t N);
 ROVER_API const char *rover_mlp_chain_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t *widths,
                                             const int32_t *activations);
@@ -412,7 +416,7 @@ ROVER_API int rover_philox4x32(const uint32_t *counter, const uint32_t *key, uin
 /* What rover_mlp_chain_act would launch — host only, no pointer is read but widths / activations and the descriptor's own fields
  * (its pointers are only tested for NULL): "mlp_small+gauss" / "chain16<16,10,8,1>+gauss" when the head is fused into the chain's last
  * kernel, "<rover_mlp_chain_route's name>;gauss" when it is a launch of its own, "none" for M = 0, NULL where the call would be
- * refused with ROVER_E_INVALID (rover_last_error(NULL) says why). */
+ * refused with ROVER_E_INVALID (rover_last_error(NULL) says why).  The pointer is valid until the calling thread's next route query. */
 ROVER_API const char *rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t *widths,
                                                 const int32_t *activations, const rover_gauss_head *head);
 

@@ -577,13 +577,19 @@ class Engine:
 
     ACTIVATIONS = {"none": 0, None: 0, "leakyrelu": 1, "tanh": 2, "relu": 3, "elu": 4}
 
+    @staticmethod
+    def _f32_rows(t, name, what, shape=None):
+        """``t`` must be a float32 GPU matrix with unit column stride (a column slice of a wider row-major tensor will do), of ``shape`` if given."""
+        if t is None or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or (shape is not None and tuple(t.shape) != shape):
+            raise RoverError(f"{what}: {name} must be a float32 GPU matrix{'' if shape is None else ' [%d,%d]' % shape} with unit column stride")
+        return t
+
     def linear_forward(self, x, weight, bias, activation, out):
         """out[:, :N] = act(x[:, :K] @ weight.T + bias); x / out may be column slices of wider row-major tensors."""
         m, k = x.shape
         n = weight.shape[0]
-        for t, name in ((x, "x"), (out, "out")):
-            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
-                raise RoverError(f"linear_forward: {name} must be a float32 GPU matrix with unit column stride")
+        self._f32_rows(x, "x", "linear_forward")
+        self._f32_rows(out, "out", "linear_forward")
         if k > 0:
             self._chk(weight, (n, k), torch.float32, "weight")
         self._chk(bias, (n,), torch.float32, "bias")
@@ -594,57 +600,45 @@ class Engine:
                     "rover_linear_forward")
         return out
 
-    CHAIN_SHAPES = {2: (96, 64), 4: (256, 160, 128, 16)}        # widths the fused chain kernel is built for
-    CHAIN_HIDDEN_ACTS = (None, "none", "leakyrelu", "relu")      # hidden activations the 4-layer chain is built for
+    @staticmethod
+    def chain_shape(layers):
+        """(k0, widths, activations) of ``layers`` (objects with .weight [n, k], .activation): what the chain route queries take."""
+        return layers[0].weight.shape[1], [l.weight.shape[0] for l in layers], [l.activation for l in layers]
 
-    def chain_fits(self, layers):
-        """True if ``layers`` (objects with .weight [n, k]) can run as one rover_mlp_chain_forward launch."""
-        lim = self.CHAIN_SHAPES.get(len(layers))
-        if lim is None or not all(l.weight.shape[0] <= m for l, m in zip(layers, lim)) or layers[0].weight.shape[1] <= 0:
-            return False
-        return len(layers) == 2 or all(l.activation in self.CHAIN_HIDDEN_ACTS for l in layers[:-1])
+    @classmethod
+    def chain_fits(cls, layers):
+        """True if ``layers`` can run as one rover_mlp_chain_forward launch — the library's answer: rover_mlp_chain_route names a kernel.
+        Whether a chain fits does not depend on the number of rows (only which kernel runs it does): asked at one fixed row count."""
+        return len(layers) > 0 and cls.chain_route(1, *cls.chain_shape(layers)) is not None
 
-    def chain_forward(self, x, layers, out):
-        """out = layers[-1](... layers[0](x)) in one kernel; ``layers``: objects with .weight [n, k], .bias [n], .activation."""
+    def _chain(self, what, x, layers, out, keep, out_name="out"):
+        """-> the ChainDesc of ``layers`` (objects with .weight [n, k], .bias [n], .activation) from x [m, k0] to out [m, n_last], all checked
+        (errors under ``what``, the calling method's name).  The arrays it points at go into ``keep``: they live until the call returns."""
         m, k0 = x.shape
-        for t, name in ((x, "x"), (out, "out")):
-            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
-                raise RoverError(f"chain_forward: {name} must be a float32 GPU matrix with unit column stride")
-        n = len(layers)
-        k = k0
-        for l in layers:
-            self._chk(l.weight, (l.weight.shape[0], k), torch.float32, "weight")
-            self._chk(l.bias, (l.weight.shape[0],), torch.float32, "bias")
-            k = l.weight.shape[0]
-        if out.shape[0] != m or out.shape[1] != k:
-            raise RoverError(f"chain_forward: out must be [{m},{k}]")
-        w = (C.c_void_p * n)(*[_ptr(l.weight) for l in layers])
-        b = (C.c_void_p * n)(*[_ptr(l.bias) for l in layers])
-        widths = (C.c_int32 * n)(*[l.weight.shape[0] for l in layers])
-        acts = (C.c_int32 * n)(*[self.ACTIVATIONS[l.activation] for l in layers])
-        self._check(self.lib.rover_mlp_chain_forward(self._h, _ptr(x), x.stride(0), m, k0, n, w, b, widths, acts, _ptr(out), out.stride(0),
-                                                     _stream(self._dev_index)), "rover_mlp_chain_forward")
-        return out
-
-    def _chain_desc(self, x, layers, out, keep):
-        m, k0 = x.shape
-        for t, name in ((x, "x"), (out, "out")):
-            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
-                raise RoverError(f"chain_pair_forward: {name} must be a float32 GPU matrix with unit column stride")
+        self._f32_rows(x, "x", what)
+        self._f32_rows(out, out_name, what)
         n, k = len(layers), k0
         for l in layers:
             self._chk(l.weight, (l.weight.shape[0], k), torch.float32, "weight")
             self._chk(l.bias, (l.weight.shape[0],), torch.float32, "bias")
             k = l.weight.shape[0]
         if out.shape[0] != m or out.shape[1] != k:
-            raise RoverError(f"chain_pair_forward: out must be [{m},{k}]")
+            raise RoverError(f"{what}: {out_name} must be [{m},{k}]")
         w = (C.c_void_p * n)(*[_ptr(l.weight) for l in layers])
         b = (C.c_void_p * n)(*[_ptr(l.bias) for l in layers])
         widths = (C.c_int32 * n)(*[l.weight.shape[0] for l in layers])
         acts = (C.c_int32 * n)(*[self.ACTIVATIONS[l.activation] for l in layers])
-        keep.extend((w, b, widths, acts))                      # the arrays the descriptor points at live until the call returns
+        keep.extend((w, b, widths, acts))
         return ChainDesc(x.data_ptr(), x.stride(0), k0, n, C.addressof(w), C.addressof(b), C.addressof(widths), C.addressof(acts),
                          out.data_ptr(), out.stride(0))
+
+    def chain_forward(self, x, layers, out):
+        """out = layers[-1](... layers[0](x)) in one kernel; ``layers``: objects with .weight [n, k], .bias [n], .activation."""
+        keep = []
+        d = self._chain("chain_forward", x, layers, out, keep)
+        self._check(self.lib.rover_mlp_chain_forward(self._h, d.x, d.x_stride, x.shape[0], d.K0, d.n_layers, d.weights, d.biases, d.widths,
+                                                     d.activations, d.y, d.y_stride, _stream(self._dev_index)), "rover_mlp_chain_forward")
+        return out
 
     def chain_pair_forward(self, xa, layers_a, out_a, xb, layers_b, out_b, copy_src=None, copy_dst=None, copy_cols=0):
         """Two 2-layer chains over the same rows (the two encoders: rover_mlp_chain_pair_forward) and, optionally,
@@ -652,35 +646,29 @@ class Engine:
         if xa.shape[0] != xb.shape[0]:
             raise RoverError("chain_pair_forward: the two chains must have the same number of rows")
         keep = []
-        da, db = self._chain_desc(xa, layers_a, out_a, keep), self._chain_desc(xb, layers_b, out_b, keep)
+        da, db = self._chain("chain_pair_forward", xa, layers_a, out_a, keep), self._chain("chain_pair_forward", xb, layers_b, out_b, keep)
         if copy_cols:
             for t, name in ((copy_src, "copy_src"), (copy_dst, "copy_dst")):
-                if (t is None or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != xa.shape[0]
-                        or t.shape[1] < copy_cols):
-                    raise RoverError(f"chain_pair_forward: {name} must be a float32 GPU matrix of the same rows with >= copy_cols columns")
+                if self._f32_rows(t, name, "chain_pair_forward").shape[0] != xa.shape[0] or t.shape[1] < copy_cols:
+                    raise RoverError(f"chain_pair_forward: {name} must have the same rows and >= copy_cols columns")
         self._check(self.lib.rover_mlp_chain_pair_forward(
             self._h, xa.shape[0], C.byref(da), C.byref(db), _ptr(copy_src) if copy_cols else None, copy_src.stride(0) if copy_cols else 0,
             _ptr(copy_dst) if copy_cols else None, copy_dst.stride(0) if copy_cols else 0, int(copy_cols), _stream(self._dev_index)),
             "rover_mlp_chain_pair_forward")
 
     # ---- the actor's Gaussian head (rover_gauss_head) --------------------------------------------------
-    def _f32_rows(self, t, m, cols, name, what):
-        if t is None or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or tuple(t.shape) != (m, cols):
-            raise RoverError(f"{what}: {name} must be a float32 GPU matrix [{m},{cols}] with unit column stride")
-        return t
-
     def _gauss_head(self, what, m, log_std, actions, log_prob, mean=None, taken_actions=None, step_dev=None, reduction="sum", **kw):
         """-> GaussHead over checked tensors (log_std [A]; actions [m, A]; log_prob [m, 1], or [m, A] with reduction None)."""
         a = int(log_std.numel())
         self._chk(log_std, (a,), torch.float32, "log_std")
         if reduction not in REDUCTIONS:
             raise RoverError(f"{what}: unknown reduction {reduction!r}")
-        self._f32_rows(actions, m, a, "actions", what)
-        self._f32_rows(log_prob, m, a if REDUCTIONS[reduction] == 5 else 1, "log_prob", what)
+        self._f32_rows(actions, "actions", what, (m, a))
+        self._f32_rows(log_prob, "log_prob", what, (m, a if REDUCTIONS[reduction] == 5 else 1))
         if taken_actions is not None:
-            self._f32_rows(taken_actions, m, a, "taken_actions", what)
+            self._f32_rows(taken_actions, "taken_actions", what, (m, a))
         if mean is not None:
-            self._f32_rows(mean, m, a, "mean", what)
+            self._f32_rows(mean, "mean", what, (m, a))
         if step_dev is not None and (not step_dev.is_cuda or step_dev.dtype != torch.int64 or step_dev.numel() != 1):
             raise RoverError(f"{what}: step_dev must be one int64 word on the GPU (read as uint64)")
         dp = lambda t: None if t is None else t.data_ptr()
@@ -693,31 +681,16 @@ class Engine:
         """chain_forward with the Gaussian head on its output (rover_mlp_chain_act): ``mean_out`` receives what chain_forward writes,
         ``actions`` / ``log_prob`` the head's results.  ``head``: taken_actions, step_dev, reduction and the scalar fields of
         gauss_head_desc (seed, step, row_offset, deterministic, clip_*, ...)."""
-        m, k0 = x.shape
-        for t, name in ((x, "x"), (mean_out, "mean_out")):
-            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
-                raise RoverError(f"chain_act: {name} must be a float32 GPU matrix with unit column stride")
-        n = len(layers)
-        k = k0
-        for l in layers:
-            self._chk(l.weight, (l.weight.shape[0], k), torch.float32, "weight")
-            self._chk(l.bias, (l.weight.shape[0],), torch.float32, "bias")
-            k = l.weight.shape[0]
-        if mean_out.shape[0] != m or mean_out.shape[1] != k:
-            raise RoverError(f"chain_act: mean_out must be [{m},{k}]")
-        desc = self._gauss_head("chain_act", m, log_std, actions, log_prob, **head)
-        w = (C.c_void_p * n)(*[_ptr(l.weight) for l in layers])
-        b = (C.c_void_p * n)(*[_ptr(l.bias) for l in layers])
-        widths = (C.c_int32 * n)(*[l.weight.shape[0] for l in layers])
-        acts = (C.c_int32 * n)(*[self.ACTIVATIONS[l.activation] for l in layers])
-        self._check(self.lib.rover_mlp_chain_act(self._h, _ptr(x), x.stride(0), m, k0, n, w, b, widths, acts, _ptr(mean_out), mean_out.stride(0),
-                                                 C.byref(desc), _stream(self._dev_index)), "rover_mlp_chain_act")
+        keep = []
+        d = self._chain("chain_act", x, layers, mean_out, keep, "mean_out")
+        desc = self._gauss_head("chain_act", x.shape[0], log_std, actions, log_prob, **head)
+        self._check(self.lib.rover_mlp_chain_act(self._h, d.x, d.x_stride, x.shape[0], d.K0, d.n_layers, d.weights, d.biases, d.widths, d.activations,
+                                                 d.y, d.y_stride, C.byref(desc), _stream(self._dev_index)), "rover_mlp_chain_act")
         return actions, log_prob
 
     def gaussian_head(self, mean, log_std, actions, log_prob, **head):
         """The head on a given ``mean`` [m, A], A <= 16 (rover_gaussian_head): one launch."""
-        if mean is None or mean.dim() != 2:
-            raise RoverError("gaussian_head: mean must be a float32 GPU matrix")
+        self._f32_rows(mean, "mean", "gaussian_head")
         desc = self._gauss_head("gaussian_head", mean.shape[0], log_std, actions, log_prob, mean=mean, **head)
         self._check(self.lib.rover_gaussian_head(self._h, mean.shape[0], C.byref(desc), _stream(self._dev_index)), "rover_gaussian_head")
         return actions, log_prob
@@ -726,7 +699,7 @@ class Engine:
         """eps [m, a] as the head draws it for (seed, step + *step_dev, row_offset) (rover_policy_noise)."""
         if out is None:
             out = torch.empty(int(m), int(a), device=self.device)
-        self._f32_rows(out, int(m), int(a), "out", "policy_noise")
+        self._f32_rows(out, "out", "policy_noise", (int(m), int(a)))
         self._check(self.lib.rover_policy_noise(self._h, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), _ptr(step_dev), int(row_offset), int(m),
                                                 int(a), _ptr(out), out.stride(0), _stream(self._dev_index)), "rover_policy_noise")
         return out

@@ -1396,19 +1396,32 @@ int rover_linear_forward(rover_ctx* c, const float* x, int64_t x_stride, int32_t
     return ROVER_OK;
 }
 
-// validated ChainArgs of one chain (0 = ok, else the error is recorded)
-static int chain_args_of(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers, const float* const* weights,
-                         const float* const* biases, const int32_t* widths, const int32_t* activations, float* y, int64_t y_stride, ChainArgs* out) {
-    if (!x || !y || !weights || !biases || !widths || !activations || M < 0 || K0 <= 0 || x_stride < K0 || (n_layers != 2 && n_layers != 4))
-        return fail(c, ROVER_E_INVALID, "mlp_chain_forward: bad arguments (M=%d K0=%d layers=%d)", M, K0, n_layers);
-    ChainArgs a{};
-    a.x = x; a.x_stride = x_stride; a.M = M; a.K0 = K0; a.n_layers = n_layers; a.y = y; a.y_stride = y_stride;
-    for (int i = 0; i < n_layers; ++i) {
-        if (!weights[i] || widths[i] <= 0 || widths[i] > 256 || activations[i] < 0 || activations[i] > 4)
-            return fail(c, ROVER_E_INVALID, "mlp_chain_forward: layer %d: width %d activation %d", i, widths[i], activations[i]);
-        a.w[i] = weights[i]; a.b[i] = biases[i]; a.n[i] = widths[i]; a.act[i] = activations[i];
+// One chain, validated in one place.  The shape half: M, K0, the depth, every width and activation — all chain_route() reads, so all a route query looks at (no pointer of
+// the descriptor but widths / activations).  0 = fine, -1 = M / K0 / the depth / a null array, i + 1 = layer i's width or activation.
+static int chain_shape_of(const rover_chain_desc& d, int32_t M, ChainArgs* a) {
+    if (!d.widths || !d.activations || M < 0 || d.K0 <= 0 || (d.n_layers != 2 && d.n_layers != 4)) return -1;
+    *a = ChainArgs{};
+    a->M = M; a->K0 = d.K0; a->n_layers = d.n_layers;
+    for (int i = 0; i < d.n_layers; ++i) {
+        if (d.widths[i] <= 0 || d.widths[i] > 256 || d.activations[i] < 0 || d.activations[i] > 4) return i + 1;
+        a->n[i] = d.widths[i]; a->act[i] = d.activations[i];
     }
-    if (y_stride < a.n[n_layers - 1]) return fail(c, ROVER_E_INVALID, "mlp_chain_forward: y_stride %lld < width %d", (long long)y_stride, a.n[n_layers - 1]);
+    return 0;
+}
+// The whole of it, for a call that launches: the shapes, then the pointers and the row strides (0 = ok, else the error is recorded
+// under `what`, the entry point that was called)
+static int chain_args_of(rover_ctx* c, const rover_chain_desc& d, int32_t M, const char* what, ChainArgs* out) {
+    ChainArgs a;
+    const int bad = chain_shape_of(d, M, &a);
+    if (bad < 0 || !d.x || !d.y || !d.weights || !d.biases || d.x_stride < d.K0)
+        return fail(c, ROVER_E_INVALID, "%s: bad arguments (M=%d K0=%d layers=%d)", what, M, d.K0, d.n_layers);
+    for (int i = 0; i < d.n_layers; ++i) {
+        if (!d.weights[i] || bad == i + 1)
+            return fail(c, ROVER_E_INVALID, "%s: layer %d: width %d activation %d", what, i, d.widths[i], d.activations[i]);
+        a.w[i] = d.weights[i]; a.b[i] = d.biases[i];
+    }
+    if (d.y_stride < a.n[d.n_layers - 1]) return fail(c, ROVER_E_INVALID, "%s: y_stride %lld < width %d", what, (long long)d.y_stride, a.n[d.n_layers - 1]);
+    a.x = d.x; a.x_stride = d.x_stride; a.y = d.y; a.y_stride = d.y_stride;
     *out = a;
     return ROVER_OK;
 }
@@ -1421,8 +1434,8 @@ static int mlp_scratch_reserve(rover_ctx* c, size_t need, hipStream_t s) {
     return ROVER_OK;
 }
 
-static int chain_refused(rover_ctx* c) {
-    return fail(c, ROVER_E_INVALID, "mlp_chain_forward: net outside the built tile shapes (<= 96 -> <= 64, or <= 256 -> <= 160 -> <= 128 -> <= 16 with hidden activations none / LeakyReLU / ReLU)");
+static int chain_refused(rover_ctx* c, const char* what) {
+    return fail(c, ROVER_E_INVALID, "%s: net outside the built tile shapes (<= 96 -> <= 64, or <= 256 -> <= 160 -> <= 128 -> <= 16 with hidden activations none / LeakyReLU / ReLU)", what);
 }
 
 // launches what chain_route() chose (never ChainKernel::None)
@@ -1437,11 +1450,12 @@ int rover_mlp_chain_forward(rover_ctx* c, const float* x, int64_t x_stride, int3
                             const float* const* weights, const float* const* biases, const int32_t* widths, const int32_t* activations,
                             float* y, int64_t y_stride, void* stream) {
     if (!c) return ROVER_E_INVALID;
-    ChainArgs a{};
-    if (int r = chain_args_of(c, x, x_stride, M, K0, n_layers, weights, biases, widths, activations, y, y_stride, &a)) return r;
+    const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
+    ChainArgs a;
+    if (int r = chain_args_of(c, d, M, "mlp_chain_forward", &a)) return r;
     if (M == 0) return ROVER_OK;
     const ChainRoute r = chain_route(a);
-    if (r.kernel == ChainKernel::None) return chain_refused(c);
+    if (r.kernel == ChainKernel::None) return chain_refused(c, "mlp_chain_forward");
     USE_DEVICE(c);
     return chain_run(c, a, r, (hipStream_t)stream);
 }
@@ -1451,12 +1465,12 @@ int rover_mlp_chain_pair_forward(rover_ctx* c, int32_t M, const rover_chain_desc
     if (!c) return ROVER_E_INVALID;
     if (!da || !db || copy_cols < 0 || (copy_cols > 0 && (!copy_src || !copy_dst || copy_src_stride < copy_cols || copy_dst_stride < copy_cols)))
         return fail(c, ROVER_E_INVALID, "mlp_chain_pair_forward: bad arguments (copy_cols=%d)", copy_cols);
-    ChainArgs a{}, b{};
-    if (int r = chain_args_of(c, da->x, da->x_stride, M, da->K0, da->n_layers, da->weights, da->biases, da->widths, da->activations, da->y, da->y_stride, &a)) return r;
-    if (int r = chain_args_of(c, db->x, db->x_stride, M, db->K0, db->n_layers, db->weights, db->biases, db->widths, db->activations, db->y, db->y_stride, &b)) return r;
+    ChainArgs a, b;
+    if (int r = chain_args_of(c, *da, M, "mlp_chain_pair_forward", &a)) return r;
+    if (int r = chain_args_of(c, *db, M, "mlp_chain_pair_forward", &b)) return r;
     if (M == 0) return ROVER_OK;
     const ChainRoute ra = chain_route(a), rb = chain_route(b);
-    if (ra.kernel == ChainKernel::None || rb.kernel == ChainKernel::None) return chain_refused(c);
+    if (ra.kernel == ChainKernel::None || rb.kernel == ChainKernel::None) return chain_refused(c, "mlp_chain_pair_forward");
     USE_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     if (chain_pair_side_by_side(ra, rb)) {
@@ -1480,36 +1494,24 @@ const char* rover_linear_route(int32_t M, int32_t K, int32_t N) {
     return M == 0 ? "none" : linear_route_name(r);
 }
 
-// the part of chain_args_of() that chain_route() reads; false where chain_args_of() refuses the shapes
-static bool chain_shape_of(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations, ChainArgs* a) {
-    if (!widths || !activations || M < 0 || K0 <= 0 || (n_layers != 2 && n_layers != 4)) return false;
-    *a = ChainArgs{};
-    a->M = M; a->K0 = K0; a->n_layers = n_layers;
-    for (int i = 0; i < n_layers; ++i) {
-        if (widths[i] <= 0 || widths[i] > 256 || activations[i] < 0 || activations[i] > 4) return false;
-        a->n[i] = widths[i]; a->act[i] = activations[i];
-    }
-    return true;
-}
-
 const char* rover_mlp_chain_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations) {
+    const rover_chain_desc d{nullptr, 0, K0, n_layers, nullptr, nullptr, widths, activations, nullptr, 0};      // a route query: shapes alone
     ChainArgs a;
-    if (!chain_shape_of(M, K0, n_layers, widths, activations, &a)) return nullptr;
+    if (chain_shape_of(d, M, &a)) return nullptr;
     return M == 0 ? "none" : chain_route_name(chain_route(a));
 }
 
 const char* rover_mlp_chain_pair_route(int32_t M, const rover_chain_desc* da, const rover_chain_desc* db) {
     ChainArgs a, b;
-    if (!da || !db || !chain_shape_of(M, da->K0, da->n_layers, da->widths, da->activations, &a) ||
-        !chain_shape_of(M, db->K0, db->n_layers, db->widths, db->activations, &b))
-        return nullptr;
+    if (!da || !db || chain_shape_of(*da, M, &a) || chain_shape_of(*db, M, &b)) return nullptr;
     if (M == 0) return "none";
     const ChainRoute ra = chain_route(a), rb = chain_route(b);
-    const char *na = chain_route_name(ra), *nb = chain_route_name(rb);
-    if (!na || !nb) return nullptr;
-    static thread_local char name[64];
+    if (ra.kernel == ChainKernel::None || rb.kernel == ChainKernel::None) return nullptr;
+    static thread_local char name[96];
+    char na[48];                                                     // (chain_route_name() may hand out one buffer twice)
+    snprintf(na, sizeof na, "%s", chain_route_name(ra));
     if (chain_pair_side_by_side(ra, rb)) snprintf(name, sizeof name, "pair(%s)", na);
-    else snprintf(name, sizeof name, "seq(%s;%s)", na, nb);
+    else snprintf(name, sizeof name, "seq(%s;%s)", na, chain_route_name(rb));
     return name;
 }
 
@@ -1544,14 +1546,14 @@ int rover_mlp_chain_act(rover_ctx* c, const float* x, int64_t x_stride, int32_t 
                         const float* const* biases, const int32_t* widths, const int32_t* activations, float* y, int64_t y_stride,
                         const rover_gauss_head* head, void* stream) {
     if (!c) return ROVER_E_INVALID;
-    ChainArgs a{};
-    GaussHead h{};
-    if (int r = chain_args_of(c, x, x_stride, M, K0, n_layers, weights, biases, widths, activations, y, y_stride, &a)) return r;
+    const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
+    ChainArgs a; GaussHead h{};
+    if (int r = chain_args_of(c, d, M, "mlp_chain_act", &a)) return r;
     if (int r = gauss_head_of(c, head, M, false, &h)) return r;
     if (a.n[n_layers - 1] != h.A) return fail(c, ROVER_E_INVALID, "mlp_chain_act: the last layer is %d wide, the head has A = %d", a.n[n_layers - 1], h.A);
     if (M == 0) return ROVER_OK;
     const ChainRoute r = chain_route(a);
-    if (r.kernel == ChainKernel::None) return chain_refused(c);
+    if (r.kernel == ChainKernel::None) return chain_refused(c, "mlp_chain_act");
     USE_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     if (chain_head_fused(r, h.A)) {
@@ -1594,9 +1596,9 @@ int rover_philox4x32(const uint32_t* counter, const uint32_t* key, uint32_t* out
 
 const char* rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations,
                                       const rover_gauss_head* head) {
-    ChainArgs a;
-    GaussHead h{};
-    if (!chain_shape_of(M, K0, n_layers, widths, activations, &a)) {
+    const rover_chain_desc d{nullptr, 0, K0, n_layers, nullptr, nullptr, widths, activations, nullptr, 0};
+    ChainArgs a; GaussHead h{};
+    if (chain_shape_of(d, M, &a)) {
         fail(nullptr, ROVER_E_INVALID, "mlp_chain_act_route: bad shapes (M=%d K0=%d layers=%d)", M, K0, n_layers);
         return nullptr;
     }

@@ -218,7 +218,9 @@ struct ChainArgs {
 enum class ChainKernel { None, SplitK, MlpSmall, Chain16_5, Chain16_6, Chain16Long };
 struct ChainRoute { ChainKernel kernel; int tn, rt; };
 ChainRoute chain_route(const ChainArgs& a);
-const char* chain_route_name(const ChainRoute& r);        // "splitk<6,2>", "chain16<16,10,8,1>", ..., or NULL
+// "splitk<6,2>", "chain16<16,10,8,1>", ..., or NULL.  This and chain_act_route_name() read one table (rover_mlp.hip: kChainKernels) and
+// compose the name in one buffer per thread: valid until the calling thread's next call of either
+const char* chain_route_name(const ChainRoute& r);
 // split-k: scratch holds chain_splitk_scratch_floats() floats
 size_t chain_splitk_scratch_floats(int M, int K0, int n0);
 hipError_t launch_chain(const ChainArgs& a, const ChainRoute& r, float* split_k_scratch, hipStream_t s);

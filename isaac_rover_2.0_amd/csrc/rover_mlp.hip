@@ -12,6 +12,7 @@
 // current one is multiplied; each wave keeps N/32 accumulator tiles.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include "rover_internal.h"
 #include "rover_philox.h"
 
@@ -685,13 +686,12 @@ static void launch_splitk_tn(const SplitkL1Pair& l, const SplitkFinPair& f, int 
     else hipLaunchKernelGGL((splitk_layer1_kernel<TN, 1>), g1, dim3(64), 0, s, l);
     hipLaunchKernelGGL((splitk_finish_kernel<TN>), g2, dim3(256), 0, s, f);
 }
-static hipError_t launch_chain_splitk(const ChainArgs& a, const ChainRoute& r, float* scratch, hipStream_t s) {
+static void launch_chain_splitk(const ChainArgs& a, const ChainRoute& r, float* scratch, dim3, hipStream_t s) {
     SplitkL1Pair l{}; SplitkFinPair f{};
     l.M = f.M = a.M;
     l.c[0] = splitk_l1_of(a, scratch);
     f.c[0] = splitk_fin_of(a, l.c[0]);
     if (r.tn == 5) launch_splitk_tn<5>(l, f, 1, r.rt, s); else launch_splitk_tn<6>(l, f, 1, r.rt, s);
-    return hipGetLastError();
 }
 // two chains over the same rows side by side (both split-k with the same tile shape); scratch_b follows chain a's part of the scratch buffer
 bool chain_pair_side_by_side(const ChainRoute& ra, const ChainRoute& rb) {
@@ -798,16 +798,32 @@ ChainRoute chain_route(const ChainArgs& a) {
     return r;
 }
 
+// ---- the one table over ChainKernel: what a route is called, what it launches, which launch carries the Gaussian head ----
+template <auto Kernel> static void chain_plain(const ChainArgs& a, const ChainRoute&, float*, dim3 grid, hipStream_t s) { hipLaunchKernelGGL(Kernel, grid, dim3(512), 0, s, a); }
+template <auto Kernel> static void chain_with_head(const ChainArgs& a, const GaussHead& h, dim3 grid, hipStream_t s) { hipLaunchKernelGGL(Kernel, grid, dim3(512), 0, s, a, h); }
+struct ChainKernelRow {
+    ChainKernel kernel; const char* name;                            // (SplitK's name: completed with <tn,rt>)
+    void (*plain)(const ChainArgs&, const ChainRoute&, float* scratch, dim3 grid, hipStream_t);
+    void (*head)(const ChainArgs&, const GaussHead&, dim3 grid, hipStream_t);      // the same chain with the head on its last tile, or null
+    int rows;                                                        // rows per workgroup: grid = ceil(M / rows) (split-k sizes its own two grids)
+};
+static const ChainKernelRow kChainKernels[] = {
+    {ChainKernel::SplitK, "splitk", launch_chain_splitk, nullptr, 16},
+    {ChainKernel::MlpSmall, "mlp_small", chain_plain<mlp_small_kernel>, chain_with_head<mlp_small_head_kernel>, 16},
+    {ChainKernel::Chain16_5, "chain16<5,4,0,0>", chain_plain<chain16_kernel<5, 4, 0, 0>>, nullptr, 128},
+    {ChainKernel::Chain16_6, "chain16<6,4,0,0>", chain_plain<chain16_kernel<6, 4, 0, 0>>, nullptr, 128},
+    {ChainKernel::Chain16Long, "chain16<16,10,8,1>", chain_plain<chain16_kernel<16, 10, 8, 1>>, chain_with_head<chain16_head_kernel<16, 10, 8, 1>>, 128},
+};
+static const ChainKernelRow* chain_kernel_row(const ChainRoute& r) {        // null: ChainKernel::None
+    for (const ChainKernelRow& k : kChainKernels) if (k.kernel == r.kernel) return &k;
+    return nullptr;
+}
+static dim3 chain_grid(const ChainKernelRow& k, const ChainArgs& a) { return dim3((uint32_t)((a.M + k.rows - 1) / k.rows)); }
+
 hipError_t launch_chain(const ChainArgs& a, const ChainRoute& r, float* scratch, hipStream_t s) {
-    const dim3 grid((uint32_t)((a.M + 127) / 128));
-    switch (r.kernel) {
-        case ChainKernel::SplitK: return launch_chain_splitk(a, r, scratch, s);
-        case ChainKernel::MlpSmall: hipLaunchKernelGGL(mlp_small_kernel, dim3((uint32_t)((a.M + 15) / 16)), dim3(512), 0, s, a); break;
-        case ChainKernel::Chain16_5: hipLaunchKernelGGL((chain16_kernel<5, 4, 0, 0>), grid, dim3(512), 0, s, a); break;
-        case ChainKernel::Chain16_6: hipLaunchKernelGGL((chain16_kernel<6, 4, 0, 0>), grid, dim3(512), 0, s, a); break;
-        case ChainKernel::Chain16Long: hipLaunchKernelGGL((chain16_kernel<16, 10, 8, 1>), grid, dim3(512), 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
+    const ChainKernelRow* k = chain_kernel_row(r);
+    if (!k) return hipErrorInvalidValue;
+    k->plain(a, r, scratch, chain_grid(*k, a), s);
     return hipGetLastError();
 }
 
@@ -815,12 +831,13 @@ hipError_t launch_chain(const ChainArgs& a, const ChainRoute& r, float* scratch,
 // Fused where the whole head of a row sits in one lane of the chain's last tile (A <= 4) on the two kernels that end the actor's
 // forward; every other chain runs its forward, then gaussian_head_kernel on the stored mean.
 bool chain_head_fused(const ChainRoute& r, int A) {
-    return A >= 1 && A <= 4 && (r.kernel == ChainKernel::MlpSmall || r.kernel == ChainKernel::Chain16Long);
+    const ChainKernelRow* k = chain_kernel_row(r);
+    return A >= 1 && A <= 4 && k && k->head;
 }
 hipError_t launch_chain_head(const ChainArgs& a, const ChainRoute& r, const GaussHead& h, hipStream_t s) {
     if (!chain_head_fused(r, h.A) || a.n[a.n_layers - 1] != h.A) return hipErrorInvalidValue;
-    if (r.kernel == ChainKernel::MlpSmall) hipLaunchKernelGGL(mlp_small_head_kernel, dim3((uint32_t)((a.M + 15) / 16)), dim3(512), 0, s, a, h);
-    else hipLaunchKernelGGL((chain16_head_kernel<16, 10, 8, 1>), dim3((uint32_t)((a.M + 127) / 128)), dim3(512), 0, s, a, h);
+    const ChainKernelRow* k = chain_kernel_row(r);
+    k->head(a, h, chain_grid(*k, a), s);
     return hipGetLastError();
 }
 hipError_t launch_gaussian_head(const float* mean, int64_t mean_stride, int M, const GaussHead& h, hipStream_t s) {
@@ -833,19 +850,6 @@ hipError_t launch_policy_noise(uint64_t seed, uint64_t step, const uint64_t* ste
     hipLaunchKernelGGL(policy_noise_kernel, dim3(blocks_for((uint64_t)M, 256u)), dim3(256), 0, s, seed, step, step_dev, row_offset, M, A, eps, eps_stride);
     return hipGetLastError();
 }
-const char* chain_act_route_name(const ChainRoute& r, int A) {
-    if (A < 1 || A > GAUSS_MAX_A) return nullptr;
-    const bool fused = chain_head_fused(r, A);
-    switch (r.kernel) {
-        case ChainKernel::SplitK: return r.tn == 5 ? (r.rt == 2 ? "splitk<5,2>;gauss" : "splitk<5,1>;gauss") : (r.rt == 2 ? "splitk<6,2>;gauss" : "splitk<6,1>;gauss");
-        case ChainKernel::MlpSmall: return fused ? "mlp_small+gauss" : "mlp_small;gauss";
-        case ChainKernel::Chain16_5: return "chain16<5,4,0,0>;gauss";
-        case ChainKernel::Chain16_6: return "chain16<6,4,0,0>;gauss";
-        case ChainKernel::Chain16Long: return fused ? "chain16<16,10,8,1>+gauss" : "chain16<16,10,8,1>;gauss";
-        default: return nullptr;
-    }
-}
-
 // the instantiation a route launches, by name (rover_linear_route / rover_mlp_chain_route)
 const char* linear_route_name(const LinearRoute& r) {
     static const char* const wide[2][5] = {{"linear_act<1,4>", "linear_act<2,4>", "linear_act<3,4>", "linear_act<4,4>", "linear_act<5,4>"},
@@ -854,15 +858,18 @@ const char* linear_route_name(const LinearRoute& r) {
     if (r.nw == 4 && r.nt >= 1 && r.nt <= 5 && (r.ny == 1 || r.ny == 2)) return wide[r.ny - 1][r.nt - 1];
     return nullptr;
 }
-const char* chain_route_name(const ChainRoute& r) {
-    switch (r.kernel) {
-        case ChainKernel::SplitK: return r.tn == 5 ? (r.rt == 2 ? "splitk<5,2>" : "splitk<5,1>") : (r.rt == 2 ? "splitk<6,2>" : "splitk<6,1>");
-        case ChainKernel::MlpSmall: return "mlp_small";
-        case ChainKernel::Chain16_5: return "chain16<5,4,0,0>";
-        case ChainKernel::Chain16_6: return "chain16<6,4,0,0>";
-        case ChainKernel::Chain16Long: return "chain16<16,10,8,1>";
-        default: return nullptr;
-    }
+// the table's name, completed ("splitk<TN,RT>", the head's suffix) in a buffer of the calling thread: valid until its next call
+static const char* chain_name(const ChainRoute& r, const char* suffix) {
+    const ChainKernelRow* k = chain_kernel_row(r);
+    if (!k) return nullptr;
+    static thread_local char buf[48];
+    if (k->kernel == ChainKernel::SplitK) snprintf(buf, sizeof buf, "%s<%d,%d>%s", k->name, r.tn, r.rt, suffix);
+    else snprintf(buf, sizeof buf, "%s%s", k->name, suffix);
+    return buf;
+}
+const char* chain_route_name(const ChainRoute& r) { return chain_name(r, ""); }
+const char* chain_act_route_name(const ChainRoute& r, int A) {
+    return A < 1 || A > GAUSS_MAX_A ? nullptr : chain_name(r, chain_head_fused(r, A) ? "+gauss" : ";gauss");
 }
 
 }  // namespace rover

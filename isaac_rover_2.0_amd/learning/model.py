@@ -12,17 +12,22 @@ log-probability of actions taken earlier — inside the kernel that ends the for
 noise keyed by (seed, call counter, GLOBAL row), so a shard draws its slice of the whole batch's noise.  The critic's ``act()`` is
 ``DeterministicMixin``'s (:198-201).
 
-Large batches run each encoder and the MLP + head as ONE fused kernel each (``rover_mlp_chain_forward``, f32 MFMA, activations
-kept in registers between the layers); otherwise every ``Layer`` is one ``rover_linear_forward`` launch.  The slices are read in
-place from ``obs_buf`` and the encoder outputs are written straight into the concat buffer, so there is no ``torch.cat``.  Training (skrl PPO,
+Nets that fit the library's chain kernels run each encoder and the MLP + head as ONE fused kernel each (``rover_mlp_chain_forward``,
+f32 MFMA, activations kept in registers between the layers); otherwise every ``Layer`` is one ``rover_linear_forward`` launch.  Which
+it is, the library says (``HeightmapNet._plan``); this file holds no width or row limit.  The slices are read in place from ``obs_buf``
+and the encoder outputs are written straight into the concat buffer, so there is no ``torch.cat``.  Training (skrl PPO,
 ``train.py``) stays out of scope: these classes hold plain tensors, initialised like ``nn.Linear``, and can load a
 ``state_dict`` saved from the reference's modules (same parameter names).
 """
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 
 import torch
+
+# how a forward runs: both encoders through chain_pair_forward; else each encoder, and the MLP + head, as a chain kernel or layer by layer
+ForwardPlan = namedtuple("ForwardPlan", "pair enc0 enc1 mlp")
 
 
 class Layer:
@@ -67,7 +72,7 @@ class HeightmapNet:
         self.network.append(mk(i, num_outputs, head_activation))                          # :181-182 / :226
         # :183 — only the stochastic actor owns a log-std parameter (DeterministicHeightmap has none, :197-241)
         self.log_std_parameter = torch.zeros(num_outputs, device=device) if head_activation == "tanh" else None
-        self._bufs = {}
+        self._bufs, self._plans = {}, {}
         # act()'s call counter, in device memory so that a captured graph draws fresh noise on every replay: read by the head's kernel,
         # advanced by act() on the same stream right after it (eager and captured alike)
         self._act_counter = torch.zeros(1, dtype=torch.int64, device=device)
@@ -79,11 +84,24 @@ class HeightmapNet:
             b = self._bufs[key] = torch.empty(rows, cols, device=self.device)
         return b
 
+    def _plan(self, rows, fused):
+        """The ForwardPlan of a batch of ``rows`` rows, asked of the library's route queries once and kept like the buffers: a chain is one
+        kernel where rover_mlp_chain_route names one; the encoders take chain_pair_forward at the batch sizes where the library runs two
+        encoders of these widths side by side ("pair(...)", rover_step.h).  That is asked with inputs long enough to split along k: at
+        those batch sizes shorter slices take the same call, which then runs them one after the other and copies the columns itself."""
+        plan = self._plans.get((rows, fused))
+        if plan is None:
+            eng = self.engine
+            chain = lambda layers: bool(fused and eng.chain_route(rows, *eng.chain_shape(layers)) is not None)
+            long_enc = [(1 << 20,) + eng.chain_shape(enc)[1:] for enc in (self.encoder0, self.encoder1)]       # (k0, widths, activations)
+            pair = bool(fused and self.num_sparse > 0 and self.num_dense > 0 and (eng.chain_pair_route(rows, *long_enc) or "").startswith("pair("))
+            plan = self._plans[(rows, fused)] = ForwardPlan(pair, chain(self.encoder0), chain(self.encoder1), chain(self.network))
+        return plan
+
     def compute(self, states, fused=None):
         """model.py:185-195 / :231-241.  ``states`` [E, num_observations] float32 (may be the task's obs_buf itself).
-        ``fused``: run each encoder and the MLP + head as ONE kernel each (``rover_mlp_chain_forward``: activations stay in
-        registers) — default for batches of >= 20 480 rows when the layer widths fit the built tile shapes; otherwise one
-        ``rover_linear_forward`` launch per layer."""
+        ``fused`` (default): each encoder and the MLP + head run as ONE kernel each (``rover_mlp_chain_forward``: activations stay in
+        registers) when the library has a chain kernel for their widths; ``fused=False``: one ``rover_linear_forward`` launch per layer."""
         cat, mlp_fused = self._encode(states, fused)
         if mlp_fused:
             e = states.shape[0]
@@ -99,29 +117,27 @@ class HeightmapNet:
     def _encode(self, states, fused):
         """Both encoders and the proprioception columns into the concat buffer -> (cat, whether the MLP + head runs as one chain kernel)."""
         e = states.shape[0]
+        plan = self._plan(e, fused is None or bool(fused))
         p, ns, nd = self.num_proprioception, self.num_sparse, self.num_dense
         ef = self.encoder0[-1].weight.shape[0]
         cat = self._buf("cat", e, p + 2 * ef)
-        if fused is None:
-            fused = True          # encoders: one fused kernel from 20 480 rows, a split-k pair below (the library decides); MLP + head: one kernel
-        if (fused and ns > 0 and nd > 0 and e < 20480 and len(self.encoder0) == 2 and len(self.encoder1) == 2
-                and self.engine.chain_fits(self.encoder0) and self.engine.chain_fits(self.encoder1)):
+        if plan.pair:
             # small batches: both encoders and the proprioception copy side by side, then the MLP + head: 3 launches instead of 6
             self.engine.chain_pair_forward(states[:, p:p + ns], self.encoder0, cat[:, p:p + ef],
                                            states[:, p + ns:p + ns + nd], self.encoder1, cat[:, p + ef:p + 2 * ef],
                                            copy_src=states, copy_dst=cat, copy_cols=p)
-            return cat, self.engine.chain_fits(self.network)
+            return cat, plan.mlp
         cat[:, 0:p] = states[:, 0:p]
-        for enc, lo, n, col in ((self.encoder0, p, ns, p), (self.encoder1, p + ns, nd, p + ef)):
+        for enc, as_chain, lo, n, col in ((self.encoder0, plan.enc0, p, ns, p), (self.encoder1, plan.enc1, p + ns, nd, p + ef)):
             x = states[:, lo:lo + n]
-            if fused and n > 0 and self.engine.chain_fits(enc):
+            if as_chain:
                 self.engine.chain_forward(x, enc, cat[:, col:col + ef])
                 continue
             for li, layer in enumerate(enc):
                 last = li == len(enc) - 1
                 out = cat[:, col:col + ef] if last else self._buf(("enc", col, li), e, layer.weight.shape[0])
                 x = self.engine.linear_forward(x, layer.weight, layer.bias, layer.activation, out)
-        return cat, bool(fused and self.engine.chain_fits(self.network))
+        return cat, plan.mlp
 
     # ---- skrl's mixins: GaussianMixin.act (actor), DeterministicMixin.act (critic) --------------------------------
     def act(self, states, taken_actions=None, deterministic=False, step=None, role="", fused=None):
