@@ -8,6 +8,11 @@ the skrl PPO agent, either a random policy (`--policy random`, the default) or t
 from the reference's module).
 
     python examples/rollout.py --envs 4096 --steps 200 [--assets /path/to/omniisaacgymenvs] [--policy actor [--checkpoint actor.pt]]
+
+`--rollouts N` (with `--policy actor`) adds what skrl's PPO does around that loop up to the weight update: a `DeterministicHeightmap` critic,
+a `RolloutMemory` of N steps (train.py:82, `rollouts: 60` in cfg/trainSKRL/RoverPPOSKRL.yaml:12) that stores states, actions, log_prob,
+values, rewards and terminated every step, and every N steps `compute_gae` (one pass on the GPU) with the critic's value of the current
+obs as `last_values`.
 """
 import argparse
 import os
@@ -29,7 +34,10 @@ def main():
     ap.add_argument("--native-rays", action="store_true", help="the reference's 1634-point distribution (1750-float obs)")
     ap.add_argument("--policy", choices=("random", "actor"), default="random", help="random actions, or StochasticActorHeightmap.act(obs)")
     ap.add_argument("--checkpoint", default="", help="--policy actor: a state_dict of the reference's StochasticActorHeightmap (torch.save)")
+    ap.add_argument("--rollouts", type=int, default=0, help="--policy actor: store N steps in a RolloutMemory, then compute_gae (0 = off)")
     args = ap.parse_args()
+    if args.rollouts < 0 or (args.rollouts and args.policy != "actor"):
+        ap.error("--rollouts N needs N >= 0 and --policy actor")
 
     scene = assets.load_reference_assets(args.assets) if args.assets else synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
     cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
@@ -52,6 +60,16 @@ def main():
             agent.load_state_dict(sd.get("policy", sd) if isinstance(sd, dict) else sd)
         print(f"policy: StochasticActorHeightmap, {sum(v.numel() for v in agent.state_dict().values()):,} parameters"
               f"{' from ' + args.checkpoint if args.checkpoint else ' (fresh initialisation)'}")
+    critic = memory = None
+    if args.rollouts:
+        from isaac_rover_amd.learning.model import DeterministicHeightmap
+        from isaac_rover_amd.learning.rollout import RolloutMemory, compute_gae
+        critic = DeterministicHeightmap(task._engine, task, seed=1)
+        memory = RolloutMemory(args.rollouts, args.envs, device=task.device, report=print)
+        for name, size, dtype in (("states", obs.shape[1], torch.float32), ("actions", task.num_actions, torch.float32), ("log_prob", 1, torch.float32),
+                                  ("values", 1, torch.float32), ("rewards", 1, torch.float32), ("terminated", 1, torch.bool),
+                                  ("returns", 1, torch.float32), ("advantages", 1, torch.float32)):
+            memory.create_tensor(name, size, dtype)
     ret = torch.zeros(args.envs, device=task.device)
     episodes = 0
     torch.cuda.synchronize()
@@ -61,7 +79,18 @@ def main():
             actions = 2 * torch.rand(args.envs, 2, device=task.device) - 1
         else:
             actions, log_prob, outputs = agent.act(obs)                            # what a PPO rollout stores next to obs and rew
+        if memory is not None:
+            values, _, _ = critic.act(obs)
+            states = obs.clone()                                                   # env.step() rewrites the observation buffer
         obs, rew, done, info = env.step(actions)
+        if memory is not None:
+            memory.add_samples(states=states, actions=actions, log_prob=log_prob, values=values, rewards=rew, terminated=done.bool())
+            if memory.memory_index == 0:                                           # full: returns and advantages of these N steps
+                last_values, _, _ = critic.act(obs)
+                returns, adv = compute_gae(task._engine, memory, last_values)
+                print(f"rollout of {args.rollouts} steps: mean return {float(returns.mean()):.4f}, advantages mean {float(adv.mean()):+.2e} "
+                      f"std {float(adv.std()):.4f}")
+                memory.reset()
         ret += rew
         episodes += int(done.sum())                                             # host sync, like a logger would do
     torch.cuda.synchronize()

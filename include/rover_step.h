@@ -420,6 +420,55 @@ ROVER_API int rover_philox4x32(const uint32_t *counter, const uint32_t *key, uin
 ROVER_API const char *rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t *widths,
                                                 const int32_t *activations, const rover_gauss_head *head);
 
+/* ---- the rollout side of PPO: returns and advantages of a stored rollout in one pass (skrl's compute_gae inside PPO._update) -------- */
+/* The reference trains through skrl: RandomMemory(memory_size=60) (train.py:82), rollouts 60, discount_factor 0.99, lambda 0.95
+ * (cfg/trainSKRL/RoverPPOSKRL.yaml:12-16).  skrl is no part of this repository: the semantics are restated from a reading of skrl
+ * 0.10 / 1.x, not verified against an installed copy, and are this project's definition.  With rewards, values [T, E] f32, dones [T, E]
+ * u8 (a torch.bool's storage, non-zero = done), last_values [E]:
+ *   adv = 0 per env;  for t = T-1 .. 0:  nv = values[t+1] (t = T-1: last_values)
+ *       adv = rewards[t] - values[t] + gamma (dones[t] ? 0 : 1) (nv + lam adv);  A[t] = adv
+ *   returns = A + values;   advantages = (A - mean(A)) / (std(A) + 1e-8), mean and UNBIASED std over all T E elements
+ * NaN and Inf get no special handling: they propagate as the formula says (a done flag multiplies by 0).  Time-limit bootstrapping
+ * (rewards += gamma values truncated at record time) is the caller's one elementwise line, not part of the kernel.
+ * Every [T, E] array is (device pointer, TIME stride in elements >= E); the env stride is 1, so skrl-shaped [T, E, 1] tensors and
+ * padded buffers are read and written in place.  returns may alias values (same pointer and stride); advantages aliases nothing the
+ * call reads.
+ * normalize: ROVER_GAE_RAW — advantages = A; ROVER_GAE_NORMALIZE — normalised with this call's own moments (needs T E >= 2: the
+ * unbiased std of one element is NaN, which the call refuses rather than emits); ROVER_GAE_NORMALIZE_GIVEN — normalised with stats_in.
+ * stats_out (optional, device double[3]) receives (count, mean, M2 = sum of squared deviations) of this call's RAW A in every mode;
+ * stats_in (device double[3], ROVER_GAE_NORMALIZE_GIVEN only) is read by the kernel when it runs.  That is how shards normalise with
+ * the global moments: each rank runs RAW + stats_out, the triples are combined (rover_combine_moments, or the same expression on
+ * device tensors) and every rank runs NORMALIZE_GIVEN with the result.
+ * returns[:, e] and the raw A[:, e] depend on env e's column alone — not on E, nor on how the envs are cut into shards: two
+ * half-shards reproduce the whole bit for bit.  The moments are f64, merged from per-block partials in a fixed order with Chan's
+ * formula: no floating-point atomics, the same inputs give the same bits on every run.
+ * The call allocates nothing and does not synchronise (the partials' buffer belongs to the ctx since rover_create): it can be captured
+ * in a graph.  Calls of one ctx run on ONE stream at a time.  Launches: one (RAW or NORMALIZE_GIVEN without stats_out), else two (the
+ * scan, then the kernel that merges the partials, writes stats_out and normalises); none for E = 0 (ROVER_OK).
+ * ROVER_E_INVALID before any launch: a NULL required pointer, a stride < E or > 2^40, T outside 1 .. 4096, E < 0, T E >= 2^31, an unknown
+ * normalize, NORMALIZE with T E < 2, returns overlapping values other than as the same array, advantages overlapping any other array, stats_out / stats_in
+ * overlapping an array or each other. */
+#define ROVER_GAE_RAW             0
+#define ROVER_GAE_NORMALIZE       1
+#define ROVER_GAE_NORMALIZE_GIVEN 2
+typedef struct {
+    int32_t T, E;                 /* 1 <= T <= 4096 time steps, E >= 0 envs, T E < 2^31                                         */
+    float gamma, lam;             /* discount_factor, lambda                                                                    */
+    const float *rewards;   int64_t rewards_stride;
+    const float *values;    int64_t values_stride;
+    const uint8_t *dones;   int64_t dones_stride;
+    const float *last_values;     /* [E] the critic's value of the state after the last stored step                             */
+    float *returns;         int64_t returns_stride;
+    float *advantages;      int64_t advantages_stride;
+    int32_t normalize;            /* ROVER_GAE_*                                                                                */
+    double *stats_out;            /* optional device [3]                                                                        */
+    const double *stats_in;       /* device [3], required with ROVER_GAE_NORMALIZE_GIVEN                                        */
+} rover_gae_desc;
+ROVER_API int rover_gae(rover_ctx *ctx, const rover_gae_desc *d, void *stream);
+/* Host only (no ctx, no device): out[3] = the moments (count, mean, M2) of the union of two disjoint samples with moments a[3], b[3] —
+ * Chan, Golub & LeVeque's pairwise update, the one the kernels run.  An empty side (count 0) leaves the other unchanged; out may be a or b. */
+ROVER_API int rover_combine_moments(const double *a, const double *b, double *out);
+
 /* ---- tuning knobs ------------------------------------------------------------------------------------- */
 /* name = "raycast_variant": 0 = auto; 1 = one half-wave per ray in env order, every cell block streamed from HBM;
  *        2 = rays counting-sorted by (map, cell), one wave per run of sorted rays, the cell's triangles held in registers

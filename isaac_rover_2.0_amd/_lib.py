@@ -93,6 +93,15 @@ class GaussHead(C.Structure):
                 ("log_prob", C.c_void_p), ("log_prob_stride", C.c_int64), ("mean", C.c_void_p), ("mean_stride", C.c_int64)]
 
 
+class GaeDesc(C.Structure):
+    _fields_ = [("T", C.c_int32), ("E", C.c_int32), ("gamma", C.c_float), ("lam", C.c_float), ("rewards", C.c_void_p), ("rewards_stride", C.c_int64),
+                ("values", C.c_void_p), ("values_stride", C.c_int64), ("dones", C.c_void_p), ("dones_stride", C.c_int64), ("last_values", C.c_void_p),
+                ("returns", C.c_void_p), ("returns_stride", C.c_int64), ("advantages", C.c_void_p), ("advantages_stride", C.c_int64),
+                ("normalize", C.c_int32), ("stats_out", C.c_void_p), ("stats_in", C.c_void_p)]
+
+
+GAE_RAW, GAE_NORMALIZE, GAE_NORMALIZE_GIVEN = 0, 1, 2
+
 REDUCTIONS = {"sum": 0, "mean": 1, "prod": 2, "max": 3, "min": 4, None: 5, "none": 5}
 
 
@@ -157,6 +166,8 @@ SYMBOLS = {
     "rover_policy_noise": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "rover_philox4x32": (C.c_int, [_P, _P, _P]),
     "rover_mlp_chain_act_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(GaussHead)]),
+    "rover_gae": (C.c_int, [_P, C.POINTER(GaeDesc), _P]),
+    "rover_combine_moments": (C.c_int, [_P, _P, _P]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
     "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
     "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -247,6 +258,30 @@ def philox4x32(counter, key):
     if rc != 0:
         raise RoverError(f"rover_philox4x32 failed ({rc}): {lib.rover_last_error(None).decode()}")
     return tuple(int(v) for v in out)
+
+
+def combine_moments(a, b):
+    """The moments (count, mean, M2) of the union of two disjoint samples from their moments ``a`` and ``b`` (Chan's pairwise update: what
+    shards do with the ``stats_out`` of their Engine.gae calls before they hand the result back as ``stats_in``).  Two float64 torch
+    tensors of 3 elements: the same IEEE operations in the same order on their device (the same bits as the host helper), nothing
+    synchronises; an empty side (count 0) leaves the other unchanged, as on the host.  Anything else (sequences, numpy arrays):
+    rover_combine_moments on the host -> a float64 numpy array of 3."""
+    if isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor):
+        if a.dtype != torch.float64 or b.dtype != torch.float64 or a.numel() != 3 or b.numel() != 3:
+            raise RoverError("combine_moments: expected two float64 tensors of 3 elements (count, mean, M2)")
+        a, b = a.reshape(3), b.reshape(3)
+        n = a[0] + b[0]
+        d, f = b[1] - a[1], b[0] / n
+        merged = torch.stack((n, a[1] + d * f, a[2] + b[2] + d * d * (a[0] * f)))
+        return torch.where(a[0] == 0, b, torch.where(b[0] == 0, a, merged))
+    ha, hb, out = _host(a, np.float64).reshape(-1), _host(b, np.float64).reshape(-1), np.empty(3, dtype=np.float64)
+    if ha.shape != (3,) or hb.shape != (3,):
+        raise RoverError("combine_moments: expected two triples (count, mean, M2)")
+    lib = load()
+    rc = lib.rover_combine_moments(ha.ctypes.data, hb.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RoverError(f"rover_combine_moments failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return out
 
 
 _FAKE = 16          # a non-null address for the descriptor of a route query (never read)
@@ -705,6 +740,48 @@ class Engine:
         return out
 
     chain_act_route = staticmethod(chain_act_route)
+
+    # ---- the rollout side of PPO (rover_gae) -------------------------------------------------------------
+    def _gae_rows(self, t, name, dtype, T=None, E=None):
+        """``t`` must be a [T, E] or skrl-shaped [T, E, 1] GPU tensor of ``dtype`` with unit env stride (a padded buffer's view will do)
+        -> (pointer, time stride in elements, T, E)."""
+        ok = t is not None and t.is_cuda and t.device == self.device and t.dtype == dtype and (t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 1))
+        if ok:
+            sh = (int(t.shape[0]), int(t.shape[1]))
+            ok = (sh[1] <= 1 or t.stride(1) == 1) and (T is None or sh == (T, E)) and (sh[0] <= 1 or t.stride(0) >= sh[1])
+        if not ok:
+            raise RoverError(f"gae: {name} must be a {dtype} tensor{'' if T is None else ' [%d,%d] or [%d,%d,1]' % (T, E, T, E)} on {self.device} "
+                             "with unit env stride and a time stride >= E")
+        return t.data_ptr(), (t.stride(0) if sh[0] > 1 else sh[1]), sh[0], sh[1]
+
+    def _gae_stats(self, t, name):
+        if t is not None and (not t.is_cuda or t.device != self.device or t.dtype != torch.float64 or t.numel() != 3 or not t.is_contiguous()):
+            raise RoverError(f"gae: {name} must be 3 contiguous float64 words (count, mean, M2) on {self.device}")
+        return None if t is None else t.data_ptr()
+
+    def gae(self, rewards, values, dones, last_values, returns, advantages, gamma=0.99, lam=0.95, normalize=True, stats_out=None, stats_in=None):
+        """rover_gae: returns and advantages of a stored rollout in one pass.  rewards / values / returns / advantages: float32 [T, E] or
+        [T, E, 1]; dones: torch.bool or uint8 of that shape; last_values: float32 [E] or [E, 1], contiguous.  Time strides are taken from
+        the tensors (padded buffers and skrl-shaped storage work in place); ``returns`` may be ``values``.  ``normalize``: False = raw A,
+        True = (A - mean) / (std + 1e-8) with this call's own moments — or, when ``stats_in`` (3 float64 on the device) is given, with
+        those.  ``stats_out`` (3 float64 on the device) receives (count, mean, M2) of this call's raw A.  Enqueues only."""
+        rp, rs, T, E = self._gae_rows(rewards, "rewards", torch.float32)
+        vp, vs, _, _ = self._gae_rows(values, "values", torch.float32, T, E)
+        if dones is not None and dones.dtype == torch.bool:
+            dones = dones.view(torch.uint8)
+        dp, ds, _, _ = self._gae_rows(dones, "dones", torch.uint8, T, E)
+        op, os_, _, _ = self._gae_rows(returns, "returns", torch.float32, T, E)
+        ap, as_, _, _ = self._gae_rows(advantages, "advantages", torch.float32, T, E)
+        if last_values is None or tuple(last_values.shape) not in ((E,), (E, 1)):
+            raise RoverError(f"gae: last_values must be [{E}] or [{E},1]")
+        self._chk(last_values, tuple(last_values.shape), torch.float32, "last_values")
+        if stats_in is not None and not normalize:
+            raise RoverError("gae: stats_in is only read when normalize is set")
+        mode = GAE_RAW if not normalize else (GAE_NORMALIZE if stats_in is None else GAE_NORMALIZE_GIVEN)
+        d = GaeDesc(T, E, float(gamma), float(lam), rp, rs, vp, vs, dp, ds, last_values.data_ptr(), op, os_, ap, as_, mode,
+                    self._gae_stats(stats_out, "stats_out"), self._gae_stats(stats_in, "stats_in"))
+        self._check(self.lib.rover_gae(self._h, C.byref(d), _stream(self._dev_index)), "rover_gae")
+        return returns, advantages
 
     # ---- which kernel a forward call runs (host only: no ctx, no launch) ----------------------------
     @staticmethod

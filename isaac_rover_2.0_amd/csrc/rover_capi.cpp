@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -123,6 +124,7 @@ struct rover_ctx {
     DevBuf<uint32_t> d_sorted;          // [E*R8] ray slots sorted by (map, cell)
     int32_t cell_rcp = 0;               // option "cell_index_mode": 0 cpu_div (x / 0.1), 1 cuda_rcp (x * (1 / 0.1))
     DevBuf<float> d_mlp_scratch;        // partial sums of the split-k small-batch encoder path (rover_mlp_chain_forward)
+    DevBuf<double> d_gae_partials;      // [GAE_MAX_BLOCKS][3] per-block (count, mean, M2) of rover_gae, sized once at rover_create
     uint64_t workspace_bytes = 0;
     bool ws_ok = false, bins_ok = false;   // false after a failed (re)allocation: the step entry points refuse to run
     bool rays_valid = false;            // the ray workspace holds a finished ray cast (rover_replay_raycast)
@@ -560,6 +562,7 @@ int rover_create(const rover_cfg* cfg, rover_ctx** out) {
     if (e == hipSuccess) e = c->d_block_cnt.alloc((size_t)cfg->num_envs / 256 + 2);
     if (e == hipSuccess) e = c->d_goal_work.alloc(2 * (size_t)cfg->num_envs);
     if (e == hipSuccess) e = c->d_ids_work.alloc((size_t)cfg->num_envs);
+    if (e == hipSuccess) e = c->d_gae_partials.alloc(3 * (size_t)GAE_MAX_BLOCKS);
     if (e != hipSuccess) { delete c; return fail(nullptr, ROVER_E_HIP, "rover_create: %s", hipGetErrorString(e)); }
     *out = c;
     return ROVER_OK;
@@ -1611,6 +1614,58 @@ const char* rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, c
     const char* name = chain_act_route_name(chain_route(a), h.A);
     if (!name) fail(nullptr, ROVER_E_INVALID, "mlp_chain_act_route: net outside the built tile shapes");
     return name;
+}
+
+// ---- rollout: GAE ----
+// the bytes [lo, hi) a [T, E] array of `size`-byte elements at a time stride covers
+struct Span { uintptr_t lo, hi; };
+static Span span_of(const void* p, int64_t stride, int32_t T, int32_t E, size_t size) {
+    return Span{(uintptr_t)p, (uintptr_t)p + ((uint64_t)(T - 1) * (uint64_t)stride + (uint64_t)E) * size};
+}
+static bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+int rover_gae(rover_ctx* c, const rover_gae_desc* d, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    if (!d) return fail(c, ROVER_E_INVALID, "gae: null descriptor");
+    if (d->T < 1 || d->T > 4096 || d->E < 0 || (int64_t)d->T * d->E >= (int64_t)1 << 31)
+        return fail(c, ROVER_E_INVALID, "gae: T = %d outside 1 .. 4096, E = %d < 0, or T E >= 2^31", d->T, d->E);
+    if (d->normalize < ROVER_GAE_RAW || d->normalize > ROVER_GAE_NORMALIZE_GIVEN) return fail(c, ROVER_E_INVALID, "gae: unknown normalize %d", d->normalize);
+    if (d->E == 0) return ROVER_OK;            // nothing to read or write: no pointer is required
+    if (!d->rewards || !d->values || !d->dones || !d->last_values || !d->returns || !d->advantages)
+        return fail(c, ROVER_E_INVALID, "gae: rewards, values, dones, last_values, returns and advantages must be given");
+    if (d->normalize == ROVER_GAE_NORMALIZE_GIVEN && !d->stats_in) return fail(c, ROVER_E_INVALID, "gae: ROVER_GAE_NORMALIZE_GIVEN needs stats_in");
+    const int64_t max_stride = (int64_t)1 << 40;       // (T - 1) stride stays far inside 64 bits: the overlap tests below cannot wrap
+    for (int64_t st : {d->rewards_stride, d->values_stride, d->dones_stride, d->returns_stride, d->advantages_stride})
+        if (st < d->E || st > max_stride) return fail(c, ROVER_E_INVALID, "gae: a time stride is shorter than its row (E = %d) or above 2^40", d->E);
+    if (d->normalize == ROVER_GAE_NORMALIZE && (int64_t)d->T * d->E < 2)
+        return fail(c, ROVER_E_INVALID, "gae: ROVER_GAE_NORMALIZE needs T E >= 2 (the unbiased std of one element is NaN)");
+    const Span rew = span_of(d->rewards, d->rewards_stride, d->T, d->E, 4), val = span_of(d->values, d->values_stride, d->T, d->E, 4),
+               don = span_of(d->dones, d->dones_stride, d->T, d->E, 1), lv = span_of(d->last_values, d->E, 1, d->E, 4),
+               ret = span_of(d->returns, d->returns_stride, d->T, d->E, 4), adv = span_of(d->advantages, d->advantages_stride, d->T, d->E, 4);
+    if (overlap(ret, val) && !(d->returns == d->values && d->returns_stride == d->values_stride))
+        return fail(c, ROVER_E_INVALID, "gae: returns overlaps values without being the same array");
+    if (overlap(ret, rew) || overlap(ret, don) || overlap(ret, lv) || overlap(adv, rew) || overlap(adv, val) || overlap(adv, don) || overlap(adv, lv) || overlap(adv, ret))
+        return fail(c, ROVER_E_INVALID, "gae: an output overlaps an array the call reads (only returns may alias values)");
+    const Span so = span_of(d->stats_out, 3, 1, 3, 8), si = span_of(d->normalize == ROVER_GAE_NORMALIZE_GIVEN ? d->stats_in : nullptr, 3, 1, 3, 8);
+    for (const Span& s : {rew, val, don, lv, ret, adv})
+        if ((d->stats_out && overlap(so, s)) || (si.lo && overlap(si, s))) return fail(c, ROVER_E_INVALID, "gae: stats_out / stats_in overlaps a [T, E] array or last_values");
+    if (d->stats_out && si.lo && overlap(so, si)) return fail(c, ROVER_E_INVALID, "gae: stats_out overlaps stats_in");
+    USE_DEVICE(c);
+    GaeArgs a{};
+    a.T = d->T; a.E = (uint32_t)d->E; a.gamma = d->gamma; a.lam = d->lam;
+    a.rewards = d->rewards; a.rewards_stride = d->rewards_stride; a.values = d->values; a.values_stride = d->values_stride;
+    a.dones = d->dones; a.dones_stride = d->dones_stride; a.last_values = d->last_values;
+    a.returns = d->returns; a.returns_stride = d->returns_stride; a.advantages = d->advantages; a.advantages_stride = d->advantages_stride;
+    a.normalize = d->normalize; a.stats_out = d->stats_out; a.stats_in = d->normalize == ROVER_GAE_NORMALIZE_GIVEN ? d->stats_in : nullptr;
+    a.partials = c->d_gae_partials.get();
+    HIP_TRY(c, launch_gae(a, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+int rover_combine_moments(const double* a, const double* b, double* out) {
+    if (!a || !b || !out) return fail(nullptr, ROVER_E_INVALID, "combine_moments: null argument");
+    gae_combine_moments(a, b, out);
+    return ROVER_OK;
 }
 
 int rover_set_option(rover_ctx* c, const char* name, int64_t value) {

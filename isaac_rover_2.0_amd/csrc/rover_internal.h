@@ -254,6 +254,28 @@ hipError_t launch_gaussian_head(const float* mean, int64_t mean_stride, int M, c
 hipError_t launch_policy_noise(uint64_t seed, uint64_t step, const uint64_t* step_dev, int64_t row_offset, int M, int A, float* eps,
                                int64_t eps_stride, hipStream_t s);
 
+// Generalised advantage estimation over a stored rollout (rover_gae of the C ABI, validated; rover_rollout.hip): rows are time steps at
+// a stride in elements, the env stride is 1.
+enum GaeNormalize { GAE_RAW = 0, GAE_NORMALIZE = 1, GAE_NORMALIZE_GIVEN = 2 };
+constexpr uint32_t GAE_MAX_BLOCKS = 2048;  // most blocks of the scan = most (count, mean, M2) partials: the ctx holds 3 doubles for each
+struct GaeArgs {
+    int32_t T; uint32_t E;
+    float gamma, lam;
+    const float* rewards; int64_t rewards_stride;
+    const float* values; int64_t values_stride;
+    const uint8_t* dones; int64_t dones_stride;
+    const float* last_values;              // [E]
+    float* returns; int64_t returns_stride;            // may alias values
+    float* advantages; int64_t advantages_stride;
+    int32_t normalize;                     // GaeNormalize
+    double* stats_out;                     // optional [3]: (count, mean, M2) of this call's raw A
+    const double* stats_in;                // [3], GAE_NORMALIZE_GIVEN
+    double* partials;                      // [GAE_MAX_BLOCKS][3], the ctx's
+};
+int gae_launches(const GaeArgs& a);        // 0 (E = 0), 1 (the scan) or 2 (+ the finishing kernel: own moments needed)
+hipError_t launch_gae(const GaeArgs& a, hipStream_t s);
+void gae_combine_moments(const double* a, const double* b, double* out);   // host: Chan's update, the one the kernels run
+
 // blocks of bs threads (or items) that cover n: the launchers' grid sizes
 static inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
 
