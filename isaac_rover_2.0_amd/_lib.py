@@ -355,6 +355,7 @@ class Engine:
             raise RoverError(f"rover_create failed ({rc}): {self.lib.rover_last_error(None).decode()}")
         self._h = h
         self.P = self.Ns = self.Nd = 0
+        self.generation = 0         # bumped by every method that changes what a launch bakes in: cached launch state is keyed on it
 
     def close(self):
         if getattr(self, "_h", None):
@@ -373,6 +374,7 @@ class Engine:
 
     # ---- tables -------------------------------------------------------------------------------
     def set_knn_map(self, which, map_indices, triangles, vertices, cell_size=0.1, shift=(0.0, 0.0)):
+        self.generation += 1
         idx = _host(map_indices, np.int32)
         tris = _host(triangles, np.int32)
         v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
@@ -385,6 +387,7 @@ class Engine:
                                                float(shift[0]), float(shift[1])), "rover_set_knn_map")
 
     def set_distribution(self, points, sparse_idx, dense_idx):
+        self.generation += 1
         pts = _host(points, np.float64)
         sp = _host(sparse_idx, np.int64)
         de = _host(dense_idx, np.int64)
@@ -395,18 +398,21 @@ class Engine:
         self.P, self.Ns, self.Nd = pts.shape[0], len(sp), len(de)
 
     def set_heightfield(self, heightmap, horizontal_scale=0.025, vertical_scale=1.0, shift=(0.0, 0.0)):
+        self.generation += 1
         hm = _host(heightmap, np.float32)
         self._check(self.lib.rover_set_heightfield(self._h, hm.ctypes.data, hm.shape[0], hm.shape[1],
                                                    horizontal_scale, vertical_scale, float(shift[0]), float(shift[1])),
                     "rover_set_heightfield")
 
     def set_stones(self, info7):
+        self.generation += 1
         info = _host(info7, np.float32)
         if info.ndim != 2 or info.shape[1] != 7:
             raise RoverError("set_stones: expected [S,7] (read_stone_info output)")
         self._check(self.lib.rover_set_stones(self._h, info.ctypes.data, info.shape[0]), "rover_set_stones")
 
     def set_curriculum_level(self, level):
+        self.generation += 1
         self._check(self.lib.rover_set_curriculum_level(self._h, int(level)), "rover_set_curriculum_level")
 
     def set_scene(self, scene, distribution):
@@ -820,10 +826,12 @@ class Engine:
     # ---- evaluation mode (rover.py:122-137, 620-641, 670-672) -------------------------------------
     def set_evaluation(self, enable=True):
         """Turns the per-env outcome latch on (fresh zeroed codes and steps, synchronises) or off (frees them)."""
+        self.generation += 1
         self._check(self.lib.rover_set_evaluation(self._h, 1 if enable else 0), "rover_set_evaluation")
 
     def eval_clear(self, env_ids=None):
         """Re-arms the given LOCAL env ids (int64 device tensor), or every env: code 0, step 0.  With ids the call synchronises."""
+        self.generation += 1
         n = 0
         if env_ids is not None:
             n = env_ids.shape[0]
@@ -841,10 +849,12 @@ class Engine:
                     "rover_eval_read")
 
     def set_option(self, name, value):
+        self.generation += 1
         self._check(self.lib.rover_set_option(self._h, name.encode(), int(value)), "rover_set_option")
 
     def set_profiling(self, enable=True, every=1):
         """Bracket the ray-cast launch of every `every`-th step with hipEvents (get_profile() sums them)."""
+        self.generation += 1
         self._check(self.lib.rover_set_profiling(self._h, max(1, int(every)) if enable else 0), "rover_set_profiling")
 
     def get_profile(self):
@@ -955,16 +965,9 @@ class Engine:
             check(fn(h, C.c_void_p(actions.data_ptr()), *rest, _stream(idx)), "rover_pre_physics_step")
         return call
 
-    def pre_physics_step(self, actions, quat, lin_hist, ang_hist, euler_pre=None, pos_targets13=None, vel_targets13=None, actions_nn=None):
-        e, f = self.num_envs, torch.float32
-        self._chk(actions_nn, (e, 2, 3), f, "actions_nn")
-        for t, sh, n in ((actions, (e, 2), "actions"), (quat, (e, 4), "quat"), (lin_hist, (e, 3), "lin_hist"),
-                         (ang_hist, (e, 3), "ang_hist"), (euler_pre, (e, 3), "euler_pre"),
-                         (pos_targets13, (e, 13), "pos_targets13"), (vel_targets13, (e, 13), "vel_targets13")):
-            self._chk(t, sh, f, n)
-        self._check(self.lib.rover_pre_physics_step(self._h, _ptr(actions), _ptr(quat), _ptr(lin_hist), _ptr(ang_hist),
-                                                    _ptr(euler_pre), _ptr(pos_targets13), _ptr(vel_targets13), _ptr(actions_nn), _stream(self._dev_index)),
-                    "rover_pre_physics_step")
+    def pre_physics_step(self, actions, *args, **kw):
+        """rover_pre_physics_step on the given tensors; arguments after ``actions``: `bind_pre_physics`."""
+        self.bind_pre_physics(*args, **kw)(actions)
 
     def ackermann(self, lin, ang):
         n = lin.shape[0]

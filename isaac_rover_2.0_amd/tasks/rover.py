@@ -34,6 +34,7 @@ from __future__ import annotations
 import math
 import os
 import random
+from operator import attrgetter, is_, itemgetter
 
 import numpy as np
 import torch
@@ -105,6 +106,77 @@ class _RockDetector:
             raise _lib.RoverError("Rock_detector.get_collisions: the detector is not bound to a task yet")
         return self._engine.get_collisions(positions.float().contiguous(), rotations.float().contiguous(),
                                            joint_states.float().contiguous())
+
+
+# Every tensor of the task whose address a cached launch holds (`RoverTask._launch_tensors`): attribute paths, then the `extras` entries.
+_LAUNCH_ATTRS = ("_rover._pos", "_rover._quat", "_rover._joint_pos", "_rover._joint_vel", "_rover._joint_pos_targets", "_rover._joint_vel_targets",
+                 "target_positions", "linear_velocity.tracker", "angular_velocity.tracker", "rover_rot", "progress_buf", "obs_buf", "rew_buf",
+                 "reset_buf", "rock_collison", "reset_env_ids_buf", "_n_reset", "rover_rotation", "heading_diff", "stone_collision", "actions_nn",
+                 "initial_pos", "base_pos")
+_LAUNCH_NAMES = _LAUNCH_ATTRS + tuple("extras." + k for k in _lib.EXTRAS)
+_launch_attrs, _launch_extras = attrgetter(*_LAUNCH_ATTRS), itemgetter(*_lib.EXTRAS)
+
+
+def _launch_key(task):
+    """(the listed tensors in the order of _LAUNCH_NAMES, the engine's generation).  Two keys are the same when the tensors are the same
+    OBJECTS (`is`): an assignment that replaces one changes the key, an in-place write (fill_, copy_, [:] += 1) does not."""
+    return _launch_attrs(task) + _launch_extras(task.extras), task._engine.generation
+
+
+class _StepLaunches:
+    """Everything the task caches across steps so that a step does no per-call checks and packs no structs: the packed StepIn / StepOut
+    (``sin``, ``sout``), the two bound calls (``pre(actions)``, ``reset(seed)``), the two captured hipGraphs (``pre_graph``, ``post_graph``;
+    None until `capture`) with the buffers only they read (``actions``, ``seed_word``), and ``seed_step``, the global step whose Philox
+    key the device word holds.  All of it is built from ONE dict of tensors by name (``tensors``: `RoverTask._launch_tensors`) and is
+    good exactly while ``key`` — those tensors themselves and the engine's generation, `_launch_key` — is the task's current key."""
+
+    def __init__(self, engine, tensors, generation, stone_margin=0.0):
+        t = self.tensors = tensors
+        self.engine, self.key = engine, (tuple(t.values()), generation)
+        pos, quat, lin, ang = t["_rover._pos"], t["_rover._quat"], t["linear_velocity.tracker"], t["angular_velocity.tracker"]
+        self.sin = engine.make_in(pos, quat, t["_rover._joint_pos"], t["target_positions"], lin, ang, t["rover_rot"], t["progress_buf"])
+        self.sout = engine.make_out(t["obs_buf"], rew=t["rew_buf"], reset=t["reset_buf"], rock_collision=t["rock_collison"],
+                                    extras={k: t["extras." + k] for k in _lib.EXTRAS}, reset_ids=t["reset_env_ids_buf"],
+                                    n_reset=t["_n_reset"], euler=t["rover_rotation"], heading_diff=t["heading_diff"],
+                                    stone_collision=t["stone_collision"], stone_margin=stone_margin)
+        # euler_pre must see the PRE-reset orientation (:343 runs before :359), so `pre` is always launched before `reset`
+        self.pre = engine.bind_pre_physics(quat, lin, ang, euler_pre=t["rover_rot"], pos_targets13=t["_rover._joint_pos_targets"],
+                                           vel_targets13=t["_rover._joint_vel_targets"], actions_nn=t["actions_nn"])
+        self.reset_kw = dict(reset_ids=t["reset_env_ids_buf"], initial_pos3=t["initial_pos"], pos3=pos, quat4=quat, reset=t["reset_buf"],
+                             progress=t["progress_buf"], n_reset_dev=t["_n_reset"], joint_pos13=t["_rover._joint_pos"],
+                             joint_vel13=t["_rover._joint_vel"], base_pos3=t["base_pos"], target3=t["target_positions"], radius=8.0)
+        self.reset = engine.bind_reset_envs(**self.reset_kw)
+        self.pre_graph = self.post_graph = self.actions = self.seed_word = self.seed_step = None
+
+    def capture(self, seed):
+        """Captures the two halves of a step as hipGraphs.  The step part of the device RNG's key is a device word the captured graph
+        advances itself (`RoverTask._rng_seed` is additive in the step for that; ``seed`` is the key of step 0), so a replay draws what
+        the eager call of the same global step would."""
+        torch.cuda.synchronize()
+        like = self.tensors["initial_pos"]
+        self.actions, self.seed_word, self.seed_step = like.new_zeros(like.shape[0], 2), like.new_zeros(1, dtype=torch.int64), None
+        pre, post = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(pre):
+            self.seed_word.add_(_to_i64(_STEP_KEY))
+            self.pre(self.actions)
+            self.engine.reset_envs(**self.reset_kw, seed=seed, seed_dev=self.seed_word)
+        with torch.cuda.graph(post):
+            self.engine.step(self.sin, self.sout, increment_progress=True, compact=True)
+        self.pre_graph, self.post_graph = pre, post
+
+    def replay_pre(self, actions, step):
+        """Replays the pre-physics half for global step ``step``.  The replay itself turns the previous step's word into this step's;
+        where the word stands for any other step (after the capture, an eager step or an assignment to ``global_step``) it is set
+        from the host first."""
+        self.actions.copy_(actions)             # (device, dtype and layout conversions included)
+        if self.seed_step != step - 1:
+            self.seed_word.fill_(_to_i64((step - 1) * _STEP_KEY))
+        self.pre_graph.replay()
+        self.seed_step = step
+
+    def invalidate(self):
+        """Nothing of this object may be launched again: no key matches it and its graphs are gone."""
+        self.key, self.pre_graph, self.post_graph = ((), None), None, None
 
 
 class RoverTask(RLTask):
@@ -215,13 +287,7 @@ class RoverTask(RLTask):
         self.base_pos = torch.zeros(e, 3, device=dev)
         self._rover = None
         self._balls = None
-        self._sin = self._sout = None
-        # graph replay (graph=True): the actions land in a persistent buffer, the step counter of the device RNG lives on the device
-        self._actions_buf = torch.zeros(e, self._num_actions, device=dev)
-        self._seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._pre_graph = self._post_graph = None
-        self._graph_level = self._graph_key = None
-        self._bound_key = self._bound_pre = self._bound_reset = None
+        self._launch = self._sin = self._sout = None      # the cached launch state (`_launches`) and, as plain attributes, its two structs
 
     # ------------------------------------------------------------------------------------------------
     # scene / views (rover.py:196-230, 455-458) — USD is out of scope; views are host pose feeders
@@ -246,22 +312,27 @@ class RoverTask(RLTask):
         positions[:, 2] = height + self.position_z_offset                                 # :218
         self.initial_pos = positions
         self._rover.set_world_poses(self.initial_pos, self._rover.get_world_poses()[1])  # :220
-        self._balls._pos = self.target_positions       # the target balls ARE the goals (:584 moves them there): one tensor, no per-step copy
-        self._bind()
+        self.rover_positions = self._rover.get_world_poses()[0]
+        self._launches()
 
-    def _bind(self):
-        """(Re)build the C-ABI argument structs over the persistent tensors."""
-        pos, quat = self._rover.get_world_poses()
-        eng = self._engine
-        self._sin = eng.make_in(pos, quat, self._rover.get_joint_positions(), self.target_positions,
-                                self.linear_velocity.tracker, self.angular_velocity.tracker, self.rover_rot,
-                                self.progress_buf)
-        self._sout = eng.make_out(self.obs_buf, rew=self.rew_buf, reset=self.reset_buf, rock_collision=self.rock_collison,
-                                  extras=self.extras, reset_ids=self.reset_env_ids_buf, n_reset=self._n_reset,
-                                  euler=self.rover_rotation, heading_diff=self.heading_diff,
-                                  stone_collision=self.stone_collision, stone_margin=self._stone_margin or 0.0)
-        self.rover_positions = pos
-        self._bound_key = None
+    def _launch_tensors(self) -> dict:
+        """By name, every tensor of the task whose address ends up in a cached struct, a bound call or a captured graph (the arguments
+        of make_in, make_out, bind_pre_physics and bind_reset_envs).  `_StepLaunches` is built from this dict and keyed on it, so what
+        is checked is what is bound.  (The graphs' own actions buffer and seed word belong to the `_StepLaunches` and go with it.)"""
+        return dict(zip(_LAUNCH_NAMES, _launch_key(self)[0]))
+
+    def _launches(self) -> _StepLaunches:
+        """The cached launch state for the tensors now in place: the current one, or a new one (one re-pack, graphs recaptured later)
+        when a listed tensor was replaced by assignment or the engine's generation moved.  In-place writes leave the key alone."""
+        cur, (tensors, generation) = self._launch, _launch_key(self)
+        if cur is None or generation != cur.key[1] or not all(map(is_, tensors, cur.key[0])):
+            if cur is not None:
+                cur.invalidate()
+            self.actions_nn = self.actions_nn.to(self._device).float().contiguous()      # (shifted in place by the kernel: a caller's replacement is made fit)
+            self._balls._pos = self.target_positions       # the target balls ARE the goals (:584 moves them there): one tensor, no per-step copy
+            cur = self._launch = _StepLaunches(self._engine, self._launch_tensors(), generation, self._stone_margin or 0.0)
+            self._sin, self._sout = cur.sin, cur.sout
+        return cur
 
     def reset(self):
         RLTask.reset(self)
@@ -278,17 +349,20 @@ class RoverTask(RLTask):
     def get_observations(self) -> dict:
         """rover.py:272-336 → rover_get_observations (prep + ray cast + collision mask + obs assembly)."""
         self.rover_positions = self._rover.get_world_poses()[0]
-        self._engine.get_observations(self._sin, self._sout)
+        cur = self._launches()
+        self._engine.get_observations(cur.sin, cur.sout)
         return {self._rover.name: {"obs_buf": self.obs_buf}}
 
     def calculate_metrics(self) -> None:
         """rover.py:460-531 → rover_calculate_metrics (rew_buf + the 8 extras, in place)."""
-        self._engine.calculate_metrics(self._sin, self._sout)
+        cur = self._launches()
+        self._engine.calculate_metrics(cur.sin, cur.sout)
 
     def is_done(self) -> None:
         """rover.py:610-647 → rover_is_done (tilt from the PRE-physics euler ``self.rover_rot``; with evaluation on, also the
         outcome codes of :620-631 and the dump of :632-640)."""
-        self._engine.is_done(self._sin, self._sout)
+        cur = self._launches()
+        self._engine.is_done(cur.sin, cur.sout)
         self._compaction_fresh = False
         self._eval_dump()
 
@@ -337,8 +411,7 @@ class RoverTask(RLTask):
         self._eval_check()
         if env_ids is not None:
             env_ids = torch.as_tensor(env_ids, device=self._device).long().contiguous()
-        self._engine.eval_clear(env_ids)
-        self._pre_graph = self._post_graph = None
+        self._engine.eval_clear(env_ids)                # (bumps the engine's generation)
 
     def _eval_dump(self):
         """:632-640: at global_step % max_episode_length == 0 the progress of the envs whose code is 2 — of their CURRENT episode,
@@ -355,10 +428,11 @@ class RoverTask(RLTask):
             return RLTask.post_physics_step(self)
         if self._is_playing():
             self.rover_positions = self._rover.get_world_poses()[0]
-            if self._use_graph and self._post_graph is not None and self._graph_level == self.curriculum_level:
-                self._post_graph.replay()
+            cur = self._launches()
+            if cur.post_graph is not None:
+                cur.post_graph.replay()
             else:
-                self._engine.step(self._sin, self._sout, increment_progress=True, compact=True)
+                self._engine.step(cur.sin, cur.sout, increment_progress=True, compact=True)
             self._compaction_fresh = True
             self._eval_dump()
         else:
@@ -391,22 +465,22 @@ class RoverTask(RLTask):
         if not self._compaction_fresh:
             self._engine.compact_resets(self.reset_buf, self.reset_env_ids_buf, self._n_reset)
         self._compaction_fresh = False
-        rv = self._rover
         if self._device_reset:
+            cur = self._launches()              # (only the actions — usually a fresh policy output — are checked per call)
             if self._use_graph and reset_yaw_deg is None and self.global_step > 10:
-                self._actions_buf.copy_(actions)            # (device, dtype and layout conversions included)
-                key = self._ptr_key(self._actions_nn_buf())
-                if self._pre_graph is None or self._graph_level != self.curriculum_level or self._graph_key != key:
-                    self._capture_graphs()
-                    self._graph_key = key
-                self._pre_graph.replay()
+                if cur.pre_graph is None:
+                    cur.capture(self._rng_seed(step=0))
+                cur.replay_pre(actions, self.global_step)
                 return
-            _actions = actions.to(self._device).float().contiguous()
-            self._launch_pre_physics(_actions, reset_yaw_deg, seed=self._rng_seed(), seed_dev=None)
+            cur.pre(actions.to(self._device).float().contiguous())
+            if reset_yaw_deg is None:
+                cur.reset(self._rng_seed())
+            else:                                           # caller-supplied yaws (tests): validated and packed per call
+                self._engine.reset_envs(**cur.reset_kw, yaw_deg=reset_yaw_deg, seed=self._rng_seed())
             return
         _actions = actions.to(self._device).float().contiguous()
         self.actions_nn = torch.cat((torch.reshape(_actions, (self.num_envs, self._num_actions, 1)), self.actions_nn), 2)[:, :, 0:3]   # :366
-        self._engine.quat_to_euler(rv.get_world_poses()[1], out=self.rover_rot)                  # :343
+        self._engine.quat_to_euler(self._rover.get_world_poses()[1], out=self.rover_rot)         # :343
         n = int(self._n_reset.item())                      # the reference's len(reset_env_ids) is the same host sync
         if n > 0:
             reset_env_ids = self.reset_env_ids_buf[:n] - self._env_offset
@@ -429,61 +503,6 @@ class RoverTask(RLTask):
         velocities[:, 5] = motor_velocities[:, 4]          # RL
         self._rover.set_joint_position_targets(positions, indices=None, joint_indices=self._rover.actuated_pos_indices)
         self._rover.set_joint_velocity_targets(velocities, indices=None, joint_indices=self._rover.actuated_vel_indices)
-
-    def _launch_pre_physics(self, _actions, reset_yaw_deg, seed, seed_dev):
-        """The device-reset form of :338-414 as launches on the current stream (eager, or while a graph is being captured)."""
-        rv = self._rover
-        ann = self._actions_nn_buf()
-        # The task's buffers persist: their checks and the argument structs are made once and reused while the same tensors are in place
-        # (the actions — usually a fresh policy output — are passed and checked per call).  Caller-supplied yaws (tests) and a captured graph's device seed take the plain path.
-        key = self._ptr_key(ann)
-        if reset_yaw_deg is None and seed_dev is None and self._bound_key == key:
-            self._bound_pre(_actions)
-            self._bound_reset(seed)
-        else:
-            # euler_pre must see the PRE-reset orientation (:343 runs before :359), so this kernel goes first
-            pre_kw = dict(euler_pre=self.rover_rot, pos_targets13=rv._joint_pos_targets, vel_targets13=rv._joint_vel_targets, actions_nn=ann)
-            reset_kw = dict(n_reset_dev=self._n_reset, joint_pos13=rv._joint_pos, joint_vel13=rv._joint_vel, base_pos3=self.base_pos,
-                            target3=self.target_positions, radius=8.0)
-            reset_args = (self.reset_env_ids_buf, self.initial_pos, rv._pos, rv._quat, self.reset_buf, self.progress_buf)
-            self._engine.pre_physics_step(_actions, rv._quat, self.linear_velocity.tracker, self.angular_velocity.tracker, **pre_kw)
-            self._engine.reset_envs(*reset_args, yaw_deg=reset_yaw_deg, seed=seed, seed_dev=seed_dev, **reset_kw)
-            if reset_yaw_deg is None and seed_dev is None:
-                self._bound_pre = self._engine.bind_pre_physics(rv._quat, self.linear_velocity.tracker,
-                                                                self.angular_velocity.tracker, **pre_kw)
-                self._bound_reset = self._engine.bind_reset_envs(*reset_args, **reset_kw)
-                self._bound_key = key
-        if self._balls._pos.data_ptr() != self.target_positions.data_ptr():                      # :584 (visual only)
-            self._balls._pos.copy_(self.target_positions)
-
-    def _ptr_key(self, ann):
-        """Addresses of every tensor a cached argument struct / captured graph holds that an assignment could have replaced since (the
-        actions are not among them: a bound call takes them per step, a captured graph reads the task's own actions buffer)."""
-        rv = self._rover
-        return (ann.data_ptr(), self.initial_pos.data_ptr(), self.base_pos.data_ptr(), self.reset_buf.data_ptr(),
-                self.progress_buf.data_ptr(), self.target_positions.data_ptr(), rv._pos.data_ptr(), rv._quat.data_ptr(),
-                rv._joint_pos.data_ptr())
-
-    def _actions_nn_buf(self):
-        """self.actions_nn as the contiguous float32 [E, 2, 3] device tensor the kernel shifts in place (a caller may have rebound it)."""
-        a = self.actions_nn
-        if not (a.is_cuda and a.dtype == torch.float32 and a.is_contiguous() and tuple(a.shape) == (self._num_envs, self._num_actions, 3)):
-            a = self.actions_nn = a.to(self._device).float().contiguous()
-        return a
-
-    def _capture_graphs(self):
-        """Captures the two halves of a step as hipGraphs over the task's persistent tensors.  The device RNG's step counter is a
-        device word the captured graph advances itself (`_rng_seed` is additive in the step for that), so a replay draws what the
-        eager call of the same global step would."""
-        torch.cuda.synchronize()
-        self._seed_dev.fill_(_to_i64((self.global_step - 1) * _STEP_KEY))       # the captured add_ makes it this step's
-        pre, post = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(pre):
-            self._seed_dev.add_(_to_i64(_STEP_KEY))
-            self._launch_pre_physics(self._actions_buf, None, seed=self._rng_seed(step=0), seed_dev=self._seed_dev)
-        with torch.cuda.graph(post):
-            self._engine.step(self._sin, self._sout, increment_progress=True, compact=True)
-        self._pre_graph, self._post_graph, self._graph_level = pre, post, self.curriculum_level
 
     def reset_idx(self, env_ids, yaw_deg=None):
         """rover.py:416-453.  The reference builds scipy's (x,y,z,w) quaternion of a rotation about x and feeds

@@ -270,7 +270,7 @@ def test_task_eval_same_codes_on_every_path():
                       ("graph", dict(graph=True))):
         task, env, h = _drive(kw)
         if label == "graph":
-            assert task._post_graph is not None          # the latch ran inside the replayed post-physics graph
+            assert task._launches().post_graph is not None          # the latch ran inside the replayed post-physics graph
         runs[label] = h
         env.close()
     for label in ("fused_again", "unfused", "graph"):

@@ -165,6 +165,22 @@ def test_device_reset_equals_host_reset():
             np.testing.assert_array_equal(a[k].cpu().numpy(), b[k].cpu().numpy(), err_msg=k)
 
 
+def _assert_twins_equal(a, b, label):
+    """Two tasks driven by the same actions hold identical buffers (what `test_task_graph_replay_equals_eager` compares at every step)."""
+    for name in ("obs_buf", "rew_buf", "reset_buf", "progress_buf", "target_positions", "rover_rot", "rover_rotation", "heading_diff",
+                 "rock_collison", "stone_collision", "actions_nn", "reset_env_ids_buf", "_n_reset", "base_pos"):
+        x, y = getattr(a, name), getattr(b, name)
+        if name == "reset_env_ids_buf":
+            n = int(a._n_reset.item())
+            x, y = x[:n], y[:n]
+        assert torch.equal(x, y), f"{label}: {name}"
+    for k in a.extras:
+        assert torch.equal(a.extras[k], b.extras[k]), f"{label}: extras.{k}"
+    for x, y in zip(a._rover.get_world_poses() + (a._rover._joint_pos_targets, a._rover._joint_vel_targets, a.linear_velocity.tracker),
+                    b._rover.get_world_poses() + (b._rover._joint_pos_targets, b._rover._joint_vel_targets, b.linear_velocity.tracker)):
+        assert torch.equal(x, y), f"{label}: rover state"
+
+
 def test_task_graph_replay_equals_eager():
     """graph=True: from global step 11 on `pre_physics_step` and `post_physics_step` replay captured hipGraphs.  Two tasks — one eager, one
     replaying — driven through VecEnv.step() by the same actions over the curriculum switch, a reset() in the middle and 60 steps leave
@@ -196,26 +212,130 @@ def test_task_graph_replay_equals_eager():
         outs = [env.step(actions.clone()) for env in envs]
         torch.cuda.synchronize()
         a, b = tasks
-        for name in ("obs_buf", "rew_buf", "reset_buf", "progress_buf", "target_positions", "rover_rot", "rover_rotation", "heading_diff",
-                     "rock_collison", "stone_collision", "actions_nn", "reset_env_ids_buf", "_n_reset", "base_pos"):
-            x, y = getattr(a, name), getattr(b, name)
-            if name == "reset_env_ids_buf":
-                n = int(a._n_reset.item())
-                x, y = x[:n], y[:n]
-            assert torch.equal(x, y), f"step {i}: {name}"
-        for k in a.extras:
-            assert torch.equal(a.extras[k], b.extras[k]), f"step {i}: extras.{k}"
-        for x, y in zip(a._rover.get_world_poses() + (a._rover._joint_pos_targets, a._rover._joint_vel_targets, a.linear_velocity.tracker),
-                        b._rover.get_world_poses() + (b._rover._joint_pos_targets, b._rover._joint_vel_targets, b.linear_velocity.tracker)):
-            assert torch.equal(x, y), f"step {i}: rover state"
+        _assert_twins_equal(a, b, f"step {i}")
         for x, y in zip(outs[0][:3], outs[1][:3]):
             assert torch.equal(x, y)
         n_resets += int(a._n_reset.item())
         if i > 12:
             redrawn += int((b.target_positions != prev_target).any(dim=1).sum().item())
-    assert tasks[1]._pre_graph is not None and tasks[1]._post_graph is not None and tasks[0]._pre_graph is None
+    graphs = [(t._launches().pre_graph, t._launches().post_graph) for t in tasks]
+    assert graphs[1][0] is not None and graphs[1][1] is not None and graphs[0] == (None, None)
     # the replayed graph did reset envs and draw new goals: all of them after reset(), then the timed-out third
     assert n_resets >= e // 3 and redrawn >= e + e // 3 - 8, (n_resets, redrawn)
+    for env in envs:
+        env.close()
+
+
+_TWIN_ENVS = 64          # one wavefront, env 0 (the goal-aliasing quirk of rover.py:544-549) included
+
+
+def _twins(graph, steps=14):
+    """(eager twin, task under test, their envs, the generator of their actions) after `steps` identical steps — past global step 12, so a
+    graph task has captured and replayed.  The scene of `test_task_graph_replay_equals_eager`, the 37-ray distribution."""
+    from isaac_rover_amd import synth
+    from isaac_rover_amd.config import SimConfig
+    from isaac_rover_amd.vec_env import VecEnv, initialize_task
+    if "scene" not in _TWIN_SCENE:
+        _TWIN_SCENE["scene"] = synth.make_scene(n_cells=128, k=16, n_stones=24)
+    envs, tasks = [], []
+    for g in (False, graph):
+        env = VecEnv(headless=True)
+        tasks.append(initialize_task(SimConfig(num_envs=_TWIN_ENVS, device="cuda:0"), env, _TWIN_SCENE["scene"],
+                                     distribution=synth.ray_distribution("37"), graph=g, stone_mask_margin=0.0))
+        envs.append(env)
+    for env in envs:
+        env.reset()
+    gen = torch.Generator().manual_seed(17)
+    for i in range(steps):
+        _twin_step(tasks, envs, gen, f"warm-up step {i}")
+    if graph:
+        assert tasks[1]._launches().pre_graph is not None and tasks[1]._launches().post_graph is not None
+    return tasks[0], tasks[1], envs, gen
+
+
+_TWIN_SCENE = {}
+
+
+def _twin_step(tasks, envs, gen, label, yaw=None):
+    """One step of both tasks on the same actions (with ``yaw``: the reset yaws given, which both tasks run eagerly), then the comparison."""
+    actions = (2 * torch.rand(_TWIN_ENVS, 2, generator=gen) - 1).cuda()
+    for task, env in zip(tasks, envs):
+        if yaw is None:
+            env.step(actions.clone())
+        else:
+            task.pre_physics_step(actions.clone(), reset_yaw_deg=yaw)
+            env._world.step()
+            task.post_physics_step()
+    torch.cuda.synchronize()
+    _assert_twins_equal(tasks[0], tasks[1], label)
+
+
+def test_task_graph_eager_step_between_replays():
+    """A step that the graph task runs eagerly (reset yaws given) between two replays: the device RNG's step word, which only a replay
+    advances, must be brought up to date before the next replay.  Every env is reset on both steps, so a replay that drew with the
+    earlier step's Philox key would give every env the goal it already has.  "Most envs": the goal angle is a continuous draw, so two
+    keys give an env the same goal with probability ~0; more than half of the envs leaves room for nothing but that."""
+    a, b, envs, gen = _twins(graph=True)
+    yaw = torch.randint(0, 361, (_TWIN_ENVS,), generator=gen, dtype=torch.int32).cuda()
+    for t in (a, b):
+        t.reset()
+    _twin_step((a, b), envs, gen, "eager step", yaw=yaw)
+    first = b.target_positions.clone()
+    for t in (a, b):
+        t.reset()
+    _twin_step((a, b), envs, gen, "replay after the eager step")
+    changed = int((b.target_positions != first).any(dim=1).sum().item())
+    assert changed > _TWIN_ENVS // 2, changed
+    assert b._launches().pre_graph is not None
+    for env in envs:
+        env.close()
+
+
+@pytest.mark.parametrize("graph", [False, True])
+def test_task_rebound_buffers_are_written(graph):
+    """Replacing `rew_buf`, `obs_buf` and an `extras` entry by fresh tensors (what the reference's `cleanup()` does): the next step
+    writes the new tensors, and `task._sout` points at them."""
+    a, b, envs, gen = _twins(graph=graph)
+    b.rew_buf, b.obs_buf = torch.zeros_like(b.rew_buf), torch.zeros_like(b.obs_buf)
+    b.extras["pos_reward"] = torch.zeros_like(b.extras["pos_reward"])
+    new = (b.rew_buf, b.obs_buf, b.extras["pos_reward"])
+    _twin_step((a, b), envs, gen, "step after rebinding")
+    assert b.rew_buf is new[0] and b.obs_buf is new[1] and b.extras["pos_reward"] is new[2]
+    assert torch.equal(new[0], a.rew_buf) and torch.equal(new[1], a.obs_buf) and torch.equal(new[2], a.extras["pos_reward"])
+    assert bool(new[1].abs().sum() > 0)
+    assert (b._sout.rew, b._sout.obs, b._sout.ex_pos_reward) == tuple(t.data_ptr() for t in new)
+    _twin_step((a, b), envs, gen, "second step after rebinding")
+    for env in envs:
+        env.close()
+
+
+def test_task_second_set_up_scene_then_post_physics_step():
+    """`set_up_scene` again after the graphs were captured, the same poses fed in, then `post_physics_step()` with no `pre_physics_step`
+    before it: the step runs on the new views' tensors (a captured graph addresses the old ones)."""
+    a, b, envs, gen = _twins(graph=True)
+    spawn = a.initial_pos.clone()
+    pos, quat = a._rover.get_world_poses(clone=True)
+    joints = a._rover.get_joint_positions().clone()
+    for t in (a, b):
+        t.set_up_scene(spawn_positions=spawn)
+        t._rover.feed(pos, quat, joints)
+        t.post_physics_step()
+    torch.cuda.synchronize()
+    _assert_twins_equal(a, b, "post_physics_step after a second set_up_scene")
+    assert bool(a.obs_buf.abs().sum() > 0) and b._sin.pos == b._rover._pos.data_ptr()
+    for env in envs:
+        env.close()
+
+
+def test_task_engine_setter_reaches_a_captured_graph():
+    """A value the kernels take by value (the curriculum level; no device buffer is re-sized) set on the engine after the capture:
+    the next step runs with it, as the eager twin's does."""
+    a, b, envs, gen = _twins(graph=True)
+    before = b._launches()
+    for t in (a, b):
+        t._engine.set_curriculum_level(1)
+    _twin_step((a, b), envs, gen, "step after set_curriculum_level(1)")
+    assert b._launches() is not before and before.post_graph is None
     for env in envs:
         env.close()
 
