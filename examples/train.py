@@ -1,0 +1,95 @@
+#!/usr/bin/env python3
+"""train.py-shaped PPO training on the MI355X rover step path (no Isaac Sim, no skrl, no autograd).
+
+`examples/rollout.py`'s loop (`--policy actor --rollouts N`) with the weight update behind it: every `--rollouts` steps
+`learning.ppo.PPO.update` runs compute_gae and `learning_epochs` x `mini_batches` minibatches of forward, PPO loss, backward
+(`rover_ppo_loss`, `rover_linear_backward`), gradient clipping and one Adam step, with the reference's hyper-parameters
+(cfg/trainSKRL/RoverPPOSKRL.yaml).  Prints losses, KL and the mean return per update.
+
+    python examples/train.py --envs 512 --native-rays --steps 120 --rollouts 60 [--time-update]
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from isaac_rover_amd import assets, config, synth, vec_env  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=512)
+    ap.add_argument("--steps", type=int, default=120)
+    ap.add_argument("--assets", default="", help="directory holding the reference's tasks/utils/terrain/... files")
+    ap.add_argument("--native-rays", action="store_true", help="the reference's 1634-point distribution (1750-float obs)")
+    ap.add_argument("--checkpoint", default="", help="a state_dict of the reference's StochasticActorHeightmap (torch.save)")
+    ap.add_argument("--rollouts", type=int, default=60, help="steps per rollout = rows of the memory (cfg/trainSKRL/RoverPPOSKRL.yaml:12)")
+    ap.add_argument("--epochs", type=int, default=4, help="learning_epochs")
+    ap.add_argument("--mini-batches", type=int, default=60, help="mini_batches")
+    ap.add_argument("--kl-threshold", type=float, default=0.008)
+    ap.add_argument("--time-update", action="store_true", help="print the wall time of each update between two torch.cuda.synchronize()")
+    args = ap.parse_args()
+    if args.rollouts < 1:
+        ap.error("--rollouts N needs N >= 1")
+
+    scene = assets.load_reference_assets(args.assets) if args.assets else synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
+    cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
+    env = vec_env.VecEnv(headless=True)
+    extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size
+    g = torch.Generator().manual_seed(0)
+    spawn = torch.zeros(args.envs, 3)
+    spawn[:, 0:2] = 0.15 * extent + 0.7 * extent * torch.rand(args.envs, 2, generator=g)
+    from isaac_rover_amd.learning.model import DeterministicHeightmap, StochasticActorHeightmap
+    from isaac_rover_amd.learning.ppo import PPO
+    from isaac_rover_amd.learning.rollout import RolloutMemory
+    from isaac_rover_amd.tasks.rover import RoverTask
+    task = RoverTask("Rover", cfg, env, scene=scene, distribution=None if args.native_rays else synth.ray_distribution("37"))
+    env.set_task(task, sim_params={"dt": 0.05}, spawn_positions=spawn)          # utils/task_util.py:45
+    obs = env.reset()
+    print(f"obs {tuple(obs.shape)}  actions {task.num_actions}  device {task.device}")
+    agent = StochasticActorHeightmap(task._engine, task)
+    if args.checkpoint:
+        sd = torch.load(args.checkpoint, map_location="cpu")
+        agent.load_state_dict(sd.get("policy", sd) if isinstance(sd, dict) else sd)
+    critic = DeterministicHeightmap(task._engine, task, seed=1)
+    memory = RolloutMemory(args.rollouts, args.envs, device=task.device, report=print)
+    for name, size, dtype in (("states", obs.shape[1], torch.float32), ("actions", task.num_actions, torch.float32), ("log_prob", 1, torch.float32),
+                              ("values", 1, torch.float32), ("rewards", 1, torch.float32), ("terminated", 1, torch.bool),
+                              ("returns", 1, torch.float32), ("advantages", 1, torch.float32)):
+        memory.create_tensor(name, size, dtype)
+    ppo = PPO(task._engine, agent, critic, memory, {"learning_epochs": args.epochs, "mini_batches": args.mini_batches, "kl_threshold": args.kl_threshold},
+              generator=torch.Generator().manual_seed(0))
+    updates = 0
+    for _ in range(args.steps):
+        actions, log_prob, _ = agent.act(obs)
+        values, _, _ = critic.act(obs)
+        states = obs.clone()                                                       # env.step() rewrites the observation buffer
+        obs, rew, done, info = env.step(actions)
+        memory.add_samples(states=states, actions=actions, log_prob=log_prob, values=values, rewards=rew, terminated=done.bool())
+        if memory.memory_index == 0:                                               # full: one PPO update on these N steps
+            last_values, _, _ = critic.act(obs)
+            last_values = last_values.clone()                                      # the update's forwards reuse the critic's buffers
+            if args.time_update:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            out = ppo.update(last_values)
+            if args.time_update:
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+            updates += 1
+            steps = sum(ppo.minibatches_done)
+            print(f"update {updates}: policy_loss {float(out['policy_loss']):+.5f}  value_loss {float(out['value_loss']):.5f}  "
+                  f"entropy_loss {float(out['entropy_loss']):+.5f}  kl {float(out['kl']):.3e}  mean return "
+                  f"{float(memory.get_tensor_by_name('returns').mean()):.4f}  minibatches stepped per epoch {ppo.minibatches_done}"
+                  + (f"  update {dt * 1e3:.1f} ms ({dt * 1e3 / max(steps, 1):.2f} ms per stepped minibatch of "
+                     f"{args.rollouts * args.envs // args.mini_batches} rows)" if args.time_update else ""))
+            memory.reset()
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -429,7 +429,8 @@ ROVER_API const char *rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n
  *       adv = rewards[t] - values[t] + gamma (dones[t] ? 0 : 1) (nv + lam adv);  A[t] = adv
  *   returns = A + values;   advantages = (A - mean(A)) / (std(A) + 1e-8), mean and UNBIASED std over all T E elements
  * NaN and Inf get no special handling: they propagate as the formula says (a done flag multiplies by 0).  Time-limit bootstrapping
- * (rewards += gamma values truncated at record time) is the caller's one elementwise line, not part of the kernel.
+ * (rewards += gamma values truncated at record time) is the caller's one elementwise line, not part of the kernel.  The weight update
+ * that consumes returns and advantages is rover_ppo_loss + rover_linear_backward below (learning/ppo.py drives them).
  * Every [T, E] array is (device pointer, TIME stride in elements >= E); the env stride is 1, so skrl-shaped [T, E, 1] tensors and
  * padded buffers are read and written in place.  returns may alias values (same pointer and stride); advantages aliases nothing the
  * call reads.
@@ -468,6 +469,77 @@ ROVER_API int rover_gae(rover_ctx *ctx, const rover_gae_desc *d, void *stream);
 /* Host only (no ctx, no device): out[3] = the moments (count, mean, M2) of the union of two disjoint samples with moments a[3], b[3] —
  * Chan, Golub & LeVeque's pairwise update, the one the kernels run.  An empty side (count 0) leaves the other unchanged; out may be a or b. */
 ROVER_API int rover_combine_moments(const double *a, const double *b, double *out);
+
+/* ---- the learner side of PPO: the backward of one Layer and the minibatch loss (skrl's PPO._update on torch autograd) --------------- */
+/* The reference trains with skrl's PPO_DEFAULT_CONFIG overridden by cfg/trainSKRL/RoverPPOSKRL.yaml (learning_epochs 4, mini_batches 60,
+ * learning_rate 1e-4, grad_norm_clip 1.0, ratio_clip 0.2, value_clip 0.2, clip_predicted_values True, entropy_loss_scale 0,
+ * value_loss_scale 1, kl_threshold 0.008; no preprocessors, no scheduler).  skrl is not installed: everything below is restated from a
+ * reading of skrl 1.x and of ATen's backward formulas (derivatives.yaml: leaky_relu / tanh / relu / elu backward from the result, clamp,
+ * minimum), and is this project's definition.
+ *
+ * rover_linear_backward: the backward of y = act(x W^T + b) as rover_linear_forward computes it.  x [M, K], y [M, N] (the layer's
+ * post-activation OUTPUT as the forward wrote it) and dy [M, N] are (device pointer, row stride in elements); weight [N][K] contiguous.
+ *   dz = dy * act'(y), the derivative taken from y alone:  none 1;  LeakyReLU y > 0 ? 1 : 0.01f;  ReLU y > 0 ? 1 : 0;
+ *                                                           Tanh 1 - y*y;  ELU y > 0 ? 1 : y + 1
+ *   dx [M, K] = dz W   (pointer, row stride)      dweight [N][K] = dz^T x   (contiguous)      dbias [N] = column sums of dz
+ * Each output is optional (NULL: not computed).  Inputs an output does not need may be NULL: y with activation 0, x without dweight,
+ * weight without dx.  N <= 256 always, K <= 256 when dx is wanted (the first encoder layers, K = 634 / 1 112, never need dx); K = 0 is
+ * legal (dweight is empty, dbias is still written); M = 0 writes zeros to dweight and dbias.  NaN and Inf propagate as the formulas say.
+ * dweight / dbias: an f32-input MFMA reduction over M, cut into splits whose f32 partials go to a scratch buffer of the ctx and are
+ * added in the order of the splits — no floating-point atomics, the same inputs give the same bits on every run.  The scratch follows
+ * the chain entry points' rule: it grows on demand (the first call of a size outside a stream capture), one stream per ctx at a time.
+ * ROVER_E_INVALID before any launch: M < 0, K < 0, N outside 1 .. 256, K > 256 with dx, an unknown activation, a NULL required pointer, a
+ * row stride shorter than its row or above 2^40, an output overlapping an input or another output. */
+ROVER_API int rover_linear_backward(rover_ctx *ctx, const float *x, int64_t x_stride, const float *y, int64_t y_stride, const float *dy,
+                                    int64_t dy_stride, int32_t M, int32_t K, const float *weight, int32_t N, int32_t activation, float *dx,
+                                    int64_t dx_stride, float *dweight, float *dbias, void *stream);
+/* What rover_linear_backward would launch — host only, like rover_linear_route: "wgrad<NT,NW>/S" (linear_wgrad_kernel<NT, NW> over S
+ * splits of M, merged when S > 1), followed by ";dgrad<NT,NW>" (";dgrad<NT,4>x2": two column halves) when want_dx and K > 0; "zero" for
+ * M = 0; NULL where the call would be refused.  The split rule (csrc/rover_train.hip linear_backward_route): M >= 8 192 — NW = 4, NT =
+ * the N tiles of 32 in groups of at most 3, S = M / 1 024 rounded down to a power of two, at most 64; below — NW = NT = 1, S = 1 / 2 / 4
+ * / 8 from 0 / 128 / 256 / 512 rows.  The pointer is valid until the calling thread's next route query. */
+ROVER_API const char *rover_linear_backward_route(int32_t M, int32_t K, int32_t N, int32_t want_dx);
+
+/* rover_ppo_loss: skrl's PPO minibatch loss at the nets' outputs, and its gradients with respect to them.  With ls', sigma and
+ * lp_i = sum_j [...] exactly as the rover_gauss_head comment defines them for taken actions a (reduction: ROVER_REDUCE_SUM only, the
+ * reference's), c = ratio_clip, vc = value_clip:
+ *   r_i = exp(lp_i - old_log_prob_i)                      kl = mean((r - 1) - (lp - old_log_prob))
+ *   policy_loss  = -mean(min(adv r, adv clamp(r, 1 - c, 1 + c)))
+ *   v'           = old_values + clamp(value - old_values, -vc, vc) if clip_predicted_values, else value
+ *   value_loss   = value_loss_scale mean((returns - v')^2)
+ *   entropy_loss = -entropy_loss_scale * mean over M and A of (0.5 + 0.5 log 2pi + ls'_j)
+ * and L = policy_loss + value_loss + entropy_loss.  The gradients are autograd's for those expressions, its tie rules included (a min
+ * tie splits the gradient in half, clamp passes the gradient on the closed interval), [.] = 1 if true else 0:
+ *   dL/dr_i     = -(adv_i / M) [1 - c <= r_i <= 1 + c  or  adv_i r_i < adv_i clamp(r_i)]
+ *   d_mean_ij   = dL/dr_i r_i (a_ij - mean_ij) / sigma_j^2
+ *   d_log_std_j = [min <= ls_j <= max, or no clip_log_std] (sum_i dL/dr_i r_i ((a_ij - mean_ij)^2 / sigma_j^2 - 1) - entropy_loss_scale / A)
+ *   d_value_i   = value_loss_scale (2 / M) (v'_i - returns_i) [|value_i - old_values_i| <= vc, or no clipping]
+ * stats (device double[4]) = (policy_loss, value_loss, entropy_loss, kl).  The per-row terms are f32 (the order of operations is
+ * written out in csrc/rover_train.hip); the sums over M are f64, merged from per-block partials in a fixed order as rover_gae merges its
+ * moments: the same inputs give the same bits.  NaN and Inf propagate as the formulas say.
+ * The partials' buffer belongs to the ctx since rover_create: the call allocates nothing, does not synchronise and can be captured.
+ * Launches: one, plus the merge; none for M = 0 (ROVER_OK).  One stream per ctx at a time.
+ * ROVER_E_INVALID before any launch: a NULL pointer (M > 0), A outside 1 .. 16, M < 0, a reduction other than ROVER_REDUCE_SUM, min_log_std >
+ * max_log_std with clip_log_std, a negative (or NaN) ratio_clip / value_clip, a row stride < A or > 2^40, an output overlapping an input
+ * or another output. */
+typedef struct {
+    int32_t M, A;                 /* rows of the minibatch; 1 .. 16 action components                                            */
+    const float *mean;      int64_t mean_stride;       /* [M, A] the actor's output ("mean_actions")                            */
+    const float *log_std;                               /* [A] log_std_parameter                                                 */
+    const float *actions;   int64_t actions_stride;    /* [M, A] the actions taken in the rollout                               */
+    const float *old_log_prob, *advantages;             /* [M]                                                                   */
+    const float *value, *old_values, *returns;          /* [M] the critic's output; the rollout's values; rover_gae's returns    */
+    int32_t clip_log_std;  float min_log_std, max_log_std;       /* as in rover_gauss_head                                      */
+    int32_t reduction;            /* ROVER_REDUCE_SUM                                                                            */
+    float ratio_clip, value_clip;
+    int32_t clip_predicted_values;
+    float entropy_loss_scale, value_loss_scale;
+    float *d_mean;          int64_t d_mean_stride;     /* [M, A] out */
+    float *d_value;                                     /* [M] out    */
+    float *d_log_std;                                   /* [A] out    */
+    double *stats;                                      /* [4] out    */
+} rover_ppo_loss_desc;
+ROVER_API int rover_ppo_loss(rover_ctx *ctx, const rover_ppo_loss_desc *d, void *stream);
 
 /* ---- tuning knobs ------------------------------------------------------------------------------------- */
 /* name = "raycast_variant": 0 = auto; 1 = one half-wave per ray in env order, every cell block streamed from HBM;

@@ -102,6 +102,16 @@ class GaeDesc(C.Structure):
 
 GAE_RAW, GAE_NORMALIZE, GAE_NORMALIZE_GIVEN = 0, 1, 2
 
+
+class PpoLossDesc(C.Structure):
+    _fields_ = [("M", C.c_int32), ("A", C.c_int32), ("mean", C.c_void_p), ("mean_stride", C.c_int64), ("log_std", C.c_void_p),
+                ("actions", C.c_void_p), ("actions_stride", C.c_int64), ("old_log_prob", C.c_void_p), ("advantages", C.c_void_p),
+                ("value", C.c_void_p), ("old_values", C.c_void_p), ("returns", C.c_void_p), ("clip_log_std", C.c_int32),
+                ("min_log_std", C.c_float), ("max_log_std", C.c_float), ("reduction", C.c_int32), ("ratio_clip", C.c_float),
+                ("value_clip", C.c_float), ("clip_predicted_values", C.c_int32), ("entropy_loss_scale", C.c_float),
+                ("value_loss_scale", C.c_float), ("d_mean", C.c_void_p), ("d_mean_stride", C.c_int64), ("d_value", C.c_void_p),
+                ("d_log_std", C.c_void_p), ("stats", C.c_void_p)]
+
 REDUCTIONS = {"sum": 0, "mean": 1, "prod": 2, "max": 3, "min": 4, None: 5, "none": 5}
 
 
@@ -168,6 +178,10 @@ SYMBOLS = {
     "rover_mlp_chain_act_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(GaussHead)]),
     "rover_gae": (C.c_int, [_P, C.POINTER(GaeDesc), _P]),
     "rover_combine_moments": (C.c_int, [_P, _P, _P]),
+    "rover_linear_backward": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64,
+                                        _P, _P, _P]),
+    "rover_linear_backward_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rover_ppo_loss": (C.c_int, [_P, C.POINTER(PpoLossDesc), _P]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
     "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
     "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -788,6 +802,69 @@ class Engine:
                     self._gae_stats(stats_out, "stats_out"), self._gae_stats(stats_in, "stats_in"))
         self._check(self.lib.rover_gae(self._h, C.byref(d), _stream(self._dev_index)), "rover_gae")
         return returns, advantages
+
+    # ---- the learner side of PPO (rover_linear_backward, rover_ppo_loss) ---------------------------------
+    def linear_backward(self, x, y, dy, weight, activation, dx=None, dweight=None, dbias=None):
+        """rover_linear_backward: the backward of ``y = act(x @ weight.T + bias)``.  ``y`` is the layer's output as linear_forward wrote
+        it, ``dy`` the gradient at it; x / y / dy / dx may be column slices of wider row-major tensors; ``dweight`` [n, k] and ``dbias``
+        [n] are contiguous.  Each output is optional (None: not computed); ``x`` may be None without ``dweight``.  Enqueues only."""
+        what = "linear_backward"
+        n, k = weight.shape
+        m = self._f32_rows(dy, "dy", what).shape[0]
+        if dy.shape[1] != n:
+            raise RoverError(f"{what}: dy must be [{m},{n}]")
+        self._f32_rows(y, "y", what, (m, n))
+        if k > 0:
+            self._chk(weight, (n, k), torch.float32, "weight")
+        if x is not None:
+            self._f32_rows(x, "x", what, (m, k))
+        elif dweight is not None and k > 0:
+            raise RoverError(f"{what}: dweight needs x")
+        if dx is not None:
+            self._f32_rows(dx, "dx", what, (m, k))
+        if dweight is not None and k > 0:
+            self._chk(dweight, (n, k), torch.float32, "dweight")
+        if dbias is not None:
+            self._chk(dbias, (n,), torch.float32, "dbias")
+        st = lambda t, cols: 0 if t is None else max(t.stride(0), cols)
+        self._check(self.lib.rover_linear_backward(self._h, _ptr(x), st(x, k), _ptr(y), st(y, n), _ptr(dy), st(dy, n), m, k, _ptr(weight), n,
+                                                   self.ACTIVATIONS[activation], _ptr(dx), st(dx, k), _ptr(dweight), _ptr(dbias),
+                                                   _stream(self._dev_index)), "rover_linear_backward")
+
+    def ppo_loss(self, mean, log_std, actions, old_log_prob, advantages, value, old_values, returns, d_mean, d_value, d_log_std, stats,
+                 ratio_clip=0.2, value_clip=0.2, clip_predicted_values=True, entropy_loss_scale=0.0, value_loss_scale=1.0, clip_log_std=True,
+                 min_log_std=-20.0, max_log_std=2.0, reduction="sum"):
+        """rover_ppo_loss: the PPO minibatch loss at the nets' outputs and its gradients.  mean / actions / d_mean: float32 [m, A] (column
+        slices will do); the per-row arrays float32 [m] or [m, 1], contiguous; log_std / d_log_std [A]; ``stats``: 4 float64 on the
+        device, receives (policy_loss, value_loss, entropy_loss, kl).  Enqueues only; capturable."""
+        what = "ppo_loss"
+        m, a = self._f32_rows(mean, "mean", what).shape
+        self._f32_rows(actions, "actions", what, (m, a))
+        self._f32_rows(d_mean, "d_mean", what, (m, a))
+        for t, name in ((old_log_prob, "old_log_prob"), (advantages, "advantages"), (value, "value"), (old_values, "old_values"), (returns, "returns"),
+                        (d_value, "d_value")):
+            if t is None or tuple(t.shape) not in ((m,), (m, 1)):
+                raise RoverError(f"{what}: {name} must be [{m}] or [{m},1]")
+            self._chk(t, tuple(t.shape), torch.float32, name)
+        self._chk(log_std, (a,), torch.float32, "log_std")
+        self._chk(d_log_std, (a,), torch.float32, "d_log_std")
+        if stats is None or not stats.is_cuda or stats.dtype != torch.float64 or stats.numel() != 4 or not stats.is_contiguous():
+            raise RoverError(f"{what}: stats must be 4 contiguous float64 words on the GPU")
+        if reduction not in REDUCTIONS:
+            raise RoverError(f"{what}: unknown reduction {reduction!r}")
+        d = PpoLossDesc(m, a, mean.data_ptr(), max(mean.stride(0), a), log_std.data_ptr(), actions.data_ptr(), max(actions.stride(0), a),
+                        old_log_prob.data_ptr(), advantages.data_ptr(), value.data_ptr(), old_values.data_ptr(), returns.data_ptr(),
+                        int(bool(clip_log_std)), float(min_log_std), float(max_log_std), REDUCTIONS[reduction], float(ratio_clip), float(value_clip),
+                        int(bool(clip_predicted_values)), float(entropy_loss_scale), float(value_loss_scale), d_mean.data_ptr(),
+                        max(d_mean.stride(0), a), d_value.data_ptr(), d_log_std.data_ptr(), stats.data_ptr())
+        self._check(self.lib.rover_ppo_loss(self._h, C.byref(d), _stream(self._dev_index)), "rover_ppo_loss")
+        return stats
+
+    @classmethod
+    def linear_backward_route(cls, m, k, n, want_dx):
+        """What linear_backward launches ("wgrad<3,4>/64;dgrad<1,4>", ...: the weight-gradient instantiation and its M-split, then the
+        dx kernel); "zero" for m = 0, None where the call would be refused."""
+        return cls._route(load().rover_linear_backward_route(int(m), int(k), int(n), int(bool(want_dx))))
 
     # ---- which kernel a forward call runs (host only: no ctx, no launch) ----------------------------
     @staticmethod

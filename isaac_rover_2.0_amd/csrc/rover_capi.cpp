@@ -125,6 +125,7 @@ struct rover_ctx {
     int32_t cell_rcp = 0;               // option "cell_index_mode": 0 cpu_div (x / 0.1), 1 cuda_rcp (x * (1 / 0.1))
     DevBuf<float> d_mlp_scratch;        // partial sums of the split-k small-batch encoder path (rover_mlp_chain_forward)
     DevBuf<double> d_gae_partials;      // [GAE_MAX_BLOCKS][3] per-block (count, mean, M2) of rover_gae, sized once at rover_create
+    DevBuf<double> d_ppo_partials;      // [PPO_MAX_BLOCKS][3 + GAUSS_MAX_A] per-block sums of rover_ppo_loss, sized once at rover_create
     uint64_t workspace_bytes = 0;
     bool ws_ok = false, bins_ok = false;   // false after a failed (re)allocation: the step entry points refuse to run
     bool rays_valid = false;            // the ray workspace holds a finished ray cast (rover_replay_raycast)
@@ -563,6 +564,7 @@ int rover_create(const rover_cfg* cfg, rover_ctx** out) {
     if (e == hipSuccess) e = c->d_goal_work.alloc(2 * (size_t)cfg->num_envs);
     if (e == hipSuccess) e = c->d_ids_work.alloc((size_t)cfg->num_envs);
     if (e == hipSuccess) e = c->d_gae_partials.alloc(3 * (size_t)GAE_MAX_BLOCKS);
+    if (e == hipSuccess) e = c->d_ppo_partials.alloc((3 + (size_t)GAUSS_MAX_A) * PPO_MAX_BLOCKS);
     if (e != hipSuccess) { delete c; return fail(nullptr, ROVER_E_HIP, "rover_create: %s", hipGetErrorString(e)); }
     *out = c;
     return ROVER_OK;
@@ -1665,6 +1667,91 @@ int rover_gae(rover_ctx* c, const rover_gae_desc* d, void* stream) {
 int rover_combine_moments(const double* a, const double* b, double* out) {
     if (!a || !b || !out) return fail(nullptr, ROVER_E_INVALID, "combine_moments: null argument");
     gae_combine_moments(a, b, out);
+    return ROVER_OK;
+}
+
+// ---- training: the backward of one Layer, the PPO loss ----
+int rover_linear_backward(rover_ctx* c, const float* x, int64_t x_stride, const float* y, int64_t y_stride, const float* dy, int64_t dy_stride,
+                          int32_t M, int32_t K, const float* weight, int32_t N, int32_t activation, float* dx, int64_t dx_stride, float* dweight,
+                          float* dbias, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    const LinearBwdRoute r = linear_backward_route(M, K, N, dx != nullptr);
+    if (!r.ok || activation < 0 || activation > 4)
+        return fail(c, ROVER_E_INVALID, "linear_backward: M=%d K=%d N=%d act=%d outside M >= 0, K >= 0 (<= 256 with dx), 1 <= N <= 256, act 0 .. 4", M, K, N, activation);
+    const bool need_x = dweight && K > 0, need_w = dx && K > 0;
+    if (M > 0 && (!dy || (activation != 0 && !y) || (need_x && !x) || (need_w && !weight)))       // M = 0: nothing is read
+        return fail(c, ROVER_E_INVALID, "linear_backward: dy, y (with an activation), x (for dweight) and weight (for dx) must be given");
+    const int64_t max_stride = (int64_t)1 << 40;
+    if (dy_stride < N || dy_stride > max_stride || (activation != 0 && (y_stride < N || y_stride > max_stride)) ||
+        (need_x && (x_stride < K || x_stride > max_stride)) || (need_w && (dx_stride < K || dx_stride > max_stride)))
+        return fail(c, ROVER_E_INVALID, "linear_backward: a row stride is shorter than its row or above 2^40");
+    if (M > 0) {
+        const Span sdy = span_of(dy, dy_stride, M, N, 4), sy = span_of(activation ? y : nullptr, y_stride, M, N, 4),
+                   sx = span_of(need_x ? x : nullptr, x_stride, M, K, 4), sw = span_of(need_w ? weight : nullptr, K, N, K, 4);
+        const Span odx = span_of(need_w ? dx : nullptr, dx_stride, M, K, 4), odw = span_of(need_x ? dweight : nullptr, K, N, K, 4),
+                   odb = span_of(dbias, N, 1, N, 4);
+        const Span outs[3] = {odx, odw, odb};
+        for (int i = 0; i < 3; ++i) {
+            if (!outs[i].lo) continue;
+            for (const Span& in : {sdy, sy, sx, sw})
+                if (in.lo && overlap(outs[i], in)) return fail(c, ROVER_E_INVALID, "linear_backward: an output overlaps an array the call reads");
+            for (int j = i + 1; j < 3; ++j)
+                if (outs[j].lo && overlap(outs[i], outs[j])) return fail(c, ROVER_E_INVALID, "linear_backward: two outputs overlap");
+        }
+    }
+    USE_DEVICE(c);
+    hipStream_t s = (hipStream_t)stream;
+    LinearBwdArgs a{x, x_stride, y, y_stride, dy, dy_stride, weight, dx, dx_stride, dweight, dbias, M, K, N, activation};
+    if (M > 0 && (dweight || dbias))
+        if (int e = mlp_scratch_reserve(c, linear_backward_scratch_floats(r, K, N), s)) return e;
+    HIP_TRY(c, launch_linear_backward(a, r, c->d_mlp_scratch.get(), s));
+    return ROVER_OK;
+}
+
+const char* rover_linear_backward_route(int32_t M, int32_t K, int32_t N, int32_t want_dx) {
+    const LinearBwdRoute r = linear_backward_route(M, K, N, want_dx != 0);
+    if (!r.ok) return nullptr;
+    return M == 0 ? "zero" : linear_backward_route_name(r);
+}
+
+int rover_ppo_loss(rover_ctx* c, const rover_ppo_loss_desc* d, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    if (!d) return fail(c, ROVER_E_INVALID, "ppo_loss: null descriptor");
+    if (d->M < 0 || d->A < 1 || d->A > GAUSS_MAX_A) return fail(c, ROVER_E_INVALID, "ppo_loss: M = %d < 0 or A = %d outside 1 .. %d", d->M, d->A, GAUSS_MAX_A);
+    if (d->reduction != ROVER_REDUCE_SUM) return fail(c, ROVER_E_INVALID, "ppo_loss: the log-prob reduction must be ROVER_REDUCE_SUM (got %d)", d->reduction);
+    if (d->clip_log_std && !(d->min_log_std <= d->max_log_std))
+        return fail(c, ROVER_E_INVALID, "ppo_loss: min_log_std %g > max_log_std %g", (double)d->min_log_std, (double)d->max_log_std);
+    if (!(d->ratio_clip >= 0.0f) || (d->clip_predicted_values && !(d->value_clip >= 0.0f)))
+        return fail(c, ROVER_E_INVALID, "ppo_loss: ratio_clip %g and value_clip %g must be >= 0", (double)d->ratio_clip, (double)d->value_clip);
+    if (d->M == 0) return ROVER_OK;            // nothing to read or write: no pointer is required
+    if (!d->mean || !d->log_std || !d->actions || !d->old_log_prob || !d->advantages || !d->value || !d->old_values || !d->returns || !d->d_mean ||
+        !d->d_value || !d->d_log_std || !d->stats)
+        return fail(c, ROVER_E_INVALID, "ppo_loss: every input, d_mean, d_value, d_log_std and stats must be given");
+    const int64_t max_stride = (int64_t)1 << 40;
+    for (int64_t st : {d->mean_stride, d->actions_stride, d->d_mean_stride})
+        if (st < d->A || st > max_stride) return fail(c, ROVER_E_INVALID, "ppo_loss: a row stride is shorter than its row (A = %d) or above 2^40", d->A);
+    const int32_t M = d->M, A = d->A;
+    const Span ins[8] = {span_of(d->mean, d->mean_stride, M, A, 4), span_of(d->log_std, A, 1, A, 4), span_of(d->actions, d->actions_stride, M, A, 4),
+                         span_of(d->old_log_prob, M, 1, M, 4), span_of(d->advantages, M, 1, M, 4), span_of(d->value, M, 1, M, 4),
+                         span_of(d->old_values, M, 1, M, 4), span_of(d->returns, M, 1, M, 4)};
+    const Span outs[4] = {span_of(d->d_mean, d->d_mean_stride, M, A, 4), span_of(d->d_value, M, 1, M, 4), span_of(d->d_log_std, A, 1, A, 4),
+                          span_of(d->stats, 4, 1, 4, 8)};
+    for (int i = 0; i < 4; ++i) {
+        for (const Span& in : ins)
+            if (overlap(outs[i], in)) return fail(c, ROVER_E_INVALID, "ppo_loss: an output overlaps an array the call reads");
+        for (int j = i + 1; j < 4; ++j)
+            if (overlap(outs[i], outs[j])) return fail(c, ROVER_E_INVALID, "ppo_loss: two outputs overlap");
+    }
+    USE_DEVICE(c);
+    PpoArgs a{};
+    a.M = M; a.A = A; a.mean = d->mean; a.mean_stride = d->mean_stride; a.log_std = d->log_std; a.actions = d->actions; a.actions_stride = d->actions_stride;
+    a.old_log_prob = d->old_log_prob; a.advantages = d->advantages; a.value = d->value; a.old_values = d->old_values; a.returns = d->returns;
+    a.clip_log_std = d->clip_log_std != 0; a.min_log_std = d->min_log_std; a.max_log_std = d->max_log_std;
+    a.ratio_clip = d->ratio_clip; a.value_clip = d->value_clip; a.clip_predicted_values = d->clip_predicted_values != 0;
+    a.entropy_loss_scale = d->entropy_loss_scale; a.value_loss_scale = d->value_loss_scale;
+    a.d_mean = d->d_mean; a.d_mean_stride = d->d_mean_stride; a.d_value = d->d_value; a.d_log_std = d->d_log_std; a.stats = d->stats;
+    a.partials = c->d_ppo_partials.get();
+    HIP_TRY(c, launch_ppo_loss(a, (hipStream_t)stream));
     return ROVER_OK;
 }
 

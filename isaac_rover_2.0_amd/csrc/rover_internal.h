@@ -276,6 +276,43 @@ int gae_launches(const GaeArgs& a);        // 0 (E = 0), 1 (the scan) or 2 (+ th
 hipError_t launch_gae(const GaeArgs& a, hipStream_t s);
 void gae_combine_moments(const double* a, const double* b, double* out);   // host: Chan's update, the one the kernels run
 
+// The backward of one Layer (rover_linear_backward of the C ABI, validated; rover_train.hip): dz = dy act'(y), dx = dz W, dW = dz^T x,
+// db = column sums of dz; every output optional (null).
+struct LinearBwdArgs {
+    const float* x; int64_t x_stride;      // [M, K]
+    const float* y; int64_t y_stride;      // [M, N] the layer's output as the forward wrote it (unused with act 0)
+    const float* dy; int64_t dy_stride;    // [M, N]
+    const float* w;                        // [N][K]
+    float* dx; int64_t dx_stride;          // [M, K]
+    float* dw; float* db;                  // [N][K], [N]
+    int32_t M, K, N, act;
+};
+// what a backward launches: linear_wgrad_kernel<nt, nw> over `splits` cuts of M of rows_per_split rows each (+ the merge when
+// splits > 1), and for dx linear_dgrad_kernel on the forward's route of an M x K output (dx.nw = 0: no dx); ok = false: refused
+struct LinearBwdRoute { bool ok; int nt, nw, splits, rows_per_split; LinearRoute dx; };
+LinearBwdRoute linear_backward_route(int M, int K, int N, bool want_dx);
+const char* linear_backward_route_name(const LinearBwdRoute& r);      // "wgrad<3,4>/64;dgrad<1,4>", or NULL; valid until the thread's next call
+size_t linear_backward_scratch_floats(const LinearBwdRoute& r, int K, int N);
+hipError_t launch_linear_backward(const LinearBwdArgs& a, const LinearBwdRoute& r, float* scratch, hipStream_t s);
+
+// The PPO minibatch loss and its gradients at the nets' outputs (rover_ppo_loss of the C ABI, validated; rover_train.hip)
+constexpr uint32_t PPO_MAX_BLOCKS = 1024;  // most blocks = most partials of 3 + GAUSS_MAX_A doubles: the ctx holds them since rover_create
+struct PpoArgs {
+    int32_t M, A;
+    const float* mean; int64_t mean_stride;
+    const float* log_std;
+    const float* actions; int64_t actions_stride;
+    const float *old_log_prob, *advantages, *value, *old_values, *returns;
+    int32_t clip_log_std; float min_log_std, max_log_std;
+    float ratio_clip, value_clip; int32_t clip_predicted_values;
+    float entropy_loss_scale, value_loss_scale;
+    float* d_mean; int64_t d_mean_stride;
+    float *d_value, *d_log_std;
+    double* stats;                         // [4] policy_loss, value_loss, entropy_loss, kl
+    double* partials;                      // [PPO_MAX_BLOCKS][3 + GAUSS_MAX_A], the ctx's
+};
+hipError_t launch_ppo_loss(const PpoArgs& a, hipStream_t s);
+
 // blocks of bs threads (or items) that cover n: the launchers' grid sizes
 static inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
 

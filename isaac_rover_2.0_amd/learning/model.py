@@ -15,9 +15,13 @@ noise keyed by (seed, call counter, GLOBAL row), so a shard draws its slice of t
 Nets that fit the library's chain kernels run each encoder and the MLP + head as ONE fused kernel each (``rover_mlp_chain_forward``,
 f32 MFMA, activations kept in registers between the layers); otherwise every ``Layer`` is one ``rover_linear_forward`` launch.  Which
 it is, the library says (``HeightmapNet._plan``); this file holds no width or row limit.  The slices are read in place from ``obs_buf``
-and the encoder outputs are written straight into the concat buffer, so there is no ``torch.cat``.  Training (skrl PPO,
-``train.py``) stays out of scope: these classes hold plain tensors, initialised like ``nn.Linear``, and can load a
-``state_dict`` saved from the reference's modules (same parameter names).
+and the encoder outputs are written straight into the concat buffer, so there is no ``torch.cat``.  These classes hold plain
+tensors, initialised like ``nn.Linear``, and can load a ``state_dict`` saved from the reference's modules (same parameter names).
+
+Training: autograd cannot see the kernels, so ``backward(d_out)`` walks an UNFUSED forward back layer by layer with
+``rover_linear_backward`` and leaves every parameter's gradient in its ``.grad``; ``parameters()`` hands the tensors to a torch
+optimiser.  The PPO loss at the outputs and the update loop (skrl's ``PPO._update``) live in ``learning/ppo.py``.  The backward of
+the fused chain kernels is not built.
 """
 from __future__ import annotations
 
@@ -73,6 +77,7 @@ class HeightmapNet:
         # :183 — only the stochastic actor owns a log-std parameter (DeterministicHeightmap has none, :197-241)
         self.log_std_parameter = torch.zeros(num_outputs, device=device) if head_activation == "tanh" else None
         self._bufs, self._plans = {}, {}
+        self._fwd = {}                         # rows -> (states, ForwardPlan) of the last forward of that batch size (backward())
         # act()'s call counter, in device memory so that a captured graph draws fresh noise on every replay: read by the head's kernel,
         # advanced by act() on the same stream right after it (eager and captured alike)
         self._act_counter = torch.zeros(1, dtype=torch.int64, device=device)
@@ -118,6 +123,7 @@ class HeightmapNet:
         """Both encoders and the proprioception columns into the concat buffer -> (cat, whether the MLP + head runs as one chain kernel)."""
         e = states.shape[0]
         plan = self._plan(e, fused is None or bool(fused))
+        self._fwd[e] = (states, plan)
         p, ns, nd = self.num_proprioception, self.num_sparse, self.num_dense
         ef = self.encoder0[-1].weight.shape[0]
         cat = self._buf("cat", e, p + 2 * ef)
@@ -191,6 +197,51 @@ class HeightmapNet:
     def get_entropy(self, role=""):
         """Normal's entropy per component, 0.5 + 0.5 log(2 pi) + log_std', as [rows of the last act(), A]."""
         return 0.5 + 0.5 * math.log(2.0 * math.pi) + self.get_log_std(role)
+
+    # ---- training: parameters and the layer-by-layer backward ---------------------------------------------------
+    def parameters(self):
+        """The parameter tensors in ``state_dict()`` order (what ``torch.optim.Adam`` and ``clip_grad_norm_`` take)."""
+        return list(self.state_dict().values())
+
+    @staticmethod
+    def _grad_of(p):
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+        return p.grad
+
+    def backward(self, d_out):
+        """``d_out`` [E, num_outputs]: the loss gradient at compute()'s output of the last forward of E rows, which must have run with
+        ``fused=False`` (it leaves every layer's output in the net's buffers).  Walks the MLP and both encoders back with
+        ``Engine.linear_backward`` and overwrites ``weight.grad`` / ``bias.grad`` of every layer (kept tensors, created on first use).
+        The encoders' dy are the column slices of d cat, read in place; the first encoder layers compute no dx.  The actor's
+        ``log_std_parameter.grad`` is ``Engine.ppo_loss``'s d_log_std, not written here.  Enqueues only."""
+        e = d_out.shape[0]
+        if e not in self._fwd:
+            raise RuntimeError(f"backward: no forward of {e} rows has run")
+        states, plan = self._fwd[e]
+        if plan.pair or plan.enc0 or plan.enc1 or plan.mlp:
+            raise RuntimeError(f"backward: the last forward of {e} rows ran fused chain kernels, which keep no layer outputs: run it with fused=False")
+        eng, g = self.engine, self._grad_of
+        p, ns, nd = self.num_proprioception, self.num_sparse, self.num_dense
+        ef = self.encoder0[-1].weight.shape[0]
+        cat = self._bufs["cat"]
+        dy = d_out
+        for li in range(len(self.network) - 1, -1, -1):
+            layer = self.network[li]
+            x = cat if li == 0 else self._bufs[("mlp", li - 1)]
+            dx = self._buf(("d_mlp", li), e, x.shape[1])
+            eng.linear_backward(x, self._bufs[("mlp", li)], dy, layer.weight, layer.activation, dx=dx, dweight=g(layer.weight), dbias=g(layer.bias))
+            dy = dx
+        d_cat = dy
+        for enc, lo, n, col in ((self.encoder0, p, ns, p), (self.encoder1, p + ns, nd, p + ef)):
+            dy = d_cat[:, col:col + ef]
+            for li in range(len(enc) - 1, -1, -1):
+                layer = enc[li]
+                y = cat[:, col:col + ef] if li == len(enc) - 1 else self._bufs[("enc", col, li)]
+                x = states[:, lo:lo + n] if li == 0 else self._bufs[("enc", col, li - 1)]
+                dx = None if li == 0 else self._buf(("d_enc", col, li), e, x.shape[1])
+                eng.linear_backward(x, y, dy, layer.weight, layer.activation, dx=dx, dweight=g(layer.weight), dbias=g(layer.bias))
+                dy = dx
 
     # ---- interop with the reference's nn.Module parameter names --------------------------------------------
     def state_dict(self):

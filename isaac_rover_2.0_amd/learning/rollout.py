@@ -5,7 +5,7 @@ mini_batches: 60, discount_factor: 0.99, lambda: 0.95`` (``cfg/trainSKRL/RoverPP
 ``compute_gae``.  ``RolloutMemory`` is the subset of skrl's ``Memory`` that PPO uses, ``compute_gae`` runs the whole recursion, the moments
 and the normalisation as ``Engine.gae`` (``rover_gae``: one or two launches) on the stored tensors in place.  The semantics are restated from
 a reading of skrl 0.10 / 1.x (skrl is no dependency of this package) and written out in ``include/rover_step.h``; the weight update
-itself stays out of scope.
+that consumes ``returns`` and ``advantages`` is ``learning/ppo.py``.
 
 Time-limit bootstrapping (skrl's ``rewards += discount_factor * values * truncated`` in ``record_transition``) is one elementwise line
 before ``add_samples`` and no part of the kernel.
