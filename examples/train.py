@@ -31,6 +31,9 @@ def main():
     ap.add_argument("--epochs", type=int, default=4, help="learning_epochs")
     ap.add_argument("--mini-batches", type=int, default=60, help="mini_batches")
     ap.add_argument("--kl-threshold", type=float, default=0.008)
+    ap.add_argument("--native-step", action="store_true", help="gradient-norm clip + Adam as two HIP launches (learning/optim.py) instead of torch's")
+    ap.add_argument("--kl-stop", choices=("host", "device"), default="host",
+                    help="where the KL early stop is decided: host = one read per minibatch; device = by the native step's gate (needs --native-step)")
     ap.add_argument("--time-update", action="store_true", help="print the wall time of each update between two torch.cuda.synchronize()")
     args = ap.parse_args()
     if args.rollouts < 1:
@@ -62,7 +65,7 @@ def main():
                               ("returns", 1, torch.float32), ("advantages", 1, torch.float32)):
         memory.create_tensor(name, size, dtype)
     ppo = PPO(task._engine, agent, critic, memory, {"learning_epochs": args.epochs, "mini_batches": args.mini_batches, "kl_threshold": args.kl_threshold},
-              generator=torch.Generator().manual_seed(0))
+              generator=torch.Generator().manual_seed(0), native_step=args.native_step, kl_stop=args.kl_stop)
     updates = 0
     for _ in range(args.steps):
         actions, log_prob, _ = agent.act(obs)

@@ -541,6 +541,78 @@ typedef struct {
 } rover_ppo_loss_desc;
 ROVER_API int rover_ppo_loss(rover_ctx *ctx, const rover_ppo_loss_desc *d, void *stream);
 
+/* ---- the optimiser step: gradient-norm clip + Adam over a list of tensors, with the KL early stop decided on the device ------------ */
+/* torch.nn.utils.clip_grad_norm_(params, clip) followed by torch.optim.Adam.step() (no weight decay, no amsgrad, one step counter for
+ * all tensors) over n_tensors f32 tensors in two launches, restated from a reading of torch 2.x; this is the project's definition.
+ *
+ * rover_optim_plan — host only, no ctx, no device, a pure function: the chunks both kernels walk, one workgroup per chunk.  The tensors
+ * are cut in tensor order, then element order, into chunks of one fixed length (a constant of the library, csrc/rover_internal.h
+ * OPTIM_CHUNK; callers read it off the plan of one long tensor and never assume a value); the last chunk of a tensor is shorter, a
+ * tensor of numel 0 yields no chunk.  *n_chunks (required) receives the count; chunks (optional) receives the records when capacity
+ * >= the count.  ROVER_E_INVALID (rover_last_error(NULL)): numel or n_chunks NULL, n_tensors outside 1 .. 256, a negative numel, total
+ * elements >= 2^31, chunks given with capacity < the count (or capacity < 0). */
+typedef struct { int32_t tensor, first, length; } rover_optim_chunk;      /* elements [first, first + length) of tensor `tensor` */
+ROVER_API int rover_optim_plan(int32_t n_tensors, const int64_t *numel, rover_optim_chunk *chunks, int64_t capacity, int64_t *n_chunks);
+
+/* rover_optim_create: binds a tensor list and its state to a handle of the ctx.  params / grads / numel are HOST arrays of n_tensors
+ * entries (device pointers to contiguous f32 tensors, 4-byte aligned; a pointer may be NULL where numel is 0); they are read during
+ * the call only.  The state belongs to the CALLER, lives on the device and must outlive the handle: exp_avg and exp_avg_sq (flat,
+ * sum(numel) floats each, tensor i at offset numel[0] + .. + numel[i-1]; zeroed by the caller before the first step), step (one
+ * int64: Adam's step count, 0 at first) and stopped (one int32 latch, 0 = open).  The ctx owns only the device chunk table, one f64
+ * partial per chunk and a 16-byte record per handle, all allocated HERE (never in the step) and freed by rover_optim_destroy or by
+ * rover_destroy.  *handle >= 0.  A destroyed handle's number may be given out again.
+ * ROVER_E_INVALID before anything is allocated: a NULL descriptor / handle / array, n_tensors outside 1 .. 256, a negative numel,
+ * total elements >= 2^31, a NULL or misaligned params[i] / grads[i] with numel[i] > 0, NULL exp_avg / exp_avg_sq with total > 0, NULL
+ * step / stopped, a parameter overlapping its own or another tensor's gradient, another parameter, exp_avg, exp_avg_sq, step or
+ * stopped; a gradient overlapping exp_avg, exp_avg_sq, step or stopped; exp_avg, exp_avg_sq, step and stopped overlapping each other.
+ * (Two gradients may overlap: they are only read.)  rover_optim_destroy: ROVER_E_INVALID for a handle that is not live. */
+typedef struct {
+    int32_t n_tensors;
+    float *const *params;         /* host [n_tensors] of device pointers */
+    const float *const *grads;    /* host [n_tensors] of device pointers */
+    const int64_t *numel;         /* host [n_tensors]                    */
+    float *exp_avg, *exp_avg_sq;  /* device, sum(numel) floats each      */
+    int64_t *step;                /* device [1]                          */
+    int32_t *stopped;             /* device [1]                          */
+} rover_optim_desc;
+ROVER_API int rover_optim_create(rover_ctx *ctx, const rover_optim_desc *d, int32_t *handle);
+ROVER_API int rover_optim_destroy(rover_ctx *ctx, int32_t handle);
+
+/* rover_optim_step: one gated step.  Exactly two launches; the call allocates nothing, does not synchronise and can be captured in a
+ * graph.  One stream per ctx at a time, like rover_ppo_loss.  gate (optional, device double[1], e.g. stats + 3 of rover_ppo_loss) and
+ * norm_out (optional, device double[1]) are read / written by the kernels when they run.
+ * Launch 1, prepare: one workgroup of 256 threads per chunk sums g*g in f64 (exact products; per thread in element order, then a
+ *   fixed tree over the lanes, then the waves in order) and stores its partial.  Workgroup 0 evaluates the gate:
+ *       if *stopped != 0, or gate is given and *gate > gate_threshold:  *stopped = 1        (a plain >: a NaN gate does not stop,
+ *       else:                                                           *step += 1           as float(kl) > threshold on the host)
+ *   and leaves the decision and the step count now in force in the handle's record.
+ * Launch 2, apply: every workgroup reads the record and returns if stopped: parameters, exp_avg, exp_avg_sq, step and norm_out are
+ *   then bit-unchanged.  Otherwise it adds the partials in chunk order (thread i takes i, i + 256, ..., then a fixed tree: the same
+ *   order in every workgroup, as rover_gae's finishing kernel merges) and forms in f64, with t = *step after the increment:
+ *       norm = sqrt(sum)        coef = grad_norm_clip > 0 ? min(1, grad_norm_clip / (norm + 1e-6)) : 1        (a NaN stays a NaN)
+ *       bc1 = 1 - beta1^t       bc2 = 1 - beta2^t       (powers by repeated squaring)
+ *   rounds coef, 1 - beta1, beta2, 1 - beta2, lr / bc1, sqrt(bc2) and eps to f32 ONCE and updates every element in f32, one rounding
+ *   per written operation, in this order:
+ *       g' = g * coef
+ *       m  = m + (g' - m) * (1 - beta1)
+ *       v  = beta2 * v + ((1 - beta2) * g') * g'
+ *       p  = p - (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps))
+ *   norm_out receives norm, the total gradient norm BEFORE clipping.
+ * Gradients are READ ONLY: unlike torch's clip_grad_norm_, the clipped gradient g' is not written back.  NaN and Inf propagate as the
+ * formulas say.  No floating-point atomics: the same inputs give the same bits on every run, whatever the alignment of the tensors
+ * (16-byte loads and stores where a tensor's bases allow, scalar ones otherwise, the same arithmetic in the same order).
+ * ROVER_E_INVALID before any launch: a NULL descriptor, a handle that is not live, lr < 0 or not finite, beta1 / beta2 outside [0, 1),
+ * eps < 0 or not finite, a NaN grad_norm_clip or gate_threshold, gate or norm_out not 8-byte aligned, norm_out overlapping gate, a
+ * parameter, a gradient, exp_avg, exp_avg_sq, step or stopped. */
+typedef struct {
+    double lr, beta1, beta2, eps;
+    double grad_norm_clip;        /* <= 0: no clipping                                                          */
+    const double *gate;           /* optional device [1]                                                        */
+    double gate_threshold;
+    double *norm_out;             /* optional device [1]                                                        */
+} rover_optim_step_desc;
+ROVER_API int rover_optim_step(rover_ctx *ctx, int32_t handle, const rover_optim_step_desc *d, void *stream);
+
 /* ---- tuning knobs ------------------------------------------------------------------------------------- */
 /* name = "raycast_variant": 0 = auto; 1 = one half-wave per ray in env order, every cell block streamed from HBM;
  *        2 = rays counting-sorted by (map, cell), one wave per run of sorted rays, the cell's triangles held in registers

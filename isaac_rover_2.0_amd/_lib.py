@@ -112,6 +112,21 @@ class PpoLossDesc(C.Structure):
                 ("value_loss_scale", C.c_float), ("d_mean", C.c_void_p), ("d_mean_stride", C.c_int64), ("d_value", C.c_void_p),
                 ("d_log_std", C.c_void_p), ("stats", C.c_void_p)]
 
+
+class OptimChunk(C.Structure):
+    _fields_ = [("tensor", C.c_int32), ("first", C.c_int32), ("length", C.c_int32)]
+
+
+class OptimDesc(C.Structure):
+    _fields_ = [("n_tensors", C.c_int32), ("params", C.c_void_p), ("grads", C.c_void_p), ("numel", C.c_void_p), ("exp_avg", C.c_void_p),
+                ("exp_avg_sq", C.c_void_p), ("step", C.c_void_p), ("stopped", C.c_void_p)]
+
+
+class OptimStepDesc(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("grad_norm_clip", C.c_double),
+                ("gate", C.c_void_p), ("gate_threshold", C.c_double), ("norm_out", C.c_void_p)]
+
+
 REDUCTIONS = {"sum": 0, "mean": 1, "prod": 2, "max": 3, "min": 4, None: 5, "none": 5}
 
 
@@ -182,6 +197,10 @@ SYMBOLS = {
                                         _P, _P, _P]),
     "rover_linear_backward_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rover_ppo_loss": (C.c_int, [_P, C.POINTER(PpoLossDesc), _P]),
+    "rover_optim_plan": (C.c_int, [C.c_int32, _P, _P, C.c_int64, _P]),
+    "rover_optim_create": (C.c_int, [_P, C.POINTER(OptimDesc), _P]),
+    "rover_optim_destroy": (C.c_int, [_P, C.c_int32]),
+    "rover_optim_step": (C.c_int, [_P, C.c_int32, C.POINTER(OptimStepDesc), _P]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
     "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
     "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -859,6 +878,68 @@ class Engine:
                         max(d_mean.stride(0), a), d_value.data_ptr(), d_log_std.data_ptr(), stats.data_ptr())
         self._check(self.lib.rover_ppo_loss(self._h, C.byref(d), _stream(self._dev_index)), "rover_ppo_loss")
         return stats
+
+    # ---- the optimiser step (rover_optim_*) ---------------------------------------------------------------
+    @classmethod
+    def optim_plan(cls, numel):
+        """rover_optim_plan: the chunks the optimiser kernels walk for tensors of ``numel`` elements -> [(tensor, first, length)], in
+        tensor order then element order.  Host only: no ctx, no device.  The chunk length is the library's constant: read it off the
+        plan of one long tensor."""
+        sizes = [int(v) for v in numel]
+        arr = (C.c_int64 * max(len(sizes), 1))(*sizes)
+        lib, n = load(), C.c_int64(0)
+        rc = lib.rover_optim_plan(len(sizes), arr, None, 0, C.byref(n))
+        if rc == 0:
+            chunks = (OptimChunk * max(n.value, 1))()
+            rc = lib.rover_optim_plan(len(sizes), arr, chunks, n.value, C.byref(n))
+        if rc != 0:
+            raise RoverError(f"rover_optim_plan failed ({rc}): {lib.rover_last_error(None).decode()}")
+        return [(int(c.tensor), int(c.first), int(c.length)) for c in chunks[:n.value]]
+
+    def _optim_word(self, t, name, dtype, what):
+        if t is None or not t.is_cuda or t.device != self.device or t.dtype != dtype or t.numel() != 1:
+            raise RoverError(f"{what}: {name} must be one {dtype} word on {self.device}")
+        return t.data_ptr()
+
+    def optim_create(self, params, grads, exp_avg, exp_avg_sq, step, stopped):
+        """rover_optim_create: binds contiguous float32 ``params`` and their ``grads`` (two lists of GPU tensors, pairwise of one shape;
+        empty tensors are allowed) to the caller's state — ``exp_avg`` / ``exp_avg_sq``: flat float32 of sum(numel) elements in tensor
+        order, zeroed; ``step``: one int64; ``stopped``: one int32 — and returns the handle.  Every tensor must stay alive, and stay
+        the same storage, as long as the handle is used."""
+        what = "optim_create"
+        params, grads = list(params), list(grads)
+        if len(params) != len(grads):
+            raise RoverError(f"{what}: {len(params)} params but {len(grads)} grads")
+        for i, (p, g) in enumerate(zip(params, grads)):
+            self._chk(p, tuple(p.shape), torch.float32, f"params[{i}]")
+            self._chk(g, tuple(p.shape), torch.float32, f"grads[{i}]")
+        n = len(params)
+        numel = [p.numel() for p in params]
+        total = sum(numel)
+        self._chk(exp_avg, (total,), torch.float32, "exp_avg")
+        self._chk(exp_avg_sq, (total,), torch.float32, "exp_avg_sq")
+        ptrs = lambda ts: (C.c_void_p * max(n, 1))(*[t.data_ptr() if t.numel() else None for t in ts])
+        pa, ga, na = ptrs(params), ptrs(grads), (C.c_int64 * max(n, 1))(*numel)
+        d = OptimDesc(n, C.cast(pa, C.c_void_p), C.cast(ga, C.c_void_p), C.cast(na, C.c_void_p), exp_avg.data_ptr() if total else None,
+                      exp_avg_sq.data_ptr() if total else None, self._optim_word(step, "step", torch.int64, what),
+                      self._optim_word(stopped, "stopped", torch.int32, what))
+        h = C.c_int32(-1)
+        self._check(self.lib.rover_optim_create(self._h, C.byref(d), C.byref(h)), "rover_optim_create")
+        return int(h.value)
+
+    def optim_destroy(self, handle):
+        self._check(self.lib.rover_optim_destroy(self._h, int(handle)), "rover_optim_destroy")
+
+    def optim_step(self, handle, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_norm_clip=0.0, gate=None, gate_threshold=0.0, norm_out=None):
+        """rover_optim_step: clip_grad_norm_ (``grad_norm_clip`` <= 0: none) and one Adam step over the handle's tensors in two launches.
+        ``gate`` (one float64 on the device, e.g. ``stats[3:]`` of ppo_loss): the step is skipped, and the handle's ``stopped`` latch
+        set, when the latch is set already or ``gate > gate_threshold``.  ``norm_out`` (one float64 on the device) receives the
+        gradient norm before clipping.  Enqueues only; capturable."""
+        what = "optim_step"
+        d = OptimStepDesc(float(lr), float(beta1), float(beta2), float(eps), float(grad_norm_clip),
+                          None if gate is None else self._optim_word(gate, "gate", torch.float64, what), float(gate_threshold),
+                          None if norm_out is None else self._optim_word(norm_out, "norm_out", torch.float64, what))
+        self._check(self.lib.rover_optim_step(self._h, int(handle), C.byref(d), _stream(self._dev_index)), "rover_optim_step")
 
     @classmethod
     def linear_backward_route(cls, m, k, n, want_dx):

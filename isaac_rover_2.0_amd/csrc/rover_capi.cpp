@@ -83,6 +83,21 @@ struct CullQueue {
     StepPlan counters_written_under{};  // the plan the counters were last written under (run_raycast)
 };
 
+struct Span { uintptr_t lo, hi; };      // the bytes [lo, hi) of an array (span_of, overlap)
+
+// One rover_optim_create: the ctx owns the chunk table, the partials and the record; the tensors and the state are the caller's
+struct OptimHandle {
+    bool live = false;
+    DevBuf<OptimChunk> chunks;          // [n_chunks] (optim_plan's chunks with their addresses)
+    DevBuf<double> partials;            // [n_chunks] sums of g*g
+    DevBuf<OptimRecord> record;         // [1] what the prepare launch leaves for the apply launch
+    uint32_t n_chunks = 0;
+    float *exp_avg = nullptr, *exp_avg_sq = nullptr;
+    int64_t* step = nullptr;
+    int32_t* stopped = nullptr;
+    std::vector<Span> spans;            // everything the step reads or writes through the handle (norm_out must stay clear of it)
+};
+
 struct rover_ctx {
     rover_cfg cfg{};
     std::string err;
@@ -126,6 +141,7 @@ struct rover_ctx {
     DevBuf<float> d_mlp_scratch;        // partial sums of the split-k small-batch encoder path (rover_mlp_chain_forward)
     DevBuf<double> d_gae_partials;      // [GAE_MAX_BLOCKS][3] per-block (count, mean, M2) of rover_gae, sized once at rover_create
     DevBuf<double> d_ppo_partials;      // [PPO_MAX_BLOCKS][3 + GAUSS_MAX_A] per-block sums of rover_ppo_loss, sized once at rover_create
+    std::vector<OptimHandle> optims;    // rover_optim_create's handles, by number (a destroyed one's slot is given out again)
     uint64_t workspace_bytes = 0;
     bool ws_ok = false, bins_ok = false;   // false after a failed (re)allocation: the step entry points refuse to run
     bool rays_valid = false;            // the ray workspace holds a finished ray cast (rover_replay_raycast)
@@ -1619,8 +1635,7 @@ const char* rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, c
 }
 
 // ---- rollout: GAE ----
-// the bytes [lo, hi) a [T, E] array of `size`-byte elements at a time stride covers
-struct Span { uintptr_t lo, hi; };
+// the bytes [lo, hi) a [T, E] array of `size`-byte elements at a time stride covers (Span: above rover_ctx)
 static Span span_of(const void* p, int64_t stride, int32_t T, int32_t E, size_t size) {
     return Span{(uintptr_t)p, (uintptr_t)p + ((uint64_t)(T - 1) * (uint64_t)stride + (uint64_t)E) * size};
 }
@@ -1752,6 +1767,144 @@ int rover_ppo_loss(rover_ctx* c, const rover_ppo_loss_desc* d, void* stream) {
     a.d_mean = d->d_mean; a.d_mean_stride = d->d_mean_stride; a.d_value = d->d_value; a.d_log_std = d->d_log_std; a.stats = d->stats;
     a.partials = c->d_ppo_partials.get();
     HIP_TRY(c, launch_ppo_loss(a, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+// ---- training: gradient-norm clip + Adam ----
+// shared by rover_optim_plan and rover_optim_create: NULL when the sizes are acceptable, else what is wrong; *total = sum(numel)
+static const char* optim_sizes_refused(int32_t n_tensors, const int64_t* numel, int64_t* total) {
+    if (!numel) return "numel is NULL";
+    if (n_tensors < 1 || n_tensors > 256) return "n_tensors outside 1 .. 256";
+    int64_t sum = 0;
+    for (int32_t i = 0; i < n_tensors; ++i) {
+        if (numel[i] < 0) return "a negative numel";
+        if (numel[i] >= (int64_t)1 << 31 || (sum += numel[i]) >= (int64_t)1 << 31) return "total elements >= 2^31";
+    }
+    *total = sum;
+    return nullptr;
+}
+
+int rover_optim_plan(int32_t n_tensors, const int64_t* numel, rover_optim_chunk* chunks, int64_t capacity, int64_t* n_chunks) {
+    int64_t total = 0;
+    if (const char* why = optim_sizes_refused(n_tensors, numel, &total)) return fail(nullptr, ROVER_E_INVALID, "optim_plan: %s", why);
+    if (!n_chunks) return fail(nullptr, ROVER_E_INVALID, "optim_plan: n_chunks is NULL");
+    const int64_t n = optim_plan(n_tensors, numel, nullptr, 0);
+    if (capacity < 0 || (chunks && capacity < n)) return fail(nullptr, ROVER_E_INVALID, "optim_plan: capacity %lld < %lld chunks", (long long)capacity, (long long)n);
+    static_assert(sizeof(rover_optim_chunk) == sizeof(OptimChunkHost), "rover_optim_chunk is OptimChunkHost");
+    if (chunks) (void)optim_plan(n_tensors, numel, reinterpret_cast<OptimChunkHost*>(chunks), capacity);
+    *n_chunks = n;
+    return ROVER_OK;
+}
+
+int rover_optim_create(rover_ctx* c, const rover_optim_desc* d, int32_t* handle) {
+    if (!c) return ROVER_E_INVALID;
+    if (!d || !handle || !d->params || !d->grads) return fail(c, ROVER_E_INVALID, "optim_create: null descriptor, handle, params or grads");
+    int64_t total = 0;
+    if (const char* why = optim_sizes_refused(d->n_tensors, d->numel, &total)) return fail(c, ROVER_E_INVALID, "optim_create: %s", why);
+    if (!d->step || !d->stopped || (total > 0 && (!d->exp_avg || !d->exp_avg_sq)))
+        return fail(c, ROVER_E_INVALID, "optim_create: exp_avg, exp_avg_sq, step and stopped must be given");
+    if ((uintptr_t)d->exp_avg % 4 || (uintptr_t)d->exp_avg_sq % 4 || (uintptr_t)d->step % 8 || (uintptr_t)d->stopped % 4)
+        return fail(c, ROVER_E_INVALID, "optim_create: exp_avg, exp_avg_sq, step or stopped is misaligned");
+    const int32_t n = d->n_tensors;
+    std::vector<Span> ps, gs;           // the tensors with elements
+    for (int32_t i = 0; i < n; ++i) {
+        if (d->numel[i] == 0) continue;
+        if (!d->params[i] || !d->grads[i] || (uintptr_t)d->params[i] % 4 || (uintptr_t)d->grads[i] % 4)
+            return fail(c, ROVER_E_INVALID, "optim_create: params[%d] or grads[%d] is NULL or misaligned", i, i);
+        ps.push_back(span_of(d->params[i], d->numel[i], 1, (int32_t)d->numel[i], 4));
+        gs.push_back(span_of(d->grads[i], d->numel[i], 1, (int32_t)d->numel[i], 4));
+    }
+    std::vector<Span> state = {span_of(d->step, 1, 1, 1, 8), span_of(d->stopped, 1, 1, 1, 4)};
+    if (total > 0) {
+        state.push_back(span_of(d->exp_avg, total, 1, (int32_t)total, 4));
+        state.push_back(span_of(d->exp_avg_sq, total, 1, (int32_t)total, 4));
+    }
+    for (size_t i = 0; i < state.size(); ++i)
+        for (size_t j = i + 1; j < state.size(); ++j)
+            if (overlap(state[i], state[j])) return fail(c, ROVER_E_INVALID, "optim_create: exp_avg, exp_avg_sq, step and stopped must not overlap each other");
+    for (size_t i = 0; i < ps.size(); ++i) {
+        for (const Span& s : state)
+            if (overlap(ps[i], s) || overlap(gs[i], s)) return fail(c, ROVER_E_INVALID, "optim_create: a parameter or a gradient overlaps the state");
+        for (size_t j = 0; j < ps.size(); ++j)
+            if (overlap(ps[i], gs[j]) || (j > i && overlap(ps[i], ps[j])))
+                return fail(c, ROVER_E_INVALID, "optim_create: a parameter overlaps a gradient or another parameter");
+    }
+    USE_DEVICE(c);
+    const int64_t n_chunks = optim_plan(n, d->numel, nullptr, 0);
+    std::vector<OptimChunkHost> plan((size_t)n_chunks);
+    (void)optim_plan(n, d->numel, plan.data(), n_chunks);
+    std::vector<int64_t> offset((size_t)n, 0);                 // of tensor i in the flat state
+    for (int32_t i = 1; i < n; ++i) offset[i] = offset[i - 1] + d->numel[i - 1];
+    const bool state_al = ((uintptr_t)d->exp_avg | (uintptr_t)d->exp_avg_sq) % 16 == 0;
+    std::vector<OptimChunk> table((size_t)n_chunks);
+    for (int64_t k = 0; k < n_chunks; ++k) {
+        const OptimChunkHost& h = plan[(size_t)k];
+        OptimChunk& o = table[(size_t)k];
+        o.p = d->params[h.tensor] + h.first;
+        o.g = d->grads[h.tensor] + h.first;
+        o.state = (uint32_t)(offset[h.tensor] + h.first);
+        o.len = (uint32_t)h.length;
+        o.flags = (((uintptr_t)d->params[h.tensor] | (uintptr_t)d->grads[h.tensor]) % 16 == 0 ? OPTIM_PG_ALIGNED : 0) |
+                  (state_al && offset[h.tensor] % 4 == 0 ? OPTIM_STATE_ALIGNED : 0);
+        o.pad = 0;
+    }
+    OptimHandle h;
+    hipError_t e = h.record.alloc(1);
+    if (e == hipSuccess && n_chunks > 0) e = h.chunks.alloc((size_t)n_chunks);
+    if (e == hipSuccess && n_chunks > 0) e = h.partials.alloc((size_t)n_chunks);
+    if (e == hipSuccess && n_chunks > 0) e = hipMemcpy(h.chunks.get(), table.data(), table.size() * sizeof(OptimChunk), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(h.record.get(), 0, sizeof(OptimRecord));
+    if (e != hipSuccess) return fail(c, ROVER_E_HIP, "optim_create: %s", hipGetErrorString(e));
+    h.live = true;
+    h.n_chunks = (uint32_t)n_chunks;
+    h.exp_avg = d->exp_avg; h.exp_avg_sq = d->exp_avg_sq; h.step = d->step; h.stopped = d->stopped;
+    h.spans = state;
+    h.spans.insert(h.spans.end(), ps.begin(), ps.end());
+    h.spans.insert(h.spans.end(), gs.begin(), gs.end());
+    size_t slot = 0;
+    while (slot < c->optims.size() && c->optims[slot].live) ++slot;
+    if (slot == c->optims.size()) c->optims.emplace_back();
+    c->optims[slot] = std::move(h);
+    *handle = (int32_t)slot;
+    return ROVER_OK;
+}
+
+static OptimHandle* optim_handle(rover_ctx* c, int32_t handle) {
+    return handle >= 0 && (size_t)handle < c->optims.size() && c->optims[(size_t)handle].live ? &c->optims[(size_t)handle] : nullptr;
+}
+
+int rover_optim_destroy(rover_ctx* c, int32_t handle) {
+    if (!c) return ROVER_E_INVALID;
+    OptimHandle* h = optim_handle(c, handle);
+    if (!h) return fail(c, ROVER_E_INVALID, "optim_destroy: handle %d is not live", handle);
+    USE_DEVICE(c);
+    *h = OptimHandle{};                 // (the owners free their device memory)
+    return ROVER_OK;
+}
+
+int rover_optim_step(rover_ctx* c, int32_t handle, const rover_optim_step_desc* d, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    if (!d) return fail(c, ROVER_E_INVALID, "optim_step: null descriptor");
+    const OptimHandle* h = optim_handle(c, handle);
+    if (!h) return fail(c, ROVER_E_INVALID, "optim_step: handle %d is not live", handle);
+    if (!(d->lr >= 0.0) || !std::isfinite(d->lr) || !(d->beta1 >= 0.0 && d->beta1 < 1.0) || !(d->beta2 >= 0.0 && d->beta2 < 1.0) ||
+        !(d->eps >= 0.0) || !std::isfinite(d->eps))
+        return fail(c, ROVER_E_INVALID, "optim_step: lr %g and eps %g must be finite and >= 0, beta1 %g and beta2 %g in [0, 1)", d->lr, d->eps, d->beta1, d->beta2);
+    if (std::isnan(d->grad_norm_clip) || std::isnan(d->gate_threshold)) return fail(c, ROVER_E_INVALID, "optim_step: grad_norm_clip or gate_threshold is NaN");
+    if ((uintptr_t)d->gate % 8 || (uintptr_t)d->norm_out % 8) return fail(c, ROVER_E_INVALID, "optim_step: gate or norm_out is not 8-byte aligned");
+    if (d->norm_out) {
+        const Span out = span_of(d->norm_out, 1, 1, 1, 8);
+        if (d->gate && overlap(out, span_of(d->gate, 1, 1, 1, 8))) return fail(c, ROVER_E_INVALID, "optim_step: norm_out overlaps gate");
+        for (const Span& s : h->spans)
+            if (overlap(out, s)) return fail(c, ROVER_E_INVALID, "optim_step: norm_out overlaps a parameter, a gradient or the state");
+    }
+    USE_DEVICE(c);
+    OptimArgs a{};
+    a.chunks = h->chunks.get(); a.n_chunks = h->n_chunks; a.partials = h->partials.get(); a.record = h->record.get();
+    a.exp_avg = h->exp_avg; a.exp_avg_sq = h->exp_avg_sq; a.step = h->step; a.stopped = h->stopped;
+    a.lr = d->lr; a.beta1 = d->beta1; a.beta2 = d->beta2; a.eps = d->eps; a.clip = d->grad_norm_clip;
+    a.gate = d->gate; a.gate_threshold = d->gate_threshold; a.norm_out = d->norm_out;
+    HIP_TRY(c, launch_optim_step(a, (hipStream_t)stream));
     return ROVER_OK;
 }
 

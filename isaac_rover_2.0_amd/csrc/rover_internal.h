@@ -313,6 +313,32 @@ struct PpoArgs {
 };
 hipError_t launch_ppo_loss(const PpoArgs& a, hipStream_t s);
 
+// Gradient-norm clip + Adam over a list of tensors (rover_optim_* of the C ABI, validated; rover_optim.hip)
+constexpr uint32_t OPTIM_CHUNK = 1024;     // elements of one chunk = of one workgroup: THE chunk length (optim_plan, both kernels)
+struct OptimChunkHost { int32_t tensor, first, length; };
+// the chunks of tensors of numel[i] elements in tensor order, then element order; a tensor of 0 elements yields none.  -> the count;
+// writes at most `capacity` records (out may be NULL with capacity 0).  Host only, no device.
+int64_t optim_plan(int32_t n_tensors, const int64_t* numel, OptimChunkHost* out, int64_t capacity);
+enum OptimChunkFlags { OPTIM_PG_ALIGNED = 1, OPTIM_STATE_ALIGNED = 2 };      // 16-byte loads / stores of (p, g) and of (m, v)
+struct OptimChunk {                        // the device table's record (32 B)
+    float* p; const float* g;              // the chunk's first parameter and gradient element
+    uint32_t state;                        // its first element in exp_avg / exp_avg_sq
+    uint32_t len, flags, pad;
+};
+static_assert(sizeof(OptimChunk) == 32, "OptimChunk must be 32 bytes");
+struct OptimRecord { int64_t step; int32_t stopped, pad; };      // what prepare leaves for apply: the step in force, the decision
+struct OptimArgs {
+    const OptimChunk* chunks; uint32_t n_chunks;
+    double* partials;                      // [n_chunks] sums of g*g
+    OptimRecord* record;
+    float *exp_avg, *exp_avg_sq;
+    int64_t* step; int32_t* stopped;
+    double lr, beta1, beta2, eps, clip;
+    const double* gate; double gate_threshold;
+    double* norm_out;
+};
+hipError_t launch_optim_step(const OptimArgs& a, hipStream_t s);          // two launches: prepare, apply
+
 // blocks of bs threads (or items) that cover n: the launchers' grid sizes
 static inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
 

@@ -8,8 +8,18 @@ in ``include/rover_step.h`` (``rover_ppo_loss``).
 
 Per minibatch: the actor's forward on the stored states with the stored actions as ``taken_actions`` (the noise counter does not move),
 the critic's forward, ``Engine.ppo_loss`` (losses, KL and the gradients at both outputs in one launch plus a merge), both nets'
-``backward`` (``rover_linear_backward`` per layer), then ``torch.nn.utils.clip_grad_norm_`` and one ``torch.optim.Adam`` step over both
-nets' parameters — the optimiser and the clipping are torch plumbing on plain tensors with ``.grad`` set.
+``backward`` (``rover_linear_backward`` per layer), then gradient-norm clipping and one Adam step over both nets' parameters.
+
+The optimiser step has two forms.  By default (``native_step=False``) it is ``torch.nn.utils.clip_grad_norm_`` and ``torch.optim.Adam``
+on plain tensors with ``.grad`` set: torch plumbing, some dozens of launches.  ``native_step=True`` runs ``learning/optim.py``'s ``Adam``
+instead: ``rover_optim_step``, two launches over all 33 tensors, deterministic, the clipped gradient not written back (``.grad`` keeps
+the unclipped one).  Both keep Adam's state in torch's ``state_dict`` layout.
+
+The KL early stop has two forms as well.  ``kl_stop="host"`` (the default) reads the minibatch's KL on the host before its step, as
+skrl does: one stream drain per minibatch.  ``kl_stop="device"`` (needs ``native_step``) hands the KL to the native step as its gate:
+every minibatch of every epoch is enqueued, the kernels skip the steps after the one whose KL exceeded the threshold (a latch, zeroed
+at the start of each epoch), and ``update()`` reads the per-epoch step counts once at its end.  The parameters come out bit-equal to
+the host form's; the skipped minibatches still cost their forward, loss and backward.
 
 Out of scope: the backward of the fused chain kernels (the update runs every layer as its own launch), gradient all-reduce across ranks,
 preprocessors, learning-rate schedulers, bf16 / fp16 training.
@@ -20,6 +30,7 @@ from itertools import chain
 
 import torch
 
+from .optim import Adam
 from .rollout import compute_gae
 
 # cfg/trainSKRL/RoverPPOSKRL.yaml over skrl's PPO_DEFAULT_CONFIG
@@ -33,10 +44,15 @@ STATS = ("policy_loss", "value_loss", "entropy_loss", "kl")
 
 
 class PPO:
-    def __init__(self, engine, policy, value, memory, cfg=None, generator=None):
+    def __init__(self, engine, policy, value, memory, cfg=None, generator=None, native_step=False, kl_stop="host"):
         """``policy`` / ``value``: the actor and critic ``HeightmapNet``; ``memory``: a ``RolloutMemory`` holding ``NAMES`` plus rewards and
         terminated; ``cfg``: skrl's keys over ``DEFAULT_CONFIG`` (an unknown key is an error); ``generator``: the CPU generator that
-        shuffles the minibatches (the same seed gives the same batches)."""
+        shuffles the minibatches (the same seed gives the same batches); ``native_step``: the optimiser step as two HIP launches
+        (``learning/optim.py``) instead of torch's; ``kl_stop``: "host" or "device" (module docstring; "device" needs ``native_step``)."""
+        if kl_stop not in ("host", "device"):
+            raise ValueError(f"PPO: kl_stop must be 'host' or 'device' (got {kl_stop!r})")
+        if kl_stop == "device" and not native_step:
+            raise ValueError("PPO: kl_stop='device' needs native_step=True (the gate is part of the native optimiser step)")
         unknown = sorted(set(cfg or {}) - set(DEFAULT_CONFIG))
         if unknown:
             raise ValueError(f"PPO: unknown cfg keys {unknown} (known: {sorted(DEFAULT_CONFIG)})")
@@ -55,7 +71,11 @@ class PPO:
         for p in self.params:
             if p.grad is None:
                 p.grad = torch.zeros_like(p)
-        self.optimizer = torch.optim.Adam(self.params, lr=float(self.cfg["learning_rate"]))
+        self.native_step, self.kl_stop = bool(native_step), kl_stop
+        if self.native_step:
+            self.optimizer = Adam(engine, self.params, lr=float(self.cfg["learning_rate"]))
+        else:
+            self.optimizer = torch.optim.Adam(self.params, lr=float(self.cfg["learning_rate"]))
         dev = policy.device
         self._stats = torch.zeros(4, dtype=torch.float64, device=dev)
         self._sum = torch.zeros(4, dtype=torch.float64, device=dev)
@@ -88,19 +108,30 @@ class PPO:
         self.policy.backward(d_mean)
         self.value.backward(d_value)
 
-    def step(self):
+    def step(self, gate=None, gate_threshold=0.0):
+        """The optimiser step on the gradients in ``.grad``.  ``gate`` (native step only): a float64 device scalar; the step is skipped
+        and the optimiser's ``stopped`` latch set once ``gate > gate_threshold``."""
+        if self.native_step:
+            self.optimizer.step(float(self.cfg["grad_norm_clip"]), gate=gate, gate_threshold=gate_threshold)
+            return
+        if gate is not None:
+            raise ValueError("PPO.step: a gate needs native_step=True")
         if self.cfg["grad_norm_clip"] > 0:
             torch.nn.utils.clip_grad_norm_(self.params, float(self.cfg["grad_norm_clip"]))
         self.optimizer.step()
 
     def update(self, last_values):
         """skrl's ``PPO._update``: compute_gae, then ``learning_epochs`` passes over ``mini_batches`` shuffled minibatches.  KL early stop
-        as skrl does it: with ``kl_threshold`` > 0 the minibatch's KL is read on the host (one 8-byte read) and, when it exceeds the
-        threshold, the rest of that epoch is skipped before the minibatch's step; with ``kl_threshold`` 0 nothing synchronises.
+        as skrl does it: with ``kl_threshold`` > 0 and ``kl_stop="host"`` the minibatch's KL is read on the host (one 8-byte read) and,
+        when it exceeds the threshold, the rest of that epoch is skipped before the minibatch's step; with ``kl_stop="device"`` the
+        native step decides the same on the device and the call synchronises once, at its end, to read ``minibatches_done``; with
+        ``kl_threshold`` 0 nothing synchronises.
         -> {policy_loss, value_loss, entropy_loss, kl}: the last epoch's means over its stepped minibatches, float64 device scalars."""
         c = self.cfg
         compute_gae(self.engine, self.memory, last_values, discount_factor=c["discount_factor"], lambda_coefficient=c["lambda"])
         self.minibatches_done = []
+        if self.kl_stop == "device" and c["kl_threshold"] > 0:
+            return self._update_device_stop()
         for _ in range(int(c["learning_epochs"])):
             self._sum.zero_()
             done = 0
@@ -113,5 +144,25 @@ class PPO:
                 self._sum += stats
                 done += 1
             self.minibatches_done.append(done)
+        mean = self._sum / max(self.minibatches_done[-1], 1)
+        return {k: mean[i] for i, k in enumerate(STATS)}
+
+    def _update_device_stop(self):
+        """The epochs with the KL stop on the device: every minibatch is enqueued, the native step is gated by the minibatch's KL, and
+        ``_sum`` takes the stats of the minibatches that stepped (the latch is read on the device).  The per-epoch step counts are the
+        differences of the optimiser's step counter, copied on the device after each epoch and read once at the end."""
+        c, opt = self.cfg, self.optimizer
+        marks = [opt.steps.clone()]
+        for _ in range(int(c["learning_epochs"])):
+            self._sum.zero_()
+            opt.stopped.zero_()
+            for batch in self.memory.sample_all(NAMES, int(c["mini_batches"]), shuffle=True, generator=self.generator):
+                stats = self.minibatch(*batch)
+                self.backward(batch[0].shape[0], batch[1].shape[1])
+                self.step(gate=stats[3:], gate_threshold=float(c["kl_threshold"]))
+                self._sum += torch.where(opt.stopped == 0, stats, torch.zeros_like(stats))
+            marks.append(opt.steps.clone())
+        counts = torch.cat(marks).cpu()                    # the update's one synchronisation
+        self.minibatches_done = [int(b - a) for a, b in zip(counts[:-1], counts[1:])]
         mean = self._sum / max(self.minibatches_done[-1], 1)
         return {k: mean[i] for i, k in enumerate(STATS)}
