@@ -3,11 +3,12 @@
 
 Mirrors the loop of the reference's `omniisaacgymenvs/train.py:57-125` (env = load...("Rover"); trainer loop:
 actions = agent.act(obs); obs, rew, done, info = env.step(actions)) with `vec_env.KinematicSim` standing in for PhysX and, for
-the skrl PPO agent, either a random policy (`--policy random`, the default) or the actor itself (`--policy actor`:
+the skrl PPO agent, either a random policy (`--policy random`, the default), the actor itself (`--policy actor`:
 `StochasticActorHeightmap.act`, sampled on the GPU in the kernel that ends its forward; `--checkpoint` loads a `state_dict` saved
-from the reference's module).
+from the reference's module) or the recurrent student the teacher is distilled into (`--policy student`: `StudentPolicy.act(obs,
+reset=done)`, the reference's `student_loader.act` with a carried GRU state; `--checkpoint best.pt` loads its `['state_dict']`).
 
-    python examples/rollout.py --envs 4096 --steps 200 [--assets /path/to/omniisaacgymenvs] [--policy actor [--checkpoint actor.pt]]
+    python examples/rollout.py --envs 4096 --steps 200 [--assets /path/to/omniisaacgymenvs] [--policy actor|student [--checkpoint actor.pt|best.pt]]
 
 `--rollouts N` (with `--policy actor`) adds what skrl's PPO does around that loop up to the weight update: a `DeterministicHeightmap` critic,
 a `RolloutMemory` of N steps (train.py:82, `rollouts: 60` in cfg/trainSKRL/RoverPPOSKRL.yaml:12) that stores states, actions, log_prob,
@@ -32,8 +33,10 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--assets", default="", help="directory holding the reference's tasks/utils/terrain/... files")
     ap.add_argument("--native-rays", action="store_true", help="the reference's 1634-point distribution (1750-float obs)")
-    ap.add_argument("--policy", choices=("random", "actor"), default="random", help="random actions, or StochasticActorHeightmap.act(obs)")
-    ap.add_argument("--checkpoint", default="", help="--policy actor: a state_dict of the reference's StochasticActorHeightmap (torch.save)")
+    ap.add_argument("--policy", choices=("random", "actor", "student"), default="random",
+                    help="random actions, StochasticActorHeightmap.act(obs), or StudentPolicy.act(obs, reset=done)")
+    ap.add_argument("--checkpoint", default="", help="--policy actor: a state_dict of the reference's StochasticActorHeightmap (torch.save); "
+                    "--policy student: the reference's best.pt (its ['state_dict'] is loaded)")
     ap.add_argument("--rollouts", type=int, default=0, help="--policy actor: store N steps in a RolloutMemory, then compute_gae (0 = off)")
     args = ap.parse_args()
     if args.rollouts < 0 or (args.rollouts and args.policy != "actor"):
@@ -60,7 +63,17 @@ def main():
             agent.load_state_dict(sd.get("policy", sd) if isinstance(sd, dict) else sd)
         print(f"policy: StochasticActorHeightmap, {sum(v.numel() for v in agent.state_dict().values()):,} parameters"
               f"{' from ' + args.checkpoint if args.checkpoint else ' (fresh initialisation)'}")
-    critic = memory = None
+    student = None
+    if args.policy == "student":
+        from isaac_rover_amd.learning.student import StudentPolicy
+        student = StudentPolicy(task._engine, task, device=task.device)
+        if args.checkpoint:
+            sd = torch.load(args.checkpoint, map_location="cpu")
+            student.load_state_dict(sd["state_dict"] if isinstance(sd, dict) and "state_dict" in sd else sd)
+        student.init_hidden(args.envs)
+        print(f"policy: StudentPolicy, {sum(v.numel() for v in student.state_dict().values()):,} parameters"
+              f"{' from ' + args.checkpoint if args.checkpoint else ' (fresh initialisation)'}")
+    critic = memory = done = None
     if args.rollouts:
         from isaac_rover_amd.learning.model import DeterministicHeightmap
         from isaac_rover_amd.learning.rollout import RolloutMemory, compute_gae
@@ -75,7 +88,9 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        if agent is None:
+        if student is not None:
+            actions = student.act(obs, reset=None if done is None else done.bool())  # an env that just ended starts from a zero hidden state
+        elif agent is None:
             actions = 2 * torch.rand(args.envs, 2, device=task.device) - 1
         else:
             actions, log_prob, outputs = agent.act(obs)                            # what a PPO rollout stores next to obs and rew

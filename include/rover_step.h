@@ -613,6 +613,43 @@ typedef struct {
 } rover_optim_step_desc;
 ROVER_API int rover_optim_step(rover_ctx *ctx, int32_t handle, const rover_optim_step_desc *d, void *stream);
 
+/* ---- the student policy's recurrent block (tasks/utils/learning_by_cheating/student_model.py:42-131; learning/student.py) ---- */
+/* rover_gru_cell: ONE layer of torch.nn.GRU for ONE time step in one launch.  This is the project's definition of the cell; gate order
+ * r, z, n; w_ih [3H][K], w_hh [3H][H] (nn.GRU's weight_ih_l*, weight_hh_l*), b_ih / b_hh [3H] or NULL (zeros):
+ *   r  = sigmoid(x.W_ir^T + b_ir + h.W_hr^T + b_hr)
+ *   z  = sigmoid(x.W_iz^T + b_iz + h.W_hz^T + b_hz)
+ *   n  = tanh   (x.W_in^T + b_in + r * (h.W_hn^T + b_hn))
+ *   h' = (1 - z) * n + z * h
+ * evaluated in f32 in this order (the library is built with -ffp-contract=off: one rounding per operation):
+ *   s_r = fma-chain over k of x then of h (exact f32 MFMA, v_mfma_f32_32x32x2_f32; one accumulator over K + H), likewise s_z;
+ *   s_in over K alone, s_hn over H alone;  sigmoid(v) = 1 / (1 + expf(-v));
+ *   r = sigmoid((s_r + b_ir) + b_hr);  z = sigmoid((s_z + b_iz) + b_hz);  n = tanhf((s_in + b_in) + r * (s_hn + b_hn));
+ *   h' = (1 - z) * n + z * h   (two products, then their sum).
+ * x [M, K], h_in [M, H] and h_out [M, H] are f32 rows at a row stride in floats (column slices of wider tensors will do).
+ * reset_mask: optional uint8 [M]; a row with a non-zero byte reads its h_in as zero, in the products and in z * h (an addition to
+ * the reference, whose student_loader.act never resets the state; NULL = the reference's behaviour).
+ * One workgroup computes a 32-column tile of h' from whole rows of h_in that other workgroups are still reading: h_out must not
+ * overlap h_in (nor x, the weights, the biases or the mask) — an overlap is refused with ROVER_E_INVALID and nothing is written.
+ * M = 0 launches nothing; K = 0 is legal (x, w_ih unread).  Widths: H = 1 .. 2 097 120 (65 535 tiles of 32 columns), K >= 0; anything else,
+ * a stride shorter than its row or above 2^40, or a missing array: ROVER_E_INVALID.  Neither [M, 3H] pre-activation tensor is
+ * written to memory.  The call allocates nothing, does not synchronise, uses no atomics (the same inputs give the same bits, and a
+ * row's result does not depend on the other rows) and can be captured in a graph. */
+ROVER_API int rover_gru_cell(rover_ctx *ctx, const float *x, int64_t x_stride, const float *h_in, int64_t h_in_stride, int32_t M, int32_t K,
+                             int32_t H, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                             const uint8_t *reset_mask, float *h_out, int64_t h_out_stride, void *stream);
+/* What rover_gru_cell would launch — host only, no ctx: "gru_cell<4>" (128 rows per workgroup) when ceil(M / 128) x ceil(H / 32)
+ * workgroups are at least 512, else "gru_cell<1>" (32 rows per workgroup); "none" for M = 0; NULL where the call would refuse the
+ * shapes.  Every limit on M, K and H lives behind this query. */
+ROVER_API const char *rover_gru_cell_route(int32_t M, int32_t K, int32_t H);
+
+/* rover_gated_sum: out = add + mul * sigmoid(pre), elementwise over [M, N] in one launch (sigmoid as above; the product, then the sum).
+ * The belief x_b + l_e * sigmoid(x_a) (student_model.py:79-85; x_a arrives LeakyReLU'd: ga's last Layer has its activation before the
+ * nn.Sigmoid) and the decoder's decoded + e * sigmoid(gate) (:121-131).  All four arrays are f32 rows at a row stride in floats; an
+ * INPUT's stride may be 0 (its one row serves every output row), otherwise strides are >= N and <= 2^40; M N < 2^38.  out overlaps no
+ * input (ROVER_E_INVALID).  M = 0 launches nothing.  Allocates nothing, does not synchronise, capturable. */
+ROVER_API int rover_gated_sum(rover_ctx *ctx, const float *add, int64_t add_stride, const float *mul, int64_t mul_stride, const float *pre,
+                              int64_t pre_stride, int32_t M, int32_t N, float *out, int64_t out_stride, void *stream);
+
 /* ---- tuning knobs ------------------------------------------------------------------------------------- */
 /* name = "raycast_variant": 0 = auto; 1 = one half-wave per ray in env order, every cell block streamed from HBM;
  *        2 = rays counting-sorted by (map, cell), one wave per run of sorted rays, the cell's triangles held in registers

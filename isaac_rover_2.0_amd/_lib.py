@@ -201,6 +201,9 @@ SYMBOLS = {
     "rover_optim_create": (C.c_int, [_P, C.POINTER(OptimDesc), _P]),
     "rover_optim_destroy": (C.c_int, [_P, C.c_int32]),
     "rover_optim_step": (C.c_int, [_P, C.c_int32, C.POINTER(OptimStepDesc), _P]),
+    "rover_gru_cell": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "rover_gru_cell_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
+    "rover_gated_sum": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
     "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
     "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -779,6 +782,50 @@ class Engine:
         return out
 
     chain_act_route = staticmethod(chain_act_route)
+
+    # ---- the student's recurrent block (rover_gru_cell, rover_gated_sum) -------------------------------------
+    def gru_cell(self, x, h_in, w_ih, w_hh, b_ih, b_hh, h_out, reset_mask=None):
+        """One layer of torch.nn.GRU for one time step (rover_gru_cell): h_out = cell(x [m, k], h_in [m, h]); w_ih [3h, k], w_hh [3h, h],
+        b_ih / b_hh [3h] or None.  x, h_in and h_out may be column slices / padded rows; ``reset_mask``: optional [m] bool / uint8 —
+        marked rows read h_in as zero.  h_out must not overlap h_in (the library refuses it)."""
+        what = "gru_cell"
+        self._f32_rows(x, "x", what)
+        m, k = x.shape
+        hd = w_hh.shape[1] if w_hh is not None and w_hh.dim() == 2 else -1
+        self._f32_rows(h_in, "h_in", what, (m, hd))
+        self._f32_rows(h_out, "h_out", what, (m, hd))
+        if k > 0:
+            self._chk(w_ih, (3 * hd, k), torch.float32, "w_ih")
+        self._chk(w_hh, (3 * hd, hd), torch.float32, "w_hh")
+        self._chk(b_ih, (3 * hd,), torch.float32, "b_ih")
+        self._chk(b_hh, (3 * hd,), torch.float32, "b_hh")
+        if reset_mask is not None:
+            if reset_mask.dtype == torch.bool:
+                reset_mask = reset_mask.view(torch.uint8)
+            self._chk(reset_mask, (m,), torch.uint8, "reset_mask")
+        self._check(self.lib.rover_gru_cell(self._h, _ptr(x), max(x.stride(0), k), _ptr(h_in), h_in.stride(0) if m > 1 else hd, m, k, hd, _ptr(w_ih) if k > 0 else None,
+                                            _ptr(w_hh), _ptr(b_ih), _ptr(b_hh), _ptr(reset_mask), _ptr(h_out), h_out.stride(0) if m > 1 else hd,
+                                            _stream(self._dev_index)), "rover_gru_cell")
+        return h_out
+
+    @classmethod
+    def gru_cell_route(cls, m, k, h):
+        """The instantiation gru_cell runs for [m, k] inputs and a hidden width h ("gru_cell<4>", "gru_cell<1>"); "none" for m = 0, None
+        where the call would be refused.  Host only."""
+        return cls._route(load().rover_gru_cell_route(int(m), int(k), int(h)))
+
+    def gated_sum(self, add, mul, pre, out):
+        """out = add + mul * sigmoid(pre) over [m, n] (rover_gated_sum), one launch.  All four are float32 GPU matrices with unit column
+        stride; an input may be a one-row matrix expanded over the rows (row stride 0)."""
+        what = "gated_sum"
+        self._f32_rows(out, "out", what)
+        m, n = out.shape
+        for t, name in ((add, "add"), (mul, "mul"), (pre, "pre")):
+            self._f32_rows(t, name, what, (m, n))
+        self._check(self.lib.rover_gated_sum(self._h, _ptr(add), add.stride(0) if m > 1 else n, _ptr(mul), mul.stride(0) if m > 1 else n, _ptr(pre),
+                                             pre.stride(0) if m > 1 else n, m, n, _ptr(out), max(out.stride(0), n), _stream(self._dev_index)),
+                    "rover_gated_sum")
+        return out
 
     # ---- the rollout side of PPO (rover_gae) -------------------------------------------------------------
     def _gae_rows(self, t, name, dtype, T=None, E=None):

@@ -1908,6 +1908,56 @@ int rover_optim_step(rover_ctx* c, int32_t handle, const rover_optim_step_desc* 
     return ROVER_OK;
 }
 
+// ---- the student policy's recurrent block (rover_gru.hip) ----
+int rover_gru_cell(rover_ctx* c, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K, int32_t H,
+                   const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
+                   int64_t h_out_stride, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    if (!gru_cell_route(M, K, H).nw) return fail(c, ROVER_E_INVALID, "gru_cell: M=%d K=%d H=%d outside M >= 0, K >= 0, 1 <= H <= %d", M, K, H, 32 * 65535);
+    if (M == 0) return ROVER_OK;                   // nothing is read or written: no pointer is required
+    if (!h_in || !w_hh || !h_out || (K > 0 && (!x || !w_ih))) return fail(c, ROVER_E_INVALID, "gru_cell: h_in, w_hh, h_out and (K > 0) x, w_ih must be given");
+    const int64_t max_stride = (int64_t)1 << 40;
+    if (h_in_stride < H || h_in_stride > max_stride || h_out_stride < H || h_out_stride > max_stride || (K > 0 && (x_stride < K || x_stride > max_stride)))
+        return fail(c, ROVER_E_INVALID, "gru_cell: a row stride is shorter than its row or above 2^40");
+    const Span out = span_of(h_out, h_out_stride, M, H, 4);
+    const int32_t G = 3 * H;                       // gate rows (H <= 32 x 65 535: no overflow)
+    const Span ins[7] = {span_of(h_in, h_in_stride, M, H, 4), span_of(K > 0 ? x : nullptr, x_stride, M, K, 4), span_of(K > 0 ? w_ih : nullptr, K, G, K, 4),
+                         span_of(w_hh, H, G, H, 4), span_of(b_ih, G, 1, G, 4), span_of(b_hh, G, 1, G, 4), span_of(reset_mask, M, 1, M, 1)};
+    for (int i = 0; i < 7; ++i)
+        if (ins[i].lo && overlap(out, ins[i]))
+            return fail(c, ROVER_E_INVALID, i == 0 ? "gru_cell: h_out overlaps h_in (a tile of h' needs whole rows of h that other workgroups still read)"
+                                                   : "gru_cell: h_out overlaps an array the call reads");
+    USE_DEVICE(c);
+    GruArgs a{x, x_stride, h_in, h_in_stride, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, M, K, H};
+    HIP_TRY(c, launch_gru_cell(a, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+const char* rover_gru_cell_route(int32_t M, int32_t K, int32_t H) {
+    const GruRoute r = gru_cell_route(M, K, H);
+    if (!r.nw) return nullptr;
+    return M == 0 ? "none" : gru_cell_route_name(r);
+}
+
+int rover_gated_sum(rover_ctx* c, const float* add, int64_t add_stride, const float* mul, int64_t mul_stride, const float* pre, int64_t pre_stride,
+                    int32_t M, int32_t N, float* out, int64_t out_stride, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    if (M < 0 || N < 1 || (int64_t)M * N >= (int64_t)1 << 38) return fail(c, ROVER_E_INVALID, "gated_sum: M=%d N=%d outside M >= 0, N >= 1, M N < 2^38", M, N);
+    if (M == 0) return ROVER_OK;
+    if (!add || !mul || !pre || !out) return fail(c, ROVER_E_INVALID, "gated_sum: add, mul, pre and out must be given");
+    const int64_t max_stride = (int64_t)1 << 40;
+    for (int64_t st : {add_stride, mul_stride, pre_stride})
+        if ((st != 0 && st < N) || st > max_stride) return fail(c, ROVER_E_INVALID, "gated_sum: an input's row stride is neither 0 nor >= N = %d, or above 2^40", N);
+    if (out_stride < N || out_stride > max_stride) return fail(c, ROVER_E_INVALID, "gated_sum: out's row stride is shorter than its row or above 2^40");
+    const Span so = span_of(out, out_stride, M, N, 4);
+    for (const Span& in : {span_of(add, add_stride, M, N, 4), span_of(mul, mul_stride, M, N, 4), span_of(pre, pre_stride, M, N, 4)})
+        if (overlap(so, in)) return fail(c, ROVER_E_INVALID, "gated_sum: out overlaps an input");
+    USE_DEVICE(c);
+    GatedSumArgs a{add, add_stride, mul, mul_stride, pre, pre_stride, out, out_stride, M, N};
+    HIP_TRY(c, launch_gated_sum(a, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
 int rover_set_option(rover_ctx* c, const char* name, int64_t value) {
     if (!c || !name) return ROVER_E_INVALID;
     USE_DEVICE(c);                                 // some options (re)allocate device workspace

@@ -203,6 +203,30 @@ LinearRoute linear_route(int M, int N);
 const char* linear_route_name(const LinearRoute& r);      // "linear_act<3,4>x2", or NULL
 hipError_t launch_linear_act(const LinearArgs& a, hipStream_t s);
 
+// One GRU layer for one time step (rover_gru_cell of the C ABI, validated; rover_gru.hip): torch.nn.GRU's cell, gates r, z, n
+struct GruArgs {
+    const float* x; int64_t x_stride;          // [M, K] rows at x_stride floats (unread when K = 0)
+    const float* h_in; int64_t h_in_stride;    // [M, H]
+    const float* w_ih; const float* w_hh;      // [3H][K], [3H][H]
+    const float* b_ih; const float* b_hh;      // [3H] each, or NULL (zeros)
+    const uint8_t* reset_mask;                 // [M] or NULL: a non-zero byte reads the row's h_in as zero
+    float* h_out; int64_t h_out_stride;        // [M, H]; overlaps nothing the call reads
+    int32_t M, K, H;
+};
+// the instantiation a cell runs: gru_cell_kernel<nw> on a grid of row slabs x 32-column tiles of the hidden state; nw = 0: refused
+struct GruRoute { int nw; };
+GruRoute gru_cell_route(int M, int K, int H);
+const char* gru_cell_route_name(const GruRoute& r);       // "gru_cell<4>", or NULL
+hipError_t launch_gru_cell(const GruArgs& a, hipStream_t s);
+
+// out = add + mul * sigmoid(pre) over [M, N] (rover_gated_sum; rover_gru.hip); an input's row stride may be 0 (one row for all)
+struct GatedSumArgs {
+    const float* add; int64_t add_stride; const float* mul; int64_t mul_stride; const float* pre; int64_t pre_stride;
+    float* out; int64_t out_stride;
+    int32_t M, N;
+};
+hipError_t launch_gated_sum(const GatedSumArgs& a, hipStream_t s);
+
 // a chain of 2 or 4 layers in one kernel (rover_mlp.hip): y = L_n(... L_1(x)), L_i(v) = act_i(W_i v + b_i)
 struct ChainArgs {
     const float* x; int64_t x_stride;      // [M, K0] rows at x_stride floats

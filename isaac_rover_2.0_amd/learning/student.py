@@ -1,0 +1,265 @@
+"""The recurrent student policy of the reference's learning-by-cheating scheme — forward pass on the MI355X.
+
+Mirrors ``omniisaacgymenvs/tasks/utils/learning_by_cheating/student_model.py`` (``Student``: two ``Encoder``s, ``Belief_Encoder`` = a
+2-layer ``nn.GRU`` + the gated ``gb`` / ``ga`` branches, ``Belief_Decoder``, ``MLP`` with a Tanh head) and ``student_loader.py``
+(``act``: one time step per env step with a carried hidden state; ``cfg_fn``: the widths in ``DEFAULT_CFG``).
+
+The GRU is the one new hot path: each layer of a time step is ONE ``rover_gru_cell`` launch (f32 MFMA, gates in the epilogue), the
+gates ``x_b + l_e * sigmoid(x_a)`` and ``decoded + e * sigmoid(gate)`` one ``rover_gated_sum`` each.  Everything else is ``Layer`` chains
+the library already runs; whether a chain is one kernel or one launch per layer is asked of the library (``Engine.chain_route``,
+``Engine.linear_route``), as ``HeightmapNet._plan`` does — this file holds no width or row limit.
+
+Things the reference does that are kept as they are:
+  * obs is sliced as ``[proprioceptive | ... | sparse | dense]``: the heightmap slices are taken from the END of the row (:208-210);
+  * ``ga``'s last ``Layer`` applies its LeakyReLU BEFORE the ``nn.Sigmoid`` (:63-68);
+  * ``Belief_Decoder`` always uses LeakyReLU (its cfg's ``activation_function`` is not read, :95-96);
+  * ``Student.forward`` hands the decoder the GRU's output SEQUENCE ``out [B, T, H]``, of which the decoder takes ``out[-1]`` — the LAST
+    BATCH ROW's sequence (:121-123,227) — so ``estimated[b, t] = decoded(out[B-1, t]) + e[b, t] * sigmoid(gate(out[B-1, t]))``.
+
+The hidden state lives in ``self.h [n_layers, E, H]`` at a fixed address.  A cell may not write over the state it reads (a tile of h'
+needs whole rows of h), so ``act()`` writes the new state into a scratch tensor and copies it back on the device: the
+same launches every call, capturable once after a warm-up.  No back-propagation through time, no distillation loop.
+"""
+from __future__ import annotations
+
+import math
+from collections import OrderedDict
+
+import torch
+
+from .model import Layer
+
+# student_loader.cfg_fn (:29-62), the keys the model reads
+DEFAULT_CFG = {
+    "encoder": {"activation_function": "leakyrelu", "encoder_features": [80, 60]},
+    "belief_encoder": {"hidden_dim": 300, "n_layers": 2, "activation_function": "leakyrelu", "gb_features": [128, 128, 120],
+                       "ga_features": [128, 128, 120]},
+    "belief_decoder": {"activation_function": "leakyrelu", "gate_features": [128, 256, 512], "decoder_features": [128, 256, 512]},
+    "mlp": {"activation_function": "leakyrelu", "network_features": [256, 160, 128]},
+}
+INFO_KEYS = ("proprioceptive", "sparse", "dense", "actions")
+
+
+def _info_of(info_or_task):
+    """``info``: the reference's dataset header (a mapping with INFO_KEYS), or a task (RoverTask: widths from its heightmap)."""
+    if hasattr(info_or_task, "keys"):
+        for k in INFO_KEYS:
+            if k not in info_or_task:
+                raise KeyError(f"StudentPolicy: info has no '{k}' (needs {', '.join(INFO_KEYS)})")
+        info = {k: int(info_or_task[k]) for k in INFO_KEYS}
+    else:
+        t, hm = info_or_task, info_or_task.Camera.heightmap
+        ns, nd = hm.get_num_sparse_vector(), hm.get_num_dense_vector()
+        info = {"proprioceptive": t.num_observations - ns - nd, "sparse": ns, "dense": nd, "actions": t.num_actions}
+    for k, v in info.items():
+        if v < 0 or (k == "actions" and v < 1):
+            raise ValueError(f"StudentPolicy: info['{k}'] = {v}")
+    return info
+
+
+def _cfg_of(cfg):
+    for sec, keys in (("encoder", ("encoder_features",)), ("belief_encoder", ("hidden_dim", "n_layers", "gb_features", "ga_features")),
+                      ("belief_decoder", ("gate_features", "decoder_features")), ("mlp", ("network_features",))):
+        if sec not in cfg:
+            raise KeyError(f"StudentPolicy: cfg has no section '{sec}'")
+        for k in keys:
+            if k not in cfg[sec]:
+                raise KeyError(f"StudentPolicy: cfg['{sec}'] has no '{k}'")
+    be = cfg["belief_encoder"]
+    ef, gb, ga = list(cfg["encoder"]["encoder_features"]), list(be["gb_features"]), list(be["ga_features"])
+    if not ef or not gb or not ga or int(be["n_layers"]) < 1 or int(be["hidden_dim"]) < 1:
+        raise ValueError("StudentPolicy: cfg needs encoder_features, gb_features, ga_features, n_layers >= 1 and hidden_dim >= 1")
+    # belief = x_b + l_e * x_a (student_model.py:83-85): the three widths are one
+    if not (gb[-1] == ga[-1] == 2 * ef[-1]):
+        raise ValueError(f"StudentPolicy: gb_features[-1] = {gb[-1]} and ga_features[-1] = {ga[-1]} must equal 2 * encoder_features[-1] = {2 * ef[-1]}")
+    return cfg
+
+
+def param_shapes(info, cfg=DEFAULT_CFG):
+    """name -> shape of every parameter of the reference's ``Student(info, cfg)``, in its ``state_dict()`` order.  Pure."""
+    info, cfg = _info_of(info), _cfg_of(cfg)
+    p, ex = info["proprioceptive"], info["sparse"] + info["dense"]
+    be, sd = cfg["belief_encoder"], OrderedDict()
+
+    def layers(prefix, k, widths):
+        for i, n in enumerate(widths):
+            sd[f"{prefix}.{i}.layer.0.weight"], sd[f"{prefix}.{i}.layer.0.bias"] = (n, k), (n,)
+            k = n
+        return k
+
+    ef = list(cfg["encoder"]["encoder_features"])
+    layers("encoder1.encoder", info["sparse"], ef)
+    layers("encoder2.encoder", info["dense"], ef)
+    hd, k = int(be["hidden_dim"]), p + 2 * ef[-1]
+    for l in range(int(be["n_layers"])):
+        sd[f"belief_encoder.gru.weight_ih_l{l}"], sd[f"belief_encoder.gru.weight_hh_l{l}"] = (3 * hd, k), (3 * hd, hd)
+        sd[f"belief_encoder.gru.bias_ih_l{l}"], sd[f"belief_encoder.gru.bias_hh_l{l}"] = (3 * hd,), (3 * hd,)
+        k = hd
+    layers("belief_encoder.gb", hd, list(be["gb_features"]))
+    layers("belief_encoder.ga", hd, list(be["ga_features"]))
+    layers("belief_decoder.gate_encoder", hd, list(cfg["belief_decoder"]["gate_features"]) + [ex])      # Belief_Decoder appends (:102-103)
+    layers("belief_decoder.decoder", hd, list(cfg["belief_decoder"]["decoder_features"]) + [ex])
+    sd["MLP.log_std_parameter"] = (info["actions"],)
+    nf = list(cfg["mlp"]["network_features"])
+    k = layers("MLP.network", p + list(be["gb_features"])[-1], nf)
+    sd[f"MLP.network.{len(nf)}.weight"], sd[f"MLP.network.{len(nf)}.bias"] = (info["actions"], k), (info["actions"],)
+    return sd
+
+
+class StudentPolicy:
+    """``Student`` + ``student_loader``: plain tensors under the reference's parameter names, ``act()`` per env step, ``forward()`` per sequence."""
+
+    def __init__(self, engine, info_or_task, cfg=DEFAULT_CFG, device="cuda:0", seed=0):
+        self.info, self.cfg = _info_of(info_or_task), _cfg_of(cfg)
+        self.engine, self.device = engine, device
+        g = torch.Generator().manual_seed(seed)
+        shapes = param_shapes(self.info, cfg)
+        be = cfg["belief_encoder"]
+        self.hidden_dim, self.n_layers = int(be["hidden_dim"]), int(be["n_layers"])
+        self._params = OrderedDict()
+
+        def chain(prefix, act, head=None):
+            """the Layers named ``prefix.i.layer.0.*`` (and the bare ``prefix.i.*`` head, activation ``head``)"""
+            out, i = [], 0
+            while f"{prefix}.{i}.layer.0.weight" in shapes or f"{prefix}.{i}.weight" in shapes:
+                plain = f"{prefix}.{i}.weight" in shapes
+                stem = f"{prefix}.{i}" if plain else f"{prefix}.{i}.layer.0"
+                n, k = shapes[stem + ".weight"]
+                layer = Layer(k, n, head if plain else act, device, g)
+                self._params[stem + ".weight"], self._params[stem + ".bias"] = layer.weight, layer.bias
+                out.append(layer)
+                i += 1
+            return out
+
+        self.encoder1 = chain("encoder1.encoder", cfg["encoder"].get("activation_function", "leakyrelu"))
+        self.encoder2 = chain("encoder2.encoder", cfg["encoder"].get("activation_function", "leakyrelu"))
+        bound = 1.0 / math.sqrt(self.hidden_dim)                     # nn.GRU.reset_parameters
+        self.gru = []
+        for l in range(self.n_layers):
+            ws = []
+            for nm in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+                name = f"belief_encoder.gru.{nm}_l{l}"
+                t = (torch.rand(*shapes[name], generator=g) * 2 - 1).mul_(bound).to(device)
+                self._params[name] = t
+                ws.append(t)
+            self.gru.append(tuple(ws))
+        self.gb = chain("belief_encoder.gb", be.get("activation_function", "leakyrelu"))
+        self.ga = chain("belief_encoder.ga", be.get("activation_function", "leakyrelu"))
+        self.gate_encoder = chain("belief_decoder.gate_encoder", "leakyrelu")
+        self.decoder = chain("belief_decoder.decoder", "leakyrelu")
+        self.log_std_parameter = self._params["MLP.log_std_parameter"] = torch.zeros(self.info["actions"], device=device)
+        self.network = chain("MLP.network", cfg["mlp"].get("activation_function", "leakyrelu"), head="tanh")
+        self._params = OrderedDict((k, self._params[k]) for k in shapes)          # the reference's order
+        self.h = None
+        self._bufs, self._plans, self._chunks = {}, {}, {}
+
+    # ---- interop with the reference's nn.Module parameter names --------------------------------------------
+    def state_dict(self):
+        return OrderedDict(self._params)
+
+    def load_state_dict(self, sd):
+        """Every parameter from ``sd`` (a checkpoint's ``['state_dict']``); a missing key is a KeyError, a wrong shape a ValueError, each naming the key."""
+        for k, v in self._params.items():
+            if k not in sd:
+                raise KeyError(f"StudentPolicy.load_state_dict: missing key '{k}'")
+            if tuple(sd[k].shape) != tuple(v.shape):
+                raise ValueError(f"StudentPolicy.load_state_dict: '{k}' has shape {tuple(sd[k].shape)}, expected {tuple(v.shape)}")
+        for k, v in self._params.items():
+            v.copy_(torch.as_tensor(sd[k]).to(device=self.device, dtype=torch.float32))
+
+    def init_hidden(self, num_envs):
+        """Zeroes ``self.h [n_layers, E, H]`` (Belief_Encoder.init_hidden, :89-92); the same tensor is kept while E stays the same."""
+        if self.h is None or self.h.shape[1] != num_envs:
+            self.h = torch.zeros(self.n_layers, num_envs, self.hidden_dim, device=self.device)
+            self._h_new = torch.empty_like(self.h)
+        else:
+            self.h.zero_()
+        return self.h
+
+    # ---- the forward ------------------------------------------------------------------------------------------
+    def _buf(self, key, rows, cols):
+        b = self._bufs.get(key)
+        if b is None or b.shape != (rows, cols):
+            b = self._bufs[key] = torch.empty(rows, cols, device=self.device)
+        return b
+
+    def _linear(self, x, layer, out):
+        """One Layer; a layer wider than one linear_forward takes (the decoder's) runs as column blocks of the width the library accepts."""
+        m, k, n = x.shape[0], x.shape[1], layer.weight.shape[0]
+        c = self._chunks.get((m, k, n))
+        if c is None:
+            c = n
+            while c > 1 and self.engine.linear_route(m, k, c) is None:
+                c = (c + 1) // 2
+            self._chunks[(m, k, n)] = c
+        for lo in range(0, n, c):
+            hi = min(n, lo + c)
+            self.engine.linear_forward(x, layer.weight[lo:hi], layer.bias[lo:hi], layer.activation, out[:, lo:hi])
+        return out
+
+    def _run(self, key, x, layers, out):
+        """``layers`` over x into ``out``: one chain kernel where the library names one for these widths, else layer by layer."""
+        m, eng = x.shape[0], self.engine
+        fused = self._plans.get((key, m))
+        if fused is None:
+            fused = self._plans[(key, m)] = eng.chain_route(m, *eng.chain_shape(layers)) is not None
+        if fused:
+            return eng.chain_forward(x, layers, out)
+        for i, layer in enumerate(layers):
+            last = i == len(layers) - 1
+            x = self._linear(x, layer, out if last else self._buf((key, i), m, layer.weight.shape[0]))
+        return out
+
+    def _step(self, obs, h_in, h_out, reset, actions, estimated):
+        """One time step: obs [E, F] (rows at any stride), h_in / h_out lists of [E, H] per layer -> actions [E, A] (and estimated)."""
+        eng, e, f = self.engine, obs.shape[0], obs.shape[1]
+        p, ns, nd = self.info["proprioceptive"], self.info["sparse"], self.info["dense"]
+        if f < p + ns + nd:
+            raise ValueError(f"StudentPolicy: obs has {f} columns, needs proprioceptive + sparse + dense = {p + ns + nd}")
+        ef = self.encoder1[-1].weight.shape[0]
+        cat = self._buf("cat", e, p + 2 * ef)                        # [p | e_l1 | e_l2]: the GRU's input (:75,222)
+        mlp_in = self._buf("mlp_in", e, p + 2 * ef)                  # [p | belief] (:159)
+        cat[:, :p] = obs[:, :p]
+        mlp_in[:, :p] = obs[:, :p]
+        self._run("enc1", obs[:, f - ns - nd:f - nd], self.encoder1, cat[:, p:p + ef])
+        self._run("enc2", obs[:, f - nd:], self.encoder2, cat[:, p + ef:p + 2 * ef])
+        x = cat
+        for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(self.gru):
+            x = eng.gru_cell(x, h_in[l], w_ih, w_hh, b_ih, b_hh, h_out[l], reset_mask=reset)
+        top = x
+        x_b = self._run("gb", top, self.gb, self._buf("x_b", e, 2 * ef))
+        x_a = self._run("ga", top, self.ga, self._buf("x_a", e, 2 * ef))
+        eng.gated_sum(x_b, cat[:, p:], x_a, mlp_in[:, p:])           # belief = x_b + l_e * sigmoid(x_a) (:79-85)
+        self._run("mlp", mlp_in, self.network, actions)
+        if estimated is not None:
+            last, ex = top[e - 1:e], ns + nd                         # the decoder reads the LAST batch row's output (module docstring)
+            gate = self._run("gate", last, self.gate_encoder, self._buf("gate", 1, ex))
+            dec = self._run("dec", last, self.decoder, self._buf("decoded", 1, ex))
+            eng.gated_sum(dec.expand(e, ex), obs[:, f - ex:], gate.expand(e, ex), estimated)
+        return actions
+
+    def act(self, obs, reset=None, reconstruct=False):
+        """student_loader.act (:21-24): obs [E, F] -> actions [E, A], the Tanh mean (no sampling); advances ``self.h`` in place (same
+        address after every call).  ``reset``: optional [E] bool / uint8 device tensor (e.g. the step's done): marked rows start from a
+        zero hidden state — an addition, the reference never resets.  ``reconstruct=True``: -> (actions, estimated [E, sparse + dense]).
+        Both are buffers of this object, overwritten by the next call of the same E.  Capturable in a graph after one warm-up call."""
+        e = obs.shape[0]
+        if self.h is None or self.h.shape[1] != e:
+            self.init_hidden(e)
+        actions = self._buf("actions", e, self.info["actions"])
+        est = self._buf("estimated", e, self.info["sparse"] + self.info["dense"]) if reconstruct else None
+        self._step(obs, list(self.h), list(self._h_new), reset, actions, est)
+        self.h.copy_(self._h_new)
+        return (actions, est) if reconstruct else actions
+
+    def forward(self, x, h):
+        """Student.forward (:199-248): x [B, T, F] (batch first), h [n_layers, B, H] -> (actions [B, T, A], estimated [B, T, S + D],
+        h [n_layers, B, H]) as a loop of T cell steps; time step t is the row view x[:, t] (row stride T F): no transpose copy."""
+        b, t_len = x.shape[0], x.shape[1]
+        actions = torch.empty(b, t_len, self.info["actions"], device=self.device)
+        est = torch.empty(b, t_len, self.info["sparse"] + self.info["dense"], device=self.device)
+        cur, nxt = h.to(torch.float32).clone(), torch.empty(self.n_layers, b, self.hidden_dim, device=self.device)
+        for t in range(t_len):
+            self._step(x[:, t], list(cur), list(nxt), None, actions[:, t], est[:, t])
+            cur, nxt = nxt, cur
+        return actions, est, cur
