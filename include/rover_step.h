@@ -668,6 +668,10 @@ ROVER_API int rover_gated_sum(rover_ctx *ctx, const float *add, int64_t add_stri
  *        2: below 98 304 rays per step).
  * name = "lane_rocks" (variant 4, sorted): 1 = the rock rays through the staged kernel too (one ray-cast launch), 0 = through the culled one
  *        (3); -1 (default) = auto: 1.
+ * name = "lane_box" (variant 4, fp32 arithmetic): the form of the sphere test's records in the staged tables the NEXT rover_set_knn_map
+ *        calls build.  0 = two bounding spheres per pair of triangles; 1 = one axis-aligned box per pair, tested on the three axes d x e_i;
+ *        -1 (default) = auto: boxes for a map in which at least three quarters of the pairs fill their box (a regular grid mesh), spheres
+ *        for any other (a decimated mesh).  One form per map; results do not depend on it (rover_info.lane_box reports it).
  * name = "ray_precision": 0 (default) = the reference's fp32 mode, which the parity tests pin.
  *        1 = every ray origin / direction rounded to fp16 before the cell lookup and the ray maths, like the reference AS
  *        SHIPPED (Camera.dtype = float16: camera.py:55,212; rock_detect.py:319,371); f32 arithmetic after that.
@@ -701,7 +705,7 @@ ROVER_API int rover_gated_sum(rover_ctx *ctx, const float *add, int64_t add_stri
  *        24 / 48 (irregular mesh, or ray_precision 2); variant 4 behind the sort 32, 64 from r = 12; in env order 16, 32 from 2^17
  *        padded ray slots, 64 from 2^20.  Results do not depend on it.
  * Every name above but "ray_precision" and "cell_index_mode" that has a ROVER_<NAME> environment variable (ROVER_RAYCAST_VARIANT,
- * ROVER_RAYCAST_RUN, ROVER_LANE_ENV_ORDER, ROVER_LANE_ROCKS, ROVER_BIN_LOW_BITS, ROVER_CULL_QUEUE_MB) takes its start value from it at
+ * ROVER_RAYCAST_RUN, ROVER_LANE_ENV_ORDER, ROVER_LANE_ROCKS, ROVER_LANE_BOX, ROVER_BIN_LOW_BITS, ROVER_CULL_QUEUE_MB) takes its start value from it at
  * rover_create; a value outside the option's range (and 0 = auto) is ignored there. */
 ROVER_API int rover_set_option(rover_ctx *ctx, const char *name, int64_t value);
 
@@ -716,6 +720,7 @@ typedef struct {
     int32_t ray_precision;         /* option "ray_precision" in force */
     int32_t raycast_sorted;        /* 1: the step sorts the rays by (map, cell) bin; 0: the ray cast walks the slots in env order */
     int32_t raycast_rocks_staged;  /* variant 4: 1 = the rocks part of the sorted list runs on the staged kernel too, 0 = on the culled one */
+    int32_t lane_box[2];           /* per map: 1 = the staged tables of the fp32 arithmetic hold one box per pair of triangles, 0 = two spheres ("lane_box") */
 } rover_info;
 ROVER_API int rover_get_info(const rover_ctx *ctx, rover_info *info);
 /* The whole ray-cast plan in force (what the next step's ray cast will run) and the other host-side values that select a code path of

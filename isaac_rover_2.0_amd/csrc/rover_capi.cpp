@@ -67,6 +67,7 @@ struct MapTables {
     DevBuf<uint16_t> rtab;              // [T_int] the nine fp16 vertex components of a triangle (20 B)
     ProofTables proof[2];
     uint32_t lane_pp = 0;               // pairs per row of the staged kernel's records
+    bool lane_box = false;              // the f32 proof's staged records are boxes (one per pair), not two spheres
     int64_t tris = 0, farok = 0, cells = 0;   // triangles; cells whose far bound can hold for a usual ray (far_build_kernel); cells
     uint64_t bytes() const {
         uint64_t b = table.bytes() + cull_idx.bytes() + rtab.bytes();
@@ -479,6 +480,12 @@ static int build_map_tables(rover_ctx* c, MapTables& m, const int32_t* map_idx, 
     m.proof[0].always = h_cnt[0]; m.proof[0].nocone = h_cnt[1];
     m.proof[1].always = h_cnt[2]; m.proof[1].nocone = h_cnt[3];
     m.farok = h_cnt[4];
+    // the form of test (A)'s records in the f32 proof's staged tables (option "lane_box"): boxes where most pairs fill theirs
+    if (a.lane.lrec && (c->knobs.lane_box > 0 || (c->knobs.lane_box < 0 && lane_box_share_met(h_cnt[5], h_cnt[6])))) {
+        if ((e = launch_lane_box(a, nullptr)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess)
+            return fail(c, ROVER_E_HIP, "set_knn_map: staged tables in box form: %s", hipGetErrorString(e));
+        m.lane_box = true;
+    }
     return ROVER_OK;
 }
 
@@ -510,6 +517,8 @@ static const KnobRow kKnobs[] = {
     {"lane_env_order", "ROVER_LANE_ENV_ORDER", -1, 1, kIntMin, kIntMax, KNOB_ENV_AS_BOOL, KNOB_SET(knobs.lane_env_order, (int)v), KNOB_REPLAN,
      "-1 (auto), 0 or 1"},
     {"lane_rocks", "ROVER_LANE_ROCKS", -1, 1, kIntMin, kIntMax, KNOB_ENV_AS_BOOL, KNOB_SET(knobs.lane_rocks, (int)v), KNOB_REPLAN, "-1 (auto), 0 or 1"},
+    {"lane_box", "ROVER_LANE_BOX", -1, 1, kIntMin, kIntMax, KNOB_ENV_AS_BOOL, KNOB_SET(knobs.lane_box, (int)v), 0,      // takes effect at the next rover_set_knn_map
+     "-1 (auto), 0 or 1"},
     {nullptr, "ROVER_CULL_LAZY", 1, 0, kIntMin, kIntMax, 0, KNOB_SET(knobs.cull_lazy, (int)v), KNOB_REPLAN, nullptr},
     {"bin_low_bits", "ROVER_BIN_LOW_BITS", 8, 12, 8, 12, KNOB_OPT_ALSO_ZERO, KNOB_SET(knobs.low_bits_opt, (uint32_t)v), KNOB_REPLAN | KNOB_BINS,
      "0 (chosen by the library) or in [8, 12]"},
@@ -794,6 +803,7 @@ static int run_raycast(rover_ctx* c, const StepPlan& p, uint32_t n_valid, hipStr
         {
             const CullProofH ph = cull_proof_h(c->knobs.cull_eta_h, c->knobs.cull_split_h);
             l.half = p.proof; l.c_a_h = ph.c_a; l.k2_far = cull_far_k2(l.half, ph);
+            l.forms = p.proof ? 0u : (c->maps[0].lane_box ? 1u : 0u) | (c->maps[1].lane_box ? 2u : 0u);
         }
         l.run = p.run; l.out = c->d_dist_out.get(); l.stats = q.stats.get();
         if (p.env_order) {      // every slot (padding included), in env order, one launch
@@ -1236,6 +1246,7 @@ int rover_get_info(const rover_ctx* c, rover_info* info) {
     info->cell_index_mode = c->cell_rcp; info->ray_precision = c->precision;
     info->raycast_sorted = c->plan.sorted ? 1 : 0;
     info->raycast_rocks_staged = c->plan.rocks_staged ? 1 : 0;
+    for (int w = 0; w < 2; ++w) info->lane_box[w] = c->maps[w].lane_box ? 1 : 0;
     return ROVER_OK;
 }
 

@@ -956,6 +956,10 @@ __global__ void __launch_bounds__(64 * CULL_WPB) cull_scan_kernel(CULL_SCAN_ARGS
 // W >= 0.00523 |h| + 1.0102 rho' + 1.01 p - 9e-7 > rho' + 0.005 (|h| + 2 rho') for every p >= 1e-6, which is all the rejection proof at the
 // top of this file uses of test (A).  (p = 1e-3 cost a tenth more candidates: 3.95 pairs per ray against 3.6 with 5e-5.)
 // Rays with a non-finite or far-away origin (|s'| >= 1e4: nothing overflows below that) are the wild rays: every pair a candidate.
+// Box form (f32 proof, chosen per map table when the map is set: launch_lane_box): the 16 bytes of a pair hold ONE box about both padded
+// triangles, {M' = fp16(M - C), half extents e (fp16, rounded up), mrg}, and the pair is cleared iff on one of the axes d x e_i the line misses the
+// box grown by the margin — any lower bound on the distance between the line and the padded triangle serves the proof.  Levels,
+// row order, test (B) and everything behind the candidate mask are those of the sphere form.
 // ---------------------------------------------------------------------------------------------------
 #define LN_CH 8u                     // pairs per chunk: one 128-byte line of a cell's record row, one 8-bit candidate mask (with 16 pairs per chunk a
                                      // terrain ray of configs[2] tested 2.4 chunks = 38 pairs on average, with 8 it tests 4.3 chunks = 34)
@@ -986,6 +990,11 @@ __global__ void __launch_bounds__(64 * CULL_WPB) cull_scan_kernel(CULL_SCAN_ARGS
 #define LN_B4_ERR 3.0e-3
 #define LN_B4_C ((float)((512.0 * LN_B4_TAU) * (512.0 * LN_B4_TAU) * 1.0001))
 static_assert(0.999 * (LN_B4_TAU - LN_B4_ERR) * CullK<0>::sigma > 1.45 * 2.0 * 1.0e-6 / CullK<0>::alpha, "f32 cull proof on B4 records: (B) must contradict (A)");
+// Test (A) in box form (header comment above): the margin is LN_BOX_ALPHA |h|_1 + mrg; LN_BOX_ALPHA pays for the roundings on top of alpha.
+#define LN_BOX_ALPHA 5.05e-3f
+#define LN_BOX_FILL 0.85             // a pair is "well filled" when its box's xy area is below this share of its larger sphere's disc, as test (A) needs them
+#define LN_BOX_SHARE 0.75            // a map is built in box form when at least this share of its non-empty pairs is well filled
+static_assert((double)LN_BOX_ALPHA >= 1.008 * CullK<0>::alpha, "f32 cull proof, box form: the margin must exceed alpha by the roundings' share");
 #define LN_WAVES 5                   // waves per SIMD the kernel is compiled for (95 VGPRs, 7.4 KB LDS): 3 / 4 / 5 -> 317 / 253 / 235 us; 6 spills
 
 __device__ __forceinline__ uint16_t half_bits_up(float v) {      // fp16 >= v (v >= 0, finite or +inf)
@@ -1000,7 +1009,8 @@ __global__ void __launch_bounds__(128) lane_build_kernel(const int4* __restrict_
                                                          uint32_t Y, float cell_size, float shift_x, float shift_y, float k1, float tau2,
                                                          double c_rho, const uint32_t* __restrict__ qrow, const float* __restrict__ nz_abs,
                                                          float4* __restrict__ lvl, uint4* __restrict__ lrec, uint2* __restrict__ lid, int half,
-                                                         float q_good) {
+                                                         float q_good, const uint16_t* __restrict__ rtab, int box /* f32 proof: the table in box form */,
+                                                         uint32_t* __restrict__ fill /* {non-empty pairs, well-filled pairs} of the map, or null */) {
     __shared__ float s_z0[128], s_z1[128], s_g[128], s_ro[128], s_qn[128];
     __shared__ uint4 s_nrec[128];
     __shared__ uint32_t s_key[128];
@@ -1092,14 +1102,80 @@ __global__ void __launch_bounds__(128) lane_build_kernel(const int4* __restrict_
         hb[e][3] = r2b;
         G = fminf(G, g);
     }
+    // The pair as ONE box (f32 proof): the axis-aligned box of both padded triangles about its own fp16-encoded centre M, half extents rounded
+    // up with the centre's displacement, the builder's 1e-4 and LN_PAD added per axis.  The pair's level bounds (G, z0, z1, rho_out) and its place
+    // in the row stay those of its two spheres, computed above though no longer stored: a suffix a ray clears passes test (A) of the sphere form
+    // on each triangle's own sphere, which is all the proof asks of a triangle the ray never tests.
+    uint16_t bx[8] = {0, 0, 0, 0xfb53u, 0xfb53u, 0xfb53u, 0x0400u, 0};       // empty pair: extents -6e4, never a candidate
+    int n_pres = 0;
+    bool well = false;
+    if (!half && (box || fill) && p < n_src) {
+        double lo[3] = {1.0e30, 1.0e30, 1.0e30}, hi[3] = {-1.0e30, -1.0e30, -1.0e30};
+        bool bok = true;
+        float r2max = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (id[e] < 0) continue;
+            ++n_pres;
+            if (hb[e][3] == 0x7c00u) { bok = false; continue; }            // no sphere record: always a candidate in either form
+            r2max = fmaxf(r2max, (float)__builtin_bit_cast(_Float16, hb[e][3]));
+            const _Float16* src = reinterpret_cast<const _Float16*>(rtab) + 10ull * (uint32_t)id[e];
+            float v[9];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) { v[q] = (float)src[q]; bok = bok && (v[q] == v[q]) && fabsf(v[q]) < 6.0e4f; }
+            // a, b, c as ctab_build_kernel<0> takes them; the corners of the padded triangle
+            const float af[3] = {v[6], v[7], v[8]}, bf[3] = {v[3] - v[6], v[4] - v[7], v[5] - v[8]}, cf[3] = {v[0] - v[6], v[1] - v[7], v[2] - v[8]};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double a = af[k], b = bf[k], c = cf[k], pad = CullK<0>::pad;
+                const double q0 = a - pad * b - pad * c, q1 = a + (1.0 + 2.0 * pad) * b - pad * c, q2 = a - pad * b + (1.0 + 2.0 * pad) * c;
+                lo[k] = fmin(lo[k], fmin(q0, fmin(q1, q2))); hi[k] = fmax(hi[k], fmax(q0, fmax(q1, q2)));
+            }
+        }
+        if (n_pres) {
+            const double C[3] = {(double)ccx, (double)ccy, (double)zc};
+            float mf[3], ef[3];
+            uint16_t mh[3], eh[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float f = bok ? (float)(0.5 * (lo[k] + hi[k]) - C[k]) : 0.0f;
+                bok = bok && fabsf(f) <= 4.0f;
+                const _Float16 h = (_Float16)(bok ? f : 0.0f);
+                mh[k] = __builtin_bit_cast(uint16_t, h); mf[k] = (float)h;
+                const double M = C[k] + (double)mf[k];
+                const double e = fmax(hi[k] - M, M - lo[k]) + 1.0e-4 + LN_PAD;
+                bok = bok && e < 4.0;
+                eh[k] = half_bits_up(bok ? (float)(e * 1.0000001) : 0.0f);
+                ef[k] = (float)__builtin_bit_cast(_Float16, eh[k]);
+            }
+            if (bok) {
+                const double rho = sqrt((double)ef[0] * ef[0] + (double)ef[1] * ef[1] + (double)ef[2] * ef[2]);
+                well = 4.0 * (double)ef[0] * ef[1] <= LN_BOX_FILL * 3.141592653589793 * (double)r2max;
+                if (box) {
+                    uint16_t mg = half_bits_up((float)((2.0 * (double)LN_BOX_ALPHA * rho + 2.0e-5) * 1.000001));
+                    if (mg < 0x0400u) mg = 0x0400u;
+                    bx[0] = mh[0]; bx[1] = mh[1]; bx[2] = mh[2]; bx[3] = eh[0]; bx[4] = eh[1]; bx[5] = eh[2]; bx[6] = mg;
+                }
+            } else if (box) {      // cannot be encoded, or holds a triangle that is always a candidate: extents 6e4 (finite: an infinity times a zero direction component would be a NaN)
+                bx[0] = bx[1] = bx[2] = 0; bx[3] = bx[4] = bx[5] = 0x7b53u; bx[6] = 0x3c00u;
+                G = -__builtin_inff();
+            }
+        }
+    }
+    if (fill) {     // (the build that decides the form counts; uniform over the block)
+        const int n0 = __syncthreads_count(n_pres > 0), n1 = __syncthreads_count(well);
+        if (p == 0) { atomicAdd(fill, (uint32_t)n0); atomicAdd(fill + 1, (uint32_t)n1); }
+    }
     // order the pairs by G (ascending; -inf = a pair that is always a candidate first, +inf = an empty pair last); pairs with a
     // steep triangle in front of the rest (their G counts as it is in the bounds: only the ORDER is forced)
     const float Gs = (pq < q_good && G > -3.0e38f && G < 3.0e38f) ? -1.0e30f + G : G;
     const uint32_t gb = __float_as_uint(Gs);
     s_key[p] = (gb & 0x80000000u) ? ~gb : (gb | 0x80000000u);
     s_src[p] = (uint8_t)p;
-    s_rec[p] = make_uint4((uint32_t)hb[0][0] | ((uint32_t)hb[0][1] << 16), (uint32_t)hb[0][2] | ((uint32_t)hb[0][3] << 16),
-                          (uint32_t)hb[1][0] | ((uint32_t)hb[1][1] << 16), (uint32_t)hb[1][2] | ((uint32_t)hb[1][3] << 16));
+    s_rec[p] = box ? make_uint4((uint32_t)bx[0] | ((uint32_t)bx[1] << 16), (uint32_t)bx[2] | ((uint32_t)bx[3] << 16),
+                                (uint32_t)bx[4] | ((uint32_t)bx[5] << 16), (uint32_t)bx[6] | ((uint32_t)bx[7] << 16))
+                   : make_uint4((uint32_t)hb[0][0] | ((uint32_t)hb[0][1] << 16), (uint32_t)hb[0][2] | ((uint32_t)hb[0][3] << 16),
+                                (uint32_t)hb[1][0] | ((uint32_t)hb[1][1] << 16), (uint32_t)hb[1][2] | ((uint32_t)hb[1][3] << 16));
     s_nrec[p] = half ? make_uint4((uint32_t)nb[0][0] | ((uint32_t)nb[0][1] << 16), (uint32_t)nb[0][2] | ((uint32_t)nb[0][3] << 16),
                                   (uint32_t)nb[1][0] | ((uint32_t)nb[1][1] << 16), (uint32_t)nb[1][2] | ((uint32_t)nb[1][3] << 16))
                      : make_uint4(b4[0], b4[1], 0u, 0u);
@@ -1198,6 +1274,19 @@ template <int HI> __device__ __forceinline__ float mix_fma(uint32_t packed, floa
     return r;
 }
 
+// box form of test (A): c - (fp16 half `HI` of `packed`) * |b|, and a * b + (low fp16 half of packed)
+template <int HI> __device__ __forceinline__ float mix_nfma_abs(uint32_t packed, float b, float c) {
+    float r;
+    if (HI) asm("v_fma_mix_f32 %0, -%1, |%2|, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(packed), "v"(b), "v"(c));
+    else    asm("v_fma_mix_f32 %0, -%1, |%2|, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(packed), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ float mix_fma_lo(float a, float b, uint32_t packed) {
+    float r;
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(a), "v"(b), "v"(packed));
+    return r;
+}
+
 // the exact phase on 2-byte entries {ray position | pair position << 6}: ids through the cell's id row, then as cull_exact
 // (cellm: per lane, the cell of run position `lane` with its map in bit 31)
 template <int H>
@@ -1280,7 +1369,7 @@ __device__ __forceinline__ void lane_exact(const RayRec* __restrict__ rays, cons
         const float4 *__restrict__ lvl1, const uint4 *__restrict__ lrec0, const uint4 *__restrict__ lrec1, const uint2 *__restrict__ lid0,    \
         const uint2 *__restrict__ lid1, const RawTri *__restrict__ rtab0, const RawTri *__restrict__ rtab1, uint32_t pp01, uint32_t run,      \
         uint32_t n_blocks, uint32_t split, uint32_t t8, uint32_t r8, uint32_t chsr, uint32_t run_r, float *__restrict__ out,                  \
-        uint4 *__restrict__ stats, float k2_far, float c_a
+        uint4 *__restrict__ stats, float k2_far, float c_a, uint32_t forms /* bit w: map w's f32 tables are in box form */
 
 template <int H>
 __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bounds__(64) lane_scan_kernel(LANE_SCAN_ARGS) {
@@ -1395,8 +1484,10 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     uint32_t cused = 0, ctot = 0, n_flush = 0;
     wave_lds_sync();
     // the tests: 64 items per round, the records straight from the cell's row (L1 / L2: a chunk is read by the bin's rays side by side)
-    auto rounds = [&](uint32_t it0, uint32_t it1, auto AB) {
-        constexpr bool kAB = decltype(AB)::value;
+    // (BX: the records are boxes.  A wave whose rays read tables of both forms runs its lists once per form, `mixed`: an item then keeps the
+    // mask of the pass that read its records for what they are)
+    auto rounds = [&](uint32_t it0, uint32_t it1, auto AB, auto BX, bool mixed) {
+        constexpr bool kAB = decltype(AB)::value, kBX = decltype(BX)::value;
         for (uint32_t base = it0; base < it1; base += 64u) {
             const bool ok = base + lane < it1;
             const uint32_t it = s_items[ok ? base + lane : it0];
@@ -1431,6 +1522,15 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
                 for (uint32_t i = 0; i < NB; ++i) {
                     const uint4 r = rec[i];
                     uint32_t sg;
+                    if (kBX) {      // {Mx, My | Mz, ex | ey, ez | mrg, -}: max over the axes d x e_i of |(d x h)_i| - sum_j e_j |d_k| - (alpha' |h|_1 + mrg) >= +0
+                        const float hx = mix_rsub<0>(r.x, ra.x), hy = mix_rsub<1>(r.x, ra.y), hz = mix_rsub<0>(r.y, ra.z);
+                        const float z = mix_fma_lo(fabsf(hx) + fabsf(hy) + fabsf(hz), LN_BOX_ALPHA, r.w);
+                        const float cx = __builtin_fmaf(rb.y, hy, -(rb.x * hz)), cy = __builtin_fmaf(ra.w, hz, -(rb.y * hx)), cz = __builtin_fmaf(rb.x, hx, -(ra.w * hy));
+                        const float tx = mix_nfma_abs<1>(r.z, rb.x, mix_nfma_abs<0>(r.z, rb.y, fabsf(cx) - z));
+                        const float ty = mix_nfma_abs<1>(r.z, ra.w, mix_nfma_abs<1>(r.y, rb.y, fabsf(cy) - z));
+                        const float tz = mix_nfma_abs<0>(r.z, ra.w, mix_nfma_abs<1>(r.y, rb.x, fabsf(cz) - z));
+                        sg = __float_as_uint(fmaxf(fmaxf(tx, ty), tz));
+                    } else {
                     {
                         const float hx = mix_rsub<0>(r.x, ra.x), hy = mix_rsub<1>(r.x, ra.y), hz = mix_rsub<0>(r.y, ra.z);
                         float t = hx * ra.w; t = __builtin_fmaf(hy, rb.x, t); t = __builtin_fmaf(hz, rb.y, t);
@@ -1446,6 +1546,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
                         float u = mix_fms_hi(qq, c_a, r.w);
                         u = __builtin_fmaf(-t, t, u);
                         sg |= __float_as_uint(u);
+                    }
                     }
                     if (kAB && !H) {      // (B) on B4 records: (n4 . d)^2 - LN_B4_C >= +0 for both triangles, or the pair stays a candidate
                         const uint4 n = nrc[i];
@@ -1465,11 +1566,23 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
                     mask = __builtin_amdgcn_alignbit(mask, sg, 31);       // (mask << 1) | sign: a pair is a candidate unless every u >= +0
                 }
             }
-            if (ok) s_cand[rl * LN_MAXCH + ch] = (uint8_t)mask;
+            const bool mine = !mixed || ((forms >> (uint32_t)__builtin_amdgcn_ds_bpermute((int)(rl << 2), (int)map)) & 1u) == (kBX ? 1u : 0u);
+            if (ok && mine) s_cand[rl * LN_MAXCH + ch] = (uint8_t)mask;
         }
     };
-    rounds(0u, ia_tot, std::false_type{});
-    if (ib_tot) rounds(ia_tot, ia_tot + ib_tot, std::true_type{});
+    // the form of a wave's records: that of its rays' map tables (behind the sort a wave is terrain or rocks but for the one at the border;
+    // in env order a wave holds both maps)
+    const uint64_t on1 = __builtin_amdgcn_ballot_w64(act && map != 0u), on0 = __builtin_amdgcn_ballot_w64(act && map == 0u);
+    const bool any_box = !H && ((on0 && (forms & 1u)) || (on1 && (forms & 2u)));
+    const bool any_sph = H || (on0 && !(forms & 1u)) || (on1 && !(forms & 2u));
+    if (any_sph) {
+        rounds(0u, ia_tot, std::false_type{}, std::false_type{}, any_box);
+        if (ib_tot) rounds(ia_tot, ia_tot + ib_tot, std::true_type{}, std::false_type{}, any_box);
+    }
+    if (!H && any_box) {
+        rounds(0u, ia_tot, std::false_type{}, std::true_type{}, any_sph);
+        if (ib_tot) rounds(ia_tot, ia_tot + ib_tot, std::true_type{}, std::true_type{}, any_sph);
+    }
     wave_lds_sync();
     // candidates -> queue entries; the exact phase whenever the queue could not take the next ray's entries (rare) and at the end
     auto flush = [&]() {
@@ -1560,18 +1673,20 @@ float cull_far_k2(int half, CullProofH ph) {
 
 uint32_t lane_pairs_per_row(uint32_t K8);
 static void lane_build(const int32_t* idx4, const uint4* ctab, uint64_t n_cells, uint32_t K8, uint32_t Y, float cell_size, float shift_x, float shift_y,
-                       const uint32_t* qrow, const float* nz_abs, LaneTables t, int half, CullProofH ph, hipStream_t s);
+                       const uint32_t* qrow, const float* nz_abs, LaneTables t, int half, CullProofH ph, const uint16_t* rtab, int box, uint32_t* fill,
+                       hipStream_t s);
 // ctab / qrow / far: the f32 proof's tables; ctab_h / qrow_h / far_h: the as-shipped fp16 arithmetic's (CullK<1>); idx4 and rtab serve both.
 hipError_t launch_cull_build(const CullBuildArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(rtab_build_kernel, dim3(blocks_for(a.T_int, 256)), dim3(256), 0, s, a.tris, a.verts, a.T_int, a.V, a.order, a.rtab);
     hipLaunchKernelGGL(ctab_build_kernel<1>, dim3(blocks_for(a.T_int, 256)), dim3(256), 0, s, a.rtab, a.T_int, a.order, a.ctab_h, a.nz_scratch, a.counts + 2, a.ph);
     hipLaunchKernelGGL(idx4_build_kernel, dim3((uint32_t)a.n_cells), dim3(256), 0, s, a.map_idx, a.K, a.K8, a.T, a.newid, a.nz_scratch, a.rtab, a.Y, a.cell_size,
                        a.shift_x, a.shift_y, a.idx4, a.qrow_h, a.counts + 2);
-    lane_build(a.idx4, a.ctab_h, a.n_cells, a.K8, a.Y, a.cell_size, a.shift_x, a.shift_y, a.qrow_h, a.nz_scratch, a.lane_h, 1, a.ph, s);      // (nz_scratch holds the fp16 proof's cone values here)
+    lane_build(a.idx4, a.ctab_h, a.n_cells, a.K8, a.Y, a.cell_size, a.shift_x, a.shift_y, a.qrow_h, a.nz_scratch, a.lane_h, 1, a.ph, a.rtab, 0, nullptr, s);      // (nz_scratch holds the fp16 proof's cone values here)
     hipLaunchKernelGGL(ctab_build_kernel<0>, dim3(blocks_for(a.T_int, 256)), dim3(256), 0, s, a.rtab, a.T_int, a.order, a.ctab, a.nz_scratch, a.counts, a.ph);
     hipLaunchKernelGGL(idx4_build_kernel, dim3((uint32_t)a.n_cells), dim3(256), 0, s, a.map_idx, a.K, a.K8, a.T, a.newid, a.nz_scratch, a.rtab, a.Y, a.cell_size,
                        a.shift_x, a.shift_y, a.idx4, a.qrow, a.counts);
-    lane_build(a.idx4, a.ctab, a.n_cells, a.K8, a.Y, a.cell_size, a.shift_x, a.shift_y, a.qrow, a.nz_scratch, a.lane, 0, a.ph, s);
+    // (sphere form; counts[5], [6]: the map's non-empty and well-filled pairs, from which the caller chooses the form — launch_lane_box)
+    lane_build(a.idx4, a.ctab, a.n_cells, a.K8, a.Y, a.cell_size, a.shift_x, a.shift_y, a.qrow, a.nz_scratch, a.lane, 0, a.ph, a.rtab, 0, a.counts + 5, s);
     float k1, k2;
     cull_far_consts(CullK<0>::c_a, 1.00001, &k1, &k2);
     hipLaunchKernelGGL(far_build_kernel, dim3(blocks_for(a.n_cells, 4)), dim3(256), 0, s, reinterpret_cast<const int4*>(a.idx4), a.ctab, a.n_cells, a.K8, a.Y,
@@ -1661,13 +1776,22 @@ uint32_t lane_pairs_per_row(uint32_t K8) { return ((K8 / 2u + LN_CH - 1u) / LN_C
 uint32_t lane_lvl_stride() { return LN_LVL; }
 
 static void lane_build(const int32_t* idx4, const uint4* ctab, uint64_t n_cells, uint32_t K8, uint32_t Y, float cell_size, float shift_x, float shift_y,
-                       const uint32_t* qrow, const float* nz_abs, LaneTables t, int half, CullProofH ph, hipStream_t s) {
+                       const uint32_t* qrow, const float* nz_abs, LaneTables t, int half, CullProofH ph, const uint16_t* rtab, int box, uint32_t* fill,
+                       hipStream_t s) {
     if (!t.lrec) return;
     float k1, k2;
     if (half) cull_far_consts(ph.c_a, 1.004, &k1, &k2); else cull_far_consts(CullK<0>::c_a, 1.00001, &k1, &k2);
     hipLaunchKernelGGL(lane_build_kernel, dim3((uint32_t)n_cells), dim3(128), 0, s, reinterpret_cast<const int4*>(idx4), ctab, K8, lane_pairs_per_row(K8),
                        Y, cell_size, shift_x, shift_y, k1, half ? ph.tau2 : CullK<0>::tau2, half ? ph.c_rho : CullK<0>::c_rho, qrow, nz_abs, t.lvl, t.lrec,
-                       t.lid, half, half ? LN_QGOOD_H : LN_QGOOD);
+                       t.lid, half, half ? LN_QGOOD_H : LN_QGOOD, rtab, box, fill);
+}
+
+bool lane_box_share_met(uint64_t pairs, uint64_t well_filled) { return pairs > 0 && (double)well_filled >= LN_BOX_SHARE * (double)pairs; }
+
+// the f32 proof's staged tables of a map once more, in box form (after launch_cull_build, whose build buffers it reads)
+hipError_t launch_lane_box(const CullBuildArgs& a, hipStream_t s) {
+    lane_build(a.idx4, a.ctab, a.n_cells, a.K8, a.Y, a.cell_size, a.shift_x, a.shift_y, a.qrow, a.nz_scratch, a.lane, 0, a.ph, a.rtab, 1, nullptr, s);
+    return hipGetLastError();
 }
 
 uint32_t lane_waves(uint32_t n_rays, uint32_t run) {
@@ -1688,7 +1812,7 @@ hipError_t launch_raycast_lane(LaneArgs a, hipStream_t s) {
     hipLaunchKernelGGL(a.half ? lane_scan_kernel<1> : lane_scan_kernel<0>, dim3((g.t8 + g.r8) * 8u * 4u), dim3(64), 0, s, a.rays, a.sorted,
                        a.n_sorted, a.lvl[0], a.lvl[1], a.lrec[0], a.lrec[1], a.lid[0], a.lid[1], reinterpret_cast<const RawTri*>(a.rtab[0]),
                        reinterpret_cast<const RawTri*>(a.rtab[1]), a.pp[0] | (a.pp[1] << 16), g.run, g.n_blocks, g.split, g.t8, g.r8, g.chs | (g.chr << 8),
-                       g.run_r, a.out, a.stats, k2, c_a);
+                       g.run_r, a.out, a.stats, k2, c_a, a.half ? 0u : a.forms);
     return hipGetLastError();
 }
 

@@ -101,6 +101,7 @@ struct LaneArgs {
     uint4* stats;
     int half;                    // the tables are the as-shipped fp16 arithmetic's, the exact phase runs it
     float c_a_h, k2_far;         // test (A)'s constant of that proof; the level bound's ray-side constant (cull_far_k2)
+    uint32_t forms;              // f32 proof: bit w = map w's pair records are boxes (launch_lane_box), else two spheres
 };
 uint32_t lane_lvl_stride();
 hipError_t launch_raycast_lane(LaneArgs a, hipStream_t s);
@@ -393,13 +394,17 @@ struct CullBuildArgs {
     uint32_t *qrow, *qrow_h;     // [cell] per proof, read only by the build kernels
     float4 *far, *far_h;         // [cell][2] far-pair bounds, then [cell] near-pair bounds, per proof
     float* nz_scratch;           // [T_int]
-    uint32_t* counts;            // [5], zeroed: always-candidate triangles, cells without a cone; the same for fp16; cells with a useful far bound
+    uint32_t* counts;            // [7], zeroed: always-candidate triangles, cells without a cone; the same for fp16; cells with a useful far bound; non-empty and well-filled pairs (f32 staged tables)
     CullProofH ph;
     uint32_t Y;
     float cell_size, shift_x, shift_y;
     LaneTables lane, lane_h;     // the staged kernel's tables per proof (null: not built)
 };
 hipError_t launch_cull_build(const CullBuildArgs& a, hipStream_t s);
+// The form of test (A)'s records in the f32 proof's staged tables: launch_cull_build builds spheres and leaves the map's non-empty and
+// well-filled pairs in counts[5], counts[6]; where lane_box_share_met, launch_lane_box builds the same tables again as boxes.
+bool lane_box_share_met(uint64_t pairs, uint64_t well_filled);
+hipError_t launch_lane_box(const CullBuildArgs& a, hipStream_t s);
 float cull_far_k2(int half, CullProofH ph);
 hipError_t launch_raycast_culled(CullArgs a, hipStream_t s);
 hipError_t launch_knn_centroids(const float* verts, const int32_t* tris, uint32_t T, uint32_t V, int ref, float* cx, float* cy,

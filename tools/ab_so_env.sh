@@ -1,11 +1,11 @@
 #!/bin/bash
 # Per-kernel table of the bench for (library, environment) pairs in ONE gpurun call:
 #   gpurun -- 'bash tools/ab_so_env.sh "ab_tmp/x.so ROVER_LANE_ROCKS=1" "ab_tmp/y.so ROVER_RAYCAST_RUN=8" -- [bench args]'
-# (copies each library over csrc/librover_step.so on the BOX; the local tree is untouched)
+# (copies each library over csrc/librover_step.so on the BOX; the local tree is untouched)   AB_REPS: alternations (default 2)
 set -u
 export TMPDIR=/tmp
 arms=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do arms+=("$1"); shift; done; [ $# -gt 0 ] && shift
-for rep in 1 2; do
+for rep in $(seq ${AB_REPS:-2}); do
 for arm in "${arms[@]}"; do
   so=${arm%% *}; ev=${arm#* }; [ "$ev" = "$arm" ] && ev="X_NONE=1"
   cp "$so" isaac_rover_2.0_amd/csrc/librover_step.so
@@ -25,9 +25,10 @@ for r in csv.DictReader(open(fs[-1])):
     parts.append((r["Name"].split("(")[0].replace("void rover::", "")[:24], us))
 try:
     d = json.loads(open(P + "/bench.json").read().strip().splitlines()[-1]); val = d["value"] / 1e6
+    ppr = (d.get("cull") or {}).get("candidate_pairs_per_ray") or -1
 except Exception as e:
-    val = -1
-print(f"{v:44s} sum {tot:7.1f} us {val:7.2f} M  " + "  ".join(f"{n}={u:.1f}" for n, u in sorted(parts, key=lambda x: -x[1])[:7]), flush=True)
+    val = ppr = -1
+print(f"{v:44s} sum {tot:7.1f} us {val:7.2f} M  pairs/ray {ppr:.3f}  " + "  ".join(f"{n}={u:.1f}" for n, u in sorted(parts, key=lambda x: -x[1])[:7]), flush=True)
 PY
 done
 done
