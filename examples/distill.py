@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Distilling a teacher into the recurrent student on the MI355X rover step path (no Isaac Sim, no autograd).
+
+The teacher (`StochasticActorHeightmap`, fresh or from `--teacher`, acting with its mean) drives `RoverTask` on a synthetic scene.
+Windows of `--window` steps of (observation, teacher action, done) are collected; after each window `learning.distill.StudentTrainer.update`
+runs one step of back-propagation through time on the student (`rover_gru_cell_train`, `rover_gru_cell_backward`, `rover_linear_dgrad`, ...,
+clip + Adam as `rover_optim_step`), with Gaussian noise on the student's heightmap columns and the clean ones as the reconstruction target.
+The hidden state is carried from window to window (truncated BPTT); an env that ended starts its next step from a zero state.
+Prints the three losses per update and saves the reference's `{"state_dict": ...}` layout, which `rollout.py --policy student --checkpoint`
+loads.
+
+    python examples/distill.py --envs 512 --window 32 --updates 20 [--teacher actor.pt] [--out student.pt]
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from isaac_rover_amd import config, synth, vec_env  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=512)
+    ap.add_argument("--window", type=int, default=32, help="time steps per update (the length back-propagation through time covers)")
+    ap.add_argument("--updates", type=int, default=20)
+    ap.add_argument("--native-rays", action="store_true", help="the reference's 1634-point distribution (1750-float obs)")
+    ap.add_argument("--teacher", default="", help="a state_dict of the reference's StochasticActorHeightmap (torch.save)")
+    ap.add_argument("--noise", type=float, default=0.05, help="standard deviation of the noise on the student's heightmap columns")
+    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--grad-norm-clip", type=float, default=1.0)
+    ap.add_argument("--recon-scale", type=float, default=0.5)
+    ap.add_argument("--torch-step", action="store_true", help="clip_grad_norm_ + torch.optim.Adam instead of the two HIP launches")
+    ap.add_argument("--out", default="", help="where to save {'state_dict': ...} (the reference's best.pt layout)")
+    args = ap.parse_args()
+    if args.window < 1 or args.updates < 1:
+        ap.error("--window and --updates need values >= 1")
+
+    scene = synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
+    cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
+    env = vec_env.VecEnv(headless=True)
+    extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size
+    g = torch.Generator().manual_seed(0)
+    spawn = torch.zeros(args.envs, 3)
+    spawn[:, 0:2] = 0.15 * extent + 0.7 * extent * torch.rand(args.envs, 2, generator=g)
+    from isaac_rover_amd.learning.distill import StudentTrainer
+    from isaac_rover_amd.learning.model import StochasticActorHeightmap
+    from isaac_rover_amd.learning.student import StudentPolicy
+    from isaac_rover_amd.tasks.rover import RoverTask
+    task = RoverTask("Rover", cfg, env, scene=scene, distribution=None if args.native_rays else synth.ray_distribution("37"))
+    env.set_task(task, sim_params={"dt": 0.05}, spawn_positions=spawn)
+    obs = env.reset()
+    teacher = StochasticActorHeightmap(task._engine, task)
+    if args.teacher:
+        sd = torch.load(args.teacher, map_location="cpu")
+        teacher.load_state_dict(sd.get("policy", sd) if isinstance(sd, dict) else sd)
+    student = StudentPolicy(task._engine, task, device=task.device, seed=1)
+    trainer = StudentTrainer(task._engine, student, lr=args.lr, grad_norm_clip=args.grad_norm_clip, recon_scale=args.recon_scale,
+                             native_step=not args.torch_step)
+    e, t_len, f, ex = args.envs, args.window, obs.shape[1], student.info["sparse"] + student.info["dense"]
+    print(f"obs {tuple(obs.shape)}  teacher {'from ' + args.teacher if args.teacher else '(fresh initialisation)'}  student "
+          f"{sum(p.numel() for p in student.parameters()):,} trainable parameters in {len(student.parameters())} tensors")
+    x = torch.empty(e, t_len, f, device=task.device)
+    clean = torch.empty(e, t_len, ex, device=task.device)
+    wanted = torch.empty(e, t_len, task.num_actions, device=task.device)
+    reset = torch.zeros(e, t_len, dtype=torch.bool, device=task.device)
+    noise_gen = torch.Generator(device=task.device).manual_seed(2)
+    h, done = None, torch.zeros(e, dtype=torch.bool, device=task.device)
+    for u in range(args.updates):
+        for t in range(t_len):
+            actions, _, _ = teacher.act(obs, deterministic=True)
+            x[:, t] = obs
+            clean[:, t] = obs[:, f - ex:]
+            wanted[:, t] = actions
+            reset[:, t] = done                                                     # an env that just ended starts from a zero hidden state
+            obs, _, done, _ = env.step(actions)
+            done = done.bool().clone()
+        x[:, :, f - ex:] += args.noise * torch.randn(e, t_len, ex, device=task.device, generator=noise_gen)
+        loss, action_loss, recon_loss, h = trainer.update(x, wanted, h0=h, reset=reset, target=clean)
+        print(f"update {u + 1}: loss {float(loss):.6f}  action_loss {float(action_loss):.6f}  recon_loss {float(recon_loss):.6f}")
+    if args.out:
+        torch.save({"state_dict": {k: v.cpu() for k, v in student.state_dict().items()}}, args.out)
+        print(f"saved {args.out}")
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

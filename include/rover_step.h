@@ -500,6 +500,18 @@ ROVER_API int rover_linear_backward(rover_ctx *ctx, const float *x, int64_t x_st
  * / 8 from 0 / 128 / 256 / 512 rows.  The pointer is valid until the calling thread's next route query. */
 ROVER_API const char *rover_linear_backward_route(int32_t M, int32_t K, int32_t N, int32_t want_dx);
 
+/* rover_linear_dgrad: the dx of rover_linear_backward alone, for ANY N >= 1 and K >= 1: dx [M, K] = (dy * act'(y)) W with W [N][K]
+ * contiguous, the same activations and derivative rules, the same kernel (a reduction over N in 32-wide slabs, one accumulator per
+ * element in the order of n) on a route without the 256 limits — the recurrent student's layers need it (K = 300, N = 900 / 1 746).
+ * y may be NULL with activation 0.  dx overlaps nothing the call reads.  M = 0 launches nothing.  ROVER_E_INVALID before any launch as
+ * for rover_linear_backward.  Allocates nothing, does not synchronise, no atomics, capturable. */
+ROVER_API int rover_linear_dgrad(rover_ctx *ctx, const float *y, int64_t y_stride, const float *dy, int64_t dy_stride, int32_t M, int32_t K,
+                                 const float *weight, int32_t N, int32_t activation, float *dx, int64_t dx_stride, void *stream);
+/* What rover_linear_dgrad would launch — host only: "dgrad<NT,NW>xNY" (linear_dgrad_kernel<NT, NW> on NY column tiles of dx): below
+ * 65 536 rows NT = NW = 1; from there NW = 4 and NT = 2 (1 when K <= 32).  "none" for M = 0; NULL where the call would be refused
+ * (M < 0, N < 1, K < 1 or more than 65 535 column tiles).  The pointer is valid until the calling thread's next route query. */
+ROVER_API const char *rover_linear_dgrad_route(int32_t M, int32_t K, int32_t N);
+
 /* rover_ppo_loss: skrl's PPO minibatch loss at the nets' outputs, and its gradients with respect to them.  With ls', sigma and
  * lp_i = sum_j [...] exactly as the rover_gauss_head comment defines them for taken actions a (reduction: ROVER_REDUCE_SUM only, the
  * reference's), c = ratio_clip, vc = value_clip:
@@ -642,6 +654,40 @@ ROVER_API int rover_gru_cell(rover_ctx *ctx, const float *x, int64_t x_stride, c
  * shapes.  Every limit on M, K and H lives behind this query. */
 ROVER_API const char *rover_gru_cell_route(int32_t M, int32_t K, int32_t H);
 
+/* rover_gru_cell_train: rover_gru_cell with one more output for the backward, gates [M, 4H] at a row stride (>= 4H): r | z | n | q with
+ * q = s_hn + b_hn as written above.  h_out has the same bits as rover_gru_cell's on the same inputs (the same kernel body; the extra
+ * stores are a template flag of the epilogue, the inference instantiations are unchanged) and the route is rover_gru_cell_route's.
+ * gates overlaps neither h_out nor anything the call reads.  Otherwise as rover_gru_cell. */
+ROVER_API int rover_gru_cell_train(rover_ctx *ctx, const float *x, int64_t x_stride, const float *h_in, int64_t h_in_stride, int32_t M,
+                                   int32_t K, int32_t H, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                                   const uint8_t *reset_mask, float *h_out, int64_t h_out_stride, float *gates, int64_t gates_stride,
+                                   void *stream);
+
+/* rover_gru_cell_backward: the backward of ONE layer for ONE time step in one launch.  dh_above [M, H] is the gradient that arrives at
+ * h' from the layer above (or from the heads), dh_next [M, H] the one from the next time step (NULL at the last step: zeros); gates
+ * [M, 4H] is what rover_gru_cell_train stored, h_in and reset_mask what it read.  With g = dh_above + dh_next and h = h_in, read as 0 on
+ * a reset row, every line one f32 rounding in this order:
+ *   d_n = g * (1 - z);   a_n = d_n * (1 - n * n)
+ *   d_z = g * (h - n);   a_z = d_z * (z * (1 - z))
+ *   d_r = a_n * q;       a_r = d_r * (r * (1 - r))
+ *   dgi [M, 3H] = [a_r | a_z | a_n]          (the gradient at x.W_ih^T + b_ih)
+ *   dgh [M, 3H] = [a_r | a_z | a_n * r]      (the gradient at h.W_hh^T + b_hh)
+ *   dh_in [M, H] = (sum over j < 3H of dgh_j * w_hh[j][.], exact f32 MFMA, one accumulator in the order of j) + g * z
+ * and dh_in is 0 on a reset row: nothing flows across an episode boundary.  The weight gradients are the caller's reductions over all
+ * time steps (dW_ih = dgi^T x, dW_hh = dgh^T h with reset rows of h zeroed: rover_linear_backward), and dx = dgi W_ih is one
+ * rover_linear_dgrad.  dgh is formed from gates while the product stages it; the workgroups of one column tile store dgi and dgh.
+ * All arrays are f32 rows at a row stride in floats.  No output overlaps an input or another output (ROVER_E_INVALID, nothing is
+ * written).  M = 0 launches nothing.  Allocates nothing, does not synchronise, no atomics (the same inputs give the same bits, and a
+ * row's result does not depend on the other rows), capturable. */
+ROVER_API int rover_gru_cell_backward(rover_ctx *ctx, const float *dh_above, int64_t dh_above_stride, const float *dh_next,
+                                      int64_t dh_next_stride, const float *gates, int64_t gates_stride, const float *h_in,
+                                      int64_t h_in_stride, const uint8_t *reset_mask, const float *w_hh, int32_t M, int32_t H, float *dgi,
+                                      int64_t dgi_stride, float *dgh, int64_t dgh_stride, float *dh_in, int64_t dh_in_stride, void *stream);
+/* What rover_gru_cell_backward would launch — host only, no ctx: "gru_bwd<4>" (128 rows per workgroup) when ceil(M / 128) x ceil(H / 32)
+ * workgroups are at least 512, else "gru_bwd<1>"; "none" for M = 0; NULL where the call would refuse the shapes (M < 0, H outside
+ * 1 .. 2 097 120).  Every limit on M and H lives behind this query. */
+ROVER_API const char *rover_gru_cell_backward_route(int32_t M, int32_t H);
+
 /* rover_gated_sum: out = add + mul * sigmoid(pre), elementwise over [M, N] in one launch (sigmoid as above; the product, then the sum).
  * The belief x_b + l_e * sigmoid(x_a) (student_model.py:79-85; x_a arrives LeakyReLU'd: ga's last Layer has its activation before the
  * nn.Sigmoid) and the decoder's decoded + e * sigmoid(gate) (:121-131).  All four arrays are f32 rows at a row stride in floats; an
@@ -649,6 +695,15 @@ ROVER_API const char *rover_gru_cell_route(int32_t M, int32_t K, int32_t H);
  * input (ROVER_E_INVALID).  M = 0 launches nothing.  Allocates nothing, does not synchronise, capturable. */
 ROVER_API int rover_gated_sum(rover_ctx *ctx, const float *add, int64_t add_stride, const float *mul, int64_t mul_stride, const float *pre,
                               int64_t pre_stride, int32_t M, int32_t N, float *out, int64_t out_stride, void *stream);
+
+/* rover_gated_sum_backward: for out = add + mul * sigmoid(pre) and d_out [M, N], with s = sigmoid(pre) as the forward evaluates it:
+ *   d_mul = d_out * s          d_pre = (d_out * mul) * (s * (1 - s))          (d_add is d_out itself and is not written)
+ * Each output is optional (NULL).  mul and pre may have a row stride of 0 as in the forward; d_out, d_mul and d_pre are per row (stride
+ * >= N): summing the rows of an output whose input was one shared row is the caller's job.  mul is read only for d_pre.  No output
+ * overlaps an input or the other output.  M = 0 launches nothing.  Allocates nothing, does not synchronise, capturable. */
+ROVER_API int rover_gated_sum_backward(rover_ctx *ctx, const float *d_out, int64_t d_out_stride, const float *mul, int64_t mul_stride,
+                                       const float *pre, int64_t pre_stride, int32_t M, int32_t N, float *d_mul, int64_t d_mul_stride,
+                                       float *d_pre, int64_t d_pre_stride, void *stream);
 
 /* ---- tuning knobs ------------------------------------------------------------------------------------- */
 /* name = "raycast_variant": 0 = auto; 1 = one half-wave per ray in env order, every cell block streamed from HBM;

@@ -204,6 +204,14 @@ SYMBOLS = {
     "rover_gru_cell": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rover_gru_cell_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
     "rover_gated_sum": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    "rover_gru_cell_train": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64,
+                                       _P]),
+    "rover_gru_cell_backward": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P,
+                                          C.c_int64, _P, C.c_int64, _P]),
+    "rover_gru_cell_backward_route": (C.c_char_p, [C.c_int32, C.c_int32]),
+    "rover_gated_sum_backward": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P]),
+    "rover_linear_dgrad": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    "rover_linear_dgrad_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
     "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
     "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -799,10 +807,7 @@ class Engine:
         self._chk(w_hh, (3 * hd, hd), torch.float32, "w_hh")
         self._chk(b_ih, (3 * hd,), torch.float32, "b_ih")
         self._chk(b_hh, (3 * hd,), torch.float32, "b_hh")
-        if reset_mask is not None:
-            if reset_mask.dtype == torch.bool:
-                reset_mask = reset_mask.view(torch.uint8)
-            self._chk(reset_mask, (m,), torch.uint8, "reset_mask")
+        reset_mask = self._mask(reset_mask, m)
         self._check(self.lib.rover_gru_cell(self._h, _ptr(x), max(x.stride(0), k), _ptr(h_in), h_in.stride(0) if m > 1 else hd, m, k, hd, _ptr(w_ih) if k > 0 else None,
                                             _ptr(w_hh), _ptr(b_ih), _ptr(b_hh), _ptr(reset_mask), _ptr(h_out), h_out.stride(0) if m > 1 else hd,
                                             _stream(self._dev_index)), "rover_gru_cell")
@@ -813,6 +818,94 @@ class Engine:
         """The instantiation gru_cell runs for [m, k] inputs and a hidden width h ("gru_cell<4>", "gru_cell<1>"); "none" for m = 0, None
         where the call would be refused.  Host only."""
         return cls._route(load().rover_gru_cell_route(int(m), int(k), int(h)))
+
+    def gru_cell_train(self, x, h_in, w_ih, w_hh, b_ih, b_hh, h_out, gates, reset_mask=None):
+        """gru_cell that also stores ``gates`` [m, 4h] = r | z | n | q for gru_cell_backward (rover_gru_cell_train); h_out has gru_cell's bits."""
+        what = "gru_cell_train"
+        self._f32_rows(x, "x", what)
+        m, k = x.shape
+        hd = w_hh.shape[1] if w_hh is not None and w_hh.dim() == 2 else -1
+        self._f32_rows(h_in, "h_in", what, (m, hd))
+        self._f32_rows(h_out, "h_out", what, (m, hd))
+        self._f32_rows(gates, "gates", what, (m, 4 * hd))
+        if k > 0:
+            self._chk(w_ih, (3 * hd, k), torch.float32, "w_ih")
+        self._chk(w_hh, (3 * hd, hd), torch.float32, "w_hh")
+        self._chk(b_ih, (3 * hd,), torch.float32, "b_ih")
+        self._chk(b_hh, (3 * hd,), torch.float32, "b_hh")
+        reset_mask = self._mask(reset_mask, m)
+        st = lambda t, cols: t.stride(0) if m > 1 else cols
+        self._check(self.lib.rover_gru_cell_train(self._h, _ptr(x), max(x.stride(0), k), _ptr(h_in), st(h_in, hd), m, k, hd, _ptr(w_ih) if k > 0 else None,
+                                                  _ptr(w_hh), _ptr(b_ih), _ptr(b_hh), _ptr(reset_mask), _ptr(h_out), st(h_out, hd), _ptr(gates),
+                                                  st(gates, 4 * hd), _stream(self._dev_index)), "rover_gru_cell_train")
+        return h_out
+
+    def _mask(self, reset_mask, m):
+        """an optional [m] bool / uint8 reset mask as the uint8 tensor the C ABI reads"""
+        if reset_mask is not None:
+            if reset_mask.dtype == torch.bool:
+                reset_mask = reset_mask.view(torch.uint8)
+            self._chk(reset_mask, (m,), torch.uint8, "reset_mask")
+        return reset_mask
+
+    def gru_cell_backward(self, dh_above, dh_next, gates, h_in, w_hh, dgi, dgh, dh_in, reset_mask=None):
+        """rover_gru_cell_backward: one layer, one time step, one launch.  dh_above / dh_next (or None) / h_in / dh_in [m, h], gates
+        [m, 4h] as gru_cell_train stored them, dgi / dgh [m, 3h]; all float32 rows with unit column stride (slices will do)."""
+        what = "gru_cell_backward"
+        hd = w_hh.shape[1] if w_hh is not None and w_hh.dim() == 2 else -1
+        m = self._f32_rows(dh_above, "dh_above", what).shape[0]
+        for t, name, cols in ((dh_above, "dh_above", hd), (gates, "gates", 4 * hd), (h_in, "h_in", hd), (dgi, "dgi", 3 * hd), (dgh, "dgh", 3 * hd),
+                              (dh_in, "dh_in", hd)) + (() if dh_next is None else ((dh_next, "dh_next", hd),)):
+            self._f32_rows(t, name, what, (m, cols))
+        self._chk(w_hh, (3 * hd, hd), torch.float32, "w_hh")
+        reset_mask = self._mask(reset_mask, m)
+        st = lambda t, cols: 0 if t is None else (t.stride(0) if m > 1 else cols)
+        self._check(self.lib.rover_gru_cell_backward(self._h, _ptr(dh_above), st(dh_above, hd), _ptr(dh_next), st(dh_next, hd), _ptr(gates), st(gates, 4 * hd),
+                                                     _ptr(h_in), st(h_in, hd), _ptr(reset_mask), _ptr(w_hh), m, hd, _ptr(dgi), st(dgi, 3 * hd), _ptr(dgh),
+                                                     st(dgh, 3 * hd), _ptr(dh_in), st(dh_in, hd), _stream(self._dev_index)), "rover_gru_cell_backward")
+        return dh_in
+
+    @classmethod
+    def gru_cell_backward_route(cls, m, h):
+        """The instantiation gru_cell_backward runs ("gru_bwd<4>", "gru_bwd<1>"); "none" for m = 0, None where refused.  Host only."""
+        return cls._route(load().rover_gru_cell_backward_route(int(m), int(h)))
+
+    def gated_sum_backward(self, d_out, mul, pre, d_mul=None, d_pre=None):
+        """rover_gated_sum_backward: d_mul = d_out * sigmoid(pre), d_pre = (d_out * mul) * s (1 - s) over [m, n]; each output optional.
+        mul / pre may be one row expanded over the rows (row stride 0); the outputs are per row."""
+        what = "gated_sum_backward"
+        m, n = self._f32_rows(d_out, "d_out", what).shape
+        self._f32_rows(pre, "pre", what, (m, n))
+        for t, name in ((mul, "mul"), (d_mul, "d_mul"), (d_pre, "d_pre")):
+            if t is not None:
+                self._f32_rows(t, name, what, (m, n))
+        if d_pre is not None and mul is None:
+            raise RoverError(f"{what}: d_pre needs mul")
+        si = lambda t: 0 if t is None else (t.stride(0) if m > 1 else n)
+        so = lambda t: 0 if t is None else max(t.stride(0), n)
+        self._check(self.lib.rover_gated_sum_backward(self._h, _ptr(d_out), so(d_out), _ptr(mul), si(mul), _ptr(pre), si(pre), m, n, _ptr(d_mul), so(d_mul),
+                                                      _ptr(d_pre), so(d_pre), _stream(self._dev_index)), "rover_gated_sum_backward")
+
+    def linear_dgrad(self, y, dy, weight, activation, dx):
+        """rover_linear_dgrad: dx = (dy * act'(y)) @ weight for any widths; ``y`` may be None with activation None.  Enqueues only."""
+        what = "linear_dgrad"
+        n, k = weight.shape
+        m = self._f32_rows(dy, "dy", what).shape[0]
+        if dy.shape[1] != n:
+            raise RoverError(f"{what}: dy must be [{m},{n}]")
+        if y is not None or self.ACTIVATIONS[activation] != 0:
+            self._f32_rows(y, "y", what, (m, n))
+        self._chk(weight, (n, k), torch.float32, "weight")
+        self._f32_rows(dx, "dx", what, (m, k))
+        st = lambda t, cols: 0 if t is None else max(t.stride(0), cols)
+        self._check(self.lib.rover_linear_dgrad(self._h, _ptr(y), st(y, n), _ptr(dy), st(dy, n), m, k, _ptr(weight), n, self.ACTIVATIONS[activation],
+                                                _ptr(dx), st(dx, k), _stream(self._dev_index)), "rover_linear_dgrad")
+        return dx
+
+    @classmethod
+    def linear_dgrad_route(cls, m, k, n):
+        """What linear_dgrad launches ("dgrad<1,1>x10", ...); "none" for m = 0, None where the call would be refused.  Host only."""
+        return cls._route(load().rover_linear_dgrad_route(int(m), int(k), int(n)))
 
     def gated_sum(self, add, mul, pre, out):
         """out = add + mul * sigmoid(pre) over [m, n] (rover_gated_sum), one launch.  All four are float32 GPU matrices with unit column
@@ -873,13 +966,15 @@ class Engine:
     def linear_backward(self, x, y, dy, weight, activation, dx=None, dweight=None, dbias=None):
         """rover_linear_backward: the backward of ``y = act(x @ weight.T + bias)``.  ``y`` is the layer's output as linear_forward wrote
         it, ``dy`` the gradient at it; x / y / dy / dx may be column slices of wider row-major tensors; ``dweight`` [n, k] and ``dbias``
-        [n] are contiguous.  Each output is optional (None: not computed); ``x`` may be None without ``dweight``.  Enqueues only."""
+        [n] are contiguous.  Each output is optional (None: not computed); ``x`` may be None without ``dweight``, ``y`` with activation None.
+        Enqueues only."""
         what = "linear_backward"
         n, k = weight.shape
         m = self._f32_rows(dy, "dy", what).shape[0]
         if dy.shape[1] != n:
             raise RoverError(f"{what}: dy must be [{m},{n}]")
-        self._f32_rows(y, "y", what, (m, n))
+        if y is not None or self.ACTIVATIONS[activation] != 0:        # without an activation the derivative needs no y
+            self._f32_rows(y, "y", what, (m, n))
         if k > 0:
             self._chk(weight, (n, k), torch.float32, "weight")
         if x is not None:

@@ -1740,6 +1740,32 @@ const char* rover_linear_backward_route(int32_t M, int32_t K, int32_t N, int32_t
     return M == 0 ? "zero" : linear_backward_route_name(r);
 }
 
+int rover_linear_dgrad(rover_ctx* c, const float* y, int64_t y_stride, const float* dy, int64_t dy_stride, int32_t M, int32_t K, const float* weight,
+                       int32_t N, int32_t activation, float* dx, int64_t dx_stride, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    const LinearRoute r = linear_dgrad_route(M, N, K);
+    if (!r.nw || activation < 0 || activation > 4)
+        return fail(c, ROVER_E_INVALID, "linear_dgrad: M=%d K=%d N=%d act=%d outside M >= 0, 1 <= K <= %d, N >= 1, act 0 .. 4", M, K, N, activation, 32 * 65535);
+    if (M == 0) return ROVER_OK;
+    if (!dy || (activation != 0 && !y) || !weight || !dx) return fail(c, ROVER_E_INVALID, "linear_dgrad: dy, y (with an activation), weight and dx must be given");
+    const int64_t max_stride = (int64_t)1 << 40;
+    if (dy_stride < N || dy_stride > max_stride || (activation != 0 && (y_stride < N || y_stride > max_stride)) || dx_stride < K || dx_stride > max_stride)
+        return fail(c, ROVER_E_INVALID, "linear_dgrad: a row stride is shorter than its row or above 2^40");
+    const Span odx = span_of(dx, dx_stride, M, K, 4);
+    for (const Span& in : {span_of(dy, dy_stride, M, N, 4), span_of(activation ? y : nullptr, y_stride, M, N, 4), span_of(weight, K, N, K, 4)})
+        if (in.lo && overlap(odx, in)) return fail(c, ROVER_E_INVALID, "linear_dgrad: dx overlaps an array the call reads");
+    USE_DEVICE(c);
+    LinearBwdArgs a{nullptr, 0, y, y_stride, dy, dy_stride, weight, dx, dx_stride, nullptr, nullptr, M, K, N, activation};
+    HIP_TRY(c, launch_linear_dgrad(a, r, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+const char* rover_linear_dgrad_route(int32_t M, int32_t K, int32_t N) {
+    const LinearRoute r = linear_dgrad_route(M, N, K);
+    if (!r.nw) return nullptr;
+    return M == 0 ? "none" : linear_dgrad_route_name(r);
+}
+
 int rover_ppo_loss(rover_ctx* c, const rover_ppo_loss_desc* d, void* stream) {
     if (!c) return ROVER_E_INVALID;
     if (!d) return fail(c, ROVER_E_INVALID, "ppo_loss: null descriptor");
@@ -1920,28 +1946,82 @@ int rover_optim_step(rover_ctx* c, int32_t handle, const rover_optim_step_desc* 
 }
 
 // ---- the student policy's recurrent block (rover_gru.hip) ----
-int rover_gru_cell(rover_ctx* c, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K, int32_t H,
-                   const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
-                   int64_t h_out_stride, void* stream) {
+static int gru_cell_run(rover_ctx* c, const char* what, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K,
+                        int32_t H, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
+                        int64_t h_out_stride, bool train, float* gates, int64_t gates_stride, void* stream) {
     if (!c) return ROVER_E_INVALID;
-    if (!gru_cell_route(M, K, H).nw) return fail(c, ROVER_E_INVALID, "gru_cell: M=%d K=%d H=%d outside M >= 0, K >= 0, 1 <= H <= %d", M, K, H, 32 * 65535);
+    if (!gru_cell_route(M, K, H).nw) return fail(c, ROVER_E_INVALID, "%s: M=%d K=%d H=%d outside M >= 0, K >= 0, 1 <= H <= %d", what, M, K, H, 32 * 65535);
     if (M == 0) return ROVER_OK;                   // nothing is read or written: no pointer is required
-    if (!h_in || !w_hh || !h_out || (K > 0 && (!x || !w_ih))) return fail(c, ROVER_E_INVALID, "gru_cell: h_in, w_hh, h_out and (K > 0) x, w_ih must be given");
+    if (!h_in || !w_hh || !h_out || (K > 0 && (!x || !w_ih))) return fail(c, ROVER_E_INVALID, "%s: h_in, w_hh, h_out and (K > 0) x, w_ih must be given", what);
+    if (train && !gates) return fail(c, ROVER_E_INVALID, "%s: gates must be given", what);
     const int64_t max_stride = (int64_t)1 << 40;
-    if (h_in_stride < H || h_in_stride > max_stride || h_out_stride < H || h_out_stride > max_stride || (K > 0 && (x_stride < K || x_stride > max_stride)))
-        return fail(c, ROVER_E_INVALID, "gru_cell: a row stride is shorter than its row or above 2^40");
+    if (h_in_stride < H || h_in_stride > max_stride || h_out_stride < H || h_out_stride > max_stride || (K > 0 && (x_stride < K || x_stride > max_stride)) ||
+        (train && (gates_stride < (int64_t)4 * H || gates_stride > max_stride)))
+        return fail(c, ROVER_E_INVALID, "%s: a row stride is shorter than its row or above 2^40", what);
     const Span out = span_of(h_out, h_out_stride, M, H, 4);
     const int32_t G = 3 * H;                       // gate rows (H <= 32 x 65 535: no overflow)
     const Span ins[7] = {span_of(h_in, h_in_stride, M, H, 4), span_of(K > 0 ? x : nullptr, x_stride, M, K, 4), span_of(K > 0 ? w_ih : nullptr, K, G, K, 4),
                          span_of(w_hh, H, G, H, 4), span_of(b_ih, G, 1, G, 4), span_of(b_hh, G, 1, G, 4), span_of(reset_mask, M, 1, M, 1)};
-    for (int i = 0; i < 7; ++i)
+    const Span og = span_of(train ? gates : nullptr, gates_stride, M, 4 * H, 4);
+    for (int i = 0; i < 7; ++i) {
         if (ins[i].lo && overlap(out, ins[i]))
-            return fail(c, ROVER_E_INVALID, i == 0 ? "gru_cell: h_out overlaps h_in (a tile of h' needs whole rows of h that other workgroups still read)"
-                                                   : "gru_cell: h_out overlaps an array the call reads");
+            return fail(c, ROVER_E_INVALID, i == 0 ? "%s: h_out overlaps h_in (a tile of h' needs whole rows of h that other workgroups still read)"
+                                                   : "%s: h_out overlaps an array the call reads", what);
+        if (og.lo && ins[i].lo && overlap(og, ins[i])) return fail(c, ROVER_E_INVALID, "%s: gates overlaps an array the call reads", what);
+    }
+    if (og.lo && overlap(og, out)) return fail(c, ROVER_E_INVALID, "%s: gates overlaps h_out", what);
     USE_DEVICE(c);
-    GruArgs a{x, x_stride, h_in, h_in_stride, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, M, K, H};
+    GruArgs a{x, x_stride, h_in, h_in_stride, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, M, K, H, train ? gates : nullptr, gates_stride};
     HIP_TRY(c, launch_gru_cell(a, (hipStream_t)stream));
     return ROVER_OK;
+}
+
+int rover_gru_cell(rover_ctx* c, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K, int32_t H,
+                   const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
+                   int64_t h_out_stride, void* stream) {
+    return gru_cell_run(c, "gru_cell", x, x_stride, h_in, h_in_stride, M, K, H, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, false, nullptr, 0, stream);
+}
+
+int rover_gru_cell_train(rover_ctx* c, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K, int32_t H,
+                         const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
+                         int64_t h_out_stride, float* gates, int64_t gates_stride, void* stream) {
+    return gru_cell_run(c, "gru_cell_train", x, x_stride, h_in, h_in_stride, M, K, H, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, true, gates,
+                        gates_stride, stream);
+}
+
+int rover_gru_cell_backward(rover_ctx* c, const float* dh_above, int64_t dh_above_stride, const float* dh_next, int64_t dh_next_stride, const float* gates,
+                            int64_t gates_stride, const float* h_in, int64_t h_in_stride, const uint8_t* reset_mask, const float* w_hh, int32_t M, int32_t H,
+                            float* dgi, int64_t dgi_stride, float* dgh, int64_t dgh_stride, float* dh_in, int64_t dh_in_stride, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    if (!gru_cell_backward_route(M, H).nw) return fail(c, ROVER_E_INVALID, "gru_cell_backward: M=%d H=%d outside M >= 0, 1 <= H <= %d", M, H, 32 * 65535);
+    if (M == 0) return ROVER_OK;
+    if (!dh_above || !gates || !h_in || !w_hh || !dgi || !dgh || !dh_in)
+        return fail(c, ROVER_E_INVALID, "gru_cell_backward: dh_above, gates, h_in, w_hh, dgi, dgh and dh_in must be given");
+    const int64_t max_stride = (int64_t)1 << 40, G = (int64_t)3 * H;
+    auto bad = [&](int64_t st, int64_t cols) { return st < cols || st > max_stride; };
+    if (bad(dh_above_stride, H) || (dh_next && bad(dh_next_stride, H)) || bad(gates_stride, 4 * (int64_t)H) || bad(h_in_stride, H) || bad(dgi_stride, G) ||
+        bad(dgh_stride, G) || bad(dh_in_stride, H))
+        return fail(c, ROVER_E_INVALID, "gru_cell_backward: a row stride is shorter than its row or above 2^40");
+    const Span ins[6] = {span_of(dh_above, dh_above_stride, M, H, 4), span_of(dh_next, dh_next_stride, M, H, 4), span_of(gates, gates_stride, M, 4 * H, 4),
+                         span_of(h_in, h_in_stride, M, H, 4), span_of(reset_mask, M, 1, M, 1), span_of(w_hh, H, 3 * H, H, 4)};
+    const Span outs[3] = {span_of(dgi, dgi_stride, M, 3 * H, 4), span_of(dgh, dgh_stride, M, 3 * H, 4), span_of(dh_in, dh_in_stride, M, H, 4)};
+    for (int i = 0; i < 3; ++i) {
+        for (const Span& in : ins)
+            if (in.lo && overlap(outs[i], in)) return fail(c, ROVER_E_INVALID, "gru_cell_backward: an output overlaps an array the call reads");
+        for (int j = i + 1; j < 3; ++j)
+            if (overlap(outs[i], outs[j])) return fail(c, ROVER_E_INVALID, "gru_cell_backward: two outputs overlap");
+    }
+    USE_DEVICE(c);
+    GruBwdArgs a{dh_above, dh_above_stride, dh_next, dh_next_stride, gates, gates_stride, h_in, h_in_stride, reset_mask, w_hh,
+                 dgi, dgi_stride, dgh, dgh_stride, dh_in, dh_in_stride, M, H};
+    HIP_TRY(c, launch_gru_cell_backward(a, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+const char* rover_gru_cell_backward_route(int32_t M, int32_t H) {
+    const GruRoute r = gru_cell_backward_route(M, H);
+    if (!r.nw) return nullptr;
+    return M == 0 ? "none" : gru_cell_backward_route_name(r);
 }
 
 const char* rover_gru_cell_route(int32_t M, int32_t K, int32_t H) {
@@ -1966,6 +2046,29 @@ int rover_gated_sum(rover_ctx* c, const float* add, int64_t add_stride, const fl
     USE_DEVICE(c);
     GatedSumArgs a{add, add_stride, mul, mul_stride, pre, pre_stride, out, out_stride, M, N};
     HIP_TRY(c, launch_gated_sum(a, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+int rover_gated_sum_backward(rover_ctx* c, const float* d_out, int64_t d_out_stride, const float* mul, int64_t mul_stride, const float* pre,
+                             int64_t pre_stride, int32_t M, int32_t N, float* d_mul, int64_t d_mul_stride, float* d_pre, int64_t d_pre_stride, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    if (M < 0 || N < 1 || (int64_t)M * N >= (int64_t)1 << 38)
+        return fail(c, ROVER_E_INVALID, "gated_sum_backward: M=%d N=%d outside M >= 0, N >= 1, M N < 2^38", M, N);
+    if (M == 0 || (!d_mul && !d_pre)) return ROVER_OK;
+    if (!d_out || !pre || (d_pre && !mul)) return fail(c, ROVER_E_INVALID, "gated_sum_backward: d_out, pre and (for d_pre) mul must be given");
+    const int64_t max_stride = (int64_t)1 << 40;
+    if ((pre_stride != 0 && pre_stride < N) || pre_stride > max_stride || (d_pre && ((mul_stride != 0 && mul_stride < N) || mul_stride > max_stride)))
+        return fail(c, ROVER_E_INVALID, "gated_sum_backward: an input's row stride is neither 0 nor >= N = %d, or above 2^40", N);
+    if (d_out_stride < N || d_out_stride > max_stride || (d_mul && (d_mul_stride < N || d_mul_stride > max_stride)) ||
+        (d_pre && (d_pre_stride < N || d_pre_stride > max_stride)))
+        return fail(c, ROVER_E_INVALID, "gated_sum_backward: a row stride of d_out, d_mul or d_pre is shorter than its row or above 2^40");
+    const Span om = span_of(d_mul, d_mul_stride, M, N, 4), op = span_of(d_pre, d_pre_stride, M, N, 4);
+    for (const Span& in : {span_of(d_out, d_out_stride, M, N, 4), span_of(d_pre ? mul : nullptr, mul_stride, M, N, 4), span_of(pre, pre_stride, M, N, 4)})
+        if (in.lo && ((om.lo && overlap(om, in)) || (op.lo && overlap(op, in)))) return fail(c, ROVER_E_INVALID, "gated_sum_backward: an output overlaps an input");
+    if (om.lo && op.lo && overlap(om, op)) return fail(c, ROVER_E_INVALID, "gated_sum_backward: d_mul overlaps d_pre");
+    USE_DEVICE(c);
+    GatedSumBwdArgs a{d_out, d_out_stride, mul, mul_stride, pre, pre_stride, d_mul, d_mul_stride, d_pre, d_pre_stride, M, N};
+    HIP_TRY(c, launch_gated_sum_backward(a, (hipStream_t)stream));
     return ROVER_OK;
 }
 

@@ -213,12 +213,31 @@ struct GruArgs {
     const uint8_t* reset_mask;                 // [M] or NULL: a non-zero byte reads the row's h_in as zero
     float* h_out; int64_t h_out_stride;        // [M, H]; overlaps nothing the call reads
     int32_t M, K, H;
+    float* gates; int64_t gates_stride;        // rover_gru_cell_train only: [M, 4H] = r | z | n | q (q = s_hn + b_hn); else NULL, unread
 };
 // the instantiation a cell runs: gru_cell_kernel<nw> on a grid of row slabs x 32-column tiles of the hidden state; nw = 0: refused
 struct GruRoute { int nw; };
 GruRoute gru_cell_route(int M, int K, int H);
 const char* gru_cell_route_name(const GruRoute& r);       // "gru_cell<4>", or NULL
-hipError_t launch_gru_cell(const GruArgs& a, hipStream_t s);
+hipError_t launch_gru_cell(const GruArgs& a, hipStream_t s);                 // a.gates set: the training instantiation of the same route
+
+// The backward of one cell (rover_gru_cell_backward of the C ABI, validated; rover_gru.hip): dgi, dgh [M, 3H] and dh_in [M, H] from the
+// gradient at h' (dh_above + dh_next), the gates the training forward stored and w_hh
+struct GruBwdArgs {
+    const float* dh_above; int64_t dh_above_stride;    // [M, H]
+    const float* dh_next; int64_t dh_next_stride;      // [M, H] or NULL (zeros)
+    const float* gates; int64_t gates_stride;          // [M, 4H] r | z | n | q
+    const float* h_in; int64_t h_in_stride;            // [M, H]
+    const uint8_t* reset_mask;                         // [M] or NULL
+    const float* w_hh;                                 // [3H][H]
+    float* dgi; int64_t dgi_stride;                    // [M, 3H]
+    float* dgh; int64_t dgh_stride;                    // [M, 3H]
+    float* dh_in; int64_t dh_in_stride;                // [M, H]
+    int32_t M, H;
+};
+GruRoute gru_cell_backward_route(int M, int H);
+const char* gru_cell_backward_route_name(const GruRoute& r);     // "gru_bwd<4>", or NULL
+hipError_t launch_gru_cell_backward(const GruBwdArgs& a, hipStream_t s);
 
 // out = add + mul * sigmoid(pre) over [M, N] (rover_gated_sum; rover_gru.hip); an input's row stride may be 0 (one row for all)
 struct GatedSumArgs {
@@ -227,6 +246,13 @@ struct GatedSumArgs {
     int32_t M, N;
 };
 hipError_t launch_gated_sum(const GatedSumArgs& a, hipStream_t s);
+// its backward: d_mul = d_out s, d_pre = (d_out mul) (s (1 - s)), s = sigmoid(pre); each output optional, per row
+struct GatedSumBwdArgs {
+    const float* d_out; int64_t d_out_stride; const float* mul; int64_t mul_stride; const float* pre; int64_t pre_stride;
+    float* d_mul; int64_t d_mul_stride; float* d_pre; int64_t d_pre_stride;
+    int32_t M, N;
+};
+hipError_t launch_gated_sum_backward(const GatedSumBwdArgs& a, hipStream_t s);
 
 // a chain of 2 or 4 layers in one kernel (rover_mlp.hip): y = L_n(... L_1(x)), L_i(v) = act_i(W_i v + b_i)
 struct ChainArgs {
@@ -319,6 +345,10 @@ LinearBwdRoute linear_backward_route(int M, int K, int N, bool want_dx);
 const char* linear_backward_route_name(const LinearBwdRoute& r);      // "wgrad<3,4>/64;dgrad<1,4>", or NULL; valid until the thread's next call
 size_t linear_backward_scratch_floats(const LinearBwdRoute& r, int K, int N);
 hipError_t launch_linear_backward(const LinearBwdArgs& a, const LinearBwdRoute& r, float* scratch, hipStream_t s);
+// dx alone for any N >= 1 and K >= 1 (rover_linear_dgrad): linear_dgrad_kernel<nt, nw> on ny column tiles of dx; nw = 0: refused
+LinearRoute linear_dgrad_route(int M, int N, int K);
+const char* linear_dgrad_route_name(const LinearRoute& r);      // "dgrad<2,4>x5", or NULL; valid until the thread's next call
+hipError_t launch_linear_dgrad(const LinearBwdArgs& a, const LinearRoute& r, hipStream_t s);
 
 // The PPO minibatch loss and its gradients at the nets' outputs (rover_ppo_loss of the C ABI, validated; rover_train.hip)
 constexpr uint32_t PPO_MAX_BLOCKS = 1024;  // most blocks = most partials of 3 + GAUSS_MAX_A doubles: the ctx holds them since rover_create

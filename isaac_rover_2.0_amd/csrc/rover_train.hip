@@ -320,6 +320,33 @@ hipError_t launch_linear_backward(const LinearBwdArgs& a, const LinearBwdRoute& 
     return hipSuccess;
 }
 
+// ---- dx alone, any width (rover_linear_dgrad) ----------------------------------------------------------------------------------------
+// The same kernel on a route of its own: linear_dgrad_kernel already tiles K over blockIdx.y and walks N in slabs, so neither width has
+// a limit but the grid's (65 535 column tiles).  One wave per 32 x 32 tile of dx below 65 536 rows (the forward's switch point); from
+// there 128-row workgroups that hold two column tiles (one when K <= 32), which halves the re-reads of the dz slab.  Reasoned, not measured.
+LinearRoute linear_dgrad_route(int M, int N, int K) {
+    if (M < 0 || N < 1 || K < 1) return LinearRoute{0, 0, 0};
+    const int64_t kt = ((int64_t)K + 31) / 32;
+    LinearRoute r = M >= 128 * 512 ? LinearRoute{4, K > 32 ? 2 : 1, 0} : LinearRoute{1, 1, 0};
+    const int64_t ny = (kt + r.nt - 1) / r.nt;
+    if (ny > 65535) return LinearRoute{0, 0, 0};
+    r.ny = (int)ny;
+    return r;
+}
+const char* linear_dgrad_route_name(const LinearRoute& r) {
+    if (!r.nw) return nullptr;
+    static thread_local char buf[48];
+    snprintf(buf, sizeof buf, "dgrad<%d,%d>x%d", r.nt, r.nw, r.ny);
+    return buf;
+}
+hipError_t launch_linear_dgrad(const LinearBwdArgs& a, const LinearRoute& r, hipStream_t s) {
+    if (a.M == 0) return hipSuccess;
+    if (r.nw == 4) return launch_dgrad_nw<4>(a, r, s);
+    if (r.nw != 1 || r.nt != 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((linear_dgrad_kernel<1, 1>), dim3((uint32_t)((a.M + 31) / 32), (uint32_t)r.ny), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
 // ---- the PPO loss ------------------------------------------------------------------------------------------------------------------
 constexpr int PPO_BLOCK = 256;
 constexpr int PPO_NSUM = 3 + GAUSS_MAX_A;                            // surrogate, squared value error, kl, then the A log-std sums

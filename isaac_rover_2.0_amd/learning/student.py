@@ -18,7 +18,13 @@ Things the reference does that are kept as they are:
 
 The hidden state lives in ``self.h [n_layers, E, H]`` at a fixed address.  A cell may not write over the state it reads (a tile of h'
 needs whole rows of h), so ``act()`` writes the new state into a scratch tensor and copies it back on the device: the
-same launches every call, capturable once after a warm-up.  No back-propagation through time, no distillation loop.
+same launches every call, capturable once after a warm-up.
+
+Training: ``forward_train()`` is ``forward()`` run so that a backward can follow — time-major inside, every layer
+unfused so that its output exists, the GRU cells through ``rover_gru_cell_train`` (which also stores the gates), everything that is
+not recurrent ONCE over all T·B rows — and ``backward()`` is back-propagation through time written out on ``rover_gru_cell_backward``,
+``rover_linear_dgrad``, ``rover_gated_sum_backward`` and ``rover_linear_backward``; it leaves every parameter's gradient in its
+``.grad``.  The distillation loss and the update loop live in ``learning/distill.py``.
 """
 from __future__ import annotations
 
@@ -152,6 +158,7 @@ class StudentPolicy:
         self._params = OrderedDict((k, self._params[k]) for k in shapes)          # the reference's order
         self.h = None
         self._bufs, self._plans, self._chunks = {}, {}, {}
+        self._saved = None                     # what the last forward_train() kept for backward()
 
     # ---- interop with the reference's nn.Module parameter names --------------------------------------------
     def state_dict(self):
@@ -263,3 +270,186 @@ class StudentPolicy:
             self._step(x[:, t], list(cur), list(nxt), None, actions[:, t], est[:, t])
             cur, nxt = nxt, cur
         return actions, est, cur
+
+    # ---- training: the forward that keeps what the backward needs, and back-propagation through time ---------------------
+    def parameters(self):
+        """The trainable tensors in ``state_dict()`` order: every parameter but ``MLP.log_std_parameter``, which takes no part in
+        ``forward()`` (the student's action is the Tanh mean) and so never has a gradient."""
+        return [v for k, v in self._params.items() if k != "MLP.log_std_parameter"]
+
+    @staticmethod
+    def _grad_of(p):
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+        return p.grad
+
+    def _run_train(self, key, x, layers, out):
+        """``layers`` over x into ``out``, layer by layer; the input and every layer's output are kept for the backward."""
+        m, ys = x.shape[0], [x]
+        for i, layer in enumerate(layers):
+            last = i == len(layers) - 1
+            ys.append(self._linear(ys[-1], layer, out if last else self._buf(("t", key, i), m, layer.weight.shape[0])))
+        self._saved[key] = ys
+        return out
+
+    def forward_train(self, x, h0, reset=None):
+        """``forward()`` with a backward to follow: x [B, T, F], h0 [n_layers, B, H], ``reset`` optional [B, T] bool / uint8 (a marked
+        row starts step t from a zero hidden state) -> (actions [B, T, A], estimated [B, T, S + D], h [n_layers, B, H]).  The first two
+        are views of buffers of this object, overwritten by the next call."""
+        if x is None or x.dim() != 3:
+            raise ValueError("StudentPolicy.forward_train: x must be [B, T, F]")
+        b, t_len, f = x.shape
+        p, ns, nd, hd = self.info["proprioceptive"], self.info["sparse"], self.info["dense"], self.hidden_dim
+        if f < p + ns + nd:
+            raise ValueError(f"StudentPolicy.forward_train: x has {f} columns, needs proprioceptive + sparse + dense = {p + ns + nd}")
+        if h0 is None or tuple(h0.shape) != (self.n_layers, b, hd):
+            raise ValueError(f"StudentPolicy.forward_train: h0 must be [{self.n_layers}, {b}, {hd}]")
+        if reset is not None and tuple(reset.shape) != (b, t_len):
+            raise ValueError(f"StudentPolicy.forward_train: reset must be [{b}, {t_len}]")
+        eng, rows, ex = self.engine, t_len * b, ns + nd
+        ef = self.encoder1[-1].weight.shape[0]
+        xt = self._buf(("t", "x"), rows, f)                          # time-major: row t B + b
+        xt.view(t_len, b, f).copy_(x.transpose(0, 1))
+        h0 = h0.to(torch.float32).contiguous()
+        rs = None if reset is None else reset.to(torch.uint8).t().contiguous()
+        self._saved = {"shape": (b, t_len, f), "x": xt, "h0": h0, "reset": rs}
+        cat, mlp_in = self._buf(("t", "cat"), rows, p + 2 * ef), self._buf(("t", "mlp_in"), rows, p + 2 * ef)
+        cat[:, :p] = xt[:, :p]
+        mlp_in[:, :p] = xt[:, :p]
+        self._run_train("enc1", xt[:, f - ex:f - nd], self.encoder1, cat[:, p:p + ef])
+        self._run_train("enc2", xt[:, f - nd:], self.encoder2, cat[:, p + ef:p + 2 * ef])
+        seq, outs, gates = cat.view(t_len, b, p + 2 * ef), [], []
+        for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(self.gru):      # layer l runs all T steps before layer l + 1
+            out = self._buf(("t", "out", l), rows, hd).view(t_len, b, hd)
+            gt = self._buf(("t", "gates", l), rows, 4 * hd).view(t_len, b, 4 * hd)
+            for t in range(t_len):
+                eng.gru_cell_train(seq[t], h0[l] if t == 0 else out[t - 1], w_ih, w_hh, b_ih, b_hh, out[t], gt[t], reset_mask=None if rs is None else rs[t])
+            outs.append(out)
+            gates.append(gt)
+            seq = out
+        self._saved["out"], self._saved["gates"] = outs, gates
+        top = seq.view(rows, hd)
+        x_b = self._run_train("gb", top, self.gb, self._buf(("t", "x_b"), rows, 2 * ef))
+        x_a = self._run_train("ga", top, self.ga, self._buf(("t", "x_a"), rows, 2 * ef))
+        eng.gated_sum(x_b, cat[:, p:], x_a, mlp_in[:, p:])
+        actions = self._run_train("mlp", mlp_in, self.network, self._buf(("t", "actions"), rows, self.info["actions"]))
+        last = seq[:, b - 1]                                         # [T, H]: the last batch row's sequence (module docstring)
+        gate = self._run_train("gate", last, self.gate_encoder, self._buf(("t", "gate"), t_len, ex))
+        dec = self._run_train("dec", last, self.decoder, self._buf(("t", "decoded"), t_len, ex))
+        est = self._buf(("t", "estimated"), rows, ex).view(t_len, b, ex)
+        x3 = xt.view(t_len, b, f)
+        for t in range(t_len):                                       # one shared row of dec / gate per time step (row stride 0)
+            eng.gated_sum(dec[t:t + 1].expand(b, ex), x3[t][:, f - ex:], gate[t:t + 1].expand(b, ex), est[t])
+        h = torch.stack([o[t_len - 1] for o in outs])
+        return actions.view(t_len, b, -1).transpose(0, 1), est.transpose(0, 1), h
+
+    def _wgrad(self, x, y, dy, weight, bias, activation):
+        """dweight / dbias of one layer over all rows, in row blocks of the width linear_backward takes (a row block of [N][K] is contiguous)."""
+        m, (n, k) = dy.shape[0], weight.shape
+        c = self._chunks.get(("w", m, k, n))
+        if c is None:
+            c = n
+            while c > 1 and self.engine.linear_backward_route(m, k, c, False) is None:
+                c = (c + 1) // 2
+            self._chunks[("w", m, k, n)] = c
+        gw, gb = self._grad_of(weight), self._grad_of(bias)
+        for lo in range(0, n, c):
+            hi = min(n, lo + c)
+            self.engine.linear_backward(x, None if y is None else y[:, lo:hi], dy[:, lo:hi], weight[lo:hi], activation, dweight=gw[lo:hi], dbias=gb[lo:hi])
+
+    def _layer_backward(self, x, y, dy, layer, dx):
+        """One Layer back: its weight.grad / bias.grad, and dx (None: not wanted).  One linear_backward where the library takes the widths,
+        else row blocks for the weights and linear_dgrad for dx."""
+        m, (n, k) = dy.shape[0], layer.weight.shape
+        one = self._chunks.get(("b", m, k, n, dx is not None))
+        if one is None:
+            one = self._chunks[("b", m, k, n, dx is not None)] = self.engine.linear_backward_route(m, k, n, dx is not None) is not None
+        if one:
+            self.engine.linear_backward(x, y, dy, layer.weight, layer.activation, dx=dx, dweight=self._grad_of(layer.weight), dbias=self._grad_of(layer.bias))
+            return dx
+        self._wgrad(x, y, dy, layer.weight, layer.bias, layer.activation)
+        if dx is not None:
+            self.engine.linear_dgrad(y, dy, layer.weight, layer.activation, dx)
+        return dx
+
+    def _chain_backward(self, key, layers, dy, want_dx):
+        """The chain ``key`` of the last forward_train back from dy at its output -> the gradient at its input (None unless ``want_dx``)."""
+        ys = self._saved[key]
+        for i in range(len(layers) - 1, -1, -1):
+            x = ys[i]
+            dx = self._buf(("t", "d", key, i), x.shape[0], x.shape[1]) if (i > 0 or want_dx) else None
+            dy = self._layer_backward(x, ys[i + 1], dy, layers[i], dx)
+        return dy
+
+    def backward(self, d_actions, d_estimated=None):
+        """Back-propagation through time from the loss gradients at the last ``forward_train()``'s outputs: d_actions [B, T, A],
+        d_estimated [B, T, S + D] or None (no reconstruction term) -> dh0 [n_layers, B, H], the gradient at h0.  Overwrites ``.grad`` of
+        every tensor of ``parameters()``.  Enqueues only."""
+        sv = self._saved
+        if not sv:
+            raise RuntimeError("StudentPolicy.backward: no forward_train has run")
+        b, t_len, f = sv["shape"]
+        p, ns, nd, hd, na = self.info["proprioceptive"], self.info["sparse"], self.info["dense"], self.hidden_dim, self.info["actions"]
+        ex, rows, eng = ns + nd, t_len * b, self.engine
+        if d_actions is None or tuple(d_actions.shape) != (b, t_len, na):
+            raise ValueError(f"StudentPolicy.backward: d_actions must be [{b}, {t_len}, {na}]")
+        if d_estimated is not None and tuple(d_estimated.shape) != (b, t_len, ex):
+            raise ValueError(f"StudentPolicy.backward: d_estimated must be [{b}, {t_len}, {ex}]")
+        ef = self.encoder1[-1].weight.shape[0]
+        xt, h0, rs, outs, gates = sv["x"], sv["h0"], sv["reset"], sv["out"], sv["gates"]
+        cat = self._bufs[("t", "cat")]
+        da = self._buf(("t", "d_actions"), rows, na)
+        da.view(t_len, b, na).copy_(d_actions.transpose(0, 1))
+        # 1. the MLP chain, 2. the belief gate: belief = x_b + l_e * sigmoid(x_a), so d x_b is d belief itself
+        d_mlp_in = self._chain_backward("mlp", self.network, da, True)
+        d_belief = d_mlp_in[:, p:]
+        d_le, d_xa = self._buf(("t", "d_le"), rows, 2 * ef), self._buf(("t", "d_xa"), rows, 2 * ef)
+        eng.gated_sum_backward(d_belief, cat[:, p:], sv["ga"][-1], d_mul=d_le, d_pre=d_xa)
+        # 3. gb / ga back to the GRU's output
+        d_top = self._buf(("t", "d_top"), rows, hd)
+        torch.add(self._chain_backward("gb", self.gb, d_belief, True), self._chain_backward("ga", self.ga, d_xa, True), out=d_top)
+        # 4. the decoder: estimated[t, b] = dec[t] + e[t, b] * sigmoid(gate[t]) with dec / gate of the LAST batch row's output
+        if d_estimated is not None:
+            de = self._buf(("t", "d_est"), rows, ex).view(t_len, b, ex)
+            de.copy_(d_estimated.transpose(0, 1))
+            d_pre = self._buf(("t", "d_gate_rows"), rows, ex).view(t_len, b, ex)
+            gate, x3 = sv["gate"][-1], xt.view(t_len, b, f)
+            for t in range(t_len):
+                eng.gated_sum_backward(de[t], x3[t][:, f - ex:], gate[t:t + 1].expand(b, ex), d_pre=d_pre[t])
+            d_dec, d_gate = de.sum(1), d_pre.sum(1)                    # one shared row per step: the batch rows' gradients add up
+        else:                                                        # no reconstruction term: the decoder's gradients are zero
+            d_dec = d_gate = torch.zeros(t_len, ex, device=self.device)
+        d_last = self._chain_backward("dec", self.decoder, d_dec, True) + self._chain_backward("gate", self.gate_encoder, d_gate, True)
+        d_top.view(t_len, b, hd)[:, b - 1] += d_last
+        # 5. the GRU, each layer from the top: the cells step back through time, everything else runs once over all T B rows
+        dh0 = torch.empty(self.n_layers, b, hd, device=self.device)
+        dh_above = d_top.view(t_len, b, hd)
+        for l in range(self.n_layers - 1, -1, -1):
+            w_ih, w_hh, b_ih, b_hh = self.gru[l]
+            k = w_ih.shape[1]
+            dgi, dgh = self._buf(("t", "dgi", l), rows, 3 * hd), self._buf(("t", "dgh", l), rows, 3 * hd)
+            dgi3, dgh3 = dgi.view(t_len, b, 3 * hd), dgh.view(t_len, b, 3 * hd)
+            pong = (self._buf(("t", "dh", 0), b, hd), self._buf(("t", "dh", 1), b, hd))
+            dh_next = None
+            for t in range(t_len - 1, -1, -1):
+                dh_in = dh0[l] if t == 0 else pong[t & 1]
+                eng.gru_cell_backward(dh_above[t], dh_next, gates[l][t], h0[l] if t == 0 else outs[l][t - 1], w_hh, dgi3[t], dgh3[t], dh_in,
+                                      reset_mask=None if rs is None else rs[t])
+                dh_next = dh_in
+            x_in = cat if l == 0 else outs[l - 1].view(rows, hd)
+            dx = self._buf(("t", "d_gru_in", l), rows, k)
+            if k > 0:
+                eng.linear_dgrad(None, dgi, w_ih, None, dx)         # the next layer's dh_above for every t at once
+            h_in = self._buf(("t", "h_in", l), rows, hd).view(t_len, b, hd)
+            h_in[0] = h0[l]
+            h_in[1:] = outs[l][:-1]
+            if rs is not None:
+                h_in.masked_fill_(rs.bool().unsqueeze(-1), 0.0)      # what the cells read: reset rows as zeros
+            self._wgrad(x_in, None, dgi, w_ih, b_ih, None)
+            self._wgrad(h_in.view(rows, hd), None, dgh, w_hh, b_hh, None)
+            dh_above = dx.view(t_len, b, k)
+        # 6. the encoders: l_e feeds the GRU's input and the belief gate
+        d_le += dh_above.view(rows, -1)[:, p:]
+        self._chain_backward("enc1", self.encoder1, d_le[:, :ef], False)
+        self._chain_backward("enc2", self.encoder2, d_le[:, ef:], False)
+        return dh0
