@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--grad-norm-clip", type=float, default=1.0)
     ap.add_argument("--recon-scale", type=float, default=0.5)
     ap.add_argument("--torch-step", action="store_true", help="clip_grad_norm_ + torch.optim.Adam instead of the two HIP launches")
+    ap.add_argument("--teacher-precision", choices=("f32", "bf16"), default="f32", help="what the teacher acts in (the student trains in f32)")
     ap.add_argument("--out", default="", help="where to save {'state_dict': ...} (the reference's best.pt layout)")
     args = ap.parse_args()
     if args.window < 1 or args.updates < 1:
@@ -53,7 +54,7 @@ def main():
     task = RoverTask("Rover", cfg, env, scene=scene, distribution=None if args.native_rays else synth.ray_distribution("37"))
     env.set_task(task, sim_params={"dt": 0.05}, spawn_positions=spawn)
     obs = env.reset()
-    teacher = StochasticActorHeightmap(task._engine, task)
+    teacher = StochasticActorHeightmap(task._engine, task, precision=args.teacher_precision)
     if args.teacher:
         sd = torch.load(args.teacher, map_location="cpu")
         teacher.load_state_dict(sd.get("policy", sd) if isinstance(sd, dict) else sd)

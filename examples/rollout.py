@@ -38,6 +38,8 @@ def main():
     ap.add_argument("--checkpoint", default="", help="--policy actor: a state_dict of the reference's StochasticActorHeightmap (torch.save); "
                     "--policy student: the reference's best.pt (its ['state_dict'] is loaded)")
     ap.add_argument("--rollouts", type=int, default=0, help="--policy actor: store N steps in a RolloutMemory, then compute_gae (0 = off)")
+    ap.add_argument("--precision", choices=("f32", "bf16"), default="f32",
+                    help="--policy actor: what the actor and the critic act in (bf16: bf16 operands, f32 accumulation and head)")
     args = ap.parse_args()
     if args.rollouts < 0 or (args.rollouts and args.policy != "actor"):
         ap.error("--rollouts N needs N >= 0 and --policy actor")
@@ -57,12 +59,13 @@ def main():
     agent = None
     if args.policy == "actor":
         from isaac_rover_amd.learning.model import StochasticActorHeightmap
-        agent = StochasticActorHeightmap(task._engine, task)
+        agent = StochasticActorHeightmap(task._engine, task, precision=args.precision)
         if args.checkpoint:
             sd = torch.load(args.checkpoint, map_location="cpu")
             agent.load_state_dict(sd.get("policy", sd) if isinstance(sd, dict) else sd)
         print(f"policy: StochasticActorHeightmap, {sum(v.numel() for v in agent.state_dict().values()):,} parameters"
-              f"{' from ' + args.checkpoint if args.checkpoint else ' (fresh initialisation)'}")
+              f"{' from ' + args.checkpoint if args.checkpoint else ' (fresh initialisation)'}"
+              f"{', acting in bf16' if args.precision == 'bf16' else ''}")
     student = None
     if args.policy == "student":
         from isaac_rover_amd.learning.student import StudentPolicy
@@ -77,7 +80,7 @@ def main():
     if args.rollouts:
         from isaac_rover_amd.learning.model import DeterministicHeightmap
         from isaac_rover_amd.learning.rollout import RolloutMemory, compute_gae
-        critic = DeterministicHeightmap(task._engine, task, seed=1)
+        critic = DeterministicHeightmap(task._engine, task, seed=1, precision=args.precision)
         memory = RolloutMemory(args.rollouts, args.envs, device=task.device, report=print)
         for name, size, dtype in (("states", obs.shape[1], torch.float32), ("actions", task.num_actions, torch.float32), ("log_prob", 1, torch.float32),
                                   ("values", 1, torch.float32), ("rewards", 1, torch.float32), ("terminated", 1, torch.bool),

@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--native-step", action="store_true", help="gradient-norm clip + Adam as two HIP launches (learning/optim.py) instead of torch's")
     ap.add_argument("--kl-stop", choices=("host", "device"), default="host",
                     help="where the KL early stop is decided: host = one read per minibatch; device = by the native step's gate (needs --native-step)")
+    ap.add_argument("--rollout-precision", choices=("f32", "bf16"), default="f32",
+                    help="what the actor and the critic ACT in while the rollout is collected; the update stays f32 (learning/ppo.py)")
     ap.add_argument("--time-update", action="store_true", help="print the wall time of each update between two torch.cuda.synchronize()")
     args = ap.parse_args()
     if args.rollouts < 1:
@@ -54,11 +56,11 @@ def main():
     env.set_task(task, sim_params={"dt": 0.05}, spawn_positions=spawn)          # utils/task_util.py:45
     obs = env.reset()
     print(f"obs {tuple(obs.shape)}  actions {task.num_actions}  device {task.device}")
-    agent = StochasticActorHeightmap(task._engine, task)
+    agent = StochasticActorHeightmap(task._engine, task, precision=args.rollout_precision)
     if args.checkpoint:
         sd = torch.load(args.checkpoint, map_location="cpu")
         agent.load_state_dict(sd.get("policy", sd) if isinstance(sd, dict) else sd)
-    critic = DeterministicHeightmap(task._engine, task, seed=1)
+    critic = DeterministicHeightmap(task._engine, task, seed=1, precision=args.rollout_precision)
     memory = RolloutMemory(args.rollouts, args.envs, device=task.device, report=print)
     for name, size, dtype in (("states", obs.shape[1], torch.float32), ("actions", task.num_actions, torch.float32), ("log_prob", 1, torch.float32),
                               ("values", 1, torch.float32), ("rewards", 1, torch.float32), ("terminated", 1, torch.bool),

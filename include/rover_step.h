@@ -420,6 +420,43 @@ ROVER_API int rover_philox4x32(const uint32_t *counter, const uint32_t *key, uin
 ROVER_API const char *rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t *widths,
                                                 const int32_t *activations, const rover_gauss_head *head);
 
+/* ---- the same chains with bf16 operands and f32 accumulation: inference for rollouts (precision = "bf16") ------------------------- */
+/* CDNA4's f32-input MFMA runs at 1/16 of the bf16 rate, and the f32 chain kernels above are bound by it.  A rollout needs the sampled
+ * action, its log-probability under the policy that ACTED, and the value: all three may come from a lower-precision forward, since PPO's
+ * ratio is pi_new / pi_behaviour with the behaviour policy's own stored log_prob.  Training stays f32; these entry points have no
+ * backward.
+ * The arithmetic, for a chain y = L_n(... L_1(x)) — the tests hold the kernels to it:
+ *   inputs and weights   every element of x and of each W_i is rounded to bf16 as it is read: round to nearest even, NaN stays NaN,
+ *                        +-Inf stays +-Inf (a finite f32 above the largest bf16 becomes Inf).  rover_bf16_round is that rounding.
+ *   products and sums    a product of two bf16 values is exact in f32; the products of a row are summed in f32 in a fixed order.
+ *   bias and activation  the f32 bias is added in f32; the activation is the f32 kernels' own, in f32.
+ *   between layers       the output of every layer but the last is rounded to bf16 (as above) before the next layer reads it.
+ *   last layer           its output is f32, not rounded.
+ *   Gaussian head        the f32 head (above) on that f32 mean: noise, clamps, log_prob and taken_actions semantics unchanged.
+ * No bf16 copy of the weights is kept anywhere: they are read as f32 and converted as they are staged, so a weight changed in place
+ * (rover_optim_step writes through raw pointers) is seen by the next call.
+ * Same parameters, shapes and refusals as rover_mlp_chain_forward / rover_mlp_chain_act, with one addition: K0 = 0 is accepted (a chain
+ * over an empty obs slice, model.py's Encoder(0, ...): the first layer is act_1(b_1), as rover_linear_forward computes it for K = 0; x and
+ * weights[0] are not read and may be NULL), so that a net with an absent heightmap part runs in one precision.  ONE kernel per tile shape covers every batch
+ * size — "chain_bf16<5,4,0,0>", "chain_bf16<6,4,0,0>" (2 layers), "chain_bf16<16,10,8,1>" (4 layers); rover_mlp_chain_act_bf16 runs the
+ * head inside the 4-layer kernel for A <= 4 ("chain_bf16<16,10,8,1>+gauss"), else as one more launch ("...;gauss").  There is no
+ * split-k family: the ctx's scratch buffer is not used, nothing allocates or synchronises, and the first call may happen inside a stream
+ * capture.  No atomics: the same bits on every run.  The route queries follow the f32 ones' contract (the instantiation's name, "none"
+ * for M = 0, NULL where the shapes are refused); the fit rule is the f32 chains', in one place (chain_fit() of csrc/rover_mlp.hip). */
+ROVER_API int rover_mlp_chain_forward_bf16(rover_ctx *ctx, const float *x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers,
+                                           const float *const *weights, const float *const *biases, const int32_t *widths,
+                                           const int32_t *activations, float *y, int64_t y_stride, void *stream);
+ROVER_API int rover_mlp_chain_act_bf16(rover_ctx *ctx, const float *x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers,
+                                       const float *const *weights, const float *const *biases, const int32_t *widths,
+                                       const int32_t *activations, float *y, int64_t y_stride, const rover_gauss_head *head,
+                                       void *stream);
+ROVER_API const char *rover_mlp_chain_route_bf16(int32_t M, int32_t K0, int32_t n_layers, const int32_t *widths,
+                                                 const int32_t *activations);
+ROVER_API const char *rover_mlp_chain_act_route_bf16(int32_t M, int32_t K0, int32_t n_layers, const int32_t *widths,
+                                                     const int32_t *activations, const rover_gauss_head *head);
+/* Host only (no ctx, no device): out[i] = the bf16 rounding of in[i] as an f32 — the one definition the kernels share. */
+ROVER_API int rover_bf16_round(const float *in, int64_t n, float *out);
+
 /* ---- the rollout side of PPO: returns and advantages of a stored rollout in one pass (skrl's compute_gae inside PPO._update) -------- */
 /* The reference trains through skrl: RandomMemory(memory_size=60) (train.py:82), rollouts 60, discount_factor 0.99, lambda 0.95
  * (cfg/trainSKRL/RoverPPOSKRL.yaml:12-16).  skrl is no part of this repository: the semantics are restated from a reading of skrl

@@ -191,6 +191,11 @@ SYMBOLS = {
     "rover_policy_noise": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "rover_philox4x32": (C.c_int, [_P, _P, _P]),
     "rover_mlp_chain_act_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(GaussHead)]),
+    "rover_mlp_chain_forward_bf16": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "rover_mlp_chain_act_bf16": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(GaussHead), _P]),
+    "rover_mlp_chain_route_bf16": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "rover_mlp_chain_act_route_bf16": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(GaussHead)]),
+    "rover_bf16_round": (C.c_int, [_P, C.c_int64, _P]),
     "rover_gae": (C.c_int, [_P, C.POINTER(GaeDesc), _P]),
     "rover_combine_moments": (C.c_int, [_P, _P, _P]),
     "rover_linear_backward": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64,
@@ -345,14 +350,37 @@ def gauss_head_desc(A, log_std=_FAKE, actions=_FAKE, log_prob=_FAKE, clip_log_st
                      A if mean_stride is None else int(mean_stride))
 
 
-def chain_act_route(m, k0, widths, activations, head=None):
+PRECISIONS = ("f32", "bf16")
+
+
+def _precision_suffix(precision):
+    """"" / "_bf16": the suffix of the chain entry points of ``precision`` (rover_mlp_chain_forward / rover_mlp_chain_forward_bf16, ...)."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
+    return "" if precision == "f32" else "_bf16"
+
+
+def chain_act_route(m, k0, widths, activations, head=None, precision="f32"):
     """rover_mlp_chain_act_route: "mlp_small+gauss" / "chain16<16,10,8,1>+gauss" (the head inside the chain's last kernel),
     "<chain route>;gauss" (the head as a launch of its own), "none" for m = 0, None where rover_mlp_chain_act would refuse the call.
-    ``head``: a GaussHead (gauss_head_desc) — default: the reference's settings with A = widths[-1]."""
+    ``head``: a GaussHead (gauss_head_desc) — default: the reference's settings with A = widths[-1].  ``precision="bf16"``:
+    rover_mlp_chain_act_route_bf16 ("chain_bf16<16,10,8,1>+gauss", ...)."""
     k0, n, w, a = Engine._chain_shape(k0, widths, activations)
     if head is None:
         head = gauss_head_desc(widths[-1])
-    return Engine._route(load().rover_mlp_chain_act_route(int(m), k0, n, w, a, C.byref(head)))
+    return Engine._route(getattr(load(), "rover_mlp_chain_act_route" + _precision_suffix(precision))(int(m), k0, n, w, a, C.byref(head)))
+
+
+def bf16_round(values):
+    """rover_bf16_round: ``values`` (anything numpy turns into float32) rounded to bf16 as the bf16 chain kernels round their inputs,
+    weights and hidden activations -> a float32 array of the same shape.  Host only."""
+    x = np.ascontiguousarray(values, dtype=np.float32)
+    out = np.empty_like(x)
+    lib = load()
+    rc = lib.rover_bf16_round(x.ctypes.data, x.size, out.ctypes.data)
+    if rc != 0:
+        raise RoverError(f"rover_bf16_round failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return out
 
 
 def _ptr(t):
@@ -717,12 +745,14 @@ class Engine:
         return ChainDesc(x.data_ptr(), x.stride(0), k0, n, C.addressof(w), C.addressof(b), C.addressof(widths), C.addressof(acts),
                          out.data_ptr(), out.stride(0))
 
-    def chain_forward(self, x, layers, out):
-        """out = layers[-1](... layers[0](x)) in one kernel; ``layers``: objects with .weight [n, k], .bias [n], .activation."""
+    def chain_forward(self, x, layers, out, precision="f32"):
+        """out = layers[-1](... layers[0](x)) in one kernel; ``layers``: objects with .weight [n, k], .bias [n], .activation.
+        ``precision="bf16"``: bf16 operands, f32 accumulation (rover_mlp_chain_forward_bf16; the arithmetic is stated in rover_step.h)."""
+        name = "rover_mlp_chain_forward" + _precision_suffix(precision)
         keep = []
         d = self._chain("chain_forward", x, layers, out, keep)
-        self._check(self.lib.rover_mlp_chain_forward(self._h, d.x, d.x_stride, x.shape[0], d.K0, d.n_layers, d.weights, d.biases, d.widths,
-                                                     d.activations, d.y, d.y_stride, _stream(self._dev_index)), "rover_mlp_chain_forward")
+        self._check(getattr(self.lib, name)(self._h, d.x, d.x_stride, x.shape[0], d.K0, d.n_layers, d.weights, d.biases, d.widths,
+                                            d.activations, d.y, d.y_stride, _stream(self._dev_index)), name)
         return out
 
     def chain_pair_forward(self, xa, layers_a, out_a, xb, layers_b, out_b, copy_src=None, copy_dst=None, copy_cols=0):
@@ -762,15 +792,17 @@ class Engine:
                                taken_stride=st(taken_actions), actions_stride=st(actions), log_prob_stride=st(log_prob), mean=dp(mean),
                                mean_stride=st(mean), **kw)
 
-    def chain_act(self, x, layers, mean_out, log_std, actions, log_prob, **head):
+    def chain_act(self, x, layers, mean_out, log_std, actions, log_prob, precision="f32", **head):
         """chain_forward with the Gaussian head on its output (rover_mlp_chain_act): ``mean_out`` receives what chain_forward writes,
         ``actions`` / ``log_prob`` the head's results.  ``head``: taken_actions, step_dev, reduction and the scalar fields of
-        gauss_head_desc (seed, step, row_offset, deterministic, clip_*, ...)."""
+        gauss_head_desc (seed, step, row_offset, deterministic, clip_*, ...).  ``precision="bf16"``: rover_mlp_chain_act_bf16 (the f32
+        head on the bf16 chain's f32 mean)."""
+        name = "rover_mlp_chain_act" + _precision_suffix(precision)
         keep = []
         d = self._chain("chain_act", x, layers, mean_out, keep, "mean_out")
         desc = self._gauss_head("chain_act", x.shape[0], log_std, actions, log_prob, **head)
-        self._check(self.lib.rover_mlp_chain_act(self._h, d.x, d.x_stride, x.shape[0], d.K0, d.n_layers, d.weights, d.biases, d.widths, d.activations,
-                                                 d.y, d.y_stride, C.byref(desc), _stream(self._dev_index)), "rover_mlp_chain_act")
+        self._check(getattr(self.lib, name)(self._h, d.x, d.x_stride, x.shape[0], d.K0, d.n_layers, d.weights, d.biases, d.widths, d.activations,
+                                            d.y, d.y_stride, C.byref(desc), _stream(self._dev_index)), name)
         return actions, log_prob
 
     def gaussian_head(self, mean, log_std, actions, log_prob, **head):
@@ -790,6 +822,7 @@ class Engine:
         return out
 
     chain_act_route = staticmethod(chain_act_route)
+    bf16_round = staticmethod(bf16_round)
 
     # ---- the student's recurrent block (rover_gru_cell, rover_gated_sum) -------------------------------------
     def gru_cell(self, x, h_in, w_ih, w_hh, b_ih, b_hh, h_out, reset_mask=None):
@@ -1109,10 +1142,11 @@ class Engine:
         return cls._route(load().rover_linear_route(int(m), int(k), int(n)))
 
     @classmethod
-    def chain_route(cls, m, k0, widths, activations):
-        """The kernel chain_forward runs ("splitk<6,2>", "mlp_small", "chain16<16,10,8,1>", ...); activations: names or codes."""
+    def chain_route(cls, m, k0, widths, activations, precision="f32"):
+        """The kernel chain_forward runs ("splitk<6,2>", "mlp_small", "chain16<16,10,8,1>", ...; ``precision="bf16"``:
+        "chain_bf16<5,4,0,0>", ...); activations: names or codes."""
         k0, n, w, a = cls._chain_shape(k0, widths, activations)
-        return cls._route(load().rover_mlp_chain_route(int(m), k0, n, w, a))
+        return cls._route(getattr(load(), "rover_mlp_chain_route" + _precision_suffix(precision))(int(m), k0, n, w, a))
 
     @classmethod
     def chain_pair_route(cls, m, a, b):

@@ -2,6 +2,7 @@
 // tables, argument checks, kernel sequencing.  No torch, no exceptions across the boundary.
 #include "../../include/rover_step.h"
 #include "rover_internal.h"
+#include "rover_bf16.h"
 #include "rover_philox.h"
 #include "rover_plan.h"
 
@@ -1430,8 +1431,10 @@ int rover_linear_forward(rover_ctx* c, const float* x, int64_t x_stride, int32_t
 
 // One chain, validated in one place.  The shape half: M, K0, the depth, every width and activation — all chain_route() reads, so all a route query looks at (no pointer of
 // the descriptor but widths / activations).  0 = fine, -1 = M / K0 / the depth / a null array, i + 1 = layer i's width or activation.
-static int chain_shape_of(const rover_chain_desc& d, int32_t M, ChainArgs* a) {
-    if (!d.widths || !d.activations || M < 0 || d.K0 <= 0 || (d.n_layers != 2 && d.n_layers != 4)) return -1;
+// min_k0: 1 for the f32 chains; 0 for the bf16 ones, which also run a chain over an EMPTY obs slice (model.py builds Encoder(0, ...) when
+// a heightmap part is absent: its first layer is act(bias), as rover_linear_forward computes it for K = 0) — x is then not read.
+static int chain_shape_of(const rover_chain_desc& d, int32_t M, ChainArgs* a, int32_t min_k0 = 1) {
+    if (!d.widths || !d.activations || M < 0 || d.K0 < min_k0 || (d.n_layers != 2 && d.n_layers != 4)) return -1;
     *a = ChainArgs{};
     a->M = M; a->K0 = d.K0; a->n_layers = d.n_layers;
     for (int i = 0; i < d.n_layers; ++i) {
@@ -1442,13 +1445,13 @@ static int chain_shape_of(const rover_chain_desc& d, int32_t M, ChainArgs* a) {
 }
 // The whole of it, for a call that launches: the shapes, then the pointers and the row strides (0 = ok, else the error is recorded
 // under `what`, the entry point that was called)
-static int chain_args_of(rover_ctx* c, const rover_chain_desc& d, int32_t M, const char* what, ChainArgs* out) {
+static int chain_args_of(rover_ctx* c, const rover_chain_desc& d, int32_t M, const char* what, ChainArgs* out, int32_t min_k0 = 1) {
     ChainArgs a;
-    const int bad = chain_shape_of(d, M, &a);
-    if (bad < 0 || !d.x || !d.y || !d.weights || !d.biases || d.x_stride < d.K0)
+    const int bad = chain_shape_of(d, M, &a, min_k0);
+    if (bad < 0 || (!d.x && d.K0 > 0) || !d.y || !d.weights || !d.biases || d.x_stride < d.K0)
         return fail(c, ROVER_E_INVALID, "%s: bad arguments (M=%d K0=%d layers=%d)", what, M, d.K0, d.n_layers);
     for (int i = 0; i < d.n_layers; ++i) {
-        if (!d.weights[i] || bad == i + 1)
+        if ((!d.weights[i] && (i > 0 || d.K0 > 0)) || bad == i + 1)
             return fail(c, ROVER_E_INVALID, "%s: layer %d: width %d activation %d", what, i, d.widths[i], d.activations[i]);
         a.w[i] = d.weights[i]; a.b[i] = d.biases[i];
     }
@@ -1478,18 +1481,39 @@ static int chain_run(rover_ctx* c, const ChainArgs& a, const ChainRoute& r, hipS
     return ROVER_OK;
 }
 
+// the f32 and the bf16 entry points differ in the route function alone (chain_route / chain_route_bf16: rover_mlp.hip)
+typedef ChainRoute (*ChainRouteFn)(const ChainArgs&);
+static int32_t chain_min_k0(ChainRouteFn route) { return route == chain_route_bf16 ? 0 : 1; }
+
+static int chain_forward(rover_ctx* c, const rover_chain_desc& d, int32_t M, const char* what, ChainRouteFn route, void* stream) {
+    if (!c) return ROVER_E_INVALID;
+    ChainArgs a;
+    if (int r = chain_args_of(c, d, M, what, &a, chain_min_k0(route))) return r;
+    if (M == 0) return ROVER_OK;
+    const ChainRoute r = route(a);
+    if (r.kernel == ChainKernel::None) return chain_refused(c, what);
+    USE_DEVICE(c);
+    return chain_run(c, a, r, (hipStream_t)stream);
+}
+
 int rover_mlp_chain_forward(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers,
                             const float* const* weights, const float* const* biases, const int32_t* widths, const int32_t* activations,
                             float* y, int64_t y_stride, void* stream) {
-    if (!c) return ROVER_E_INVALID;
     const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
-    ChainArgs a;
-    if (int r = chain_args_of(c, d, M, "mlp_chain_forward", &a)) return r;
-    if (M == 0) return ROVER_OK;
-    const ChainRoute r = chain_route(a);
-    if (r.kernel == ChainKernel::None) return chain_refused(c, "mlp_chain_forward");
-    USE_DEVICE(c);
-    return chain_run(c, a, r, (hipStream_t)stream);
+    return chain_forward(c, d, M, "mlp_chain_forward", chain_route, stream);
+}
+
+int rover_mlp_chain_forward_bf16(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers,
+                                 const float* const* weights, const float* const* biases, const int32_t* widths, const int32_t* activations,
+                                 float* y, int64_t y_stride, void* stream) {
+    const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
+    return chain_forward(c, d, M, "mlp_chain_forward_bf16", chain_route_bf16, stream);
+}
+
+int rover_bf16_round(const float* in, int64_t n, float* out) {
+    if (n < 0 || (n > 0 && (!in || !out))) return fail(nullptr, ROVER_E_INVALID, "bf16_round: bad arguments (n=%lld)", (long long)n);
+    for (int64_t i = 0; i < n; ++i) out[i] = (float)bf16_rne(in[i]);
+    return ROVER_OK;
 }
 
 int rover_mlp_chain_pair_forward(rover_ctx* c, int32_t M, const rover_chain_desc* da, const rover_chain_desc* db, const float* copy_src,
@@ -1526,11 +1550,17 @@ const char* rover_linear_route(int32_t M, int32_t K, int32_t N) {
     return M == 0 ? "none" : linear_route_name(r);
 }
 
-const char* rover_mlp_chain_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations) {
+static const char* chain_route_query(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations, ChainRouteFn route) {
     const rover_chain_desc d{nullptr, 0, K0, n_layers, nullptr, nullptr, widths, activations, nullptr, 0};      // a route query: shapes alone
     ChainArgs a;
-    if (chain_shape_of(d, M, &a)) return nullptr;
-    return M == 0 ? "none" : chain_route_name(chain_route(a));
+    if (chain_shape_of(d, M, &a, chain_min_k0(route))) return nullptr;
+    return M == 0 ? "none" : chain_route_name(route(a));
+}
+const char* rover_mlp_chain_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations) {
+    return chain_route_query(M, K0, n_layers, widths, activations, chain_route);
+}
+const char* rover_mlp_chain_route_bf16(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations) {
+    return chain_route_query(M, K0, n_layers, widths, activations, chain_route_bf16);
 }
 
 const char* rover_mlp_chain_pair_route(int32_t M, const rover_chain_desc* da, const rover_chain_desc* db) {
@@ -1574,18 +1604,16 @@ static int gauss_head_of(rover_ctx* c, const rover_gauss_head* g, int32_t M, boo
     return ROVER_OK;
 }
 
-int rover_mlp_chain_act(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers, const float* const* weights,
-                        const float* const* biases, const int32_t* widths, const int32_t* activations, float* y, int64_t y_stride,
-                        const rover_gauss_head* head, void* stream) {
+static int chain_act(rover_ctx* c, const rover_chain_desc& d, int32_t M, const rover_gauss_head* head, const char* what, ChainRouteFn route,
+                     void* stream) {
     if (!c) return ROVER_E_INVALID;
-    const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
     ChainArgs a; GaussHead h{};
-    if (int r = chain_args_of(c, d, M, "mlp_chain_act", &a)) return r;
+    if (int r = chain_args_of(c, d, M, what, &a, chain_min_k0(route))) return r;
     if (int r = gauss_head_of(c, head, M, false, &h)) return r;
-    if (a.n[n_layers - 1] != h.A) return fail(c, ROVER_E_INVALID, "mlp_chain_act: the last layer is %d wide, the head has A = %d", a.n[n_layers - 1], h.A);
+    if (a.n[d.n_layers - 1] != h.A) return fail(c, ROVER_E_INVALID, "%s: the last layer is %d wide, the head has A = %d", what, a.n[d.n_layers - 1], h.A);
     if (M == 0) return ROVER_OK;
-    const ChainRoute r = chain_route(a);
-    if (r.kernel == ChainKernel::None) return chain_refused(c, "mlp_chain_act");
+    const ChainRoute r = route(a);
+    if (r.kernel == ChainKernel::None) return chain_refused(c, what);
     USE_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     if (chain_head_fused(r, h.A)) {
@@ -1595,6 +1623,20 @@ int rover_mlp_chain_act(rover_ctx* c, const float* x, int64_t x_stride, int32_t 
     if (int e = chain_run(c, a, r, s)) return e;
     HIP_TRY(c, launch_gaussian_head(a.y, a.y_stride, M, h, s));
     return ROVER_OK;
+}
+
+int rover_mlp_chain_act(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers, const float* const* weights,
+                        const float* const* biases, const int32_t* widths, const int32_t* activations, float* y, int64_t y_stride,
+                        const rover_gauss_head* head, void* stream) {
+    const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
+    return chain_act(c, d, M, head, "mlp_chain_act", chain_route, stream);
+}
+
+int rover_mlp_chain_act_bf16(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers, const float* const* weights,
+                             const float* const* biases, const int32_t* widths, const int32_t* activations, float* y, int64_t y_stride,
+                             const rover_gauss_head* head, void* stream) {
+    const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
+    return chain_act(c, d, M, head, "mlp_chain_act_bf16", chain_route_bf16, stream);
 }
 
 int rover_gaussian_head(rover_ctx* c, int32_t M, const rover_gauss_head* head, void* stream) {
@@ -1626,11 +1668,11 @@ int rover_philox4x32(const uint32_t* counter, const uint32_t* key, uint32_t* out
     return ROVER_OK;
 }
 
-const char* rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations,
-                                      const rover_gauss_head* head) {
+static const char* chain_act_route_query(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations,
+                                         const rover_gauss_head* head, ChainRouteFn route) {
     const rover_chain_desc d{nullptr, 0, K0, n_layers, nullptr, nullptr, widths, activations, nullptr, 0};
     ChainArgs a; GaussHead h{};
-    if (chain_shape_of(d, M, &a)) {
+    if (chain_shape_of(d, M, &a, chain_min_k0(route))) {
         fail(nullptr, ROVER_E_INVALID, "mlp_chain_act_route: bad shapes (M=%d K0=%d layers=%d)", M, K0, n_layers);
         return nullptr;
     }
@@ -1640,9 +1682,17 @@ const char* rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, c
         return nullptr;
     }
     if (M == 0) return "none";
-    const char* name = chain_act_route_name(chain_route(a), h.A);
+    const char* name = chain_act_route_name(route(a), h.A);
     if (!name) fail(nullptr, ROVER_E_INVALID, "mlp_chain_act_route: net outside the built tile shapes");
     return name;
+}
+const char* rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations,
+                                      const rover_gauss_head* head) {
+    return chain_act_route_query(M, K0, n_layers, widths, activations, head, chain_route);
+}
+const char* rover_mlp_chain_act_route_bf16(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations,
+                                           const rover_gauss_head* head) {
+    return chain_act_route_query(M, K0, n_layers, widths, activations, head, chain_route_bf16);
 }
 
 // ---- rollout: GAE ----

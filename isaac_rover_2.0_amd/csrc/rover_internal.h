@@ -266,9 +266,12 @@ struct ChainArgs {
 // which kernel runs a chain, decided once from M, K0, the widths and the activations (no pointer is read): split-k (a 2-layer chain
 // at small batches, first layer split along k through a scratch buffer; tn output tiles, rt row tiles per wave), mlp_small (a 4-layer
 // net at small batches) or chain16 with the tile shape the widths need; None: outside the built tile shapes
-enum class ChainKernel { None, SplitK, MlpSmall, Chain16_5, Chain16_6, Chain16Long };
+enum class ChainKernel { None, SplitK, MlpSmall, Chain16_5, Chain16_6, Chain16Long, Bf16_5, Bf16_6, Bf16Long };
 struct ChainRoute { ChainKernel kernel; int tn, rt; };
 ChainRoute chain_route(const ChainArgs& a);
+// the same fit rule for precision = "bf16" (bf16 operands, f32 accumulation): chain_bf16<...> at every batch size, never split-k
+// (the rounding its kernels apply to every operand: bf16_rne() of rover_bf16.h)
+ChainRoute chain_route_bf16(const ChainArgs& a);
 // "splitk<6,2>", "chain16<16,10,8,1>", ..., or NULL.  This and chain_act_route_name() read one table (rover_mlp.hip: kChainKernels) and
 // compose the name in one buffer per thread: valid until the calling thread's next call of either
 const char* chain_route_name(const ChainRoute& r);

@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "rover_internal.h"
+#include "rover_bf16.h"
 #include "rover_philox.h"
 
 namespace rover {
@@ -525,6 +526,253 @@ __global__ void __launch_bounds__(512, 4) chain16_head_kernel(ChainArgs a, Gauss
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The same chains with bf16 operands and f32 accumulation (precision = "bf16": inference only; the arithmetic is
+// stated in rover_step.h at rover_mlp_chain_forward_bf16).  v_mfma_f32_16x16x32_bf16, transposed like chain16: D[n][m] = W[n][k] X^T[k][m],
+// A = W (lane (m, g): row 16 t + m, 8 k-values), B = X^T (lane (m, g): batch row m, 8 k-values), D: lane (m, g) holds features
+// 16 t + 4 g + r (r < 4) of batch row m — chain16's accumulator layout exactly, so its bias / activation / store / head code is used
+// as it is.  One k-step is 32 deep: lane group g supplies k-slots 8 g .. 8 g + 7 of BOTH operands, and a sum over k does not care
+// which feature sits in which slot as long as the two operands agree.
+//   * layer 1: x rows and weight rows are read as f32 (16 bytes at any float address), rounded to bf16 (bf16_rne) and staged as
+//     [row][32 k] bf16 slabs in natural k order; a lane reads 16 bytes at slot 8 g of its row from each.
+//   * later layers: two adjacent accumulator tiles (2 s, 2 s + 1) are ONE k-step after a pairwise v_cvt_pk_bf16_f32: element j of lane
+//     group g is feature 32 s + 16 (j >> 2) + 4 g + (j & 3).  The weight slab of step s is staged with that permutation — the 8 bytes
+//     from columns 32 s + 16 h + 4 g' .. + 3 go to slot 8 g' + 4 h — so the A operand is one 16-byte read too.  An odd tile count
+//     (80 = 5 tiles) leaves the upper half of the last step zero on both operands.
+// The rounded activations of a whole layer are 2 VGPRs per 16 features: the 4-layer chain needs no split of its first layer.
+// Rows of 32 bf16 at a pitch of 40 (20 words, C16_WP's): the 16-byte reads of 8 lanes fall on 8 different bank groups.
+// ---------------------------------------------------------------------------------------------------
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#define B16_P 40
+
+__device__ __forceinline__ bf16x4 b16_round4(const f32x4& v) { return bf16x4{bf16_rne(v[0]), bf16_rne(v[1]), bf16_rne(v[2]), bf16_rne(v[3])}; }
+
+// a layer's activated f32 tiles -> the next layer's B fragments, rounded (features past the layer's width are zero already)
+template <int T>
+__device__ __forceinline__ void b16_pack(const f32x4 (&acc)[T], bf16x8 (&out)[(T + 1) / 2]) {
+#pragma unroll
+    for (int s = 0; s < (T + 1) / 2; ++s)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            out[s][j] = bf16_rne(acc[2 * s][j]);
+            out[s][4 + j] = 2 * s + 1 < T ? bf16_rne(acc[2 * s + 1][j]) : bf16_rne(0.0f);
+        }
+}
+
+// a hidden layer of the 4-layer chain: bias + none / LeakyReLU / ReLU (c16_bias_act_hidden's arithmetic) on the tiles whose first
+// feature is n_base, rounded and packed tile by tile.  A tile wholly inside the layer's width (a wave-uniform test: every tile of
+// 256 / 160 / 128) reads its four biases as one 16-byte load and needs no per-value mask; c16_bias_act_hidden's per-value branches,
+// hoisted over the barriers, held ~40 SGPR pairs of masks and spilled.
+template <bool FULL>
+__device__ __forceinline__ f32x4 b16_tile_act(const f32x4& acc, const float* __restrict__ bias, uint32_t n0 /* 16 t + 4 g */, uint32_t n_total, int act) {
+    const float slope = act == 1 ? 0.01f : 1.0f;
+    f32x4 b = {0.0f, 0.0f, 0.0f, 0.0f}, out;
+    if (bias) {
+        if (FULL) b = *reinterpret_cast<const f32x4u*>(bias + n0);
+        else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (n0 + r < n_total) b[r] = bias[n0 + r];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float v = acc[r] + b[r];
+        const float neg = act == 3 ? 0.0f : slope * v;
+        const float o = v > 0.0f ? v : neg;
+        out[r] = (FULL || n0 + r < n_total) ? o : 0.0f;
+    }
+    return out;
+}
+template <int T>
+__device__ __forceinline__ void b16_hidden_pack(const f32x4 (&acc)[T], const float* __restrict__ bias, uint32_t n_base, int n_total, int act,
+                                                uint32_t g, bf16x8* __restrict__ out) {
+    static_assert(T % 2 == 0, "whole k-steps");          // (T2 = 10, T3 = 8, T1 / 2 = 8)
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const uint32_t nb = n_base + 16u * t;
+        const f32x4 v = nb + 16u <= (uint32_t)n_total ? b16_tile_act<true>(acc[t], bias, nb + 4u * g, (uint32_t)n_total, act)
+                                                      : b16_tile_act<false>(acc[t], bias, nb + 4u * g, (uint32_t)n_total, act);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[t / 2][4 * (t & 1) + r] = bf16_rne(v[r]);
+    }
+}
+
+// elements k .. k + 3 of a row of `len` floats, zero past its end or when the row does not exist
+__device__ __forceinline__ f32x4 b16_load4(const float* __restrict__ p, uint32_t k, uint32_t len, bool row_ok) {
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (row_ok) {
+        if (k + 4u <= len) v = *reinterpret_cast<const f32x4u*>(p + k);
+        else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (k + e < len) v[e] = p[k + e];
+        }
+    }
+    return v;
+}
+
+// layer 1 for the TN output tiles that start at weight row n_off: both operands from LDS slabs of 32 k.  512 threads stage 128 x rows and TN * 16 weight rows, 4 floats
+// -> 8 bytes each (thread (c4 = tid % 8, r0 = tid / 8): rows r0 + 64 j).  PF: the next slab is fetched under the MFMAs (the encoders).
+template <int TN, bool PF>
+__device__ __forceinline__ void b16_layer1(f32x4 (&a1)[TN], const ChainArgs& a, uint32_t n_off, uint32_t row0, __bf16* __restrict__ Xs,
+                                           __bf16* __restrict__ Ws, uint32_t tid, uint32_t wave, uint32_t m, uint32_t g) {
+    constexpr int WJ = (TN * 16 + 63) / 64;
+    asm volatile("" : "+v"(tid), "+v"(m));                           // (see b16_layer)
+    const uint32_t c4 = tid & 7u, r0 = tid >> 3;
+    f32x4 px[2], pw[WJ];
+    auto fetch = [&](uint32_t k0) {
+        const uint32_t k = k0 + 4u * c4;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const uint32_t gr = row0 + r0 + 64u * j;
+            px[j] = b16_load4(a.x + (size_t)gr * a.x_stride, k, (uint32_t)a.K0, gr < (uint32_t)a.M);
+        }
+#pragma unroll
+        for (int j = 0; j < WJ; ++j) {
+            const uint32_t nl = r0 + 64u * j, n = n_off + nl;
+            pw[j] = b16_load4(a.w[0] + (size_t)n * a.K0, k, (uint32_t)a.K0, nl < TN * 16u && n < (uint32_t)a.n[0]);
+        }
+    };
+    if (PF && a.K0 > 0) fetch(0);                                    // (K0 = 0: an empty slice, x and w[0] may be null)
+    for (uint32_t k0 = 0; k0 < (uint32_t)a.K0; k0 += 32u) {
+        if (!PF) fetch(k0);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) *reinterpret_cast<bf16x4*>(Xs + (r0 + 64u * j) * B16_P + 4u * c4) = b16_round4(px[j]);
+#pragma unroll
+        for (int j = 0; j < WJ; ++j)
+            if (r0 + 64u * j < TN * 16u) *reinterpret_cast<bf16x4*>(Ws + (r0 + 64u * j) * B16_P + 4u * c4) = b16_round4(pw[j]);
+        __syncthreads();
+        if (PF && k0 + 32u < (uint32_t)a.K0) fetch(k0 + 32u);          // in flight during the MFMAs below
+        const bf16x8 xb = *reinterpret_cast<const bf16x8*>(Xs + (wave * 16u + m) * B16_P + 8u * g);
+#pragma unroll
+        for (int t = 0; t < TN; ++t) {
+            const bf16x8 wa = *reinterpret_cast<const bf16x8*>(Ws + (16u * t + m) * B16_P + 8u * g);
+            a1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb, a1[t], 0, 0, 0);
+        }
+    }
+}
+
+// one register-fed layer: out[TO] = W . in, in = KS k-steps of 32 features.  The [TO * 16][32] weight slab of step s + 1 is fetched
+// into registers before the MFMAs of step s and stored (rounded, permuted as above) into the other LDS buffer after them.
+template <int KS, int TO>
+__device__ __forceinline__ void b16_layer(const bf16x8 (&in)[KS], f32x4 (&out)[TO], const float* __restrict__ w, int n_in, int n_out,
+                                          uint32_t col0 /* feature index of in[0]'s first slot */, __bf16* __restrict__ Wb /* 2 x [TO * 16][B16_P] */,
+                                          uint32_t tid, uint32_t m, uint32_t g) {
+    constexpr uint32_t BUF = TO * 16u * B16_P;
+    constexpr int NJ = (TO * 16 + 63) / 64;
+    // the thread index is made opaque per layer: hipcc otherwise computes every later layer's staging addresses and masks at the top of
+    // the kernel and carries them (spilled) through the layers before
+    asm volatile("" : "+v"(tid), "+v"(m), "+v"(g));
+    const uint32_t c4 = tid & 7u, sr = tid >> 3;                     // 16-byte column of the f32 slab; first slab row of this thread
+    const uint32_t slot = 8u * (c4 & 3u) + 4u * (c4 >> 2);           // columns 16 h + 4 g' .. + 3 (c4 = 4 h + g') -> slots 8 g' + 4 h .. + 3
+    f32x4 pw[NJ];
+    auto fetch = [&](int s) {
+        const uint32_t col = col0 + 32u * s + 4u * c4;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const uint32_t n = sr + 64u * j;
+            pw[j] = b16_load4(w + (size_t)n * n_in, col, (uint32_t)n_in, n < (uint32_t)n_out && n < TO * 16u);
+        }
+    };
+    auto stash = [&](uint32_t buf) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const uint32_t n = sr + 64u * j;
+            if (n < TO * 16u) *reinterpret_cast<bf16x4*>(Wb + buf * BUF + n * B16_P + slot) = b16_round4(pw[j]);
+        }
+    };
+    __syncthreads();                                                 // the previous user of the LDS is done
+    fetch(0);
+    stash(0);
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        const uint32_t buf = (uint32_t)s & 1u;
+        if (s + 1 < KS) fetch(s + 1);                                // in flight during the MFMAs below
+#pragma unroll
+        for (int to = 0; to < TO; ++to) {
+            const bf16x8 wa = *reinterpret_cast<const bf16x8*>(Wb + buf * BUF + (16u * to + m) * B16_P + 8u * g);
+            out[to] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, in[s], out[to], 0, 0, 0);
+        }
+        if (s + 1 < KS) {
+            stash(buf ^ 1u);                                         // nobody reads the other buffer now
+            __syncthreads();
+        }
+    }
+}
+
+// T1..T4 as in chain16_body (T3 = T4 = 0: a 2-layer chain).  Every layer's output but the last is rounded to bf16 (b16_pack); the
+// last layer's is f32 and takes chain16's epilogue, the Gaussian head included.  The 4-layer chain computes layer 1 in two halves of
+// T1 / 2 tiles (the input rows are staged twice: k = 124 is four slabs), each rounded, packed and fed into layer 2's accumulators as
+// soon as it is done, as chain16_body does: at most 32 + 40 live accumulator registers, and the kernel stays under 128 VGPRs.
+template <int T1, int T2, int T3, int T4, bool HEAD>
+__device__ __forceinline__ void chain_b16_body(const ChainArgs& a, const GaussHead* gauss) {
+    constexpr bool LONG = T3 != 0;
+    constexpr uint32_t L1 = (128u + (LONG ? T1 / 2 : T1) * 16u) * B16_P;                 // layer 1: input rows + weight rows, 32 k each
+    constexpr uint32_t TOMAX = T2 > T3 ? (T2 > T4 ? T2 : T4) : (T3 > T4 ? T3 : T4);
+    constexpr uint32_t LN = 2u * TOMAX * 16u * B16_P;                                    // later layers: two weight slabs
+    __shared__ __attribute__((aligned(16))) __bf16 lds[L1 > LN ? L1 : LN];
+    __bf16* Xs = lds;
+    __bf16* Ws = lds + 128u * B16_P;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t m = lane & 15u, g = lane >> 4;
+    const uint32_t row0 = blockIdx.x * 128u;
+    const uint32_t row = row0 + wave * 16u + m;
+    f32x4 a2[T2];
+    c16_zero(a2);
+    if constexpr (!LONG) {
+        bf16x8 h1[(T1 + 1) / 2];
+        {
+            f32x4 a1[T1];
+            c16_zero(a1);
+            b16_layer1<T1, true>(a1, a, 0u, row0, Xs, Ws, tid, wave, m, g);
+            c16_bias_act(a1, a.b[0], a.n[0], a.act[0], g);
+            b16_pack(a1, h1);
+        }
+        b16_layer<(T1 + 1) / 2, T2>(h1, a2, a.w[1], a.n[0], a.n[1], 0u, lds, tid, m, g);
+        c16_bias_act(a2, a.b[1], a.n[1], a.act[1], g);
+        c16_store(a2, a.y, a.y_stride, a.n[1], a.M, row, g);
+    } else {
+        static_assert(T1 % 4 == 0, "a half of layer 1 is a whole number of k-steps");
+        constexpr int T1H = T1 / 2;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            bf16x8 h1[T1H / 2];
+            {
+                f32x4 a1[T1H];
+                c16_zero(a1);
+                if (h) __syncthreads();                              // layer 2's weight slabs share the LDS with layer 1's
+                b16_layer1<T1H, false>(a1, a, (uint32_t)h * T1H * 16u, row0, Xs, Ws, tid, wave, m, g);
+                b16_hidden_pack(a1, a.b[0], (uint32_t)h * T1H * 16u, a.n[0], a.act[0], g, h1);
+            }
+            b16_layer<T1H / 2, T2>(h1, a2, a.w[1], a.n[0], a.n[1], (uint32_t)h * T1H * 16u, lds, tid, m, g);
+        }
+        bf16x8 h2[(T2 + 1) / 2];
+        b16_hidden_pack(a2, a.b[1], 0u, a.n[1], a.act[1], g, h2);
+        f32x4 a3[T3];
+        c16_zero(a3);
+        b16_layer<(T2 + 1) / 2, T3>(h2, a3, a.w[2], a.n[1], a.n[2], 0u, lds, tid, m, g);
+        bf16x8 h3[(T3 + 1) / 2];
+        b16_hidden_pack(a3, a.b[2], 0u, a.n[2], a.act[2], g, h3);
+        f32x4 a4[T4];
+        c16_zero(a4);
+        b16_layer<(T3 + 1) / 2, T4>(h3, a4, a.w[3], a.n[2], a.n[3], 0u, lds, tid, m, g);
+        c16_bias_act(a4, a.b[3], a.n[3], a.act[3], g);
+        if constexpr (HEAD) c16_gauss(a4[0], *gauss, a.M, row, g);
+        c16_store(a4, a.y, a.y_stride, a.n[3], a.M, row, g);
+    }
+}
+template <int T1, int T2, int T3, int T4>
+__global__ void __launch_bounds__(512, 4) chain_bf16_kernel(ChainArgs a) {
+    chain_b16_body<T1, T2, T3, T4, false>(a, nullptr);
+}
+template <int T1, int T2, int T3, int T4>
+__global__ void __launch_bounds__(512, 4) chain_bf16_head_kernel(ChainArgs a, GaussHead h) {
+    static_assert(T4 == 1, "the head sits on the 4-layer chain's last tile");
+    chain_b16_body<T1, T2, T3, T4, true>(a, &h);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Small batches (round 3): a 2-layer chain (an Encoder, learning/model.py:122-150) with its first layer SPLIT ALONG K.
 // Below ~16 k rows the chain kernel above is latency-bound, not throughput-bound: M / 128 workgroups each walk the whole k range of
 // layer 1 (35 slabs of 32 for the 1 112-wide dense slice, ~1.3 us each) one after the other — 0.16-0.18 ms for the actor forward from
@@ -778,13 +1026,19 @@ __global__ void __launch_bounds__(512) mlp_small_head_kernel(ChainArgs a, GaussH
 // tile shapes instantiated: the reference's encoder (<= 80 -> <= 64, or <= 96 -> <= 64) and MLP (<= 256 -> <= 160 -> <= 128 -> <= 16,
 // hidden activations none / LeakyReLU / ReLU); anything else: ChainKernel::None (the caller runs layer by layer).  The same nets go
 // to the same kernels at every batch size: split-k (2 layers) and mlp_small (4 layers) below 20 480 rows, chain16 from there on.
-ChainRoute chain_route(const ChainArgs& a) {
+// the fit rule, once: 0 = outside the built tile shapes, 5 / 6 = a 2-layer chain of that many first-layer tiles, 16 = the 4-layer chain
+static int chain_fit(const ChainArgs& a) {
     auto cheap = [](int act) { return act == 0 || act == 1 || act == 3; };
-    const bool mlp4 = a.n_layers == 4 && a.n[0] <= 256 && a.n[1] <= 160 && a.n[2] <= 128 && a.n[3] <= 16 && cheap(a.act[0]) && cheap(a.act[1]) &&
-                      cheap(a.act[2]);
+    if (a.n_layers == 2 && a.n[0] <= 96 && a.n[1] <= 64) return a.n[0] <= 80 ? 5 : 6;
+    if (a.n_layers == 4 && a.n[0] <= 256 && a.n[1] <= 160 && a.n[2] <= 128 && a.n[3] <= 16 && cheap(a.act[0]) && cheap(a.act[1]) && cheap(a.act[2]))
+        return 16;
+    return 0;
+}
+ChainRoute chain_route(const ChainArgs& a) {
+    const int fit = chain_fit(a);
     ChainRoute r{ChainKernel::None, 0, 0};
-    if (a.n_layers == 2 && a.n[0] <= 96 && a.n[1] <= 64) {
-        r.tn = a.n[0] <= 80 ? 5 : 6;
+    if (fit == 5 || fit == 6) {
+        r.tn = fit;
         if (a.M < 20480 && a.K0 >= 128) {                           // small batches: first layer split along k through a scratch buffer
             int chunk;
             splitk_chunks(a.M, a.K0, &chunk, &r.rt);
@@ -792,10 +1046,18 @@ ChainRoute chain_route(const ChainArgs& a) {
         } else {
             r.kernel = r.tn == 5 ? ChainKernel::Chain16_5 : ChainKernel::Chain16_6;
         }
-    } else if (mlp4) {
+    } else if (fit == 16) {
         r.kernel = a.M < 20480 && a.K0 <= 256 ? ChainKernel::MlpSmall : ChainKernel::Chain16Long;     // small batches: latency, not throughput
     }
     return r;
+}
+// precision = "bf16": the same nets, one kernel per tile shape at every batch size (no split-k family, no scratch buffer)
+ChainRoute chain_route_bf16(const ChainArgs& a) {
+    const int fit = chain_fit(a);
+    if (fit == 5) return ChainRoute{ChainKernel::Bf16_5, 5, 0};
+    if (fit == 6) return ChainRoute{ChainKernel::Bf16_6, 6, 0};
+    if (fit == 16) return ChainRoute{ChainKernel::Bf16Long, 0, 0};
+    return ChainRoute{ChainKernel::None, 0, 0};
 }
 
 // ---- the one table over ChainKernel: what a route is called, what it launches, which launch carries the Gaussian head ----
@@ -813,6 +1075,9 @@ static const ChainKernelRow kChainKernels[] = {
     {ChainKernel::Chain16_5, "chain16<5,4,0,0>", chain_plain<chain16_kernel<5, 4, 0, 0>>, nullptr, 128},
     {ChainKernel::Chain16_6, "chain16<6,4,0,0>", chain_plain<chain16_kernel<6, 4, 0, 0>>, nullptr, 128},
     {ChainKernel::Chain16Long, "chain16<16,10,8,1>", chain_plain<chain16_kernel<16, 10, 8, 1>>, chain_with_head<chain16_head_kernel<16, 10, 8, 1>>, 128},
+    {ChainKernel::Bf16_5, "chain_bf16<5,4,0,0>", chain_plain<chain_bf16_kernel<5, 4, 0, 0>>, nullptr, 128},
+    {ChainKernel::Bf16_6, "chain_bf16<6,4,0,0>", chain_plain<chain_bf16_kernel<6, 4, 0, 0>>, nullptr, 128},
+    {ChainKernel::Bf16Long, "chain_bf16<16,10,8,1>", chain_plain<chain_bf16_kernel<16, 10, 8, 1>>, chain_with_head<chain_bf16_head_kernel<16, 10, 8, 1>>, 128},
 };
 static const ChainKernelRow* chain_kernel_row(const ChainRoute& r) {        // null: ChainKernel::None
     for (const ChainKernelRow& k : kChainKernels) if (k.kernel == r.kernel) return &k;

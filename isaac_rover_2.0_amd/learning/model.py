@@ -22,6 +22,12 @@ Training: autograd cannot see the kernels, so ``backward(d_out)`` walks an UNFUS
 ``rover_linear_backward`` and leaves every parameter's gradient in its ``.grad``; ``parameters()`` hands the tensors to a torch
 optimiser.  The PPO loss at the outputs and the update loop (skrl's ``PPO._update``) live in ``learning/ppo.py``.  The backward of
 the fused chain kernels is not built.
+
+``precision="bf16"`` (opt-in, inference only): the same three chains with bf16 operands and f32 accumulation
+(``rover_mlp_chain_forward_bf16`` / ``rover_mlp_chain_act_bf16``: every input, weight and hidden activation rounded to bf16, f32 bias,
+activation and Gaussian head; the arithmetic is stated in ``include/rover_step.h``, the reasoning in DESIGN.md §4.13).  What a rollout
+stores is the acting policy's own action, log-probability and value, so PPO's ratio stays exact; training, and ``act(taken_actions=...)``
+inside the update, stay f32.
 """
 from __future__ import annotations
 
@@ -47,13 +53,20 @@ class HeightmapNet:
 
     def __init__(self, engine, num_observations, num_sparse, num_dense, num_outputs, head_activation, mlp_features=(256, 160, 128),
                  encoder_features=(80, 60), activation_function="leakyrelu", device="cuda:0", seed=0, clip_actions=False, clip_log_std=True,
-                 min_log_std=-20.0, max_log_std=2.0, reduction="sum", row_offset=0, action_low=-1.0, action_high=1.0):
-        """``seed`` initialises the weights and keys the action noise; ``row_offset``: the global row of this net's row 0 (a shard's
+                 min_log_std=-20.0, max_log_std=2.0, reduction="sum", row_offset=0, action_low=-1.0, action_high=1.0, precision="f32"):
+        """``precision``: "f32" (default) or "bf16" — what compute() / act() run when their own ``precision`` argument is None.  bf16 is
+        for large rollout batches.  Measured on an MI355X with the native 1 750-float obs (EXPERIMENTS.md §19): act() in f32 is faster at
+        512 and 4 096 rows (63 against 83 us, 80 against 103 us: the f32 split-k / mlp_small routes), the two are level at 8 192 rows
+        (107 us each), and bf16 is faster from 16 384 rows on (111 against 177 us; 187 against 337 us at 65 536).
+        ``seed`` initialises the weights and keys the action noise; ``row_offset``: the global row of this net's row 0 (a shard's
         env_offset); ``clip_*`` / ``min_log_std`` / ``max_log_std`` / ``reduction``: skrl's mixin arguments (model.py:153-156,198-201);
         ``action_low`` / ``action_high``: the action space's bounds, used only with ``clip_actions``."""
         g = torch.Generator().manual_seed(seed)
         if reduction not in ("sum", "mean", "prod", "max", "min", None):
             raise ValueError(f"reduction must be one of 'sum', 'mean', 'prod', 'max', 'min' or None, not {reduction!r}")
+        if precision not in ("f32", "bf16"):
+            raise ValueError(f"precision must be 'f32' or 'bf16', not {precision!r}")
+        self.precision = precision
         self.seed, self.row_offset, self.reduction = int(seed), int(row_offset), reduction
         self.clip_actions, self.clip_log_std = bool(clip_actions), bool(clip_log_std)
         self.min_log_std, self.max_log_std = float(min_log_std), float(max_log_std)
@@ -89,28 +102,53 @@ class HeightmapNet:
             b = self._bufs[key] = torch.empty(rows, cols, device=self.device)
         return b
 
-    def _plan(self, rows, fused):
+    def _precision(self, precision, fused):
+        precision = self.precision if precision is None else precision
+        if precision not in ("f32", "bf16"):
+            raise ValueError(f"precision must be 'f32' or 'bf16', not {precision!r}")
+        if precision == "bf16" and fused is not None and not fused:
+            raise ValueError("precision='bf16' runs the fused chain kernels only: fused=False has no bf16 layer kernels")
+        return precision
+
+    @staticmethod
+    def _kw(precision):
+        """The engine calls' precision argument: named only where it is not their default."""
+        return {} if precision == "f32" else {"precision": precision}
+
+    def _plan(self, rows, fused, precision="f32"):
         """The ForwardPlan of a batch of ``rows`` rows, asked of the library's route queries once and kept like the buffers: a chain is one
         kernel where rover_mlp_chain_route names one; the encoders take chain_pair_forward at the batch sizes where the library runs two
         encoders of these widths side by side ("pair(...)", rover_step.h).  That is asked with inputs long enough to split along k: at
-        those batch sizes shorter slices take the same call, which then runs them one after the other and copies the columns itself."""
-        plan = self._plans.get((rows, fused))
+        those batch sizes shorter slices take the same call, which then runs them one after the other and copies the columns itself.
+        ``precision="bf16"``: all three chains as bf16 chain kernels (rover_mlp_chain_route_bf16 must name one for each), never a pair."""
+        plan = self._plans.get((rows, fused, precision))
+        if plan is None and precision == "bf16":
+            # all three chains in bf16 or none: no silent mix of precisions (an empty heightmap slice is a chain too: K0 = 0)
+            for name, layers in (("encoder0", self.encoder0), ("encoder1", self.encoder1), ("network", self.network)):
+                if self.engine.chain_route(rows, *self.engine.chain_shape(layers), precision="bf16") is None:
+                    raise ValueError(f"precision='bf16': {name} {self.engine.chain_shape(layers)} fits no bf16 chain kernel "
+                                     "(rover_mlp_chain_route_bf16 refuses it; the built tile shapes are listed in rover_step.h)")
+            plan = self._plans[(rows, fused, precision)] = ForwardPlan(False, True, True, True)
         if plan is None:
             eng = self.engine
             chain = lambda layers: bool(fused and eng.chain_route(rows, *eng.chain_shape(layers)) is not None)
             long_enc = [(1 << 20,) + eng.chain_shape(enc)[1:] for enc in (self.encoder0, self.encoder1)]       # (k0, widths, activations)
             pair = bool(fused and self.num_sparse > 0 and self.num_dense > 0 and (eng.chain_pair_route(rows, *long_enc) or "").startswith("pair("))
-            plan = self._plans[(rows, fused)] = ForwardPlan(pair, chain(self.encoder0), chain(self.encoder1), chain(self.network))
+            plan = self._plans[(rows, fused, precision)] = ForwardPlan(pair, chain(self.encoder0), chain(self.encoder1), chain(self.network))
         return plan
 
-    def compute(self, states, fused=None):
+    def compute(self, states, fused=None, precision=None):
         """model.py:185-195 / :231-241.  ``states`` [E, num_observations] float32 (may be the task's obs_buf itself).
         ``fused`` (default): each encoder and the MLP + head run as ONE kernel each (``rover_mlp_chain_forward``: activations stay in
-        registers) when the library has a chain kernel for their widths; ``fused=False``: one ``rover_linear_forward`` launch per layer."""
-        cat, mlp_fused = self._encode(states, fused)
+        registers) when the library has a chain kernel for their widths; ``fused=False``: one ``rover_linear_forward`` launch per layer.
+        ``precision`` (default: the net's): "bf16" runs all three chains with bf16 operands and f32 accumulation — ValueError if one of
+        them fits no bf16 chain kernel, or with ``fused=False``."""
+        precision = self._precision(precision, fused)
+        cat, mlp_fused = self._encode(states, fused, precision)
         if mlp_fused:
             e = states.shape[0]
-            return self.engine.chain_forward(cat, self.network, self._buf(("mlp", len(self.network) - 1), e, self.network[-1].weight.shape[0]))
+            return self.engine.chain_forward(cat, self.network, self._buf(("mlp", len(self.network) - 1), e, self.network[-1].weight.shape[0]),
+                                             **self._kw(precision))
         return self._mlp_layers(cat)
 
     def _mlp_layers(self, cat):
@@ -119,10 +157,11 @@ class HeightmapNet:
             x = self.engine.linear_forward(x, layer.weight, layer.bias, layer.activation, self._buf(("mlp", li), cat.shape[0], layer.weight.shape[0]))
         return x
 
-    def _encode(self, states, fused):
-        """Both encoders and the proprioception columns into the concat buffer -> (cat, whether the MLP + head runs as one chain kernel)."""
+    def _encode(self, states, fused, precision="f32"):
+        """Both encoders and the proprioception columns into the concat buffer -> (cat, whether the MLP + head runs as one chain kernel).
+        The proprioception columns are copied as f32 in either precision (the bf16 MLP chain rounds them as it reads them)."""
         e = states.shape[0]
-        plan = self._plan(e, fused is None or bool(fused))
+        plan = self._plan(e, fused is None or bool(fused), precision)
         self._fwd[e] = (states, plan)
         p, ns, nd = self.num_proprioception, self.num_sparse, self.num_dense
         ef = self.encoder0[-1].weight.shape[0]
@@ -137,7 +176,7 @@ class HeightmapNet:
         for enc, as_chain, lo, n, col in ((self.encoder0, plan.enc0, p, ns, p), (self.encoder1, plan.enc1, p + ns, nd, p + ef)):
             x = states[:, lo:lo + n]
             if as_chain:
-                self.engine.chain_forward(x, enc, cat[:, col:col + ef])
+                self.engine.chain_forward(x, enc, cat[:, col:col + ef], **self._kw(precision))
                 continue
             for li, layer in enumerate(enc):
                 last = li == len(enc) - 1
@@ -146,7 +185,7 @@ class HeightmapNet:
         return cat, plan.mlp
 
     # ---- skrl's mixins: GaussianMixin.act (actor), DeterministicMixin.act (critic) --------------------------------
-    def act(self, states, taken_actions=None, deterministic=False, step=None, role="", fused=None):
+    def act(self, states, taken_actions=None, deterministic=False, step=None, role="", fused=None, precision=None):
         """Actor: -> (actions [E, A], log_prob [E, 1] ([E, A] with reduction None), {"mean_actions": mean [E, A]}) with
         mean = compute(states), actions = mean + exp(log_std') eps (``deterministic``: mean), clamped to the action bounds only with
         ``clip_actions``, and log_prob that of ``taken_actions`` if given, else of the returned actions.  Also skrl's calling shape:
@@ -156,12 +195,14 @@ class HeightmapNet:
         counter lives on the device and advances by one per act() — not when ``taken_actions`` is given (an evaluation of old actions)
         and not when ``step`` (an explicit counter value) is passed.  Capturing act() in a graph: warm it up once first; every replay
         then reads and advances the same counter an eager call does.
+        ``precision`` (default: the net's) as in compute(): with "bf16" the mean comes from the bf16 chains and the head is the f32
+        head on it — log_prob is exactly that of the policy that acted.
         Critic (no log-std parameter): -> (value, None, {})."""
         if isinstance(states, dict):
             inputs = states
             states, taken_actions = inputs["states"], inputs.get("taken_actions", taken_actions)
         if self.log_std_parameter is None:
-            value = self.compute(states, fused)
+            value = self.compute(states, fused, precision)
             if self.clip_actions:
                 value = torch.clamp(value, self.action_low, self.action_high)
             return value, None, {}
@@ -177,9 +218,10 @@ class HeightmapNet:
             head["step_dev"] = self._act_counter
         else:
             head["step"] = int(step)
-        cat, mlp_fused = self._encode(states, fused)
+        precision = self._precision(precision, fused)
+        cat, mlp_fused = self._encode(states, fused, precision)
         if mlp_fused:
-            self.engine.chain_act(cat, self.network, mean, self.log_std_parameter, actions, log_prob, **head)
+            self.engine.chain_act(cat, self.network, mean, self.log_std_parameter, actions, log_prob, **self._kw(precision), **head)
         else:
             self.engine.gaussian_head(self._mlp_layers(cat), self.log_std_parameter, actions, log_prob, **head)
         if step is None and taken_actions is None:

@@ -23,6 +23,10 @@ the host form's; the skipped minibatches still cost their forward, loss and back
 
 Out of scope: the backward of the fused chain kernels (the update runs every layer as its own launch), gradient all-reduce across ranks,
 preprocessors, learning-rate schedulers, bf16 / fp16 training.
+
+Training precision is f32 whatever the nets' ``precision``: the update's forwards pass ``precision="f32"`` explicitly.  A rollout may
+ACT in bf16 (``HeightmapNet(precision="bf16")``): the stored ``log_prob`` is then the bf16 behaviour policy's own, the ratio
+``pi_new / pi_behaviour`` is exact, and only the KL estimate of the first minibatch picks up the small f32 - bf16 offset.
 """
 from __future__ import annotations
 
@@ -93,8 +97,8 @@ class PPO:
         """Forward of both nets, the loss and every gradient of one minibatch (no optimiser step) -> the device stats tensor.  Enqueues
         only; after one warm-up call of the same size it can be captured in a graph."""
         c, pol = self.cfg, self.policy
-        _, _, out = pol.act(states, taken_actions=actions, fused=False)
-        v, _, _ = self.value.act(states, fused=False)
+        _, _, out = pol.act(states, taken_actions=actions, fused=False, precision="f32")
+        v, _, _ = self.value.act(states, fused=False, precision="f32")
         d_mean, d_value = self._grads(states.shape[0], actions.shape[1])
         self.engine.ppo_loss(out["mean_actions"], pol.log_std_parameter, actions, log_prob, advantages, v, values, returns, d_mean, d_value,
                              pol.log_std_parameter.grad, self._stats, ratio_clip=c["ratio_clip"], value_clip=c["value_clip"],
