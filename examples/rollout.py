@@ -39,7 +39,8 @@ def main():
                     "--policy student: the reference's best.pt (its ['state_dict'] is loaded)")
     ap.add_argument("--rollouts", type=int, default=0, help="--policy actor: store N steps in a RolloutMemory, then compute_gae (0 = off)")
     ap.add_argument("--precision", choices=("f32", "bf16"), default="f32",
-                    help="--policy actor: what the actor and the critic act in (bf16: bf16 operands, f32 accumulation and head)")
+                    help="--policy actor: what the actor and the critic act in (bf16: bf16 operands, f32 accumulation and head); "
+                    "--policy student: what StudentPolicy.act runs in (bf16: every matrix product, the GRU state stays f32)")
     args = ap.parse_args()
     if args.rollouts < 0 or (args.rollouts and args.policy != "actor"):
         ap.error("--rollouts N needs N >= 0 and --policy actor")
@@ -69,13 +70,14 @@ def main():
     student = None
     if args.policy == "student":
         from isaac_rover_amd.learning.student import StudentPolicy
-        student = StudentPolicy(task._engine, task, device=task.device)
+        student = StudentPolicy(task._engine, task, device=task.device, precision=args.precision)
         if args.checkpoint:
             sd = torch.load(args.checkpoint, map_location="cpu")
             student.load_state_dict(sd["state_dict"] if isinstance(sd, dict) and "state_dict" in sd else sd)
         student.init_hidden(args.envs)
         print(f"policy: StudentPolicy, {sum(v.numel() for v in student.state_dict().values()):,} parameters"
-              f"{' from ' + args.checkpoint if args.checkpoint else ' (fresh initialisation)'}")
+              f"{' from ' + args.checkpoint if args.checkpoint else ' (fresh initialisation)'}"
+              f"{', acting in bf16' if args.precision == 'bf16' else ''}")
     critic = memory = done = None
     if args.rollouts:
         from isaac_rover_amd.learning.model import DeterministicHeightmap

@@ -454,6 +454,14 @@ ROVER_API const char *rover_mlp_chain_route_bf16(int32_t M, int32_t K0, int32_t 
                                                  const int32_t *activations);
 ROVER_API const char *rover_mlp_chain_act_route_bf16(int32_t M, int32_t K0, int32_t n_layers, const int32_t *widths,
                                                      const int32_t *activations, const rover_gauss_head *head);
+/* rover_linear_forward_bf16: ONE Layer under the same contract — x and W rounded to bf16 as they are read, exact products summed in
+ * f32 in a fixed order, f32 bias and activation, f32 output.  Whoever reads y next rounds it as it reads, so a net run layer by layer
+ * through this call has the arithmetic of a chain ("rounded before the next layer reads it").  Parameters and refusals are
+ * rover_linear_forward's (N <= 256, K >= 0, rows at a stride); no split-k, no scratch, capturable.  rover_linear_route_bf16:
+ * "linear_bf16<128,128>" (128 rows x 128 columns per workgroup), "none" for M = 0, NULL where refused. */
+ROVER_API int rover_linear_forward_bf16(rover_ctx *ctx, const float *x, int64_t x_stride, int32_t M, int32_t K, const float *weight,
+                                        const float *bias, int32_t N, int32_t activation, float *y, int64_t y_stride, void *stream);
+ROVER_API const char *rover_linear_route_bf16(int32_t M, int32_t K, int32_t N);
 /* Host only (no ctx, no device): out[i] = the bf16 rounding of in[i] as an f32 — the one definition the kernels share. */
 ROVER_API int rover_bf16_round(const float *in, int64_t n, float *out);
 
@@ -690,6 +698,25 @@ ROVER_API int rover_gru_cell(rover_ctx *ctx, const float *x, int64_t x_stride, c
  * workgroups are at least 512, else "gru_cell<1>" (32 rows per workgroup); "none" for M = 0; NULL where the call would refuse the
  * shapes.  Every limit on M, K and H lives behind this query. */
 ROVER_API const char *rover_gru_cell_route(int32_t M, int32_t K, int32_t H);
+
+/* rover_gru_cell_bf16: the same cell with bf16 operands in its matrix products and everything else in f32 (precision = "bf16",
+ * inference only).  Parameters, shapes, strides, reset_mask, refusals (overlap included), M = 0 and K = 0 are
+ * rover_gru_cell's.  The arithmetic — the tests hold the kernel to it:
+ *   operands      every element of x, h_in, w_ih and w_hh is rounded to bf16 as it is read for the products (rover_bf16_round: nearest
+ *                 even, NaN stays NaN, +-Inf stays +-Inf).  No bf16 copy of the weights or of the state exists anywhere.
+ *   products      exact in f32, summed in f32 in a fixed order on v_mfma_f32_16x16x32_bf16: s_r and s_z over K + H, s_in over the x slabs
+ *                 alone, s_hn over the h slabs alone.  x and h are each zero-filled to a multiple of 32, so no k-step mixes the two
+ *                 (r multiplies s_hn only).
+ *   epilogue      rover_gru_cell's, operation for operation, in f32: the f32 biases, sigmoid(v) = 1 / (1 + expf(-v)), tanhf,
+ *                 h' = (1 - z) * n + z * h with the UNROUNDED f32 h_in (0 on a reset row).  h_out is f32.
+ * The state stays f32 on purpose: with z near 1 the cell is h' = h + (1 - z)(n - h), and a state rounded to 8 significant bits every
+ * step would drop every update below 2^-9 |h|.
+ * rover_gru_cell_route_bf16 — host only, no ctx: "gru_cell_bf16<128,64>" (128 rows x 64 columns of the hidden state per workgroup, at
+ * every batch size); "none" for M = 0; NULL where the call would refuse the shapes. */
+ROVER_API int rover_gru_cell_bf16(rover_ctx *ctx, const float *x, int64_t x_stride, const float *h_in, int64_t h_in_stride, int32_t M,
+                                  int32_t K, int32_t H, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
+                                  const uint8_t *reset_mask, float *h_out, int64_t h_out_stride, void *stream);
+ROVER_API const char *rover_gru_cell_route_bf16(int32_t M, int32_t K, int32_t H);
 
 /* rover_gru_cell_train: rover_gru_cell with one more output for the backward, gates [M, 4H] at a row stride (>= 4H): r | z | n | q with
  * q = s_hn + b_hn as written above.  h_out has the same bits as rover_gru_cell's on the same inputs (the same kernel body; the extra

@@ -196,6 +196,8 @@ SYMBOLS = {
     "rover_mlp_chain_route_bf16": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rover_mlp_chain_act_route_bf16": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(GaussHead)]),
     "rover_bf16_round": (C.c_int, [_P, C.c_int64, _P]),
+    "rover_linear_forward_bf16": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    "rover_linear_route_bf16": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
     "rover_gae": (C.c_int, [_P, C.POINTER(GaeDesc), _P]),
     "rover_combine_moments": (C.c_int, [_P, _P, _P]),
     "rover_linear_backward": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64,
@@ -208,6 +210,8 @@ SYMBOLS = {
     "rover_optim_step": (C.c_int, [_P, C.c_int32, C.POINTER(OptimStepDesc), _P]),
     "rover_gru_cell": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rover_gru_cell_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
+    "rover_gru_cell_bf16": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "rover_gru_cell_route_bf16": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
     "rover_gated_sum": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "rover_gru_cell_train": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64,
                                        _P]),
@@ -354,7 +358,8 @@ PRECISIONS = ("f32", "bf16")
 
 
 def _precision_suffix(precision):
-    """"" / "_bf16": the suffix of the chain entry points of ``precision`` (rover_mlp_chain_forward / rover_mlp_chain_forward_bf16, ...)."""
+    """"" / "_bf16": the suffix of the entry points of ``precision`` (rover_mlp_chain_forward / rover_mlp_chain_forward_bf16, rover_gru_cell /
+    rover_gru_cell_bf16, rover_linear_forward / rover_linear_forward_bf16 and their route queries)."""
     if precision not in PRECISIONS:
         raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
     return "" if precision == "f32" else "_bf16"
@@ -697,8 +702,11 @@ class Engine:
             raise RoverError(f"{what}: {name} must be a float32 GPU matrix{'' if shape is None else ' [%d,%d]' % shape} with unit column stride")
         return t
 
-    def linear_forward(self, x, weight, bias, activation, out):
-        """out[:, :N] = act(x[:, :K] @ weight.T + bias); x / out may be column slices of wider row-major tensors."""
+    def linear_forward(self, x, weight, bias, activation, out, precision="f32"):
+        """out[:, :N] = act(x[:, :K] @ weight.T + bias); x / out may be column slices of wider row-major tensors.
+        ``precision="bf16"``: x and weight rounded to bf16 as they are read, f32 accumulation, bias, activation and output
+        (rover_linear_forward_bf16; the arithmetic is stated in rover_step.h)."""
+        name = "rover_linear_forward" + _precision_suffix(precision)
         m, k = x.shape
         n = weight.shape[0]
         self._f32_rows(x, "x", "linear_forward")
@@ -708,9 +716,8 @@ class Engine:
         self._chk(bias, (n,), torch.float32, "bias")
         if out.shape[0] != m or out.shape[1] != n:
             raise RoverError(f"linear_forward: out must be [{m},{n}]")
-        self._check(self.lib.rover_linear_forward(self._h, _ptr(x), max(x.stride(0), k), m, k, _ptr(weight), _ptr(bias), n,
-                                                  self.ACTIVATIONS[activation], _ptr(out), out.stride(0), _stream(self._dev_index)),
-                    "rover_linear_forward")
+        self._check(getattr(self.lib, name)(self._h, _ptr(x), max(x.stride(0), k), m, k, _ptr(weight), _ptr(bias), n,
+                                            self.ACTIVATIONS[activation], _ptr(out), out.stride(0), _stream(self._dev_index)), name)
         return out
 
     @staticmethod
@@ -825,11 +832,13 @@ class Engine:
     bf16_round = staticmethod(bf16_round)
 
     # ---- the student's recurrent block (rover_gru_cell, rover_gated_sum) -------------------------------------
-    def gru_cell(self, x, h_in, w_ih, w_hh, b_ih, b_hh, h_out, reset_mask=None):
+    def gru_cell(self, x, h_in, w_ih, w_hh, b_ih, b_hh, h_out, reset_mask=None, precision="f32"):
         """One layer of torch.nn.GRU for one time step (rover_gru_cell): h_out = cell(x [m, k], h_in [m, h]); w_ih [3h, k], w_hh [3h, h],
         b_ih / b_hh [3h] or None.  x, h_in and h_out may be column slices / padded rows; ``reset_mask``: optional [m] bool / uint8 —
-        marked rows read h_in as zero.  h_out must not overlap h_in (the library refuses it)."""
-        what = "gru_cell"
+        marked rows read h_in as zero.  h_out must not overlap h_in (the library refuses it).  ``precision="bf16"``: the operands of the
+        matrix products rounded to bf16 as they are read; gates, blend and h_out in f32 on the unrounded h_in (rover_gru_cell_bf16)."""
+        name = "rover_gru_cell" + _precision_suffix(precision)
+        what = name[len("rover_"):]
         self._f32_rows(x, "x", what)
         m, k = x.shape
         hd = w_hh.shape[1] if w_hh is not None and w_hh.dim() == 2 else -1
@@ -841,16 +850,16 @@ class Engine:
         self._chk(b_ih, (3 * hd,), torch.float32, "b_ih")
         self._chk(b_hh, (3 * hd,), torch.float32, "b_hh")
         reset_mask = self._mask(reset_mask, m)
-        self._check(self.lib.rover_gru_cell(self._h, _ptr(x), max(x.stride(0), k), _ptr(h_in), h_in.stride(0) if m > 1 else hd, m, k, hd, _ptr(w_ih) if k > 0 else None,
+        self._check(getattr(self.lib, name)(self._h, _ptr(x), max(x.stride(0), k), _ptr(h_in), h_in.stride(0) if m > 1 else hd, m, k, hd, _ptr(w_ih) if k > 0 else None,
                                             _ptr(w_hh), _ptr(b_ih), _ptr(b_hh), _ptr(reset_mask), _ptr(h_out), h_out.stride(0) if m > 1 else hd,
-                                            _stream(self._dev_index)), "rover_gru_cell")
+                                            _stream(self._dev_index)), name)
         return h_out
 
     @classmethod
-    def gru_cell_route(cls, m, k, h):
-        """The instantiation gru_cell runs for [m, k] inputs and a hidden width h ("gru_cell<4>", "gru_cell<1>"); "none" for m = 0, None
-        where the call would be refused.  Host only."""
-        return cls._route(load().rover_gru_cell_route(int(m), int(k), int(h)))
+    def gru_cell_route(cls, m, k, h, precision="f32"):
+        """The instantiation gru_cell runs for [m, k] inputs and a hidden width h ("gru_cell<4>", "gru_cell<1>"; ``precision="bf16"``:
+        "gru_cell_bf16<128,64>"); "none" for m = 0, None where the call would be refused.  Host only."""
+        return cls._route(getattr(load(), "rover_gru_cell_route" + _precision_suffix(precision))(int(m), int(k), int(h)))
 
     def gru_cell_train(self, x, h_in, w_ih, w_hh, b_ih, b_hh, h_out, gates, reset_mask=None):
         """gru_cell that also stores ``gates`` [m, 4h] = r | z | n | q for gru_cell_backward (rover_gru_cell_train); h_out has gru_cell's bits."""
@@ -1136,10 +1145,10 @@ class Engine:
                 (C.c_int32 * n)(*[a if isinstance(a, int) else cls.ACTIVATIONS[a] for a in activations]))
 
     @classmethod
-    def linear_route(cls, m, k, n):
-        """The instantiation linear_forward runs for an [m, k] x [n, k]^T layer ("linear_act<3,4>x2", ...); "none" for m = 0,
-        None where the call would be refused."""
-        return cls._route(load().rover_linear_route(int(m), int(k), int(n)))
+    def linear_route(cls, m, k, n, precision="f32"):
+        """The instantiation linear_forward runs for an [m, k] x [n, k]^T layer ("linear_act<3,4>x2", ...; ``precision="bf16"``:
+        "linear_bf16<128,128>"); "none" for m = 0, None where the call would be refused."""
+        return cls._route(getattr(load(), "rover_linear_route" + _precision_suffix(precision))(int(m), int(k), int(n)))
 
     @classmethod
     def chain_route(cls, m, k0, widths, activations, precision="f32"):

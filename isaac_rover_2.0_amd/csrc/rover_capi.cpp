@@ -1416,17 +1416,29 @@ static int build_knn_map_impl(rover_ctx* c, const float* vertices, int32_t V, co
     return ROVER_OK;
 }
 
-int rover_linear_forward(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K, const float* weight, const float* bias,
-                         int32_t N, int32_t activation, float* y, int64_t y_stride, void* stream) {
+// the f32 and the bf16 layer differ in the launch alone (launch_linear_act: rover_mlp.hip; launch_linear_bf16: rover_bf16_tile.hip)
+static int linear_forward_run(rover_ctx* c, const char* what, hipError_t (*launch)(const LinearArgs&, hipStream_t), const float* x, int64_t x_stride,
+                              int32_t M, int32_t K, const float* weight, const float* bias, int32_t N, int32_t activation, float* y, int64_t y_stride,
+                              void* stream) {
     if (!c) return ROVER_E_INVALID;
     // K = 0: a layer over an empty obs slice (model.py builds Encoder(0, ...) when a heightmap part is absent) = act(bias)
     if ((K > 0 && (!x || !weight)) || !y || M < 0 || K < 0 || N <= 0 || N > 256 || x_stride < K || y_stride < N || activation < 0 || activation > 4)
-        return fail(c, ROVER_E_INVALID, "linear_forward: bad arguments (M=%d K=%d N=%d act=%d)", M, K, N, activation);
+        return fail(c, ROVER_E_INVALID, "%s: bad arguments (M=%d K=%d N=%d act=%d)", what, M, K, N, activation);
     if (M == 0) return ROVER_OK;
     USE_DEVICE(c);
     LinearArgs a{x, x_stride, weight, bias, y, y_stride, M, K, N, activation};
-    HIP_TRY(c, launch_linear_act(a, (hipStream_t)stream));
+    HIP_TRY(c, launch(a, (hipStream_t)stream));
     return ROVER_OK;
+}
+
+int rover_linear_forward(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K, const float* weight, const float* bias,
+                         int32_t N, int32_t activation, float* y, int64_t y_stride, void* stream) {
+    return linear_forward_run(c, "linear_forward", launch_linear_act, x, x_stride, M, K, weight, bias, N, activation, y, y_stride, stream);
+}
+
+int rover_linear_forward_bf16(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K, const float* weight, const float* bias,
+                              int32_t N, int32_t activation, float* y, int64_t y_stride, void* stream) {
+    return linear_forward_run(c, "linear_forward_bf16", launch_linear_bf16, x, x_stride, M, K, weight, bias, N, activation, y, y_stride, stream);
 }
 
 // One chain, validated in one place.  The shape half: M, K0, the depth, every width and activation — all chain_route() reads, so all a route query looks at (no pointer of
@@ -1548,6 +1560,12 @@ const char* rover_linear_route(int32_t M, int32_t K, int32_t N) {
     const LinearRoute r = linear_route(M, N);
     if (K < 0 || !r.nw) return nullptr;
     return M == 0 ? "none" : linear_route_name(r);
+}
+
+const char* rover_linear_route_bf16(int32_t M, int32_t K, int32_t N) {
+    const char* name = linear_route_bf16_name(M, N);
+    if (K < 0 || !name) return nullptr;
+    return M == 0 ? "none" : name;
 }
 
 static const char* chain_route_query(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations, ChainRouteFn route) {
@@ -1998,7 +2016,8 @@ int rover_optim_step(rover_ctx* c, int32_t handle, const rover_optim_step_desc* 
 // ---- the student policy's recurrent block (rover_gru.hip) ----
 static int gru_cell_run(rover_ctx* c, const char* what, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K,
                         int32_t H, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
-                        int64_t h_out_stride, bool train, float* gates, int64_t gates_stride, void* stream) {
+                        int64_t h_out_stride, bool train, float* gates, int64_t gates_stride, void* stream,
+                        hipError_t (*launch)(const GruArgs&, hipStream_t) = launch_gru_cell) {
     if (!c) return ROVER_E_INVALID;
     if (!gru_cell_route(M, K, H).nw) return fail(c, ROVER_E_INVALID, "%s: M=%d K=%d H=%d outside M >= 0, K >= 0, 1 <= H <= %d", what, M, K, H, 32 * 65535);
     if (M == 0) return ROVER_OK;                   // nothing is read or written: no pointer is required
@@ -2022,7 +2041,7 @@ static int gru_cell_run(rover_ctx* c, const char* what, const float* x, int64_t 
     if (og.lo && overlap(og, out)) return fail(c, ROVER_E_INVALID, "%s: gates overlaps h_out", what);
     USE_DEVICE(c);
     GruArgs a{x, x_stride, h_in, h_in_stride, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, M, K, H, train ? gates : nullptr, gates_stride};
-    HIP_TRY(c, launch_gru_cell(a, (hipStream_t)stream));
+    HIP_TRY(c, launch(a, (hipStream_t)stream));
     return ROVER_OK;
 }
 
@@ -2030,6 +2049,13 @@ int rover_gru_cell(rover_ctx* c, const float* x, int64_t x_stride, const float* 
                    const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
                    int64_t h_out_stride, void* stream) {
     return gru_cell_run(c, "gru_cell", x, x_stride, h_in, h_in_stride, M, K, H, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, false, nullptr, 0, stream);
+}
+
+int rover_gru_cell_bf16(rover_ctx* c, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K, int32_t H,
+                        const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
+                        int64_t h_out_stride, void* stream) {
+    return gru_cell_run(c, "gru_cell_bf16", x, x_stride, h_in, h_in_stride, M, K, H, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, false, nullptr, 0,
+                        stream, launch_gru_cell_bf16);
 }
 
 int rover_gru_cell_train(rover_ctx* c, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K, int32_t H,
@@ -2078,6 +2104,12 @@ const char* rover_gru_cell_route(int32_t M, int32_t K, int32_t H) {
     const GruRoute r = gru_cell_route(M, K, H);
     if (!r.nw) return nullptr;
     return M == 0 ? "none" : gru_cell_route_name(r);
+}
+
+const char* rover_gru_cell_route_bf16(int32_t M, int32_t K, int32_t H) {
+    const char* name = gru_cell_route_bf16_name(M, K, H);
+    if (!name) return nullptr;
+    return M == 0 ? "none" : name;
 }
 
 int rover_gated_sum(rover_ctx* c, const float* add, int64_t add_stride, const float* mul, int64_t mul_stride, const float* pre, int64_t pre_stride,

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rover_internal.h"
+#include "rover_act.h"
 
 namespace rover {
 
@@ -25,7 +26,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define GRU_BK 32
 #define GRU_PITCH 33
 
-__device__ __forceinline__ float gru_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }     // expf(+big) = inf -> 0, expf(-big) = 0 -> 1: no NaN
+// (gru_sigmoid is rover_act.h's)
 
 // TRAIN: the epilogue also stores r | z | n | q (q = s_hn + b_hn) to a.gates for the backward; h' is computed by the same operations.
 template <int NW, bool TRAIN = false>

@@ -203,6 +203,9 @@ struct LinearRoute { int nw, nt, ny; };
 LinearRoute linear_route(int M, int N);
 const char* linear_route_name(const LinearRoute& r);      // "linear_act<3,4>x2", or NULL
 hipError_t launch_linear_act(const LinearArgs& a, hipStream_t s);
+// the same layer with bf16 operands (rover_bf16_tile.hip): one instantiation, linear_route's refusals; the name, or NULL
+const char* linear_route_bf16_name(int M, int N);        // "linear_bf16<128,128>"
+hipError_t launch_linear_bf16(const LinearArgs& a, hipStream_t s);
 
 // One GRU layer for one time step (rover_gru_cell of the C ABI, validated; rover_gru.hip): torch.nn.GRU's cell, gates r, z, n
 struct GruArgs {
@@ -220,6 +223,9 @@ struct GruRoute { int nw; };
 GruRoute gru_cell_route(int M, int K, int H);
 const char* gru_cell_route_name(const GruRoute& r);       // "gru_cell<4>", or NULL
 hipError_t launch_gru_cell(const GruArgs& a, hipStream_t s);                 // a.gates set: the training instantiation of the same route
+// the same cell with bf16 operands and an f32 state (rover_bf16_tile.hip): one instantiation, gru_cell_route's refusals; no gates
+const char* gru_cell_route_bf16_name(int M, int K, int H);       // "gru_cell_bf16<128,64>", or NULL
+hipError_t launch_gru_cell_bf16(const GruArgs& a, hipStream_t s);
 
 // The backward of one cell (rover_gru_cell_backward of the C ABI, validated; rover_gru.hip): dgi, dgh [M, 3H] and dh_in [M, H] from the
 // gradient at h' (dh_above + dh_next), the gates the training forward stored and w_hh

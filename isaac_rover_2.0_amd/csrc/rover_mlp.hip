@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "rover_internal.h"
+#include "rover_act.h"
 #include "rover_bf16.h"
 #include "rover_philox.h"
 
@@ -24,16 +25,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define MLP_BK 32
 #define MLP_PITCH 33
 #define MLP_MAX_NT 8          // N <= 256
-
-__device__ __forceinline__ float mlp_act(float v, int act) {
-    switch (act) {
-        case 1: return v > 0.0f ? v : 0.01f * v;                    // nn.LeakyReLU() default slope (model.py:112)
-        case 2: return tanhf(v);                                    // nn.Tanh (model.py:115,182)
-        case 3: return v > 0.0f ? v : 0.0f;                         // nn.ReLU
-        case 4: return v > 0.0f ? v : expm1f(v);                    // nn.ELU (alpha 1)
-        default: return v;
-    }
-}
 
 // NW waves per workgroup, 32 rows each: 4 for large batches, 1 when M / 128 workgroups would leave most of the 256 CUs idle
 template <int NT, int NW>
@@ -160,8 +151,7 @@ hipError_t launch_linear_act(const LinearArgs& a, hipStream_t s) {
 // layer's B operand (k-index g <-> lane group g) register r pairs with weight column 16 t + 4 g + r, i.e. element r of the 16-byte
 // read at column 4 g of the [n_out][16] weight slab of input tile t.
 // ---------------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));       // a float4 at any float address (global_load_dwordx4)
+// (f32x4, and f32x4u — a float4 at any float address — are rover_bf16.h's)
 #define C16_XP 36
 #define C16_WP 20
 
@@ -541,11 +531,7 @@ __global__ void __launch_bounds__(512, 4) chain16_head_kernel(ChainArgs a, Gauss
 // The rounded activations of a whole layer are 2 VGPRs per 16 features: the 4-layer chain needs no split of its first layer.
 // Rows of 32 bf16 at a pitch of 40 (20 words, C16_WP's): the 16-byte reads of 8 lanes fall on 8 different bank groups.
 // ---------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#define B16_P 40
-
-__device__ __forceinline__ bf16x4 b16_round4(const f32x4& v) { return bf16x4{bf16_rne(v[0]), bf16_rne(v[1]), bf16_rne(v[2]), bf16_rne(v[3])}; }
+// (bf16x4 / bf16x8, the pitch B16_P, b16_round4 and b16_load4 are rover_bf16.h's: rover_bf16_tile.hip stages its slabs the same way)
 
 // a layer's activated f32 tiles -> the next layer's B fragments, rounded (features past the layer's width are zero already)
 template <int T>
@@ -595,19 +581,6 @@ __device__ __forceinline__ void b16_hidden_pack(const f32x4 (&acc)[T], const flo
 #pragma unroll
         for (int r = 0; r < 4; ++r) out[t / 2][4 * (t & 1) + r] = bf16_rne(v[r]);
     }
-}
-
-// elements k .. k + 3 of a row of `len` floats, zero past its end or when the row does not exist
-__device__ __forceinline__ f32x4 b16_load4(const float* __restrict__ p, uint32_t k, uint32_t len, bool row_ok) {
-    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (row_ok) {
-        if (k + 4u <= len) v = *reinterpret_cast<const f32x4u*>(p + k);
-        else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) if (k + e < len) v[e] = p[k + e];
-        }
-    }
-    return v;
 }
 
 // layer 1 for the TN output tiles that start at weight row n_off: both operands from LDS slabs of 32 k.  512 threads stage 128 x rows and TN * 16 weight rows, 4 floats

@@ -20,6 +20,17 @@ The hidden state lives in ``self.h [n_layers, E, H]`` at a fixed address.  A cel
 needs whole rows of h), so ``act()`` writes the new state into a scratch tensor and copies it back on the device: the
 same launches every call, capturable once after a warm-up.
 
+``precision="bf16"`` (opt-in, inference only): every matrix product of ``act()`` / ``forward()`` on bf16 operands
+with f32 accumulation — the encoders and the MLP on the bf16 chain kernels, the cells on ``rover_gru_cell_bf16``, the ``gb`` / ``ga``
+branches, the decoder and its gate layer by layer on ``rover_linear_forward_bf16`` (each layer's f32 output is rounded by whoever reads
+it: a chain's arithmetic).  ``rover_gated_sum``, the proprioceptive copy and ``self.h`` stay f32: the cell's blend ``z * h`` takes the
+unrounded state, since a state rounded to 8 bits every step would drop every update below 2^-9 |h|.  A student never mixes precisions
+(a chain or layer that fits no bf16 kernel is a ValueError naming it); training is f32 whatever the policy's precision.  Measured on
+the MI355X at native width (obs 1 750, H = 300; EXPERIMENTS.md §20; µs per captured ``act()``, median, f32 against bf16): 406 / 321 at
+512 envs, 660 / 321 at 4 096, 823 / 459 at 16 384, 2 501 / 1 066 at 65 536 — bf16 is faster at every size measured, there is no
+crossover in that range (at 512 envs its ``Layer`` and encoder launches are slower than the f32 ones and the cells pay for them), and
+its actions are within 2e-4 of the f32 ones.  The default stays f32: a policy's arithmetic is the user's choice.
+
 Training: ``forward_train()`` is ``forward()`` run so that a backward can follow — time-major inside, every layer
 unfused so that its output exists, the GRU cells through ``rover_gru_cell_train`` (which also stores the gates), everything that is
 not recurrent ONCE over all T·B rows — and ``backward()`` is back-propagation through time written out on ``rover_gru_cell_backward``,
@@ -115,7 +126,10 @@ def param_shapes(info, cfg=DEFAULT_CFG):
 class StudentPolicy:
     """``Student`` + ``student_loader``: plain tensors under the reference's parameter names, ``act()`` per env step, ``forward()`` per sequence."""
 
-    def __init__(self, engine, info_or_task, cfg=DEFAULT_CFG, device="cuda:0", seed=0):
+    def __init__(self, engine, info_or_task, cfg=DEFAULT_CFG, device="cuda:0", seed=0, precision="f32"):
+        """``precision``: "f32" (default) or "bf16" — what act() / forward() run when their own ``precision`` argument is None (module
+        docstring).  The parameters, ``self.h`` and training are f32 either way."""
+        self.precision = self._precision_of(precision)
         self.info, self.cfg = _info_of(info_or_task), _cfg_of(cfg)
         self.engine, self.device = engine, device
         g = torch.Generator().manual_seed(seed)
@@ -184,42 +198,66 @@ class StudentPolicy:
         return self.h
 
     # ---- the forward ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _precision_of(precision):
+        if precision not in ("f32", "bf16"):
+            raise ValueError(f"StudentPolicy: precision must be 'f32' or 'bf16', not {precision!r}")
+        return precision
+
+    @staticmethod
+    def _kw(precision):
+        """The engine calls' precision argument: named only where it is not their default."""
+        return {} if precision == "f32" else {"precision": precision}
+
     def _buf(self, key, rows, cols):
         b = self._bufs.get(key)
         if b is None or b.shape != (rows, cols):
             b = self._bufs[key] = torch.empty(rows, cols, device=self.device)
         return b
 
-    def _linear(self, x, layer, out):
-        """One Layer; a layer wider than one linear_forward takes (the decoder's) runs as column blocks of the width the library accepts."""
+    def _linear(self, x, layer, out, precision="f32", name="layer"):
+        """One Layer; a layer wider than one linear_forward takes (the decoder's) runs as column blocks of the width the library accepts
+        (asked per precision).  bf16: a layer of which not even one column fits is a ValueError naming it — never an f32 layer instead."""
         m, k, n = x.shape[0], x.shape[1], layer.weight.shape[0]
-        c = self._chunks.get((m, k, n))
+        kw = self._kw(precision)
+        ck = (m, k, n) if precision == "f32" else (m, k, n, precision)
+        c = self._chunks.get(ck)
         if c is None:
             c = n
-            while c > 1 and self.engine.linear_route(m, k, c) is None:
+            while c > 1 and self.engine.linear_route(m, k, c, **kw) is None:
                 c = (c + 1) // 2
-            self._chunks[(m, k, n)] = c
+            if precision != "f32" and self.engine.linear_route(m, k, c, **kw) is None:
+                raise ValueError(f"StudentPolicy: precision='{precision}': {name} [{m}, {k}] -> {n} fits no {precision} layer kernel")
+            self._chunks[ck] = c
         for lo in range(0, n, c):
             hi = min(n, lo + c)
-            self.engine.linear_forward(x, layer.weight[lo:hi], layer.bias[lo:hi], layer.activation, out[:, lo:hi])
+            self.engine.linear_forward(x, layer.weight[lo:hi], layer.bias[lo:hi], layer.activation, out[:, lo:hi], **kw)
         return out
 
-    def _run(self, key, x, layers, out):
-        """``layers`` over x into ``out``: one chain kernel where the library names one for these widths, else layer by layer."""
-        m, eng = x.shape[0], self.engine
-        fused = self._plans.get((key, m))
+    def _run(self, key, x, layers, out, precision="f32"):
+        """``layers`` over x into ``out``: one chain kernel where the library names one for these widths (and this precision), else layer
+        by layer.  Either way every product of a bf16 run is a bf16 kernel's: a layer's f32 output is rounded by whoever reads it."""
+        m, eng, kw = x.shape[0], self.engine, self._kw(precision)
+        pk = (key, m) if precision == "f32" else (key, m, precision)
+        fused = self._plans.get(pk)
         if fused is None:
-            fused = self._plans[(key, m)] = eng.chain_route(m, *eng.chain_shape(layers)) is not None
+            fused = self._plans[pk] = eng.chain_route(m, *eng.chain_shape(layers), **kw) is not None
         if fused:
-            return eng.chain_forward(x, layers, out)
+            return eng.chain_forward(x, layers, out, **kw)
         for i, layer in enumerate(layers):
             last = i == len(layers) - 1
-            x = self._linear(x, layer, out if last else self._buf((key, i), m, layer.weight.shape[0]))
+            x = self._linear(x, layer, out if last else self._buf((key, i), m, layer.weight.shape[0]), precision, f"{key}[{i}]")
         return out
 
-    def _step(self, obs, h_in, h_out, reset, actions, estimated):
-        """One time step: obs [E, F] (rows at any stride), h_in / h_out lists of [E, H] per layer -> actions [E, A] (and estimated)."""
+    def _step(self, obs, h_in, h_out, reset, actions, estimated, precision="f32"):
+        """One time step: obs [E, F] (rows at any stride), h_in / h_out lists of [E, H] per layer -> actions [E, A] (and estimated).
+        ``precision="bf16"``: every matrix product in bf16 (chains, cells, layers); the copies, the gated sums and h stay f32."""
         eng, e, f = self.engine, obs.shape[0], obs.shape[1]
+        if precision != "f32" and (("cell", e, precision) not in self._plans):          # a student never mixes precisions
+            if eng.gru_cell_route(e, 0, self.hidden_dim, precision=precision) is None:
+                raise ValueError(f"StudentPolicy: precision='{precision}': the GRU cell [{e}, {self.hidden_dim}] fits no {precision} cell kernel")
+            self._plans[("cell", e, precision)] = True
+        run = lambda key, x, layers, out: self._run(key, x, layers, out, precision)
         p, ns, nd = self.info["proprioceptive"], self.info["sparse"], self.info["dense"]
         if f < p + ns + nd:
             raise ValueError(f"StudentPolicy: obs has {f} columns, needs proprioceptive + sparse + dense = {p + ns + nd}")
@@ -228,46 +266,50 @@ class StudentPolicy:
         mlp_in = self._buf("mlp_in", e, p + 2 * ef)                  # [p | belief] (:159)
         cat[:, :p] = obs[:, :p]
         mlp_in[:, :p] = obs[:, :p]
-        self._run("enc1", obs[:, f - ns - nd:f - nd], self.encoder1, cat[:, p:p + ef])
-        self._run("enc2", obs[:, f - nd:], self.encoder2, cat[:, p + ef:p + 2 * ef])
+        run("enc1", obs[:, f - ns - nd:f - nd], self.encoder1, cat[:, p:p + ef])
+        run("enc2", obs[:, f - nd:], self.encoder2, cat[:, p + ef:p + 2 * ef])
         x = cat
         for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(self.gru):
-            x = eng.gru_cell(x, h_in[l], w_ih, w_hh, b_ih, b_hh, h_out[l], reset_mask=reset)
+            x = eng.gru_cell(x, h_in[l], w_ih, w_hh, b_ih, b_hh, h_out[l], reset_mask=reset, **self._kw(precision))
         top = x
-        x_b = self._run("gb", top, self.gb, self._buf("x_b", e, 2 * ef))
-        x_a = self._run("ga", top, self.ga, self._buf("x_a", e, 2 * ef))
+        x_b = run("gb", top, self.gb, self._buf("x_b", e, 2 * ef))
+        x_a = run("ga", top, self.ga, self._buf("x_a", e, 2 * ef))
         eng.gated_sum(x_b, cat[:, p:], x_a, mlp_in[:, p:])           # belief = x_b + l_e * sigmoid(x_a) (:79-85)
-        self._run("mlp", mlp_in, self.network, actions)
+        run("mlp", mlp_in, self.network, actions)
         if estimated is not None:
             last, ex = top[e - 1:e], ns + nd                         # the decoder reads the LAST batch row's output (module docstring)
-            gate = self._run("gate", last, self.gate_encoder, self._buf("gate", 1, ex))
-            dec = self._run("dec", last, self.decoder, self._buf("decoded", 1, ex))
+            gate = run("gate", last, self.gate_encoder, self._buf("gate", 1, ex))
+            dec = run("dec", last, self.decoder, self._buf("decoded", 1, ex))
             eng.gated_sum(dec.expand(e, ex), obs[:, f - ex:], gate.expand(e, ex), estimated)
         return actions
 
-    def act(self, obs, reset=None, reconstruct=False):
+    def act(self, obs, reset=None, reconstruct=False, precision=None):
         """student_loader.act (:21-24): obs [E, F] -> actions [E, A], the Tanh mean (no sampling); advances ``self.h`` in place (same
         address after every call).  ``reset``: optional [E] bool / uint8 device tensor (e.g. the step's done): marked rows start from a
         zero hidden state — an addition, the reference never resets.  ``reconstruct=True``: -> (actions, estimated [E, sparse + dense]).
-        Both are buffers of this object, overwritten by the next call of the same E.  Capturable in a graph after one warm-up call."""
+        Both are buffers of this object, overwritten by the next call of the same E.  Capturable in a graph after one warm-up call.
+        ``precision`` (default: the policy's): "bf16" runs every matrix product of the step in bf16; ``self.h`` stays f32."""
+        precision = self.precision if precision is None else self._precision_of(precision)
         e = obs.shape[0]
         if self.h is None or self.h.shape[1] != e:
             self.init_hidden(e)
         actions = self._buf("actions", e, self.info["actions"])
         est = self._buf("estimated", e, self.info["sparse"] + self.info["dense"]) if reconstruct else None
-        self._step(obs, list(self.h), list(self._h_new), reset, actions, est)
+        self._step(obs, list(self.h), list(self._h_new), reset, actions, est, precision)
         self.h.copy_(self._h_new)
         return (actions, est) if reconstruct else actions
 
-    def forward(self, x, h):
+    def forward(self, x, h, precision=None):
         """Student.forward (:199-248): x [B, T, F] (batch first), h [n_layers, B, H] -> (actions [B, T, A], estimated [B, T, S + D],
-        h [n_layers, B, H]) as a loop of T cell steps; time step t is the row view x[:, t] (row stride T F): no transpose copy."""
+        h [n_layers, B, H]) as a loop of T cell steps; time step t is the row view x[:, t] (row stride T F): no transpose copy.
+        ``precision`` as in act()."""
+        precision = self.precision if precision is None else self._precision_of(precision)
         b, t_len = x.shape[0], x.shape[1]
         actions = torch.empty(b, t_len, self.info["actions"], device=self.device)
         est = torch.empty(b, t_len, self.info["sparse"] + self.info["dense"], device=self.device)
         cur, nxt = h.to(torch.float32).clone(), torch.empty(self.n_layers, b, self.hidden_dim, device=self.device)
         for t in range(t_len):
-            self._step(x[:, t], list(cur), list(nxt), None, actions[:, t], est[:, t])
+            self._step(x[:, t], list(cur), list(nxt), None, actions[:, t], est[:, t], precision)
             cur, nxt = nxt, cur
         return actions, est, cur
 
