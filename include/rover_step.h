@@ -791,6 +791,11 @@ ROVER_API int rover_gated_sum_backward(rover_ctx *ctx, const float *d_out, int64
  *        calls build.  0 = two bounding spheres per pair of triangles; 1 = one axis-aligned box per pair, tested on the three axes d x e_i;
  *        -1 (default) = auto: boxes for a map in which at least three quarters of the pairs fill their box (a regular grid mesh), spheres
  *        for any other (a decimated mesh).  One form per map; results do not depend on it (rover_info.lane_box reports it).
+ * name = "lane_pair_rows" (variant 4, both arithmetics): the rows of the staged tables the NEXT rover_set_knn_map calls build.  0 = one row
+ *        per cell; 1 = one row per two cells (ix, 2j), (ix, 2j + 1), holding the union of their triangles about the midpoint of their
+ *        centres — where every union fits a row of 128 pairs, else the map keeps one row per cell; -1 (default) = auto: the terrain map
+ *        only (nearly all of its cells hold rays, and two neighbours' rays share a wave: a row is read once for both; a rock ray streams its
+ *        row alone).  Results do not depend on it (rover_info.lane_pair_rows reports it).
  * name = "ray_precision": 0 (default) = the reference's fp32 mode, which the parity tests pin.
  *        1 = every ray origin / direction rounded to fp16 before the cell lookup and the ray maths, like the reference AS
  *        SHIPPED (Camera.dtype = float16: camera.py:55,212; rock_detect.py:319,371); f32 arithmetic after that.
@@ -824,7 +829,7 @@ ROVER_API int rover_gated_sum_backward(rover_ctx *ctx, const float *d_out, int64
  *        24 / 48 (irregular mesh, or ray_precision 2); variant 4 behind the sort 32, 64 from r = 12; in env order 16, 32 from 2^17
  *        padded ray slots, 64 from 2^20.  Results do not depend on it.
  * Every name above but "ray_precision" and "cell_index_mode" that has a ROVER_<NAME> environment variable (ROVER_RAYCAST_VARIANT,
- * ROVER_RAYCAST_RUN, ROVER_LANE_ENV_ORDER, ROVER_LANE_ROCKS, ROVER_LANE_BOX, ROVER_BIN_LOW_BITS, ROVER_CULL_QUEUE_MB) takes its start value from it at
+ * ROVER_RAYCAST_RUN, ROVER_LANE_ENV_ORDER, ROVER_LANE_ROCKS, ROVER_LANE_BOX, ROVER_LANE_PAIR_ROWS, ROVER_BIN_LOW_BITS, ROVER_CULL_QUEUE_MB) takes its start value from it at
  * rover_create; a value outside the option's range (and 0 = auto) is ignored there. */
 ROVER_API int rover_set_option(rover_ctx *ctx, const char *name, int64_t value);
 
@@ -840,6 +845,7 @@ typedef struct {
     int32_t raycast_sorted;        /* 1: the step sorts the rays by (map, cell) bin; 0: the ray cast walks the slots in env order */
     int32_t raycast_rocks_staged;  /* variant 4: 1 = the rocks part of the sorted list runs on the staged kernel too, 0 = on the culled one */
     int32_t lane_box[2];           /* per map: 1 = the staged tables of the fp32 arithmetic hold one box per pair of triangles, 0 = two spheres ("lane_box") */
+    int32_t lane_pair_rows[2];     /* per map: 1 = the staged tables hold one row per two cells that neighbour in iy, 0 = one per cell ("lane_pair_rows") */
 } rover_info;
 ROVER_API int rover_get_info(const rover_ctx *ctx, rover_info *info);
 /* The whole ray-cast plan in force (what the next step's ray cast will run) and the other host-side values that select a code path of

@@ -57,7 +57,7 @@ class Info(C.Structure):
                 ("K", C.c_int32 * 2), ("K8", C.c_int32 * 2), ("X", C.c_int32 * 2), ("Y", C.c_int32 * 2),
                 ("table_bytes", C.c_uint64 * 2), ("workspace_bytes", C.c_uint64), ("raycast_variant", C.c_int32),
                 ("cell_index_mode", C.c_int32), ("ray_precision", C.c_int32), ("raycast_sorted", C.c_int32),
-                ("raycast_rocks_staged", C.c_int32), ("lane_box", C.c_int32 * 2)]
+                ("raycast_rocks_staged", C.c_int32), ("lane_box", C.c_int32 * 2), ("lane_pair_rows", C.c_int32 * 2)]
 
 
 class CullInfo(C.Structure):

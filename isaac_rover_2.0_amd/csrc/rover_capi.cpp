@@ -69,6 +69,7 @@ struct MapTables {
     ProofTables proof[2];
     uint32_t lane_pp = 0;               // pairs per row of the staged kernel's records
     bool lane_box = false;              // the f32 proof's staged records are boxes (one per pair), not two spheres
+    bool lane_pair_rows = false;        // the staged tables (both proofs) hold one row per two cells that neighbour in iy (lane_pp pairs: their union)
     int64_t tris = 0, farok = 0, cells = 0;   // triangles; cells whose far bound can hold for a usual ray (far_build_kernel); cells
     uint64_t bytes() const {
         uint64_t b = table.bytes() + cull_idx.bytes() + rtab.bytes();
@@ -407,7 +408,7 @@ static void cull_numbering(const std::vector<float2>& cen, std::vector<uint32_t>
 
 // rover_set_knn_map's work, into `m` alone: the re-packed map, then — where the culled ray cast can serve the map (64 lanes x 4 triangles;
 // triangle ids and the map bit share 32 bits of a queue entry) — its tables, then the staged kernel's.  The build's own buffers go on return.
-static int build_map_tables(rover_ctx* c, MapTables& m, const int32_t* map_idx, int32_t X, int32_t Y, int32_t K, const int32_t* tris,
+static int build_map_tables(rover_ctx* c, MapTables& m, int which, const int32_t* map_idx, int32_t X, int32_t Y, int32_t K, const int32_t* tris,
                             int32_t T, const uint16_t* verts, int32_t V, float cell, float shift_x, float shift_y) {
     const uint64_t n_cells = (uint64_t)X * Y;
     const uint32_t K8 = (uint32_t)((K + 7) / 8 * 8);
@@ -481,8 +482,37 @@ static int build_map_tables(rover_ctx* c, MapTables& m, const int32_t* map_idx, 
     m.proof[0].always = h_cnt[0]; m.proof[0].nocone = h_cnt[1];
     m.proof[1].always = h_cnt[2]; m.proof[1].nocone = h_cnt[3];
     m.farok = h_cnt[4];
+    const bool box = a.lane.lrec && (c->knobs.lane_box > 0 || (c->knobs.lane_box < 0 && lane_box_share_met(h_cnt[5], h_cnt[6])));
+    // One row per two cells (option "lane_pair_rows": auto = the terrain map, whose cells nearly all hold rays, so that a row is read once for
+    // the rays of both): taken where every row's union fits a row — else the map keeps the per-cell tables built above.  The tables are
+    // allocated again for the form (rows of the largest union: about 0.6 of the per-cell size); as before, a proof whose tables do not fit goes without.
+    if ((a.lane.lrec || a.lane_h.lrec) && n_cells < (1ull << 24) && (uint32_t)T < (1u << 30) &&
+        (c->knobs.lane_pair_rows > 0 || (c->knobs.lane_pair_rows < 0 && which == ROVER_MAP_TERRAIN))) {
+        const uint64_t n_rows = lane_pair_rows_count(n_cells, (uint32_t)Y);
+        DevBuf<uint2> d_upair;
+        if (d_upair.alloc(n_rows * 128ull) == hipSuccess) {
+            if ((e = launch_lane_union(a, d_upair.get(), nullptr)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess ||
+                (e = hipMemcpy(h_cnt + 7, d_cnt.get() + 7, sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess)
+                return fail(c, ROVER_E_HIP, "set_knn_map: staged tables, the rows' unions: %s", hipGetErrorString(e));
+            const uint32_t pp = lane_pair_rows_pp(h_cnt[7]);
+            if (pp) {
+                for (int k = 0; k < 2; ++k) {
+                    ProofTables& p = m.proof[k];
+                    if (!p.lrec.get()) continue;
+                    p.lvl.reset(); p.lrec.reset(); p.lid.reset();
+                    if (p.lvl.alloc(n_rows * lane_lvl_stride()) != hipSuccess || p.lrec.alloc(n_rows * 2ull * pp) != hipSuccess ||
+                        p.lid.alloc(n_rows * pp) != hipSuccess) { p.lvl.reset(); p.lrec.reset(); p.lid.reset(); }
+                }
+                a.lane = m.proof[0].view(); a.lane_h = m.proof[1].view();
+                if ((e = launch_lane_pair_rows(a, d_upair.get(), pp, box ? 1 : 0, nullptr)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess)
+                    return fail(c, ROVER_E_HIP, "set_knn_map: staged tables in shared-row form: %s", hipGetErrorString(e));
+                m.lane_pp = pp; m.lane_pair_rows = true; m.lane_box = box && a.lane.lrec;
+                return ROVER_OK;
+            }
+        }
+    }
     // the form of test (A)'s records in the f32 proof's staged tables (option "lane_box"): boxes where most pairs fill theirs
-    if (a.lane.lrec && (c->knobs.lane_box > 0 || (c->knobs.lane_box < 0 && lane_box_share_met(h_cnt[5], h_cnt[6])))) {
+    if (box) {
         if ((e = launch_lane_box(a, nullptr)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess)
             return fail(c, ROVER_E_HIP, "set_knn_map: staged tables in box form: %s", hipGetErrorString(e));
         m.lane_box = true;
@@ -519,6 +549,8 @@ static const KnobRow kKnobs[] = {
      "-1 (auto), 0 or 1"},
     {"lane_rocks", "ROVER_LANE_ROCKS", -1, 1, kIntMin, kIntMax, KNOB_ENV_AS_BOOL, KNOB_SET(knobs.lane_rocks, (int)v), KNOB_REPLAN, "-1 (auto), 0 or 1"},
     {"lane_box", "ROVER_LANE_BOX", -1, 1, kIntMin, kIntMax, KNOB_ENV_AS_BOOL, KNOB_SET(knobs.lane_box, (int)v), 0,      // takes effect at the next rover_set_knn_map
+     "-1 (auto), 0 or 1"},
+    {"lane_pair_rows", "ROVER_LANE_PAIR_ROWS", -1, 1, kIntMin, kIntMax, KNOB_ENV_AS_BOOL, KNOB_SET(knobs.lane_pair_rows, (int)v), 0,      // (the same)
      "-1 (auto), 0 or 1"},
     {nullptr, "ROVER_CULL_LAZY", 1, 0, kIntMin, kIntMax, 0, KNOB_SET(knobs.cull_lazy, (int)v), KNOB_REPLAN, nullptr},
     {"bin_low_bits", "ROVER_BIN_LOW_BITS", 8, 12, 8, 12, KNOB_OPT_ALSO_ZERO, KNOB_SET(knobs.low_bits_opt, (uint32_t)v), KNOB_REPLAN | KNOB_BINS,
@@ -614,7 +646,7 @@ int rover_set_knn_map(rover_ctx* c, int which, const int32_t* map_idx, int32_t X
     if ((uint64_t)X * (uint64_t)Y > 0xffffffffull) return fail(c, ROVER_E_INVALID, "set_knn_map: X*Y exceeds 2^32 cells");
     USE_DEVICE(c);
     MapTables m;
-    if (int r = build_map_tables(c, m, map_idx, X, Y, K, tris, T, verts, V, cell, shift_x, shift_y)) return r;      // (the previous map stays)
+    if (int r = build_map_tables(c, m, which, map_idx, X, Y, K, tris, T, verts, V, cell, shift_x, shift_y)) return r;      // (the previous map stays)
     c->maps[which] = std::move(m);
     c->rays_valid = false;
     return replan(c, REALLOC_BINS);
@@ -805,6 +837,7 @@ static int run_raycast(rover_ctx* c, const StepPlan& p, uint32_t n_valid, hipStr
             const CullProofH ph = cull_proof_h(c->knobs.cull_eta_h, c->knobs.cull_split_h);
             l.half = p.proof; l.c_a_h = ph.c_a; l.k2_far = cull_far_k2(l.half, ph);
             l.forms = p.proof ? 0u : (c->maps[0].lane_box ? 1u : 0u) | (c->maps[1].lane_box ? 2u : 0u);
+            for (int w = 0; w < 2; ++w) { l.forms |= c->maps[w].lane_pair_rows ? 4u << w : 0u; l.y[w] = (uint32_t)c->maps[w].knn.Y; }
         }
         l.run = p.run; l.out = c->d_dist_out.get(); l.stats = q.stats.get();
         if (p.env_order) {      // every slot (padding included), in env order, one launch
@@ -1247,7 +1280,7 @@ int rover_get_info(const rover_ctx* c, rover_info* info) {
     info->cell_index_mode = c->cell_rcp; info->ray_precision = c->precision;
     info->raycast_sorted = c->plan.sorted ? 1 : 0;
     info->raycast_rocks_staged = c->plan.rocks_staged ? 1 : 0;
-    for (int w = 0; w < 2; ++w) info->lane_box[w] = c->maps[w].lane_box ? 1 : 0;
+    for (int w = 0; w < 2; ++w) { info->lane_box[w] = c->maps[w].lane_box ? 1 : 0; info->lane_pair_rows[w] = c->maps[w].lane_pair_rows ? 1 : 0; }
     return ROVER_OK;
 }
 

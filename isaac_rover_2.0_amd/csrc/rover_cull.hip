@@ -960,6 +960,10 @@ __global__ void __launch_bounds__(64 * CULL_WPB) cull_scan_kernel(CULL_SCAN_ARGS
 // triangles, {M' = fp16(M - C), half extents e (fp16, rounded up), mrg}, and the pair is cleared iff on one of the axes d x e_i the line misses the
 // box grown by the margin — any lower bound on the distance between the line and the padded triangle serves the proof.  Levels,
 // row order, test (B) and everything behind the candidate mask are those of the sphere form.
+// Shared-row form (either proof, chosen per map when the map is set: launch_lane_pair_rows): one row — records, levels, ids — for the
+// two cells (ix, 2j), (ix, 2j + 1), built from the union of their triangles about the midpoint of their centres; the tests run as they are (a bound
+// over a superset bounds each cell's subset, the origin's offset o comes from the row's header), and the exact phase drops a triangle whose id
+// word says that the ray's own cell does not list it.
 // ---------------------------------------------------------------------------------------------------
 #define LN_CH 8u                     // pairs per chunk: one 128-byte line of a cell's record row, one 8-bit candidate mask (with 16 pairs per chunk a
                                      // terrain ray of configs[2] tested 2.4 chunks = 38 pairs on average, with 8 it tests 4.3 chunks = 34)
@@ -1004,24 +1008,109 @@ __device__ __forceinline__ uint16_t half_bits_up(float v) {      // fp16 >= v (v
     return b;
 }
 
+// Shared-row form of the staged tables: row (ix, j) serves the cells (ix, 2j) and (ix, 2j + 1) — neighbours in the sort
+// key, so their rays share waves — and holds the union of their triangles, paired again as idx4_build_kernel pairs a cell's (partners
+// 2p, 2p + 1 that are both in the union share a pair, the rest pair up in id order).  One workgroup of 512 threads per row: upair[row][128]
+// = the union's pairs as two id words, bits 30 / 31 of a word = the even / odd cell of the row lists that triangle (0 = no triangle); the
+// largest union of the map, in pairs, goes to *max_pairs (a union of more than 128 pairs is cut: the caller then refuses the form).
+#define LN_IDMASK 0x3fffffffu
+__global__ void __launch_bounds__(512) lane_union_kernel(const int32_t* __restrict__ idx4, uint32_t K8, uint32_t Y, uint32_t Yh,
+                                                         uint2* __restrict__ upair, uint32_t* __restrict__ max_pairs) {
+    __shared__ uint32_t key[512], scan[2][512], uid[512];
+    __shared__ uint32_t row[256];
+    const uint32_t r = blockIdx.x, tid = threadIdx.x, ix = r / Yh, iy = 2u * (r % Yh);
+    const uint32_t side = tid >> 8, k = tid & 255u;
+    uint32_t kv = 0xffffffffu;
+    if (k < K8 && iy + side < Y) {
+        const int32_t t = idx4[((uint64_t)ix * Y + iy + side) * K8 + k];
+        if (t >= 0) kv = ((uint32_t)t << 1) | side;
+    }
+    key[tid] = kv;
+    __syncthreads();
+    for (uint32_t len = 2; len <= 512u; len <<= 1) {
+        for (uint32_t stride = len >> 1; stride > 0; stride >>= 1) {
+            if (tid < 256u) {
+                const uint32_t lo = ((tid / stride) * stride << 1) + (tid % stride), hi = lo + stride;
+                const bool up = (lo & len) == 0;
+                const uint32_t a = key[lo], b = key[hi];
+                if ((a > b) == up) { key[lo] = b; key[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    auto excl_scan = [&](uint32_t* a, uint32_t v) -> uint32_t {     // exclusive prefix sum over the 512 threads; a[511] + own value of the last = the total
+        a[tid] = v;
+        __syncthreads();
+        for (uint32_t off = 1; off < 512u; off <<= 1) {
+            const uint32_t add = tid >= off ? a[tid - off] : 0u;
+            __syncthreads();
+            a[tid] += add;
+            __syncthreads();
+        }
+        return a[tid] - v;
+    };
+    // the distinct triangles, in id order, with their membership bits
+    const uint32_t me = key[tid], t_me = me >> 1;
+    const bool present = me != 0xffffffffu;
+    const bool uniq = present && (tid == 0u || (key[tid - 1u] >> 1) != t_me);
+    const uint32_t upos = excl_scan(scan[0], uniq ? 1u : 0u);
+    const uint32_t n_u = scan[0][511];
+    uid[tid] = 0xffffffffu;
+    __syncthreads();
+    if (uniq) {
+        uint32_t mem = 1u << (me & 1u);
+        if (tid + 1u < 512u && key[tid + 1u] != 0xffffffffu && (key[tid + 1u] >> 1) == t_me) mem |= 1u << (key[tid + 1u] & 1u);
+        uid[upos] = t_me | (mem << 30);
+    }
+    __syncthreads();
+    // pairing, as idx4_build_kernel's
+    const uint32_t w = uid[tid], id = w & LN_IDMASK;
+    const bool here = tid < n_u;
+    const bool first = here && !(id & 1u) && tid + 1u < n_u && (uid[tid + 1u] & LN_IDMASK) == (id | 1u);
+    const bool second = here && (id & 1u) && tid > 0u && (uid[tid - 1u] & LN_IDMASK) == (id ^ 1u);
+    const bool single = here && !first && !second;
+    const uint32_t pf = excl_scan(scan[0], first ? 1u : 0u), ps = excl_scan(scan[1], single ? 1u : 0u);
+    const uint32_t n_first = scan[0][511], n_single = scan[1][511];
+    const uint32_t m = first ? pf : (second ? pf - 1u : n_first + (ps >> 1)), e = first ? 0u : (second ? 1u : (ps & 1u));
+    if (tid < 256u) row[tid] = 0u;
+    __syncthreads();
+    if (here && m < 128u) row[2u * m + e] = w;
+    __syncthreads();
+    if (tid < 128u) upair[(uint64_t)r * 128u + tid] = make_uint2(row[2u * tid], row[2u * tid + 1u]);
+    if (tid == 0u) atomicMax(max_pairs, n_first + ((n_single + 1u) >> 1));
+}
+
 // one workgroup of 128 threads per cell, thread = source pair (idx4's (lane, slot)); see the header comment for the record
+// (upair: the map in shared-row form — one workgroup per row, thread = pair of the row's union, the centre between the two cells' centres)
 __global__ void __launch_bounds__(128) lane_build_kernel(const int4* __restrict__ idx4, const uint4* __restrict__ ctab, uint32_t K8, uint32_t pp,
                                                          uint32_t Y, float cell_size, float shift_x, float shift_y, float k1, float tau2,
                                                          double c_rho, const uint32_t* __restrict__ qrow, const float* __restrict__ nz_abs,
                                                          float4* __restrict__ lvl, uint4* __restrict__ lrec, uint2* __restrict__ lid, int half,
                                                          float q_good, const uint16_t* __restrict__ rtab, int box /* f32 proof: the table in box form */,
-                                                         uint32_t* __restrict__ fill /* {non-empty pairs, well-filled pairs} of the map, or null */) {
+                                                         uint32_t* __restrict__ fill /* {non-empty pairs, well-filled pairs} of the map, or null */,
+                                                         const uint2* __restrict__ upair /* shared-row form: lane_union_kernel's rows, else null */) {
     __shared__ float s_z0[128], s_z1[128], s_g[128], s_ro[128], s_qn[128];
     __shared__ uint4 s_nrec[128];
     __shared__ uint32_t s_key[128];
     __shared__ uint8_t s_src[128];
     __shared__ uint4 s_rec[128];
     __shared__ uint2 s_id[128];
-    const uint32_t cell = blockIdx.x, p = threadIdx.x, L = K8 >> 2, n_src = K8 >> 1;
-    const float ccx = (float)(cell / Y) * cell_size + shift_x, ccy = (float)(cell % Y) * cell_size + shift_y;
+    // (`cell` is the row of the tables: a cell, or in shared-row form the row of two cells)
+    const uint32_t cell = blockIdx.x, p = threadIdx.x, L = K8 >> 2, n_src = upair ? 128u : K8 >> 1, Yh = (Y + 1u) >> 1;
+    const uint32_t c_ix = upair ? cell / Yh : cell / Y, c_iy = upair ? 2u * (cell % Yh) : cell % Y;
+    const bool two = upair && c_iy + 1u < Y;                                   // (Y odd: a column's last row serves one cell, about that cell's centre)
+    const float ccx = (float)c_ix * cell_size + shift_x, ccy = two ? ((float)c_iy + 0.5f) * cell_size + shift_y : (float)c_iy * cell_size + shift_y;
     int32_t id[2] = {-1, -1};
+    uint32_t mem[2] = {0u, 0u};
     uint4 rec[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-    if (p < n_src) {
+    if (upair) {
+        const uint2 u = upair[(uint64_t)cell * 128u + p];
+        mem[0] = u.x >> 30; mem[1] = u.y >> 30;
+        if (mem[0]) id[0] = (int32_t)(u.x & LN_IDMASK);
+        if (mem[1]) id[1] = (int32_t)(u.y & LN_IDMASK);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) if (id[e] >= 0) rec[e] = ctab[id[e]];
+    } else if (p < n_src) {
         const int4 r4 = idx4[(uint64_t)cell * L + (p % L)];
         const uint32_t slot = p / L;
         id[0] = slot ? r4.z : r4.x; id[1] = slot ? r4.w : r4.y;
@@ -1179,7 +1268,7 @@ __global__ void __launch_bounds__(128) lane_build_kernel(const int4* __restrict_
     s_nrec[p] = half ? make_uint4((uint32_t)nb[0][0] | ((uint32_t)nb[0][1] << 16), (uint32_t)nb[0][2] | ((uint32_t)nb[0][3] << 16),
                                   (uint32_t)nb[1][0] | ((uint32_t)nb[1][1] << 16), (uint32_t)nb[1][2] | ((uint32_t)nb[1][3] << 16))
                      : make_uint4(b4[0], b4[1], 0u, 0u);
-    s_id[p] = make_uint2(id[0] >= 0 ? (uint32_t)id[0] : CULL_NOID, id[1] >= 0 ? (uint32_t)id[1] : CULL_NOID);
+    s_id[p] = make_uint2((id[0] >= 0 ? (uint32_t)id[0] : CULL_NOID) | (mem[0] << 30), (id[1] >= 0 ? (uint32_t)id[1] : CULL_NOID) | (mem[1] << 30));
     s_g[p] = G; s_z0[p] = pz0; s_z1[p] = pz1; s_ro[p] = pro; s_qn[p] = pq;
     __syncthreads();
     for (uint32_t len = 2; len <= 128u; len <<= 1) {
@@ -1227,7 +1316,10 @@ __global__ void __launch_bounds__(128) lane_build_kernel(const int4* __restrict_
         s_q16[p] = q16;
     }
     __syncthreads();
-    if (p == 0) lvl[(uint64_t)cell * LN_LVL] = make_float4(ccx, ccy, zc, __uint_as_float(qrow[cell]));
+    if (p == 0) {       // (shared-row form: the cone of the union = the narrower of the two cells')
+        const uint32_t c0 = upair ? c_ix * Y + c_iy : cell;
+        lvl[(uint64_t)cell * LN_LVL] = make_float4(ccx, ccy, zc, __uint_as_float(two ? min(qrow[c0], qrow[c0 + 1u]) : qrow[c0]));
+    }
     if (p < 8u) {           // levels 2p, 2p + 1 in one float4
         lvl[(uint64_t)cell * LN_LVL + 1u + p] = make_float4(__uint_as_float(s_lv[2u * p].x), __uint_as_float(s_lv[2u * p].y),
                                                             __uint_as_float(s_lv[2u * p + 1u].x), __uint_as_float(s_lv[2u * p + 1u].y));
@@ -1288,20 +1380,20 @@ __device__ __forceinline__ float mix_fma_lo(float a, float b, uint32_t packed) {
 }
 
 // the exact phase on 2-byte entries {ray position | pair position << 6}: ids through the cell's id row, then as cull_exact
-// (cellm: per lane, the cell of run position `lane` with its map in bit 31)
+// (cellm: per lane, the table row of run position `lane` with its map in bit 31 and, in shared-row form, the ray's parity iy & 1 in bit 30)
 template <int H>
 __device__ __forceinline__ void lane_exact(const RayRec* __restrict__ rays, const RawTri* __restrict__ rt0, const RawTri* __restrict__ rt1,
                                            const uint2* __restrict__ lid0, const uint2* __restrict__ lid1, uint32_t pp01, const uint16_t* q, uint32_t n,
                                            const float4* s_abs /* LDS: per run position {origin, -}, {direction, -} as the ray record holds them */,
-                                           uint32_t cellm, uint32_t lane, uint32_t* bk) {
+                                           uint32_t cellm, uint32_t lane, uint32_t* bk, uint32_t forms) {
     if (n == 0u) return;
     auto ids_of = [&](uint32_t i, uint32_t& pos, uint32_t& map) {
         const uint32_t e = q[min(i, n - 1u)];
         pos = e & 63u;
         const uint32_t c = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pos << 2), (int)cellm);
-        map = c >> 31;
-        const uint32_t pp = map ? pp01 >> 16 : pp01 & 0xffffu;
-        return (map ? lid1 : lid0)[(uint64_t)(c & 0x7fffffffu) * pp + (e >> 6)];
+        map = c >> 30;                                                 // the map in bit 1, the ray's parity within a shared row in bit 0
+        const uint32_t pp = (map & 2u) ? pp01 >> 16 : pp01 & 0xffffu;
+        return ((map & 2u) ? lid1 : lid0)[(uint64_t)(c & LN_IDMASK) * pp + (e >> 6)];
     };
     // Two rounds in flight: while round k's 64 entries are evaluated, round k + 1's triangle / ray records (addressed through its ids,
     // which arrived during round k - 1) and round k + 2's ids are on their way — a round waits for memory only where the arithmetic of
@@ -1309,8 +1401,12 @@ __device__ __forceinline__ void lane_exact(const RayRec* __restrict__ rays, cons
     struct Recs { RawTri r0, r1; float4 ra, rb; uint32_t id0, id1, pos; };
     auto recs_of = [&](uint2 idp, uint32_t pos, uint32_t map) {
         Recs x;
-        const RawTri* rt = map ? rt1 : rt0;
-        x.id0 = idp.x; x.id1 = idp.y; x.pos = pos;
+        const RawTri* rt = (map & 2u) ? rt1 : rt0;
+        // shared-row form: bit 30 + parity of an id word says that the ray's own cell lists the triangle; one it does not list is no triangle
+        const uint32_t mbit = ((forms >> (2u + (map >> 1))) & 1u) ? 30u + (map & 1u) : 32u;
+        x.id0 = mbit < 32u && !((idp.x >> mbit) & 1u) ? CULL_NOID : idp.x & LN_IDMASK;
+        x.id1 = mbit < 32u && !((idp.y >> mbit) & 1u) ? CULL_NOID : idp.y & LN_IDMASK;
+        x.pos = pos;
         x.r0 = rt[x.id0 == CULL_NOID ? 0u : x.id0]; x.r1 = rt[x.id1 == CULL_NOID ? 0u : x.id1];
         x.ra = s_abs[2u * pos]; x.rb = s_abs[2u * pos + 1u];          // (from LDS: two gathers less per round)
         return x;
@@ -1369,7 +1465,8 @@ __device__ __forceinline__ void lane_exact(const RayRec* __restrict__ rays, cons
         const float4 *__restrict__ lvl1, const uint4 *__restrict__ lrec0, const uint4 *__restrict__ lrec1, const uint2 *__restrict__ lid0,    \
         const uint2 *__restrict__ lid1, const RawTri *__restrict__ rtab0, const RawTri *__restrict__ rtab1, uint32_t pp01, uint32_t run,      \
         uint32_t n_blocks, uint32_t split, uint32_t t8, uint32_t r8, uint32_t chsr, uint32_t run_r, float *__restrict__ out,                  \
-        uint4 *__restrict__ stats, float k2_far, float c_a, uint32_t forms /* bit w: map w's f32 tables are in box form */
+        uint4 *__restrict__ stats, float k2_far, float c_a, uint32_t forms /* bit w: map w's f32 tables are in box form; bit 2 + w: map w's   \
+        tables are in shared-row form */, FastDiv yd0, FastDiv yd1, uint32_t y0, uint32_t y1 /* shared-row form: the map's Y, and the division by it */
 
 template <int H>
 __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bounds__(64) lane_scan_kernel(LANE_SCAN_ARGS) {
@@ -1407,7 +1504,13 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     const uint32_t cell = __float_as_uint(rsa.w), rflags = __float_as_uint(rsb.w), map = rflags & 1u;
     const bool act = in_run && (rflags & 2u) != 0u;
     const uint32_t pp = map ? pp01 >> 16 : pp01 & 0xffffu, nch = pp / LN_CH;
-    const float4* lp = (map ? lvl1 : lvl0) + (uint64_t)cell * LN_LVL;
+    // the row of the map's tables: the cell, or — shared-row form — the row of cells (ix, 2j), (ix, 2j + 1), with the ray's parity iy & 1
+    uint32_t rowi = cell, par = 0u;
+    if ((forms >> (2u + map)) & 1u) {
+        const uint32_t Y = map ? y1 : y0, ix = map ? yd1.div(cell) : yd0.div(cell), iy = cell - ix * Y;
+        rowi = ix * ((Y + 1u) >> 1) + (iy >> 1); par = iy & 1u;
+    }
+    const float4* lp = (map ? lvl1 : lvl0) + (uint64_t)rowi * LN_LVL;
     const float4 hdr = lp[0];
     float4 lv[8];                                             // 16 levels x {G, z0 | z1, rho_out} (fp16)
 #pragma unroll
@@ -1454,10 +1557,12 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     // The items, in the order bin by bin, chunk by chunk, the bin's rays that test the chunk: lanes that read the same 128-byte line of a
     // record row sit next to each other.  Position of item (ray, k) = items of the bins before + items of the bin's chunks before k + the
     // ray's rank among the bin's rays with more than k items.  Two lists: the (A) items, behind them the (A) + (B) items.
-    const uint32_t key = cell | (map << 31);
+    const uint32_t cellm = rowi | (par << 30) | (map << 31), key = cellm & ~(1u << 30);       // (the ROW: lanes that read the same line sit side by side across both cells of a shared row)
     const uint32_t prevk = (uint32_t)__shfl_up((int)key, 1, 64);
     const bool head = act && (lane == 0u || key != prevk);
     const uint64_t heads = __builtin_amdgcn_ballot_w64(head);
+    const uint32_t n_bins = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(                      // (the counter keeps counting CELLS)
+        act && (lane == 0u || cellm != (uint32_t)__shfl_up((int)cellm, 1, 64))));
     const uint64_t lt = (1ull << lane) - 1ull, le = (lt << 1) | 1ull;         // bits below / up to this lane
     const uint64_t below = heads & le, above = heads & ~le;
     const uint32_t lo = below ? 63u - (uint32_t)__builtin_clzll(below) : 0u, hi = above ? (uint32_t)__builtin_ctzll(above) : n_run;
@@ -1467,7 +1572,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     const uint32_t base_a = (uint32_t)__shfl((int)(ia_incl - n_a), (int)lo, 64), base_b = ia_tot + (uint32_t)__shfl((int)(ib_incl - n_b), (int)lo, 64);
     wave_lds_sync();
     {
-        const char* rowp = reinterpret_cast<const char*>(map ? lrec1 : lrec0) + (uint64_t)cell * (2u * 16u) * pp;
+        const char* rowp = reinterpret_cast<const char*>(map ? lrec1 : lrec0) + (uint64_t)rowi * (2u * 16u) * pp;
         const uint64_t ra64 = (uint64_t)reinterpret_cast<uintptr_t>(rowp);
         s_abs[2u * lane] = rsa; s_abs[2u * lane + 1u] = rsb;
         s_ray[2u * lane] = make_float4(sx, sy, sz, rsb.x);
@@ -1587,7 +1692,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     // candidates -> queue entries; the exact phase whenever the queue could not take the next ray's entries (rare) and at the end
     auto flush = [&]() {
         wave_lds_sync();
-        lane_exact<H>(rays, rtab0, rtab1, lid0, lid1, pp01, s_q, cused, s_abs, key, lane, s_bk);
+        lane_exact<H>(rays, rtab0, rtab1, lid0, lid1, pp01, s_q, cused, s_abs, cellm, lane, s_bk, forms);
         ctot += cused;
         cused = 0;
         ++n_flush;
@@ -1642,7 +1747,6 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
         const uint32_t n_both = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(allc || ab) & am);
         const uint32_t n_askip = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(act && L == 0u) & am);
         const uint32_t n_fskip = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(act && !allc && 2u * L <= nch) & am);
-        const uint32_t n_bins = (uint32_t)__builtin_popcountll(heads);
         const uint32_t n_rays = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(act));          // (env order: without the padding slots)
         if (lane == 0u) stats[wave] = make_uint4(ctot, n_rays | (n_fskip << 8), n_both | (n_askip << 8), n_bins | (min(ia_tot + ib_tot, 0x3ffffu) << 8) | (min(n_flush, 63u) << 26));
     }
@@ -1674,7 +1778,7 @@ float cull_far_k2(int half, CullProofH ph) {
 uint32_t lane_pairs_per_row(uint32_t K8);
 static void lane_build(const int32_t* idx4, const uint4* ctab, uint64_t n_cells, uint32_t K8, uint32_t Y, float cell_size, float shift_x, float shift_y,
                        const uint32_t* qrow, const float* nz_abs, LaneTables t, int half, CullProofH ph, const uint16_t* rtab, int box, uint32_t* fill,
-                       hipStream_t s);
+                       hipStream_t s, const uint2* upair = nullptr, uint32_t pp_shared = 0);
 // ctab / qrow / far: the f32 proof's tables; ctab_h / qrow_h / far_h: the as-shipped fp16 arithmetic's (CullK<1>); idx4 and rtab serve both.
 hipError_t launch_cull_build(const CullBuildArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(rtab_build_kernel, dim3(blocks_for(a.T_int, 256)), dim3(256), 0, s, a.tris, a.verts, a.T_int, a.V, a.order, a.rtab);
@@ -1777,13 +1881,15 @@ uint32_t lane_lvl_stride() { return LN_LVL; }
 
 static void lane_build(const int32_t* idx4, const uint4* ctab, uint64_t n_cells, uint32_t K8, uint32_t Y, float cell_size, float shift_x, float shift_y,
                        const uint32_t* qrow, const float* nz_abs, LaneTables t, int half, CullProofH ph, const uint16_t* rtab, int box, uint32_t* fill,
-                       hipStream_t s) {
+                       hipStream_t s, const uint2* upair, uint32_t pp_shared) {
     if (!t.lrec) return;
     float k1, k2;
     if (half) cull_far_consts(ph.c_a, 1.004, &k1, &k2); else cull_far_consts(CullK<0>::c_a, 1.00001, &k1, &k2);
-    hipLaunchKernelGGL(lane_build_kernel, dim3((uint32_t)n_cells), dim3(128), 0, s, reinterpret_cast<const int4*>(idx4), ctab, K8, lane_pairs_per_row(K8),
+    // (shared-row form: one workgroup per row of two cells, rows of pp_shared pairs)
+    const uint32_t n_rows = upair ? (uint32_t)(n_cells / Y) * ((Y + 1u) / 2u) : (uint32_t)n_cells;
+    hipLaunchKernelGGL(lane_build_kernel, dim3(n_rows), dim3(128), 0, s, reinterpret_cast<const int4*>(idx4), ctab, K8, upair ? pp_shared : lane_pairs_per_row(K8),
                        Y, cell_size, shift_x, shift_y, k1, half ? ph.tau2 : CullK<0>::tau2, half ? ph.c_rho : CullK<0>::c_rho, qrow, nz_abs, t.lvl, t.lrec,
-                       t.lid, half, half ? LN_QGOOD_H : LN_QGOOD, rtab, box, fill);
+                       t.lid, half, half ? LN_QGOOD_H : LN_QGOOD, rtab, box, fill, upair);
 }
 
 bool lane_box_share_met(uint64_t pairs, uint64_t well_filled) { return pairs > 0 && (double)well_filled >= LN_BOX_SHARE * (double)pairs; }
@@ -1791,6 +1897,26 @@ bool lane_box_share_met(uint64_t pairs, uint64_t well_filled) { return pairs > 0
 // the f32 proof's staged tables of a map once more, in box form (after launch_cull_build, whose build buffers it reads)
 hipError_t launch_lane_box(const CullBuildArgs& a, hipStream_t s) {
     lane_build(a.idx4, a.ctab, a.n_cells, a.K8, a.Y, a.cell_size, a.shift_x, a.shift_y, a.qrow, a.nz_scratch, a.lane, 0, a.ph, a.rtab, 1, nullptr, s);
+    return hipGetLastError();
+}
+
+// Shared-row form.  launch_lane_union: the rows' unions into upair [rows][128] and the largest union, in pairs, into
+// counts[7]; where that fits a row (lane_pair_rows_pp != 0) launch_lane_pair_rows builds both proofs' tables — sized by the caller for rows of
+// that many pairs — from them (after launch_cull_build, whose build buffers it reads; it leaves the fp16 proof's cone values in nz_scratch).
+uint64_t lane_pair_rows_count(uint64_t n_cells, uint32_t Y) { return (n_cells / Y) * ((Y + 1u) / 2u); }
+uint32_t lane_pair_rows_pp(uint32_t max_union_pairs) {
+    return max_union_pairs == 0u || max_union_pairs > LN_MAXCH * LN_CH ? 0u : ((max_union_pairs + LN_CH - 1u) / LN_CH) * LN_CH;
+}
+hipError_t launch_lane_union(const CullBuildArgs& a, uint2* upair, hipStream_t s) {
+    hipLaunchKernelGGL(lane_union_kernel, dim3((uint32_t)lane_pair_rows_count(a.n_cells, a.Y)), dim3(512), 0, s, a.idx4, a.K8, a.Y, (a.Y + 1u) / 2u, upair, a.counts + 7);
+    return hipGetLastError();
+}
+hipError_t launch_lane_pair_rows(const CullBuildArgs& a, const uint2* upair, uint32_t pp, int box, hipStream_t s) {
+    lane_build(a.idx4, a.ctab, a.n_cells, a.K8, a.Y, a.cell_size, a.shift_x, a.shift_y, a.qrow, a.nz_scratch, a.lane, 0, a.ph, a.rtab, box, nullptr, s, upair, pp);
+    if (a.lane_h.lrec) {
+        hipLaunchKernelGGL(ctab_build_kernel<1>, dim3(blocks_for(a.T_int, 256)), dim3(256), 0, s, a.rtab, a.T_int, a.order, a.ctab_h, a.nz_scratch, (uint32_t*)nullptr, a.ph);
+        lane_build(a.idx4, a.ctab_h, a.n_cells, a.K8, a.Y, a.cell_size, a.shift_x, a.shift_y, a.qrow_h, a.nz_scratch, a.lane_h, 1, a.ph, a.rtab, 0, nullptr, s, upair, pp);
+    }
     return hipGetLastError();
 }
 
@@ -1812,7 +1938,8 @@ hipError_t launch_raycast_lane(LaneArgs a, hipStream_t s) {
     hipLaunchKernelGGL(a.half ? lane_scan_kernel<1> : lane_scan_kernel<0>, dim3((g.t8 + g.r8) * 8u * 4u), dim3(64), 0, s, a.rays, a.sorted,
                        a.n_sorted, a.lvl[0], a.lvl[1], a.lrec[0], a.lrec[1], a.lid[0], a.lid[1], reinterpret_cast<const RawTri*>(a.rtab[0]),
                        reinterpret_cast<const RawTri*>(a.rtab[1]), a.pp[0] | (a.pp[1] << 16), g.run, g.n_blocks, g.split, g.t8, g.r8, g.chs | (g.chr << 8),
-                       g.run_r, a.out, a.stats, k2, c_a, a.half ? 0u : a.forms);
+                       g.run_r, a.out, a.stats, k2, c_a, a.half ? a.forms & 0xcu : a.forms, make_fastdiv(a.y[0] ? a.y[0] : 1u), make_fastdiv(a.y[1] ? a.y[1] : 1u),
+                       a.y[0], a.y[1]);
     return hipGetLastError();
 }
 

@@ -101,7 +101,8 @@ struct LaneArgs {
     uint4* stats;
     int half;                    // the tables are the as-shipped fp16 arithmetic's, the exact phase runs it
     float c_a_h, k2_far;         // test (A)'s constant of that proof; the level bound's ray-side constant (cull_far_k2)
-    uint32_t forms;              // f32 proof: bit w = map w's pair records are boxes (launch_lane_box), else two spheres
+    uint32_t forms;              // bit w (f32 proof) = map w's pair records are boxes (launch_lane_box), else two spheres; bit 2 + w = map w's tables are in shared-row form
+    uint32_t y[2];               // per map: its Y (cell = ix * Y + iy), what the shared-row form finds a cell's row with
 };
 uint32_t lane_lvl_stride();
 hipError_t launch_raycast_lane(LaneArgs a, hipStream_t s);
@@ -433,7 +434,7 @@ struct CullBuildArgs {
     uint32_t *qrow, *qrow_h;     // [cell] per proof, read only by the build kernels
     float4 *far, *far_h;         // [cell][2] far-pair bounds, then [cell] near-pair bounds, per proof
     float* nz_scratch;           // [T_int]
-    uint32_t* counts;            // [7], zeroed: always-candidate triangles, cells without a cone; the same for fp16; cells with a useful far bound; non-empty and well-filled pairs (f32 staged tables)
+    uint32_t* counts;            // [8], zeroed: [7] the largest union of a shared row, in pairs (launch_lane_union); [0..6] always-candidate triangles, cells without a cone; the same for fp16; cells with a useful far bound; non-empty and well-filled pairs (f32 staged tables)
     CullProofH ph;
     uint32_t Y;
     float cell_size, shift_x, shift_y;
@@ -444,6 +445,13 @@ hipError_t launch_cull_build(const CullBuildArgs& a, hipStream_t s);
 // well-filled pairs in counts[5], counts[6]; where lane_box_share_met, launch_lane_box builds the same tables again as boxes.
 bool lane_box_share_met(uint64_t pairs, uint64_t well_filled);
 hipError_t launch_lane_box(const CullBuildArgs& a, hipStream_t s);
+// Shared-row form of a map's staged tables, both proofs: one row per two cells that neighbour in iy.  launch_lane_union leaves
+// the rows' unions in upair [lane_pair_rows_count][128] and the largest one in counts[7]; lane_pair_rows_pp gives the pairs per row for it,
+// or 0 where a union does not fit a row (the map then keeps its per-cell tables); launch_lane_pair_rows builds the tables.
+uint64_t lane_pair_rows_count(uint64_t n_cells, uint32_t Y);
+uint32_t lane_pair_rows_pp(uint32_t max_union_pairs);
+hipError_t launch_lane_union(const CullBuildArgs& a, uint2* upair, hipStream_t s);
+hipError_t launch_lane_pair_rows(const CullBuildArgs& a, const uint2* upair, uint32_t pp, int box, hipStream_t s);
 float cull_far_k2(int half, CullProofH ph);
 hipError_t launch_raycast_culled(CullArgs a, hipStream_t s);
 hipError_t launch_knn_centroids(const float* verts, const int32_t* tris, uint32_t T, uint32_t V, int ref, float* cx, float* cy,

@@ -27,6 +27,7 @@ struct Knobs {
     uint32_t low_bits_opt = 0;          // "bin_low_bits": 0 chosen by the library, else 8..12
     uint64_t cull_budget = 1536ull << 20;   // "cull_queue_mb": most bytes the candidate queue may take
     int lane_box = -1;                  // "lane_box": the f32 proof's staged records of the next rover_set_knn_map as boxes: -1 auto (where most pairs fill theirs), 0 spheres, 1 boxes
+    int lane_pair_rows = -1;            // "lane_pair_rows": the staged tables of the next rover_set_knn_map with one row per two cells: -1 auto (the terrain map), 0 no map, 1 both maps
     int staged_tables = 3;              // "staged_tables": which proofs' staged-kernel tables the next rover_set_knn_map builds (bit 0 f32, bit 1 fp16)
     uint32_t early_out = 1;             // "raycast_early_out": the binned kernel's whole-pair rejection (bit-identical results)
     double cull_eta_h = 0.08;           // ROVER_CULLH_ETA: free parameter of the fp16 proof (rover_cull.hip, cull_proof_h)
