@@ -10,6 +10,10 @@ Prints the three losses per update and saves the reference's `{"state_dict": ...
 loads.
 
     python examples/distill.py --envs 512 --window 32 --updates 20 [--teacher actor.pt] [--out student.pt]
+
+`--device-noise`, `--obs-offset S` or `--obs-dropout P` switch the perception model to `learning.noise.HeightmapNoise`: every step's
+observation is written into the window by one `rover_obs_noise` launch (Gaussian noise `--noise` per column, a Gaussian offset per env
+and episode, dropout to 0), counter-based and independent of the batch shape; the window-sized `torch.randn` tensor is then never made.
 """
 import argparse
 import os
@@ -30,6 +34,10 @@ def main():
     ap.add_argument("--native-rays", action="store_true", help="the reference's 1634-point distribution (1750-float obs)")
     ap.add_argument("--teacher", default="", help="a state_dict of the reference's StochasticActorHeightmap (torch.save)")
     ap.add_argument("--noise", type=float, default=0.05, help="standard deviation of the noise on the student's heightmap columns")
+    ap.add_argument("--obs-offset", type=float, default=0.0, help="standard deviation of a per-env, per-episode offset on the heightmap columns")
+    ap.add_argument("--obs-dropout", type=float, default=0.0, help="probability of a heightmap column reading 0")
+    ap.add_argument("--device-noise", action="store_true", help="the noise as one rover_obs_noise launch per step instead of torch.randn "
+                    "(implied by --obs-offset / --obs-dropout)")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--grad-norm-clip", type=float, default=1.0)
     ap.add_argument("--recon-scale", type=float, default=0.5)
@@ -68,18 +76,28 @@ def main():
     clean = torch.empty(e, t_len, ex, device=task.device)
     wanted = torch.empty(e, t_len, task.num_actions, device=task.device)
     reset = torch.zeros(e, t_len, dtype=torch.bool, device=task.device)
-    noise_gen = torch.Generator(device=task.device).manual_seed(2)
+    noise = noise_gen = None
+    if args.device_noise or args.obs_offset or args.obs_dropout:
+        from isaac_rover_amd.learning.noise import HeightmapNoise
+        noise = HeightmapNoise(task._engine, task, sigma_point=args.noise, sigma_offset=args.obs_offset, dropout=args.obs_dropout, seed=2)
+        print(f"perception: rover_obs_noise, sigma_point {args.noise} sigma_offset {args.obs_offset} dropout {args.obs_dropout}")
+    else:
+        noise_gen = torch.Generator(device=task.device).manual_seed(2)
     h, done = None, torch.zeros(e, dtype=torch.bool, device=task.device)
     for u in range(args.updates):
         for t in range(t_len):
             actions, _, _ = teacher.act(obs, deterministic=True)
-            x[:, t] = obs
+            if noise is None:
+                x[:, t] = obs
+            else:
+                noise.apply(obs, out=x[:, t], reset=done)                          # the noisy row straight into the window
             clean[:, t] = obs[:, f - ex:]
             wanted[:, t] = actions
             reset[:, t] = done                                                     # an env that just ended starts from a zero hidden state
             obs, _, done, _ = env.step(actions)
             done = done.bool().clone()
-        x[:, :, f - ex:] += args.noise * torch.randn(e, t_len, ex, device=task.device, generator=noise_gen)
+        if noise is None:
+            x[:, :, f - ex:] += args.noise * torch.randn(e, t_len, ex, device=task.device, generator=noise_gen)
         loss, action_loss, recon_loss, h = trainer.update(x, wanted, h0=h, reset=reset, target=clean)
         print(f"update {u + 1}: loss {float(loss):.6f}  action_loss {float(action_loss):.6f}  recon_loss {float(recon_loss):.6f}")
     if args.out:

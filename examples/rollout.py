@@ -41,7 +41,14 @@ def main():
     ap.add_argument("--precision", choices=("f32", "bf16"), default="f32",
                     help="--policy actor: what the actor and the critic act in (bf16: bf16 operands, f32 accumulation and head); "
                     "--policy student: what StudentPolicy.act runs in (bf16: every matrix product, the GRU state stays f32)")
+    ap.add_argument("--obs-noise", type=float, default=0.0, help="--policy actor / student: standard deviation of Gaussian noise on the heightmap "
+                    "columns the policy sees (rover_obs_noise; the task and its rewards keep the clean observation)")
+    ap.add_argument("--obs-offset", type=float, default=0.0, help="... of a per-env, per-episode offset on them")
+    ap.add_argument("--obs-dropout", type=float, default=0.0, help="... probability of a heightmap column reading 0")
     args = ap.parse_args()
+    noisy = bool(args.obs_noise or args.obs_offset or args.obs_dropout)
+    if noisy and args.policy == "random":
+        ap.error("--obs-noise / --obs-offset / --obs-dropout need --policy actor or student")
     if args.rollouts < 0 or (args.rollouts and args.policy != "actor"):
         ap.error("--rollouts N needs N >= 0 and --policy actor")
 
@@ -78,6 +85,11 @@ def main():
         print(f"policy: StudentPolicy, {sum(v.numel() for v in student.state_dict().values()):,} parameters"
               f"{' from ' + args.checkpoint if args.checkpoint else ' (fresh initialisation)'}"
               f"{', acting in bf16' if args.precision == 'bf16' else ''}")
+    noise = None
+    if noisy:
+        from isaac_rover_amd.learning.noise import HeightmapNoise
+        noise = HeightmapNoise(task._engine, task, sigma_point=args.obs_noise, sigma_offset=args.obs_offset, dropout=args.obs_dropout, seed=3)
+        print(f"perception: rover_obs_noise, sigma_point {args.obs_noise} sigma_offset {args.obs_offset} dropout {args.obs_dropout}")
     critic = memory = done = None
     if args.rollouts:
         from isaac_rover_amd.learning.model import DeterministicHeightmap
@@ -93,12 +105,13 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
+        seen = obs if noise is None else noise.apply(obs, reset=done)              # what the policy sees; the task keeps the clean obs
         if student is not None:
-            actions = student.act(obs, reset=None if done is None else done.bool())  # an env that just ended starts from a zero hidden state
+            actions = student.act(seen, reset=None if done is None else done.bool())  # an env that just ended starts from a zero hidden state
         elif agent is None:
             actions = 2 * torch.rand(args.envs, 2, device=task.device) - 1
         else:
-            actions, log_prob, outputs = agent.act(obs)                            # what a PPO rollout stores next to obs and rew
+            actions, log_prob, outputs = agent.act(seen)                           # what a PPO rollout stores next to obs and rew
         if memory is not None:
             values, _, _ = critic.act(obs)
             states = obs.clone()                                                   # env.step() rewrites the observation buffer

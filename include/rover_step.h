@@ -769,6 +769,57 @@ ROVER_API int rover_gated_sum_backward(rover_ctx *ctx, const float *d_out, int64
                                        const float *pre, int64_t pre_stride, int32_t M, int32_t N, float *d_mul, int64_t d_mul_stride,
                                        float *d_pre, int64_t d_pre_stride, void *stream);
 
+/* ---- exteroception noise: the sensor model between the task's observation and a policy (learning/noise.py) ------------------------- */
+/* The reference's authors tried Gaussian noise, dropout, a constant offset and zeroed columns on the observation (tasks/rover.py:326-329,
+ * commented out) and carry is_evaluation_with_noise / max_noise_dev = 0.2; what follows is this project's definition.  The task's own
+ * observation stays clean: the call maps in [M, F] to out [M, F] (f32 rows at a row stride in floats).
+ * Columns [0, first) — the proprioceptive ones — are copied bit for bit.  For heightmap column c = col - first, 0 <= c < C = F - first,
+ * global row g = row_offset + r, call counter t = step + *step_dev (mod 2^64; step_dev NULL: step alone) and column pair p = c / 2:
+ *   w    = philox(counter = (g, t & 0xffffffff, t >> 32, 0x60000000 | p), key = (seed & 0xffffffff, seed >> 32))
+ *   eps  = the head's Box-Muller pair from (w[0], w[1]) exactly as the rover_gauss_head comment writes it: eps[2 p] the cos branch,
+ *          eps[2 p + 1] the sin branch
+ *   u_c  = w[2] >> 8 for even c, w[3] >> 8 for odd c                                     (a 24-bit integer)
+ *   e    = episode ? episode[r] : 0                                                       (int64, taken mod 2^64)
+ *   wo   = philox(counter = (g, e & 0xffffffff, e >> 32, 0x70000000), key as above)
+ *   eo   = the cos branch of the pair from (wo[0], wo[1])     (one draw per env and episode: the same for every column and every call)
+ *   s    = row_scale ? row_scale[r] : 1.0f
+ *   v    = (in[r, col] + (sigma_offset * s) * eo) + (sigma_point * s) * eps_c            f32, one rounding per written operation
+ *   out[r, col] = u_c < thr ? drop_value : v,      thr = (uint32) llrint(dropout * 2^24), computed once on the host
+ * (rover_obs_noise_threshold returns that thr: 0 for dropout 0 — nothing dropped —, 2^24 for 1 — everything.)
+ * Streams: word 3 of the counter is 0 in the goal / yaw draws and 0x50000000 | pair in the action noise, so the four streams are disjoint
+ * under one seed.  A value depends on (seed, t, g, c), on e and on the row's own inputs — not on M, not on a stride, not on how a batch is
+ * sharded (a shard passes its env_offset as row_offset), not on eager execution against graph replay.  The library never writes
+ * *step_dev or episode: the caller advances them with work enqueued on the same stream after the call, as for act().
+ * A sigma of 0 switches its term off: the term is +0.0f and its draw is not made, whatever s is.  With sigma_point = sigma_offset = 0
+ * and dropout = 0 the call therefore computes (in + 0.0f) + 0.0f: out equals in, except that -0.0f becomes +0.0f (a NaN stays a NaN).
+ * sigma_point = 0 with dropout > 0 still takes u_c from words 2 and 3 of the same Philox call.  Everywhere else the results are the
+ * written formula's, bit for bit, on both of the kernel's paths: a column pair moves as one 8-byte load and one 8-byte store when first
+ * and both strides are even and both bases 8-byte aligned (the native obs: first 4, stride 1 750), as two scalars otherwise.
+ * One launch (csrc/rover_noise.hip); plain vector loads and stores, no atomics.  The call allocates nothing, does not synchronise and can
+ * be captured in a graph; one stream per ctx at a time.  M = 0 or F = 0: ROVER_OK, no launch.  out may be exactly in (same pointer and
+ * stride): the in-place form, which leaves columns [0, first) alone.
+ * ROVER_E_INVALID before any launch — the descriptor is checked before the ctx is looked at, so with a NULL ctx rover_last_error(NULL)
+ * names the refusal (a NULL ctx itself is refused last) —: a NULL descriptor; NULL in / out with M F > 0; a row stride < F or > 2^40;
+ * M < 0 or F < 0; first outside 0 .. F; C > 2^21; a negative or non-finite sigma; dropout outside [0, 1] or NaN; a non-finite
+ * drop_value; row_offset < 0 or row_offset + M > 2^32; out overlapping in other than as the same array; row_scale, episode or step_dev
+ * overlapping out. */
+typedef struct {
+    const float *in;        int64_t in_stride;     /* [M, F]                                                                     */
+    float *out;             int64_t out_stride;    /* [M, F]; may be exactly in                                                   */
+    int32_t M, F, first;                           /* first: the number of leading columns left alone, 0 .. F                      */
+    float sigma_point, sigma_offset;               /* per-element and per-episode standard deviations, >= 0                        */
+    double dropout;                                /* probability of a column reading drop_value, 0 .. 1                           */
+    float drop_value;
+    const float *row_scale;                        /* optional device [M]: scales both sigmas of its row                           */
+    const int64_t *episode;                        /* optional device [M]: the row's episode count, keys the offset draw           */
+    uint64_t seed, step;
+    const uint64_t *step_dev;                      /* optional device [1], added to step when the kernel runs                      */
+    int64_t row_offset;                            /* global row of row 0: >= 0, row_offset + M <= 2^32                            */
+} rover_obs_noise_desc;
+ROVER_API int rover_obs_noise(rover_ctx *ctx, const rover_obs_noise_desc *d, void *stream);
+/* Host only (no ctx, no device): *thr = (uint32) llrint(dropout * 2^24); ROVER_E_INVALID for a NULL thr or dropout outside [0, 1]. */
+ROVER_API int rover_obs_noise_threshold(double dropout, uint32_t *thr);
+
 /* ---- tuning knobs ------------------------------------------------------------------------------------- */
 /* name = "raycast_variant": 0 = auto; 1 = one half-wave per ray in env order, every cell block streamed from HBM;
  *        2 = rays counting-sorted by (map, cell), one wave per run of sorted rays, the cell's triangles held in registers

@@ -127,6 +127,13 @@ class OptimStepDesc(C.Structure):
                 ("gate", C.c_void_p), ("gate_threshold", C.c_double), ("norm_out", C.c_void_p)]
 
 
+class ObsNoiseDesc(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_stride", C.c_int64), ("out", C.c_void_p), ("out_stride", C.c_int64), ("M", C.c_int32), ("F", C.c_int32),
+                ("first", C.c_int32), ("sigma_point", C.c_float), ("sigma_offset", C.c_float), ("dropout", C.c_double), ("drop_value", C.c_float),
+                ("row_scale", C.c_void_p), ("episode", C.c_void_p), ("seed", C.c_uint64), ("step", C.c_uint64), ("step_dev", C.c_void_p),
+                ("row_offset", C.c_int64)]
+
+
 REDUCTIONS = {"sum": 0, "mean": 1, "prod": 2, "max": 3, "min": 4, None: 5, "none": 5}
 
 
@@ -221,6 +228,8 @@ SYMBOLS = {
     "rover_gated_sum_backward": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P]),
     "rover_linear_dgrad": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "rover_linear_dgrad_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
+    "rover_obs_noise": (C.c_int, [_P, C.POINTER(ObsNoiseDesc), _P]),
+    "rover_obs_noise_threshold": (C.c_int, [C.c_double, _P]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
     "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
     "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -352,6 +361,25 @@ def gauss_head_desc(A, log_std=_FAKE, actions=_FAKE, log_prob=_FAKE, clip_log_st
                      taken_actions, A if taken_stride is None else int(taken_stride), actions, A if actions_stride is None else int(actions_stride),
                      log_prob, (A if red == 5 else 1) if log_prob_stride is None else int(log_prob_stride), mean,
                      A if mean_stride is None else int(mean_stride))
+
+
+def obs_noise_desc(m, f, first, in_=_FAKE, out=_FAKE, in_stride=None, out_stride=None, sigma_point=0.0, sigma_offset=0.0, dropout=0.0,
+                   drop_value=0.0, row_scale=None, episode=None, seed=0, step=0, step_dev=None, row_offset=0):
+    """A rover_obs_noise_desc from plain values (pointers as integers; the strides default to ``f``)."""
+    f = int(f)
+    return ObsNoiseDesc(in_, f if in_stride is None else int(in_stride), out, f if out_stride is None else int(out_stride), int(m), f, int(first),
+                        float(sigma_point), float(sigma_offset), float(dropout), float(drop_value), row_scale, episode, int(seed) & (2 ** 64 - 1),
+                        int(step) & (2 ** 64 - 1), step_dev, int(row_offset))
+
+
+def obs_noise_threshold(dropout):
+    """rover_obs_noise_threshold: the integer rover_obs_noise compares a column's 24-bit dropout word with, llrint(dropout 2^24).  Host only."""
+    out = C.c_uint32()
+    lib = load()
+    rc = lib.rover_obs_noise_threshold(float(dropout), C.byref(out))
+    if rc != 0:
+        raise RoverError(f"rover_obs_noise_threshold failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return int(out.value)
 
 
 PRECISIONS = ("f32", "bf16")
@@ -826,6 +854,33 @@ class Engine:
         self._f32_rows(out, "out", "policy_noise", (int(m), int(a)))
         self._check(self.lib.rover_policy_noise(self._h, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), _ptr(step_dev), int(row_offset), int(m),
                                                 int(a), _ptr(out), out.stride(0), _stream(self._dev_index)), "rover_policy_noise")
+        return out
+
+    def obs_noise(self, obs, out=None, *, first, sigma_point=0.0, sigma_offset=0.0, dropout=0.0, drop_value=0.0, row_scale=None, episode=None,
+                  seed=0, step=0, step_dev=None, row_offset=0):
+        """The exteroception noise on ``obs`` [m, f] (rover_obs_noise, one launch): columns [0, first) copied, every later column
+        ``(obs + (sigma_offset s) eo) + (sigma_point s) eps``, or ``drop_value`` with probability ``dropout``; counter-based, keyed by
+        (seed, step + *step_dev, row_offset + row, column) and, for the offset draw eo, by ``episode`` [m] int64.  ``row_scale`` [m]
+        float32 is s (default 1).  ``out`` None: a new tensor; ``out is obs`` (or a view of the same memory): in place.  Strides come from
+        the tensors: ``out = x[:, t]`` of a [B, T, F] window works."""
+        what = "obs_noise"
+        self._f32_rows(obs, "obs", what)
+        m, f = obs.shape
+        if out is None:
+            out = torch.empty(m, f, device=obs.device)
+        self._f32_rows(out, "out", what, (m, f))
+        if obs.device != self.device or out.device != self.device:
+            raise RoverError(f"{what}: obs and out must be on {self.device}")
+        if row_scale is not None:
+            self._chk(row_scale, (m,), torch.float32, "row_scale")
+        if episode is not None:
+            self._chk(episode, (m,), torch.int64, "episode")
+        if step_dev is not None and (not step_dev.is_cuda or step_dev.dtype != torch.int64 or step_dev.numel() != 1):
+            raise RoverError(f"{what}: step_dev must be one int64 word on the GPU (read as uint64)")
+        dp = lambda t: None if t is None else t.data_ptr()
+        desc = obs_noise_desc(m, f, first, dp(obs), dp(out), max(obs.stride(0), f), max(out.stride(0), f), sigma_point, sigma_offset, dropout, drop_value,
+                              dp(row_scale), dp(episode), seed, step, dp(step_dev), row_offset)
+        self._check(self.lib.rover_obs_noise(self._h, C.byref(desc), _stream(self._dev_index)), "rover_obs_noise")
         return out
 
     chain_act_route = staticmethod(chain_act_route)

@@ -2187,6 +2187,53 @@ int rover_gated_sum_backward(rover_ctx* c, const float* d_out, int64_t d_out_str
     return ROVER_OK;
 }
 
+// Validates the whole descriptor before the ctx is looked at (a NULL ctx reports through rover_last_error(NULL)): the refusals can be
+// checked without a device.
+int rover_obs_noise(rover_ctx* c, const rover_obs_noise_desc* d, void* stream) {
+    if (!d) return fail(c, ROVER_E_INVALID, "obs_noise: null descriptor");
+    if (d->M < 0 || d->F < 0) return fail(c, ROVER_E_INVALID, "obs_noise: M = %d or F = %d is negative", d->M, d->F);
+    if (d->first < 0 || d->first > d->F) return fail(c, ROVER_E_INVALID, "obs_noise: first = %d outside 0 .. F = %d", d->first, d->F);
+    if (d->F - d->first > (1 << 21)) return fail(c, ROVER_E_INVALID, "obs_noise: %d heightmap columns, more than 2^21", d->F - d->first);
+    if (!(d->sigma_point >= 0.0f) || !std::isfinite(d->sigma_point) || !(d->sigma_offset >= 0.0f) || !std::isfinite(d->sigma_offset))
+        return fail(c, ROVER_E_INVALID, "obs_noise: sigma_point = %g or sigma_offset = %g is negative or not finite", (double)d->sigma_point, (double)d->sigma_offset);
+    if (!(d->dropout >= 0.0 && d->dropout <= 1.0)) return fail(c, ROVER_E_INVALID, "obs_noise: dropout = %g outside [0, 1]", d->dropout);
+    if (!std::isfinite(d->drop_value)) return fail(c, ROVER_E_INVALID, "obs_noise: drop_value is not finite");
+    if (d->row_offset < 0 || d->row_offset + (int64_t)d->M > (int64_t)1 << 32)
+        return fail(c, ROVER_E_INVALID, "obs_noise: row_offset = %lld is negative or row_offset + M passes 2^32", (long long)d->row_offset);
+    const bool empty = d->M == 0 || d->F == 0;
+    if (!empty) {
+        if (!d->in || !d->out) return fail(c, ROVER_E_INVALID, "obs_noise: in and out must be given");
+        const int64_t max_stride = (int64_t)1 << 40;
+        if (d->in_stride < d->F || d->out_stride < d->F || d->in_stride > max_stride || d->out_stride > max_stride)
+            return fail(c, ROVER_E_INVALID, "obs_noise: a row stride is shorter than its row (F = %d) or above 2^40", d->F);
+        const Span si = span_of(d->in, d->in_stride, d->M, d->F, 4), so = span_of(d->out, d->out_stride, d->M, d->F, 4);
+        if (overlap(si, so) && !(d->in == d->out && d->in_stride == d->out_stride))
+            return fail(c, ROVER_E_INVALID, "obs_noise: out overlaps in without being the same array (same pointer and stride)");
+        const Span side[3] = {span_of(d->row_scale, d->M, 1, d->M, 4), span_of(d->episode, d->M, 1, d->M, 8), span_of(d->step_dev, 1, 1, 1, 8)};
+        for (const Span& s : side)
+            if (s.lo && overlap(s, so)) return fail(c, ROVER_E_INVALID, "obs_noise: row_scale, episode or step_dev overlaps out");
+    }
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "obs_noise: null ctx");
+    if (empty) return ROVER_OK;
+    USE_DEVICE(c);
+    ObsNoiseArgs a{};
+    a.in = d->in; a.in_stride = d->in_stride; a.out = d->out; a.out_stride = d->out_stride;
+    a.M = d->M; a.F = d->F; a.first = d->first;
+    a.sigma_point = d->sigma_point; a.sigma_offset = d->sigma_offset; a.drop_value = d->drop_value;
+    (void)rover_obs_noise_threshold(d->dropout, &a.thr);
+    a.row_scale = d->row_scale; a.episode = d->episode;
+    a.seed = d->seed; a.step = d->step; a.step_dev = d->step_dev; a.row_offset = d->row_offset;
+    HIP_TRY(c, launch_obs_noise(a, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+// Host only: the dropout threshold rover_obs_noise compares a column's 24-bit word with
+int rover_obs_noise_threshold(double dropout, uint32_t* thr) {
+    if (!thr || !(dropout >= 0.0 && dropout <= 1.0)) return fail(nullptr, ROVER_E_INVALID, "obs_noise_threshold: null argument or dropout = %g outside [0, 1]", dropout);
+    *thr = (uint32_t)llrint(dropout * 16777216.0);
+    return ROVER_OK;
+}
+
 int rover_set_option(rover_ctx* c, const char* name, int64_t value) {
     if (!c || !name) return ROVER_E_INVALID;
     USE_DEVICE(c);                                 // some options (re)allocate device workspace

@@ -315,6 +315,23 @@ hipError_t launch_gaussian_head(const float* mean, int64_t mean_stride, int M, c
 hipError_t launch_policy_noise(uint64_t seed, uint64_t step, const uint64_t* step_dev, int64_t row_offset, int M, int A, float* eps,
                                int64_t eps_stride, hipStream_t s);
 
+// The exteroception noise on an observation matrix (rover_obs_noise of the C ABI, validated; rover_noise.hip): columns [0, first) are
+// copied, every heightmap column c = col - first gets v = (in + (sigma_offset s) eo) + (sigma_point s) eps_c, or drop_value where the
+// column's 24-bit word is below thr.  A sigma of 0 switches its term (and its draw) off; thr = 0 switches the dropout off.
+struct ObsNoiseArgs {
+    const float* in; int64_t in_stride;    // [M, F] rows at in_stride floats
+    float* out; int64_t out_stride;        // [M, F]; out == in (and the same stride): in place, the first columns are then left alone
+    int32_t M, F, first;
+    float sigma_point, sigma_offset, drop_value;
+    uint32_t thr;                          // llrint(dropout 2^24): 0 .. 2^24
+    const float* row_scale;                // optional [M]
+    const int64_t* episode;                // optional [M]
+    uint64_t seed, step;
+    const uint64_t* step_dev;              // optional [1]: added to step on the device
+    int64_t row_offset;                    // global row of local row 0
+};
+hipError_t launch_obs_noise(const ObsNoiseArgs& a, hipStream_t s);
+
 // Generalised advantage estimation over a stored rollout (rover_gae of the C ABI, validated; rover_rollout.hip): rows are time steps at
 // a stride in elements, the env stride is 1.
 enum GaeNormalize { GAE_RAW = 0, GAE_NORMALIZE = 1, GAE_NORMALIZE_GIVEN = 2 };

@@ -17,6 +17,7 @@
 #include "rover_act.h"
 #include "rover_bf16.h"
 #include "rover_philox.h"
+#include "rover_gauss.h"
 
 namespace rover {
 
@@ -278,18 +279,12 @@ __device__ __forceinline__ void c16_store(const f32x4 (&acc)[T], float* __restri
 // Noise: Philox4x32-10 keyed by the seed, counter (global row, call counter lo, hi, 0x50000000 | component pair) -> two uniforms ->
 // Box-Muller.  A draw depends on (seed, call counter, global row, component) alone: not on the batch size, the kernel route or the
 // sharding.  u0 = (24 bits + 1) 2^-24 in (0, 1] keeps the logarithm finite: |eps| <= sqrt(48 ln 2).  sincospif takes the angle in
-// half turns, so 2 pi u1 is never rounded.
+// half turns, so 2 pi u1 is never rounded (rover_gauss.h, shared with the exteroception noise of rover_noise.hip).
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void gauss_eps_pair(uint64_t seed, uint64_t t, uint32_t g, uint32_t p, float& e0, float& e1) {
     uint32_t c[4] = {g, (uint32_t)t, (uint32_t)(t >> 32), 0x50000000u | p};
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float u0 = (float)((c[0] >> 8) + 1u) * (1.0f / 16777216.0f);
-    const float u1 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
-    const float rad = sqrtf(-2.0f * logf(u0));
-    float sn, cs;
-    sincospif(2.0f * u1, &sn, &cs);
-    e0 = rad * cs;
-    e1 = rad * sn;
+    gauss_pair_of_words(c[0], c[1], e0, e1);                               // rover_gauss.h: the one copy of the Box-Muller pair
 }
 
 __device__ __forceinline__ float gauss_clamp(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }     // a NaN stays a NaN (torch.clamp)

@@ -8,7 +8,8 @@ task.  Every tensor computation of ``get_observations`` / ``calculate_metrics`` 
 class is host-side bookkeeping only and raises if the library or a GPU is missing (no CPU fallback).
 
 What is NOT here: USD stage building (:187-270), the dead teacher/student loaders (:169-172),
-teacher-data dumps (:298-317), the evaluation branch's prints and its unread ``is_evaluation_with_noise`` / ``max_noise_dev``.
+teacher-data dumps (:298-317), the evaluation branch's prints and its unread ``is_evaluation_with_noise`` / ``max_noise_dev``
+(the sensor model those stand for lives outside the task, in ``learning/noise.py``: the observation returned here stays the clean one).
 
 Evaluation mode (``is_evaluation=True``; :122-137, :620-641, :670-672) is the reference's: one outcome code per rover in
 ``self.rover_eval_res`` (1 collided or out of area, 2 reached the goal, 3 timed out; the first outcome counts), latched on the
