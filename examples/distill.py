@@ -44,13 +44,16 @@ def main():
     ap.add_argument("--torch-step", action="store_true", help="clip_grad_norm_ + torch.optim.Adam instead of the two HIP launches")
     ap.add_argument("--teacher-precision", choices=("f32", "bf16"), default="f32", help="what the teacher acts in (the student trains in f32)")
     ap.add_argument("--out", default="", help="where to save {'state_dict': ...} (the reference's best.pt layout)")
+    ap.add_argument("--sim", choices=("kinematic", "terrain"), default="kinematic",
+                    help="what moves the rovers between two steps: vec_env.KinematicSim, a flat unicycle, or TerrainSim, the terrain-following "
+                         "motion model (one rover_motion_step launch per control step: tilt from the ground under the wheels, joint state)")
     args = ap.parse_args()
     if args.window < 1 or args.updates < 1:
         ap.error("--window and --updates need values >= 1")
 
     scene = synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
     cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
-    env = vec_env.VecEnv(headless=True)
+    env = vec_env.VecEnv(headless=True, sim=args.sim)
     extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size
     g = torch.Generator().manual_seed(0)
     spawn = torch.zeros(args.envs, 3)

@@ -45,6 +45,9 @@ def main():
                     "columns the policy sees (rover_obs_noise; the task and its rewards keep the clean observation)")
     ap.add_argument("--obs-offset", type=float, default=0.0, help="... of a per-env, per-episode offset on them")
     ap.add_argument("--obs-dropout", type=float, default=0.0, help="... probability of a heightmap column reading 0")
+    ap.add_argument("--sim", choices=("kinematic", "terrain"), default="kinematic",
+                    help="what moves the rovers between two steps: vec_env.KinematicSim, a flat unicycle, or TerrainSim, the terrain-following "
+                         "motion model (one rover_motion_step launch per control step: tilt from the ground under the wheels, joint state)")
     args = ap.parse_args()
     noisy = bool(args.obs_noise or args.obs_offset or args.obs_dropout)
     if noisy and args.policy == "random":
@@ -54,7 +57,7 @@ def main():
 
     scene = assets.load_reference_assets(args.assets) if args.assets else synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
     cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
-    env = vec_env.VecEnv(headless=True)
+    env = vec_env.VecEnv(headless=True, sim=args.sim)
     extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size
     g = torch.Generator().manual_seed(0)
     spawn = torch.zeros(args.envs, 3)
@@ -129,7 +132,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{args.steps} steps x {args.envs} envs in {dt:.2f} s = {args.steps * args.envs / dt:,.0f} env-steps/s "
-          f"(incl. {args.policy} policy + toy pose feeder); episodes finished: {episodes}; mean return {float(ret.mean()):.4f}")
+          f"(incl. {args.policy} policy + {'toy pose feeder' if args.sim == 'kinematic' else 'terrain-following motion model'}); episodes finished: {episodes}; mean return {float(ret.mean()):.4f}")
     env.close()
 
 

@@ -37,13 +37,16 @@ def main():
     ap.add_argument("--rollout-precision", choices=("f32", "bf16"), default="f32",
                     help="what the actor and the critic ACT in while the rollout is collected; the update stays f32 (learning/ppo.py)")
     ap.add_argument("--time-update", action="store_true", help="print the wall time of each update between two torch.cuda.synchronize()")
+    ap.add_argument("--sim", choices=("kinematic", "terrain"), default="kinematic",
+                    help="what moves the rovers between two steps: vec_env.KinematicSim, a flat unicycle, or TerrainSim, the terrain-following "
+                         "motion model (one rover_motion_step launch per control step: tilt from the ground under the wheels, joint state)")
     args = ap.parse_args()
     if args.rollouts < 1:
         ap.error("--rollouts N needs N >= 1")
 
     scene = assets.load_reference_assets(args.assets) if args.assets else synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
     cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
-    env = vec_env.VecEnv(headless=True)
+    env = vec_env.VecEnv(headless=True, sim=args.sim)
     extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size
     g = torch.Generator().manual_seed(0)
     spawn = torch.zeros(args.envs, 3)

@@ -820,6 +820,46 @@ ROVER_API int rover_obs_noise(rover_ctx *ctx, const rover_obs_noise_desc *d, voi
 /* Host only (no ctx, no device): *thr = (uint32) llrint(dropout * 2^24); ROVER_E_INVALID for a NULL thr or dropout outside [0, 1]. */
 ROVER_API int rover_obs_noise_threshold(double dropout, uint32_t *thr);
 
+/* ---- terrain-following motion model: what moves the rovers between two steps (vec_env.TerrainSim) ------------------------------------ */
+/* PhysX is out of scope; this is the project's own definition of a deterministic, stateless, kinematic pose feeder that keeps the six
+ * wheels on the heightfield of rover_set_heightfield.  f32 on the device, one rounding per written operation, one thread per env.
+ * Wheel layout (kinematics.py:20-25, order FL, FR, ML, MR, RL, RR), as (right r_i, forward f_i):
+ *   (-0.385, 0.438) (0.385, 0.438) (-0.447, 0) (0.447, 0) (-0.385, -0.411) (0.385, -0.411);   body coordinates a_i = f_i, b_i = -r_i (left).
+ * Body forward is world +x at yaw 0.  Each of `substeps` sub-steps of length dt, on the pose (x, y, z; quaternion w, qx, qy, qz):
+ *   1. v = lin[e * cmd_stride] * max_lin,  w = ang[e * cmd_stride] * max_ang;  v_eff = |v / w| > 0.45f ? v : 0    (turn on the spot,
+ *      kinematics.py:34-39: w = 0 with v != 0 keeps v, v = w = 0 gives 0)
+ *   2. yaw0 = atan2(2 (w qz + qx qy), 1 - 2 (qy^2 + qz^2))   (the yaw of tensor_quat_to_eul: valid for a tilted body and for the reset
+ *      kernel's quaternion);   yaw1 = yaw0 + w dt,  c = cos(yaw1),  s = sin(yaw1)
+ *   3. x1 = x + (v_eff c) dt,   y1 = y + (v_eff s) dt
+ *   4. wheel contact i at ((x1 + f_i c) + r_i s, (y1 + f_i s) - r_i c);  z_i = the heightfield there, exactly as rover_sample_height
+ *      reads it (clamp, round half to even, lookup, times vertical_scale; option cell_index_mode applies)
+ *   5. the least-squares plane z = z_c + p a + q b through the six samples: (z_c, p, q) = C z with the constant C [3][6] =
+ *      pinv([1, a_i, b_i]) (rover_motion_plane_fit), each row summed from i = 0 upwards
+ *   6. pitch = -atan(p),  roll = atan(q cos(pitch)) — the one roll for which the body's y axis lies in the plane —, yaw = yaw1, turned
+ *      into a quaternion by the ZYX formula on the half angles:  w = (cr cp) cy + (sr sp) sy,  qx = (sr cp) cy - (cr sp) sy,
+ *      qy = (cr sp) cy + (sr cp) sy,  qz = (cr cp) sy - (sr sp) cy;   tensor_quat_to_eul of it is (roll, pitch, yaw1) up to rounding
+ *      and the wrap of yaw
+ *   7. z1 = z_c + ride_height
+ * pos3 and quat4 are updated IN PLACE (the step kernels borrow the same pointers); between sub-steps the pose stays in registers, and
+ * `substeps` = n gives the bits of n calls with `substeps` = 1.  After the last sub-step, where the joint quadruple is given, all 13
+ * columns are copied: joint_pos13 <- joint_pos_targets13, joint_vel13 <- joint_vel_targets13 (ideal actuators).
+ * One launch of ceil(E / 256) workgroups (csrc/rover_motion.hip), plain vector loads and stores, no atomics, no LDS.  The call
+ * allocates nothing, does not synchronise and can be captured in a graph.  E = 0: ROVER_OK, no launch.
+ * ROVER_E_INVALID before any launch (the descriptor is checked before the ctx is looked at, as for rover_obs_noise): a NULL descriptor;
+ * E < 0; substeps < 1; cmd_stride < 1; dt not finite or not > 0; a NULL pos3, quat4, lin or ang with E > 0; a joint quadruple given
+ * only in part.  ROVER_E_STATE: no heightfield (rover_set_heightfield). */
+typedef struct {
+    float *pos3, *quat4;                           /* [E, 3], [E, 4] (w, x, y, z): read and written in place                       */
+    const float *lin, *ang;                        /* env e's commands at [e * cmd_stride]                                         */
+    int32_t cmd_stride, E, substeps;               /* cmd_stride 3: column 0 of the task's [E, 3] histories, newest first          */
+    float dt, max_lin, max_ang, ride_height;
+    const float *joint_pos_targets13, *joint_vel_targets13;      /* optional [E, 13]: all four or none                              */
+    float *joint_pos13, *joint_vel13;
+} rover_motion_desc;
+ROVER_API int rover_motion_step(rover_ctx *ctx, const rover_motion_desc *d, void *stream);
+/* Host only (no ctx, no device): the 18 floats of C, row-major (z_c's row, p's, q's), computed in double and rounded to f32 once. */
+ROVER_API int rover_motion_plane_fit(float out[18]);
+
 /* ---- tuning knobs ------------------------------------------------------------------------------------- */
 /* name = "raycast_variant": 0 = auto; 1 = one half-wave per ray in env order, every cell block streamed from HBM;
  *        2 = rays counting-sorted by (map, cell), one wave per run of sorted rays, the cell's triangles held in registers

@@ -134,6 +134,12 @@ class ObsNoiseDesc(C.Structure):
                 ("row_offset", C.c_int64)]
 
 
+class MotionDesc(C.Structure):
+    _fields_ = [("pos3", C.c_void_p), ("quat4", C.c_void_p), ("lin", C.c_void_p), ("ang", C.c_void_p), ("cmd_stride", C.c_int32), ("E", C.c_int32),
+                ("substeps", C.c_int32), ("dt", C.c_float), ("max_lin", C.c_float), ("max_ang", C.c_float), ("ride_height", C.c_float),
+                ("joint_pos_targets13", C.c_void_p), ("joint_vel_targets13", C.c_void_p), ("joint_pos13", C.c_void_p), ("joint_vel13", C.c_void_p)]
+
+
 REDUCTIONS = {"sum": 0, "mean": 1, "prod": 2, "max": 3, "min": 4, None: 5, "none": 5}
 
 
@@ -230,6 +236,8 @@ SYMBOLS = {
     "rover_linear_dgrad_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
     "rover_obs_noise": (C.c_int, [_P, C.POINTER(ObsNoiseDesc), _P]),
     "rover_obs_noise_threshold": (C.c_int, [C.c_double, _P]),
+    "rover_motion_step": (C.c_int, [_P, C.POINTER(MotionDesc), _P]),
+    "rover_motion_plane_fit": (C.c_int, [_P]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
     "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
     "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -380,6 +388,24 @@ def obs_noise_threshold(dropout):
     if rc != 0:
         raise RoverError(f"rover_obs_noise_threshold failed ({rc}): {lib.rover_last_error(None).decode()}")
     return int(out.value)
+
+
+def motion_desc(e, pos3=_FAKE, quat4=_FAKE, lin=_FAKE, ang=_FAKE, cmd_stride=3, substeps=1, dt=0.05, max_lin=1.0, max_ang=1.0, ride_height=0.3,
+                joint_pos_targets13=None, joint_vel_targets13=None, joint_pos13=None, joint_vel13=None):
+    """A rover_motion_desc from plain values (pointers as integers)."""
+    return MotionDesc(pos3, quat4, lin, ang, int(cmd_stride), int(e), int(substeps), float(dt), float(max_lin), float(max_ang), float(ride_height),
+                      joint_pos_targets13, joint_vel_targets13, joint_pos13, joint_vel13)
+
+
+def motion_plane_fit():
+    """rover_motion_plane_fit: the constant C [3, 6] of the motion model's plane fit, (z_c, p, q) = C z over the six wheel contacts
+    (FL, FR, ML, MR, RL, RR) -> a float32 array.  Host only."""
+    out = np.empty((3, 6), dtype=np.float32)
+    lib = load()
+    rc = lib.rover_motion_plane_fit(out.ctypes.data)
+    if rc != 0:
+        raise RoverError(f"rover_motion_plane_fit failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return out
 
 
 PRECISIONS = ("f32", "bf16")
@@ -882,6 +908,36 @@ class Engine:
                               dp(row_scale), dp(episode), seed, step, dp(step_dev), row_offset)
         self._check(self.lib.rover_obs_noise(self._h, C.byref(desc), _stream(self._dev_index)), "rover_obs_noise")
         return out
+
+    def motion_step(self, pos, quat, lin, ang, *, dt, substeps=1, max_lin=1.0, max_ang=1.0, ride_height=0.3, joints=None):
+        """``substeps`` sub-steps of length ``dt`` of the terrain-following motion model on ``pos`` [e, 3] and ``quat`` [e, 4] (w, x, y, z),
+        IN PLACE (rover_motion_step, one launch; needs set_heightfield): the commands ``lin`` / ``ang`` [e] scaled by ``max_lin`` /
+        ``max_ang`` move the body, the six wheel contacts' terrain heights give z, roll and pitch.  ``lin`` and ``ang`` may be one column
+        of a wider matrix (``tracker[:, 0]``): their common stride is passed on.  ``joints``: None, or (joint_pos_targets, joint_vel_targets,
+        joint_pos, joint_vel), each [e, 13] — after the last sub-step the state becomes the targets."""
+        what = "motion_step"
+        e = pos.shape[0] if pos is not None and pos.dim() == 2 else -1
+        self._chk(pos, (e, 3), torch.float32, "pos")
+        self._chk(quat, (e, 4), torch.float32, "quat")
+        if pos is None or quat is None or e < 0:
+            raise RoverError(f"{what}: pos [e, 3] and quat [e, 4] must be given")
+        for t, name in ((lin, "lin"), (ang, "ang")):
+            if t is None or not t.is_cuda or t.device != self.device or t.dtype != torch.float32 or tuple(t.shape) != (e,):
+                raise RoverError(f"{what}: {name} must be a float32 vector [{e}] on {self.device}")
+        stride = 1 if e <= 1 else lin.stride(0)
+        if e > 1 and (stride < 1 or ang.stride(0) != stride):
+            raise RoverError(f"{what}: lin and ang must have the same positive stride (got {lin.stride(0)} and {ang.stride(0)})")
+        jp = [None] * 4
+        if joints is not None:
+            if len(joints) != 4:
+                raise RoverError(f"{what}: joints = (joint_pos_targets, joint_vel_targets, joint_pos, joint_vel)")
+            for t, name in zip(joints, ("joint_pos_targets", "joint_vel_targets", "joint_pos", "joint_vel")):
+                if t is None:
+                    raise RoverError(f"{what}: {name} is missing")
+                self._chk(t, (e, 13), torch.float32, name)
+            jp = [t.data_ptr() for t in joints]
+        desc = motion_desc(e, pos.data_ptr(), quat.data_ptr(), lin.data_ptr(), ang.data_ptr(), stride, substeps, dt, max_lin, max_ang, ride_height, *jp)
+        self._check(self.lib.rover_motion_step(self._h, C.byref(desc), _stream(self._dev_index)), "rover_motion_step")
 
     chain_act_route = staticmethod(chain_act_route)
     bf16_round = staticmethod(bf16_round)

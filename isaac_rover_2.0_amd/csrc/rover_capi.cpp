@@ -2234,6 +2234,41 @@ int rover_obs_noise_threshold(double dropout, uint32_t* thr) {
     return ROVER_OK;
 }
 
+// The descriptor is validated before the ctx is looked at, as for rover_obs_noise
+int rover_motion_step(rover_ctx* c, const rover_motion_desc* d, void* stream) {
+    if (!d) return fail(c, ROVER_E_INVALID, "motion_step: null descriptor");
+    if (d->E < 0 || d->substeps < 1 || d->cmd_stride < 1)
+        return fail(c, ROVER_E_INVALID, "motion_step: E = %d is negative, substeps = %d or cmd_stride = %d is below 1", d->E, d->substeps, d->cmd_stride);
+    if (!std::isfinite(d->dt) || !(d->dt > 0.0f)) return fail(c, ROVER_E_INVALID, "motion_step: dt = %g is not finite or not > 0", (double)d->dt);
+    if (d->E > 0 && (!d->pos3 || !d->quat4 || !d->lin || !d->ang)) return fail(c, ROVER_E_INVALID, "motion_step: pos3, quat4, lin and ang must be given");
+    const int n_joint = (d->joint_pos_targets13 != nullptr) + (d->joint_vel_targets13 != nullptr) + (d->joint_pos13 != nullptr) + (d->joint_vel13 != nullptr);
+    if (n_joint != 0 && n_joint != 4)
+        return fail(c, ROVER_E_INVALID, "motion_step: joint_pos_targets13, joint_vel_targets13, joint_pos13 and joint_vel13 go together (%d of 4 given)", n_joint);
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "motion_step: null ctx");
+    if (!c->have_hf) return fail(c, ROVER_E_STATE, "motion_step: rover_set_heightfield first");
+    if (d->E == 0) return ROVER_OK;
+    USE_DEVICE(c);
+    MotionArgs a{};
+    a.h = c->hf;
+    a.pos3 = d->pos3; a.quat4 = d->quat4; a.lin = d->lin; a.ang = d->ang;
+    a.cmd_stride = d->cmd_stride; a.E = (uint32_t)d->E; a.substeps = d->substeps;
+    a.dt = d->dt; a.max_lin = d->max_lin; a.max_ang = d->max_ang; a.ride_height = d->ride_height;
+    motion_plane_fit(a.fit);
+    a.joint_pos_targets13 = d->joint_pos_targets13; a.joint_vel_targets13 = d->joint_vel_targets13;
+    a.joint_pos13 = d->joint_pos13; a.joint_vel13 = d->joint_vel13;
+    HIP_TRY(c, launch_motion(a, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+// Host only: the constant of the motion model's plane fit
+int rover_motion_plane_fit(float out[18]) {
+    if (!out) return fail(nullptr, ROVER_E_INVALID, "motion_plane_fit: null argument");
+    float fit[3][MOTION_WHEELS];
+    motion_plane_fit(fit);
+    memcpy(out, fit, sizeof fit);
+    return ROVER_OK;
+}
+
 int rover_set_option(rover_ctx* c, const char* name, int64_t value) {
     if (!c || !name) return ROVER_E_INVALID;
     USE_DEVICE(c);                                 // some options (re)allocate device workspace

@@ -332,6 +332,24 @@ struct ObsNoiseArgs {
 };
 hipError_t launch_obs_noise(const ObsNoiseArgs& a, hipStream_t s);
 
+// The terrain-following motion model (rover_motion_step of the C ABI, validated; rover_motion.hip): `substeps` sub-steps of length dt on
+// the poses in place, one thread per env, then the optional copy of the joint targets into the joint state.
+#define MOTION_WHEELS 6
+struct MotionArgs {
+    HeightDev h;
+    float *pos3, *quat4;                   // [E, 3], [E, 4] (w, x, y, z): read and written in place
+    const float *lin, *ang;                // the env's commands at [e * cmd_stride]
+    int32_t cmd_stride;
+    uint32_t E;
+    int32_t substeps;
+    float dt, max_lin, max_ang, ride_height;
+    float fit[3][MOTION_WHEELS];           // motion_plane_fit(): (z_c, p, q) = fit . z
+    const float *joint_pos_targets13, *joint_vel_targets13;      // all four given, or all four NULL
+    float *joint_pos13, *joint_vel13;
+};
+void motion_plane_fit(float out[3][MOTION_WHEELS]);       // host, double arithmetic rounded to f32 once: pinv([1, a_i, b_i])
+hipError_t launch_motion(const MotionArgs& a, hipStream_t s);
+
 // Generalised advantage estimation over a stored rollout (rover_gae of the C ABI, validated; rover_rollout.hip): rows are time steps at
 // a stride in elements, the env stride is 1.
 enum GaeNormalize { GAE_RAW = 0, GAE_NORMALIZE = 1, GAE_NORMALIZE_GIVEN = 2 };

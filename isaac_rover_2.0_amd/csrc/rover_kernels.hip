@@ -35,6 +35,7 @@
 #include "rover_internal.h"
 #include "rover_philox.h"
 #include "rover_raymath.h"
+#include "rover_height.h"      // cell_coord, height_at
 
 namespace rover {
 
@@ -100,19 +101,6 @@ __device__ __forceinline__ void wheel_chain(float x, float y, float z, const flo
     float y2 = t1[1] + y1 * csx + z1 * ssx;
     float z2 = t1[2] + x1 * ssy + csy * c1;
     body_xf(x2, y2, z2, t, px, py, pz, ox, oy, oz);
-}
-
-// camera.py:241-253: clamp bound is the dim-0 size for both axes; torch.round is half-to-even.
-// `/ horizontal_scale` (a Python float): ATen's CPU kernel divides (rcp = 0, what the golden vectors pin); ATen's CUDA
-// kernel multiplies by 1 / scale rounded to f32 (rcp = 1, option cell_index_mode) — they differ next to .5 ties only.
-__device__ __forceinline__ uint32_t cell_coord(float v, float shift, float cell, float inv_cell, int32_t rcp, int32_t dim0) {
-    float s = rcp ? (v - shift) * inv_cell : (v - shift) / cell;
-    float hi = (float)(dim0 - 1);
-    s = (s < 0.0f) ? 0.0f : s;
-    s = (s > hi) ? hi : s;
-    s = rintf(s);
-    if (!(s == s)) return 0u;          // NaN pose: the reference raises; map to cell 0 (all tests then miss)
-    return (uint32_t)s;
 }
 
 // The ray's normal-cone bound for the culled ray cast (rover_cull.hip), a 16-bit fraction rounded up, 0xffff = none; (dx, dy, dz) = the
@@ -921,13 +909,6 @@ __device__ __forceinline__ void goal_from_draw(float u, float radius, const floa
     float gx = radius * cosf(alpha) + 0.0f, gy = radius * sinf(alpha) + 0.0f;   // :560-561
     x = gx + initial_pos3[3ull * id];                                       // :563-564
     y = gy + initial_pos3[3ull * id + 1];
-}
-
-__device__ __forceinline__ float height_at(const HeightDev& h, float x, float y) {
-    uint32_t ix = cell_coord(x, h.shift_x, h.hscale, h.inv_hscale, h.rcp, h.N0);
-    uint32_t iy = cell_coord(y, h.shift_y, h.hscale, h.inv_hscale, h.rcp, h.N0);
-    if (iy > (uint32_t)(h.N1 - 1)) iy = (uint32_t)(h.N1 - 1);
-    return h.hm[(uint64_t)ix * h.N1 + iy] * h.vscale;
 }
 
 // GOAL_LANES lanes share one entry and test GOAL_LANES consecutive draws at once (the first clear one wins, exactly what the

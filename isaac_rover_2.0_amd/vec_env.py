@@ -5,7 +5,9 @@ Mirrors the contract of omni.isaac.gym's ``VecEnvBase`` as the reference uses it
 ``(obs, rew, dones, info)`` with ``task.pre_physics_step`` before and ``task.post_physics_step`` after the
 physics sub-steps, observations clipped to ``clip_obs`` and actions to ``clip_actions``.
 PhysX is replaced by ``KinematicSim``: a toy unicycle integrator that moves each rover along the commanded
-(linear, angular) velocity and keeps it on the heightfield — a pose FEEDER, not a simulator.
+(linear, angular) velocity and keeps it on the heightfield — a pose FEEDER, not a simulator.  ``VecEnv(sim="terrain")`` selects
+``TerrainSim`` instead: the terrain-following motion model of ``rover_motion_step``, one HIP launch per control step,
+which also tilts the body with the ground under its six wheels, obeys Ackermann's turn-on-the-spot rule and writes the joint state.
 """
 from __future__ import annotations
 
@@ -38,8 +40,38 @@ class KinematicSim:
         quat[:, 3] = torch.sin(yaw / 2)
 
 
+class TerrainSim:
+    """``KinematicSim``'s interface on the terrain-following motion model (``Engine.motion_step``): the rover poses are advanced in place
+    on the task's engine and heightfield, and the joint state follows the joint targets (ideal actuators).  ``advance(n)`` folds ``n``
+    sub-steps of length ``dt`` into one launch; ``step`` is ``advance(1)``."""
+
+    def __init__(self, task, dt: float = 0.05, max_lin: float = 1.0, max_ang: float = 1.0, ride_height: float = 0.3):
+        self.task, self.dt, self.max_lin, self.max_ang, self.ride_height = task, dt, max_lin, max_ang, ride_height
+        self._playing = True
+
+    def is_playing(self):
+        return self._playing
+
+    def step(self, render: bool = False):
+        self.advance(1)
+
+    def advance(self, n: int = 1):
+        t = self.task
+        r = t._rover
+        pos, quat = r.get_world_poses()
+        t._engine.motion_step(pos, quat, t.linear_velocity.get_state(0), t.angular_velocity.get_state(0), dt=self.dt, substeps=n,
+                              max_lin=self.max_lin, max_ang=self.max_ang, ride_height=self.ride_height,
+                              joints=(r._joint_pos_targets, r._joint_vel_targets, r.get_joint_positions(), r.get_joint_velocities()))
+
+
+SIMS = {"kinematic": KinematicSim, "terrain": TerrainSim}
+
+
 class VecEnv:
-    def __init__(self, headless: bool = True, sim_device: int = 0):
+    def __init__(self, headless: bool = True, sim_device: int = 0, sim: str = "kinematic"):
+        if sim not in SIMS:
+            raise ValueError(f"sim must be one of {tuple(SIMS)}, not {sim!r}")
+        self._sim = sim
         self._render = not headless
         self._task = None
         self._world = None
@@ -47,7 +79,7 @@ class VecEnv:
     def set_task(self, task, backend="torch", sim_params=None, init_sim=True, spawn_positions=None) -> None:
         self._task = task
         task._env = self
-        self._world = KinematicSim(task, dt=(sim_params or {}).get("dt", 0.05))
+        self._world = SIMS[self._sim](task, dt=(sim_params or {}).get("dt", 0.05))
         task.set_up_scene(spawn_positions=spawn_positions)
         task.post_reset()
         self.num_envs = task.num_envs
@@ -64,8 +96,12 @@ class VecEnv:
         task = self._task
         actions = torch.clamp(actions, -task.clip_actions, task.clip_actions).to(task.device)
         task.pre_physics_step(actions)
-        for _ in range(task.control_frequency_inv):
-            self._world.step(render=False)
+        advance = getattr(self._world, "advance", None)
+        if advance is not None:
+            advance(task.control_frequency_inv)
+        else:
+            for _ in range(task.control_frequency_inv):
+                self._world.step(render=False)
         obs, rew, resets, extras = task.post_physics_step()
         obs = torch.clamp(obs, -task.clip_obs, task.clip_obs)
         return obs, rew, resets, extras

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Times the two pose feeders of vec_env on the GPU: TerrainSim.advance(1) (one rover_motion_step launch) against KinematicSim.step()
+(about fifteen torch ops and a height lookup), both as VecEnv's world object would call them, on the same task (EXPERIMENTS.md §22).
+
+    python tools/motion_timing.py [--envs 512 4096 65536] [--reps 30] [--feeders kinematic terrain] [--json out.json]
+
+Per size one task is built (synthetic scene, 37-ray distribution), stepped a few times with random actions so that the histories, the
+joint targets and the poses are those of a rollout, and then each feeder is called in windows of --inner calls between two device
+events; the windows of the two feeders alternate, so that a drift of the machine meets both.  A figure is the time of one call inside
+such a window — enqueue cost included where the host is the limit, as in a rollout —: median (min .. max) over --reps windows.
+"terrain_graph" is the same window of TerrainSim calls captured once in a graph and replayed: the device's share of a call, with no
+enqueue cost.  --feeders kinematic alone runs on a tree without TerrainSim.  Needs a GPU; there is no fallback."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from isaac_rover_amd import _lib, config, synth, vec_env  # noqa: E402
+from isaac_rover_amd.tasks.rover import RoverTask  # noqa: E402
+
+
+def window(fn, inner):
+    """-> microseconds per call over one event-bracketed window of ``inner`` calls."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(inner):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / inner
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, nargs="+", default=[512, 4096, 65536])
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--inner", type=int, default=200, help="calls per window")
+    ap.add_argument("--feeders", nargs="+", choices=("kinematic", "terrain"), default=["kinematic", "terrain"])
+    ap.add_argument("--json", default="")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("motion_timing: needs a GPU")
+    scene = synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
+    extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size
+    result = {"version": _lib.version(), "inner": args.inner, "reps": args.reps, "sizes": {}}
+    for e in args.envs:
+        env = vec_env.VecEnv(headless=True)
+        task = RoverTask("Rover", config.SimConfig(num_envs=e, device="cuda:0"), env, scene=scene, distribution=synth.ray_distribution("37"))
+        g = torch.Generator().manual_seed(0)
+        spawn = torch.zeros(e, 3)
+        spawn[:, 0:2] = 0.15 * extent + 0.7 * extent * torch.rand(e, 2, generator=g)
+        env.set_task(task, sim_params={"dt": 0.05}, spawn_positions=spawn)
+        env.reset()
+        for _ in range(5):
+            env.step(2 * torch.rand(e, 2, device=task.device) - 1)
+        worlds = {"kinematic": lambda: vec_env.KinematicSim(task, dt=0.05), "terrain": lambda: vec_env.TerrainSim(task, dt=0.05)}
+        calls = {}
+        for name in args.feeders:
+            w = worlds[name]()
+            calls[name] = (lambda w=w: w.advance(1)) if name == "terrain" else (lambda w=w: w.step(render=False))
+        pos, quat = task._rover.get_world_poses()
+        start = (pos.clone(), quat.clone())
+        if "terrain" in calls:
+            for _ in range(3):
+                calls["terrain"]()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for _ in range(args.inner):
+                    calls["terrain"]()
+        samples = {name: [] for name in calls}
+        for name, fn in calls.items():                               # warm-up: every op's code object loaded
+            for _ in range(10):
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(args.reps):
+            for name, fn in calls.items():
+                pos.copy_(start[0]), quat.copy_(start[1])            # every window starts from the same poses
+                torch.cuda.synchronize()
+                samples[name].append(window(fn, args.inner))
+            if "terrain" in calls:
+                pos.copy_(start[0]), quat.copy_(start[1])
+                torch.cuda.synchronize()
+                samples.setdefault("terrain_graph", []).append(window(graph.replay, 1) / args.inner)
+        rec = {name: (statistics.median(v), min(v), max(v)) for name, v in samples.items()}
+        result["sizes"][str(e)] = rec
+        print(f"--- {e} envs (us per call: median (min .. max); {args.inner} calls per window, {args.reps} windows, alternating)")
+        for name, (med, lo, hi) in rec.items():
+            print(f"{name:14s} {med:10.2f} ({lo:.2f} .. {hi:.2f})")
+        env.close()
+        del task, env
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(result, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
