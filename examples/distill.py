@@ -47,9 +47,16 @@ def main():
     ap.add_argument("--sim", choices=("kinematic", "terrain"), default="kinematic",
                     help="what moves the rovers between two steps: vec_env.KinematicSim, a flat unicycle, or TerrainSim, the terrain-following "
                          "motion model (one rover_motion_step launch per control step: tilt from the ground under the wheels, joint state)")
+    ap.add_argument("--track-interval", type=int, default=0,
+                    help="every N env steps print the episode statistics kept on the device (learning/tracking.py:EpisodeTracker, one "
+                         "rover_episode_track call per step, one read per N steps): skrl's nine Reward / Episode tags, the interval's exact "
+                         "episode figures and the means of the eight reward components; 0 = off")
+    ap.add_argument("--track-window", type=int, default=100, help="how many of the last finished episodes the Total reward / Total timesteps tags cover (skrl: 100)")
     args = ap.parse_args()
     if args.window < 1 or args.updates < 1:
         ap.error("--window and --updates need values >= 1")
+    if args.track_interval < 0 or not 1 <= args.track_window <= 1024:
+        ap.error("--track-interval N needs N >= 0, --track-window W needs W in 1 .. 1024")
 
     scene = synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
     cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
@@ -86,6 +93,10 @@ def main():
         print(f"perception: rover_obs_noise, sigma_point {args.noise} sigma_offset {args.obs_offset} dropout {args.obs_dropout}")
     else:
         noise_gen = torch.Generator(device=task.device).manual_seed(2)
+    tracker = None
+    if args.track_interval:
+        from isaac_rover_amd.learning.tracking import EpisodeTracker
+        tracker = EpisodeTracker.for_task(task, window=args.track_window)
     h, done = None, torch.zeros(e, dtype=torch.bool, device=task.device)
     for u in range(args.updates):
         for t in range(t_len):
@@ -97,7 +108,11 @@ def main():
             clean[:, t] = obs[:, f - ex:]
             wanted[:, t] = actions
             reset[:, t] = done                                                     # an env that just ended starts from a zero hidden state
-            obs, _, done, _ = env.step(actions)
+            obs, rew, done, info = env.step(actions)
+            if tracker is not None:
+                tracker.step(rew, done, info)                                      # two launches, nothing read back
+                if (u * t_len + t + 1) % args.track_interval == 0:
+                    print(f"step {u * t_len + t + 1}: {tracker.read().line()}")
             done = done.bool().clone()
         if noise is None:
             x[:, :, f - ex:] += args.noise * torch.randn(e, t_len, ex, device=task.device, generator=noise_gen)

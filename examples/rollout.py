@@ -48,7 +48,14 @@ def main():
     ap.add_argument("--sim", choices=("kinematic", "terrain"), default="kinematic",
                     help="what moves the rovers between two steps: vec_env.KinematicSim, a flat unicycle, or TerrainSim, the terrain-following "
                          "motion model (one rover_motion_step launch per control step: tilt from the ground under the wheels, joint state)")
+    ap.add_argument("--track-interval", type=int, default=0,
+                    help="every N steps print the episode statistics kept on the device (learning/tracking.py:EpisodeTracker, one "
+                         "rover_episode_track call per step, one read per N steps): skrl's nine Reward / Episode tags, the interval's exact "
+                         "episode figures and the means of the eight reward components; 0 = off")
+    ap.add_argument("--track-window", type=int, default=100, help="how many of the last finished episodes the Total reward / Total timesteps tags cover (skrl: 100)")
     args = ap.parse_args()
+    if args.track_interval < 0 or not 1 <= args.track_window <= 1024:
+        ap.error("--track-interval N needs N >= 0, --track-window W needs W in 1 .. 1024")
     noisy = bool(args.obs_noise or args.obs_offset or args.obs_dropout)
     if noisy and args.policy == "random":
         ap.error("--obs-noise / --obs-offset / --obs-dropout need --policy actor or student")
@@ -67,6 +74,10 @@ def main():
     env.set_task(task, sim_params={"dt": 0.05}, spawn_positions=spawn)          # utils/task_util.py:45
     obs = env.reset()
     print(f"obs {tuple(obs.shape)}  actions {task.num_actions}  device {task.device}")
+    tracker = None
+    if args.track_interval:
+        from isaac_rover_amd.learning.tracking import EpisodeTracker
+        tracker = EpisodeTracker.for_task(task, window=args.track_window)
     agent = None
     if args.policy == "actor":
         from isaac_rover_amd.learning.model import StochasticActorHeightmap
@@ -107,7 +118,7 @@ def main():
     episodes = 0
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for step in range(args.steps):
         seen = obs if noise is None else noise.apply(obs, reset=done)              # what the policy sees; the task keeps the clean obs
         if student is not None:
             actions = student.act(seen, reset=None if done is None else done.bool())  # an env that just ended starts from a zero hidden state
@@ -119,6 +130,10 @@ def main():
             values, _, _ = critic.act(obs)
             states = obs.clone()                                                   # env.step() rewrites the observation buffer
         obs, rew, done, info = env.step(actions)
+        if tracker is not None:
+            tracker.step(rew, done, info)                                          # two launches, nothing read back
+            if (step + 1) % args.track_interval == 0:
+                print(f"step {step + 1}: {tracker.read().line()}")
         if memory is not None:
             memory.add_samples(states=states, actions=actions, log_prob=log_prob, values=values, rewards=rew, terminated=done.bool())
             if memory.memory_index == 0:                                           # full: returns and advantages of these N steps

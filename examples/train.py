@@ -40,7 +40,14 @@ def main():
     ap.add_argument("--sim", choices=("kinematic", "terrain"), default="kinematic",
                     help="what moves the rovers between two steps: vec_env.KinematicSim, a flat unicycle, or TerrainSim, the terrain-following "
                          "motion model (one rover_motion_step launch per control step: tilt from the ground under the wheels, joint state)")
+    ap.add_argument("--track-interval", type=int, default=0,
+                    help="every N steps print the episode statistics kept on the device (learning/tracking.py:EpisodeTracker, one "
+                         "rover_episode_track call per step, one read per N steps): skrl's nine Reward / Episode tags, the interval's exact "
+                         "episode figures and the means of the eight reward components; 0 = off")
+    ap.add_argument("--track-window", type=int, default=100, help="how many of the last finished episodes the Total reward / Total timesteps tags cover (skrl: 100)")
     args = ap.parse_args()
+    if args.track_interval < 0 or not 1 <= args.track_window <= 1024:
+        ap.error("--track-interval N needs N >= 0, --track-window W needs W in 1 .. 1024")
     if args.rollouts < 1:
         ap.error("--rollouts N needs N >= 1")
 
@@ -59,6 +66,10 @@ def main():
     env.set_task(task, sim_params={"dt": 0.05}, spawn_positions=spawn)          # utils/task_util.py:45
     obs = env.reset()
     print(f"obs {tuple(obs.shape)}  actions {task.num_actions}  device {task.device}")
+    tracker = None
+    if args.track_interval:
+        from isaac_rover_amd.learning.tracking import EpisodeTracker
+        tracker = EpisodeTracker.for_task(task, window=args.track_window)
     agent = StochasticActorHeightmap(task._engine, task, precision=args.rollout_precision)
     if args.checkpoint:
         sd = torch.load(args.checkpoint, map_location="cpu")
@@ -72,11 +83,15 @@ def main():
     ppo = PPO(task._engine, agent, critic, memory, {"learning_epochs": args.epochs, "mini_batches": args.mini_batches, "kl_threshold": args.kl_threshold},
               generator=torch.Generator().manual_seed(0), native_step=args.native_step, kl_stop=args.kl_stop)
     updates = 0
-    for _ in range(args.steps):
+    for step in range(args.steps):
         actions, log_prob, _ = agent.act(obs)
         values, _, _ = critic.act(obs)
         states = obs.clone()                                                       # env.step() rewrites the observation buffer
         obs, rew, done, info = env.step(actions)
+        if tracker is not None:
+            tracker.step(rew, done, info)                                          # two launches, nothing read back
+            if (step + 1) % args.track_interval == 0:
+                print(f"step {step + 1}: {tracker.read().line()}")
         memory.add_samples(states=states, actions=actions, log_prob=log_prob, values=values, rewards=rew, terminated=done.bool())
         if memory.memory_index == 0:                                               # full: one PPO update on these N steps
             last_values, _, _ = critic.act(obs)

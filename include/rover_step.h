@@ -860,6 +860,82 @@ ROVER_API int rover_motion_step(rover_ctx *ctx, const rover_motion_desc *d, void
 /* Host only (no ctx, no device): the 18 floats of C, row-major (z_c's row, p's, q's), computed in double and rounded to f32 once. */
 ROVER_API int rover_motion_plane_fit(float out[18]);
 
+/* ---- episode statistics on the device (learning/tracking.py:EpisodeTracker) ----------------------------------------------------------- */
+/* What skrl's agent writes every write_interval steps (instantaneous reward, total reward and length of the episodes in a deque of the
+ * last W, each as max / min / mean), the exact totals of a reporting interval and the sums of up to 16 reward components, kept on the
+ * device: one call per env step, at most two launches, no host read.  All state is the caller's device memory; the library keeps none.
+ *
+ * Inputs of one call: rewards [E] f32 (finite by contract); done [E] with elements of done_size = 1 byte (bool / uint8) or 8 bytes
+ * (int64, the task's reset_buf), non-zero = the episode ended with this step; K component columns, each [E] of kind ROVER_TRACK_F32 or
+ * ROVER_TRACK_I64, every element converted to f64 (one rounding for |i64| > 2^53) before it is summed.
+ * State: per env cum_reward [E] f32 and cum_steps [E] i32; the window ring_ret [W] f32, ring_len [W] i32, ring_count (one i64: the
+ * episodes ever appended); the interval record (rover_track_record below).  A fresh record is all zero except the minima, which hold
+ * +inf / INT32_MAX, and the maxima, which hold -inf / INT32_MIN: a constant the caller writes.
+ * One call, in this order:
+ *   1. per env:  c = cum_reward[e] + rewards[e]  (one f32 add),  n = cum_steps[e] + 1;  done[e]: (c, n) is a finished episode and
+ *      cum_reward[e] = 0, cum_steps[e] = 0;  otherwise cum_reward[e] = c, cum_steps[e] = n
+ *   2. ring:  this call's finished episodes, in ascending env order, are appended: entry j goes to slot (ring_count + j) mod W (only
+ *      the last min(n_finished, W) of them are written); then ring_count += n_finished
+ *   3. record:  calls += 1;  inst_min / inst_max / inst_sum take every rewards[e];  ep_count += n_finished and the ep_* fields take every
+ *      finished (c, n) (ep_ret_sumsq the f64 product c c, which is exact);  comp_sum[k] takes every element of column k;  and if
+ *      ring_count > 0:  win_calls += 1, win_ret_mean_sum += (the f64 sum of the min(ring_count, W) valid slots) / their number,
+ *      win_ret_min / win_ret_max take the ring's min / max, and the same three for the lengths (their sum is an exact integer)
+ * Arithmetic: every f32 value (cum_reward, ring entries, each min / max) and every integer is exact — a restatement in float32 gives the
+ * same bits (tests/track_ref.py); in a minimum or maximum -0 orders below +0.  The f64 sums are formed in a fixed order that depends on
+ * E, W and K alone: the same inputs give the same bits on every run.  No floating-point atomics, no atomics at all.
+ * Launches (csrc/rover_track.hip): an update kernel of ceil(E / 256) workgroups (step 1, the workgroup's finished pairs compacted in env
+ * order into the scratch, one partial record per workgroup) and a one-workgroup merge kernel (steps 2 and 3); E = 0 launches the merge
+ * kernel alone and is a counted call with no envs: calls += 1, the inst_*, ep_* and comp_sum fields stay, the win_* fields take the
+ * ring as in every call.  The call allocates nothing, does not synchronise and can be captured in a graph.
+ * ROVER_E_INVALID before any launch (the descriptor is checked before the ctx is looked at, as for rover_motion_step): a NULL
+ * descriptor; E < 0; W outside 1 .. 1024; K outside 0 .. 16; done_size other than 1 or 8; a comp_kind below K other than the two kinds;
+ * a NULL ring_ret, ring_len, ring_count or record; with E > 0 a NULL rewards, done, cum_reward, cum_steps or scratch, or a NULL comp
+ * below K; scratch_bytes below what rover_track_sizes reports. */
+#define ROVER_TRACK_MAX_COMPONENTS 16
+#define ROVER_TRACK_MAX_WINDOW 1024
+#define ROVER_TRACK_F32 0
+#define ROVER_TRACK_I64 1
+typedef struct {
+    int64_t calls;
+    double inst_sum;                               /* over every env of every call                                                 */
+    int64_t ep_count;
+    double ep_ret_sum, ep_ret_sumsq;
+    int64_t ep_len_sum;
+    int64_t win_calls;                             /* the calls at whose end the ring was not empty                                */
+    double win_ret_mean_sum, win_len_mean_sum;     /* over those calls, the ring's mean return / length                            */
+    double comp_sum[ROVER_TRACK_MAX_COMPONENTS];   /* over every env of every call                                                 */
+    float inst_min, inst_max;
+    float ep_ret_min, ep_ret_max;
+    int32_t ep_len_min, ep_len_max;
+    float win_ret_min, win_ret_max;                /* over those calls, the ring's min / max                                       */
+    int32_t win_len_min, win_len_max;
+} rover_track_record;                              /* 240 bytes */
+typedef struct {
+    const float *rewards;                          /* [E]                                                                          */
+    const void *done;                              /* [E] elements of done_size bytes                                              */
+    int32_t done_size, E, W, K;
+    const void *comp[ROVER_TRACK_MAX_COMPONENTS];  /* K columns [E]                                                                */
+    int32_t comp_kind[ROVER_TRACK_MAX_COMPONENTS];
+    float *cum_reward;                             /* [E]                                                                          */
+    int32_t *cum_steps;                            /* [E]                                                                          */
+    float *ring_ret;                               /* [W]                                                                          */
+    int32_t *ring_len;                             /* [W]                                                                          */
+    int64_t *ring_count;
+    rover_track_record *record;
+    void *scratch;                                 /* scratch_bytes of rover_track_sizes, 8-byte aligned; only this call's         */
+    int64_t scratch_bytes;
+} rover_track_desc;
+typedef struct {
+    int32_t workgroup;                             /* envs per update workgroup (256)                                              */
+    int32_t n_partials;                            /* ceil(E / workgroup)                                                          */
+    int64_t partial_bytes;                         /* one workgroup's partial record                                               */
+    int64_t finished_slots;                        /* n_partials * workgroup (return, length) pairs of 8 bytes                     */
+    int64_t scratch_bytes;                         /* n_partials * partial_bytes + 8 * finished_slots                              */
+} rover_track_sizes_out;
+ROVER_API int rover_episode_track(rover_ctx *ctx, const rover_track_desc *d, void *stream);
+/* Host only (no ctx, no device).  ROVER_E_INVALID: a NULL out, E < 0, W outside 1 .. 1024, K outside 0 .. 16. */
+ROVER_API int rover_track_sizes(int32_t E, int32_t W, int32_t K, rover_track_sizes_out *out);
+
 /* ---- tuning knobs ------------------------------------------------------------------------------------- */
 /* name = "raycast_variant": 0 = auto; 1 = one half-wave per ray in env order, every cell block streamed from HBM;
  *        2 = rays counting-sorted by (map, cell), one wave per run of sorted rays, the cell's triangles held in registers

@@ -140,6 +140,31 @@ class MotionDesc(C.Structure):
                 ("joint_pos_targets13", C.c_void_p), ("joint_vel_targets13", C.c_void_p), ("joint_pos13", C.c_void_p), ("joint_vel13", C.c_void_p)]
 
 
+TRACK_MAX_COMPONENTS, TRACK_MAX_WINDOW = 16, 1024
+TRACK_F32, TRACK_I64 = 0, 1
+
+
+class TrackRecord(C.Structure):
+    """rover_track_record: the interval record of rover_episode_track (240 bytes, fixed layout)."""
+    _fields_ = [("calls", C.c_int64), ("inst_sum", C.c_double), ("ep_count", C.c_int64), ("ep_ret_sum", C.c_double), ("ep_ret_sumsq", C.c_double),
+                ("ep_len_sum", C.c_int64), ("win_calls", C.c_int64), ("win_ret_mean_sum", C.c_double), ("win_len_mean_sum", C.c_double),
+                ("comp_sum", C.c_double * TRACK_MAX_COMPONENTS), ("inst_min", C.c_float), ("inst_max", C.c_float), ("ep_ret_min", C.c_float),
+                ("ep_ret_max", C.c_float), ("ep_len_min", C.c_int32), ("ep_len_max", C.c_int32), ("win_ret_min", C.c_float),
+                ("win_ret_max", C.c_float), ("win_len_min", C.c_int32), ("win_len_max", C.c_int32)]
+
+
+class TrackDesc(C.Structure):
+    _fields_ = [("rewards", C.c_void_p), ("done", C.c_void_p), ("done_size", C.c_int32), ("E", C.c_int32), ("W", C.c_int32), ("K", C.c_int32),
+                ("comp", C.c_void_p * TRACK_MAX_COMPONENTS), ("comp_kind", C.c_int32 * TRACK_MAX_COMPONENTS), ("cum_reward", C.c_void_p),
+                ("cum_steps", C.c_void_p), ("ring_ret", C.c_void_p), ("ring_len", C.c_void_p), ("ring_count", C.c_void_p), ("record", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
+
+
+class TrackSizes(C.Structure):
+    _fields_ = [("workgroup", C.c_int32), ("n_partials", C.c_int32), ("partial_bytes", C.c_int64), ("finished_slots", C.c_int64),
+                ("scratch_bytes", C.c_int64)]
+
+
 REDUCTIONS = {"sum": 0, "mean": 1, "prod": 2, "max": 3, "min": 4, None: 5, "none": 5}
 
 
@@ -238,6 +263,8 @@ SYMBOLS = {
     "rover_obs_noise_threshold": (C.c_int, [C.c_double, _P]),
     "rover_motion_step": (C.c_int, [_P, C.POINTER(MotionDesc), _P]),
     "rover_motion_plane_fit": (C.c_int, [_P]),
+    "rover_episode_track": (C.c_int, [_P, C.POINTER(TrackDesc), _P]),
+    "rover_track_sizes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(TrackSizes)]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
     "rover_eval_clear": (C.c_int, [_P, _P, C.c_int32, _P]),
     "rover_eval_read": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -406,6 +433,43 @@ def motion_plane_fit():
     if rc != 0:
         raise RoverError(f"rover_motion_plane_fit failed ({rc}): {lib.rover_last_error(None).decode()}")
     return out
+
+
+def track_sizes(e, w=100, k=0):
+    """rover_track_sizes: what rover_episode_track needs for ``e`` envs as a dict (workgroup, n_partials, partial_bytes, finished_slots,
+    scratch_bytes).  Host only."""
+    out = TrackSizes()
+    lib = load()
+    rc = lib.rover_track_sizes(int(e), int(w), int(k), C.byref(out))
+    if rc != 0:
+        raise RoverError(f"rover_track_sizes failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return {name: int(getattr(out, name)) for name, _ in TrackSizes._fields_}
+
+
+def track_desc(e, w=100, comps=(), rewards=_FAKE, done=_FAKE, done_size=1, cum_reward=_FAKE, cum_steps=_FAKE, ring_ret=_FAKE, ring_len=_FAKE,
+               ring_count=_FAKE, record=_FAKE, scratch=_FAKE, scratch_bytes=None, k=None):
+    """A rover_track_desc from plain values (pointers as integers).  ``comps``: (pointer, kind) pairs; ``k`` overrides their number;
+    ``scratch_bytes`` defaults to what rover_track_sizes reports for ``e``."""
+    d = TrackDesc()
+    d.rewards, d.done, d.done_size, d.E, d.W = rewards, done, int(done_size), int(e), int(w)
+    d.K = len(comps) if k is None else int(k)
+    for i, (ptr, kind) in enumerate(comps):
+        d.comp[i], d.comp_kind[i] = ptr, int(kind)
+    d.cum_reward, d.cum_steps, d.ring_ret, d.ring_len, d.ring_count, d.record, d.scratch = cum_reward, cum_steps, ring_ret, ring_len, ring_count, record, scratch
+    if scratch_bytes is None:
+        scratch_bytes = track_sizes(e, 1, 0)["scratch_bytes"] if e >= 0 else 0
+    d.scratch_bytes = int(scratch_bytes)
+    return d
+
+
+def track_fresh_record():
+    """The interval record before its first call: zeros, minima at +inf / INT32_MAX, maxima at -inf / INT32_MIN."""
+    r = TrackRecord()
+    r.inst_min = r.ep_ret_min = r.win_ret_min = float("inf")
+    r.inst_max = r.ep_ret_max = r.win_ret_max = float("-inf")
+    r.ep_len_min = r.win_len_min = 2 ** 31 - 1
+    r.ep_len_max = r.win_len_max = -2 ** 31
+    return r
 
 
 PRECISIONS = ("f32", "bf16")
@@ -938,6 +1002,47 @@ class Engine:
             jp = [t.data_ptr() for t in joints]
         desc = motion_desc(e, pos.data_ptr(), quat.data_ptr(), lin.data_ptr(), ang.data_ptr(), stride, substeps, dt, max_lin, max_ang, ride_height, *jp)
         self._check(self.lib.rover_motion_step(self._h, C.byref(desc), _stream(self._dev_index)), "rover_motion_step")
+
+    def episode_track(self, rewards, done, *, cum_reward, cum_steps, ring_ret, ring_len, ring_count, record, scratch, components=(), desc=None):
+        """One env step of the episode statistics (rover_episode_track: two launches, no host read, capturable): ``rewards`` [e] float32
+        and ``done`` [e] (bool, uint8 or int64) are folded into the per-env state ``cum_reward`` [e] float32 / ``cum_steps`` [e] int32, the
+        window ``ring_ret`` [w] float32 / ``ring_len`` [w] int32 / ``ring_count`` [1] int64 and the interval ``record`` (uint8
+        [sizeof(TrackRecord)], a _lib.track_fresh_record() before its first call); ``components``: up to 16 float32 or int64 vectors [e]
+        whose sums the record keeps; ``scratch``: uint8, at least track_sizes(e)["scratch_bytes"].  Returns the descriptor; passed back as
+        ``desc`` with the same tensors it skips the checks (the tensors must then be the ones it was built from)."""
+        what = "episode_track"
+        if desc is None:
+            if rewards is None or rewards.dim() != 1:
+                raise RoverError(f"{what}: rewards must be a float32 vector")
+            e, w = rewards.shape[0], (ring_ret.shape[0] if ring_ret is not None and ring_ret.dim() == 1 else -1)
+            self._chk(rewards, (e,), torch.float32, "rewards")
+            if done is None or done.dtype not in (torch.bool, torch.uint8, torch.int64):
+                raise RoverError(f"{what}: done must be a bool, uint8 or int64 vector [{e}]")
+            self._chk(done, (e,), done.dtype, "done")
+            if not 1 <= w <= TRACK_MAX_WINDOW:
+                raise RoverError(f"{what}: ring_ret must be a float32 vector of 1 .. {TRACK_MAX_WINDOW} slots")
+            if len(components) > TRACK_MAX_COMPONENTS:
+                raise RoverError(f"{what}: {len(components)} components, at most {TRACK_MAX_COMPONENTS}")
+            for t, shape, dtype, name in ((cum_reward, (e,), torch.float32, "cum_reward"), (cum_steps, (e,), torch.int32, "cum_steps"),
+                                          (ring_ret, (w,), torch.float32, "ring_ret"), (ring_len, (w,), torch.int32, "ring_len"),
+                                          (ring_count, (1,), torch.int64, "ring_count"), (record, (C.sizeof(TrackRecord),), torch.uint8, "record")):
+                if t is None:
+                    raise RoverError(f"{what}: {name} is missing")
+                self._chk(t, shape, dtype, name)
+            comps = []
+            for i, t in enumerate(components):
+                if t is None or t.dtype not in (torch.float32, torch.int64):
+                    raise RoverError(f"{what}: component {i} must be a float32 or int64 vector [{e}]")
+                self._chk(t, (e,), t.dtype, f"component {i}")
+                comps.append((t.data_ptr(), TRACK_I64 if t.dtype == torch.int64 else TRACK_F32))
+            need = track_sizes(e, w, len(comps))["scratch_bytes"]
+            if scratch is None or scratch.dim() != 1 or scratch.numel() < need:
+                raise RoverError(f"{what}: scratch must be a uint8 vector of at least {need} bytes")
+            self._chk(scratch, (scratch.numel(),), torch.uint8, "scratch")
+            desc = track_desc(e, w, comps, rewards.data_ptr(), done.data_ptr(), done.element_size(), cum_reward.data_ptr(), cum_steps.data_ptr(),
+                              ring_ret.data_ptr(), ring_len.data_ptr(), ring_count.data_ptr(), record.data_ptr(), scratch.data_ptr(), scratch.numel())
+        self._check(self.lib.rover_episode_track(self._h, C.byref(desc), _stream(self._dev_index)), "rover_episode_track")
+        return desc
 
     chain_act_route = staticmethod(chain_act_route)
     bf16_round = staticmethod(bf16_round)

@@ -2269,6 +2269,62 @@ int rover_motion_plane_fit(float out[18]) {
     return ROVER_OK;
 }
 
+static bool track_shape_ok(int32_t E, int32_t W, int32_t K) {
+    return E >= 0 && W >= 1 && W <= ROVER_TRACK_MAX_WINDOW && K >= 0 && K <= ROVER_TRACK_MAX_COMPONENTS;
+}
+
+// Host only: what the descriptor's scratch must cover
+int rover_track_sizes(int32_t E, int32_t W, int32_t K, rover_track_sizes_out* out) {
+    if (!out) return fail(nullptr, ROVER_E_INVALID, "track_sizes: null argument");
+    if (!track_shape_ok(E, W, K))
+        return fail(nullptr, ROVER_E_INVALID, "track_sizes: E = %d is negative, W = %d is outside 1 .. %d or K = %d is outside 0 .. %d", E, W,
+                    ROVER_TRACK_MAX_WINDOW, K, ROVER_TRACK_MAX_COMPONENTS);
+    out->workgroup = TRACK_BLOCK;
+    out->n_partials = (int32_t)track_partials((uint32_t)E);
+    out->partial_bytes = (int64_t)track_partial_bytes();
+    out->finished_slots = (int64_t)out->n_partials * TRACK_BLOCK;
+    out->scratch_bytes = (int64_t)track_scratch_bytes((uint32_t)E);
+    return ROVER_OK;
+}
+
+// The descriptor is validated before the ctx is looked at, as for rover_motion_step
+int rover_episode_track(rover_ctx* c, const rover_track_desc* d, void* stream) {
+    if (!d) return fail(c, ROVER_E_INVALID, "episode_track: null descriptor");
+    if (!track_shape_ok(d->E, d->W, d->K))
+        return fail(c, ROVER_E_INVALID, "episode_track: E = %d is negative, W = %d is outside 1 .. %d or K = %d is outside 0 .. %d", d->E, d->W,
+                    ROVER_TRACK_MAX_WINDOW, d->K, ROVER_TRACK_MAX_COMPONENTS);
+    if (d->done_size != 1 && d->done_size != 8) return fail(c, ROVER_E_INVALID, "episode_track: done_size = %d is neither 1 nor 8", d->done_size);
+    for (int32_t k = 0; k < d->K; ++k)
+        if (d->comp_kind[k] != ROVER_TRACK_F32 && d->comp_kind[k] != ROVER_TRACK_I64)
+            return fail(c, ROVER_E_INVALID, "episode_track: comp_kind[%d] = %d is neither ROVER_TRACK_F32 nor ROVER_TRACK_I64", k, d->comp_kind[k]);
+    if (!d->ring_ret || !d->ring_len || !d->ring_count || !d->record)
+        return fail(c, ROVER_E_INVALID, "episode_track: ring_ret, ring_len, ring_count and record must be given");
+    if (d->E > 0) {
+        if (!d->rewards || !d->done || !d->cum_reward || !d->cum_steps || !d->scratch)
+            return fail(c, ROVER_E_INVALID, "episode_track: rewards, done, cum_reward, cum_steps and scratch must be given");
+        for (int32_t k = 0; k < d->K; ++k)
+            if (!d->comp[k]) return fail(c, ROVER_E_INVALID, "episode_track: comp[%d] is NULL (K = %d)", k, d->K);
+        if (((uintptr_t)d->scratch & 7u) != 0) return fail(c, ROVER_E_INVALID, "episode_track: scratch is not 8-byte aligned");
+        if (d->scratch_bytes < (int64_t)track_scratch_bytes((uint32_t)d->E))
+            return fail(c, ROVER_E_INVALID, "episode_track: scratch_bytes = %lld is below the %llu of rover_track_sizes", (long long)d->scratch_bytes,
+                        (unsigned long long)track_scratch_bytes((uint32_t)d->E));
+    }
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "episode_track: null ctx");
+    USE_DEVICE(c);
+    TrackArgs a{};
+    a.rewards = d->rewards; a.done = d->done; a.done8 = d->done_size == 8;
+    a.E = (uint32_t)d->E; a.W = (uint32_t)d->W; a.K = (uint32_t)d->K;
+    for (int32_t k = 0; k < d->K; ++k) {
+        a.comp[k] = d->comp[k];
+        if (d->comp_kind[k] == ROVER_TRACK_I64) a.comp_i64 |= 1u << k;
+    }
+    a.cum_reward = d->cum_reward; a.cum_steps = d->cum_steps;
+    a.ring_ret = d->ring_ret; a.ring_len = d->ring_len; a.ring_count = d->ring_count;
+    a.record = d->record; a.scratch = d->scratch;
+    HIP_TRY(c, launch_track(a, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
 int rover_set_option(rover_ctx* c, const char* name, int64_t value) {
     if (!c || !name) return ROVER_E_INVALID;
     USE_DEVICE(c);                                 // some options (re)allocate device workspace

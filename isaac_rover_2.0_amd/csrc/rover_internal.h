@@ -350,6 +350,30 @@ struct MotionArgs {
 void motion_plane_fit(float out[3][MOTION_WHEELS]);       // host, double arithmetic rounded to f32 once: pinv([1, a_i, b_i])
 hipError_t launch_motion(const MotionArgs& a, hipStream_t s);
 
+// Episode statistics (rover_episode_track of the C ABI, validated; rover_track.hip): one env step's rewards, done flags and component
+// columns folded into the per-env state, the window ring and the interval record; the definition is in include/rover_step.h.
+#define TRACK_BLOCK 256
+#define TRACK_MAX_COMP 16
+struct TrackArgs {
+    const float* rewards;                  // [E]
+    const void* done;                      // [E] of 1 or 8 bytes
+    int32_t done8;                         // 1: int64 flags
+    uint32_t E, W, K;
+    const void* comp[TRACK_MAX_COMP];      // K columns [E]
+    uint32_t comp_i64;                     // bit k: column k is int64 (else f32)
+    float* cum_reward;
+    int32_t* cum_steps;
+    float* ring_ret;
+    int32_t* ring_len;
+    int64_t* ring_count;
+    void* record;                          // rover_track_record
+    void* scratch;                         // track_scratch_bytes(E), 8-byte aligned: the partials, then the finished returns, then the lengths
+};
+uint32_t track_partial_bytes();
+static inline uint32_t track_partials(uint32_t E) { return (uint32_t)(((uint64_t)E + TRACK_BLOCK - 1) / TRACK_BLOCK); }
+static inline uint64_t track_scratch_bytes(uint32_t E) { return (uint64_t)track_partials(E) * ((uint64_t)track_partial_bytes() + 8ull * TRACK_BLOCK); }
+hipError_t launch_track(const TrackArgs& a, hipStream_t s);
+
 // Generalised advantage estimation over a stored rollout (rover_gae of the C ABI, validated; rover_rollout.hip): rows are time steps at
 // a stride in elements, the env stride is 1.
 enum GaeNormalize { GAE_RAW = 0, GAE_NORMALIZE = 1, GAE_NORMALIZE_GIVEN = 2 };
