@@ -273,7 +273,8 @@ ROVER_API int rover_eval_read(rover_ctx *ctx, int64_t *eval_res, int64_t *eval_s
  * triangles [T,3] int32 (host or device pointers); map_idx_out [X,Y,K] int32 is a DEVICE pointer.  Ranking is exact f32
  * squared distance with ties broken by triangle id; the reference ranks fp16-rounded distances with torch.topk (ties
  * unspecified), so its maps agree with this one only up to that rounding.  Synchronous (init-time tool); needs no
- * prior set_* call.  Fails with ROVER_E_INVALID when T < K or a search ring holds more than 8192 candidates. */
+ * prior set_* call.  A vertex index outside [0, V) reads vertex 0; a triangle with a NaN centroid ranks after every other.
+ * Fails with ROVER_E_INVALID when T < K, K > 4096, a centroid is infinite, or a search ring holds more than 8192 candidates. */
 ROVER_API int rover_build_knn_map(rover_ctx *ctx, const float *vertices, int32_t V, const int32_t *triangles, int32_t T,
                                   int32_t X, int32_t Y, float res, int32_t K, int32_t *map_idx_out);
 

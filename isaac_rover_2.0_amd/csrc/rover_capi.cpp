@@ -1408,12 +1408,20 @@ static int build_knn_map_impl(rover_ctx* c, const float* vertices, int32_t V, co
     std::vector<float> hx((size_t)T), hy((size_t)T);
     KNN_TRY(hipMemcpy(hx.data(), d_cx.get(), d_cx.bytes(), hipMemcpyDeviceToHost));
     KNN_TRY(hipMemcpy(hy.data(), d_cy.get(), d_cy.bytes(), hipMemcpyDeviceToHost));
-    float x0 = hx[0], x1 = hx[0], y0 = hy[0], y1 = hy[0];
+    // (NaN centroids are left out of the box, the first triangle's included: they all land in bucket 0 and rank last)
+    float x0 = 0.0f, x1 = 0.0f, y0 = 0.0f, y1 = 0.0f;
+    bool any_x = false, any_y = false;
     for (int32_t t = 0; t < T; ++t) {
-        if (hx[t] == hx[t]) { x0 = hx[t] < x0 ? hx[t] : x0; x1 = hx[t] > x1 ? hx[t] : x1; }
-        if (hy[t] == hy[t]) { y0 = hy[t] < y0 ? hy[t] : y0; y1 = hy[t] > y1 ? hy[t] : y1; }
+        if (hx[t] == hx[t]) { x0 = (any_x && x0 < hx[t]) ? x0 : hx[t]; x1 = (any_x && x1 > hx[t]) ? x1 : hx[t]; any_x = true; }
+        if (hy[t] == hy[t]) { y0 = (any_y && y0 < hy[t]) ? y0 : hy[t]; y1 = (any_y && y1 > hy[t]) ? y1 : hy[t]; any_y = true; }
     }
+    // the largest |coordinate - origin| of any centroid or cell point: knn_select_kernel's stop slack is absolute in it
+    const double cell_x1 = (double)((float)(X - 1) * res), cell_y1 = (double)((float)(Y - 1) * res);
+    const float span = (float)std::max({(double)x1 - x0, (double)y1 - y0, std::fabs((double)x0), std::fabs(cell_x1 - x0), std::fabs((double)y0),
+                                        std::fabs(cell_y1 - y0)});
     const double area = ((double)x1 - x0 + 1e-6) * ((double)y1 - y0 + 1e-6);
+    // (an infinite centroid would make the bucket edge infinite or NaN, and the sizing below would never settle)
+    if (!std::isfinite(area)) return fail(c, ROVER_E_INVALID, "build_knn_map: the centroids' bounding box is not finite");
     double gsz = std::sqrt(area * (double)K / (4.0 * (double)T));
     if (gsz < (double)res) gsz = (double)res;
     // A cell's search gathers whole rings of buckets into LDS (8192 candidates at most).  On a strongly non-uniform mesh (a
@@ -1436,8 +1444,8 @@ static int build_knn_map_impl(rover_ctx* c, const float* vertices, int32_t V, co
         e2 = d_start.alloc((size_t)nb + 1);
         if (e2 == hipSuccess) e2 = hipMemcpy(d_start.get(), d_cur.get(), d_cur.bytes(), hipMemcpyDeviceToDevice);
         if (e2 == hipSuccess) e2 = launch_knn_bucket(d_cx.get(), d_cy.get(), (uint32_t)T, x0, y0, inv_g, nbx, nby, d_cur.get(), d_items.get(), 0, nullptr);
-        if (e2 == hipSuccess) e2 = launch_knn_select(d_cx.get(), d_cy.get(), d_start.get(), d_items.get(), x0, y0, g, nbx, nby, (uint32_t)X, (uint32_t)Y, res,
-                                                     (uint32_t)K, d_cell.get(), d_cell.get() ? d_cell.get() + X : nullptr, map_idx_out, d_over.get(), nullptr);
+        if (e2 == hipSuccess) e2 = launch_knn_select(d_cx.get(), d_cy.get(), d_start.get(), d_items.get(), x0, y0, g, span, nbx, nby, (uint32_t)X, (uint32_t)Y,
+                                                     res, (uint32_t)K, d_cell.get(), d_cell.get() ? d_cell.get() + X : nullptr, map_idx_out, d_over.get(), nullptr);
         if (e2 == hipSuccess) e2 = hipDeviceSynchronize();
         over = 0;
         if (e2 == hipSuccess) e2 = hipMemcpy(&over, d_over.get(), sizeof over, hipMemcpyDeviceToHost);

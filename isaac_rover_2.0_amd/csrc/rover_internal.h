@@ -519,8 +519,8 @@ hipError_t launch_knn_bucket(const float* cx, const float* cy, uint32_t T, float
                              uint32_t* cursor, uint32_t* items, int count, hipStream_t s);
 hipError_t launch_scan_exclusive(uint32_t* data, uint32_t n, uint32_t* block_sums, hipStream_t s);
 hipError_t launch_knn_select(const float* cx, const float* cy, const uint32_t* bucket_start, const uint32_t* items, float ox, float oy,
-                             float g, uint32_t nbx, uint32_t nby, uint32_t X, uint32_t Y, float res, uint32_t K, const float* cell_x,
-                             const float* cell_y, int32_t* out, int32_t* overflow, hipStream_t s);
+                             float g, float span, uint32_t nbx, uint32_t nby, uint32_t X, uint32_t Y, float res, uint32_t K,
+                             const float* cell_x, const float* cell_y, int32_t* out, int32_t* overflow, hipStream_t s);
 hipError_t launch_assemble_obs(const ObsArgs& a, hipStream_t s);
 hipError_t launch_export_dist(const float* dist, const RayRec* rays, uint32_t E, uint32_t R8, uint32_t P, int precision, float* ray_dist,
                               float* wheel, float* body, float* ray_src, float* hit_pt, hipStream_t s);

@@ -1549,6 +1549,7 @@ __global__ void __launch_bounds__(256) raycast_binned_kernel(const RayRec* __res
 // reference ranks fp16-rounded distances with an unspecified tie order, so it cannot be matched bit for bit).
 // ---------------------------------------------------------------------------------------------------
 #define KNN_CAP 8192
+#define KNN_STOP_SLACK 0x1p-20f          // knn_select_kernel's stop test; tests/knn_ref.py (STOP_SLACK) restates the value
 
 // ref = 1: the reference's own arithmetic — numpy float64 centroid of the (float64) open3d vertices (rover_utils.py:68-70),
 // then torch.tensor(..., dtype=float16) (:72), which converts double -> float -> half; kept here as the half's float value.
@@ -1589,7 +1590,7 @@ __global__ void __launch_bounds__(256) knn_bucket_kernel(const float* __restrict
 
 __global__ void __launch_bounds__(256) knn_select_kernel(const float* __restrict__ cx, const float* __restrict__ cy,
                                                          const uint32_t* __restrict__ bucket_start, const uint32_t* __restrict__ items,
-                                                         float ox, float oy, float g, uint32_t nbx, uint32_t nby, uint32_t X,
+                                                         float ox, float oy, float g, float span, uint32_t nbx, uint32_t nby, uint32_t X,
                                                          uint32_t Y, float res, uint32_t K, const float* __restrict__ cell_x,
                                                          const float* __restrict__ cell_y, int32_t* __restrict__ out,
                                                          int32_t* __restrict__ overflow) {
@@ -1650,12 +1651,23 @@ __global__ void __launch_bounds__(256) knn_select_kernel(const float* __restrict
                     __syncthreads();
                 }
             }
-            // every triangle not gathered yet is at least r*g away (its bucket is > r rings out)
-            // (reference ranking: an ungathered triangle is >= reach away in the fp16-rounded coordinates and its fp16 distance is
-            //  at most a factor 1 - 2^-9.9 below that, so a K-th key strictly below reach (1 - 2^-9) cannot be undercut or tied)
+            // Every triangle not gathered yet lies more than r buckets out along one axis.  In real numbers that puts it more than r*g
+            // away; in knn_bucket's float32 it does not quite ("KNN stop test").  With u = 2^-24, c the centroid's and p
+            // the cell's coordinate on that axis, o the origin and F(v) = fl(fl(v - o) * inv_g), which is monotone in v:
+            //   floor(F(c)) >= floor(F(p)) + r + 1 (the clamps of knn_bucket keep that)   =>   F(c) - F(p) > r
+            //   F(v) = (v - o) / g * (1 + e), |e| <= 3u + 3u^2: the subtraction, the product, and inv_g = fl(1 / g) (the same for both)
+            //   =>  c - p > r g (1 - u) - 4 (1 + u) u span,      span >= |c - o|, |p - o|  (the host passes it: the largest one there is)
+            //   d2 = fl(fl(dx dx) + fl(dy dy)) >= fl(dx dx) with dx = fl(c - p)   =>   d2 >= (c - p)^2 (1 - u)^3
+            // so d2 > (r g (1 - 2.5 u) - 4.1 u span)^2, while lim below is at most r g (1 - 13 u) - 15.9 u span and fl(lim lim) <=
+            // lim^2 (1 + u): a K-th key <= lim^2 is strictly below every ungathered key, ties included.  The slack has a part relative
+            // to the reach and a part absolute in span: a relative factor alone does not cover a mesh far from its cells.
+            // (reference ranking: an ungathered triangle is >= reach away in the fp16-rounded coordinates, up to the same few u span, and
+            //  its fp16 distance is at most a factor 1 - 2^-9.9 below that, so a K-th key strictly below reach (1 - 2^-9) cannot be
+            //  undercut or tied: tests/test_knn_ring_property.py holds both claims against the arithmetic)
             const float reach = (float)r * g;
+            const float lim = reach - (reach + span) * KNN_STOP_SLACK;
             const float kth = n >= K ? __uint_as_float((uint32_t)(keys[K - 1] >> 32)) : __builtin_inff();
-            if (covers_all || (ref ? kth < reach * (1.0f - 1.0f / 512.0f) : kth <= reach * reach)) {
+            if (covers_all || (ref ? kth < reach * (1.0f - 1.0f / 512.0f) : (lim > 0.0f && kth <= lim * lim))) {
                 for (uint32_t k = tid; k < K; k += 256) out[(uint64_t)cell * K + k] = k < n ? (int32_t)(uint32_t)keys[k] : 0;
                 return;
             }
@@ -1803,9 +1815,9 @@ hipError_t launch_scan_exclusive(uint32_t* data, uint32_t n, uint32_t* block_sum
 }
 
 hipError_t launch_knn_select(const float* cx, const float* cy, const uint32_t* bucket_start, const uint32_t* items, float ox, float oy,
-                             float g, uint32_t nbx, uint32_t nby, uint32_t X, uint32_t Y, float res, uint32_t K, const float* cell_x,
-                             const float* cell_y, int32_t* out, int32_t* overflow, hipStream_t s) {
-    hipLaunchKernelGGL(knn_select_kernel, dim3(X * Y), dim3(256), 0, s, cx, cy, bucket_start, items, ox, oy, g, nbx, nby, X, Y, res, K,
+                             float g, float span, uint32_t nbx, uint32_t nby, uint32_t X, uint32_t Y, float res, uint32_t K,
+                             const float* cell_x, const float* cell_y, int32_t* out, int32_t* overflow, hipStream_t s) {
+    hipLaunchKernelGGL(knn_select_kernel, dim3(X * Y), dim3(256), 0, s, cx, cy, bucket_start, items, ox, oy, g, span, nbx, nby, X, Y, res, K,
                        cell_x, cell_y, out, overflow);
     return hipGetLastError();
 }

@@ -1145,22 +1145,7 @@ def test_errors_are_loud():
         _lib.Engine(0, device=0)
 
 
-def _knn_brute_force(verts, tris, n_x, n_y, res, k):
-    """numpy restatement of rover_utils.py:68-108 with the builder's stated ranking (f32 squared distance, ties by id)."""
-    v = verts.astype(np.float32)
-    cx = (v[tris[:, 0], 0] + v[tris[:, 1], 0] + v[tris[:, 2], 0]) / np.float32(3)
-    cy = (v[tris[:, 0], 1] + v[tris[:, 1], 1] + v[tris[:, 2], 1]) / np.float32(3)
-    out = np.zeros((n_x, n_y, k), np.int32)
-    ids = np.arange(len(tris), dtype=np.uint64)
-    for x in range(n_x):
-        px = np.float32(x) * np.float32(res)
-        dx = cx - px
-        for y in range(n_y):
-            dy = cy - np.float32(y) * np.float32(res)
-            d2 = (dx * dx + dy * dy).astype(np.float32)
-            key = (d2.view(np.uint32).astype(np.uint64) << np.uint64(32)) | ids
-            out[x, y] = np.sort(key)[:k].astype(np.uint64) & np.uint64(0xffffffff)
-    return out
+from knn_ref import brute_force as _knn_brute_force      # rover_utils.py:68-108 with the builder's stated ranking (f32 squared distance, ties by id)
 
 
 @pytest.mark.parametrize("n_tri,n_x,n_y,k,res,extent", [(3000, 24, 20, 16, 0.1, 2.4), (900, 16, 16, 200, 0.1, 1.5),

@@ -176,15 +176,7 @@ def test_task_reset_idx_matches_reference():
 
 
 # --------------------------------------------------------------------------------------------------------------- f-3
-def _fp16_distances(verts, tris, cell_x, cell_y, i):
-    """The reference's distances for map row i (rover_utils.py:68-72,99-100): fp16 centroids (float64 mean -> float -> half),
-    fp16(c - p) per axis, norm in f32 rounded to fp16.  Returns [Y, T] fp16."""
-    v = verts.astype(np.float64)
-    cx = ((v[tris[:, 0], 0] + v[tris[:, 1], 0] + v[tris[:, 2], 0]) / 3).astype(np.float32).astype(np.float16).astype(np.float32)
-    cy = ((v[tris[:, 0], 1] + v[tris[:, 1], 1] + v[tris[:, 2], 1]) / 3).astype(np.float32).astype(np.float16).astype(np.float32)
-    dx = (cx - np.float32(cell_x[i])).astype(np.float16).astype(np.float32)
-    dy = (cy[None, :] - cell_y.astype(np.float32)[:, None]).astype(np.float16).astype(np.float32)
-    return np.sqrt(dx[None, :] * dx[None, :] + dy * dy).astype(np.float16)
+from knn_ref import fp16_distances as _fp16_distances     # the reference's distances for one map row (rover_utils.py:68-72,99-100)
 
 
 @pytest.mark.parametrize("kind", ["grid10m", "soup50m"])
