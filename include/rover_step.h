@@ -290,6 +290,41 @@ ROVER_API int rover_build_knn_map_ref(rover_ctx *ctx, const float *vertices, int
                                       int32_t X, int32_t Y, float res, int32_t K, const uint16_t *cell_x_f16,
                                       const uint16_t *cell_y_f16, int32_t *map_idx_out);
 
+/* ---- heightfield from a triangle mesh: what rover_set_heightfield takes, made from the mesh the rays hit ------------------------
+ * For every node of an N0 x N1 grid the highest point of the mesh above it.  vertices [V,3] float32 and triangles [T,3] int32 are host
+ * or device pointers; hm_out [N0][N1] float32 is a DEVICE pointer and holds metres (a scene built from it has vertical_scale 1); stats
+ * is a host pointer and may be NULL: {nodes no triangle covers, triangles skipped}.  Synchronous (init-time tool); needs no prior set_*
+ * call.  This is the project's own definition (the reference ships its heightfield as an asset, without a generator):
+ *
+ *  1. Node (i, j) sits at world (shift_x + i hs, shift_y + j hs), hs = horizontal_scale: the point whose lookup rover_sample_height
+ *     rounds to (i, j).  In sub-units, 256 per node spacing, its coordinates are (256 i, 256 j).
+ *  2. A vertex's xy is snapped once, in double: X = (int64) rint((((double) x - (double) shift_x) / (double) hs) * 256.0), in that
+ *     order (rint: to nearest, ties to even); Y likewise.  z stays the f32 value, read as a double.
+ *  3. A triangle is SKIPPED and counted in stats[1] when an index lies outside [0, V), when a coordinate (x, y or z) of one of its
+ *     vertices is not finite, or when a snapped |X| or |Y| exceeds 2^25 (that limit keeps every edge function within 2^53: exact in
+ *     int64 and exactly convertible to double).  A triangle with area = (bx - ax)(cy - ay) - (by - ay)(cx - ax) == 0 — a vertical
+ *     wall, a sliver snapped flat — contributes nothing and is not counted.
+ *  4. At node p = (px, py):  wa = (cx - bx)(py - by) - (cy - by)(px - bx),  wb = (ax - cx)(py - cy) - (ay - cy)(px - cx),
+ *     wc = (bx - ax)(py - ay) - (by - ay)(px - ax); where area < 0 all three and the area are negated.  The node is covered iff
+ *     wa >= 0 && wb >= 0 && wc >= 0: edges and vertices are inclusive, a shared edge belongs to both triangles.  All of it is integer
+ *     arithmetic, so coverage is exact, watertight and independent of any order.
+ *  5. z = (float)((((double) wa * za + (double) wb * zb) + (double) wc * zc) / (double) area): one IEEE rounding per operation (no
+ *     fused multiply-add), the correctly rounded f64 division, then one rounding to f32.
+ *  6. hm[i][j] is the maximum of z over the covering triangles — a rock on the terrain wins over the ground under it — in the IEEE
+ *     order with -0 below +0.  A node that no triangle covers gets `fill` and is counted in stats[0].
+ *
+ * The maximum is taken with an integer atomic on an order-preserving key of the f32 bits, so the result is the same bits on every run.
+ * The arguments are validated before the ctx is looked at (with a NULL ctx rover_last_error(NULL) has the text).  ROVER_E_INVALID: N0 or
+ * N1 outside 1 .. 131072, horizontal_scale not finite or <= 0, a shift not finite, V < 0, T < 0, vertices NULL with V > 0, triangles NULL
+ * with T > 0, hm_out NULL, a NULL ctx. */
+ROVER_API int rover_build_heightfield(rover_ctx *ctx, const float *vertices, int32_t V, const int32_t *triangles, int32_t T,
+                                      int32_t N0, int32_t N1, float horizontal_scale, float shift_x, float shift_y,
+                                      float fill, float *hm_out, int64_t stats[2]);
+/* Host only (no ctx, no device): the sizes that separate the rasteriser's code paths.  out[0]: the largest bounding box, in nodes
+ * (clipped to the grid), that a group of out[3] lanes rasterises on its own; a larger box is cut along the grid's multiples of
+ * out[1] (i) x out[2] (j) nodes into tiles, one workgroup each.  ROVER_E_INVALID for a NULL out. */
+ROVER_API int rover_heightfield_limits(int32_t out[4]);
+
 /* ---- policy-side consumer of the obs layout ("next" row f-4): learning/model.py:105-121 Layer = Linear + activation --- */
 #define ROVER_ACT_NONE      0
 #define ROVER_ACT_LEAKYRELU 1   /* nn.LeakyReLU(), slope 0.01 (cfg/trainSKRL/RoverPPOSKRL.yaml:5,9) */

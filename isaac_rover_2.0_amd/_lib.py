@@ -218,6 +218,8 @@ SYMBOLS = {
     "rover_replay_raycast": (C.c_int, [_P, _P]),
     "rover_build_knn_map": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
     "rover_build_knn_map_ref": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P]),
+    "rover_build_heightfield": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
+    "rover_heightfield_limits": (C.c_int, [_P]),
     "rover_linear_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "rover_mlp_chain_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rover_mlp_chain_pair_forward": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
@@ -433,6 +435,18 @@ def motion_plane_fit():
     if rc != 0:
         raise RoverError(f"rover_motion_plane_fit failed ({rc}): {lib.rover_last_error(None).decode()}")
     return out
+
+
+def heightfield_limits():
+    """rover_heightfield_limits: the sizes that separate the code paths of rover_build_heightfield as a dict — ``small_nodes``: the
+    largest bounding box (nodes, clipped to the grid) one lane group rasterises; larger boxes are cut at the grid's multiples of
+    ``tile_i`` x ``tile_j`` nodes, one workgroup per tile; ``group_lanes``: the lanes of a group.  Host only."""
+    out = (C.c_int32 * 4)()
+    lib = load()
+    rc = lib.rover_heightfield_limits(out)
+    if rc != 0:
+        raise RoverError(f"rover_heightfield_limits failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return {"small_nodes": int(out[0]), "tile_i": int(out[1]), "tile_j": int(out[2]), "group_lanes": int(out[3])}
 
 
 def track_sizes(e, w=100, k=0):
@@ -810,6 +824,28 @@ class Engine:
                                                      None if tabs[1] is None else tabs[1].ctypes.data, _ptr(out)),
                     "rover_build_knn_map_ref")
         return out
+
+    def build_heightfield(self, vertices, triangles, n0, n1, horizontal_scale=0.025, shift=(0.0, 0.0), fill=0.0):
+        """rover_build_heightfield: for every node (i, j) of an ``n0`` x ``n1`` grid at ``horizontal_scale`` metres, node (0, 0) at
+        ``shift``, the highest point of the mesh above it (the definition is in include/rover_step.h) -> (hm [n0, n1] float32 device
+        tensor in metres, nodes no triangle covers — they hold ``fill`` —, triangles skipped).  ``vertices`` [V, 3] / ``triangles`` [T, 3]:
+        anything numpy understands, or torch tensors; float32 / int32 contiguous tensors on this device are passed as they are."""
+        def arg(a, np_dtype, t_dtype):
+            if isinstance(a, torch.Tensor) and a.is_cuda and a.device == self.device and a.dtype == t_dtype and a.is_contiguous():
+                return a, a.data_ptr(), tuple(a.shape)
+            h = _host(a, np_dtype)
+            return h, h.ctypes.data, h.shape
+        v, v_ptr, v_shape = arg(vertices, np.float32, torch.float32)
+        t, t_ptr, t_shape = arg(triangles, np.int32, torch.int32)
+        if len(v_shape) != 2 or v_shape[1] != 3 or len(t_shape) != 2 or t_shape[1] != 3:
+            raise RoverError("build_heightfield: expected vertices [V,3] and triangles [T,3]")
+        n0, n1 = int(n0), int(n1)
+        out = torch.empty(max(n0, 0), max(n1, 0), dtype=torch.float32, device=self.device) if max(n0, n1) <= 131072 else None
+        stats = (C.c_int64 * 2)()
+        self._check(self.lib.rover_build_heightfield(self._h, v_ptr if v_shape[0] else None, v_shape[0], t_ptr if t_shape[0] else None, t_shape[0],
+                                                     n0, n1, float(horizontal_scale), float(shift[0]), float(shift[1]), float(fill),
+                                                     _ptr(out) if out is not None and out.numel() else None, stats), "rover_build_heightfield")
+        return out, int(stats[0]), int(stats[1])
 
     ACTIVATIONS = {"none": 0, None: 0, "leakyrelu": 1, "tanh": 2, "relu": 3, "elu": 4}
 

@@ -120,6 +120,19 @@ def load_ply(path: str):
         return verts, faces
 
 
+def save_ply(path: str, vertices, triangles) -> None:
+    """Writes a binary_little_endian PLY (float x y z, triangle faces as ``list uchar int``) that :func:`load_ply` reads back unchanged."""
+    v = np.ascontiguousarray(vertices, dtype="<f4").reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, dtype="<i4").reshape(-1, 3)
+    faces = np.empty(len(t), dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    faces["n"], faces["v"] = 3, t
+    with open(path, "wb") as f:
+        f.write((f"ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+                 f"element face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii"))
+        f.write(v.tobytes())
+        f.write(faces.tobytes())
+
+
 def build_knn_map(engine, vertices, triangles, n_cells: int = 600, res: float = 0.1, k: int = 200, ranking: str = "exact_f32",
                   cell_x_f16=None, cell_y_f16=None) -> KnnMap:
     """``_get_knn_triangles`` (rover_utils.py:52-123) on the GPU: K nearest triangle centroids per map cell, returned in
@@ -163,3 +176,91 @@ def build_irregular_scene(engine, spec, k: int = 200, ranking: str = "exact_f32"
     n_x, n_y = int(round(spec.extent_x / 0.1)), int(round(spec.extent_y / 0.1))
     maps = [engine.build_knn_map(verts, t, n_x, n_y, 0.1, k, ranking=ranking).cpu() for t in (tris, rock_tris)]
     return synth.make_irregular_scene(spec, k, maps[0], maps[1])
+
+
+# ---------------------------------------------------------------------------------------------------------
+# a whole scene from the two meshes: heightfield (rover_build_heightfield) and stone list on top of the two KNN maps
+# ---------------------------------------------------------------------------------------------------------
+def stones_from_mesh(vertices, triangles) -> np.ndarray:
+    """The content of ``stone_info.npy`` from the rocks-only mesh (``big_stones.ply``) -> [S, 6] float64, host numpy.
+
+    This is the project's OWN definition (the reference ships ``stone_info.npy`` as an asset, without a generator): a stone is a connected
+    component of the mesh, triangles being joined through vertices with identical (x, y, z) — so a vertex stored twice still joins its
+    triangles.  Row = [bbox centre x, bbox centre y, min z, 2 width_x, 2 width_y, height] over the component's vertices, rows sorted by
+    (x, y).  ``read_stone_info`` consumes it unchanged: its radius max(row[3], row[4]) / 4 is half the larger footprint width.
+    A triangle with an index outside the vertex table is left out; vertices no triangle uses make no stone."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    t = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+    t = t[((t >= 0) & (t < len(v))).all(axis=1)]
+    if len(t) == 0:
+        return np.zeros((0, 6), dtype=np.float64)
+    _, rep = np.unique(v, axis=0, return_inverse=True)             # vertices with the same coordinates share a representative
+    rep = rep.reshape(-1)
+    parent = np.arange(rep.max() + 1)
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    for a, b, c in rep[t]:
+        ra, rb, rc = find(a), find(b), find(c)
+        m = min(ra, rb, rc)
+        parent[ra] = parent[rb] = parent[rc] = m
+    used = np.unique(t)
+    root = np.asarray([find(a) for a in rep[used]])
+    rows = []
+    for r in np.unique(root):
+        p = v[used[root == r]]
+        lo, hi = p.min(axis=0), p.max(axis=0)
+        rows.append([(lo[0] + hi[0]) / 2.0, (lo[1] + hi[1]) / 2.0, lo[2], 2.0 * (hi[0] - lo[0]), 2.0 * (hi[1] - lo[1]), hi[2] - lo[2]])
+    rows = np.asarray(rows, dtype=np.float64)
+    return rows[np.lexsort((rows[:, 1], rows[:, 0]))]
+
+
+def build_scene_from_meshes(engine, terrain_mesh, rocks_mesh, n_cells: int = 600, res: float = 0.1, k: int = 200,
+                            horizontal_scale: float = 0.025, shift=(0.0, 0.0, 0.0), ranking: str = "exact_f32", fill=None,
+                            return_stats: bool = False):
+    """A Scene from ``terrain_mesh`` = (vertices, triangles) of ``map.ply`` (terrain with rocks) and ``rocks_mesh`` of ``big_stones.ply``.
+
+    Both KNN maps come from :func:`build_knn_map`.  The heightfield — round(n_cells res / horizontal_scale) nodes per side, in metres
+    (vertical_scale 1) — is rasterised by ``rover_build_heightfield`` from the terrain mesh's fp16-ROUNDED vertices (``KnnMap.vertices``
+    back in float32): the surface the rays hit, so the rover stands on what it observes.  ``fill`` (the height of a node no triangle
+    covers): None = the lowest finite vertex z.  The stones are :func:`stones_from_mesh` of the rocks mesh.  ``shift`` is the Scene's:
+    node (0, 0) of the heightfield sits at (shift[0], shift[1]); the KNN builder itself places cell (0, 0) at the mesh's origin.
+    ``return_stats``: -> (Scene, uncovered nodes, skipped triangles)."""
+    tv, tt = terrain_mesh
+    rv, rt = rocks_mesh
+    terrain = build_knn_map(engine, tv, tt, n_cells=n_cells, res=res, k=k, ranking=ranking)
+    rocks = build_knn_map(engine, rv, rt, n_cells=n_cells, res=res, k=k, ranking=ranking)
+    out = _scene_on_maps(engine, terrain, rocks, rocks_mesh, n_cells, res, horizontal_scale, shift, fill)
+    return out if return_stats else out[0]
+
+
+def _scene_on_maps(engine, terrain: KnnMap, rocks: KnnMap, rocks_mesh, n_cells, res, horizontal_scale, shift, fill):
+    """The heightfield and the stones on top of two finished KNN maps -> (Scene, uncovered nodes, skipped triangles)."""
+    v32 = terrain.vertices.to(torch.float32).numpy()
+    if fill is None:
+        z = v32[:, 2]
+        z = z[np.isfinite(z)]
+        fill = float(z.min()) if z.size else 0.0
+    n = int(round(n_cells * res / horizontal_scale))
+    hm, uncovered, skipped = engine.build_heightfield(v32, terrain.triangles.numpy(), n, n, horizontal_scale, (shift[0], shift[1]), fill)
+    scene = Scene(terrain=terrain, rocks=rocks, stone_info_raw=stones_from_mesh(*rocks_mesh), heightmap=hm.cpu(),
+                  horizontal_scale=horizontal_scale, vertical_scale=1.0, shift=tuple(float(s) for s in shift))
+    return scene, uncovered, skipped
+
+
+def generate_scene_files(engine, terrain_dir: str, n_cells: int = 600, res: float = 0.1, k: int = 200, horizontal_scale: float = 0.025,
+                         ranking: str = "exact_f32", fill=None):
+    """Everything a Scene needs, from ``map.ply`` and ``big_stones.ply`` in ``terrain_dir``: writes ``knn_terrain/``, ``knn_rocks/``
+    (by :func:`generate_knn_triangles`), ``heightmap_tensor.pt`` (float32 [N, N], metres) and ``stone_info.npy`` ([S, 6] float64) next to
+    them — the layout :func:`load_reference_assets` reads when ``terrain_dir`` is ``<root>/tasks/utils/terrain``.
+    -> (Scene, uncovered nodes, skipped triangles)."""
+    maps = generate_knn_triangles(engine, terrain_dir, n_cells, n_cells, res, k, ranking=ranking)
+    scene, uncovered, skipped = _scene_on_maps(engine, maps["knn_terrain"], maps["knn_rocks"], load_ply(os.path.join(terrain_dir, "big_stones.ply")),
+                                               n_cells, res, horizontal_scale, (0.0, 0.0, 0.0), fill)
+    torch.save(scene.heightmap, os.path.join(terrain_dir, "heightmap_tensor.pt"))
+    np.save(os.path.join(terrain_dir, "stone_info.npy"), scene.stone_info_raw)
+    return scene, uncovered, skipped

@@ -1457,6 +1457,79 @@ static int build_knn_map_impl(rover_ctx* c, const float* vertices, int32_t V, co
     return ROVER_OK;
 }
 
+// Host only: the sizes that separate the rasteriser's routes
+int rover_heightfield_limits(int32_t out[4]) {
+    if (!out) return fail(nullptr, ROVER_E_INVALID, "heightfield_limits: null argument");
+    out[0] = RASTER_SMALL_NODES; out[1] = RASTER_TILE_I; out[2] = RASTER_TILE_J; out[3] = RASTER_GROUP;
+    return ROVER_OK;
+}
+
+// The arguments are validated before the ctx is looked at, as for rover_motion_step
+int rover_build_heightfield(rover_ctx* c, const float* vertices, int32_t V, const int32_t* triangles, int32_t T, int32_t N0, int32_t N1,
+                            float horizontal_scale, float shift_x, float shift_y, float fill, float* hm_out, int64_t stats[2]) {
+    if (N0 < 1 || N1 < 1 || N0 > RASTER_MAX_NODES || N1 > RASTER_MAX_NODES)
+        return fail(c, ROVER_E_INVALID, "build_heightfield: N0 = %d or N1 = %d is outside 1 .. %d", N0, N1, RASTER_MAX_NODES);
+    if (!std::isfinite(horizontal_scale) || !(horizontal_scale > 0.0f))
+        return fail(c, ROVER_E_INVALID, "build_heightfield: horizontal_scale = %g is not finite or not > 0", (double)horizontal_scale);
+    if (!std::isfinite(shift_x) || !std::isfinite(shift_y))
+        return fail(c, ROVER_E_INVALID, "build_heightfield: shift = (%g, %g) is not finite", (double)shift_x, (double)shift_y);
+    if (V < 0 || T < 0) return fail(c, ROVER_E_INVALID, "build_heightfield: V = %d or T = %d is negative", V, T);
+    if ((V > 0 && !vertices) || (T > 0 && !triangles) || !hm_out)
+        return fail(c, ROVER_E_INVALID, "build_heightfield: vertices, triangles and hm_out must be given");
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "build_heightfield: null ctx");
+    USE_DEVICE(c);
+#define HF_TRY(expr)                                                                                          \
+    do {                                                                                                      \
+        hipError_t e__ = (expr);                                                                              \
+        if (e__ != hipSuccess) return fail(c, ROVER_E_HIP, "build_heightfield: %s: %s", #expr, hipGetErrorString(e__)); \
+    } while (0)
+    DevBuf<float> d_v;
+    DevBuf<int32_t> d_t;
+    DevBuf<uint4> d_snap;
+    DevBuf<uint32_t> d_large, d_tiles;
+    DevBuf<unsigned long long> d_counts;            // {uncovered, skipped, length of the list}
+    DevBuf<uint64_t> d_start;
+    const size_t nv = V > 0 ? (size_t)V : 1, nt = T > 0 ? (size_t)T : 1;
+    const uint64_t nodes = (uint64_t)N0 * (uint64_t)N1;
+    HF_TRY(d_v.alloc(nv * 3));
+    HF_TRY(d_t.alloc(nt * 3));
+    HF_TRY(d_snap.alloc(nv));
+    HF_TRY(d_large.alloc(nt));
+    HF_TRY(d_tiles.alloc(nt));
+    HF_TRY(d_counts.alloc(3));
+    if (V > 0) HF_TRY(hipMemcpy(d_v.get(), vertices, (size_t)V * 3 * sizeof(float), hipMemcpyDefault));
+    if (T > 0) HF_TRY(hipMemcpy(d_t.get(), triangles, (size_t)T * 3 * sizeof(int32_t), hipMemcpyDefault));
+    HF_TRY(hipMemset(d_counts.get(), 0, d_counts.bytes()));
+    HF_TRY(hipMemset(hm_out, 0, nodes * sizeof(float)));                                  // key 0: never covered
+    RasterArgs a{};
+    a.snap = d_snap.get(); a.tris = d_t.get(); a.V = V; a.T = T; a.N0 = N0; a.N1 = N1;
+    a.keys = reinterpret_cast<uint32_t*>(hm_out);
+    a.n_large = reinterpret_cast<uint32_t*>(d_counts.get() + 2);
+    a.large_tri = d_large.get(); a.large_tiles = d_tiles.get(); a.stats = d_counts.get();
+    HF_TRY(launch_raster_snap(d_v.get(), (uint32_t)V, horizontal_scale, shift_x, shift_y, d_snap.get(), nullptr));
+    HF_TRY(launch_raster_small(a, nullptr));
+    unsigned long long counts[3] = {0, 0, 0};
+    HF_TRY(hipMemcpy(counts, d_counts.get(), sizeof counts, hipMemcpyDeviceToHost));      // (synchronises)
+    const uint32_t n_large = (uint32_t)(counts[2] & 0xffffffffull);
+    if (n_large > (uint32_t)T) return fail(c, ROVER_E_HIP, "build_heightfield: the list holds %u triangles of %d", n_large, T);
+    if (n_large) {
+        std::vector<uint32_t> tiles(n_large);
+        std::vector<uint64_t> start((size_t)n_large + 1);
+        HF_TRY(hipMemcpy(tiles.data(), d_tiles.get(), (size_t)n_large * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        start[0] = 0;
+        for (uint32_t i = 0; i < n_large; ++i) start[(size_t)i + 1] = start[i] + tiles[i];
+        HF_TRY(d_start.alloc(start.size()));
+        HF_TRY(hipMemcpy(d_start.get(), start.data(), d_start.bytes(), hipMemcpyHostToDevice));
+        HF_TRY(launch_raster_large(a, d_start.get(), n_large, start[n_large], nullptr));
+    }
+    HF_TRY(launch_raster_decode(a.keys, nodes, fill, d_counts.get(), nullptr));
+    HF_TRY(hipDeviceSynchronize());
+    HF_TRY(hipMemcpy(counts, d_counts.get(), sizeof counts, hipMemcpyDeviceToHost));
+#undef HF_TRY
+    if (stats) { stats[0] = (int64_t)counts[0]; stats[1] = (int64_t)counts[1]; }
+    return ROVER_OK;
+}
+
 // the f32 and the bf16 layer differ in the launch alone (launch_linear_act: rover_mlp.hip; launch_linear_bf16: rover_bf16_tile.hip)
 static int linear_forward_run(rover_ctx* c, const char* what, hipError_t (*launch)(const LinearArgs&, hipStream_t), const float* x, int64_t x_stride,
                               int32_t M, int32_t K, const float* weight, const float* bias, int32_t N, int32_t activation, float* y, int64_t y_stride,

@@ -374,6 +374,30 @@ static inline uint32_t track_partials(uint32_t E) { return (uint32_t)(((uint64_t
 static inline uint64_t track_scratch_bytes(uint32_t E) { return (uint64_t)track_partials(E) * ((uint64_t)track_partial_bytes() + 8ull * TRACK_BLOCK); }
 hipError_t launch_track(const TrackArgs& a, hipStream_t s);
 
+// The heightfield of a triangle mesh (rover_build_heightfield of the C ABI, validated; rover_raster.hip): snap the vertices, scatter every
+// triangle into the nodes of its box (small boxes by a lane group, large ones listed and rasterised per tile by a second launch), decode.
+#define RASTER_SUB 256                     // sub-units per node spacing
+#define RASTER_MAX_SNAP (1 << 25)          // largest |X|, |Y| of a snapped vertex: every edge function stays within 2^53
+#define RASTER_MAX_NODES 131072            // largest N0, N1: 256 (N - 1) < 2^25
+#define RASTER_GROUP 16                    // lanes per triangle on the small route
+#define RASTER_SMALL_NODES 512             // largest box (nodes) of the small route
+#define RASTER_TILE_I 32                   // the large route's tile: rows (4 waves x 8) ...
+#define RASTER_TILE_J 64                   // ... x consecutive j (one per lane)
+struct RasterArgs {
+    const void* snap;                      // [V] 16-byte snapped vertices (launch_raster_snap)
+    const int32_t* tris;                   // [T, 3]
+    int32_t V, T, N0, N1;
+    uint32_t* keys;                        // [N0][N1]: hm_out while it holds keys (all 0 before the first triangle)
+    uint32_t* n_large;                     // [1] length of the list
+    uint32_t* large_tri;                   // [T] the listed triangles ...
+    uint32_t* large_tiles;                 // [T] ... and how many tiles each one's box touches
+    unsigned long long* stats;             // [2] {uncovered nodes, skipped triangles}
+};
+hipError_t launch_raster_snap(const float* vertices, uint32_t V, float hs, float shift_x, float shift_y, void* snap, hipStream_t s);
+hipError_t launch_raster_small(const RasterArgs& a, hipStream_t s);
+hipError_t launch_raster_large(const RasterArgs& a, const uint64_t* tile_start, uint32_t n_large, uint64_t total, hipStream_t s);
+hipError_t launch_raster_decode(uint32_t* keys, uint64_t n, float fill, unsigned long long* stats, hipStream_t s);
+
 // Generalised advantage estimation over a stored rollout (rover_gae of the C ABI, validated; rover_rollout.hip): rows are time steps at
 // a stride in elements, the env stride is 1.
 enum GaeNormalize { GAE_RAW = 0, GAE_NORMALIZE = 1, GAE_NORMALIZE_GIVEN = 2 };
