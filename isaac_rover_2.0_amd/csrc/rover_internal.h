@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "rover_plan.h"      // the integer helpers plan_step shares with the launchers (bin_*, cull_queue_entries, cull_stat_slots, lane_*)
 
 // Test (B) for a whole set of triangles by its normal cone (rover_cull.hip, header comment): the ray-side constant of the f32 proof.
@@ -204,6 +205,25 @@ struct LinearRoute { int nw, nt, ny; };
 LinearRoute linear_route(int M, int N);
 const char* linear_route_name(const LinearRoute& r);      // "linear_act<3,4>x2", or NULL
 hipError_t launch_linear_act(const LinearArgs& a, hipStream_t s);
+// Launches what a LinearRoute names, for the forward and for dgrad alike: launch(nt, nw, grid) with nt and nw as integral constants
+// — <1..5, 4> or <1, 1> — on a grid of 32 nw-row slabs x r.ny; any other route is refused.
+template <class Launch>
+hipError_t launch_linear_route(int M, const LinearRoute& r, Launch&& launch) {
+    if ((r.nw != 4 && r.nw != 1) || (r.nw == 1 && r.nt != 1)) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)((M + 32 * r.nw - 1) / (32 * r.nw)), (uint32_t)r.ny);
+    const std::integral_constant<int, 1> one{};
+    const std::integral_constant<int, 4> four{};
+    switch (r.nw == 1 ? 0 : r.nt) {
+        case 0: launch(one, one, grid); break;
+        case 1: launch(one, four, grid); break;
+        case 2: launch(std::integral_constant<int, 2>{}, four, grid); break;
+        case 3: launch(std::integral_constant<int, 3>{}, four, grid); break;
+        case 4: launch(four, four, grid); break;
+        case 5: launch(std::integral_constant<int, 5>{}, four, grid); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
 // the same layer with bf16 operands (rover_bf16_tile.hip): one instantiation, linear_route's refusals; the name, or NULL
 const char* linear_route_bf16_name(int M, int N);        // "linear_bf16<128,128>"
 hipError_t launch_linear_bf16(const LinearArgs& a, hipStream_t s);

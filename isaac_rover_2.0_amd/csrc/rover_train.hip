@@ -17,7 +17,8 @@
 // the address mod 32 per 32-lane half: 32 consecutive words never conflict).  dz is formed in registers while dy and y are fetched
 // (dy act'(y), 0 past M / N); no dz tensor exists in HBM.  A workgroup = NW waves: they share the dz slab [32][NT x 32] and take one
 // 32-column tile of x each, NT accumulator tiles per wave (<= 48 VGPRs), the next slab's loads in flight under the MFMAs (the
-// forward's fetch / stash / sync skeleton).  grid = (K tiles / NW, N tiles / NT, S): M is cut into S splits of whole slabs.
+// slab loop of the f32 tile core, rover_f32_tile.h, with both slabs k-major).  grid = (K tiles / NW, N tiles / NT, S): M is cut into
+// S splits of whole slabs.
 //   * M >= 8 192: NW = 4, NT <= 3 (N = 80: all of dz in one workgroup, x read once), S = M / 1 024 rounded down to a power of two,
 //     at most 64 — 80 x 1 112 at 65 536 rows: 9 x 1 x 64 = 576 workgroups of 4 waves on 256 CUs;
 //   * below: NW = NT = 1 (one wave per 32 x 32 tile) and S = 1 / 2 / 4 / 8 from 0 / 128 / 256 / 512 rows: at 512 rows the same layer is
@@ -28,9 +29,9 @@
 // columns of each staged dz slab (row order) — K = 0 still has that one K tile, so db is written and dW is empty.
 // The scratch is the ctx's, grown on demand outside a stream capture (the chain kernels' rule).
 //
-// dx = dz W is a GEMM of the forward's shape with dz as the left operand: linear_act_kernel's structure (a 32-row x 32-k slab of the
-// left operand at a 33-word pitch, column reads conflict-free), specialised: the left slab is dz formed during staging, and W is read
-// as it lies ([n][k], lane on k: B[kk = n][j = k]) instead of transposed.  Its route is the forward's own for an M x K output
+// dx = dz W is a GEMM of the forward's shape with dz as the left operand, on the same core: the left slab is k-minor like the
+// forward's (32 rows x 32 k at the 33-word pitch) with dz formed by its staging functor, and W is a k-major slab, read as it lies
+// ([n][k], lane on k: B[kk = n][j = k]) instead of transposed.  Its route is the forward's own for an M x K output
 // (linear_route(M, K)).
 //
 // ---- the PPO loss ----------------------------------------------------------------------------------------------------------------
@@ -42,10 +43,9 @@
 #include <stdio.h>
 #include <algorithm>
 #include "rover_internal.h"
+#include "rover_f32_tile.h"
 
 namespace rover {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // act'(v) from the stored output y = act(v)
 __device__ __forceinline__ float act_grad_from_y(float y, int act) {
@@ -62,81 +62,55 @@ __device__ __forceinline__ float dz_at(const LinearBwdArgs& a, uint32_t row, uin
     return a.act == 0 ? dy : dy * act_grad_from_y(a.y[(size_t)row * a.y_stride + col], a.act);
 }
 
-// ---- dW / db -------------------------------------------------------------------------------------------------------------------------
+// ---- dW / db: on the f32 tile core (rover_f32_tile.h), both operands k-major (the reduction index is the batch row) ----------------
 template <int NT, int NW>
 __global__ void __launch_bounds__(64 * NW) linear_wgrad_kernel(LinearBwdArgs a, int K, int rows_per_split, float* __restrict__ wpart,
                                                                 float* __restrict__ bpart) {
     static_assert(NT * 32 <= 64 * NW, "one thread per dz column sums db");
-    constexpr uint32_t RSTEP = 2u * NW, DP = NT * 32u, XP = NW * 32u;
-    __shared__ float Dz[32 * DP];
-    __shared__ float Xs[32 * XP];
+    using DSlab = F32KMajor<NW, 32 * NT>;
+    using XSlab = F32KMajor<NW, 32 * NW>;
+    constexpr uint32_t DP = NT * 32u, XP = NW * 32u;
+    __shared__ float Dz[DSlab::WORDS];
+    __shared__ float Xs[XSlab::WORDS];
+    const DSlab ds{Dz};
+    const XSlab xs{Xs};
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t k0 = blockIdx.x * XP, n0 = blockIdx.y * DP, split = blockIdx.z;
     const uint32_t m_lo = split * (uint32_t)rows_per_split, m_hi = min((uint32_t)a.M, m_lo + (uint32_t)rows_per_split);
-    const uint32_t ar = lane & 31u, ak = lane >> 5;
-    const uint32_t sc = tid & 31u, sr = tid >> 5;
     f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-    float pd[NT * 32 / RSTEP], px[NW * 32 / RSTEP];
+    f32_zero(acc);
+    float pd[DSlab::NP], px[XSlab::NP];
     auto fetch = [&](uint32_t m0) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int j = 0; j < (int)(32 / RSTEP); ++j) {
-                const uint32_t row = m0 + sr + RSTEP * j, col = n0 + 32u * t + sc;
-                pd[t * (32 / RSTEP) + j] = (row < m_hi && col < (uint32_t)a.N) ? dz_at(a, row, col) : 0.0f;
-            }
-#pragma unroll
-        for (int t = 0; t < NW; ++t)
-#pragma unroll
-            for (int j = 0; j < (int)(32 / RSTEP); ++j) {
-                const uint32_t row = m0 + sr + RSTEP * j, col = k0 + 32u * t + sc;
-                px[t * (32 / RSTEP) + j] = (row < m_hi && col < (uint32_t)K) ? a.x[(size_t)row * a.x_stride + col] : 0.0f;
-            }
-    };
-    auto stash = [&]() {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int j = 0; j < (int)(32 / RSTEP); ++j) Dz[(sr + RSTEP * j) * DP + 32u * t + sc] = pd[t * (32 / RSTEP) + j];
-#pragma unroll
-        for (int t = 0; t < NW; ++t)
-#pragma unroll
-            for (int j = 0; j < (int)(32 / RSTEP); ++j) Xs[(sr + RSTEP * j) * XP + 32u * t + sc] = px[t * (32 / RSTEP) + j];
+        DSlab::stage(pd, [&](uint32_t r, uint32_t c) {
+            const uint32_t row = m0 + r, col = n0 + c;
+            return (row < m_hi && col < (uint32_t)a.N) ? dz_at(a, row, col) : 0.0f;
+        });
+        XSlab::stage(px, [&](uint32_t r, uint32_t c) {
+            const uint32_t row = m0 + r, col = k0 + c;
+            return (row < m_hi && col < (uint32_t)K) ? a.x[(size_t)row * a.x_stride + col] : 0.0f;
+        });
     };
     const bool sum_db = bpart != nullptr && blockIdx.x == 0 && tid < DP;
     float dbs = 0.0f;
-    fetch(m_lo);
-    for (uint32_t m0 = m_lo; m0 < m_hi; m0 += 32u) {
-        stash();
-        __syncthreads();
-        if (m0 + 32u < m_hi) fetch(m0 + 32u);                        // in flight during the MFMAs below
-        if (sum_db)
-            for (uint32_t r = 0; r < 32u; ++r) dbs += Dz[r * DP + tid];      // rows past the split are zeros
-#pragma unroll 4
-        for (uint32_t kk = 0; kk < 32u; kk += 2) {
-            const float bv = Xs[(kk + ak) * XP + wave * 32u + ar];
+    f32_slabs(m_lo, m_hi, fetch, [&](uint32_t) { ds.stash(pd); xs.stash(px); },
+              [&] {
+                  if (sum_db)
+                      for (uint32_t r = 0; r < 32u; ++r) dbs += Dz[r * DP + tid];      // rows past the split are zeros
+              },
+              [&](uint32_t kk) {
+                  const float bv = xs.operand(wave, kk);
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float av = Dz[(kk + ak) * DP + 32u * t + ar];
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
+                  for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ds.operand(t, kk), bv, acc[t], 0, 0, 0);
+              });
     if (sum_db && n0 + tid < (uint32_t)a.N) bpart[(size_t)split * a.N + n0 + tid] = dbs;
-    // C/D layout of the 32x32 MFMA: col = lane & 31 (k), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (n)
-    const uint32_t col = k0 + wave * 32u + (lane & 31u);
+    const uint32_t col = k0 + wave * 32u + f32_cd(lane, 0).col;      // the tile's column is k, its row n
     if (col >= (uint32_t)K) return;
     float* __restrict__ o = wpart + (size_t)split * a.N * K;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const uint32_t n = n0 + 32u * t + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * (lane >> 5);
+            const uint32_t n = n0 + 32u * t + f32_cd(lane, r).row;
             if (n < (uint32_t)a.N) o[(size_t)n * K + col] = acc[t][r];
         }
 }
@@ -156,69 +130,42 @@ __global__ void __launch_bounds__(256) wgrad_merge_kernel(const float* __restric
     }
 }
 
-// ---- dx: linear_act_kernel's structure with dz as the left operand and W read as it lies ------------------------------------------
-#define TRAIN_PITCH 33
+// ---- dx: on the f32 tile core, dz formed while staged as the k-minor left operand and W read as it lies (k-major) ---------------------
 template <int NT, int NW>
 __global__ void __launch_bounds__(64 * NW) linear_dgrad_kernel(LinearBwdArgs a) {
-    constexpr uint32_t BM = 32u * NW, RSTEP = 2u * NW, WP = NT * 32u;
-    __shared__ float As[BM * TRAIN_PITCH];                            // dz[m][n slab]
-    __shared__ float Ws[32 * WP];                                     // W[n slab][k tile columns]
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t row0 = blockIdx.x * BM, c0 = blockIdx.y * WP;
-    const uint32_t ar = lane & 31u, ak = lane >> 5;
-    const uint32_t sc = tid & 31u, sr = tid >> 5;
+    using ASlab = F32KMinor<NW, 32 * NW>;
+    using WSlab = F32KMajor<NW, 32 * NT>;
+    __shared__ float As[ASlab::WORDS];                                // dz[m][n slab]
+    __shared__ float Ws[WSlab::WORDS];                                // W[n slab][k tile columns]
+    const ASlab as{As};
+    const WSlab ws{Ws};
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t row0 = blockIdx.x * (32u * NW), c0 = blockIdx.y * (NT * 32u);
     f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-    float pa[BM / RSTEP], pw[NT * 32 / RSTEP];
+    f32_zero(acc);
+    float pa[ASlab::NP], pw[WSlab::NP];
     auto fetch = [&](uint32_t n0) {
-        const uint32_t gn = n0 + sc;
-#pragma unroll
-        for (int j = 0; j < (int)(BM / RSTEP); ++j) {
-            const uint32_t gr = row0 + sr + RSTEP * j;
-            pa[j] = (gn < (uint32_t)a.N && gr < (uint32_t)a.M) ? dz_at(a, gr, gn) : 0.0f;
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int j = 0; j < (int)(32 / RSTEP); ++j) {
-                const uint32_t n = n0 + sr + RSTEP * j, col = c0 + 32u * t + sc;
-                pw[t * (32 / RSTEP) + j] = (n < (uint32_t)a.N && col < (uint32_t)a.K) ? a.w[(size_t)n * a.K + col] : 0.0f;
-            }
+        ASlab::stage(pa, [&](uint32_t r, uint32_t c) {
+            const uint32_t gr = row0 + r, gn = n0 + c;
+            return (gn < (uint32_t)a.N && gr < (uint32_t)a.M) ? dz_at(a, gr, gn) : 0.0f;
+        });
+        WSlab::stage(pw, [&](uint32_t r, uint32_t c) {
+            const uint32_t n = n0 + r, col = c0 + c;
+            return (n < (uint32_t)a.N && col < (uint32_t)a.K) ? a.w[(size_t)n * a.K + col] : 0.0f;
+        });
     };
-    auto stash = [&]() {
+    f32_slabs(0u, (uint32_t)a.N, fetch, [&](uint32_t) { as.stash(pa); ws.stash(pw); }, [] {}, [&](uint32_t kk) {
+        const float av = as.operand(wave, kk);
 #pragma unroll
-        for (int j = 0; j < (int)(BM / RSTEP); ++j) As[(sr + RSTEP * j) * TRAIN_PITCH + sc] = pa[j];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int j = 0; j < (int)(32 / RSTEP); ++j) Ws[(sr + RSTEP * j) * WP + 32u * t + sc] = pw[t * (32 / RSTEP) + j];
-    };
-    fetch(0);
-    for (uint32_t n0 = 0; n0 < (uint32_t)a.N; n0 += 32u) {
-        stash();
-        __syncthreads();
-        if (n0 + 32u < (uint32_t)a.N) fetch(n0 + 32u);                 // in flight during the MFMAs below
-#pragma unroll 4
-        for (uint32_t kk = 0; kk < 32u; kk += 2) {
-            const float av = As[(wave * 32u + ar) * TRAIN_PITCH + kk + ak];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float bv = Ws[(kk + ak) * WP + 32u * t + ar];
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
-            }
-        }
-        __syncthreads();
-    }
+        for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, ws.operand(t, kk), acc[t], 0, 0, 0);
+    });
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        const uint32_t col = c0 + 32u * t + (lane & 31u);
+        const uint32_t col = c0 + 32u * t + f32_cd(lane, 0).col;
         if (col >= (uint32_t)a.K) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const uint32_t row = row0 + wave * 32u + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4u * (lane >> 5);
+            const uint32_t row = row0 + wave * 32u + f32_cd(lane, r).row;
             if (row < (uint32_t)a.M) a.dx[(size_t)row * a.dx_stride + col] = acc[t][r];
         }
     }
@@ -261,20 +208,6 @@ static void launch_wgrad(const LinearBwdArgs& a, int K, const LinearBwdRoute& r,
     const dim3 grid((uint32_t)std::max(1, (K + 32 * NW - 1) / (32 * NW)), (uint32_t)((a.N + 32 * NT - 1) / (32 * NT)), (uint32_t)r.splits);
     hipLaunchKernelGGL((linear_wgrad_kernel<NT, NW>), grid, dim3(64 * NW), 0, s, a, K, r.rows_per_split, wpart, bpart);
 }
-template <int NW>
-static hipError_t launch_dgrad_nw(const LinearBwdArgs& a, const LinearRoute& r, hipStream_t s) {
-    const dim3 grid((uint32_t)((a.M + 32 * NW - 1) / (32 * NW)), (uint32_t)r.ny);
-    switch (r.nt) {
-        case 1: hipLaunchKernelGGL((linear_dgrad_kernel<1, NW>), grid, dim3(64 * NW), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((linear_dgrad_kernel<2, NW>), grid, dim3(64 * NW), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((linear_dgrad_kernel<3, NW>), grid, dim3(64 * NW), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((linear_dgrad_kernel<4, NW>), grid, dim3(64 * NW), 0, s, a); break;
-        case 5: hipLaunchKernelGGL((linear_dgrad_kernel<5, NW>), grid, dim3(64 * NW), 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 // scratch: linear_backward_scratch_floats() floats (unused with one split)
 hipError_t launch_linear_backward(const LinearBwdArgs& a, const LinearBwdRoute& r, float* scratch, hipStream_t s) {
     if (!r.ok) return hipErrorInvalidValue;
@@ -311,13 +244,7 @@ hipError_t launch_linear_backward(const LinearBwdArgs& a, const LinearBwdRoute& 
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
     }
-    if (a.dx && a.K > 0) {
-        if (r.dx.nw == 4) return launch_dgrad_nw<4>(a, r.dx, s);
-        if (r.dx.nw != 1) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((linear_dgrad_kernel<1, 1>), dim3((uint32_t)((a.M + 31) / 32), (uint32_t)r.dx.ny), dim3(64), 0, s, a);
-        return hipGetLastError();
-    }
-    return hipSuccess;
+    return a.dx && a.K > 0 ? launch_linear_dgrad(a, r.dx, s) : hipSuccess;
 }
 
 // ---- dx alone, any width (rover_linear_dgrad) ----------------------------------------------------------------------------------------
@@ -341,10 +268,9 @@ const char* linear_dgrad_route_name(const LinearRoute& r) {
 }
 hipError_t launch_linear_dgrad(const LinearBwdArgs& a, const LinearRoute& r, hipStream_t s) {
     if (a.M == 0) return hipSuccess;
-    if (r.nw == 4) return launch_dgrad_nw<4>(a, r, s);
-    if (r.nw != 1 || r.nt != 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((linear_dgrad_kernel<1, 1>), dim3((uint32_t)((a.M + 31) / 32), (uint32_t)r.ny), dim3(64), 0, s, a);
-    return hipGetLastError();
+    return launch_linear_route(a.M, r, [&](auto nt, auto nw, dim3 grid) {
+        hipLaunchKernelGGL((linear_dgrad_kernel<decltype(nt)::value, decltype(nw)::value>), grid, dim3(64 * decltype(nw)::value), 0, s, a);
+    });
 }
 
 // ---- the PPO loss ------------------------------------------------------------------------------------------------------------------
