@@ -999,6 +999,9 @@ ROVER_API int rover_track_sizes(int32_t E, int32_t W, int32_t K, rover_track_siz
  *        centres — where every union fits a row of 128 pairs, else the map keeps one row per cell; -1 (default) = auto: the terrain map
  *        only (nearly all of its cells hold rays, and two neighbours' rays share a wave: a row is read once for both; a rock ray streams its
  *        row alone).  Results do not depend on it (rover_info.lane_pair_rows reports it).
+ * name = "lane_rebase" (variant 4, both arithmetics): how the staged kernel measures a steep ray against a row's suffix bounds.  0 = from
+ *        the ray's origin; 1 (default) = from the point where the ray's line crosses the row's own height, so that the origin's height
+ *        above the ground no longer widens the bound.  Read at every launch; no table and no plan depends on it, nor do the results.
  * name = "ray_precision": 0 (default) = the reference's fp32 mode, which the parity tests pin.
  *        1 = every ray origin / direction rounded to fp16 before the cell lookup and the ray maths, like the reference AS
  *        SHIPPED (Camera.dtype = float16: camera.py:55,212; rock_detect.py:319,371); f32 arithmetic after that.
@@ -1032,7 +1035,7 @@ ROVER_API int rover_track_sizes(int32_t E, int32_t W, int32_t K, rover_track_siz
  *        24 / 48 (irregular mesh, or ray_precision 2); variant 4 behind the sort 32, 64 from r = 12; in env order 16, 32 from 2^17
  *        padded ray slots, 64 from 2^20.  Results do not depend on it.
  * Every name above but "ray_precision" and "cell_index_mode" that has a ROVER_<NAME> environment variable (ROVER_RAYCAST_VARIANT,
- * ROVER_RAYCAST_RUN, ROVER_LANE_ENV_ORDER, ROVER_LANE_ROCKS, ROVER_LANE_BOX, ROVER_LANE_PAIR_ROWS, ROVER_BIN_LOW_BITS, ROVER_CULL_QUEUE_MB) takes its start value from it at
+ * ROVER_RAYCAST_RUN, ROVER_LANE_ENV_ORDER, ROVER_LANE_ROCKS, ROVER_LANE_BOX, ROVER_LANE_PAIR_ROWS, ROVER_LANE_REBASE, ROVER_BIN_LOW_BITS, ROVER_CULL_QUEUE_MB) takes its start value from it at
  * rover_create; a value outside the option's range (and 0 = auto) is ignored there. */
 ROVER_API int rover_set_option(rover_ctx *ctx, const char *name, int64_t value);
 

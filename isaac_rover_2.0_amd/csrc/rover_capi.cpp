@@ -141,6 +141,7 @@ struct rover_ctx {
     DevBuf<uint32_t> d_block_sums;      // [4096] bucket totals + [4097] bucket starts
     DevBuf<uint32_t> d_sorted;          // [E*R8] ray slots sorted by (map, cell)
     int32_t cell_rcp = 0;               // option "cell_index_mode": 0 cpu_div (x / 0.1), 1 cuda_rcp (x * (1 / 0.1))
+    int32_t lane_rebase = 1;            // option "lane_rebase": the staged kernel's level loop measures a ray from the point where its line crosses the row's height (bit 4 of LaneArgs::forms; results do not depend on it)
     DevBuf<float> d_mlp_scratch;        // partial sums of the split-k small-batch encoder path (rover_mlp_chain_forward)
     DevBuf<double> d_gae_partials;      // [GAE_MAX_BLOCKS][3] per-block (count, mean, M2) of rover_gae, sized once at rover_create
     DevBuf<double> d_ppo_partials;      // [PPO_MAX_BLOCKS][3 + GAUSS_MAX_A] per-block sums of rover_ppo_loss, sized once at rover_create
@@ -552,6 +553,8 @@ static const KnobRow kKnobs[] = {
      "-1 (auto), 0 or 1"},
     {"lane_pair_rows", "ROVER_LANE_PAIR_ROWS", -1, 1, kIntMin, kIntMax, KNOB_ENV_AS_BOOL, KNOB_SET(knobs.lane_pair_rows, (int)v), 0,      // (the same)
      "-1 (auto), 0 or 1"},
+    {"lane_rebase", "ROVER_LANE_REBASE", 0, 1, kIntMin, kIntMax, KNOB_ENV_AS_BOOL, KNOB_SET(lane_rebase, (int32_t)v), 0,      // read at every launch: no plan, no table depends on it
+     "0 or 1"},
     {nullptr, "ROVER_CULL_LAZY", 1, 0, kIntMin, kIntMax, 0, KNOB_SET(knobs.cull_lazy, (int)v), KNOB_REPLAN, nullptr},
     {"bin_low_bits", "ROVER_BIN_LOW_BITS", 8, 12, 8, 12, KNOB_OPT_ALSO_ZERO, KNOB_SET(knobs.low_bits_opt, (uint32_t)v), KNOB_REPLAN | KNOB_BINS,
      "0 (chosen by the library) or in [8, 12]"},
@@ -838,6 +841,7 @@ static int run_raycast(rover_ctx* c, const StepPlan& p, uint32_t n_valid, hipStr
             l.half = p.proof; l.c_a_h = ph.c_a; l.k2_far = cull_far_k2(l.half, ph);
             l.forms = p.proof ? 0u : (c->maps[0].lane_box ? 1u : 0u) | (c->maps[1].lane_box ? 2u : 0u);
             for (int w = 0; w < 2; ++w) { l.forms |= c->maps[w].lane_pair_rows ? 4u << w : 0u; l.y[w] = (uint32_t)c->maps[w].knn.Y; }
+            l.forms |= c->lane_rebase ? 16u : 0u;
         }
         l.run = p.run; l.out = c->d_dist_out.get(); l.stats = q.stats.get();
         if (p.env_order) {      // every slot (padding included), in env order, one launch

@@ -999,6 +999,11 @@ static_assert(0.999 * (LN_B4_TAU - LN_B4_ERR) * CullK<0>::sigma > 1.45 * 2.0 * 1
 #define LN_BOX_FILL 0.85             // a pair is "well filled" when its box's xy area is below this share of its larger sphere's disc, as test (A) needs them
 #define LN_BOX_SHARE 0.75            // a map is built in box form when at least this share of its non-empty pairs is well filled
 static_assert((double)LN_BOX_ALPHA >= 1.008 * CullK<0>::alpha, "f32 cull proof, box form: the margin must exceed alpha by the roundings' share");
+// The level loop from the point s' where the ray's line crosses z_c (lane_scan_kernel, "lane_rebase"): what s'_xy may be off by per metre of
+// |s_z - z_c|.  fl(sz * fl(1 / dz)) is within 2^-23 + 2^-24 = 1.8e-7 of sz / dz, a steep ray has |dxy| / |dz| <= tan(acos 0.9) = 0.4844, and the
+// error enters the inequality times |dz| 1.0004 + c3 < 1.03: 9e-8 per metre, taken four times over.
+#define LN_REB_ERR 1.0e-6f
+static_assert((double)LN_REB_ERR >= 4.0 * 1.03 * 0.4844 * 1.8e-7, "lane_rebase: the rounding of s' must fit its term of the level inequality");
 #define LN_WAVES 5                   // waves per SIMD the kernel is compiled for (95 VGPRs, 7.4 KB LDS): 3 / 4 / 5 -> 317 / 253 / 235 us; 6 spills
 
 __device__ __forceinline__ uint16_t half_bits_up(float v) {      // fp16 >= v (v >= 0, finite or +inf)
@@ -1466,7 +1471,7 @@ __device__ __forceinline__ void lane_exact(const RayRec* __restrict__ rays, cons
         const uint2 *__restrict__ lid1, const RawTri *__restrict__ rtab0, const RawTri *__restrict__ rtab1, uint32_t pp01, uint32_t run,      \
         uint32_t n_blocks, uint32_t split, uint32_t t8, uint32_t r8, uint32_t chsr, uint32_t run_r, float *__restrict__ out,                  \
         uint4 *__restrict__ stats, float k2_far, float c_a, uint32_t forms /* bit w: map w's f32 tables are in box form; bit 2 + w: map w's   \
-        tables are in shared-row form */, FastDiv yd0, FastDiv yd1, uint32_t y0, uint32_t y1 /* shared-row form: the map's Y, and the division by it */
+        tables are in shared-row form; bit 4: the level loop from the line's point at the row's height ("lane_rebase") */, FastDiv yd0, FastDiv yd1, uint32_t y0, uint32_t y1 /* shared-row form: the map's Y, and the division by it */
 
 template <int H>
 __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bounds__(64) lane_scan_kernel(LANE_SCAN_ARGS) {
@@ -1531,22 +1536,43 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
         //     |dz| G_k - c3 rho_k - (|dz| + c3) o  >  dzm_k (|dxy| + k2 |dz|^2),     c3 = k2 |dz| |dxy|
         // every term of the right-hand sides with the factor 1.0004 (>= the 1.0001^3 the unsorted form gives its largest term), G_k with
         // its 0.9999 G - 1e-5 from lane_build_kernel: two v_fma_mix and a compare per level instead of twenty operations
-        const float o = __builtin_amdgcn_sqrtf(sx * sx + sy * sy);
+        //
+        // Rebased (forms bit 4, "lane_rebase"): W is the distance from a centre to the ray's LINE, so e may be taken from any
+        // point of the line.  From s' = s - (sz / dz) d, where the line crosses the row's own height z_c: o' = dist_xy(s', C) is the line's
+        // true offset at ground height and dzm' = the suffix's own deviation from z_c — the drift dzm |dxy| / |dz| of a ray that starts a
+        // metre above what it hits leaves e as a vector instead of entering it in full.  a_max stays about the ORIGIN (test (A)'s h is
+        // s - m): |h . d^| <= |(s' - m) . d^| + |sz| |d| / |dz|, i.e. times k2 |dz| one more term k2 |d| |sz| that no level depends on:
+        //     |dz| G_k - c3 rho_k - (|dz| + c3) o' - kz |sz|  >  dzm'_k (|dxy| + k2 |dz|^2),     kz = k2 |d|_max 1.0004 + LN_REB_ERR
+        // with |d| <= 1.0021 (either proof).  Rounding of s': 1 / dz (v_rcp_f32: 1 ulp), its product with sz and the fma's sum move s'_xy by
+        // < 2.6e-7 |sz| |dxy| / |dz| + 6e-8 |s'_xy|: the first is LN_REB_ERR |sz| (times |dz| + c3 < 1.03, static_assert), the second
+        // a 1e-7 of o' under its 1.0004 (of which the sorted form uses 1.0003).  s'_z = 0 is exact by construction.  A ray that is not
+        // steep, not tame or not active computes a value here (an infinity or a NaN for dz = 0: every compare false) that is overridden below.
+        const bool reb = (forms >> 4) & 1u;
+        const float tz = sz * __builtin_amdgcn_rcpf(rsb.z);
+        const float lx = reb ? __builtin_fmaf(-tz, rsb.x, sx) : sx, ly = reb ? __builtin_fmaf(-tz, rsb.y, sy) : sy;
+        const float o = __builtin_amdgcn_sqrtf(lx * lx + ly * ly);
         const float dxy2 = rsb.x * rsb.x + rsb.y * rsb.y, adz = fabsf(rsb.z), sq = __builtin_amdgcn_sqrtf(dxy2);
         const bool steep = adz * adz >= 0.81f * (dxy2 + adz * adz) * 1.0001f;
         const float c3 = k2_far * adz * sq * 1.0004f, nc3 = -c3;
         const float c4 = (sq + k2_far * adz * adz) * 1.0004f;
-        const float base = -((adz * 1.0004f + c3) * o);
+        const float kz = reb ? k2_far * (1.0004f * 1.0021f) + LN_REB_ERR : 0.0f;
+        const float base = -((adz * 1.0004f + c3) * o + kz * fabsf(sz));
         const uint32_t qw[8] = {__float_as_uint(lq0.x), __float_as_uint(lq0.y), __float_as_uint(lq0.z), __float_as_uint(lq0.w),
                                 __float_as_uint(lq1.x), __float_as_uint(lq1.y), __float_as_uint(lq1.z), __float_as_uint(lq1.w)};
+        // (the loop once per form, chosen by the wave: the rebased one measures heights from the constant 0, so s' costs no register
+        //  beside sx, sy, sz, which stay live for s_ray — one more VGPR here spills: 96 are all there are at 5 waves per SIMD)
+        auto scan = [&](auto REB) {
 #pragma unroll
-        for (int k = (int)LN_MAXCH - 1; k >= 0; --k) {
-            const uint32_t w0 = __float_as_uint((k & 1) ? lv[k >> 1].z : lv[k >> 1].x), w1 = __float_as_uint((k & 1) ? lv[k >> 1].w : lv[k >> 1].y);
-            const float dzm = fmaxf(fabsf(mix_rsub<1>(w0, sz)), fabsf(mix_rsub<0>(w1, sz)));
-            const float lhs = mix_fma<0>(w0, adz, mix_fma<1>(w1, nc3, base));
-            const uint32_t q16 = (k & 1) ? qw[k >> 1] >> 16 : qw[k >> 1] & 0xffffu;
-            L = (lhs > dzm * c4) & (q16 >= rq) ? (uint32_t)k : L;
-        }
+            for (int k = (int)LN_MAXCH - 1; k >= 0; --k) {
+                const uint32_t w0 = __float_as_uint((k & 1) ? lv[k >> 1].z : lv[k >> 1].x), w1 = __float_as_uint((k & 1) ? lv[k >> 1].w : lv[k >> 1].y);
+                const float lz = decltype(REB)::value ? 0.0f : sz;
+                const float dzm = fmaxf(fabsf(mix_rsub<1>(w0, lz)), fabsf(mix_rsub<0>(w1, lz)));
+                const float lhs = mix_fma<0>(w0, adz, mix_fma<1>(w1, nc3, base));
+                const uint32_t q16 = (k & 1) ? qw[k >> 1] >> 16 : qw[k >> 1] & 0xffffu;
+                L = (lhs > dzm * c4) & (q16 >= rq) ? (uint32_t)k : L;
+            }
+        };
+        if (reb) scan(std::true_type{}); else scan(std::false_type{});
         if (!steep) L = nch;
     }
     const bool allc = act && !tame;                           // a wild ray: every pair of the cell is a candidate, nothing is tested
@@ -1938,7 +1964,7 @@ hipError_t launch_raycast_lane(LaneArgs a, hipStream_t s) {
     hipLaunchKernelGGL(a.half ? lane_scan_kernel<1> : lane_scan_kernel<0>, dim3((g.t8 + g.r8) * 8u * 4u), dim3(64), 0, s, a.rays, a.sorted,
                        a.n_sorted, a.lvl[0], a.lvl[1], a.lrec[0], a.lrec[1], a.lid[0], a.lid[1], reinterpret_cast<const RawTri*>(a.rtab[0]),
                        reinterpret_cast<const RawTri*>(a.rtab[1]), a.pp[0] | (a.pp[1] << 16), g.run, g.n_blocks, g.split, g.t8, g.r8, g.chs | (g.chr << 8),
-                       g.run_r, a.out, a.stats, k2, c_a, a.half ? a.forms & 0xcu : a.forms, make_fastdiv(a.y[0] ? a.y[0] : 1u), make_fastdiv(a.y[1] ? a.y[1] : 1u),
+                       g.run_r, a.out, a.stats, k2, c_a, a.half ? a.forms & 0x1cu : a.forms, make_fastdiv(a.y[0] ? a.y[0] : 1u), make_fastdiv(a.y[1] ? a.y[1] : 1u),
                        a.y[0], a.y[1]);
     return hipGetLastError();
 }

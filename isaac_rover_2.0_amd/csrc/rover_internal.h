@@ -102,7 +102,7 @@ struct LaneArgs {
     uint4* stats;
     int half;                    // the tables are the as-shipped fp16 arithmetic's, the exact phase runs it
     float c_a_h, k2_far;         // test (A)'s constant of that proof; the level bound's ray-side constant (cull_far_k2)
-    uint32_t forms;              // bit w (f32 proof) = map w's pair records are boxes (launch_lane_box), else two spheres; bit 2 + w = map w's tables are in shared-row form
+    uint32_t forms;              // bit w (f32 proof) = map w's pair records are boxes (launch_lane_box), else two spheres; bit 2 + w = map w's tables are in shared-row form; bit 4 = the level loop measures a ray from where its line crosses the row's height ("lane_rebase")
     uint32_t y[2];               // per map: its Y (cell = ix * Y + iy), what the shared-row form finds a cell's row with
 };
 uint32_t lane_lvl_stride();
