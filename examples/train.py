@@ -7,6 +7,11 @@
 (cfg/trainSKRL/RoverPPOSKRL.yaml).  Prints losses, KL and the mean return per update.
 
     python examples/train.py --envs 512 --native-rays --steps 120 --rollouts 60 [--time-update]
+
+`--state-preprocessor` / `--value-preprocessor` put skrl's RunningStandardScaler (`learning/preprocess.py`, `rover_scaler_update` /
+`rover_scaler_apply`) where skrl's PPO puts it: the nets read the normalised observation, the memory stores the denormalised value, the
+update trains both scalers.  `--lr-scheduler kl` steps skrl's KLAdaptiveRL once per epoch.  `--save PATH` writes `{policy, value,
+state_preprocessor, value_preprocessor}` after the last step (the scalers' entries under skrl's three keys), `--load PATH` resumes from it.
 """
 import argparse
 import os
@@ -36,6 +41,11 @@ def main():
                     help="where the KL early stop is decided: host = one read per minibatch; device = by the native step's gate (needs --native-step)")
     ap.add_argument("--rollout-precision", choices=("f32", "bf16"), default="f32",
                     help="what the actor and the critic ACT in while the rollout is collected; the update stays f32 (learning/ppo.py)")
+    ap.add_argument("--state-preprocessor", action="store_true", help="a RunningStandardScaler on the observation (learning/preprocess.py)")
+    ap.add_argument("--value-preprocessor", action="store_true", help="a RunningStandardScaler on values and returns")
+    ap.add_argument("--lr-scheduler", choices=("none", "kl"), default="none", help="kl = skrl's KLAdaptiveRL, one step per epoch (not with --kl-stop device)")
+    ap.add_argument("--save", default="", help="after the last step, torch.save {policy, value, state_preprocessor, value_preprocessor} here")
+    ap.add_argument("--load", default="", help="resume from a file --save wrote (a skrl agent checkpoint's preprocessor entries load as well)")
     ap.add_argument("--time-update", action="store_true", help="print the wall time of each update between two torch.cuda.synchronize()")
     ap.add_argument("--sim", choices=("kinematic", "terrain"), default="kinematic",
                     help="what moves the rovers between two steps: vec_env.KinematicSim, a flat unicycle, or TerrainSim, the terrain-following "
@@ -80,12 +90,36 @@ def main():
                               ("values", 1, torch.float32), ("rewards", 1, torch.float32), ("terminated", 1, torch.bool),
                               ("returns", 1, torch.float32), ("advantages", 1, torch.float32)):
         memory.create_tensor(name, size, dtype)
+    extra = {}
+    if args.state_preprocessor or args.value_preprocessor or args.lr_scheduler == "kl":
+        from isaac_rover_amd.learning.ppo import KLAdaptiveRL
+        from isaac_rover_amd.learning.preprocess import RunningStandardScaler
+        if args.state_preprocessor:
+            extra["state_preprocessor"] = RunningStandardScaler(task._engine, obs.shape[1])
+        if args.value_preprocessor:
+            extra["value_preprocessor"] = RunningStandardScaler(task._engine, 1)
+        if args.lr_scheduler == "kl":
+            extra["lr_scheduler"] = KLAdaptiveRL()
+        print("preprocessors: " + ", ".join(k for k in ("state_preprocessor", "value_preprocessor") if k in extra)
+              + ("  lr scheduler: KLAdaptiveRL" if "lr_scheduler" in extra else ""))
     ppo = PPO(task._engine, agent, critic, memory, {"learning_epochs": args.epochs, "mini_batches": args.mini_batches, "kl_threshold": args.kl_threshold},
-              generator=torch.Generator().manual_seed(0), native_step=args.native_step, kl_stop=args.kl_stop)
+              generator=torch.Generator().manual_seed(0), native_step=args.native_step, kl_stop=args.kl_stop, **extra)
+    if args.load:
+        ck = torch.load(args.load, map_location="cpu")
+        agent.load_state_dict(ck["policy"])
+        critic.load_state_dict(ck["value"])
+        for name in ("state_preprocessor", "value_preprocessor"):
+            if name in extra and ck.get(name) is not None:
+                extra[name].load_state_dict(ck[name])
+        print(f"resumed from {args.load}: " + ", ".join(k for k in ("policy", "value", "state_preprocessor", "value_preprocessor") if ck.get(k) is not None))
+    normalized = torch.empty_like(obs) if args.state_preprocessor else None
     updates = 0
     for step in range(args.steps):
-        actions, log_prob, _ = agent.act(obs)
-        values, _, _ = critic.act(obs)
+        seen = obs if normalized is None else ppo.preprocess_states(obs, out=normalized)      # what the nets read
+        actions, log_prob, _ = agent.act(seen)
+        values, _, _ = critic.act(seen)
+        if args.value_preprocessor:
+            values = ppo.denormalize_values(values)
         states = obs.clone()                                                       # env.step() rewrites the observation buffer
         obs, rew, done, info = env.step(actions)
         if tracker is not None:
@@ -94,8 +128,8 @@ def main():
                 print(f"step {step + 1}: {tracker.read().line()}")
         memory.add_samples(states=states, actions=actions, log_prob=log_prob, values=values, rewards=rew, terminated=done.bool())
         if memory.memory_index == 0:                                               # full: one PPO update on these N steps
-            last_values, _, _ = critic.act(obs)
-            last_values = last_values.clone()                                      # the update's forwards reuse the critic's buffers
+            last_values, _, _ = critic.act(obs if normalized is None else ppo.preprocess_states(obs, out=normalized))
+            last_values = ppo.denormalize_values(last_values) if args.value_preprocessor else last_values.clone()      # the update's forwards reuse the critic's buffers
             if args.time_update:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -109,8 +143,15 @@ def main():
                   f"entropy_loss {float(out['entropy_loss']):+.5f}  kl {float(out['kl']):.3e}  mean return "
                   f"{float(memory.get_tensor_by_name('returns').mean()):.4f}  minibatches stepped per epoch {ppo.minibatches_done}"
                   + (f"  update {dt * 1e3:.1f} ms ({dt * 1e3 / max(steps, 1):.2f} ms per stepped minibatch of "
-                     f"{args.rollouts * args.envs // args.mini_batches} rows)" if args.time_update else ""))
+                     f"{args.rollouts * args.envs // args.mini_batches} rows)" if args.time_update else "")
+                  + (f"  lr {ppo.learning_rates[-1]:.3e}" if ppo.learning_rates else ""))
             memory.reset()
+    if args.save:
+        torch.save({"policy": {k: v.detach().cpu() for k, v in agent.state_dict().items()}, "value": {k: v.detach().cpu() for k, v in critic.state_dict().items()},
+                    "state_preprocessor": {k: v.cpu() for k, v in extra["state_preprocessor"].state_dict().items()} if "state_preprocessor" in extra else None,
+                    "value_preprocessor": {k: v.cpu() for k, v in extra["value_preprocessor"].state_dict().items()} if "value_preprocessor" in extra else None},
+                   args.save)
+        print(f"saved policy, value and preprocessors to {args.save}")
     env.close()
 
 

@@ -856,6 +856,81 @@ ROVER_API int rover_obs_noise(rover_ctx *ctx, const rover_obs_noise_desc *d, voi
 /* Host only (no ctx, no device): *thr = (uint32) llrint(dropout * 2^24); ROVER_E_INVALID for a NULL thr or dropout outside [0, 1]. */
 ROVER_API int rover_obs_noise_threshold(double dropout, uint32_t *thr);
 
+/* ---- running standard scaler: skrl's RunningStandardScaler for states and values (learning/preprocess.py) ----------------------------- */
+/* The reference's train.py imports skrl's RunningStandardScaler (omniisaacgymenvs/train.py); every skrl PPO recipe for Isaac tasks passes
+ * it for states and values.  skrl is no dependency: the definition is restated here.  The state is the caller's, all float64 on the
+ * device: mean [N] (skrl's running_mean, starts at 0), var [N] (running_variance, starts at 1) and count [1] (current_count, starts at 1:
+ * one pseudo-sample).
+ *
+ * rover_scaler_update: a TRAIN call on x [M, N] (f32 rows at a row stride in floats).  Per column, with mb the mean of the M values
+ * and vb their UNBIASED variance M2 / (M - 1) (torch.var), in f64, every line one rounding per operation in the written order:
+ *     delta = mb - mean
+ *     total = count + M
+ *     m2    = (var * count + vb * M) + (((delta * delta) * count) * M) / total
+ *     mean  = mean + (delta * M) / total
+ *     var   = m2 / total
+ *     count = total
+ * Exactly two launches (csrc/rover_scaler.hip); the call allocates nothing, does not synchronise and can be captured in a graph; one
+ * stream per ctx at a time.  rover_scaler_plan (host only, no ctx, a pure function of (M, N) — never of the device, so the same inputs
+ * give the same bits on any machine) splits the rows into n_chunks chunks of rows_per_chunk rows (the last one shorter) and chooses
+ *     ROVER_SCALER_NARROW for N <= 8:  rows_per_chunk = 16 384; the 256 threads of a workgroup split the chunk's rows (thread t takes
+ *                                      rows t, t + 256, ...: at most 64), column by column, and add their sums in a fixed binary tree;
+ *     ROVER_SCALER_WIDE   otherwise:   rows_per_chunk = 32 for M <= 8 192, else 128; a thread owns two neighbouring columns and walks
+ *                                      the chunk's rows in order (one 8-byte load per row where x and its stride allow, two scalar loads
+ *                                      otherwise: the same additions in the same order);
+ *     scratch_bytes = 8 + 24 n_chunks N (caller-owned, 8-byte aligned; its contents mean nothing between calls).
+ * Launch 1 leaves per chunk and column (count n, mean, M2) in f64 in scratch, from plain sums: S1 = sum x and S2 = sum x x with x widened
+ *   to f64 (each product is exact), mean = S1 / n, M2 = max(S2 - (S1 S1) / n, 0) (a NaN stays a NaN).  Every x enters its sum through at
+ *   most a = 136 additions, so with u = 2^-53 and g(k) = k u / (1 - k u):  |dS1| <= g(a) sum|x|,  |dS2| <= g(a) sum x^2,  and
+ *   |dM2| <= 4 g(a + 3) sum x^2 per chunk (S1^2 / n <= sum x^2).  It also copies *count into the scratch header.
+ * Launch 2 merges the chunks IN CHUNK ORDER in two levels (Chan: tot = n + nk, d = mean_k - mean, f = nk / tot, mean += d f,
+ *   M2 = (M2 + M2_k) + (d d)(n f), n = tot — at most 10 roundings per merge, each relative to a quantity bounded by sum x^2, resp.
+ *   sum|x| / n for the mean): the chunks form 8 runs of ceil(n_chunks / 8) consecutive chunks (the last runs shorter or empty), one thread
+ *   per column and run merges its run's chunks in order, then one thread per column merges the 8 runs in order, empty ones passed over.
+ *   It then folds (M, mb, vb = M2 / (M - 1)) into the state as written above with the count from
+ *   the header, and writes *count.  Over C chunks:  |d mb| <= (g(a + 1) + 4 C u) sum|x| / M,  |d M2| <= (4 g(a + 3) + 10 C u) sum x^2.
+ * skip_if: optional device int32[1], read when launch 2 runs; nonzero: mean, var and count stay bit-unchanged (the device-side KL stop
+ * of learning/ppo.py hands the optimiser's `stopped` latch here).  No floating-point atomics: the same inputs give the same bits on
+ * every run, whatever the alignment or the row stride of x.
+ *
+ * rover_scaler_apply: one launch, y [M, N] from x [M, N] and the statistics as they are on the device when the kernel runs, in f32,
+ * one rounding per operation in this order, with m = f32(mean), s = sqrtf(f32(var)), e = f32(epsilon), c = f32(clip):
+ *     forward:   y = clamp((x - m) / (s + e), -c, +c)
+ *     inverse:   y = s * clamp(x, -c, +c) + m
+ * clamp is torch.clamp: a NaN stays a NaN in both directions; +-Inf clamps to +-c.  y may be exactly x (same pointer and stride: in
+ * place); any other overlap is refused.  M = 0: ROVER_OK, no launch.  Allocates nothing, does not synchronise, capturable.
+ *
+ * ROVER_E_INVALID before any launch — every check is made before the ctx is looked at, so with a NULL ctx rover_last_error(NULL) names
+ * the refusal (a NULL ctx itself is refused last) —: a NULL descriptor or a NULL x, y, mean, var, count or scratch; N outside 1 .. 4096;
+ * M < 0 or M N >= 2^31; update with M < 2 (skrl's vb would be a NaN: a documented deviation); a row stride < N or > 2^40; mean, var,
+ * count or scratch not 8-byte aligned; the state overlapping x, y, scratch, skip_if or itself; scratch overlapping x; scratch_bytes below
+ * the plan's; a negative or non-finite epsilon or clip; y overlapping x other than as the same array. */
+#define ROVER_SCALER_WIDE 0
+#define ROVER_SCALER_NARROW 1
+typedef struct {
+    int32_t route;                                 /* ROVER_SCALER_WIDE / ROVER_SCALER_NARROW                                       */
+    int32_t rows_per_chunk, n_chunks;
+    int64_t scratch_bytes;
+} rover_scaler_plan_desc;
+ROVER_API int rover_scaler_plan(int32_t M, int32_t N, rover_scaler_plan_desc *plan);
+typedef struct {
+    const float *x;         int64_t x_stride;      /* [M, N]                                                                        */
+    int32_t M, N;
+    double *mean, *var, *count;                    /* device [N], [N], [1]: read and written by launch 2                            */
+    void *scratch;          int64_t scratch_bytes; /* device, >= the plan's scratch_bytes                                           */
+    const int32_t *skip_if;                        /* optional device [1]                                                           */
+} rover_scaler_update_desc;
+ROVER_API int rover_scaler_update(rover_ctx *ctx, const rover_scaler_update_desc *d, void *stream);
+typedef struct {
+    const float *x;         int64_t x_stride;      /* [M, N]                                                                        */
+    float *y;               int64_t y_stride;      /* [M, N]; may be exactly x                                                      */
+    int32_t M, N;
+    const double *mean, *var;                      /* device [N] each                                                               */
+    double epsilon, clip;                          /* >= 0, finite; rounded to f32 once                                             */
+    int32_t inverse;                               /* 0: forward, else inverse                                                      */
+} rover_scaler_apply_desc;
+ROVER_API int rover_scaler_apply(rover_ctx *ctx, const rover_scaler_apply_desc *d, void *stream);
+
 /* ---- terrain-following motion model: what moves the rovers between two steps (vec_env.TerrainSim) ------------------------------------ */
 /* PhysX is out of scope; this is the project's own definition of a deterministic, stateless, kinematic pose feeder that keeps the six
  * wheels on the heightfield of rover_set_heightfield.  f32 on the device, one rounding per written operation, one thread per env.

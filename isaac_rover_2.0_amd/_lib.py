@@ -134,6 +134,23 @@ class ObsNoiseDesc(C.Structure):
                 ("row_offset", C.c_int64)]
 
 
+class ScalerPlanDesc(C.Structure):
+    _fields_ = [("route", C.c_int32), ("rows_per_chunk", C.c_int32), ("n_chunks", C.c_int32), ("scratch_bytes", C.c_int64)]
+
+
+SCALER_WIDE, SCALER_NARROW = 0, 1
+
+
+class ScalerUpdateDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64), ("M", C.c_int32), ("N", C.c_int32), ("mean", C.c_void_p), ("var", C.c_void_p),
+                ("count", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64), ("skip_if", C.c_void_p)]
+
+
+class ScalerApplyDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_stride", C.c_int64), ("y", C.c_void_p), ("y_stride", C.c_int64), ("M", C.c_int32), ("N", C.c_int32),
+                ("mean", C.c_void_p), ("var", C.c_void_p), ("epsilon", C.c_double), ("clip", C.c_double), ("inverse", C.c_int32)]
+
+
 class MotionDesc(C.Structure):
     _fields_ = [("pos3", C.c_void_p), ("quat4", C.c_void_p), ("lin", C.c_void_p), ("ang", C.c_void_p), ("cmd_stride", C.c_int32), ("E", C.c_int32),
                 ("substeps", C.c_int32), ("dt", C.c_float), ("max_lin", C.c_float), ("max_ang", C.c_float), ("ride_height", C.c_float),
@@ -263,6 +280,9 @@ SYMBOLS = {
     "rover_linear_dgrad_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
     "rover_obs_noise": (C.c_int, [_P, C.POINTER(ObsNoiseDesc), _P]),
     "rover_obs_noise_threshold": (C.c_int, [C.c_double, _P]),
+    "rover_scaler_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(ScalerPlanDesc)]),
+    "rover_scaler_update": (C.c_int, [_P, C.POINTER(ScalerUpdateDesc), _P]),
+    "rover_scaler_apply": (C.c_int, [_P, C.POINTER(ScalerApplyDesc), _P]),
     "rover_motion_step": (C.c_int, [_P, C.POINTER(MotionDesc), _P]),
     "rover_motion_plane_fit": (C.c_int, [_P]),
     "rover_episode_track": (C.c_int, [_P, C.POINTER(TrackDesc), _P]),
@@ -417,6 +437,32 @@ def obs_noise_threshold(dropout):
     if rc != 0:
         raise RoverError(f"rover_obs_noise_threshold failed ({rc}): {lib.rover_last_error(None).decode()}")
     return int(out.value)
+
+
+def scaler_plan(m, n):
+    """rover_scaler_plan: how rover_scaler_update splits ``m`` rows of ``n`` columns, as a dict (route, rows_per_chunk, n_chunks,
+    scratch_bytes).  Host only, a pure function of (m, n)."""
+    out = ScalerPlanDesc()
+    lib = load()
+    rc = lib.rover_scaler_plan(int(m), int(n), C.byref(out))
+    if rc != 0:
+        raise RoverError(f"rover_scaler_plan failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return {name: int(getattr(out, name)) for name, _ in ScalerPlanDesc._fields_}
+
+
+def scaler_update_desc(m, n, x=1 << 36, x_stride=None, mean=_FAKE, var=_FAKE + (1 << 15), count=_FAKE + (1 << 16), scratch=1 << 20,
+                       scratch_bytes=None, skip_if=None):
+    """A rover_scaler_update_desc from plain values (pointers as integers; the stride defaults to ``n``, ``scratch_bytes`` to the plan's;
+    the default addresses are never read and disjoint for every legal shape)."""
+    if scratch_bytes is None:
+        scratch_bytes = scaler_plan(m, n)["scratch_bytes"]
+    return ScalerUpdateDesc(x, int(n) if x_stride is None else int(x_stride), int(m), int(n), mean, var, count, scratch, int(scratch_bytes), skip_if)
+
+
+def scaler_apply_desc(m, n, x=1 << 36, y=1 << 36, x_stride=None, y_stride=None, mean=_FAKE, var=_FAKE + (1 << 15), epsilon=1e-8, clip=5.0, inverse=False):
+    """A rover_scaler_apply_desc from plain values (pointers as integers; the strides default to ``n``)."""
+    return ScalerApplyDesc(x, int(n) if x_stride is None else int(x_stride), y, int(n) if y_stride is None else int(y_stride), int(m), int(n),
+                           mean, var, float(epsilon), float(clip), int(bool(inverse)))
 
 
 def motion_desc(e, pos3=_FAKE, quat4=_FAKE, lin=_FAKE, ang=_FAKE, cmd_stride=3, substeps=1, dt=0.05, max_lin=1.0, max_ang=1.0, ride_height=0.3,
@@ -1007,6 +1053,50 @@ class Engine:
         desc = obs_noise_desc(m, f, first, dp(obs), dp(out), max(obs.stride(0), f), max(out.stride(0), f), sigma_point, sigma_offset, dropout, drop_value,
                               dp(row_scale), dp(episode), seed, step, dp(step_dev), row_offset)
         self._check(self.lib.rover_obs_noise(self._h, C.byref(desc), _stream(self._dev_index)), "rover_obs_noise")
+        return out
+
+    scaler_plan = staticmethod(scaler_plan)
+
+    def _scaler_state(self, what, n, mean, var, count=None):
+        self._chk(mean, (n,), torch.float64, "mean")
+        self._chk(var, (n,), torch.float64, "var")
+        self._chk(count, (1,), torch.float64, "count")
+        if mean is None or var is None:
+            raise RoverError(f"{what}: mean and var must be given")
+
+    def scaler_update(self, x, mean, var, count, scratch, skip_if=None):
+        """A train call of skrl's RunningStandardScaler on ``x`` [m, n] (rover_scaler_update, two launches, no host read, capturable):
+        the batch's column means and unbiased variances are folded into ``mean`` / ``var`` [n] and ``count`` [1], float64 on the device.
+        ``scratch``: uint8, at least ``scaler_plan(m, n)["scratch_bytes"]``.  ``skip_if``: one int32 on the device; nonzero when the
+        kernels run leaves the state bit-unchanged."""
+        what = "scaler_update"
+        self._f32_rows(x, "x", what)
+        m, n = x.shape
+        self._scaler_state(what, n, mean, var, count)
+        if count is None or scratch is None or not scratch.is_cuda or scratch.dtype != torch.uint8 or scratch.dim() != 1:
+            raise RoverError(f"{what}: count and a uint8 scratch vector on the GPU must be given")
+        if skip_if is not None and (not skip_if.is_cuda or skip_if.dtype != torch.int32 or skip_if.numel() != 1):
+            raise RoverError(f"{what}: skip_if must be one int32 word on the GPU")
+        desc = ScalerUpdateDesc(x.data_ptr(), max(x.stride(0), n), m, n, mean.data_ptr(), var.data_ptr(), count.data_ptr(), scratch.data_ptr(),
+                                scratch.numel(), None if skip_if is None else skip_if.data_ptr())
+        self._check(self.lib.rover_scaler_update(self._h, C.byref(desc), _stream(self._dev_index)), "rover_scaler_update")
+
+    def scaler_apply(self, x, mean, var, out=None, *, epsilon=1e-8, clip=5.0, inverse=False):
+        """``clamp((x - mean) / (sqrt(var) + epsilon), -clip, clip)``, or with ``inverse`` ``sqrt(var) * clamp(x, -clip, clip) + mean``, on
+        ``x`` [m, n] in f32 (rover_scaler_apply, one launch); the float64 statistics are read on the device when the kernel runs.
+        ``out`` None: a new tensor; ``out is x`` (or a view of the same memory): in place."""
+        what = "scaler_apply"
+        self._f32_rows(x, "x", what)
+        m, n = x.shape
+        if out is None:
+            out = torch.empty(m, n, device=x.device)
+        self._f32_rows(out, "out", what, (m, n))
+        if x.device != self.device or out.device != self.device:
+            raise RoverError(f"{what}: x and out must be on {self.device}")
+        self._scaler_state(what, n, mean, var)
+        desc = scaler_apply_desc(m, n, x.data_ptr(), out.data_ptr(), max(x.stride(0), n), max(out.stride(0), n), mean.data_ptr(), var.data_ptr(),
+                                 epsilon, clip, inverse)
+        self._check(self.lib.rover_scaler_apply(self._h, C.byref(desc), _stream(self._dev_index)), "rover_scaler_apply")
         return out
 
     def motion_step(self, pos, quat, lin, ang, *, dt, substeps=1, max_lin=1.0, max_ang=1.0, ride_height=0.3, joints=None):

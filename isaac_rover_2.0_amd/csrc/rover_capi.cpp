@@ -2319,6 +2319,86 @@ int rover_obs_noise_threshold(double dropout, uint32_t* thr) {
     return ROVER_OK;
 }
 
+// Host only, a pure function of (M, N): the route, the chunking and the scratch of rover_scaler_update
+int rover_scaler_plan(int32_t M, int32_t N, rover_scaler_plan_desc* plan) {
+    if (!plan) return fail(nullptr, ROVER_E_INVALID, "scaler_plan: null plan");
+    if (N < 1 || N > 4096) return fail(nullptr, ROVER_E_INVALID, "scaler_plan: N = %d outside 1 .. 4096", N);
+    if (M < 0 || (int64_t)M * N >= (int64_t)1 << 31) return fail(nullptr, ROVER_E_INVALID, "scaler_plan: M = %d is negative or M N >= 2^31", M);
+    const bool narrow = (uint32_t)N <= SCALER_NARROW_MAX_N;
+    plan->route = narrow ? ROVER_SCALER_NARROW : ROVER_SCALER_WIDE;
+    plan->rows_per_chunk = narrow ? 16384 : (M <= 8192 ? 32 : 128);
+    plan->n_chunks = (int32_t)(((int64_t)M + plan->rows_per_chunk - 1) / plan->rows_per_chunk);
+    plan->scratch_bytes = 8 + (int64_t)24 * plan->n_chunks * N;
+    return ROVER_OK;
+}
+
+static bool aligned8(const void* p) { return (uintptr_t)p % 8 == 0; }
+
+// The descriptor is validated before the ctx is looked at, as for rover_obs_noise
+int rover_scaler_update(rover_ctx* c, const rover_scaler_update_desc* d, void* stream) {
+    if (!d) return fail(c, ROVER_E_INVALID, "scaler_update: null descriptor");
+    rover_scaler_plan_desc plan;
+    if (d->N < 1 || d->N > 4096) return fail(c, ROVER_E_INVALID, "scaler_update: N = %d outside 1 .. 4096", d->N);
+    if (d->M < 0 || (int64_t)d->M * d->N >= (int64_t)1 << 31) return fail(c, ROVER_E_INVALID, "scaler_update: M = %d is negative or M N >= 2^31", d->M);
+    if (d->M < 2) return fail(c, ROVER_E_INVALID, "scaler_update: M = %d rows, a train call needs at least 2 (the unbiased variance of one row is undefined)", d->M);
+    if (!d->x || !d->mean || !d->var || !d->count || !d->scratch) return fail(c, ROVER_E_INVALID, "scaler_update: x, mean, var, count and scratch must be given (null pointer)");
+    if (d->x_stride < d->N || d->x_stride > (int64_t)1 << 40) return fail(c, ROVER_E_INVALID, "scaler_update: the row stride of x is shorter than its row (N = %d) or above 2^40", d->N);
+    if (!aligned8(d->mean) || !aligned8(d->var) || !aligned8(d->count) || !aligned8(d->scratch))
+        return fail(c, ROVER_E_INVALID, "scaler_update: mean, var, count or scratch is not 8-byte aligned");
+    (void)rover_scaler_plan(d->M, d->N, &plan);
+    if (d->scratch_bytes < plan.scratch_bytes)
+        return fail(c, ROVER_E_INVALID, "scaler_update: scratch of %lld bytes, the plan needs %lld", (long long)d->scratch_bytes, (long long)plan.scratch_bytes);
+    {
+        const Span sx = span_of(d->x, d->x_stride, d->M, d->N, 4), ss = span_of(d->scratch, 1, 1, 1, (size_t)d->scratch_bytes);
+        const Span st[3] = {span_of(d->mean, 1, 1, d->N, 8), span_of(d->var, 1, 1, d->N, 8), span_of(d->count, 1, 1, 1, 8)};
+        for (int i = 0; i < 3; ++i) {
+            if (overlap(st[i], sx) || overlap(st[i], ss)) return fail(c, ROVER_E_INVALID, "scaler_update: the state (mean, var, count) overlaps x or scratch");
+            for (int j = 0; j < i; ++j)
+                if (overlap(st[i], st[j])) return fail(c, ROVER_E_INVALID, "scaler_update: mean, var and count overlap each other");
+            if (d->skip_if && overlap(st[i], span_of(d->skip_if, 1, 1, 1, 4))) return fail(c, ROVER_E_INVALID, "scaler_update: skip_if overlaps the state");
+        }
+        if (overlap(sx, ss)) return fail(c, ROVER_E_INVALID, "scaler_update: scratch overlaps x");
+        if (d->skip_if && overlap(ss, span_of(d->skip_if, 1, 1, 1, 4))) return fail(c, ROVER_E_INVALID, "scaler_update: skip_if overlaps scratch");
+    }
+    if ((uintptr_t)d->skip_if % 4) return fail(c, ROVER_E_INVALID, "scaler_update: skip_if is not 4-byte aligned");
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "scaler_update: null ctx");
+    USE_DEVICE(c);
+    ScalerUpdateArgs a{};
+    a.x = d->x; a.x_stride = d->x_stride;
+    a.M = (uint32_t)d->M; a.N = (uint32_t)d->N; a.rows_per_chunk = (uint32_t)plan.rows_per_chunk; a.n_chunks = (uint32_t)plan.n_chunks;
+    a.partials = (double*)d->scratch + 1;
+    a.mean = d->mean; a.var = d->var; a.count = d->count; a.skip_if = d->skip_if;
+    HIP_TRY(c, launch_scaler_update(a, plan.route == ROVER_SCALER_NARROW ? SCALER_ROUTE_NARROW : SCALER_ROUTE_WIDE, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+int rover_scaler_apply(rover_ctx* c, const rover_scaler_apply_desc* d, void* stream) {
+    if (!d) return fail(c, ROVER_E_INVALID, "scaler_apply: null descriptor");
+    if (d->N < 1 || d->N > 4096) return fail(c, ROVER_E_INVALID, "scaler_apply: N = %d outside 1 .. 4096", d->N);
+    if (d->M < 0 || (int64_t)d->M * d->N >= (int64_t)1 << 31) return fail(c, ROVER_E_INVALID, "scaler_apply: M = %d is negative or M N >= 2^31", d->M);
+    if (!(d->epsilon >= 0.0) || !std::isfinite(d->epsilon) || !(d->clip >= 0.0) || !std::isfinite(d->clip))
+        return fail(c, ROVER_E_INVALID, "scaler_apply: epsilon = %g or clip = %g is negative or not finite", d->epsilon, d->clip);
+    if (!d->mean || !d->var) return fail(c, ROVER_E_INVALID, "scaler_apply: mean and var must be given (null pointer)");
+    if (!aligned8(d->mean) || !aligned8(d->var)) return fail(c, ROVER_E_INVALID, "scaler_apply: mean or var is not 8-byte aligned");
+    if (d->M > 0) {
+        if (!d->x || !d->y) return fail(c, ROVER_E_INVALID, "scaler_apply: x and y must be given (null pointer)");
+        const int64_t max_stride = (int64_t)1 << 40;
+        if (d->x_stride < d->N || d->y_stride < d->N || d->x_stride > max_stride || d->y_stride > max_stride)
+            return fail(c, ROVER_E_INVALID, "scaler_apply: a row stride is shorter than its row (N = %d) or above 2^40", d->N);
+        const Span sx = span_of(d->x, d->x_stride, d->M, d->N, 4), sy = span_of(d->y, d->y_stride, d->M, d->N, 4);
+        if (overlap(sx, sy) && !(d->x == d->y && d->x_stride == d->y_stride))
+            return fail(c, ROVER_E_INVALID, "scaler_apply: y overlaps x without being the same array (same pointer and stride)");
+        for (const Span& st : {span_of(d->mean, 1, 1, d->N, 8), span_of(d->var, 1, 1, d->N, 8)})
+            if (overlap(st, sx) || overlap(st, sy)) return fail(c, ROVER_E_INVALID, "scaler_apply: the state (mean, var) overlaps x or y");
+    }
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "scaler_apply: null ctx");
+    if (d->M == 0) return ROVER_OK;
+    USE_DEVICE(c);
+    ScalerApplyArgs a{d->x, d->x_stride, d->y, d->y_stride, (uint32_t)d->M, (uint32_t)d->N, d->mean, d->var, (float)d->epsilon, (float)d->clip};
+    HIP_TRY(c, launch_scaler_apply(a, d->inverse != 0, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
 // The descriptor is validated before the ctx is looked at, as for rover_obs_noise
 int rover_motion_step(rover_ctx* c, const rover_motion_desc* d, void* stream) {
     if (!d) return fail(c, ROVER_E_INVALID, "motion_step: null descriptor");

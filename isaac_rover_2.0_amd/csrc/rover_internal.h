@@ -352,6 +352,29 @@ struct ObsNoiseArgs {
 };
 hipError_t launch_obs_noise(const ObsNoiseArgs& a, hipStream_t s);
 
+// skrl's RunningStandardScaler (rover_scaler_update / rover_scaler_apply of the C ABI, validated; rover_scaler.hip).  The plan's numbers
+// come from rover_scaler_plan; `partials` points one double past the scratch's start (the header double keeps the count the call
+// started from): three planes [n_chunks][N] of count, mean, M2.
+#define SCALER_ROUTE_WIDE 0
+#define SCALER_ROUTE_NARROW 1
+#define SCALER_NARROW_MAX_N 8u             // narrow route (rows split over a workgroup's lanes) for N <= 8
+struct ScalerUpdateArgs {
+    const float* x; int64_t x_stride;      // [M, N] rows at x_stride floats
+    uint32_t M, N, rows_per_chunk, n_chunks;
+    double* partials;
+    double *mean, *var, *count;            // [N], [N], [1]: the caller's state
+    const int32_t* skip_if;                // optional [1]: nonzero when the kernel runs = the state stays unchanged
+};
+hipError_t launch_scaler_update(const ScalerUpdateArgs& a, int route, hipStream_t s);      // two launches: moments, fold
+struct ScalerApplyArgs {
+    const float* x; int64_t x_stride;
+    float* y; int64_t y_stride;            // y == x (and the same stride): in place
+    uint32_t M, N;
+    const double *mean, *var;
+    float epsilon, clip;
+};
+hipError_t launch_scaler_apply(const ScalerApplyArgs& a, bool inverse, hipStream_t s);
+
 // The terrain-following motion model (rover_motion_step of the C ABI, validated; rover_motion.hip): `substeps` sub-steps of length dt on
 // the poses in place, one thread per env, then the optional copy of the joint targets into the joint state.
 #define MOTION_WHEELS 6
