@@ -977,9 +977,7 @@ __global__ void __launch_bounds__(64 * CULL_WPB) cull_scan_kernel(CULL_SCAN_ARGS
 #define LN_QGOOD_H 0.2f              // (fp16 proof: 0.2 / 0.35 / 0.5 / 0.7 -> 477 / 506 / 536 / 545 us for the terrain part)
 #define LN_QCAP 1024u                // 2-byte queue entries per wave
 #define LN_PAD 5.0e-5                // added to a triangle's radius: what pays for the relative coordinates' rounding (header comment: >= 1e-6 would do)
-#define LN_AB 8u                     // pairs an item keeps in flight: test (A) only (a record per pair) ...
-#define LN_ABB 4u                    // ... tests (A) and (B) (two records per pair)
-#define LN_ABB4 4u                   // ... tests (A) and (B4) (f32 proof: 16 + 8 bytes per pair)
+#define LN_AB 8u                     // records an item keeps in flight: a chunk's (A) records, then — an (A) + (B) item — its (B) records in the same registers
 // Test (B) of the f32 proof on 4-byte records ("B4", the second half of a cell's row: 8 B per pair instead of 16).  A record holds the
 // triangle's unit normal as three signed 10-bit integers n4 = round(511 n^) (bits 0-9, 10-19, 20-29), n^ the direction of the ctab record's
 // fp16 normal (within 5e-4 of N / |N|: fp16 components of a vector of length r / tau >= 1); the builder decodes its own code and keeps it only
@@ -1582,7 +1580,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     const uint32_t n_a = (act && !allc && !ab) ? L : 0u, n_b = ab ? L : 0u;
     // The items, in the order bin by bin, chunk by chunk, the bin's rays that test the chunk: lanes that read the same 128-byte line of a
     // record row sit next to each other.  Position of item (ray, k) = items of the bins before + items of the bin's chunks before k + the
-    // ray's rank among the bin's rays with more than k items.  Two lists: the (A) items, behind them the (A) + (B) items.
+    // ray's rank among the bin's rays with more than k items.  Two lists in one array: the (A) items, behind them the (A) + (B) items.
     const uint32_t cellm = rowi | (par << 30) | (map << 31), key = cellm & ~(1u << 30);       // (the ROW: lanes that read the same line sit side by side across both cells of a shared row)
     const uint32_t prevk = (uint32_t)__shfl_up((int)key, 1, 64);
     const bool head = act && (lane == 0u || key != prevk);
@@ -1617,40 +1615,32 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     // the tests: 64 items per round, the records straight from the cell's row (L1 / L2: a chunk is read by the bin's rays side by side)
     // (BX: the records are boxes.  A wave whose rays read tables of both forms runs its lists once per form, `mixed`: an item then keeps the
     // mask of the pass that read its records for what they are)
-    auto rounds = [&](uint32_t it0, uint32_t it1, auto AB, auto BX, bool mixed) {
-        constexpr bool kAB = decltype(AB)::value, kBX = decltype(BX)::value;
-        for (uint32_t base = it0; base < it1; base += 64u) {
-            const bool ok = base + lane < it1;
-            const uint32_t it = s_items[ok ? base + lane : it0];
+    // One walk over both lists: a round takes items base .. base + 63 and runs test (A) for all of them, then — only in a round that reaches
+    // into the (A) + (B) part, which the wave knows from base, ia_tot and ib_tot — test (B) in the lanes whose item lies there.  The few
+    // (A) + (B) items of a terrain wave so ride in the empty lanes of its last (A) round instead of a round of their own (EXPERIMENTS.md 9.13).
+    const uint32_t it_tot = ia_tot + ib_tot;
+    auto rounds = [&](auto BX, bool mixed) {
+        constexpr bool kBX = decltype(BX)::value;
+        static_assert(LN_CH <= LN_AB, "test (B) takes a chunk's records into the registers test (A) has released");
+        for (uint32_t base = 0u; base < it_tot; base += 64u) {
+            const bool ok = base + lane < it_tot;
+            const uint32_t it = s_items[ok ? base + lane : 0u];
             const uint32_t rl = it & 63u, ch = it >> 6;
             const float4 ra = s_ray[2u * rl], rb = s_ray[2u * rl + 1u];
             // (the row's address comes out of LDS as an integer: say that it is global memory, or the loads are FLAT ones — which count on
             // both wait counters and so cannot be waited for one by one)
             typedef uint32_t U4 __attribute__((ext_vector_type(4)));
             typedef const U4 __attribute__((address_space(1))) * GRow;
-            const GRow cp = (GRow)((uintptr_t)((uint64_t)__float_as_uint(rb.z) | ((uint64_t)__float_as_uint(rb.w) << 32))) + ch * LN_CH;
-            // (the (B) records of the row lie pp records behind the (A) records; pp by the map of the item's ray)
-            const uint32_t ppi = kAB ? ((uint32_t)__builtin_amdgcn_ds_bpermute((int)(rl << 2), (int)map) ? pp01 >> 16 : pp01 & 0xffffu) : 0u;
+            const GRow row = (GRow)((uintptr_t)((uint64_t)__float_as_uint(rb.z) | ((uint64_t)__float_as_uint(rb.w) << 32)));
+            const GRow cp = row + ch * LN_CH;
             uint32_t mask = 0;
-            constexpr uint32_t NB = kAB ? (H ? LN_ABB : LN_ABB4) : LN_AB;            // records in flight per batch
+            uint4 rec[LN_AB];                                   // the records in flight: a batch of (A) records, then the chunk's (B) records
 #pragma unroll 1                                                // (one batch of LN_AB pairs at a time: with 16-pair chunks fully unrolled the compiler kept all in flight, 128 VGPRs and spills)
-            for (uint32_t hf = 0; hf < LN_CH / NB; ++hf) {
-                uint4 rec[NB], nrc[kAB ? NB : 1u];
+            for (uint32_t hf = 0; hf < LN_CH / LN_AB; ++hf) {
 #pragma unroll
-                for (uint32_t i = 0; i < NB; ++i) {
-                    { const U4 v = cp[hf * NB + i]; rec[i] = make_uint4(v.x, v.y, v.z, v.w); }
-                    if (kAB && H) { const U4 v = cp[ppi + hf * NB + i]; nrc[i] = make_uint4(v.x, v.y, v.z, v.w); }
-                }
-                if (kAB && !H) {      // B4 records, 8 B per pair: two pairs per 16-byte load (the pair's chunk starts ch * 64 bytes into the B4 rows)
-                    const GRow bp = (GRow)((uintptr_t)((uint64_t)__float_as_uint(rb.z) | ((uint64_t)__float_as_uint(rb.w) << 32))) + ppi + ch * (LN_CH / 2u);
+                for (uint32_t i = 0; i < LN_AB; ++i) { const U4 v = cp[hf * LN_AB + i]; rec[i] = make_uint4(v.x, v.y, v.z, v.w); }
 #pragma unroll
-                    for (uint32_t i = 0; i < NB; i += 2) {
-                        const U4 v = bp[(hf * NB + i) >> 1];
-                        nrc[i] = make_uint4(v.x, v.y, 0u, 0u); nrc[i + 1u] = make_uint4(v.z, v.w, 0u, 0u);
-                    }
-                }
-#pragma unroll
-                for (uint32_t i = 0; i < NB; ++i) {
+                for (uint32_t i = 0; i < LN_AB; ++i) {
                     const uint4 r = rec[i];
                     uint32_t sg;
                     if (kBX) {      // {Mx, My | Mz, ex | ey, ez | mrg, -}: max over the axes d x e_i of |(d x h)_i| - sum_j e_j |d_k| - (alpha' |h|_1 + mrg) >= +0
@@ -1679,22 +1669,43 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
                         sg |= __float_as_uint(u);
                     }
                     }
-                    if (kAB && !H) {      // (B) on B4 records: (n4 . d)^2 - LN_B4_C >= +0 for both triangles, or the pair stays a candidate
-                        const uint4 n = nrc[i];
+                    mask = __builtin_amdgcn_alignbit(mask, sg, 31);       // (mask << 1) | sign: a pair is a candidate unless every u >= +0
+                }
+            }
+            if (ib_tot && base + 64u > ia_tot) {                // (wave-uniform) the round holds (A) + (B) items: test (B) in their lanes, ORed into the (A) mask
+                // (the (B) records of the row lie pp records behind the (A) records; pp by the map of the item's ray)
+                const uint32_t ppi = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(rl << 2), (int)map) ? pp01 >> 16 : pp01 & 0xffffu;
+                if (ok && base + lane >= ia_tot) {
+                    uint32_t mb = 0;
+                    if (!H) {      // B4 records, 8 B per pair: two pairs per 16-byte load (the pair's chunk starts ch * 64 bytes into the B4 rows)
+                        const GRow bp = row + ppi + ch * (LN_CH / 2u);
+#pragma unroll
+                        for (uint32_t i = 0; i < LN_CH / 2u; ++i) { const U4 v = bp[i]; rec[i] = make_uint4(v.x, v.y, v.z, v.w); }
+                        // (B) on B4 records: (n4 . d)^2 - LN_B4_C >= +0 for both triangles, or the pair stays a candidate
                         auto b4t = [&](uint32_t c) {
                             const float nx = (float)__builtin_amdgcn_sbfe((int)c, 0, 10), ny = (float)__builtin_amdgcn_sbfe((int)c, 10, 10),
                                         nz = (float)__builtin_amdgcn_sbfe((int)c, 20, 10);
                             float t = nx * ra.w; t = __builtin_fmaf(ny, rb.x, t); t = __builtin_fmaf(nz, rb.y, t);
                             return __builtin_fmaf(t, t, -LN_B4_C);
                         };
-                        sg |= __float_as_uint(b4t(n.x)) | __float_as_uint(b4t(n.y));
-                    } else if (kAB) {      // (B): (n . d)^2 - r2B >= +0 for both triangles, or the pair stays a candidate
-                        const uint4 n = nrc[i];
-                        float t0 = mix_mul<0>(n.x, ra.w); t0 = mix_fma<1>(n.x, rb.x, t0); t0 = mix_fma<0>(n.y, rb.y, t0);
-                        float t1 = mix_mul<0>(n.z, ra.w); t1 = mix_fma<1>(n.z, rb.x, t1); t1 = mix_fma<0>(n.w, rb.y, t1);
-                        sg |= __float_as_uint(mix_fms_hi(t0, t0, n.y)) | __float_as_uint(mix_fms_hi(t1, t1, n.w));
+#pragma unroll
+                        for (uint32_t i = 0; i < LN_CH / 2u; ++i) {
+                            const uint4 n = rec[i];
+                            mb = __builtin_amdgcn_alignbit(mb, __float_as_uint(b4t(n.x)) | __float_as_uint(b4t(n.y)), 31);
+                            mb = __builtin_amdgcn_alignbit(mb, __float_as_uint(b4t(n.z)) | __float_as_uint(b4t(n.w)), 31);
+                        }
+                    } else {       // (B): (n . d)^2 - r2B >= +0 for both triangles, or the pair stays a candidate
+#pragma unroll
+                        for (uint32_t i = 0; i < LN_CH; ++i) { const U4 v = cp[ppi + i]; rec[i] = make_uint4(v.x, v.y, v.z, v.w); }
+#pragma unroll
+                        for (uint32_t i = 0; i < LN_CH; ++i) {
+                            const uint4 n = rec[i];
+                            float t0 = mix_mul<0>(n.x, ra.w); t0 = mix_fma<1>(n.x, rb.x, t0); t0 = mix_fma<0>(n.y, rb.y, t0);
+                            float t1 = mix_mul<0>(n.z, ra.w); t1 = mix_fma<1>(n.z, rb.x, t1); t1 = mix_fma<0>(n.w, rb.y, t1);
+                            mb = __builtin_amdgcn_alignbit(mb, __float_as_uint(mix_fms_hi(t0, t0, n.y)) | __float_as_uint(mix_fms_hi(t1, t1, n.w)), 31);
+                        }
                     }
-                    mask = __builtin_amdgcn_alignbit(mask, sg, 31);       // (mask << 1) | sign: a pair is a candidate unless every u >= +0
+                    mask |= mb;
                 }
             }
             const bool mine = !mixed || ((forms >> (uint32_t)__builtin_amdgcn_ds_bpermute((int)(rl << 2), (int)map)) & 1u) == (kBX ? 1u : 0u);
@@ -1706,14 +1717,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(LN_WAVES, 8))) __launch_bound
     const uint64_t on1 = __builtin_amdgcn_ballot_w64(act && map != 0u), on0 = __builtin_amdgcn_ballot_w64(act && map == 0u);
     const bool any_box = !H && ((on0 && (forms & 1u)) || (on1 && (forms & 2u)));
     const bool any_sph = H || (on0 && !(forms & 1u)) || (on1 && !(forms & 2u));
-    if (any_sph) {
-        rounds(0u, ia_tot, std::false_type{}, std::false_type{}, any_box);
-        if (ib_tot) rounds(ia_tot, ia_tot + ib_tot, std::true_type{}, std::false_type{}, any_box);
-    }
-    if (!H && any_box) {
-        rounds(0u, ia_tot, std::false_type{}, std::true_type{}, any_sph);
-        if (ib_tot) rounds(ia_tot, ia_tot + ib_tot, std::true_type{}, std::true_type{}, any_sph);
-    }
+    if (any_sph) rounds(std::false_type{}, any_box);
+    if (!H && any_box) rounds(std::true_type{}, any_sph);
     wave_lds_sync();
     // candidates -> queue entries; the exact phase whenever the queue could not take the next ray's entries (rare) and at the end
     auto flush = [&]() {
