@@ -501,6 +501,27 @@ ROVER_API const char *rover_linear_route_bf16(int32_t M, int32_t K, int32_t N);
 /* Host only (no ctx, no device): out[i] = the bf16 rounding of in[i] as an f32 — the one definition the kernels share. */
 ROVER_API int rover_bf16_round(const float *in, int64_t n, float *out);
 
+/* ---- Operand rules: the array arguments of the learning entry points ------------------------------------------------------------------ */
+/* rover_gae, rover_linear_backward, rover_linear_dgrad, rover_ppo_loss, rover_optim_create / _step, rover_gru_cell / _bf16 / _train,
+ * rover_gru_cell_backward, rover_gated_sum / _backward, rover_obs_noise and rover_scaler_update / _apply check their arrays by one set of
+ * rules (csrc/rover_operands.h).  An operand is (pointer, row stride in elements, rows, cols); a one-row array has no stride argument.
+ * An operand the call does not look at (an input no requested output needs, stats_in outside NORMALIZE_GIVEN, ...) is not checked at all,
+ * whatever its pointer and stride; an optional operand given as NULL neither.  For the others, in this order, each rule over all operands
+ * before the next; the first breach is ROVER_E_INVALID before any launch, nothing is written, and rover_last_error names the operand(s):
+ *   1. a required operand with elements is NULL;
+ *   2. a row stride is outside cols .. 2^40 (where an entry point says so a stride of 0 is legal too: one row serves every row);
+ *   3. a pointer is not aligned as the entry point requires;
+ *   4. "extent too large": rows x stride x element size passes 2^62 bytes, or the array would pass the end of the address space — so no
+ *      extent the later rules compute can wrap;
+ *   5. a written operand overlaps a read one ("<b> overlaps <a>", a before b in the entry point's argument order).  Where an entry point
+ *      says a pair may be the same array it may coincide exactly, same pointer and same stride; any other overlap of the two is refused
+ *      ("... without being the same array");
+ *   6. two written operands overlap.  State an entry point updates, and the few small records noted below, count as written.
+ * Operands that are only read may overlap each other.  Shape, range and scalar checks come first, and an empty call (M = 0, E = 0)
+ * returns ROVER_OK before any pointer is asked for, unless its entry says otherwise.
+ * The ctx is looked at last: with a NULL ctx every refusal above is still made and reported through rover_last_error(NULL), and a call
+ * that keeps every rule is refused with "<entry>: null ctx" (ROVER_E_INVALID). */
+
 /* ---- the rollout side of PPO: returns and advantages of a stored rollout in one pass (skrl's compute_gae inside PPO._update) -------- */
 /* The reference trains through skrl: RandomMemory(memory_size=60) (train.py:82), rollouts 60, discount_factor 0.99, lambda 0.95
  * (cfg/trainSKRL/RoverPPOSKRL.yaml:12-16).  skrl is no part of this repository: the semantics are restated from a reading of skrl
@@ -527,9 +548,9 @@ ROVER_API int rover_bf16_round(const float *in, int64_t n, float *out);
  * The call allocates nothing and does not synchronise (the partials' buffer belongs to the ctx since rover_create): it can be captured
  * in a graph.  Calls of one ctx run on ONE stream at a time.  Launches: one (RAW or NORMALIZE_GIVEN without stats_out), else two (the
  * scan, then the kernel that merges the partials, writes stats_out and normalises); none for E = 0 (ROVER_OK).
- * ROVER_E_INVALID before any launch: a NULL required pointer, a stride < E or > 2^40, T outside 1 .. 4096, E < 0, T E >= 2^31, an unknown
- * normalize, NORMALIZE with T E < 2, returns overlapping values other than as the same array, advantages overlapping any other array, stats_out / stats_in
- * overlapping an array or each other. */
+ * ROVER_E_INVALID before any launch: T outside 1 .. 4096, E < 0, T E >= 2^31, an unknown normalize, NORMALIZE with T E < 2, and the
+ * operand rules: stats_out is optional, returns and values may be the same array, stats_in counts under NORMALIZE_GIVEN only and then
+ * stands clear of every array and of stats_out like a written operand. */
 #define ROVER_GAE_RAW             0
 #define ROVER_GAE_NORMALIZE       1
 #define ROVER_GAE_NORMALIZE_GIVEN 2
@@ -569,8 +590,9 @@ ROVER_API int rover_combine_moments(const double *a, const double *b, double *ou
  * dweight / dbias: an f32-input MFMA reduction over M, cut into splits whose f32 partials go to a scratch buffer of the ctx and are
  * added in the order of the splits — no floating-point atomics, the same inputs give the same bits on every run.  The scratch follows
  * the chain entry points' rule: it grows on demand (the first call of a size outside a stream capture), one stream per ctx at a time.
- * ROVER_E_INVALID before any launch: M < 0, K < 0, N outside 1 .. 256, K > 256 with dx, an unknown activation, a NULL required pointer, a
- * row stride shorter than its row or above 2^40, an output overlapping an input or another output. */
+ * ROVER_E_INVALID before any launch: M < 0, K < 0, N outside 1 .. 256, K > 256 with dx, an unknown activation, and the operand rules: y
+ * counts only with an activation, x only for dweight with K > 0, weight and dx only for dx with K > 0; dbias is optional.  M = 0 needs
+ * no pointer, but the strides of dy, y, x and dx are still checked. */
 ROVER_API int rover_linear_backward(rover_ctx *ctx, const float *x, int64_t x_stride, const float *y, int64_t y_stride, const float *dy,
                                     int64_t dy_stride, int32_t M, int32_t K, const float *weight, int32_t N, int32_t activation, float *dx,
                                     int64_t dx_stride, float *dweight, float *dbias, void *stream);
@@ -584,8 +606,8 @@ ROVER_API const char *rover_linear_backward_route(int32_t M, int32_t K, int32_t 
 /* rover_linear_dgrad: the dx of rover_linear_backward alone, for ANY N >= 1 and K >= 1: dx [M, K] = (dy * act'(y)) W with W [N][K]
  * contiguous, the same activations and derivative rules, the same kernel (a reduction over N in 32-wide slabs, one accumulator per
  * element in the order of n) on a route without the 256 limits — the recurrent student's layers need it (K = 300, N = 900 / 1 746).
- * y may be NULL with activation 0.  dx overlaps nothing the call reads.  M = 0 launches nothing.  ROVER_E_INVALID before any launch as
- * for rover_linear_backward.  Allocates nothing, does not synchronise, no atomics, capturable. */
+ * y counts only with an activation.  M = 0 launches nothing.  ROVER_E_INVALID before any launch: the shapes, an unknown activation, the
+ * operand rules.  Allocates nothing, does not synchronise, no atomics, capturable. */
 ROVER_API int rover_linear_dgrad(rover_ctx *ctx, const float *y, int64_t y_stride, const float *dy, int64_t dy_stride, int32_t M, int32_t K,
                                  const float *weight, int32_t N, int32_t activation, float *dx, int64_t dx_stride, void *stream);
 /* What rover_linear_dgrad would launch — host only: "dgrad<NT,NW>xNY" (linear_dgrad_kernel<NT, NW> on NY column tiles of dx): below
@@ -612,9 +634,9 @@ ROVER_API const char *rover_linear_dgrad_route(int32_t M, int32_t K, int32_t N);
  * moments: the same inputs give the same bits.  NaN and Inf propagate as the formulas say.
  * The partials' buffer belongs to the ctx since rover_create: the call allocates nothing, does not synchronise and can be captured.
  * Launches: one, plus the merge; none for M = 0 (ROVER_OK).  One stream per ctx at a time.
- * ROVER_E_INVALID before any launch: a NULL pointer (M > 0), A outside 1 .. 16, M < 0, a reduction other than ROVER_REDUCE_SUM, min_log_std >
- * max_log_std with clip_log_std, a negative (or NaN) ratio_clip / value_clip, a row stride < A or > 2^40, an output overlapping an input
- * or another output. */
+ * ROVER_E_INVALID before any launch: A outside 1 .. 16, M < 0, a reduction other than ROVER_REDUCE_SUM, min_log_std > max_log_std with
+ * clip_log_std, a negative (or NaN) ratio_clip / value_clip, and the operand rules (every pointer is required; d_mean, d_value,
+ * d_log_std and stats are written). */
 typedef struct {
     int32_t M, A;                 /* rows of the minibatch; 1 .. 16 action components                                            */
     const float *mean;      int64_t mean_stride;       /* [M, A] the actor's output ("mean_actions")                            */
@@ -655,10 +677,11 @@ ROVER_API int rover_optim_plan(int32_t n_tensors, const int64_t *numel, rover_op
  * partial per chunk and a 16-byte record per handle, all allocated HERE (never in the step) and freed by rover_optim_destroy or by
  * rover_destroy.  *handle >= 0.  A destroyed handle's number may be given out again.
  * ROVER_E_INVALID before anything is allocated: a NULL descriptor / handle / array, n_tensors outside 1 .. 256, a negative numel,
- * total elements >= 2^31, a NULL or misaligned params[i] / grads[i] with numel[i] > 0, NULL exp_avg / exp_avg_sq with total > 0, NULL
- * step / stopped, a parameter overlapping its own or another tensor's gradient, another parameter, exp_avg, exp_avg_sq, step or
- * stopped; a gradient overlapping exp_avg, exp_avg_sq, step or stopped; exp_avg, exp_avg_sq, step and stopped overlapping each other.
- * (Two gradients may overlap: they are only read.)  rover_optim_destroy: ROVER_E_INVALID for a handle that is not live. */
+ * total elements >= 2^31; the operand rules for the state (step 8-byte aligned, stopped, exp_avg and exp_avg_sq 4-byte aligned, all
+ * written; the moments have no element when the total is 0); and, by the same bounded extents, for the lists: a NULL or misaligned
+ * params[i] / grads[i] with numel[i] > 0, a parameter overlapping its own or another tensor's gradient, another parameter or the state,
+ * a gradient overlapping the state.  (Two gradients may overlap: they are only read.)  The ctx is needed only to keep the handle.
+ * rover_optim_destroy: ROVER_E_INVALID for a handle that is not live. */
 typedef struct {
     int32_t n_tensors;
     float *const *params;         /* host [n_tensors] of device pointers */
@@ -694,9 +717,9 @@ ROVER_API int rover_optim_destroy(rover_ctx *ctx, int32_t handle);
  * Gradients are READ ONLY: unlike torch's clip_grad_norm_, the clipped gradient g' is not written back.  NaN and Inf propagate as the
  * formulas say.  No floating-point atomics: the same inputs give the same bits on every run, whatever the alignment of the tensors
  * (16-byte loads and stores where a tensor's bases allow, scalar ones otherwise, the same arithmetic in the same order).
- * ROVER_E_INVALID before any launch: a NULL descriptor, a handle that is not live, lr < 0 or not finite, beta1 / beta2 outside [0, 1),
- * eps < 0 or not finite, a NaN grad_norm_clip or gate_threshold, gate or norm_out not 8-byte aligned, norm_out overlapping gate, a
- * parameter, a gradient, exp_avg, exp_avg_sq, step or stopped. */
+ * ROVER_E_INVALID before any launch, in this order: a NULL descriptor, lr < 0 or not finite, beta1 / beta2 outside [0, 1), eps < 0 or
+ * not finite, a NaN grad_norm_clip or gate_threshold; the operand rules for gate and norm_out (both optional, 8-byte aligned); a NULL
+ * ctx; a handle that is not live; norm_out overlapping a parameter, a gradient, exp_avg, exp_avg_sq, step or stopped of the handle. */
 typedef struct {
     double lr, beta1, beta2, eps;
     double grad_norm_clip;        /* <= 0: no clipping                                                          */
@@ -721,11 +744,10 @@ ROVER_API int rover_optim_step(rover_ctx *ctx, int32_t handle, const rover_optim
  * x [M, K], h_in [M, H] and h_out [M, H] are f32 rows at a row stride in floats (column slices of wider tensors will do).
  * reset_mask: optional uint8 [M]; a row with a non-zero byte reads its h_in as zero, in the products and in z * h (an addition to
  * the reference, whose student_loader.act never resets the state; NULL = the reference's behaviour).
- * One workgroup computes a 32-column tile of h' from whole rows of h_in that other workgroups are still reading: h_out must not
- * overlap h_in (nor x, the weights, the biases or the mask) — an overlap is refused with ROVER_E_INVALID and nothing is written.
- * M = 0 launches nothing; K = 0 is legal (x, w_ih unread).  Widths: H = 1 .. 2 097 120 (65 535 tiles of 32 columns), K >= 0; anything else,
- * a stride shorter than its row or above 2^40, or a missing array: ROVER_E_INVALID.  Neither [M, 3H] pre-activation tensor is
- * written to memory.  The call allocates nothing, does not synchronise, uses no atomics (the same inputs give the same bits, and a
+ * One workgroup computes a 32-column tile of h' from whole rows of h_in that other workgroups are still reading: h_out may not even
+ * be h_in.  M = 0 launches nothing; K = 0 is legal (x and w_ih do not count).  Widths: H = 1 .. 2 097 120 (65 535 tiles of 32 columns),
+ * K >= 0; anything else, or a breach of the operand rules (b_ih, b_hh and reset_mask are optional; h_out is the one written operand):
+ * ROVER_E_INVALID.  Neither [M, 3H] pre-activation tensor is written to memory.  The call allocates nothing, does not synchronise, uses no atomics (the same inputs give the same bits, and a
  * row's result does not depend on the other rows) and can be captured in a graph. */
 ROVER_API int rover_gru_cell(rover_ctx *ctx, const float *x, int64_t x_stride, const float *h_in, int64_t h_in_stride, int32_t M, int32_t K,
                              int32_t H, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
@@ -757,7 +779,7 @@ ROVER_API const char *rover_gru_cell_route_bf16(int32_t M, int32_t K, int32_t H)
 /* rover_gru_cell_train: rover_gru_cell with one more output for the backward, gates [M, 4H] at a row stride (>= 4H): r | z | n | q with
  * q = s_hn + b_hn as written above.  h_out has the same bits as rover_gru_cell's on the same inputs (the same kernel body; the extra
  * stores are a template flag of the epilogue, the inference instantiations are unchanged) and the route is rover_gru_cell_route's.
- * gates overlaps neither h_out nor anything the call reads.  Otherwise as rover_gru_cell. */
+ * gates is a second written operand (required here).  Otherwise as rover_gru_cell. */
 ROVER_API int rover_gru_cell_train(rover_ctx *ctx, const float *x, int64_t x_stride, const float *h_in, int64_t h_in_stride, int32_t M,
                                    int32_t K, int32_t H, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
                                    const uint8_t *reset_mask, float *h_out, int64_t h_out_stride, float *gates, int64_t gates_stride,
@@ -776,8 +798,8 @@ ROVER_API int rover_gru_cell_train(rover_ctx *ctx, const float *x, int64_t x_str
  * and dh_in is 0 on a reset row: nothing flows across an episode boundary.  The weight gradients are the caller's reductions over all
  * time steps (dW_ih = dgi^T x, dW_hh = dgh^T h with reset rows of h zeroed: rover_linear_backward), and dx = dgi W_ih is one
  * rover_linear_dgrad.  dgh is formed from gates while the product stages it; the workgroups of one column tile store dgi and dgh.
- * All arrays are f32 rows at a row stride in floats.  No output overlaps an input or another output (ROVER_E_INVALID, nothing is
- * written).  M = 0 launches nothing.  Allocates nothing, does not synchronise, no atomics (the same inputs give the same bits, and a
+ * All arrays are f32 rows at a row stride in floats.  Operand rules: dh_next and reset_mask are optional; dgi, dgh and dh_in are
+ * written.  M = 0 launches nothing.  Allocates nothing, does not synchronise, no atomics (the same inputs give the same bits, and a
  * row's result does not depend on the other rows), capturable. */
 ROVER_API int rover_gru_cell_backward(rover_ctx *ctx, const float *dh_above, int64_t dh_above_stride, const float *dh_next,
                                       int64_t dh_next_stride, const float *gates, int64_t gates_stride, const float *h_in,
@@ -791,16 +813,16 @@ ROVER_API const char *rover_gru_cell_backward_route(int32_t M, int32_t H);
 /* rover_gated_sum: out = add + mul * sigmoid(pre), elementwise over [M, N] in one launch (sigmoid as above; the product, then the sum).
  * The belief x_b + l_e * sigmoid(x_a) (student_model.py:79-85; x_a arrives LeakyReLU'd: ga's last Layer has its activation before the
  * nn.Sigmoid) and the decoder's decoded + e * sigmoid(gate) (:121-131).  All four arrays are f32 rows at a row stride in floats; an
- * INPUT's stride may be 0 (its one row serves every output row), otherwise strides are >= N and <= 2^40; M N < 2^38.  out overlaps no
- * input (ROVER_E_INVALID).  M = 0 launches nothing.  Allocates nothing, does not synchronise, capturable. */
+ * INPUT's stride may be 0 (its one row serves every output row), out's may not; M N < 2^38.  out may not be an input, not even
+ * exactly (operand rules).  M = 0 launches nothing.  Allocates nothing, does not synchronise, capturable. */
 ROVER_API int rover_gated_sum(rover_ctx *ctx, const float *add, int64_t add_stride, const float *mul, int64_t mul_stride, const float *pre,
                               int64_t pre_stride, int32_t M, int32_t N, float *out, int64_t out_stride, void *stream);
 
 /* rover_gated_sum_backward: for out = add + mul * sigmoid(pre) and d_out [M, N], with s = sigmoid(pre) as the forward evaluates it:
  *   d_mul = d_out * s          d_pre = (d_out * mul) * (s * (1 - s))          (d_add is d_out itself and is not written)
  * Each output is optional (NULL).  mul and pre may have a row stride of 0 as in the forward; d_out, d_mul and d_pre are per row (stride
- * >= N): summing the rows of an output whose input was one shared row is the caller's job.  mul is read only for d_pre.  No output
- * overlaps an input or the other output.  M = 0 launches nothing.  Allocates nothing, does not synchronise, capturable. */
+ * >= N): summing the rows of an output whose input was one shared row is the caller's job.  mul counts only for d_pre.  With neither
+ * output the call returns ROVER_OK at once; otherwise the operand rules hold.  M = 0 launches nothing.  Allocates nothing, does not synchronise, capturable. */
 ROVER_API int rover_gated_sum_backward(rover_ctx *ctx, const float *d_out, int64_t d_out_stride, const float *mul, int64_t mul_stride,
                                        const float *pre, int64_t pre_stride, int32_t M, int32_t N, float *d_mul, int64_t d_mul_stride,
                                        float *d_pre, int64_t d_pre_stride, void *stream);
@@ -834,11 +856,9 @@ ROVER_API int rover_gated_sum_backward(rover_ctx *ctx, const float *d_out, int64
  * One launch (csrc/rover_noise.hip); plain vector loads and stores, no atomics.  The call allocates nothing, does not synchronise and can
  * be captured in a graph; one stream per ctx at a time.  M = 0 or F = 0: ROVER_OK, no launch.  out may be exactly in (same pointer and
  * stride): the in-place form, which leaves columns [0, first) alone.
- * ROVER_E_INVALID before any launch — the descriptor is checked before the ctx is looked at, so with a NULL ctx rover_last_error(NULL)
- * names the refusal (a NULL ctx itself is refused last) —: a NULL descriptor; NULL in / out with M F > 0; a row stride < F or > 2^40;
- * M < 0 or F < 0; first outside 0 .. F; C > 2^21; a negative or non-finite sigma; dropout outside [0, 1] or NaN; a non-finite
- * drop_value; row_offset < 0 or row_offset + M > 2^32; out overlapping in other than as the same array; row_scale, episode or step_dev
- * overlapping out. */
+ * ROVER_E_INVALID before any launch: a NULL descriptor; M < 0 or F < 0; first outside 0 .. F; C > 2^21; a negative or non-finite sigma;
+ * dropout outside [0, 1] or NaN; a non-finite drop_value; row_offset < 0 or row_offset + M > 2^32; and, unless M = 0 or F = 0, the
+ * operand rules: row_scale, episode and step_dev are optional, out and in may be the same array.  An empty call still wants a ctx. */
 typedef struct {
     const float *in;        int64_t in_stride;     /* [M, F]                                                                     */
     float *out;             int64_t out_stride;    /* [M, F]; may be exactly in                                                   */
@@ -900,11 +920,11 @@ ROVER_API int rover_obs_noise_threshold(double dropout, uint32_t *thr);
  * clamp is torch.clamp: a NaN stays a NaN in both directions; +-Inf clamps to +-c.  y may be exactly x (same pointer and stride: in
  * place); any other overlap is refused.  M = 0: ROVER_OK, no launch.  Allocates nothing, does not synchronise, capturable.
  *
- * ROVER_E_INVALID before any launch — every check is made before the ctx is looked at, so with a NULL ctx rover_last_error(NULL) names
- * the refusal (a NULL ctx itself is refused last) —: a NULL descriptor or a NULL x, y, mean, var, count or scratch; N outside 1 .. 4096;
- * M < 0 or M N >= 2^31; update with M < 2 (skrl's vb would be a NaN: a documented deviation); a row stride < N or > 2^40; mean, var,
- * count or scratch not 8-byte aligned; the state overlapping x, y, scratch, skip_if or itself; scratch overlapping x; scratch_bytes below
- * the plan's; a negative or non-finite epsilon or clip; y overlapping x other than as the same array. */
+ * ROVER_E_INVALID before any launch: a NULL descriptor; N outside 1 .. 4096; M < 0 or M N >= 2^31; update with M < 2 (skrl's vb would
+ * be a NaN: a documented deviation); scratch_bytes below the plan's; a negative or non-finite epsilon or clip; and the operand rules.
+ * Update: scratch is a written extent of scratch_bytes bytes; mean, var and count are state; those four are 8-byte aligned; skip_if is
+ * optional and 4-byte aligned.  Apply: mean and var (8-byte aligned, required even for M = 0) are only read but stand clear of x, y
+ * and each other like state; x and y count for M > 0 and may be the same array; M = 0 still wants a ctx. */
 #define ROVER_SCALER_WIDE 0
 #define ROVER_SCALER_NARROW 1
 typedef struct {

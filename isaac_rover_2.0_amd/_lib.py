@@ -465,6 +465,32 @@ def scaler_apply_desc(m, n, x=1 << 36, y=1 << 36, x_stride=None, y_stride=None, 
                            mean, var, float(epsilon), float(clip), int(bool(inverse)))
 
 
+def gae_desc(t, e, rewards=1 << 40, values=2 << 40, dones=3 << 40, last_values=4 << 40, returns=5 << 40, advantages=6 << 40, stats_out=None,
+             stats_in=None, normalize=GAE_RAW, gamma=0.99, lam=0.95, **strides):
+    """A rover_gae_desc from plain values (pointers as integers, disjoint by default; ``<name>_stride`` defaults to ``e``)."""
+    st = lambda name: int(strides.pop(name + "_stride", e))
+    d = GaeDesc(int(t), int(e), float(gamma), float(lam), rewards, st("rewards"), values, st("values"), dones, st("dones"), last_values, returns,
+                st("returns"), advantages, st("advantages"), int(normalize), stats_out, stats_in)
+    if strides:
+        raise TypeError(f"gae_desc: unknown arguments {sorted(strides)}")
+    return d
+
+
+def ppo_loss_desc(m, a, mean_stride=None, actions_stride=None, d_mean_stride=None, **ptrs):
+    """A rover_ppo_loss_desc from plain values: skrl's scalars, the strides default to ``a``, every pointer an integer (disjoint fake
+    addresses by default; ``name=None`` or another address through ``ptrs``)."""
+    names = ("mean", "log_std", "actions", "old_log_prob", "advantages", "value", "old_values", "returns", "d_mean", "d_value", "d_log_std", "stats")
+    p = {name: (i + 1) << 40 for i, name in enumerate(names)}
+    if set(ptrs) - set(names):
+        raise TypeError(f"ppo_loss_desc: unknown arguments {sorted(set(ptrs) - set(names))}")
+    p.update(ptrs)
+    a = int(a)
+    st = lambda v: a if v is None else int(v)
+    return PpoLossDesc(int(m), a, p["mean"], st(mean_stride), p["log_std"], p["actions"], st(actions_stride), p["old_log_prob"], p["advantages"], p["value"],
+                       p["old_values"], p["returns"], 1, -20.0, 2.0, REDUCTIONS["sum"], 0.2, 0.2, 1, 0.0, 1.0, p["d_mean"], st(d_mean_stride), p["d_value"],
+                       p["d_log_std"], p["stats"])
+
+
 def motion_desc(e, pos3=_FAKE, quat4=_FAKE, lin=_FAKE, ang=_FAKE, cmd_stride=3, substeps=1, dt=0.05, max_lin=1.0, max_ang=1.0, ride_height=0.3,
                 joint_pos_targets13=None, joint_vel_targets13=None, joint_pos13=None, joint_vel13=None):
     """A rover_motion_desc from plain values (pointers as integers)."""
@@ -568,6 +594,15 @@ def bf16_round(values):
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _rows(t, cols, m):
+    """(pointer, row stride in elements) of ``t`` [m, cols] as the C ABI takes them.  None -> (None, 0); at most one row -> ``cols`` (a
+    one-row tensor's stride(0) means nothing); otherwise stride(0) as it is, the 0 of a row-expanded tensor included: the C layer refuses
+    a stride where it is not allowed, the binding does not invent a dense one."""
+    if t is None:
+        return None, 0
+    return t.data_ptr(), (t.stride(0) if m > 1 else cols)
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -916,8 +951,8 @@ class Engine:
         self._chk(bias, (n,), torch.float32, "bias")
         if out.shape[0] != m or out.shape[1] != n:
             raise RoverError(f"linear_forward: out must be [{m},{n}]")
-        self._check(getattr(self.lib, name)(self._h, _ptr(x), max(x.stride(0), k), m, k, _ptr(weight), _ptr(bias), n,
-                                            self.ACTIVATIONS[activation], _ptr(out), out.stride(0), _stream(self._dev_index)), name)
+        self._check(getattr(self.lib, name)(self._h, *_rows(x, k, m), m, k, _ptr(weight), _ptr(bias), n,
+                                            self.ACTIVATIONS[activation], *_rows(out, n, m), _stream(self._dev_index)), name)
         return out
 
     @staticmethod
@@ -949,8 +984,7 @@ class Engine:
         widths = (C.c_int32 * n)(*[l.weight.shape[0] for l in layers])
         acts = (C.c_int32 * n)(*[self.ACTIVATIONS[l.activation] for l in layers])
         keep.extend((w, b, widths, acts))
-        return ChainDesc(x.data_ptr(), x.stride(0), k0, n, C.addressof(w), C.addressof(b), C.addressof(widths), C.addressof(acts),
-                         out.data_ptr(), out.stride(0))
+        return ChainDesc(*_rows(x, k0, m), k0, n, C.addressof(w), C.addressof(b), C.addressof(widths), C.addressof(acts), *_rows(out, k, m))
 
     def chain_forward(self, x, layers, out, precision="f32"):
         """out = layers[-1](... layers[0](x)) in one kernel; ``layers``: objects with .weight [n, k], .bias [n], .activation.
@@ -973,10 +1007,9 @@ class Engine:
             for t, name in ((copy_src, "copy_src"), (copy_dst, "copy_dst")):
                 if self._f32_rows(t, name, "chain_pair_forward").shape[0] != xa.shape[0] or t.shape[1] < copy_cols:
                     raise RoverError(f"chain_pair_forward: {name} must have the same rows and >= copy_cols columns")
-        self._check(self.lib.rover_mlp_chain_pair_forward(
-            self._h, xa.shape[0], C.byref(da), C.byref(db), _ptr(copy_src) if copy_cols else None, copy_src.stride(0) if copy_cols else 0,
-            _ptr(copy_dst) if copy_cols else None, copy_dst.stride(0) if copy_cols else 0, int(copy_cols), _stream(self._dev_index)),
-            "rover_mlp_chain_pair_forward")
+        copy = lambda t: _rows(t if copy_cols else None, int(copy_cols), xa.shape[0])
+        self._check(self.lib.rover_mlp_chain_pair_forward(self._h, xa.shape[0], C.byref(da), C.byref(db), *copy(copy_src), *copy(copy_dst), int(copy_cols),
+                                                          _stream(self._dev_index)), "rover_mlp_chain_pair_forward")
 
     # ---- the actor's Gaussian head (rover_gauss_head) --------------------------------------------------
     def _gauss_head(self, what, m, log_std, actions, log_prob, mean=None, taken_actions=None, step_dev=None, reduction="sum", **kw):
@@ -994,10 +1027,9 @@ class Engine:
         if step_dev is not None and (not step_dev.is_cuda or step_dev.dtype != torch.int64 or step_dev.numel() != 1):
             raise RoverError(f"{what}: step_dev must be one int64 word on the GPU (read as uint64)")
         dp = lambda t: None if t is None else t.data_ptr()
-        st = lambda t: 0 if t is None else t.stride(0)
-        return gauss_head_desc(a, dp(log_std), dp(actions), dp(log_prob), reduction=reduction, step_dev=dp(step_dev), taken_actions=dp(taken_actions),
-                               taken_stride=st(taken_actions), actions_stride=st(actions), log_prob_stride=st(log_prob), mean=dp(mean),
-                               mean_stride=st(mean), **kw)
+        (tp, ts), (ap, as_), (lp, ls), (mp, ms) = (_rows(t, cols, m) for t, cols in ((taken_actions, a), (actions, a), (log_prob, log_prob.shape[1]), (mean, a)))
+        return gauss_head_desc(a, dp(log_std), ap, lp, reduction=reduction, step_dev=dp(step_dev), taken_actions=tp, taken_stride=ts, actions_stride=as_,
+                               log_prob_stride=ls, mean=mp, mean_stride=ms, **kw)
 
     def chain_act(self, x, layers, mean_out, log_std, actions, log_prob, precision="f32", **head):
         """chain_forward with the Gaussian head on its output (rover_mlp_chain_act): ``mean_out`` receives what chain_forward writes,
@@ -1025,7 +1057,7 @@ class Engine:
             out = torch.empty(int(m), int(a), device=self.device)
         self._f32_rows(out, "out", "policy_noise", (int(m), int(a)))
         self._check(self.lib.rover_policy_noise(self._h, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), _ptr(step_dev), int(row_offset), int(m),
-                                                int(a), _ptr(out), out.stride(0), _stream(self._dev_index)), "rover_policy_noise")
+                                                int(a), *_rows(out, int(a), int(m)), _stream(self._dev_index)), "rover_policy_noise")
         return out
 
     def obs_noise(self, obs, out=None, *, first, sigma_point=0.0, sigma_offset=0.0, dropout=0.0, drop_value=0.0, row_scale=None, episode=None,
@@ -1050,8 +1082,9 @@ class Engine:
         if step_dev is not None and (not step_dev.is_cuda or step_dev.dtype != torch.int64 or step_dev.numel() != 1):
             raise RoverError(f"{what}: step_dev must be one int64 word on the GPU (read as uint64)")
         dp = lambda t: None if t is None else t.data_ptr()
-        desc = obs_noise_desc(m, f, first, dp(obs), dp(out), max(obs.stride(0), f), max(out.stride(0), f), sigma_point, sigma_offset, dropout, drop_value,
-                              dp(row_scale), dp(episode), seed, step, dp(step_dev), row_offset)
+        (ip, is_), (op, os_) = _rows(obs, f, m), _rows(out, f, m)
+        desc = obs_noise_desc(m, f, first, ip, op, is_, os_, sigma_point, sigma_offset, dropout, drop_value, dp(row_scale), dp(episode), seed, step,
+                              dp(step_dev), row_offset)
         self._check(self.lib.rover_obs_noise(self._h, C.byref(desc), _stream(self._dev_index)), "rover_obs_noise")
         return out
 
@@ -1077,7 +1110,7 @@ class Engine:
             raise RoverError(f"{what}: count and a uint8 scratch vector on the GPU must be given")
         if skip_if is not None and (not skip_if.is_cuda or skip_if.dtype != torch.int32 or skip_if.numel() != 1):
             raise RoverError(f"{what}: skip_if must be one int32 word on the GPU")
-        desc = ScalerUpdateDesc(x.data_ptr(), max(x.stride(0), n), m, n, mean.data_ptr(), var.data_ptr(), count.data_ptr(), scratch.data_ptr(),
+        desc = ScalerUpdateDesc(*_rows(x, n, m), m, n, mean.data_ptr(), var.data_ptr(), count.data_ptr(), scratch.data_ptr(),
                                 scratch.numel(), None if skip_if is None else skip_if.data_ptr())
         self._check(self.lib.rover_scaler_update(self._h, C.byref(desc), _stream(self._dev_index)), "rover_scaler_update")
 
@@ -1094,8 +1127,8 @@ class Engine:
         if x.device != self.device or out.device != self.device:
             raise RoverError(f"{what}: x and out must be on {self.device}")
         self._scaler_state(what, n, mean, var)
-        desc = scaler_apply_desc(m, n, x.data_ptr(), out.data_ptr(), max(x.stride(0), n), max(out.stride(0), n), mean.data_ptr(), var.data_ptr(),
-                                 epsilon, clip, inverse)
+        (xp, xs), (yp, ys) = _rows(x, n, m), _rows(out, n, m)
+        desc = scaler_apply_desc(m, n, xp, yp, xs, ys, mean.data_ptr(), var.data_ptr(), epsilon, clip, inverse)
         self._check(self.lib.rover_scaler_apply(self._h, C.byref(desc), _stream(self._dev_index)), "rover_scaler_apply")
         return out
 
@@ -1192,9 +1225,8 @@ class Engine:
         self._chk(b_ih, (3 * hd,), torch.float32, "b_ih")
         self._chk(b_hh, (3 * hd,), torch.float32, "b_hh")
         reset_mask = self._mask(reset_mask, m)
-        self._check(getattr(self.lib, name)(self._h, _ptr(x), max(x.stride(0), k), _ptr(h_in), h_in.stride(0) if m > 1 else hd, m, k, hd, _ptr(w_ih) if k > 0 else None,
-                                            _ptr(w_hh), _ptr(b_ih), _ptr(b_hh), _ptr(reset_mask), _ptr(h_out), h_out.stride(0) if m > 1 else hd,
-                                            _stream(self._dev_index)), name)
+        self._check(getattr(self.lib, name)(self._h, *_rows(x, k, m), *_rows(h_in, hd, m), m, k, hd, _ptr(w_ih) if k > 0 else None, _ptr(w_hh), _ptr(b_ih),
+                                            _ptr(b_hh), _ptr(reset_mask), *_rows(h_out, hd, m), _stream(self._dev_index)), name)
         return h_out
 
     @classmethod
@@ -1218,10 +1250,9 @@ class Engine:
         self._chk(b_ih, (3 * hd,), torch.float32, "b_ih")
         self._chk(b_hh, (3 * hd,), torch.float32, "b_hh")
         reset_mask = self._mask(reset_mask, m)
-        st = lambda t, cols: t.stride(0) if m > 1 else cols
-        self._check(self.lib.rover_gru_cell_train(self._h, _ptr(x), max(x.stride(0), k), _ptr(h_in), st(h_in, hd), m, k, hd, _ptr(w_ih) if k > 0 else None,
-                                                  _ptr(w_hh), _ptr(b_ih), _ptr(b_hh), _ptr(reset_mask), _ptr(h_out), st(h_out, hd), _ptr(gates),
-                                                  st(gates, 4 * hd), _stream(self._dev_index)), "rover_gru_cell_train")
+        self._check(self.lib.rover_gru_cell_train(self._h, *_rows(x, k, m), *_rows(h_in, hd, m), m, k, hd, _ptr(w_ih) if k > 0 else None, _ptr(w_hh),
+                                                  _ptr(b_ih), _ptr(b_hh), _ptr(reset_mask), *_rows(h_out, hd, m), *_rows(gates, 4 * hd, m),
+                                                  _stream(self._dev_index)), "rover_gru_cell_train")
         return h_out
 
     def _mask(self, reset_mask, m):
@@ -1243,10 +1274,9 @@ class Engine:
             self._f32_rows(t, name, what, (m, cols))
         self._chk(w_hh, (3 * hd, hd), torch.float32, "w_hh")
         reset_mask = self._mask(reset_mask, m)
-        st = lambda t, cols: 0 if t is None else (t.stride(0) if m > 1 else cols)
-        self._check(self.lib.rover_gru_cell_backward(self._h, _ptr(dh_above), st(dh_above, hd), _ptr(dh_next), st(dh_next, hd), _ptr(gates), st(gates, 4 * hd),
-                                                     _ptr(h_in), st(h_in, hd), _ptr(reset_mask), _ptr(w_hh), m, hd, _ptr(dgi), st(dgi, 3 * hd), _ptr(dgh),
-                                                     st(dgh, 3 * hd), _ptr(dh_in), st(dh_in, hd), _stream(self._dev_index)), "rover_gru_cell_backward")
+        self._check(self.lib.rover_gru_cell_backward(self._h, *_rows(dh_above, hd, m), *_rows(dh_next, hd, m), *_rows(gates, 4 * hd, m), *_rows(h_in, hd, m),
+                                                     _ptr(reset_mask), _ptr(w_hh), m, hd, *_rows(dgi, 3 * hd, m), *_rows(dgh, 3 * hd, m),
+                                                     *_rows(dh_in, hd, m), _stream(self._dev_index)), "rover_gru_cell_backward")
         return dh_in
 
     @classmethod
@@ -1265,10 +1295,8 @@ class Engine:
                 self._f32_rows(t, name, what, (m, n))
         if d_pre is not None and mul is None:
             raise RoverError(f"{what}: d_pre needs mul")
-        si = lambda t: 0 if t is None else (t.stride(0) if m > 1 else n)
-        so = lambda t: 0 if t is None else max(t.stride(0), n)
-        self._check(self.lib.rover_gated_sum_backward(self._h, _ptr(d_out), so(d_out), _ptr(mul), si(mul), _ptr(pre), si(pre), m, n, _ptr(d_mul), so(d_mul),
-                                                      _ptr(d_pre), so(d_pre), _stream(self._dev_index)), "rover_gated_sum_backward")
+        self._check(self.lib.rover_gated_sum_backward(self._h, *_rows(d_out, n, m), *_rows(mul, n, m), *_rows(pre, n, m), m, n, *_rows(d_mul, n, m),
+                                                      *_rows(d_pre, n, m), _stream(self._dev_index)), "rover_gated_sum_backward")
 
     def linear_dgrad(self, y, dy, weight, activation, dx):
         """rover_linear_dgrad: dx = (dy * act'(y)) @ weight for any widths; ``y`` may be None with activation None.  Enqueues only."""
@@ -1281,9 +1309,8 @@ class Engine:
             self._f32_rows(y, "y", what, (m, n))
         self._chk(weight, (n, k), torch.float32, "weight")
         self._f32_rows(dx, "dx", what, (m, k))
-        st = lambda t, cols: 0 if t is None else max(t.stride(0), cols)
-        self._check(self.lib.rover_linear_dgrad(self._h, _ptr(y), st(y, n), _ptr(dy), st(dy, n), m, k, _ptr(weight), n, self.ACTIVATIONS[activation],
-                                                _ptr(dx), st(dx, k), _stream(self._dev_index)), "rover_linear_dgrad")
+        self._check(self.lib.rover_linear_dgrad(self._h, *_rows(y, n, m), *_rows(dy, n, m), m, k, _ptr(weight), n, self.ACTIVATIONS[activation],
+                                                *_rows(dx, k, m), _stream(self._dev_index)), "rover_linear_dgrad")
         return dx
 
     @classmethod
@@ -1299,9 +1326,8 @@ class Engine:
         m, n = out.shape
         for t, name in ((add, "add"), (mul, "mul"), (pre, "pre")):
             self._f32_rows(t, name, what, (m, n))
-        self._check(self.lib.rover_gated_sum(self._h, _ptr(add), add.stride(0) if m > 1 else n, _ptr(mul), mul.stride(0) if m > 1 else n, _ptr(pre),
-                                             pre.stride(0) if m > 1 else n, m, n, _ptr(out), max(out.stride(0), n), _stream(self._dev_index)),
-                    "rover_gated_sum")
+        self._check(self.lib.rover_gated_sum(self._h, *_rows(add, n, m), *_rows(mul, n, m), *_rows(pre, n, m), m, n, *_rows(out, n, m),
+                                             _stream(self._dev_index)), "rover_gated_sum")
         return out
 
     # ---- the rollout side of PPO (rover_gae) -------------------------------------------------------------
@@ -1315,7 +1341,7 @@ class Engine:
         if not ok:
             raise RoverError(f"gae: {name} must be a {dtype} tensor{'' if T is None else ' [%d,%d] or [%d,%d,1]' % (T, E, T, E)} on {self.device} "
                              "with unit env stride and a time stride >= E")
-        return t.data_ptr(), (t.stride(0) if sh[0] > 1 else sh[1]), sh[0], sh[1]
+        return (*_rows(t, sh[1], sh[0]), sh[0], sh[1])
 
     def _gae_stats(self, t, name):
         if t is not None and (not t.is_cuda or t.device != self.device or t.dtype != torch.float64 or t.numel() != 3 or not t.is_contiguous()):
@@ -1371,9 +1397,8 @@ class Engine:
             self._chk(dweight, (n, k), torch.float32, "dweight")
         if dbias is not None:
             self._chk(dbias, (n,), torch.float32, "dbias")
-        st = lambda t, cols: 0 if t is None else max(t.stride(0), cols)
-        self._check(self.lib.rover_linear_backward(self._h, _ptr(x), st(x, k), _ptr(y), st(y, n), _ptr(dy), st(dy, n), m, k, _ptr(weight), n,
-                                                   self.ACTIVATIONS[activation], _ptr(dx), st(dx, k), _ptr(dweight), _ptr(dbias),
+        self._check(self.lib.rover_linear_backward(self._h, *_rows(x, k, m), *_rows(y, n, m), *_rows(dy, n, m), m, k, _ptr(weight), n,
+                                                   self.ACTIVATIONS[activation], *_rows(dx, k, m), _ptr(dweight), _ptr(dbias),
                                                    _stream(self._dev_index)), "rover_linear_backward")
 
     def ppo_loss(self, mean, log_std, actions, old_log_prob, advantages, value, old_values, returns, d_mean, d_value, d_log_std, stats,
@@ -1397,11 +1422,10 @@ class Engine:
             raise RoverError(f"{what}: stats must be 4 contiguous float64 words on the GPU")
         if reduction not in REDUCTIONS:
             raise RoverError(f"{what}: unknown reduction {reduction!r}")
-        d = PpoLossDesc(m, a, mean.data_ptr(), max(mean.stride(0), a), log_std.data_ptr(), actions.data_ptr(), max(actions.stride(0), a),
+        d = PpoLossDesc(m, a, *_rows(mean, a, m), log_std.data_ptr(), *_rows(actions, a, m),
                         old_log_prob.data_ptr(), advantages.data_ptr(), value.data_ptr(), old_values.data_ptr(), returns.data_ptr(),
                         int(bool(clip_log_std)), float(min_log_std), float(max_log_std), REDUCTIONS[reduction], float(ratio_clip), float(value_clip),
-                        int(bool(clip_predicted_values)), float(entropy_loss_scale), float(value_loss_scale), d_mean.data_ptr(),
-                        max(d_mean.stride(0), a), d_value.data_ptr(), d_log_std.data_ptr(), stats.data_ptr())
+                        int(bool(clip_predicted_values)), float(entropy_loss_scale), float(value_loss_scale), *_rows(d_mean, a, m), d_value.data_ptr(), d_log_std.data_ptr(), stats.data_ptr())
         self._check(self.lib.rover_ppo_loss(self._h, C.byref(d), _stream(self._dev_index)), "rover_ppo_loss")
         return stats
 

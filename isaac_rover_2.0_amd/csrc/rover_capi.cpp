@@ -4,6 +4,7 @@
 #include "rover_internal.h"
 #include "rover_bf16.h"
 #include "rover_philox.h"
+#include "rover_operands.h"
 #include "rover_plan.h"
 
 #include <algorithm>
@@ -85,8 +86,6 @@ struct CullQueue {
     StepPlan sized_for{};               // the plan both were sized for (alloc_cull_queue)
     StepPlan counters_written_under{};  // the plan the counters were last written under (run_raycast)
 };
-
-struct Span { uintptr_t lo, hi; };      // the bytes [lo, hi) of an array (span_of, overlap)
 
 // One rover_optim_create: the ctx owns the chunk table, the partials and the record; the tensors and the state are the caller's
 struct OptimHandle {
@@ -1831,39 +1830,33 @@ const char* rover_mlp_chain_act_route_bf16(int32_t M, int32_t K0, int32_t n_laye
     return chain_act_route_query(M, K0, n_layers, widths, activations, head, chain_route_bf16);
 }
 
-// ---- rollout: GAE ----
-// the bytes [lo, hi) a [T, E] array of `size`-byte elements at a time stride covers (Span: above rover_ctx)
-static Span span_of(const void* p, int64_t stride, int32_t T, int32_t E, size_t size) {
-    return Span{(uintptr_t)p, (uintptr_t)p + ((uint64_t)(T - 1) * (uint64_t)stride + (uint64_t)E) * size};
+// ---- the learning entry points ----
+// Each lists its arrays as an operand table (rover_operands.h), which applies the operand rules of rover_step.h; the ctx is looked at last
+// (`need_ctx`: here), so every refusal is reached with a NULL ctx too and reports through rover_last_error(NULL).
+static int check_operands(rover_ctx* c, Operands& ops, bool need_ctx = true) {
+    char why[512];
+    if (ops.refused(why, sizeof why)) return fail(c, ROVER_E_INVALID, "%s", why);
+    return need_ctx && !c ? fail(nullptr, ROVER_E_INVALID, "%s: null ctx", ops.entry()) : ROVER_OK;
 }
-static bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
 
+// ---- rollout: GAE ----
 int rover_gae(rover_ctx* c, const rover_gae_desc* d, void* stream) {
-    if (!c) return ROVER_E_INVALID;
     if (!d) return fail(c, ROVER_E_INVALID, "gae: null descriptor");
     if (d->T < 1 || d->T > 4096 || d->E < 0 || (int64_t)d->T * d->E >= (int64_t)1 << 31)
         return fail(c, ROVER_E_INVALID, "gae: T = %d outside 1 .. 4096, E = %d < 0, or T E >= 2^31", d->T, d->E);
     if (d->normalize < ROVER_GAE_RAW || d->normalize > ROVER_GAE_NORMALIZE_GIVEN) return fail(c, ROVER_E_INVALID, "gae: unknown normalize %d", d->normalize);
     if (d->E == 0) return ROVER_OK;            // nothing to read or write: no pointer is required
-    if (!d->rewards || !d->values || !d->dones || !d->last_values || !d->returns || !d->advantages)
-        return fail(c, ROVER_E_INVALID, "gae: rewards, values, dones, last_values, returns and advantages must be given");
-    if (d->normalize == ROVER_GAE_NORMALIZE_GIVEN && !d->stats_in) return fail(c, ROVER_E_INVALID, "gae: ROVER_GAE_NORMALIZE_GIVEN needs stats_in");
-    const int64_t max_stride = (int64_t)1 << 40;       // (T - 1) stride stays far inside 64 bits: the overlap tests below cannot wrap
-    for (int64_t st : {d->rewards_stride, d->values_stride, d->dones_stride, d->returns_stride, d->advantages_stride})
-        if (st < d->E || st > max_stride) return fail(c, ROVER_E_INVALID, "gae: a time stride is shorter than its row (E = %d) or above 2^40", d->E);
-    if (d->normalize == ROVER_GAE_NORMALIZE && (int64_t)d->T * d->E < 2)
+    const int32_t T = d->T, E = d->E;
+    if (d->normalize == ROVER_GAE_NORMALIZE && (int64_t)T * E < 2)
         return fail(c, ROVER_E_INVALID, "gae: ROVER_GAE_NORMALIZE needs T E >= 2 (the unbiased std of one element is NaN)");
-    const Span rew = span_of(d->rewards, d->rewards_stride, d->T, d->E, 4), val = span_of(d->values, d->values_stride, d->T, d->E, 4),
-               don = span_of(d->dones, d->dones_stride, d->T, d->E, 1), lv = span_of(d->last_values, d->E, 1, d->E, 4),
-               ret = span_of(d->returns, d->returns_stride, d->T, d->E, 4), adv = span_of(d->advantages, d->advantages_stride, d->T, d->E, 4);
-    if (overlap(ret, val) && !(d->returns == d->values && d->returns_stride == d->values_stride))
-        return fail(c, ROVER_E_INVALID, "gae: returns overlaps values without being the same array");
-    if (overlap(ret, rew) || overlap(ret, don) || overlap(ret, lv) || overlap(adv, rew) || overlap(adv, val) || overlap(adv, don) || overlap(adv, lv) || overlap(adv, ret))
-        return fail(c, ROVER_E_INVALID, "gae: an output overlaps an array the call reads (only returns may alias values)");
-    const Span so = span_of(d->stats_out, 3, 1, 3, 8), si = span_of(d->normalize == ROVER_GAE_NORMALIZE_GIVEN ? d->stats_in : nullptr, 3, 1, 3, 8);
-    for (const Span& s : {rew, val, don, lv, ret, adv})
-        if ((d->stats_out && overlap(so, s)) || (si.lo && overlap(si, s))) return fail(c, ROVER_E_INVALID, "gae: stats_out / stats_in overlaps a [T, E] array or last_values");
-    if (d->stats_out && si.lo && overlap(so, si)) return fail(c, ROVER_E_INVALID, "gae: stats_out overlaps stats_in");
+    Operands ops("gae");
+    ops.read("rewards", d->rewards, d->rewards_stride, T, E, 4).read("values", d->values, d->values_stride, T, E, 4)
+        .read("dones", d->dones, d->dones_stride, T, E, 1).read("last_values", d->last_values, E, 1, E, 4)
+        .written("returns", d->returns, d->returns_stride, T, E, 4).written("advantages", d->advantages, d->advantages_stride, T, E, 4)
+        .written("stats_out", d->stats_out, 3, 1, 3, 8, OP_OPTIONAL)
+        .same_array("returns", "values");
+    if (d->normalize == ROVER_GAE_NORMALIZE_GIVEN) ops.state("stats_in", d->stats_in, 3, 1, 3, 8);     // only read, but clear of every array
+    if (int e = check_operands(c, ops)) return e;
     USE_DEVICE(c);
     GaeArgs a{};
     a.T = d->T; a.E = (uint32_t)d->E; a.gamma = d->gamma; a.lam = d->lam;
@@ -1886,31 +1879,18 @@ int rover_combine_moments(const double* a, const double* b, double* out) {
 int rover_linear_backward(rover_ctx* c, const float* x, int64_t x_stride, const float* y, int64_t y_stride, const float* dy, int64_t dy_stride,
                           int32_t M, int32_t K, const float* weight, int32_t N, int32_t activation, float* dx, int64_t dx_stride, float* dweight,
                           float* dbias, void* stream) {
-    if (!c) return ROVER_E_INVALID;
     const LinearBwdRoute r = linear_backward_route(M, K, N, dx != nullptr);
     if (!r.ok || activation < 0 || activation > 4)
         return fail(c, ROVER_E_INVALID, "linear_backward: M=%d K=%d N=%d act=%d outside M >= 0, K >= 0 (<= 256 with dx), 1 <= N <= 256, act 0 .. 4", M, K, N, activation);
     const bool need_x = dweight && K > 0, need_w = dx && K > 0;
-    if (M > 0 && (!dy || (activation != 0 && !y) || (need_x && !x) || (need_w && !weight)))       // M = 0: nothing is read
-        return fail(c, ROVER_E_INVALID, "linear_backward: dy, y (with an activation), x (for dweight) and weight (for dx) must be given");
-    const int64_t max_stride = (int64_t)1 << 40;
-    if (dy_stride < N || dy_stride > max_stride || (activation != 0 && (y_stride < N || y_stride > max_stride)) ||
-        (need_x && (x_stride < K || x_stride > max_stride)) || (need_w && (dx_stride < K || dx_stride > max_stride)))
-        return fail(c, ROVER_E_INVALID, "linear_backward: a row stride is shorter than its row or above 2^40");
-    if (M > 0) {
-        const Span sdy = span_of(dy, dy_stride, M, N, 4), sy = span_of(activation ? y : nullptr, y_stride, M, N, 4),
-                   sx = span_of(need_x ? x : nullptr, x_stride, M, K, 4), sw = span_of(need_w ? weight : nullptr, K, N, K, 4);
-        const Span odx = span_of(need_w ? dx : nullptr, dx_stride, M, K, 4), odw = span_of(need_x ? dweight : nullptr, K, N, K, 4),
-                   odb = span_of(dbias, N, 1, N, 4);
-        const Span outs[3] = {odx, odw, odb};
-        for (int i = 0; i < 3; ++i) {
-            if (!outs[i].lo) continue;
-            for (const Span& in : {sdy, sy, sx, sw})
-                if (in.lo && overlap(outs[i], in)) return fail(c, ROVER_E_INVALID, "linear_backward: an output overlaps an array the call reads");
-            for (int j = i + 1; j < 3; ++j)
-                if (outs[j].lo && overlap(outs[i], outs[j])) return fail(c, ROVER_E_INVALID, "linear_backward: two outputs overlap");
-        }
-    }
+    Operands ops("linear_backward");        // M = 0: the [M, .] operands have no element and need no pointer, their strides are checked all the same
+    ops.read("dy", dy, dy_stride, M, N, 4);
+    if (activation) ops.read("y", y, y_stride, M, N, 4);
+    if (need_x) ops.read("x", x, x_stride, M, K, 4);
+    if (need_w) ops.read("weight", weight, K, M > 0 ? N : 0, K, 4).written("dx", dx, dx_stride, M, K, 4);
+    if (need_x) ops.written("dweight", dweight, K, M > 0 ? N : 0, K, 4);
+    ops.written("dbias", dbias, N, M > 0 ? 1 : 0, N, 4, OP_OPTIONAL);     // (M = 0 only zeroes dweight / dbias: they were never checked there)
+    if (int e = check_operands(c, ops)) return e;
     USE_DEVICE(c);
     hipStream_t s = (hipStream_t)stream;
     LinearBwdArgs a{x, x_stride, y, y_stride, dy, dy_stride, weight, dx, dx_stride, dweight, dbias, M, K, N, activation};
@@ -1928,18 +1908,15 @@ const char* rover_linear_backward_route(int32_t M, int32_t K, int32_t N, int32_t
 
 int rover_linear_dgrad(rover_ctx* c, const float* y, int64_t y_stride, const float* dy, int64_t dy_stride, int32_t M, int32_t K, const float* weight,
                        int32_t N, int32_t activation, float* dx, int64_t dx_stride, void* stream) {
-    if (!c) return ROVER_E_INVALID;
     const LinearRoute r = linear_dgrad_route(M, N, K);
     if (!r.nw || activation < 0 || activation > 4)
         return fail(c, ROVER_E_INVALID, "linear_dgrad: M=%d K=%d N=%d act=%d outside M >= 0, 1 <= K <= %d, N >= 1, act 0 .. 4", M, K, N, activation, 32 * 65535);
     if (M == 0) return ROVER_OK;
-    if (!dy || (activation != 0 && !y) || !weight || !dx) return fail(c, ROVER_E_INVALID, "linear_dgrad: dy, y (with an activation), weight and dx must be given");
-    const int64_t max_stride = (int64_t)1 << 40;
-    if (dy_stride < N || dy_stride > max_stride || (activation != 0 && (y_stride < N || y_stride > max_stride)) || dx_stride < K || dx_stride > max_stride)
-        return fail(c, ROVER_E_INVALID, "linear_dgrad: a row stride is shorter than its row or above 2^40");
-    const Span odx = span_of(dx, dx_stride, M, K, 4);
-    for (const Span& in : {span_of(dy, dy_stride, M, N, 4), span_of(activation ? y : nullptr, y_stride, M, N, 4), span_of(weight, K, N, K, 4)})
-        if (in.lo && overlap(odx, in)) return fail(c, ROVER_E_INVALID, "linear_dgrad: dx overlaps an array the call reads");
+    Operands ops("linear_dgrad");
+    ops.read("dy", dy, dy_stride, M, N, 4);
+    if (activation) ops.read("y", y, y_stride, M, N, 4);
+    ops.read("weight", weight, K, N, K, 4).written("dx", dx, dx_stride, M, K, 4);
+    if (int e = check_operands(c, ops)) return e;
     USE_DEVICE(c);
     LinearBwdArgs a{nullptr, 0, y, y_stride, dy, dy_stride, weight, dx, dx_stride, nullptr, nullptr, M, K, N, activation};
     HIP_TRY(c, launch_linear_dgrad(a, r, (hipStream_t)stream));
@@ -1953,7 +1930,6 @@ const char* rover_linear_dgrad_route(int32_t M, int32_t K, int32_t N) {
 }
 
 int rover_ppo_loss(rover_ctx* c, const rover_ppo_loss_desc* d, void* stream) {
-    if (!c) return ROVER_E_INVALID;
     if (!d) return fail(c, ROVER_E_INVALID, "ppo_loss: null descriptor");
     if (d->M < 0 || d->A < 1 || d->A > GAUSS_MAX_A) return fail(c, ROVER_E_INVALID, "ppo_loss: M = %d < 0 or A = %d outside 1 .. %d", d->M, d->A, GAUSS_MAX_A);
     if (d->reduction != ROVER_REDUCE_SUM) return fail(c, ROVER_E_INVALID, "ppo_loss: the log-prob reduction must be ROVER_REDUCE_SUM (got %d)", d->reduction);
@@ -1962,24 +1938,14 @@ int rover_ppo_loss(rover_ctx* c, const rover_ppo_loss_desc* d, void* stream) {
     if (!(d->ratio_clip >= 0.0f) || (d->clip_predicted_values && !(d->value_clip >= 0.0f)))
         return fail(c, ROVER_E_INVALID, "ppo_loss: ratio_clip %g and value_clip %g must be >= 0", (double)d->ratio_clip, (double)d->value_clip);
     if (d->M == 0) return ROVER_OK;            // nothing to read or write: no pointer is required
-    if (!d->mean || !d->log_std || !d->actions || !d->old_log_prob || !d->advantages || !d->value || !d->old_values || !d->returns || !d->d_mean ||
-        !d->d_value || !d->d_log_std || !d->stats)
-        return fail(c, ROVER_E_INVALID, "ppo_loss: every input, d_mean, d_value, d_log_std and stats must be given");
-    const int64_t max_stride = (int64_t)1 << 40;
-    for (int64_t st : {d->mean_stride, d->actions_stride, d->d_mean_stride})
-        if (st < d->A || st > max_stride) return fail(c, ROVER_E_INVALID, "ppo_loss: a row stride is shorter than its row (A = %d) or above 2^40", d->A);
     const int32_t M = d->M, A = d->A;
-    const Span ins[8] = {span_of(d->mean, d->mean_stride, M, A, 4), span_of(d->log_std, A, 1, A, 4), span_of(d->actions, d->actions_stride, M, A, 4),
-                         span_of(d->old_log_prob, M, 1, M, 4), span_of(d->advantages, M, 1, M, 4), span_of(d->value, M, 1, M, 4),
-                         span_of(d->old_values, M, 1, M, 4), span_of(d->returns, M, 1, M, 4)};
-    const Span outs[4] = {span_of(d->d_mean, d->d_mean_stride, M, A, 4), span_of(d->d_value, M, 1, M, 4), span_of(d->d_log_std, A, 1, A, 4),
-                          span_of(d->stats, 4, 1, 4, 8)};
-    for (int i = 0; i < 4; ++i) {
-        for (const Span& in : ins)
-            if (overlap(outs[i], in)) return fail(c, ROVER_E_INVALID, "ppo_loss: an output overlaps an array the call reads");
-        for (int j = i + 1; j < 4; ++j)
-            if (overlap(outs[i], outs[j])) return fail(c, ROVER_E_INVALID, "ppo_loss: two outputs overlap");
-    }
+    Operands ops("ppo_loss");
+    ops.read("mean", d->mean, d->mean_stride, M, A, 4).read("log_std", d->log_std, A, 1, A, 4).read("actions", d->actions, d->actions_stride, M, A, 4)
+        .read("old_log_prob", d->old_log_prob, M, 1, M, 4).read("advantages", d->advantages, M, 1, M, 4).read("value", d->value, M, 1, M, 4)
+        .read("old_values", d->old_values, M, 1, M, 4).read("returns", d->returns, M, 1, M, 4)
+        .written("d_mean", d->d_mean, d->d_mean_stride, M, A, 4).written("d_value", d->d_value, M, 1, M, 4)
+        .written("d_log_std", d->d_log_std, A, 1, A, 4).written("stats", d->stats, 4, 1, 4, 8);
+    if (int e = check_operands(c, ops)) return e;
     USE_DEVICE(c);
     PpoArgs a{};
     a.M = M; a.A = A; a.mean = d->mean; a.mean_stride = d->mean_stride; a.log_std = d->log_std; a.actions = d->actions; a.actions_stride = d->actions_stride;
@@ -2020,31 +1986,26 @@ int rover_optim_plan(int32_t n_tensors, const int64_t* numel, rover_optim_chunk*
 }
 
 int rover_optim_create(rover_ctx* c, const rover_optim_desc* d, int32_t* handle) {
-    if (!c) return ROVER_E_INVALID;
     if (!d || !handle || !d->params || !d->grads) return fail(c, ROVER_E_INVALID, "optim_create: null descriptor, handle, params or grads");
     int64_t total = 0;
     if (const char* why = optim_sizes_refused(d->n_tensors, d->numel, &total)) return fail(c, ROVER_E_INVALID, "optim_create: %s", why);
-    if (!d->step || !d->stopped || (total > 0 && (!d->exp_avg || !d->exp_avg_sq)))
-        return fail(c, ROVER_E_INVALID, "optim_create: exp_avg, exp_avg_sq, step and stopped must be given");
-    if ((uintptr_t)d->exp_avg % 4 || (uintptr_t)d->exp_avg_sq % 4 || (uintptr_t)d->step % 8 || (uintptr_t)d->stopped % 4)
-        return fail(c, ROVER_E_INVALID, "optim_create: exp_avg, exp_avg_sq, step or stopped is misaligned");
+    Operands st("optim_create");        // the state by the operand rules (total = 0: the moments have no element); the tensor lists by the loops below
+    st.state("step", d->step, 1, 1, 1, 8, 0, 8).state("stopped", d->stopped, 1, 1, 1, 4, 0, 4)
+        .state("exp_avg", d->exp_avg, total, 1, total, 4, 0, 4).state("exp_avg_sq", d->exp_avg_sq, total, 1, total, 4, 0, 4);
+    if (int e = check_operands(c, st, false)) return e;
     const int32_t n = d->n_tensors;
-    std::vector<Span> ps, gs;           // the tensors with elements
+    std::vector<Span> ps, gs, state = {st.span(0), st.span(1)};         // the tensors with elements; the state with elements
+    if (total > 0) state.insert(state.end(), {st.span(2), st.span(3)});
     for (int32_t i = 0; i < n; ++i) {
         if (d->numel[i] == 0) continue;
         if (!d->params[i] || !d->grads[i] || (uintptr_t)d->params[i] % 4 || (uintptr_t)d->grads[i] % 4)
             return fail(c, ROVER_E_INVALID, "optim_create: params[%d] or grads[%d] is NULL or misaligned", i, i);
-        ps.push_back(span_of(d->params[i], d->numel[i], 1, (int32_t)d->numel[i], 4));
-        gs.push_back(span_of(d->grads[i], d->numel[i], 1, (int32_t)d->numel[i], 4));
+        Span p, g;
+        if (!span_of(d->params[i], d->numel[i], 1, d->numel[i], 4, &p) || !span_of(d->grads[i], d->numel[i], 1, d->numel[i], 4, &g))
+            return fail(c, ROVER_E_INVALID, "optim_create: params[%d] or grads[%d]: extent too large", i, i);
+        ps.push_back(p);
+        gs.push_back(g);
     }
-    std::vector<Span> state = {span_of(d->step, 1, 1, 1, 8), span_of(d->stopped, 1, 1, 1, 4)};
-    if (total > 0) {
-        state.push_back(span_of(d->exp_avg, total, 1, (int32_t)total, 4));
-        state.push_back(span_of(d->exp_avg_sq, total, 1, (int32_t)total, 4));
-    }
-    for (size_t i = 0; i < state.size(); ++i)
-        for (size_t j = i + 1; j < state.size(); ++j)
-            if (overlap(state[i], state[j])) return fail(c, ROVER_E_INVALID, "optim_create: exp_avg, exp_avg_sq, step and stopped must not overlap each other");
     for (size_t i = 0; i < ps.size(); ++i) {
         for (const Span& s : state)
             if (overlap(ps[i], s) || overlap(gs[i], s)) return fail(c, ROVER_E_INVALID, "optim_create: a parameter or a gradient overlaps the state");
@@ -2052,6 +2013,7 @@ int rover_optim_create(rover_ctx* c, const rover_optim_desc* d, int32_t* handle)
             if (overlap(ps[i], gs[j]) || (j > i && overlap(ps[i], ps[j])))
                 return fail(c, ROVER_E_INVALID, "optim_create: a parameter overlaps a gradient or another parameter");
     }
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "optim_create: null ctx");       // the ctx is only where the handle is kept
     USE_DEVICE(c);
     const int64_t n_chunks = optim_plan(n, d->numel, nullptr, 0);
     std::vector<OptimChunkHost> plan((size_t)n_chunks);
@@ -2106,21 +2068,20 @@ int rover_optim_destroy(rover_ctx* c, int32_t handle) {
 }
 
 int rover_optim_step(rover_ctx* c, int32_t handle, const rover_optim_step_desc* d, void* stream) {
-    if (!c) return ROVER_E_INVALID;
     if (!d) return fail(c, ROVER_E_INVALID, "optim_step: null descriptor");
-    const OptimHandle* h = optim_handle(c, handle);
-    if (!h) return fail(c, ROVER_E_INVALID, "optim_step: handle %d is not live", handle);
     if (!(d->lr >= 0.0) || !std::isfinite(d->lr) || !(d->beta1 >= 0.0 && d->beta1 < 1.0) || !(d->beta2 >= 0.0 && d->beta2 < 1.0) ||
         !(d->eps >= 0.0) || !std::isfinite(d->eps))
         return fail(c, ROVER_E_INVALID, "optim_step: lr %g and eps %g must be finite and >= 0, beta1 %g and beta2 %g in [0, 1)", d->lr, d->eps, d->beta1, d->beta2);
     if (std::isnan(d->grad_norm_clip) || std::isnan(d->gate_threshold)) return fail(c, ROVER_E_INVALID, "optim_step: grad_norm_clip or gate_threshold is NaN");
-    if ((uintptr_t)d->gate % 8 || (uintptr_t)d->norm_out % 8) return fail(c, ROVER_E_INVALID, "optim_step: gate or norm_out is not 8-byte aligned");
-    if (d->norm_out) {
-        const Span out = span_of(d->norm_out, 1, 1, 1, 8);
-        if (d->gate && overlap(out, span_of(d->gate, 1, 1, 1, 8))) return fail(c, ROVER_E_INVALID, "optim_step: norm_out overlaps gate");
+    Operands ops("optim_step");
+    ops.read("gate", d->gate, 1, 1, 1, 8, OP_OPTIONAL, 8).written("norm_out", d->norm_out, 1, 1, 1, 8, OP_OPTIONAL, 8);
+    if (int e = check_operands(c, ops)) return e;
+    const OptimHandle* h = optim_handle(c, handle);
+    if (!h) return fail(c, ROVER_E_INVALID, "optim_step: handle %d is not live", handle);
+    Span out;
+    if (d->norm_out && span_of(d->norm_out, 1, 1, 1, 8, &out))
         for (const Span& s : h->spans)
             if (overlap(out, s)) return fail(c, ROVER_E_INVALID, "optim_step: norm_out overlaps a parameter, a gradient or the state");
-    }
     USE_DEVICE(c);
     OptimArgs a{};
     a.chunks = h->chunks.get(); a.n_chunks = h->n_chunks; a.partials = h->partials.get(); a.record = h->record.get();
@@ -2136,27 +2097,16 @@ static int gru_cell_run(rover_ctx* c, const char* what, const float* x, int64_t 
                         int32_t H, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
                         int64_t h_out_stride, bool train, float* gates, int64_t gates_stride, void* stream,
                         hipError_t (*launch)(const GruArgs&, hipStream_t) = launch_gru_cell) {
-    if (!c) return ROVER_E_INVALID;
     if (!gru_cell_route(M, K, H).nw) return fail(c, ROVER_E_INVALID, "%s: M=%d K=%d H=%d outside M >= 0, K >= 0, 1 <= H <= %d", what, M, K, H, 32 * 65535);
     if (M == 0) return ROVER_OK;                   // nothing is read or written: no pointer is required
-    if (!h_in || !w_hh || !h_out || (K > 0 && (!x || !w_ih))) return fail(c, ROVER_E_INVALID, "%s: h_in, w_hh, h_out and (K > 0) x, w_ih must be given", what);
-    if (train && !gates) return fail(c, ROVER_E_INVALID, "%s: gates must be given", what);
-    const int64_t max_stride = (int64_t)1 << 40;
-    if (h_in_stride < H || h_in_stride > max_stride || h_out_stride < H || h_out_stride > max_stride || (K > 0 && (x_stride < K || x_stride > max_stride)) ||
-        (train && (gates_stride < (int64_t)4 * H || gates_stride > max_stride)))
-        return fail(c, ROVER_E_INVALID, "%s: a row stride is shorter than its row or above 2^40", what);
-    const Span out = span_of(h_out, h_out_stride, M, H, 4);
-    const int32_t G = 3 * H;                       // gate rows (H <= 32 x 65 535: no overflow)
-    const Span ins[7] = {span_of(h_in, h_in_stride, M, H, 4), span_of(K > 0 ? x : nullptr, x_stride, M, K, 4), span_of(K > 0 ? w_ih : nullptr, K, G, K, 4),
-                         span_of(w_hh, H, G, H, 4), span_of(b_ih, G, 1, G, 4), span_of(b_hh, G, 1, G, 4), span_of(reset_mask, M, 1, M, 1)};
-    const Span og = span_of(train ? gates : nullptr, gates_stride, M, 4 * H, 4);
-    for (int i = 0; i < 7; ++i) {
-        if (ins[i].lo && overlap(out, ins[i]))
-            return fail(c, ROVER_E_INVALID, i == 0 ? "%s: h_out overlaps h_in (a tile of h' needs whole rows of h that other workgroups still read)"
-                                                   : "%s: h_out overlaps an array the call reads", what);
-        if (og.lo && ins[i].lo && overlap(og, ins[i])) return fail(c, ROVER_E_INVALID, "%s: gates overlaps an array the call reads", what);
-    }
-    if (og.lo && overlap(og, out)) return fail(c, ROVER_E_INVALID, "%s: gates overlaps h_out", what);
+    const int64_t G = (int64_t)3 * H;              // gate rows
+    Operands ops(what);
+    ops.read("h_in", h_in, h_in_stride, M, H, 4);  // (h_out may not even be h_in: a tile of h' needs whole rows of h that other workgroups still read)
+    if (K > 0) ops.read("x", x, x_stride, M, K, 4).read("w_ih", w_ih, K, G, K, 4);
+    ops.read("w_hh", w_hh, H, G, H, 4).read("b_ih", b_ih, G, 1, G, 4, OP_OPTIONAL).read("b_hh", b_hh, G, 1, G, 4, OP_OPTIONAL)
+        .read("reset_mask", reset_mask, M, 1, M, 1, OP_OPTIONAL).written("h_out", h_out, h_out_stride, M, H, 4);
+    if (train) ops.written("gates", gates, gates_stride, M, (int64_t)4 * H, 4);
+    if (int e = check_operands(c, ops)) return e;
     USE_DEVICE(c);
     GruArgs a{x, x_stride, h_in, h_in_stride, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, M, K, H, train ? gates : nullptr, gates_stride};
     HIP_TRY(c, launch(a, (hipStream_t)stream));
@@ -2186,25 +2136,15 @@ int rover_gru_cell_train(rover_ctx* c, const float* x, int64_t x_stride, const f
 int rover_gru_cell_backward(rover_ctx* c, const float* dh_above, int64_t dh_above_stride, const float* dh_next, int64_t dh_next_stride, const float* gates,
                             int64_t gates_stride, const float* h_in, int64_t h_in_stride, const uint8_t* reset_mask, const float* w_hh, int32_t M, int32_t H,
                             float* dgi, int64_t dgi_stride, float* dgh, int64_t dgh_stride, float* dh_in, int64_t dh_in_stride, void* stream) {
-    if (!c) return ROVER_E_INVALID;
     if (!gru_cell_backward_route(M, H).nw) return fail(c, ROVER_E_INVALID, "gru_cell_backward: M=%d H=%d outside M >= 0, 1 <= H <= %d", M, H, 32 * 65535);
     if (M == 0) return ROVER_OK;
-    if (!dh_above || !gates || !h_in || !w_hh || !dgi || !dgh || !dh_in)
-        return fail(c, ROVER_E_INVALID, "gru_cell_backward: dh_above, gates, h_in, w_hh, dgi, dgh and dh_in must be given");
-    const int64_t max_stride = (int64_t)1 << 40, G = (int64_t)3 * H;
-    auto bad = [&](int64_t st, int64_t cols) { return st < cols || st > max_stride; };
-    if (bad(dh_above_stride, H) || (dh_next && bad(dh_next_stride, H)) || bad(gates_stride, 4 * (int64_t)H) || bad(h_in_stride, H) || bad(dgi_stride, G) ||
-        bad(dgh_stride, G) || bad(dh_in_stride, H))
-        return fail(c, ROVER_E_INVALID, "gru_cell_backward: a row stride is shorter than its row or above 2^40");
-    const Span ins[6] = {span_of(dh_above, dh_above_stride, M, H, 4), span_of(dh_next, dh_next_stride, M, H, 4), span_of(gates, gates_stride, M, 4 * H, 4),
-                         span_of(h_in, h_in_stride, M, H, 4), span_of(reset_mask, M, 1, M, 1), span_of(w_hh, H, 3 * H, H, 4)};
-    const Span outs[3] = {span_of(dgi, dgi_stride, M, 3 * H, 4), span_of(dgh, dgh_stride, M, 3 * H, 4), span_of(dh_in, dh_in_stride, M, H, 4)};
-    for (int i = 0; i < 3; ++i) {
-        for (const Span& in : ins)
-            if (in.lo && overlap(outs[i], in)) return fail(c, ROVER_E_INVALID, "gru_cell_backward: an output overlaps an array the call reads");
-        for (int j = i + 1; j < 3; ++j)
-            if (overlap(outs[i], outs[j])) return fail(c, ROVER_E_INVALID, "gru_cell_backward: two outputs overlap");
-    }
+    const int64_t G = (int64_t)3 * H;
+    Operands ops("gru_cell_backward");
+    ops.read("dh_above", dh_above, dh_above_stride, M, H, 4).read("dh_next", dh_next, dh_next_stride, M, H, 4, OP_OPTIONAL)
+        .read("gates", gates, gates_stride, M, (int64_t)4 * H, 4).read("h_in", h_in, h_in_stride, M, H, 4)
+        .read("reset_mask", reset_mask, M, 1, M, 1, OP_OPTIONAL).read("w_hh", w_hh, H, G, H, 4)
+        .written("dgi", dgi, dgi_stride, M, G, 4).written("dgh", dgh, dgh_stride, M, G, 4).written("dh_in", dh_in, dh_in_stride, M, H, 4);
+    if (int e = check_operands(c, ops)) return e;
     USE_DEVICE(c);
     GruBwdArgs a{dh_above, dh_above_stride, dh_next, dh_next_stride, gates, gates_stride, h_in, h_in_stride, reset_mask, w_hh,
                  dgi, dgi_stride, dgh, dgh_stride, dh_in, dh_in_stride, M, H};
@@ -2232,17 +2172,12 @@ const char* rover_gru_cell_route_bf16(int32_t M, int32_t K, int32_t H) {
 
 int rover_gated_sum(rover_ctx* c, const float* add, int64_t add_stride, const float* mul, int64_t mul_stride, const float* pre, int64_t pre_stride,
                     int32_t M, int32_t N, float* out, int64_t out_stride, void* stream) {
-    if (!c) return ROVER_E_INVALID;
     if (M < 0 || N < 1 || (int64_t)M * N >= (int64_t)1 << 38) return fail(c, ROVER_E_INVALID, "gated_sum: M=%d N=%d outside M >= 0, N >= 1, M N < 2^38", M, N);
     if (M == 0) return ROVER_OK;
-    if (!add || !mul || !pre || !out) return fail(c, ROVER_E_INVALID, "gated_sum: add, mul, pre and out must be given");
-    const int64_t max_stride = (int64_t)1 << 40;
-    for (int64_t st : {add_stride, mul_stride, pre_stride})
-        if ((st != 0 && st < N) || st > max_stride) return fail(c, ROVER_E_INVALID, "gated_sum: an input's row stride is neither 0 nor >= N = %d, or above 2^40", N);
-    if (out_stride < N || out_stride > max_stride) return fail(c, ROVER_E_INVALID, "gated_sum: out's row stride is shorter than its row or above 2^40");
-    const Span so = span_of(out, out_stride, M, N, 4);
-    for (const Span& in : {span_of(add, add_stride, M, N, 4), span_of(mul, mul_stride, M, N, 4), span_of(pre, pre_stride, M, N, 4)})
-        if (overlap(so, in)) return fail(c, ROVER_E_INVALID, "gated_sum: out overlaps an input");
+    Operands ops("gated_sum");
+    ops.read("add", add, add_stride, M, N, 4, OP_STRIDE0).read("mul", mul, mul_stride, M, N, 4, OP_STRIDE0).read("pre", pre, pre_stride, M, N, 4, OP_STRIDE0)
+        .written("out", out, out_stride, M, N, 4);
+    if (int e = check_operands(c, ops)) return e;
     USE_DEVICE(c);
     GatedSumArgs a{add, add_stride, mul, mul_stride, pre, pre_stride, out, out_stride, M, N};
     HIP_TRY(c, launch_gated_sum(a, (hipStream_t)stream));
@@ -2251,21 +2186,15 @@ int rover_gated_sum(rover_ctx* c, const float* add, int64_t add_stride, const fl
 
 int rover_gated_sum_backward(rover_ctx* c, const float* d_out, int64_t d_out_stride, const float* mul, int64_t mul_stride, const float* pre,
                              int64_t pre_stride, int32_t M, int32_t N, float* d_mul, int64_t d_mul_stride, float* d_pre, int64_t d_pre_stride, void* stream) {
-    if (!c) return ROVER_E_INVALID;
     if (M < 0 || N < 1 || (int64_t)M * N >= (int64_t)1 << 38)
         return fail(c, ROVER_E_INVALID, "gated_sum_backward: M=%d N=%d outside M >= 0, N >= 1, M N < 2^38", M, N);
     if (M == 0 || (!d_mul && !d_pre)) return ROVER_OK;
-    if (!d_out || !pre || (d_pre && !mul)) return fail(c, ROVER_E_INVALID, "gated_sum_backward: d_out, pre and (for d_pre) mul must be given");
-    const int64_t max_stride = (int64_t)1 << 40;
-    if ((pre_stride != 0 && pre_stride < N) || pre_stride > max_stride || (d_pre && ((mul_stride != 0 && mul_stride < N) || mul_stride > max_stride)))
-        return fail(c, ROVER_E_INVALID, "gated_sum_backward: an input's row stride is neither 0 nor >= N = %d, or above 2^40", N);
-    if (d_out_stride < N || d_out_stride > max_stride || (d_mul && (d_mul_stride < N || d_mul_stride > max_stride)) ||
-        (d_pre && (d_pre_stride < N || d_pre_stride > max_stride)))
-        return fail(c, ROVER_E_INVALID, "gated_sum_backward: a row stride of d_out, d_mul or d_pre is shorter than its row or above 2^40");
-    const Span om = span_of(d_mul, d_mul_stride, M, N, 4), op = span_of(d_pre, d_pre_stride, M, N, 4);
-    for (const Span& in : {span_of(d_out, d_out_stride, M, N, 4), span_of(d_pre ? mul : nullptr, mul_stride, M, N, 4), span_of(pre, pre_stride, M, N, 4)})
-        if (in.lo && ((om.lo && overlap(om, in)) || (op.lo && overlap(op, in)))) return fail(c, ROVER_E_INVALID, "gated_sum_backward: an output overlaps an input");
-    if (om.lo && op.lo && overlap(om, op)) return fail(c, ROVER_E_INVALID, "gated_sum_backward: d_mul overlaps d_pre");
+    Operands ops("gated_sum_backward");
+    ops.read("d_out", d_out, d_out_stride, M, N, 4);
+    if (d_pre) ops.read("mul", mul, mul_stride, M, N, 4, OP_STRIDE0);
+    ops.read("pre", pre, pre_stride, M, N, 4, OP_STRIDE0).written("d_mul", d_mul, d_mul_stride, M, N, 4, OP_OPTIONAL)
+        .written("d_pre", d_pre, d_pre_stride, M, N, 4, OP_OPTIONAL);
+    if (int e = check_operands(c, ops)) return e;
     USE_DEVICE(c);
     GatedSumBwdArgs a{d_out, d_out_stride, mul, mul_stride, pre, pre_stride, d_mul, d_mul_stride, d_pre, d_pre_stride, M, N};
     HIP_TRY(c, launch_gated_sum_backward(a, (hipStream_t)stream));
@@ -2287,16 +2216,12 @@ int rover_obs_noise(rover_ctx* c, const rover_obs_noise_desc* d, void* stream) {
         return fail(c, ROVER_E_INVALID, "obs_noise: row_offset = %lld is negative or row_offset + M passes 2^32", (long long)d->row_offset);
     const bool empty = d->M == 0 || d->F == 0;
     if (!empty) {
-        if (!d->in || !d->out) return fail(c, ROVER_E_INVALID, "obs_noise: in and out must be given");
-        const int64_t max_stride = (int64_t)1 << 40;
-        if (d->in_stride < d->F || d->out_stride < d->F || d->in_stride > max_stride || d->out_stride > max_stride)
-            return fail(c, ROVER_E_INVALID, "obs_noise: a row stride is shorter than its row (F = %d) or above 2^40", d->F);
-        const Span si = span_of(d->in, d->in_stride, d->M, d->F, 4), so = span_of(d->out, d->out_stride, d->M, d->F, 4);
-        if (overlap(si, so) && !(d->in == d->out && d->in_stride == d->out_stride))
-            return fail(c, ROVER_E_INVALID, "obs_noise: out overlaps in without being the same array (same pointer and stride)");
-        const Span side[3] = {span_of(d->row_scale, d->M, 1, d->M, 4), span_of(d->episode, d->M, 1, d->M, 8), span_of(d->step_dev, 1, 1, 1, 8)};
-        for (const Span& s : side)
-            if (s.lo && overlap(s, so)) return fail(c, ROVER_E_INVALID, "obs_noise: row_scale, episode or step_dev overlaps out");
+        Operands ops("obs_noise");
+        ops.read("in", d->in, d->in_stride, d->M, d->F, 4).written("out", d->out, d->out_stride, d->M, d->F, 4)
+            .read("row_scale", d->row_scale, d->M, 1, d->M, 4, OP_OPTIONAL).read("episode", d->episode, d->M, 1, d->M, 8, OP_OPTIONAL)
+            .read("step_dev", d->step_dev, 1, 1, 1, 8, OP_OPTIONAL)
+            .same_array("out", "in");
+        if (int e = check_operands(c, ops, false)) return e;
     }
     if (!c) return fail(nullptr, ROVER_E_INVALID, "obs_noise: null ctx");
     if (empty) return ROVER_OK;
@@ -2332,8 +2257,6 @@ int rover_scaler_plan(int32_t M, int32_t N, rover_scaler_plan_desc* plan) {
     return ROVER_OK;
 }
 
-static bool aligned8(const void* p) { return (uintptr_t)p % 8 == 0; }
-
 // The descriptor is validated before the ctx is looked at, as for rover_obs_noise
 int rover_scaler_update(rover_ctx* c, const rover_scaler_update_desc* d, void* stream) {
     if (!d) return fail(c, ROVER_E_INVALID, "scaler_update: null descriptor");
@@ -2341,27 +2264,14 @@ int rover_scaler_update(rover_ctx* c, const rover_scaler_update_desc* d, void* s
     if (d->N < 1 || d->N > 4096) return fail(c, ROVER_E_INVALID, "scaler_update: N = %d outside 1 .. 4096", d->N);
     if (d->M < 0 || (int64_t)d->M * d->N >= (int64_t)1 << 31) return fail(c, ROVER_E_INVALID, "scaler_update: M = %d is negative or M N >= 2^31", d->M);
     if (d->M < 2) return fail(c, ROVER_E_INVALID, "scaler_update: M = %d rows, a train call needs at least 2 (the unbiased variance of one row is undefined)", d->M);
-    if (!d->x || !d->mean || !d->var || !d->count || !d->scratch) return fail(c, ROVER_E_INVALID, "scaler_update: x, mean, var, count and scratch must be given (null pointer)");
-    if (d->x_stride < d->N || d->x_stride > (int64_t)1 << 40) return fail(c, ROVER_E_INVALID, "scaler_update: the row stride of x is shorter than its row (N = %d) or above 2^40", d->N);
-    if (!aligned8(d->mean) || !aligned8(d->var) || !aligned8(d->count) || !aligned8(d->scratch))
-        return fail(c, ROVER_E_INVALID, "scaler_update: mean, var, count or scratch is not 8-byte aligned");
     (void)rover_scaler_plan(d->M, d->N, &plan);
     if (d->scratch_bytes < plan.scratch_bytes)
         return fail(c, ROVER_E_INVALID, "scaler_update: scratch of %lld bytes, the plan needs %lld", (long long)d->scratch_bytes, (long long)plan.scratch_bytes);
-    {
-        const Span sx = span_of(d->x, d->x_stride, d->M, d->N, 4), ss = span_of(d->scratch, 1, 1, 1, (size_t)d->scratch_bytes);
-        const Span st[3] = {span_of(d->mean, 1, 1, d->N, 8), span_of(d->var, 1, 1, d->N, 8), span_of(d->count, 1, 1, 1, 8)};
-        for (int i = 0; i < 3; ++i) {
-            if (overlap(st[i], sx) || overlap(st[i], ss)) return fail(c, ROVER_E_INVALID, "scaler_update: the state (mean, var, count) overlaps x or scratch");
-            for (int j = 0; j < i; ++j)
-                if (overlap(st[i], st[j])) return fail(c, ROVER_E_INVALID, "scaler_update: mean, var and count overlap each other");
-            if (d->skip_if && overlap(st[i], span_of(d->skip_if, 1, 1, 1, 4))) return fail(c, ROVER_E_INVALID, "scaler_update: skip_if overlaps the state");
-        }
-        if (overlap(sx, ss)) return fail(c, ROVER_E_INVALID, "scaler_update: scratch overlaps x");
-        if (d->skip_if && overlap(ss, span_of(d->skip_if, 1, 1, 1, 4))) return fail(c, ROVER_E_INVALID, "scaler_update: skip_if overlaps scratch");
-    }
-    if ((uintptr_t)d->skip_if % 4) return fail(c, ROVER_E_INVALID, "scaler_update: skip_if is not 4-byte aligned");
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "scaler_update: null ctx");
+    Operands ops("scaler_update");
+    ops.read("x", d->x, d->x_stride, d->M, d->N, 4).written("scratch", d->scratch, 0, 1, d->scratch_bytes, 1, OP_BYTES, 8)
+        .state("mean", d->mean, d->N, 1, d->N, 8, 0, 8).state("var", d->var, d->N, 1, d->N, 8, 0, 8).state("count", d->count, 1, 1, 1, 8, 0, 8)
+        .read("skip_if", d->skip_if, 1, 1, 1, 4, OP_OPTIONAL, 4);
+    if (int e = check_operands(c, ops)) return e;
     USE_DEVICE(c);
     ScalerUpdateArgs a{};
     a.x = d->x; a.x_stride = d->x_stride;
@@ -2378,20 +2288,10 @@ int rover_scaler_apply(rover_ctx* c, const rover_scaler_apply_desc* d, void* str
     if (d->M < 0 || (int64_t)d->M * d->N >= (int64_t)1 << 31) return fail(c, ROVER_E_INVALID, "scaler_apply: M = %d is negative or M N >= 2^31", d->M);
     if (!(d->epsilon >= 0.0) || !std::isfinite(d->epsilon) || !(d->clip >= 0.0) || !std::isfinite(d->clip))
         return fail(c, ROVER_E_INVALID, "scaler_apply: epsilon = %g or clip = %g is negative or not finite", d->epsilon, d->clip);
-    if (!d->mean || !d->var) return fail(c, ROVER_E_INVALID, "scaler_apply: mean and var must be given (null pointer)");
-    if (!aligned8(d->mean) || !aligned8(d->var)) return fail(c, ROVER_E_INVALID, "scaler_apply: mean or var is not 8-byte aligned");
-    if (d->M > 0) {
-        if (!d->x || !d->y) return fail(c, ROVER_E_INVALID, "scaler_apply: x and y must be given (null pointer)");
-        const int64_t max_stride = (int64_t)1 << 40;
-        if (d->x_stride < d->N || d->y_stride < d->N || d->x_stride > max_stride || d->y_stride > max_stride)
-            return fail(c, ROVER_E_INVALID, "scaler_apply: a row stride is shorter than its row (N = %d) or above 2^40", d->N);
-        const Span sx = span_of(d->x, d->x_stride, d->M, d->N, 4), sy = span_of(d->y, d->y_stride, d->M, d->N, 4);
-        if (overlap(sx, sy) && !(d->x == d->y && d->x_stride == d->y_stride))
-            return fail(c, ROVER_E_INVALID, "scaler_apply: y overlaps x without being the same array (same pointer and stride)");
-        for (const Span& st : {span_of(d->mean, 1, 1, d->N, 8), span_of(d->var, 1, 1, d->N, 8)})
-            if (overlap(st, sx) || overlap(st, sy)) return fail(c, ROVER_E_INVALID, "scaler_apply: the state (mean, var) overlaps x or y");
-    }
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "scaler_apply: null ctx");
+    Operands ops("scaler_apply");
+    if (d->M > 0) ops.read("x", d->x, d->x_stride, d->M, d->N, 4).written("y", d->y, d->y_stride, d->M, d->N, 4).same_array("y", "x");
+    ops.state("mean", d->mean, d->N, 1, d->N, 8, 0, 8).state("var", d->var, d->N, 1, d->N, 8, 0, 8);      // only read here, but clear of x and y too
+    if (int e = check_operands(c, ops)) return e;
     if (d->M == 0) return ROVER_OK;
     USE_DEVICE(c);
     ScalerApplyArgs a{d->x, d->x_stride, d->y, d->y_stride, (uint32_t)d->M, (uint32_t)d->N, d->mean, d->var, (float)d->epsilon, (float)d->clip};

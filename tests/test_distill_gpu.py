@@ -155,13 +155,13 @@ def test_gru_cell_backward_refuses_overlap_and_bad_arguments(eng):
     g = dev(bwd_data(m, hd, seed=2))
     snap = {k: v.clone() for k, v in g.items()}
     dgi, dgh, dh_in = (torch.full((m, n), 3.25, device=DEV) for n in (3 * hd, 3 * hd, hd))
-    with pytest.raises(RoverError, match="overlaps an array the call reads"):
+    with pytest.raises(RoverError, match="dh_in overlaps dh_next"):
         eng.gru_cell_backward(g["dh_above"], g["dh_next"], g["gates"], g["h_in"], g["w_hh"], dgi, dgh, g["dh_next"])
-    with pytest.raises(RoverError, match="overlaps an array the call reads"):
+    with pytest.raises(RoverError, match="dgi overlaps gates"):
         eng.gru_cell_backward(g["dh_above"], g["dh_next"], g["gates"], g["h_in"], g["w_hh"], g["gates"][:, :3 * hd], dgh, dh_in)
-    with pytest.raises(RoverError, match="two outputs overlap"):
+    with pytest.raises(RoverError, match="dgh overlaps dgi"):
         eng.gru_cell_backward(g["dh_above"], g["dh_next"], g["gates"], g["h_in"], g["w_hh"], dgi, dgi, dh_in)
-    with pytest.raises(RoverError, match="two outputs overlap"):
+    with pytest.raises(RoverError, match="dh_in overlaps dgh"):
         eng.gru_cell_backward(g["dh_above"], g["dh_next"], g["gates"], g["h_in"], g["w_hh"], dgi, dgh, dgh[:, :hd])
     with pytest.raises(RoverError):
         eng.gru_cell_backward(g["dh_above"], g["dh_next"], g["gates"][:, :-1], g["h_in"], g["w_hh"], dgi, dgh, dh_in)
