@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from isaac_rover_amd import config, synth, vec_env  # noqa: E402
+from isaac_rover_amd import assets, config, synth, vec_env  # noqa: E402
 
 
 def main():
@@ -52,13 +52,17 @@ def main():
                          "rover_episode_track call per step, one read per N steps): skrl's nine Reward / Episode tags, the interval's exact "
                          "episode figures and the means of the eight reward components; 0 = off")
     ap.add_argument("--track-window", type=int, default=100, help="how many of the last finished episodes the Total reward / Total timesteps tags cover (skrl: 100)")
+    ap.add_argument("--scene", choices=("synth", "mars"), default="synth",
+                    help="synth = the synthetic sine-and-discs scene; mars = a 60 m yard from the reference's Mars terrain "
+                         "generator (assets.build_mars_scene: hills and rocks from --scene-seed, both KNN maps and the heightfield on the GPU)")
+    ap.add_argument("--scene-seed", type=int, default=10, help="--scene mars: the generator's seed (10 = the reference's own)")
     args = ap.parse_args()
     if args.window < 1 or args.updates < 1:
         ap.error("--window and --updates need values >= 1")
     if args.track_interval < 0 or not 1 <= args.track_window <= 1024:
         ap.error("--track-interval N needs N >= 0, --track-window W needs W in 1 .. 1024")
 
-    scene = synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
+    scene = assets.example_scene(args.scene, args.scene_seed)
     cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
     env = vec_env.VecEnv(headless=True, sim=args.sim)
     extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size

@@ -55,13 +55,17 @@ def main():
                          "rover_episode_track call per step, one read per N steps): skrl's nine Reward / Episode tags, the interval's exact "
                          "episode figures and the means of the eight reward components; 0 = off")
     ap.add_argument("--track-window", type=int, default=100, help="how many of the last finished episodes the Total reward / Total timesteps tags cover (skrl: 100)")
+    ap.add_argument("--scene", choices=("synth", "mars"), default="synth",
+                    help="without --assets: synth = the synthetic sine-and-discs scene; mars = a 60 m yard from the reference's Mars terrain "
+                         "generator (assets.build_mars_scene: hills and rocks from --scene-seed, both KNN maps and the heightfield on the GPU)")
+    ap.add_argument("--scene-seed", type=int, default=10, help="--scene mars: the generator's seed (10 = the reference's own)")
     args = ap.parse_args()
     if args.track_interval < 0 or not 1 <= args.track_window <= 1024:
         ap.error("--track-interval N needs N >= 0, --track-window W needs W in 1 .. 1024")
     if args.rollouts < 1:
         ap.error("--rollouts N needs N >= 1")
 
-    scene = assets.load_reference_assets(args.assets) if args.assets else synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
+    scene = assets.load_reference_assets(args.assets) if args.assets else assets.example_scene(args.scene, args.scene_seed)
     cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
     env = vec_env.VecEnv(headless=True, sim=args.sim)
     extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size

@@ -157,6 +157,16 @@ class MotionDesc(C.Structure):
                 ("joint_pos_targets13", C.c_void_p), ("joint_vel_targets13", C.c_void_p), ("joint_pos13", C.c_void_p), ("joint_vel13", C.c_void_p)]
 
 
+MARS_MAX_SIDE, MARS_MAX_CLASSES, MARS_MAX_TABLE, MARS_TILE = 131072, 16, 129, 16
+
+
+class MarsDesc(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("n_hills", C.c_int32), ("hill_window", C.c_void_p), ("hill_amp", C.c_void_p),
+                ("g", C.c_void_p), ("g_len", C.c_int32), ("n_classes", C.c_int32), ("class_side", C.c_void_p), ("class_tables", C.c_void_p),
+                ("n_stamps", C.c_int32), ("stamp_row", C.c_void_p), ("stamp_col", C.c_void_p), ("stamp_class", C.c_void_p),
+                ("stamp_factor", C.c_void_p), ("stamp_kept", C.c_void_p)]
+
+
 TRACK_MAX_COMPONENTS, TRACK_MAX_WINDOW = 16, 1024
 TRACK_F32, TRACK_I64 = 0, 1
 
@@ -237,6 +247,8 @@ SYMBOLS = {
     "rover_build_knn_map_ref": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P]),
     "rover_build_heightfield": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
     "rover_heightfield_limits": (C.c_int, [_P]),
+    "rover_mars_heightfield": (C.c_int, [_P, C.POINTER(MarsDesc), _P, _P, _P]),
+    "rover_mars_tiles": (C.c_int, [C.POINTER(MarsDesc), _P, _P, C.c_int64, _P]),
     "rover_linear_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "rover_mlp_chain_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "rover_mlp_chain_pair_forward": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
@@ -519,6 +531,49 @@ def heightfield_limits():
     if rc != 0:
         raise RoverError(f"rover_heightfield_limits failed ({rc}): {lib.rover_last_error(None).decode()}")
     return {"small_nodes": int(out[0]), "tile_i": int(out[1]), "tile_j": int(out[2]), "group_lanes": int(out[3])}
+
+
+def mars_desc(rows, cols, hill_window=(), hill_amp=(), g=(1.0,), class_tables=(), stamp_row=(), stamp_col=(), stamp_class=(), stamp_factor=(),
+              stamp_kept=None):
+    """A rover_mars_desc from host arrays -> (MarsDesc, the arrays it points into: keep them alive as long as the descriptor).
+    ``hill_window`` [H, 6] (r0, r1, c0, c1, a0, b0), ``class_tables`` a sequence of square float64 arrays, ``stamp_kept`` defaults to
+    all kept.  Nothing is checked here: the library does that."""
+    win = np.ascontiguousarray(hill_window, dtype=np.int32).reshape(-1, 6)
+    amp = np.ascontiguousarray(hill_amp, dtype=np.float64).reshape(-1)
+    gg = np.ascontiguousarray(g, dtype=np.float64).reshape(-1)
+    tabs = [np.ascontiguousarray(t, dtype=np.float64) for t in class_tables]
+    side = np.asarray([t.shape[0] for t in tabs], dtype=np.int32)
+    flat = np.concatenate([t.reshape(-1) for t in tabs]) if tabs else np.zeros(0, dtype=np.float64)
+    sr, sc, sk = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (stamp_row, stamp_col, stamp_class))
+    sf = np.ascontiguousarray(stamp_factor, dtype=np.float64).reshape(-1)
+    kept = np.ones(len(sr), dtype=np.uint8) if stamp_kept is None else np.ascontiguousarray(np.asarray(stamp_kept) != 0, dtype=np.uint8).reshape(-1)
+    if len(win) != len(amp) or not (len(sr) == len(sc) == len(sk) == len(sf) == len(kept)) or any(t.ndim != 2 or t.shape[0] != t.shape[1] for t in tabs):
+        raise RoverError("mars_desc: hill arrays, stamp arrays or class tables of inconsistent shapes")
+    ptr = lambda a: a.ctypes.data if a.size else None
+    d = MarsDesc(int(rows), int(cols), len(amp), ptr(win), ptr(amp), ptr(gg), len(gg), len(tabs), ptr(side), ptr(flat), len(sr), ptr(sr), ptr(sc),
+                 ptr(sk), ptr(sf), ptr(kept))
+    return d, (win, amp, gg, side, flat, sr, sc, sk, sf, kept)
+
+
+def mars_plan_desc(plan):
+    """The rover_mars_desc of a ``terrain_gen.MarsPlan`` -> (MarsDesc, keep-alive)."""
+    return mars_desc(plan.side, plan.side, plan.hill_windows(), plan.hill_amp, plan.g, plan.class_tables, plan.stamp_rows, plan.stamp_cols,
+                     plan.stamp_class, plan.stamp_factor, plan.stamp_kept)
+
+
+def mars_tiles(desc):
+    """rover_mars_tiles: the per-tile stamp lists rover_mars_heightfield builds for ``desc`` (a MarsDesc) -> (tile_start [tiles + 1],
+    tile_items) int32 arrays; tile (ti, tj) of MARS_TILE^2 nodes has the number ti ceil(cols / MARS_TILE) + tj.  Host only."""
+    lib = load()
+    n = C.c_int64()
+    rc = lib.rover_mars_tiles(C.byref(desc), None, None, 0, C.byref(n))
+    if rc == 0:
+        tiles = ((desc.rows + MARS_TILE - 1) // MARS_TILE) * ((desc.cols + MARS_TILE - 1) // MARS_TILE)
+        start, items = np.zeros(tiles + 1, dtype=np.int32), np.zeros(max(n.value, 1), dtype=np.int32)
+        rc = lib.rover_mars_tiles(C.byref(desc), start.ctypes.data, items.ctypes.data, n.value, C.byref(n))
+    if rc != 0:
+        raise RoverError(f"rover_mars_tiles failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return start, items[:n.value]
 
 
 def track_sizes(e, w=100, k=0):
@@ -927,6 +982,18 @@ class Engine:
                                                      n0, n1, float(horizontal_scale), float(shift[0]), float(shift[1]), float(fill),
                                                      _ptr(out) if out is not None and out.numel() else None, stats), "rover_build_heightfield")
         return out, int(stats[0]), int(stats[1])
+
+    def mars_heightfield(self, plan, rock_mask=True):
+        """rover_mars_heightfield: the heightfield of the reference's Mars terrain generator from ``plan`` — a ``terrain_gen.MarsPlan``, or a
+        ``MarsDesc`` (mars_desc: any rectangle) -> (hf [rows, cols] float64 device tensor in metres, rock_mask uint8 device tensor: 1 where
+        a kept stamp covers the node; None with ``rock_mask=False``).  The definition is in include/rover_step.h; synchronous."""
+        desc, keep = (plan, None) if isinstance(plan, MarsDesc) else mars_plan_desc(plan)
+        ok = 1 <= desc.rows <= MARS_MAX_SIDE and 1 <= desc.cols <= MARS_MAX_SIDE
+        hf = torch.empty(desc.rows, desc.cols, dtype=torch.float64, device=self.device) if ok else None
+        mask = torch.empty(desc.rows, desc.cols, dtype=torch.uint8, device=self.device) if ok and rock_mask else None
+        self._check(self.lib.rover_mars_heightfield(self._h, C.byref(desc), _ptr(hf), _ptr(mask), _stream(self._dev_index)), "rover_mars_heightfield")
+        del keep
+        return hf, mask
 
     ACTIVATIONS = {"none": 0, None: 0, "leakyrelu": 1, "tanh": 2, "relu": 3, "elu": 4}
 

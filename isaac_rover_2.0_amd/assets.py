@@ -252,6 +252,51 @@ def _scene_on_maps(engine, terrain: KnnMap, rocks: KnnMap, rocks_mesh, n_cells, 
     return scene, uncovered, skipped
 
 
+def mars_meshes(engine, plan, k: int = 0):
+    """The two meshes of a generated Mars terrain: ``Engine.mars_heightfield(plan)``, every node a vertex
+    (``terrain_gen.heightfield_to_trimesh``) -> (vertices, triangles = ``map.ply``, rock triangles = ``big_stones.ply``).  The rocks-only
+    mesh is the project's own definition: the triangles with at least one vertex under a kept rock stamp (the rock mask), so it includes
+    the rocks' side walls.  Fewer than ``k`` of them is a ValueError: a KNN map of ``k`` triangles per cell cannot be built from it."""
+    from . import terrain_gen
+    hf, mask = engine.mars_heightfield(plan)
+    verts, tris = terrain_gen.heightfield_to_trimesh(hf.cpu().numpy(), plan.horizontal_scale)
+    on_rock = mask.cpu().numpy().reshape(-1) != 0
+    rock_tris = np.ascontiguousarray(tris[on_rock[tris].any(axis=1)])
+    if len(rock_tris) < k:
+        raise ValueError(f"the generated terrain has {len(rock_tris)} rock triangles, fewer than k = {k}: use a larger field, a finer gen_scale or a smaller k")
+    return verts, tris, rock_tris
+
+
+def build_mars_scene(engine, seed: int = 10, n_cells: int = 600, res: float = 0.1, k: int = 200, horizontal_scale: float = 0.025, gen_scale=None,
+                     **plan_kw):
+    """A whole Scene from one seed, on the reference's own Mars terrain generator: ``terrain_gen.plan_mars_terrain`` at ``gen_scale``
+    metres per node (default ``res``; ``width`` defaults to n_cells res, the other ``plan_kw`` are the planner's), the heights by
+    ``Engine.mars_heightfield``, :func:`mars_meshes`, then :func:`build_scene_from_meshes` as for any two meshes -> (Scene, plan).
+    ``plan.rocks`` lists the rocks as the reference records them, [x, y, z, radius]."""
+    from . import terrain_gen
+    width = plan_kw.pop("width", n_cells * res)
+    plan = terrain_gen.plan_mars_terrain(width, res if gen_scale is None else gen_scale, seed=seed, **plan_kw)
+    verts, tris, rock_tris = mars_meshes(engine, plan, k)
+    scene = build_scene_from_meshes(engine, (verts, tris), (verts, rock_tris), n_cells=n_cells, res=res, k=k, horizontal_scale=horizontal_scale)
+    return scene, plan
+
+
+def example_scene(kind: str = "synth", seed: int = 10) -> Scene:
+    """The full-size scene of the examples: ``synth`` = ``synth.make_scene`` (the benchmark's kind of scene), ``mars`` = a 60 m yard of
+    :func:`build_mars_scene` from ``seed`` on an engine of its own (device 0)."""
+    if kind == "synth":
+        from . import synth
+        return synth.make_scene(n_cells=600, k=200, n_stones=128, device="cuda")
+    if kind != "mars":
+        raise ValueError(f"example_scene: unknown kind {kind!r}")
+    from . import _lib
+    eng = _lib.Engine(1, device=0)
+    try:
+        return build_mars_scene(eng, seed=seed)[0]
+    finally:
+        eng.close()
+
+
 def generate_scene_files(engine, terrain_dir: str, n_cells: int = 600, res: float = 0.1, k: int = 200, horizontal_scale: float = 0.025,
                          ranking: str = "exact_f32", fill=None):
     """Everything a Scene needs, from ``map.ply`` and ``big_stones.ply`` in ``terrain_dir``: writes ``knn_terrain/``, ``knn_rocks/``

@@ -1533,6 +1533,163 @@ int rover_build_heightfield(rover_ctx* c, const float* vertices, int32_t V, cons
     return ROVER_OK;
 }
 
+// ---- Mars terrain generator ----
+static_assert(MARS_TILE == ROVER_MARS_TILE, "the kernel's tile is the ABI's");
+
+// shared by rover_mars_heightfield and rover_mars_tiles: true when the descriptor is acceptable, else *why says what is wrong.  This is
+// what keeps the kernel inside its buffers: a window or a kept stamp that fails here never reaches the device.
+static bool mars_desc_ok(const rover_mars_desc* d, std::string* why) {
+    char buf[256];
+    buf[0] = 0;
+#define MARS_REFUSE(...) do { snprintf(buf, sizeof buf, __VA_ARGS__); *why = buf; return false; } while (0)
+    if (!d) MARS_REFUSE("desc is NULL");
+    if (d->rows < 1 || d->cols < 1 || d->rows > ROVER_MARS_MAX_SIDE || d->cols > ROVER_MARS_MAX_SIDE)
+        MARS_REFUSE("rows = %d or cols = %d is outside 1 .. %d", d->rows, d->cols, ROVER_MARS_MAX_SIDE);
+    if (d->n_hills < 0) MARS_REFUSE("n_hills = %d is negative", d->n_hills);
+    if (d->n_classes < 0 || d->n_classes > ROVER_MARS_MAX_CLASSES) MARS_REFUSE("n_classes = %d is outside 0 .. %d", d->n_classes, ROVER_MARS_MAX_CLASSES);
+    if (d->n_stamps < 0) MARS_REFUSE("n_stamps = %d is negative", d->n_stamps);
+    if (d->g_len < 1 || !d->g) MARS_REFUSE("g is NULL or g_len = %d is below 1", d->g_len);
+    if (d->n_hills > 0 && (!d->hill_window || !d->hill_amp)) MARS_REFUSE("hill_window or hill_amp is NULL with n_hills = %d", d->n_hills);
+    if (d->n_classes > 0 && (!d->class_side || !d->class_tables)) MARS_REFUSE("class_side or class_tables is NULL with n_classes = %d", d->n_classes);
+    if (d->n_stamps > 0 && (!d->stamp_row || !d->stamp_col || !d->stamp_class || !d->stamp_factor || !d->stamp_kept))
+        MARS_REFUSE("a stamp array is NULL with n_stamps = %d", d->n_stamps);
+    for (int32_t k = 0; k < d->n_classes; ++k)
+        if (d->class_side[k] < 1 || d->class_side[k] > ROVER_MARS_MAX_TABLE)
+            MARS_REFUSE("class_side[%d] = %d is outside 1 .. %d", k, d->class_side[k], ROVER_MARS_MAX_TABLE);
+    for (int32_t i = 0; i < d->n_hills; ++i) {
+        const int32_t* w = d->hill_window + 6 * (size_t)i;
+        const int64_t r0 = w[0], r1 = w[1], c0 = w[2], c1 = w[3], a0 = w[4], b0 = w[5];
+        if (r0 < 0 || r1 < r0 || r1 > d->rows || c0 < 0 || c1 < c0 || c1 > d->cols)
+            MARS_REFUSE("hill_window[%d] = rows %d:%d, columns %d:%d is not inside the %d x %d field", i, w[0], w[1], w[2], w[3], d->rows, d->cols);
+        if (a0 < 0 || b0 < 0 || a0 + (r1 - r0) > d->g_len || b0 + (c1 - c0) > d->g_len)
+            MARS_REFUSE("hill_window[%d] reads g from %d and %d: outside its %d entries", i, w[4], w[5], d->g_len);
+        if (!std::isfinite(d->hill_amp[i])) MARS_REFUSE("hill_amp[%d] is not finite", i);
+    }
+    for (int32_t s = 0; s < d->n_stamps; ++s) {
+        if (!d->stamp_kept[s]) continue;
+        const int32_t k = d->stamp_class[s];
+        if (k < 0 || k >= d->n_classes) MARS_REFUSE("stamp_class[%d] = %d is outside 0 .. %d", s, k, d->n_classes - 1);
+        const int64_t side = d->class_side[k], r = d->stamp_row[s], c = d->stamp_col[s];
+        if (r < 0 || c < 0 || r + side > d->rows || c + side > d->cols)
+            MARS_REFUSE("stamp %d (stamp_row = %d, stamp_col = %d, side %d) is not inside the %d x %d field", s, d->stamp_row[s], d->stamp_col[s],
+                        (int)side, d->rows, d->cols);
+        if (!std::isfinite(d->stamp_factor[s])) MARS_REFUSE("stamp_factor[%d] is not finite", s);
+    }
+#undef MARS_REFUSE
+    return true;
+}
+
+static inline uint32_t mars_tiles_of(int32_t n) { return ((uint32_t)n + MARS_TILE - 1) / MARS_TILE; }
+
+// the total length of the tile lists of a descriptor that passed mars_desc_ok
+static int64_t mars_count_items(const rover_mars_desc& d) {
+    int64_t total = 0;
+    for (int32_t s = 0; s < d.n_stamps; ++s) {
+        if (!d.stamp_kept[s]) continue;
+        const int32_t side = d.class_side[d.stamp_class[s]], r = d.stamp_row[s], c = d.stamp_col[s];
+        total += (int64_t)((r + side - 1) / MARS_TILE - r / MARS_TILE + 1) * ((c + side - 1) / MARS_TILE - c / MARS_TILE + 1);
+    }
+    return total;
+}
+
+// start [tiles + 1], items [mars_count_items]: the stamps are visited in index order, so every tile's list is ascending
+static void mars_fill_lists(const rover_mars_desc& d, int32_t* start, int32_t* items) {
+    const uint32_t tiles_c = mars_tiles_of(d.cols);
+    const size_t tiles = (size_t)mars_tiles_of(d.rows) * tiles_c;
+    std::fill(start, start + tiles + 1, 0);
+    for (int pass = 0; pass < 2; ++pass) {
+        std::vector<int32_t> cursor;
+        if (pass == 1) {                                  // counts -> exclusive sum
+            int32_t sum = 0;
+            for (size_t t = 0; t <= tiles; ++t) { const int32_t n = start[t]; start[t] = sum; sum += n; }
+            cursor.assign(start, start + tiles);
+        }
+        for (int32_t s = 0; s < d.n_stamps; ++s) {
+            if (!d.stamp_kept[s]) continue;
+            const int32_t side = d.class_side[d.stamp_class[s]], r = d.stamp_row[s], c = d.stamp_col[s];
+            for (int32_t ti = r / MARS_TILE; ti <= (r + side - 1) / MARS_TILE; ++ti)
+                for (int32_t tj = c / MARS_TILE; tj <= (c + side - 1) / MARS_TILE; ++tj) {
+                    const size_t t = (size_t)ti * tiles_c + (size_t)tj;
+                    if (pass == 0) ++start[t]; else items[cursor[t]++] = s;
+                }
+        }
+    }
+}
+
+int rover_mars_tiles(const rover_mars_desc* d, int32_t* tile_start, int32_t* tile_items, int64_t capacity, int64_t* n_items) {
+    std::string why;
+    if (!mars_desc_ok(d, &why)) return fail(nullptr, ROVER_E_INVALID, "mars_tiles: %s", why.c_str());
+    if (!n_items) return fail(nullptr, ROVER_E_INVALID, "mars_tiles: n_items is NULL");
+    const int64_t n = mars_count_items(*d);
+    if (n > INT32_MAX) return fail(nullptr, ROVER_E_INVALID, "mars_tiles: the tile lists hold %lld items, more than 2^31 - 1", (long long)n);
+    const bool want = tile_start || tile_items;
+    if (want && (!tile_start || (!tile_items && n > 0))) return fail(nullptr, ROVER_E_INVALID, "mars_tiles: tile_start and tile_items go together");
+    if (capacity < 0 || (want && capacity < n))
+        return fail(nullptr, ROVER_E_INVALID, "mars_tiles: capacity %lld < %lld items", (long long)capacity, (long long)n);
+    if (want) mars_fill_lists(*d, tile_start, tile_items);
+    *n_items = n;
+    return ROVER_OK;
+}
+
+// The arguments are validated before the ctx is looked at, as for rover_build_heightfield
+int rover_mars_heightfield(rover_ctx* c, const rover_mars_desc* d, double* hf, uint8_t* rock_mask, void* stream) {
+    std::string why;
+    if (!mars_desc_ok(d, &why)) return fail(c, ROVER_E_INVALID, "mars_heightfield: %s", why.c_str());
+    if (!hf) return fail(c, ROVER_E_INVALID, "mars_heightfield: hf is NULL");
+    const int64_t n_items = mars_count_items(*d);
+    if (n_items > INT32_MAX) return fail(c, ROVER_E_INVALID, "mars_heightfield: the tile lists hold %lld items, more than 2^31 - 1", (long long)n_items);
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "mars_heightfield: null ctx");
+    USE_DEVICE(c);
+#define MARS_TRY(expr)                                                                                        \
+    do {                                                                                                      \
+        hipError_t e__ = (expr);                                                                              \
+        if (e__ != hipSuccess) return fail(c, ROVER_E_HIP, "mars_heightfield: %s: %s", #expr, hipGetErrorString(e__)); \
+    } while (0)
+    // host tables in the kernel's records
+    const uint32_t tiles_r = mars_tiles_of(d->rows), tiles_c = mars_tiles_of(d->cols);
+    const size_t tiles = (size_t)tiles_r * tiles_c;
+    std::vector<MarsHill> hills((size_t)d->n_hills);
+    for (int32_t i = 0; i < d->n_hills; ++i) {
+        const int32_t* w = d->hill_window + 6 * (size_t)i;
+        hills[i] = MarsHill{w[0], w[1], w[2], w[3], w[4], w[5], d->hill_amp[i]};
+    }
+    uint32_t table_at[ROVER_MARS_MAX_CLASSES + 1] = {0};
+    for (int32_t k = 0; k < d->n_classes; ++k) table_at[k + 1] = table_at[k] + (uint32_t)(d->class_side[k] * d->class_side[k]);
+    const size_t table_doubles = table_at[d->n_classes];
+    std::vector<MarsStamp> stamps((size_t)d->n_stamps, MarsStamp{0, 0, 0u, 0u, 0.0, 0.0});
+    for (int32_t s = 0; s < d->n_stamps; ++s)
+        if (d->stamp_kept[s]) {
+            const int32_t k = d->stamp_class[s];
+            stamps[s] = MarsStamp{d->stamp_row[s], d->stamp_col[s], (uint32_t)d->class_side[k], table_at[k], d->stamp_factor[s], 0.0};
+        }
+    std::vector<int32_t> start(tiles + 1), items((size_t)n_items);
+    mars_fill_lists(*d, start.data(), items.data());
+    DevBuf<MarsHill> d_hills;
+    DevBuf<MarsStamp> d_stamps;
+    DevBuf<double> d_g, d_tables;
+    DevBuf<int32_t> d_start, d_items;
+    MARS_TRY(d_hills.alloc(std::max<size_t>(hills.size(), 1)));
+    MARS_TRY(d_stamps.alloc(std::max<size_t>(stamps.size(), 1)));
+    MARS_TRY(d_g.alloc((size_t)d->g_len));
+    MARS_TRY(d_tables.alloc(std::max<size_t>(table_doubles, 1)));
+    MARS_TRY(d_start.alloc(start.size()));
+    MARS_TRY(d_items.alloc(std::max<size_t>(items.size(), 1)));
+    if (!hills.empty()) MARS_TRY(hipMemcpy(d_hills.get(), hills.data(), hills.size() * sizeof(MarsHill), hipMemcpyHostToDevice));
+    if (!stamps.empty()) MARS_TRY(hipMemcpy(d_stamps.get(), stamps.data(), stamps.size() * sizeof(MarsStamp), hipMemcpyHostToDevice));
+    MARS_TRY(hipMemcpy(d_g.get(), d->g, (size_t)d->g_len * sizeof(double), hipMemcpyHostToDevice));
+    if (table_doubles) MARS_TRY(hipMemcpy(d_tables.get(), d->class_tables, table_doubles * sizeof(double), hipMemcpyHostToDevice));
+    MARS_TRY(hipMemcpy(d_start.get(), start.data(), start.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!items.empty()) MARS_TRY(hipMemcpy(d_items.get(), items.data(), items.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    MarsArgs a{};
+    a.hf = hf; a.mask = rock_mask; a.rows = d->rows; a.cols = d->cols; a.tiles_r = tiles_r; a.tiles_c = tiles_c;
+    a.hills = d_hills.get(); a.n_hills = d->n_hills; a.g = d_g.get(); a.tables = d_tables.get(); a.stamps = d_stamps.get();
+    a.tile_start = d_start.get(); a.tile_items = d_items.get();
+    MARS_TRY(launch_mars_heightfield(a, (hipStream_t)stream));
+    MARS_TRY(hipStreamSynchronize((hipStream_t)stream));          // the tables above are freed on return
+#undef MARS_TRY
+    return ROVER_OK;
+}
+
 // the f32 and the bf16 layer differ in the launch alone (launch_linear_act: rover_mlp.hip; launch_linear_bf16: rover_bf16_tile.hip)
 static int linear_forward_run(rover_ctx* c, const char* what, hipError_t (*launch)(const LinearArgs&, hipStream_t), const float* x, int64_t x_stride,
                               int32_t M, int32_t K, const float* weight, const float* bias, int32_t N, int32_t activation, float* y, int64_t y_stride,

@@ -441,6 +441,26 @@ hipError_t launch_raster_small(const RasterArgs& a, hipStream_t s);
 hipError_t launch_raster_large(const RasterArgs& a, const uint64_t* tile_start, uint32_t n_large, uint64_t total, hipStream_t s);
 hipError_t launch_raster_decode(uint32_t* keys, uint64_t n, float fill, unsigned long long* stats, hipStream_t s);
 
+// The Mars terrain generator's heightfield (rover_mars_heightfield of the C ABI, validated; rover_mars.hip): one workgroup per
+// MARS_TILE^2 nodes adds the hills, then walks the tile's stamp list (built on the host) in ascending order through LDS.
+#define MARS_TILE 16                       // = ROVER_MARS_TILE
+#define MARS_CHUNK 128                     // stamp records staged in LDS at a time (4 KiB)
+struct MarsHill { int32_t r0, r1, c0, c1, a0, b0; double amp; };       // rows r0 .. r1 - 1, columns c0 .. c1 - 1; g from a0 / b0
+struct MarsStamp { int32_t row, col; uint32_t side, table; double factor, pad; };      // table: the class table's first element
+static_assert(sizeof(MarsHill) == 32 && sizeof(MarsStamp) == 32, "Mars records must be 32 bytes");
+struct MarsArgs {
+    double* hf; uint8_t* mask;             // [rows][cols]; mask may be null
+    int32_t rows, cols;
+    uint32_t tiles_r, tiles_c;
+    const MarsHill* hills; int32_t n_hills;
+    const double* g;
+    const double* tables;
+    const MarsStamp* stamps;               // [n_stamps], indexed by stamp id (dropped stamps hold zeros and are in no list)
+    const int32_t* tile_start;             // [tiles_r tiles_c + 1]
+    const int32_t* tile_items;
+};
+hipError_t launch_mars_heightfield(const MarsArgs& a, hipStream_t s);
+
 // Generalised advantage estimation over a stored rollout (rover_gae of the C ABI, validated; rover_rollout.hip): rows are time steps at
 // a stride in elements, the env stride is 1.
 enum GaeNormalize { GAE_RAW = 0, GAE_NORMALIZE = 1, GAE_NORMALIZE_GIVEN = 2 };
