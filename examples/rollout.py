@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--sim", choices=("kinematic", "terrain"), default="kinematic",
                     help="what moves the rovers between two steps: vec_env.KinematicSim, a flat unicycle, or TerrainSim, the terrain-following "
                          "motion model (one rover_motion_step launch per control step: tilt from the ground under the wheels, joint state)")
+    ap.add_argument("--suspension", choices=("plane", "bogie"), default="plane",
+                    help="with --sim terrain: plane fits a plane through the six wheel contacts; bogie solves the rocker-bogie posture, which keeps "
+                         "all six wheels down and writes the three passive joints (uprightness penalty, wheel-ray origins)")
     ap.add_argument("--track-interval", type=int, default=0,
                     help="every N steps print the episode statistics kept on the device (learning/tracking.py:EpisodeTracker, one "
                          "rover_episode_track call per step, one read per N steps): skrl's nine Reward / Episode tags, the interval's exact "
@@ -58,6 +61,8 @@ def main():
                          "generator (assets.build_mars_scene: hills and rocks from --scene-seed, both KNN maps and the heightfield on the GPU)")
     ap.add_argument("--scene-seed", type=int, default=10, help="--scene mars: the generator's seed (10 = the reference's own)")
     args = ap.parse_args()
+    if args.suspension != "plane" and args.sim != "terrain":
+        ap.error("--suspension bogie needs --sim terrain")
     if args.track_interval < 0 or not 1 <= args.track_window <= 1024:
         ap.error("--track-interval N needs N >= 0, --track-window W needs W in 1 .. 1024")
     noisy = bool(args.obs_noise or args.obs_offset or args.obs_dropout)
@@ -68,7 +73,7 @@ def main():
 
     scene = assets.load_reference_assets(args.assets) if args.assets else assets.example_scene(args.scene, args.scene_seed)
     cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
-    env = vec_env.VecEnv(headless=True, sim=args.sim)
+    env = vec_env.VecEnv(headless=True, sim=args.sim, suspension=args.suspension)
     extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size
     g = torch.Generator().manual_seed(0)
     spawn = torch.zeros(args.envs, 3)
@@ -151,7 +156,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{args.steps} steps x {args.envs} envs in {dt:.2f} s = {args.steps * args.envs / dt:,.0f} env-steps/s "
-          f"(incl. {args.policy} policy + {'toy pose feeder' if args.sim == 'kinematic' else 'terrain-following motion model'}); episodes finished: {episodes}; mean return {float(ret.mean()):.4f}")
+          f"(incl. {args.policy} policy + {'toy pose feeder' if args.sim == 'kinematic' else 'terrain-following motion model' + (', rocker-bogie posture' if args.suspension == 'bogie' else '')}); episodes finished: {episodes}; mean return {float(ret.mean()):.4f}")
     env.close()
 
 

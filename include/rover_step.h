@@ -1047,6 +1047,60 @@ ROVER_API int rover_motion_step(rover_ctx *ctx, const rover_motion_desc *d, void
 /* Host only (no ctx, no device): the 18 floats of C, row-major (z_c's row, p's, q's), computed in double and rounded to f32 once. */
 ROVER_API int rover_motion_plane_fit(float out[18]);
 
+/* ---- rocker-bogie posture: the motion model's opt-in second mode (TerrainSim(suspension="bogie")) -------------------------------------- */
+/* The plane of rover_motion_step leaves wheels above bumps or sunk into them; a rocker-bogie keeps all six down and takes up the
+ * difference in its three passive joints — joint columns 0, 1, 2: FL_Boogie, FR_Boogie, R_Boogie.  This mode solves that posture and
+ * writes the three angles into the joint state, where the step kernels read them: the uprightness penalty (rover.py:476, 492) and the
+ * suspension transform of the 24 wheel rays (rock_detect.py:263-277).  Again this project's own definition: f32, one rounding per
+ * written operation, one thread per env, stateless.  Each of `substeps` sub-steps of length dt:
+ *   1.-3. commands, heading and position exactly as steps 1-3 of rover_motion_step
+ *   4. wheel contacts at the layout of the wheel rays, not of kinematics.py: (a_i, b_i) = (forward, left) of the wheel frame's origin
+ *      with all joints at 0 (T0 + T1 of rock_detect.py:201-215), in the order FL, FR, CL, CR, RL, RR:
+ *        (0.439, 0.385) (0.439, -0.385) (0.007, 0.447) (0.007, -0.447) (-0.440, 0.385) (-0.440, -0.385);   every origin's body z is -0.167.
+ *      Contact i at ((x1 + a_i c) - b_i s, (y1 + a_i s) + b_i c): sampled at yaw only — the posture does not move the sample points —;
+ *      z_i = the heightfield there as in step 4 of rover_motion_step; all six loads are issued before the first is used
+ *   5. posture.  Unknowns u = (z_c, roll, pitch, j0, j1, j2).  Targets t_i = z_i + (ride_height - 0.167f): flat ground at height h gives
+ *      z = h + ride_height, as the plane mode does.  F(u)_i is the world z of wheel i's frame origin through the reference's own chain
+ *      with zero steering.  With T0_i = (x0, y0, -0.197) = ((0.286, +-0.385), (-0.146, +-0.447), (-0.440, +-0.385)), T1 = (0.153, 0, 0.03)
+ *      for i < 4 and (0, 0, 0.03) for the rear pair, susY = (-j0, j1, -j0, j1) for i < 4 and susX = -j2 for the rear pair:
+ *        i < 4:   bx = (0.153 + x0 cos susY) - sin susY * -0.197,   by = y0,   bz = (0.03 + x0 sin susY) + cos susY * -0.197
+ *        i >= 4:  bx = x0,   by = y0 cos susX + -0.197 sin susX,   bz = 0.03 + (-0.197 cos susX - y0 sin susX)
+ *      (the chain's factors cos 0 = 1 and sin 0 = 0 of the angle a wheel does not have are left out), and through the third row of the
+ *      ZYX body rotation:   F_i = (z_c - bx sin pitch) + cos pitch * (bz cos roll + by sin roll).
+ *      Chord iteration from u = 0, `iters` times:   r_i = t_i - F(u)_i,   u_n <- u_n + sum_i D[n][i] r_i, each row summed from i = 0
+ *      upwards.  D [6][6] = inv(J), J = dF/du at u = 0 — rows (1, b_i, -a_i, then -x0 in column 3 for FL and CL, +x0 in column 4 for FR
+ *      and CR, y0 in column 5 for RL and RR), condition number 10.6 — in double on the host, each entry rounded to f32 once
+ *      (rover_motion_bogie_fit).  The error contracts by the size of the angles per iteration: 4 iterations leave less than 1e-6 m at
+ *      0.3 rad.  After the last iteration the joint angles are clamped to [-max_bogie, max_bogie]; the body pose is NOT re-solved, so a
+ *      clamped env's pose is the unclamped solve's.  max_bogie's default of 0.6 rad is this project's choice: the repository holds no
+ *      joint limits for the asset.
+ *   6. (roll, pitch, yaw1) to the quaternion by the ZYX half-angle formula of step 6 of rover_motion_step; no atan, the angles are the
+ *      unknowns themselves
+ *   7. z1 = z_c;  pos3 and quat4 are written in place
+ * `substeps` = n gives the bits of n calls with `substeps` = 1 (every sub-step's solve starts from u = 0).  On a planar heightfield
+ * z = h + p a + q b the three joints are 0 to rounding and the body lies in the plane in this sense: -sin pitch = p and
+ * cos pitch sin roll = q, the body's x and y axes rise by p and q per metre.  Because the contacts are sampled at yaw only, that is
+ * the plane over the body's own horizontal coordinates; against the world plane's normal (tan pitch = -p) the body's z axis is off by
+ * a term of third order in the slope, 0.014 rad at p = 0.3.  The iteration converges while the wheel-height differences stay near
+ * 0.1 m (angles up to about 0.3 rad); on a step of several decimetres under one wheel it does not, the angles it returns are finite
+ * but meaningless, and the joints sit at the clamp.
+ * Joint state, after the last sub-step, where the joint quadruple is given: joint_vel13 <- joint_vel_targets13, all 13 columns (the
+ * passive joints' velocity is not modelled); joint_pos13 <- joint_pos_targets13 in columns 3-12 and the last solve's clamped (j0, j1, j2)
+ * in columns 0-2, whatever the targets hold there.  The workgroup copies all 13 columns of its rows cooperatively, as in
+ * rover_motion_step; a workgroup BARRIER follows, and then each env's own thread overwrites columns 0-2 — the copy does not skip them.
+ * One launch of ceil(E / 256) workgroups (csrc/rover_motion.hip), no LDS, no atomics.  Enqueues only, allocates nothing, capturable.
+ * E = 0: ROVER_OK, no launch.  ROVER_E_INVALID before any launch, all decided before the ctx is looked at: every refusal of
+ * rover_motion_step; a NULL params; iters outside 1 .. ROVER_BOGIE_MAX_ITERS; max_bogie not finite or not > 0.  ROVER_E_STATE: no
+ * heightfield.  rover_motion_step, rover_motion_desc and rover_motion_plane_fit are unchanged by this mode. */
+#define ROVER_BOGIE_MAX_ITERS 8
+typedef struct {
+    int32_t iters;                                 /* 1 .. 8; 4 is the binding's default                                           */
+    float max_bogie;                               /* rad, finite and > 0; 0.6 is the binding's default                            */
+} rover_bogie_params;
+ROVER_API int rover_motion_step_bogie(rover_ctx *ctx, const rover_motion_desc *d, const rover_bogie_params *p, void *stream);
+/* Host only (no ctx, no device): the 36 floats of D, row-major (z_c's row, roll's, pitch's, j0's, j1's, j2's). */
+ROVER_API int rover_motion_bogie_fit(float out[36]);
+
 /* ---- episode statistics on the device (learning/tracking.py:EpisodeTracker) ----------------------------------------------------------- */
 /* What skrl's agent writes every write_interval steps (instantaneous reward, total reward and length of the episodes in a deque of the
  * last W, each as max / min / mean), the exact totals of a reporting interval and the sums of up to 16 reward components, kept on the

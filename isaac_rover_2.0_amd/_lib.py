@@ -157,6 +157,11 @@ class MotionDesc(C.Structure):
                 ("joint_pos_targets13", C.c_void_p), ("joint_vel_targets13", C.c_void_p), ("joint_pos13", C.c_void_p), ("joint_vel13", C.c_void_p)]
 
 
+class BogieParams(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("max_bogie", C.c_float)]
+
+
+SUSPENSIONS = ("plane", "bogie")
 MARS_MAX_SIDE, MARS_MAX_CLASSES, MARS_MAX_TABLE, MARS_TILE = 131072, 16, 129, 16
 
 
@@ -297,6 +302,8 @@ SYMBOLS = {
     "rover_scaler_apply": (C.c_int, [_P, C.POINTER(ScalerApplyDesc), _P]),
     "rover_motion_step": (C.c_int, [_P, C.POINTER(MotionDesc), _P]),
     "rover_motion_plane_fit": (C.c_int, [_P]),
+    "rover_motion_step_bogie": (C.c_int, [_P, C.POINTER(MotionDesc), C.POINTER(BogieParams), _P]),
+    "rover_motion_bogie_fit": (C.c_int, [_P]),
     "rover_episode_track": (C.c_int, [_P, C.POINTER(TrackDesc), _P]),
     "rover_track_sizes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(TrackSizes)]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),
@@ -518,6 +525,17 @@ def motion_plane_fit():
     rc = lib.rover_motion_plane_fit(out.ctypes.data)
     if rc != 0:
         raise RoverError(f"rover_motion_plane_fit failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return out
+
+
+def motion_bogie_fit():
+    """rover_motion_bogie_fit: the constant D [6, 6] of the rocker-bogie posture solve, the inverse of the Jacobian at rest of the six
+    wheel-origin heights by (z_c, roll, pitch, j0, j1, j2) -> a float32 array.  Host only."""
+    out = np.empty((6, 6), dtype=np.float32)
+    lib = load()
+    rc = lib.rover_motion_bogie_fit(out.ctypes.data)
+    if rc != 0:
+        raise RoverError(f"rover_motion_bogie_fit failed ({rc}): {lib.rover_last_error(None).decode()}")
     return out
 
 
@@ -1199,13 +1217,19 @@ class Engine:
         self._check(self.lib.rover_scaler_apply(self._h, C.byref(desc), _stream(self._dev_index)), "rover_scaler_apply")
         return out
 
-    def motion_step(self, pos, quat, lin, ang, *, dt, substeps=1, max_lin=1.0, max_ang=1.0, ride_height=0.3, joints=None):
+    def motion_step(self, pos, quat, lin, ang, *, dt, substeps=1, max_lin=1.0, max_ang=1.0, ride_height=0.3, joints=None,
+                    suspension="plane", iters=4, max_bogie=0.6):
         """``substeps`` sub-steps of length ``dt`` of the terrain-following motion model on ``pos`` [e, 3] and ``quat`` [e, 4] (w, x, y, z),
         IN PLACE (rover_motion_step, one launch; needs set_heightfield): the commands ``lin`` / ``ang`` [e] scaled by ``max_lin`` /
         ``max_ang`` move the body, the six wheel contacts' terrain heights give z, roll and pitch.  ``lin`` and ``ang`` may be one column
         of a wider matrix (``tracker[:, 0]``): their common stride is passed on.  ``joints``: None, or (joint_pos_targets, joint_vel_targets,
-        joint_pos, joint_vel), each [e, 13] — after the last sub-step the state becomes the targets."""
+        joint_pos, joint_vel), each [e, 13] — after the last sub-step the state becomes the targets.
+        ``suspension="bogie"`` (rover_motion_step_bogie) solves the rocker-bogie posture instead of fitting a plane: ``iters`` chord
+        iterations put all six wheels on the ground, and the three passive joint angles, clamped to +-``max_bogie`` rad, go to columns
+        0-2 of joint_pos.  ``iters`` and ``max_bogie`` are not read with ``suspension="plane"``."""
         what = "motion_step"
+        if suspension not in SUSPENSIONS:
+            raise RoverError(f"{what}: suspension must be one of {SUSPENSIONS}, not {suspension!r}")
         e = pos.shape[0] if pos is not None and pos.dim() == 2 else -1
         self._chk(pos, (e, 3), torch.float32, "pos")
         self._chk(quat, (e, 4), torch.float32, "quat")
@@ -1227,6 +1251,10 @@ class Engine:
                 self._chk(t, (e, 13), torch.float32, name)
             jp = [t.data_ptr() for t in joints]
         desc = motion_desc(e, pos.data_ptr(), quat.data_ptr(), lin.data_ptr(), ang.data_ptr(), stride, substeps, dt, max_lin, max_ang, ride_height, *jp)
+        if suspension == "bogie":
+            par = BogieParams(int(iters), float(max_bogie))
+            self._check(self.lib.rover_motion_step_bogie(self._h, C.byref(desc), C.byref(par), _stream(self._dev_index)), "rover_motion_step_bogie")
+            return
         self._check(self.lib.rover_motion_step(self._h, C.byref(desc), _stream(self._dev_index)), "rover_motion_step")
 
     def episode_track(self, rewards, done, *, cum_reward, cum_steps, ring_ret, ring_len, ring_count, record, scratch, components=(), desc=None):

@@ -2456,29 +2456,68 @@ int rover_scaler_apply(rover_ctx* c, const rover_scaler_apply_desc* d, void* str
     return ROVER_OK;
 }
 
-// The descriptor is validated before the ctx is looked at, as for rover_obs_noise
-int rover_motion_step(rover_ctx* c, const rover_motion_desc* d, void* stream) {
-    if (!d) return fail(c, ROVER_E_INVALID, "motion_step: null descriptor");
+// The checks that rover_motion_step and rover_motion_step_bogie share, in two parts: the descriptor's own, which need no ctx ...
+static int motion_check_desc(rover_ctx* c, const rover_motion_desc* d, const char* what) {
+    if (!d) return fail(c, ROVER_E_INVALID, "%s: null descriptor", what);
     if (d->E < 0 || d->substeps < 1 || d->cmd_stride < 1)
-        return fail(c, ROVER_E_INVALID, "motion_step: E = %d is negative, substeps = %d or cmd_stride = %d is below 1", d->E, d->substeps, d->cmd_stride);
-    if (!std::isfinite(d->dt) || !(d->dt > 0.0f)) return fail(c, ROVER_E_INVALID, "motion_step: dt = %g is not finite or not > 0", (double)d->dt);
-    if (d->E > 0 && (!d->pos3 || !d->quat4 || !d->lin || !d->ang)) return fail(c, ROVER_E_INVALID, "motion_step: pos3, quat4, lin and ang must be given");
+        return fail(c, ROVER_E_INVALID, "%s: E = %d is negative, substeps = %d or cmd_stride = %d is below 1", what, d->E, d->substeps, d->cmd_stride);
+    if (!std::isfinite(d->dt) || !(d->dt > 0.0f)) return fail(c, ROVER_E_INVALID, "%s: dt = %g is not finite or not > 0", what, (double)d->dt);
+    if (d->E > 0 && (!d->pos3 || !d->quat4 || !d->lin || !d->ang)) return fail(c, ROVER_E_INVALID, "%s: pos3, quat4, lin and ang must be given", what);
     const int n_joint = (d->joint_pos_targets13 != nullptr) + (d->joint_vel_targets13 != nullptr) + (d->joint_pos13 != nullptr) + (d->joint_vel13 != nullptr);
     if (n_joint != 0 && n_joint != 4)
-        return fail(c, ROVER_E_INVALID, "motion_step: joint_pos_targets13, joint_vel_targets13, joint_pos13 and joint_vel13 go together (%d of 4 given)", n_joint);
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "motion_step: null ctx");
-    if (!c->have_hf) return fail(c, ROVER_E_STATE, "motion_step: rover_set_heightfield first");
-    if (d->E == 0) return ROVER_OK;
-    USE_DEVICE(c);
-    MotionArgs a{};
+        return fail(c, ROVER_E_INVALID, "%s: joint_pos_targets13, joint_vel_targets13, joint_pos13 and joint_vel13 go together (%d of 4 given)", what, n_joint);
+    return ROVER_OK;
+}
+
+// ... and the ctx's, after which the kernel's arguments are filled in
+static int motion_check_ctx(rover_ctx* c, const rover_motion_desc* d, const char* what, MotionArgs& a) {
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "%s: null ctx", what);
+    if (!c->have_hf) return fail(c, ROVER_E_STATE, "%s: rover_set_heightfield first", what);
     a.h = c->hf;
     a.pos3 = d->pos3; a.quat4 = d->quat4; a.lin = d->lin; a.ang = d->ang;
     a.cmd_stride = d->cmd_stride; a.E = (uint32_t)d->E; a.substeps = d->substeps;
     a.dt = d->dt; a.max_lin = d->max_lin; a.max_ang = d->max_ang; a.ride_height = d->ride_height;
-    motion_plane_fit(a.fit);
     a.joint_pos_targets13 = d->joint_pos_targets13; a.joint_vel_targets13 = d->joint_vel_targets13;
     a.joint_pos13 = d->joint_pos13; a.joint_vel13 = d->joint_vel13;
+    return ROVER_OK;
+}
+
+// The descriptor is validated before the ctx is looked at, as for rover_obs_noise
+int rover_motion_step(rover_ctx* c, const rover_motion_desc* d, void* stream) {
+    const char* what = "motion_step";
+    if (int e = motion_check_desc(c, d, what)) return e;
+    MotionArgs a{};
+    if (int e = motion_check_ctx(c, d, what, a)) return e;
+    if (d->E == 0) return ROVER_OK;
+    USE_DEVICE(c);
+    motion_plane_fit(a.fit);
     HIP_TRY(c, launch_motion(a, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+// The rocker-bogie posture mode: rover_motion_step's refusals and the two parameters', all before the ctx is looked at
+int rover_motion_step_bogie(rover_ctx* c, const rover_motion_desc* d, const rover_bogie_params* p, void* stream) {
+    const char* what = "motion_step_bogie";
+    if (int e = motion_check_desc(c, d, what)) return e;
+    if (!p) return fail(c, ROVER_E_INVALID, "%s: null parameters", what);
+    if (p->iters < 1 || p->iters > ROVER_BOGIE_MAX_ITERS)
+        return fail(c, ROVER_E_INVALID, "%s: iters = %d is outside 1 .. %d", what, p->iters, ROVER_BOGIE_MAX_ITERS);
+    if (!std::isfinite(p->max_bogie) || !(p->max_bogie > 0.0f))
+        return fail(c, ROVER_E_INVALID, "%s: max_bogie = %g is not finite or not > 0", what, (double)p->max_bogie);
+    MotionArgs a{};
+    if (int e = motion_check_ctx(c, d, what, a)) return e;
+    if (d->E == 0) return ROVER_OK;
+    USE_DEVICE(c);
+    HIP_TRY(c, launch_motion_bogie(a, p->iters, p->max_bogie, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+// Host only: the constant of the posture solve
+int rover_motion_bogie_fit(float out[36]) {
+    if (!out) return fail(nullptr, ROVER_E_INVALID, "motion_bogie_fit: null argument");
+    float inv[MOTION_WHEELS][MOTION_WHEELS];
+    motion_bogie_fit(inv);
+    memcpy(out, inv, sizeof inv);
     return ROVER_OK;
 }
 

@@ -392,6 +392,10 @@ struct MotionArgs {
 };
 void motion_plane_fit(float out[3][MOTION_WHEELS]);       // host, double arithmetic rounded to f32 once: pinv([1, a_i, b_i])
 hipError_t launch_motion(const MotionArgs& a, hipStream_t s);
+// The rocker-bogie posture mode (rover_motion_step_bogie, validated): the same arguments (fit is not read), `iters` chord iterations with
+// the constant inverse of the Jacobian at rest, the joint angles clamped to +-max_bogie into columns 0-2 of joint_pos13.
+void motion_bogie_fit(float out[MOTION_WHEELS][MOTION_WHEELS]);      // host, double arithmetic rounded to f32 once: inv(dF/du at u = 0)
+hipError_t launch_motion_bogie(const MotionArgs& a, int32_t iters, float max_bogie, hipStream_t s);
 
 // Episode statistics (rover_episode_track of the C ABI, validated; rover_track.hip): one env step's rewards, done flags and component
 // columns folded into the per-env state, the window ring and the interval record; the definition is in include/rover_step.h.

@@ -8,6 +8,11 @@
 // across sub-steps; nothing is shared between threads: no LDS, no atomics.  After the last sub-step the block copies its envs' rows of
 // the joint targets into the joint state (ideal actuators), as one contiguous range.
 //
+// rover_motion_bogie_kernel is the rocker-bogie posture mode (rover_motion_step_bogie): the same steps 1-3, the contacts
+// at the wheel rays' layout, and in place of the plane fit the six unknowns (z_c, roll, pitch, j0, j1, j2) that put all six wheel-frame
+// origins on their targets, by a chord iteration with the constant inverse of the Jacobian at rest.  The three joint angles go to columns
+// 0-2 of the joint state.  rover_motion_kernel is not touched by it.
+//
 // Built with -ffp-contract=off: every written f32 operation is one IEEE rounding, in the written order (tests/motion_ref.py restates it).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -134,6 +139,184 @@ __global__ void __launch_bounds__(256) rover_motion_kernel(MotionKernelArgs k) {
 }
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// ---- the rocker-bogie posture mode ------------------------------------------------------------------------------------------------------
+// rock_detect.py:201-215: the wheel frame's origin is T1 + Rsus(T0) in the body frame (FL, FR, CL, CR, RL, RR); T0's z is -0.197 and
+// T1's z 0.03 for every wheel, T1's x is 0.153 on the four bogie wheels and 0 on the rear pair, T1's y is 0
+#define BOGIE_T0 {{0.286, 0.385}, {0.286, -0.385}, {-0.146, 0.447}, {-0.146, -0.447}, {-0.440, 0.385}, {-0.440, -0.385}}
+// (forward a_i, left b_i) of the origins with all joints at 0: T0 + T1
+#define BOGIE_LAYOUT {{0.439, 0.385}, {0.439, -0.385}, {0.007, 0.447}, {0.007, -0.447}, {-0.440, 0.385}, {-0.440, -0.385}}
+
+// out = inv(g) by cofactors, as motion_plane_fit inverts its normal matrix
+static void inv3(const double g[3][3], double out[3][3]) {
+    const double det = g[0][0] * (g[1][1] * g[2][2] - g[1][2] * g[2][1]) - g[0][1] * (g[1][0] * g[2][2] - g[1][2] * g[2][0]) +
+                       g[0][2] * (g[1][0] * g[2][1] - g[1][1] * g[2][0]);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;
+            out[r][c] = (g[r1][c1] * g[r2][c2] - g[r1][c2] * g[r2][c1]) / det;
+        }
+}
+
+// D = inv(J), J = dF/du at u = 0 for u = (z_c, roll, pitch, j0, j1, j2): dF_i/dz_c = 1, dF_i/droll = b_i, dF_i/dpitch = -a_i, and a wheel
+// swings about its pivot: dF/dj0 = -x0 (FL, CL: susY = -j0), dF/dj1 = +x0 (FR, CR: susY = j1), dF/dj2 = y0 (RL, RR: susX = -j2).
+// The layout is mirror-symmetric, so J splits into two 3 x 3 systems over the three axles k = front, centre, rear: the half sums of the
+// left and right rows determine (z_c, pitch, p = (j1 - j0) / 2) through S = [1, -a_k, x0_k | 0 for the rear], the half differences
+// determine (roll, m = (j0 + j1) / 2, j2) through A = [b_k, -x0_k | 0, 0 | y0 for the rear]; j0 = m - p, j1 = m + p.  Inverted by
+// cofactors in double, each entry of D rounded to f32 once; the entries that are 0 by symmetry (roll does not answer to the rear pair)
+// come out as exact zeros.
+void motion_bogie_fit(float out[MOTION_WHEELS][MOTION_WHEELS]) {
+    const double t0[MOTION_WHEELS][2] = BOGIE_T0, ab[MOTION_WHEELS][2] = BOGIE_LAYOUT;
+    double S[3][3], A[3][3], Si[3][3], Ai[3][3];
+    for (int k = 0; k < 3; ++k) {
+        const int i = 2 * k;                   // the axle's left wheel
+        S[k][0] = 1.0; S[k][1] = -ab[i][0]; S[k][2] = (k < 2) ? t0[i][0] : 0.0;
+        A[k][0] = ab[i][1]; A[k][1] = (k < 2) ? -t0[i][0] : 0.0; A[k][2] = (k < 2) ? 0.0 : t0[i][1];
+    }
+    inv3(S, Si);
+    inv3(A, Ai);
+    for (int k = 0; k < 3; ++k)
+        for (int side = 0; side < 2; ++side) {
+            const int i = 2 * k + side;
+            const double sg = side ? -0.5 : 0.5;
+            const double zc = 0.5 * Si[0][k], pitch = 0.5 * Si[1][k], p = 0.5 * Si[2][k];
+            const double roll = sg * Ai[0][k], m = sg * Ai[1][k], j2 = sg * Ai[2][k];
+            out[0][i] = (float)zc; out[1][i] = (float)roll; out[2][i] = (float)pitch;
+            out[3][i] = (float)(m - p); out[4][i] = (float)(m + p); out[5][i] = (float)j2;
+            for (int n = 0; n < MOTION_WHEELS; ++n) out[n][i] += 0.0f;         // a zero is +0
+        }
+}
+
+struct BogieKernelArgs {
+    MotionArgs m;                          // m.fit is not used
+    int32_t quat_vec, joint_vec;
+    float inv[MOTION_WHEELS][MOTION_WHEELS];       // motion_bogie_fit()
+    int32_t iters;
+    float max_bogie;
+};
+
+template <int RCP>
+__global__ void __launch_bounds__(256) rover_motion_bogie_kernel(BogieKernelArgs k) {
+    const MotionArgs& a = k.m;
+    HeightDev hf = a.h;
+    hf.rcp = RCP;
+    const float ab[MOTION_WHEELS][2] = BOGIE_LAYOUT, t0[MOTION_WHEELS][2] = BOGIE_T0;
+    const float t0z = -0.197f, t1x = 0.153f, t1z = 0.03f;
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    float u[MOTION_WHEELS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};        // (z_c, roll, pitch, j0, j1, j2) of the last sub-step
+    if (e < a.E) {
+        float* pp = a.pos3 + 3ull * e;
+        float* qp = a.quat4 + 4ull * e;
+        float px = pp[0], py = pp[1];
+        float qw, qx, qy, qz;
+        if (k.quat_vec) {
+            const float4 q = *reinterpret_cast<const float4*>(qp);
+            qw = q.x; qx = q.y; qy = q.z; qz = q.w;
+        } else {
+            qw = qp[0]; qx = qp[1]; qy = qp[2]; qz = qp[3];
+        }
+        // 1. commands, as rover_motion_kernel
+        const float v = a.lin[(uint64_t)e * (uint32_t)a.cmd_stride] * a.max_lin;
+        const float w = a.ang[(uint64_t)e * (uint32_t)a.cmd_stride] * a.max_ang;
+        const float v_eff = (fabsf(v / w) > 0.45f) ? v : 0.0f;
+        const float dyaw = w * a.dt;
+        const float off = a.ride_height - 0.167f;                  // the origins lie at body z = -0.167
+        for (int32_t s = 0; s < a.substeps; ++s) {
+            // 2. heading, 3. position
+            const float yaw0 = atan2f(2.0f * (qw * qz + qx * qy), 1.0f - (2.0f * (qy * qy + qz * qz)));
+            const float yaw = yaw0 + dyaw;
+            const float cs = cosf(yaw), sn = sinf(yaw);
+            px = px + (v_eff * cs) * a.dt;
+            py = py + (v_eff * sn) * a.dt;
+            // 4. the six wheel contacts, sampled at yaw only: every lookup is issued before the first one is used
+            float t[MOTION_WHEELS];
+#pragma unroll
+            for (int i = 0; i < MOTION_WHEELS; ++i) {
+                const float wx = (px + ab[i][0] * cs) - ab[i][1] * sn;
+                const float wy = (py + ab[i][0] * sn) + ab[i][1] * cs;
+                t[i] = height_at(hf, wx, wy);
+            }
+#pragma unroll
+            for (int i = 0; i < MOTION_WHEELS; ++i) t[i] = t[i] + off;
+            // 5. posture: the chord iteration u <- u + D (t - F(u)) from u = 0
+#pragma unroll
+            for (int i = 0; i < MOTION_WHEELS; ++i) u[i] = 0.0f;
+            for (int32_t it = 0; it < k.iters; ++it) {
+                const float sr = sinf(u[1]), cr = cosf(u[1]), sp = sinf(u[2]), cp = cosf(u[2]);
+                const float sus[3] = {-u[3], u[4], -u[5]};          // susY of FL and CL, susY of FR and CR, susX of RL and RR
+                float ss[3], cc[3];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) { ss[j] = sinf(sus[j]); cc[j] = cosf(sus[j]); }
+                float r[MOTION_WHEELS];
+#pragma unroll
+                for (int i = 0; i < MOTION_WHEELS; ++i) {
+                    float bx, by, bz;                               // the wheel frame's origin in the body frame: rock_detect.py:275-277
+                    if (i < 4) {                                    // susX = 0
+                        const float ssy = ss[i & 1], csy = cc[i & 1];
+                        bx = (t1x + t0[i][0] * csy) - ssy * t0z;
+                        by = t0[i][1];
+                        bz = (t1z + t0[i][0] * ssy) + csy * t0z;
+                    } else {                                        // susY = 0, T1's x is 0
+                        const float c1 = t0z * cc[2] - t0[i][1] * ss[2];
+                        bx = t0[i][0];
+                        by = t0[i][1] * cc[2] + t0z * ss[2];
+                        bz = t1z + c1;
+                    }
+                    const float h = bz * cr + by * sr;              // the ZYX rotation's third row: (-sin pitch, cos pitch sin roll, cos pitch cos roll)
+                    r[i] = t[i] - ((u[0] - bx * sp) + cp * h);
+                }
+#pragma unroll
+                for (int n = 0; n < MOTION_WHEELS; ++n) {
+                    float acc = k.inv[n][0] * r[0];
+#pragma unroll
+                    for (int i = 1; i < MOTION_WHEELS; ++i) acc = acc + k.inv[n][i] * r[i];
+                    u[n] = u[n] + acc;
+                }
+            }
+            // 6. orientation: roll and pitch are the unknowns themselves
+            const float hr = u[1] * 0.5f, hp = u[2] * 0.5f, hy = yaw * 0.5f;
+            const float chr = cosf(hr), shr = sinf(hr), chp = cosf(hp), shp = sinf(hp), cy = cosf(hy), sy = sinf(hy);
+            qw = (chr * chp) * cy + (shr * shp) * sy;
+            qx = (shr * chp) * cy - (chr * shp) * sy;
+            qy = (chr * shp) * cy + (shr * chp) * sy;
+            qz = (chr * chp) * sy - (shr * shp) * cy;
+        }
+        // 7. pose: z = z_c
+        pp[0] = px; pp[1] = py; pp[2] = u[0];
+        if (k.quat_vec) {
+            *reinterpret_cast<float4*>(qp) = make_float4(qw, qx, qy, qz);
+        } else {
+            qp[0] = qw; qp[1] = qx; qp[2] = qy; qp[3] = qz;
+        }
+    }
+    if (a.joint_pos13) {
+        // the block copies its envs' rows, all 13 columns; a barrier, then each env's thread overwrites columns 0-2 of its position row
+        // with the clamped joint angles (the barrier is in uniform control flow: joint_pos13 is a kernel argument)
+        const uint64_t n = 13ull * a.E;
+        copy_joint_rows(a.joint_pos_targets13, a.joint_pos13, n, k.joint_vec != 0);
+        copy_joint_rows(a.joint_vel_targets13, a.joint_vel13, n, k.joint_vec != 0);
+        __syncthreads();
+        if (e < a.E) {
+            float* jp = a.joint_pos13 + 13ull * e;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) jp[j] = fminf(fmaxf(u[3 + j], -k.max_bogie), k.max_bogie);
+        }
+    }
+}
+
+static int32_t joint_vec_of(const MotionArgs& a) {
+    return (a.joint_pos13 && aligned16(a.joint_pos13) && aligned16(a.joint_vel13) && aligned16(a.joint_pos_targets13) &&
+            aligned16(a.joint_vel_targets13)) ? 1 : 0;
+}
+
+hipError_t launch_motion_bogie(const MotionArgs& a, int32_t iters, float max_bogie, hipStream_t s) {
+    if (a.E == 0) return hipSuccess;
+    BogieKernelArgs k{a, aligned16(a.quat4) ? 1 : 0, joint_vec_of(a), {}, iters, max_bogie};
+    motion_bogie_fit(k.inv);
+    if (a.h.rcp) hipLaunchKernelGGL(rover_motion_bogie_kernel<1>, dim3(blocks_for(a.E, 256)), dim3(256), 0, s, k);
+    else hipLaunchKernelGGL(rover_motion_bogie_kernel<0>, dim3(blocks_for(a.E, 256)), dim3(256), 0, s, k);
+    return hipGetLastError();
+}
 
 hipError_t launch_motion(const MotionArgs& a, hipStream_t s) {
     if (a.E == 0) return hipSuccess;

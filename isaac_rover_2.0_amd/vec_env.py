@@ -8,6 +8,8 @@ PhysX is replaced by ``KinematicSim``: a toy unicycle integrator that moves each
 (linear, angular) velocity and keeps it on the heightfield — a pose FEEDER, not a simulator.  ``VecEnv(sim="terrain")`` selects
 ``TerrainSim`` instead: the terrain-following motion model of ``rover_motion_step``, one HIP launch per control step,
 which also tilts the body with the ground under its six wheels, obeys Ackermann's turn-on-the-spot rule and writes the joint state.
+``VecEnv(sim="terrain", suspension="bogie")`` runs its rocker-bogie posture mode: all six wheels on the ground, the three
+passive suspension joints in the joint state, where the uprightness penalty and the wheel rays read them.
 """
 from __future__ import annotations
 
@@ -43,10 +45,16 @@ class KinematicSim:
 class TerrainSim:
     """``KinematicSim``'s interface on the terrain-following motion model (``Engine.motion_step``): the rover poses are advanced in place
     on the task's engine and heightfield, and the joint state follows the joint targets (ideal actuators).  ``advance(n)`` folds ``n``
-    sub-steps of length ``dt`` into one launch; ``step`` is ``advance(1)``."""
+    sub-steps of length ``dt`` into one launch; ``step`` is ``advance(1)``.  ``suspension="bogie"`` solves the rocker-bogie posture
+    (``iters`` chord iterations, joints clamped to +-``max_bogie`` rad) and writes the passive joints into columns 0-2 of the joint
+    positions; ``"plane"``, the default, fits a plane and leaves them at the targets' 0."""
 
-    def __init__(self, task, dt: float = 0.05, max_lin: float = 1.0, max_ang: float = 1.0, ride_height: float = 0.3):
+    def __init__(self, task, dt: float = 0.05, max_lin: float = 1.0, max_ang: float = 1.0, ride_height: float = 0.3,
+                 suspension: str = "plane", iters: int = 4, max_bogie: float = 0.6):
+        if suspension not in SUSPENSIONS:
+            raise ValueError(f"suspension must be one of {SUSPENSIONS}, not {suspension!r}")
         self.task, self.dt, self.max_lin, self.max_ang, self.ride_height = task, dt, max_lin, max_ang, ride_height
+        self.suspension, self.iters, self.max_bogie = suspension, iters, max_bogie
         self._playing = True
 
     def is_playing(self):
@@ -61,17 +69,23 @@ class TerrainSim:
         pos, quat = r.get_world_poses()
         t._engine.motion_step(pos, quat, t.linear_velocity.get_state(0), t.angular_velocity.get_state(0), dt=self.dt, substeps=n,
                               max_lin=self.max_lin, max_ang=self.max_ang, ride_height=self.ride_height,
-                              joints=(r._joint_pos_targets, r._joint_vel_targets, r.get_joint_positions(), r.get_joint_velocities()))
+                              joints=(r._joint_pos_targets, r._joint_vel_targets, r.get_joint_positions(), r.get_joint_velocities()),
+                              suspension=self.suspension, iters=self.iters, max_bogie=self.max_bogie)
 
 
+SUSPENSIONS = ("plane", "bogie")
 SIMS = {"kinematic": KinematicSim, "terrain": TerrainSim}
 
 
 class VecEnv:
-    def __init__(self, headless: bool = True, sim_device: int = 0, sim: str = "kinematic"):
+    def __init__(self, headless: bool = True, sim_device: int = 0, sim: str = "kinematic", suspension: str = "plane"):
         if sim not in SIMS:
             raise ValueError(f"sim must be one of {tuple(SIMS)}, not {sim!r}")
-        self._sim = sim
+        if suspension not in SUSPENSIONS:
+            raise ValueError(f"suspension must be one of {SUSPENSIONS}, not {suspension!r}")
+        if suspension != "plane" and sim != "terrain":
+            raise ValueError(f"suspension={suspension!r} needs sim='terrain': KinematicSim writes no joint state")
+        self._sim, self._suspension = sim, suspension
         self._render = not headless
         self._task = None
         self._world = None
@@ -79,7 +93,8 @@ class VecEnv:
     def set_task(self, task, backend="torch", sim_params=None, init_sim=True, spawn_positions=None) -> None:
         self._task = task
         task._env = self
-        self._world = SIMS[self._sim](task, dt=(sim_params or {}).get("dt", 0.05))
+        kw = {"suspension": self._suspension} if self._sim == "terrain" else {}
+        self._world = SIMS[self._sim](task, dt=(sim_params or {}).get("dt", 0.05), **kw)
         task.set_up_scene(spawn_positions=spawn_positions)
         task.post_reset()
         self.num_envs = task.num_envs

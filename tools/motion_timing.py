@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
-"""Times the two pose feeders of vec_env on the GPU: TerrainSim.advance(1) (one rover_motion_step launch) against KinematicSim.step()
-(about fifteen torch ops and a height lookup), both as VecEnv's world object would call them, on the same task (EXPERIMENTS.md §22).
+"""Times the pose feeders of vec_env on the GPU: TerrainSim.advance(1) (one rover_motion_step launch) against KinematicSim.step()
+(about fifteen torch ops and a height lookup), both as VecEnv's world object would call them, on the same task (EXPERIMENTS.md §22),
+and "bogie", TerrainSim(suspension="bogie").advance(1) (one rover_motion_step_bogie launch; EXPERIMENTS.md §29).
 
-    python tools/motion_timing.py [--envs 512 4096 65536] [--reps 30] [--feeders kinematic terrain] [--json out.json]
+    python tools/motion_timing.py [--envs 512 4096 65536] [--reps 30] [--feeders kinematic terrain bogie] [--json out.json]
 
 Per size one task is built (synthetic scene, 37-ray distribution), stepped a few times with random actions so that the histories, the
 joint targets and the poses are those of a rollout, and then each feeder is called in windows of --inner calls between two device
 events; the windows of the two feeders alternate, so that a drift of the machine meets both.  A figure is the time of one call inside
 such a window — enqueue cost included where the host is the limit, as in a rollout —: median (min .. max) over --reps windows.
-"terrain_graph" is the same window of TerrainSim calls captured once in a graph and replayed: the device's share of a call, with no
-enqueue cost.  --feeders kinematic alone runs on a tree without TerrainSim.  Needs a GPU; there is no fallback."""
+"terrain_graph" / "bogie_graph" is the same window of TerrainSim calls captured once in a graph and replayed: the device's share of a
+call, with no enqueue cost.  --feeders kinematic alone runs on a tree without TerrainSim, --feeders kinematic terrain on one without the
+bogie mode.  Needs a GPU; there is no fallback."""
 import argparse
 import json
 import os
@@ -40,7 +42,7 @@ def main():
     ap.add_argument("--envs", type=int, nargs="+", default=[512, 4096, 65536])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200, help="calls per window")
-    ap.add_argument("--feeders", nargs="+", choices=("kinematic", "terrain"), default=["kinematic", "terrain"])
+    ap.add_argument("--feeders", nargs="+", choices=("kinematic", "terrain", "bogie"), default=["kinematic", "terrain", "bogie"])
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -58,21 +60,25 @@ def main():
         env.reset()
         for _ in range(5):
             env.step(2 * torch.rand(e, 2, device=task.device) - 1)
-        worlds = {"kinematic": lambda: vec_env.KinematicSim(task, dt=0.05), "terrain": lambda: vec_env.TerrainSim(task, dt=0.05)}
+        worlds = {"kinematic": lambda: vec_env.KinematicSim(task, dt=0.05), "terrain": lambda: vec_env.TerrainSim(task, dt=0.05),
+                  "bogie": lambda: vec_env.TerrainSim(task, dt=0.05, suspension="bogie")}
         calls = {}
         for name in args.feeders:
             w = worlds[name]()
-            calls[name] = (lambda w=w: w.advance(1)) if name == "terrain" else (lambda w=w: w.step(render=False))
+            calls[name] = (lambda w=w: w.step(render=False)) if name == "kinematic" else (lambda w=w: w.advance(1))
         pos, quat = task._rover.get_world_poses()
         start = (pos.clone(), quat.clone())
-        if "terrain" in calls:
+        graphs = {}
+        for name in ("terrain", "bogie"):
+            if name not in calls:
+                continue
             for _ in range(3):
-                calls["terrain"]()
+                calls[name]()
             torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            graphs[name] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[name]):
                 for _ in range(args.inner):
-                    calls["terrain"]()
+                    calls[name]()
         samples = {name: [] for name in calls}
         for name, fn in calls.items():                               # warm-up: every op's code object loaded
             for _ in range(10):
@@ -83,10 +89,10 @@ def main():
                 pos.copy_(start[0]), quat.copy_(start[1])            # every window starts from the same poses
                 torch.cuda.synchronize()
                 samples[name].append(window(fn, args.inner))
-            if "terrain" in calls:
+            for name, graph in graphs.items():
                 pos.copy_(start[0]), quat.copy_(start[1])
                 torch.cuda.synchronize()
-                samples.setdefault("terrain_graph", []).append(window(graph.replay, 1) / args.inner)
+                samples.setdefault(name + "_graph", []).append(window(graph.replay, 1) / args.inner)
         rec = {name: (statistics.median(v), min(v), max(v)) for name, v in samples.items()}
         result["sizes"][str(e)] = rec
         print(f"--- {e} envs (us per call: median (min .. max); {args.inner} calls per window, {args.reps} windows, alternating)")
