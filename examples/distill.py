@@ -14,6 +14,8 @@ loads.
 `--device-noise`, `--obs-offset S` or `--obs-dropout P` switch the perception model to `learning.noise.HeightmapNoise`: every step's
 observation is written into the window by one `rover_obs_noise` launch (Gaussian noise `--noise` per column, a Gaussian offset per env
 and episode, dropout to 0), counter-based and independent of the batch shape; the window-sized `torch.randn` tensor is then never made.
+`--occlusion [--camera F L U] [--sight-step S] [--sight-clearance C]` adds the line-of-sight stage behind it (`HeightmapOcclusion`, one
+`rover_obs_occlusion` launch on the window row): columns a camera on the mast cannot see read 0; the target stays the clean row.
 """
 import argparse
 import os
@@ -37,7 +39,13 @@ def main():
     ap.add_argument("--obs-offset", type=float, default=0.0, help="standard deviation of a per-env, per-episode offset on the heightmap columns")
     ap.add_argument("--obs-dropout", type=float, default=0.0, help="probability of a heightmap column reading 0")
     ap.add_argument("--device-noise", action="store_true", help="the noise as one rover_obs_noise launch per step instead of torch.randn "
-                    "(implied by --obs-offset / --obs-dropout)")
+                    "(implied by --obs-offset / --obs-dropout / --occlusion)")
+    ap.add_argument("--occlusion", action="store_true",
+                    help="after the noise, heightmap columns whose measured point a camera on the mast cannot see read 0 in the window "
+                         "(rover_obs_occlusion); the reconstruction target stays the clean row")
+    ap.add_argument("--camera", type=float, nargs=3, default=(0.0, 0.0, 0.7), metavar=("F", "L", "U"), help="--occlusion: the camera in the body frame, metres")
+    ap.add_argument("--sight-step", type=float, default=0.05, help="--occlusion: spacing of the samples along a sight line, metres")
+    ap.add_argument("--sight-clearance", type=float, default=0.03, help="--occlusion: how far the ground must rise above the sight line to hide, metres")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--grad-norm-clip", type=float, default=1.0)
     ap.add_argument("--recon-scale", type=float, default=0.5)
@@ -96,12 +104,17 @@ def main():
     wanted = torch.empty(e, t_len, task.num_actions, device=task.device)
     reset = torch.zeros(e, t_len, dtype=torch.bool, device=task.device)
     noise = noise_gen = None
-    if args.device_noise or args.obs_offset or args.obs_dropout:
+    if args.device_noise or args.obs_offset or args.obs_dropout or args.occlusion:
         from isaac_rover_amd.learning.noise import HeightmapNoise
         noise = HeightmapNoise(task._engine, task, sigma_point=args.noise, sigma_offset=args.obs_offset, dropout=args.obs_dropout, seed=2)
         print(f"perception: rover_obs_noise, sigma_point {args.noise} sigma_offset {args.obs_offset} dropout {args.obs_dropout}")
     else:
         noise_gen = torch.Generator(device=task.device).manual_seed(2)
+    occlusion = None
+    if args.occlusion:
+        from isaac_rover_amd.learning.noise import HeightmapOcclusion
+        occlusion = HeightmapOcclusion(task._engine, task, camera=args.camera, step=args.sight_step, clearance=args.sight_clearance)
+        print(f"perception: rover_obs_occlusion, camera {tuple(args.camera)} step {args.sight_step} clearance {args.sight_clearance}")
     tracker = None
     if args.track_interval:
         from isaac_rover_amd.learning.tracking import EpisodeTracker
@@ -114,6 +127,8 @@ def main():
                 x[:, t] = obs
             else:
                 noise.apply(obs, out=x[:, t], reset=done)                          # the noisy row straight into the window
+                if occlusion is not None:                                          # ... and what the camera cannot see out of it, in place
+                    occlusion.apply(obs, noisy=x[:, t], out=x[:, t])
             clean[:, t] = obs[:, f - ex:]
             wanted[:, t] = actions
             reset[:, t] = done                                                     # an env that just ended starts from a zero hidden state

@@ -45,6 +45,12 @@ def main():
                     "columns the policy sees (rover_obs_noise; the task and its rewards keep the clean observation)")
     ap.add_argument("--obs-offset", type=float, default=0.0, help="... of a per-env, per-episode offset on them")
     ap.add_argument("--obs-dropout", type=float, default=0.0, help="... probability of a heightmap column reading 0")
+    ap.add_argument("--occlusion", action="store_true",
+                    help="--policy actor / student: heightmap columns whose measured point a camera on the mast cannot see read 0 "
+                         "(rover_obs_occlusion: the line-of-sight stage of the sensor model, after the noise; the task keeps the clean observation)")
+    ap.add_argument("--camera", type=float, nargs=3, default=(0.0, 0.0, 0.7), metavar=("F", "L", "U"), help="--occlusion: the camera in the body frame, metres")
+    ap.add_argument("--sight-step", type=float, default=0.05, help="--occlusion: spacing of the samples along a sight line, metres")
+    ap.add_argument("--sight-clearance", type=float, default=0.03, help="--occlusion: how far the ground must rise above the sight line to hide, metres")
     ap.add_argument("--sim", choices=("kinematic", "terrain"), default="kinematic",
                     help="what moves the rovers between two steps: vec_env.KinematicSim, a flat unicycle, or TerrainSim, the terrain-following "
                          "motion model (one rover_motion_step launch per control step: tilt from the ground under the wheels, joint state)")
@@ -68,6 +74,8 @@ def main():
     noisy = bool(args.obs_noise or args.obs_offset or args.obs_dropout)
     if noisy and args.policy == "random":
         ap.error("--obs-noise / --obs-offset / --obs-dropout need --policy actor or student")
+    if args.occlusion and args.policy == "random":
+        ap.error("--occlusion needs --policy actor or student")
     if args.rollouts < 0 or (args.rollouts and args.policy != "actor"):
         ap.error("--rollouts N needs N >= 0 and --policy actor")
 
@@ -113,6 +121,12 @@ def main():
         from isaac_rover_amd.learning.noise import HeightmapNoise
         noise = HeightmapNoise(task._engine, task, sigma_point=args.obs_noise, sigma_offset=args.obs_offset, dropout=args.obs_dropout, seed=3)
         print(f"perception: rover_obs_noise, sigma_point {args.obs_noise} sigma_offset {args.obs_offset} dropout {args.obs_dropout}")
+    occlusion = hidden = None
+    if args.occlusion:
+        from isaac_rover_amd.learning.noise import HeightmapOcclusion
+        occlusion = HeightmapOcclusion(task._engine, task, camera=args.camera, step=args.sight_step, clearance=args.sight_clearance)
+        hidden = torch.zeros(args.envs, occlusion.columns, dtype=torch.uint8, device=task.device)
+        print(f"perception: rover_obs_occlusion, camera {tuple(args.camera)} step {args.sight_step} clearance {args.sight_clearance}")
     critic = memory = done = None
     if args.rollouts:
         from isaac_rover_amd.learning.model import DeterministicHeightmap
@@ -129,6 +143,8 @@ def main():
     t0 = time.perf_counter()
     for step in range(args.steps):
         seen = obs if noise is None else noise.apply(obs, reset=done)              # what the policy sees; the task keeps the clean obs
+        if occlusion is not None:                                                  # the poses are still the ones obs was made from
+            seen = occlusion.apply(obs, noisy=seen, out=None if seen is obs else seen, hidden=hidden)
         if student is not None:
             actions = student.act(seen, reset=None if done is None else done.bool())  # an env that just ended starts from a zero hidden state
         elif agent is None:
@@ -157,6 +173,8 @@ def main():
     dt = time.perf_counter() - t0
     print(f"{args.steps} steps x {args.envs} envs in {dt:.2f} s = {args.steps * args.envs / dt:,.0f} env-steps/s "
           f"(incl. {args.policy} policy + {'toy pose feeder' if args.sim == 'kinematic' else 'terrain-following motion model' + (', rocker-bogie posture' if args.suspension == 'bogie' else '')}); episodes finished: {episodes}; mean return {float(ret.mean()):.4f}")
+    if hidden is not None:
+        print(f"occlusion: {100.0 * float(hidden.float().mean()):.2f} % of the heightmap columns hidden at the last step")
     env.close()
 
 

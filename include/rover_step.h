@@ -559,7 +559,8 @@ ROVER_API int rover_bf16_round(const float *in, int64_t n, float *out);
 
 /* ---- Operand rules: the array arguments of the learning entry points ------------------------------------------------------------------ */
 /* rover_gae, rover_linear_backward, rover_linear_dgrad, rover_ppo_loss, rover_optim_create / _step, rover_gru_cell / _bf16 / _train,
- * rover_gru_cell_backward, rover_gated_sum / _backward, rover_obs_noise and rover_scaler_update / _apply check their arrays by one set of
+ * rover_gru_cell_backward, rover_gated_sum / _backward, rover_obs_noise, rover_obs_occlusion and rover_scaler_update / _apply check their
+ * arrays by one set of
  * rules (csrc/rover_operands.h).  An operand is (pointer, row stride in elements, rows, cols); a one-row array has no stride argument.
  * An operand the call does not look at (an input no requested output needs, stats_in outside NORMALIZE_GIVEN, ...) is not checked at all,
  * whatever its pointer and stride; an optional operand given as NULL neither.  For the others, in this order, each rule over all operands
@@ -932,6 +933,82 @@ ROVER_API int rover_obs_noise(rover_ctx *ctx, const rover_obs_noise_desc *d, voi
 /* Host only (no ctx, no device): *thr = (uint32) llrint(dropout * 2^24); ROVER_E_INVALID for a NULL thr or dropout outside [0, 1]. */
 ROVER_API int rover_obs_noise_threshold(double dropout, uint32_t *thr);
 
+/* ---- line-of-sight occlusion: which heightmap columns a mast camera cannot see (learning/noise.py:HeightmapOcclusion) --------------- */
+/* The task's heightmap is cast straight down from 3 cm above the ground, so it sees behind every rock; a camera on a mast does not.  The
+ * reference has no camera model (tasks/utils/camera/rover_depth.py is a vestige of one); what follows is this project's definition.  The
+ * task's own observation stays clean.  The library is built with -ffp-contract=off: every operation below is ONE f32 operation with one
+ * IEEE rounding, in the written order; / and sqrtf are the correctly rounded ones (as cell_coord of rover_height.h relies on).
+ * Configuration (rover_set_occlusion stores it in the ctx): camera[3], the camera in the body frame (forward, left, up; metres); step > 0,
+ * the spacing of the samples along a sight line (metres); clearance, by how much the ground must rise above the sight line to hide
+ * (metres); max_steps in 2 .. 4096, the most intervals a sight line is cut into; miss > 0, in observation units: a column at or beyond it
+ * holds the clipped 11.0 m sentinel (clipObservations) and has no point to ask about.
+ * Per call: row r, heightmap column c, 0 <= c < C = Ns + Nd; point j = c < Ns ? sparse_idx[c] : dense_idx[c - Ns]; body point b = the
+ * three f64 coordinates of points[j] (rover_set_distribution), each rounded to f32 once on the host (column 0 is forward); pose
+ * p = pos3[r], q = quat4[r] = (w, x, y, z), used as given and not normalised.
+ *   r00 = 1 - 2 (y y + z z)   r01 = 2 (x y - w z)       r02 = 2 (x z + w y)
+ *   r10 = 2 (x y + w z)       r11 = 1 - 2 (x x + z z)   r12 = 2 (y z - w x)
+ *   r20 = 2 (x z - w y)       r21 = 2 (y z + w x)       r22 = 1 - 2 (x x + y y)
+ *   rot(v)_i = (r_i0 v0 + r_i1 v1) + r_i2 v2
+ *   Cam = p + rot(camera)      S = p + rot(b)      D = (-r02, -r12, -r22)        (the ray of camera.py:196-212: body ZYX rotation, rover "down")
+ *   v = clean[r, first + c];   if !(|v| < miss): visible                          (a NaN is visible too)
+ *   d = 2 v (exact);           T_i = S_i + d D_i                                  (the point the ray cast measured: obs = distance / 2)
+ *   dx = Tx - Cam_x, dy = Ty - Cam_y, dz = Tz - Cam_z
+ *   L = sqrtf(dx dx + dy dy);  u = ceilf(L / step);  n = u < (float) max_steps ? (int) u : max_steps    (a NaN u: max_steps);  n <= 1: visible
+ *   for k = 1 .. n - 1:  t = (float) k / (float) n
+ *        h = the heightfield at (Cam_x + t dx, Cam_y + t dy), read exactly as rover_sample_height reads it (clamp, round half to even,
+ *            node, times vertical_scale; option cell_index_mode applies)
+ *        hidden if  h > (Cam_z + t dz) + clearance                                (a NaN height never hides, nor does a NaN sight line)
+ *   out[r, first + c] = hidden ? drop_value : in[r, first + c];   columns [0, first) are copied bit for bit when out != in
+ * Three arrays, on purpose: clean is the task's clean observation and gives the geometry; in is what a visible column is copied from — it
+ * may be clean itself, or the output of rover_obs_noise on it —; out may be exactly in (same pointer and stride), which leaves columns
+ * [0, first) alone.  The composition is rover_obs_noise(clean -> x) followed by rover_obs_occlusion(clean, x -> x): a hidden column reads
+ * exactly drop_value.
+ * Optional outputs: hidden_u8 [M, C] at a row stride in bytes, 1 = hidden, 0 otherwise, every column written; target3 [M, C, 3] dense,
+ * the point T — for a column that is visible by the miss test (no T exists) the three floats are LEFT UNWRITTEN.
+ * The result depends on the row's own inputs only: not on M, a stride, how a batch is sharded (a shard passes its own slices of pos3 and
+ * quat4), the order in which threads take columns, or eager execution against graph replay.
+ * Two routes compute the same bits (option "occlusion_route"): 0 marches the columns in obs order and reads every sample's node; 1 takes
+ * the columns in the order of rover_occlusion_order (far first, so that a wave's lanes march about equally long) and first asks a table
+ * of the maxima of 8 x 8-node tiles: where tilemax <= (Cam_z + t dz) + clearance the node cannot hide (h <= tilemax) and is not read.
+ * The test is conservative, so the mask is the plain march's by construction.  The default is 1.
+ * One launch (csrc/rover_occlusion.hip); plain vector loads and stores, no atomics.  The call allocates nothing, does not synchronise and
+ * can be captured in a graph.  M = 0 or F = 0: ROVER_OK, no launch.
+ * ROVER_E_INVALID before any launch (the descriptor is checked before the ctx is looked at, as for rover_obs_noise): a NULL descriptor;
+ * M < 0 or F < 0; first outside 0 .. F; a non-finite drop_value; and, unless M = 0 or F = 0, the operand rules: pos3, quat4, clean, in
+ * and out must be given, hidden_u8 and target3 are optional, out may not overlap clean (nor pos3, quat4 or another output), and may
+ * overlap in only by being exactly in.  An empty call still wants a ctx.
+ * ROVER_E_STATE: no distribution; no heightfield; no rover_set_occlusion; F - first != Ns + Nd; the distribution or the heightfield was
+ * set again after rover_set_occlusion (the message names rover_set_occlusion: call it again).
+ * rover_set_occlusion owns what it derives — the columns' f32 body points, the column order and the tile-max table (one small reduction
+ * launch over the heightfield; NaN nodes are ignored, as fmaxf ignores them) — under one validity key: the pair of counters that
+ * rover_set_distribution and rover_set_heightfield advance.  It needs both set, may synchronise, and refuses with ROVER_E_INVALID a NULL
+ * cfg, a non-finite field, step <= 0, max_steps outside 2 .. 4096 and miss <= 0 (all before the ctx is looked at). */
+typedef struct {
+    float camera[3];                               /* body frame: forward, left, up (m)                                            */
+    float step;                                    /* sample spacing along the sight line (m), > 0                                 */
+    float clearance;                               /* the ground hides when it is more than this above the sight line (m)          */
+    int32_t max_steps;                             /* 2 .. 4096                                                                    */
+    float miss;                                    /* observation units, > 0: |clean| >= miss has no point                         */
+} rover_occlusion_cfg;
+ROVER_API int rover_set_occlusion(rover_ctx *ctx, const rover_occlusion_cfg *cfg);
+typedef struct {
+    const float *pos3, *quat4;                     /* [M, 3], [M, 4] (w, x, y, z): the poses the observation was made from         */
+    const float *clean;     int64_t clean_stride;  /* [M, F]: the clean observation (the geometry)                                 */
+    const float *in;        int64_t in_stride;     /* [M, F]: what a visible column is copied from; may be clean                   */
+    float *out;             int64_t out_stride;    /* [M, F]; may be exactly in                                                    */
+    int32_t M, F, first;                           /* first: the number of leading columns left alone, 0 .. F                      */
+    float drop_value;
+    uint8_t *hidden_u8;     int64_t hidden_stride; /* optional [M, C] at a row stride in bytes: 1 = hidden                         */
+    float *target3;                                /* optional [M, C, 3] dense: T (unwritten where the miss test said visible)     */
+} rover_obs_occlusion_desc;
+ROVER_API int rover_obs_occlusion(rover_ctx *ctx, const rover_obs_occlusion_desc *d, void *stream);
+/* Host only (no ctx, no device): order[0 .. Ns + Nd) = the heightmap columns sorted by the horizontal distance of their body point from
+ * the camera, far first, ties in column order (a stable sort).  The key of column c is (bx - camera[0])^2 + (by - camera[1])^2 in
+ * double arithmetic on the f32-rounded coordinates.  ROVER_E_INVALID: a NULL points or order, P <= 0, Ns < 0 or Nd < 0, a NULL index list
+ * with a count above 0, a NULL or non-finite camera, an index outside [0, P). */
+ROVER_API int rover_occlusion_order(const double *points, int32_t P, const int64_t *sparse_idx, int32_t Ns, const int64_t *dense_idx,
+                                    int32_t Nd, const float camera[3], int32_t *order);
+
 /* ---- running standard scaler: skrl's RunningStandardScaler for states and values (learning/preprocess.py) ----------------------------- */
 /* The reference's train.py imports skrl's RunningStandardScaler (omniisaacgymenvs/train.py); every skrl PPO recipe for Isaac tasks passes
  * it for states and values.  skrl is no dependency: the definition is restated here.  The state is the caller's, all float64 on the
@@ -1207,6 +1284,8 @@ ROVER_API int rover_track_sizes(int32_t E, int32_t W, int32_t K, rover_track_siz
  * name = "lane_rebase" (variant 4, both arithmetics): how the staged kernel measures a steep ray against a row's suffix bounds.  0 = from
  *        the ray's origin; 1 (default) = from the point where the ray's line crosses the row's own height, so that the origin's height
  *        above the ground no longer widens the bound.  Read at every launch; no table and no plan depends on it, nor do the results.
+ * name = "occlusion_route" (rover_obs_occlusion): 0 = the plain march (columns in obs order, every sample's node read); 1 (default) = the
+ *        columns in rover_occlusion_order and the tile-max table in front of the node reads.  Read at every call; results do not depend on it.
  * name = "ray_precision": 0 (default) = the reference's fp32 mode, which the parity tests pin.
  *        1 = every ray origin / direction rounded to fp16 before the cell lookup and the ray maths, like the reference AS
  *        SHIPPED (Camera.dtype = float16: camera.py:55,212; rock_detect.py:319,371); f32 arithmetic after that.

@@ -134,6 +134,16 @@ class ObsNoiseDesc(C.Structure):
                 ("row_offset", C.c_int64)]
 
 
+class OcclusionCfg(C.Structure):
+    _fields_ = [("camera", C.c_float * 3), ("step", C.c_float), ("clearance", C.c_float), ("max_steps", C.c_int32), ("miss", C.c_float)]
+
+
+class ObsOcclusionDesc(C.Structure):
+    _fields_ = [("pos3", C.c_void_p), ("quat4", C.c_void_p), ("clean", C.c_void_p), ("clean_stride", C.c_int64), ("in_", C.c_void_p),
+                ("in_stride", C.c_int64), ("out", C.c_void_p), ("out_stride", C.c_int64), ("M", C.c_int32), ("F", C.c_int32), ("first", C.c_int32),
+                ("drop_value", C.c_float), ("hidden_u8", C.c_void_p), ("hidden_stride", C.c_int64), ("target3", C.c_void_p)]
+
+
 class ScalerPlanDesc(C.Structure):
     _fields_ = [("route", C.c_int32), ("rows_per_chunk", C.c_int32), ("n_chunks", C.c_int32), ("scratch_bytes", C.c_int64)]
 
@@ -297,6 +307,9 @@ SYMBOLS = {
     "rover_linear_dgrad_route": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32]),
     "rover_obs_noise": (C.c_int, [_P, C.POINTER(ObsNoiseDesc), _P]),
     "rover_obs_noise_threshold": (C.c_int, [C.c_double, _P]),
+    "rover_set_occlusion": (C.c_int, [_P, C.POINTER(OcclusionCfg)]),
+    "rover_obs_occlusion": (C.c_int, [_P, C.POINTER(ObsOcclusionDesc), _P]),
+    "rover_occlusion_order": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "rover_scaler_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(ScalerPlanDesc)]),
     "rover_scaler_update": (C.c_int, [_P, C.POINTER(ScalerUpdateDesc), _P]),
     "rover_scaler_apply": (C.c_int, [_P, C.POINTER(ScalerApplyDesc), _P]),
@@ -456,6 +469,41 @@ def obs_noise_threshold(dropout):
     if rc != 0:
         raise RoverError(f"rover_obs_noise_threshold failed ({rc}): {lib.rover_last_error(None).decode()}")
     return int(out.value)
+
+
+def occlusion_cfg(camera=(0.0, 0.0, 0.7), step=0.05, clearance=0.03, max_steps=256, miss=5.0):
+    """A rover_occlusion_cfg from plain values (the defaults are HeightmapOcclusion's)."""
+    cam = tuple(float(v) for v in camera)
+    if len(cam) != 3:
+        raise RoverError("occlusion_cfg: camera must have three components (forward, left, up)")
+    return OcclusionCfg((C.c_float * 3)(*cam), float(step), float(clearance), int(max_steps), float(miss))
+
+
+def obs_occlusion_desc(m, f, first, pos3=_FAKE, quat4=_FAKE, clean=_FAKE, in_=_FAKE + (1 << 44), out=_FAKE + (2 << 44), clean_stride=None,
+                       in_stride=None, out_stride=None, drop_value=0.0, hidden_u8=None, hidden_stride=None, target3=None):
+    """A rover_obs_occlusion_desc from plain values (pointers as integers; the strides default to ``f``, hidden's to ``f - first``)."""
+    f, first = int(f), int(first)
+    return ObsOcclusionDesc(pos3, quat4, clean, f if clean_stride is None else int(clean_stride), in_, f if in_stride is None else int(in_stride),
+                            out, f if out_stride is None else int(out_stride), int(m), f, first, float(drop_value), hidden_u8,
+                            f - first if hidden_stride is None else int(hidden_stride), target3)
+
+
+def occlusion_order(points, sparse_idx, dense_idx, camera=(0.0, 0.0, 0.7)):
+    """rover_occlusion_order: the heightmap columns far first by the horizontal distance of their body point from ``camera``, ties in
+    column order -> int32 numpy array [Ns + Nd], the permutation the occlusion kernel's route 1 walks.  Host only."""
+    pts, sp, de = _host(points, np.float64), _host(sparse_idx, np.int64).reshape(-1), _host(dense_idx, np.int64).reshape(-1)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise RoverError("occlusion_order: points must be [P,3]")
+    cam = np.ascontiguousarray(camera, dtype=np.float32).reshape(-1)
+    if cam.shape != (3,):
+        raise RoverError("occlusion_order: camera must have three components")
+    out = np.empty(len(sp) + len(de), dtype=np.int32)
+    lib = load()
+    rc = lib.rover_occlusion_order(pts.ctypes.data, pts.shape[0], sp.ctypes.data if len(sp) else None, len(sp), de.ctypes.data if len(de) else None,
+                                   len(de), cam.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RoverError(f"rover_occlusion_order failed ({rc}): {lib.rover_last_error(None).decode()}")
+    return out
 
 
 def scaler_plan(m, n):
@@ -1171,6 +1219,44 @@ class Engine:
         desc = obs_noise_desc(m, f, first, ip, op, is_, os_, sigma_point, sigma_offset, dropout, drop_value, dp(row_scale), dp(episode), seed, step,
                               dp(step_dev), row_offset)
         self._check(self.lib.rover_obs_noise(self._h, C.byref(desc), _stream(self._dev_index)), "rover_obs_noise")
+        return out
+
+    def configure_occlusion(self, camera=(0.0, 0.0, 0.7), step=0.05, clearance=0.03, max_steps=256, miss=5.0):
+        """The line-of-sight stage's configuration (rover_set_occlusion): needs set_distribution and set_heightfield, derives the column
+        order and the tile-max table of the heightfield, and has to be called again after either of the two is set again."""
+        cfg = occlusion_cfg(camera, step, clearance, max_steps, miss)
+        self._check(self.lib.rover_set_occlusion(self._h, C.byref(cfg)), "rover_set_occlusion")
+
+    def obs_occlusion(self, clean, in_=None, out=None, *, first, pos, quat, drop_value=0.0, hidden=None, target=None):
+        """Which heightmap columns of ``clean`` [m, f] a mast camera at the poses ``pos`` [m, 3] / ``quat`` [m, 4] (w, x, y, z) cannot see
+        (rover_obs_occlusion, one launch): out = ``drop_value`` where hidden, ``in_`` elsewhere (``in_`` None: ``clean``; it may be the
+        output of obs_noise on ``clean``); columns [0, first) copied.  ``out`` None: a new tensor; ``out is in_`` (or a view of the same
+        memory): in place — but never ``clean`` itself.  ``hidden``: optional uint8 [m, f - first], 1 = hidden.  ``target``: optional
+        float32 [m, f - first, 3], the measured points (unwritten where ``|clean| >= miss``).  Strides come from the tensors."""
+        what = "obs_occlusion"
+        self._f32_rows(clean, "clean", what)
+        m, f = clean.shape
+        if in_ is None:
+            in_ = clean
+        self._f32_rows(in_, "in_", what, (m, f))
+        if out is None:
+            out = torch.empty(m, f, device=clean.device)
+        self._f32_rows(out, "out", what, (m, f))
+        if clean.device != self.device or in_.device != self.device or out.device != self.device:
+            raise RoverError(f"{what}: clean, in_ and out must be on {self.device}")
+        self._chk(pos, (m, 3), torch.float32, "pos")
+        self._chk(quat, (m, 4), torch.float32, "quat")
+        if pos is None or quat is None:
+            raise RoverError(f"{what}: pos [m, 3] and quat [m, 4] must be given")
+        c = f - int(first)
+        if hidden is not None and (not hidden.is_cuda or hidden.device != self.device or hidden.dtype != torch.uint8 or hidden.dim() != 2
+                                   or tuple(hidden.shape) != (m, c) or (c > 0 and hidden.stride(1) != 1)):
+            raise RoverError(f"{what}: hidden must be a uint8 GPU matrix [{m},{c}] with unit column stride")
+        self._chk(target, (m, c, 3), torch.float32, "target")
+        (cp, cs), (ip, is_), (op, os_), (hp, hs) = _rows(clean, f, m), _rows(in_, f, m), _rows(out, f, m), _rows(hidden, c, m)
+        desc = obs_occlusion_desc(m, f, first, pos.data_ptr(), quat.data_ptr(), cp, ip, op, cs, is_, os_, drop_value, hp, hs,
+                                  None if target is None else target.data_ptr())
+        self._check(self.lib.rover_obs_occlusion(self._h, C.byref(desc), _stream(self._dev_index)), "rover_obs_occlusion")
         return out
 
     scaler_plan = staticmethod(scaler_plan)

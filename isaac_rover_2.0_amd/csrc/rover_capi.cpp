@@ -100,6 +100,18 @@ struct OptimHandle {
     std::vector<Span> spans;            // everything the step reads or writes through the handle (norm_out must stay clear of it)
 };
 
+// Everything rover_set_occlusion derives, under one validity key: the counters of rover_set_distribution and rover_set_heightfield it was
+// built under.  rover_obs_occlusion runs only while both still stand.
+struct OcclusionTables {
+    bool set = false;
+    rover_occlusion_cfg cfg{};
+    DevBuf<float> body3;                // [C][3] the columns' body points, f64 rounded to f32 once
+    DevBuf<int32_t> order;              // [C] rover_occlusion_order
+    DevBuf<float> tilemax;              // [TN0][TN1] maxima of the OCC_TILE x OCC_TILE-node tiles of the heightfield
+    int32_t TN0 = 0, TN1 = 0;
+    uint64_t dist_gen = 0, hf_gen = 0;  // the key
+};
+
 struct rover_ctx {
     rover_cfg cfg{};
     std::string err;
@@ -123,6 +135,9 @@ struct rover_ctx {
     DevBuf<float4> d_grid_xyr;
     StoneGridDev sgrid{};
     bool have_stones = false;
+    uint64_t dist_gen = 0, hf_gen = 0;  // advanced by rover_set_distribution / rover_set_heightfield: the validity key of derived tables
+    OcclusionTables occ;                // rover_set_occlusion
+    int32_t occlusion_route = 1;        // option "occlusion_route": 0 plain march, 1 ordered columns + tile-max table (results do not depend on it)
     // per-step workspace
     DevBuf<RayRec> d_rays;
     DevBuf<float> d_dist_out;       // [E*R8]
@@ -566,6 +581,8 @@ static const KnobRow kKnobs[] = {
     // (what an observation means changes with these two: rover_calculate_metrics wants a fresh rover_get_observations)
     {"ray_precision", nullptr, 0, 2, 1, 0, 0, KNOB_SET(precision, (int)v), KNOB_REPLAN | KNOB_RAYS_OBS, "0 (fp32), 1 (fp16 sources) or 2 (as shipped)"},
     {"cell_index_mode", nullptr, 0, 1, 1, 0, 0, KNOB_SET(cell_rcp, (int32_t)v), KNOB_RAYS_OBS, "0 (cpu_div) or 1 (cuda_rcp)"},
+    {"occlusion_route", nullptr, 0, 1, 1, 0, 0, KNOB_SET(occlusion_route, (int32_t)v), 0,      // read at every call: no table depends on it
+     "0 (plain march) or 1 (ordered columns and the tile-max table)"},
 };
 #undef KNOB_SET
 
@@ -672,6 +689,7 @@ int rover_set_distribution(rover_ctx* c, const double* pts, int32_t P, const int
     for (int32_t v : idx)
         if (v < 0 || v >= P) return fail(c, ROVER_E_INVALID, "set_distribution: index %d outside [0,%d)", v, P);
     c->have_dist = false;
+    ++c->dist_gen;
     c->d_dist.reset(); c->d_obs_idx.reset();
     const int r = [&]() -> int {
         HIP_TRY(c, c->d_dist.alloc(hp.size()));
@@ -694,6 +712,7 @@ int rover_set_heightfield(rover_ctx* c, const float* hm, int32_t N0, int32_t N1,
     HIP_TRY(c, d.alloc((uint64_t)N0 * N1));
     HIP_TRY(c, hipMemcpy(d.get(), hm, d.bytes(), hipMemcpyDefault));       // (the previous heightfield stays in place)
     c->d_hm = std::move(d);
+    ++c->hf_gen;
     c->hf = HeightDev{c->d_hm.get(), N0, N1, hscale, vscale, sx, sy, 1.0f / hscale, c->cell_rcp};
     c->have_hf = true;
     return ROVER_OK;
@@ -2398,6 +2417,113 @@ int rover_obs_noise(rover_ctx* c, const rover_obs_noise_desc* d, void* stream) {
 int rover_obs_noise_threshold(double dropout, uint32_t* thr) {
     if (!thr || !(dropout >= 0.0 && dropout <= 1.0)) return fail(nullptr, ROVER_E_INVALID, "obs_noise_threshold: null argument or dropout = %g outside [0, 1]", dropout);
     *thr = (uint32_t)llrint(dropout * 16777216.0);
+    return ROVER_OK;
+}
+
+// Host only: the heightmap columns far first by the horizontal distance of their body point from the camera, ties in column order
+int rover_occlusion_order(const double* points, int32_t P, const int64_t* sparse_idx, int32_t Ns, const int64_t* dense_idx, int32_t Nd,
+                          const float camera[3], int32_t* order) {
+    if (!points || !order || !camera || P <= 0 || Ns < 0 || Nd < 0 || (Ns > 0 && !sparse_idx) || (Nd > 0 && !dense_idx))
+        return fail(nullptr, ROVER_E_INVALID, "occlusion_order: null argument or bad counts (P=%d Ns=%d Nd=%d)", P, Ns, Nd);
+    if (!std::isfinite(camera[0]) || !std::isfinite(camera[1]) || !std::isfinite(camera[2]))
+        return fail(nullptr, ROVER_E_INVALID, "occlusion_order: the camera is not finite");
+    const int32_t C = Ns + Nd;
+    std::vector<double> key((size_t)C);
+    for (int32_t c = 0; c < C; ++c) {
+        const int64_t j = c < Ns ? sparse_idx[c] : dense_idx[c - Ns];
+        if (j < 0 || j >= P) return fail(nullptr, ROVER_E_INVALID, "occlusion_order: index %lld outside [0,%d)", (long long)j, P);
+        const double ax = (double)(float)points[3 * j] - (double)camera[0], ay = (double)(float)points[3 * j + 1] - (double)camera[1];
+        const double k = ax * ax + ay * ay;
+        key[(size_t)c] = k == k ? k : -1.0;        // a NaN point goes last
+    }
+    for (int32_t c = 0; c < C; ++c) order[c] = c;
+    std::stable_sort(order, order + C, [&](int32_t a, int32_t b) { return key[(size_t)a] > key[(size_t)b]; });
+    return ROVER_OK;
+}
+
+// The cfg is validated before the ctx is looked at.  Builds the three derived tables whole, then moves them into the ctx in one assignment
+// (a failure half way leaves the previous configuration in force).
+int rover_set_occlusion(rover_ctx* c, const rover_occlusion_cfg* cfg) {
+    if (!cfg) return fail(c, ROVER_E_INVALID, "set_occlusion: null cfg");
+    if (!std::isfinite(cfg->camera[0]) || !std::isfinite(cfg->camera[1]) || !std::isfinite(cfg->camera[2]) || !std::isfinite(cfg->step) ||
+        !std::isfinite(cfg->clearance) || !std::isfinite(cfg->miss))
+        return fail(c, ROVER_E_INVALID, "set_occlusion: camera, step, clearance and miss must be finite");
+    if (!(cfg->step > 0.0f)) return fail(c, ROVER_E_INVALID, "set_occlusion: step = %g is not > 0", (double)cfg->step);
+    if (cfg->max_steps < 2 || cfg->max_steps > 4096) return fail(c, ROVER_E_INVALID, "set_occlusion: max_steps = %d outside 2 .. 4096", cfg->max_steps);
+    if (!(cfg->miss > 0.0f)) return fail(c, ROVER_E_INVALID, "set_occlusion: miss = %g is not > 0", (double)cfg->miss);
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "set_occlusion: null ctx");
+    if (!c->have_dist) return fail(c, ROVER_E_STATE, "set_occlusion: rover_set_distribution first");
+    if (!c->have_hf) return fail(c, ROVER_E_STATE, "set_occlusion: rover_set_heightfield first");
+    USE_DEVICE(c);
+    const int32_t C = c->Ns + c->Nd;
+    std::vector<double> pts((size_t)c->P * 3);
+    std::vector<int32_t> idx((size_t)C);
+    HIP_TRY(c, hipMemcpy(pts.data(), c->d_dist.get(), pts.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (C) HIP_TRY(c, hipMemcpy(idx.data(), c->d_obs_idx.get(), idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<int64_t> idx64(idx.begin(), idx.end());
+    std::vector<float> body((size_t)C * 3);
+    for (int32_t k = 0; k < C; ++k)
+        for (int i = 0; i < 3; ++i) body[(size_t)3 * k + i] = (float)pts[(size_t)3 * idx[(size_t)k] + i];
+    std::vector<int32_t> order((size_t)C);
+    if (int e = rover_occlusion_order(pts.data(), c->P, idx64.data(), c->Ns, idx64.data() + c->Ns, c->Nd, cfg->camera, order.data()))
+        return fail(c, e, "set_occlusion: %s", g_create_err.c_str());
+    OcclusionTables t;
+    t.cfg = *cfg;
+    t.TN0 = (c->hf.N0 + OCC_TILE - 1) / OCC_TILE; t.TN1 = (c->hf.N1 + OCC_TILE - 1) / OCC_TILE;
+    HIP_TRY(c, t.body3.alloc(body.size() + 1));
+    HIP_TRY(c, t.order.alloc(order.size() + 1));
+    HIP_TRY(c, t.tilemax.alloc((size_t)t.TN0 * t.TN1));
+    if (C) HIP_TRY(c, hipMemcpy(t.body3.get(), body.data(), body.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (C) HIP_TRY(c, hipMemcpy(t.order.get(), order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, launch_occlusion_tiles(c->hf, t.tilemax.get(), t.TN0, t.TN1, nullptr));
+    HIP_TRY(c, hipStreamSynchronize(nullptr));
+    t.dist_gen = c->dist_gen; t.hf_gen = c->hf_gen;
+    t.set = true;
+    c->occ = std::move(t);
+    return ROVER_OK;
+}
+
+// The descriptor is validated before the ctx is looked at, as for rover_obs_noise
+int rover_obs_occlusion(rover_ctx* c, const rover_obs_occlusion_desc* d, void* stream) {
+    if (!d) return fail(c, ROVER_E_INVALID, "obs_occlusion: null descriptor");
+    if (d->M < 0 || d->F < 0) return fail(c, ROVER_E_INVALID, "obs_occlusion: M = %d or F = %d is negative", d->M, d->F);
+    if (d->first < 0 || d->first > d->F) return fail(c, ROVER_E_INVALID, "obs_occlusion: first = %d outside 0 .. F = %d", d->first, d->F);
+    if (!std::isfinite(d->drop_value)) return fail(c, ROVER_E_INVALID, "obs_occlusion: drop_value is not finite");
+    const bool empty = d->M == 0 || d->F == 0;
+    const int64_t C = (int64_t)d->F - d->first;
+    if (!empty) {
+        Operands ops("obs_occlusion");
+        ops.read("pos3", d->pos3, 3, d->M, 3, 4).read("quat4", d->quat4, 4, d->M, 4, 4)
+            .read("clean", d->clean, d->clean_stride, d->M, d->F, 4).read("in", d->in, d->in_stride, d->M, d->F, 4)
+            .written("out", d->out, d->out_stride, d->M, d->F, 4)
+            .written("hidden_u8", d->hidden_u8, d->hidden_stride, d->M, C, 1, OP_OPTIONAL).written("target3", d->target3, 3 * C, d->M, 3 * C, 4, OP_OPTIONAL)
+            .same_array("out", "in");
+        if (int e = check_operands(c, ops, false)) return e;
+    }
+    if (!c) return fail(nullptr, ROVER_E_INVALID, "obs_occlusion: null ctx");
+    if (!c->have_dist) return fail(c, ROVER_E_STATE, "obs_occlusion: rover_set_distribution first");
+    if (!c->have_hf) return fail(c, ROVER_E_STATE, "obs_occlusion: rover_set_heightfield first");
+    if (!c->occ.set) return fail(c, ROVER_E_STATE, "obs_occlusion: rover_set_occlusion first");
+    if (c->occ.dist_gen != c->dist_gen || c->occ.hf_gen != c->hf_gen)
+        return fail(c, ROVER_E_STATE, "obs_occlusion: the %s was set again after rover_set_occlusion: call rover_set_occlusion again",
+                    c->occ.dist_gen != c->dist_gen ? "distribution" : "heightfield");
+    if (C != (int64_t)c->Ns + c->Nd)
+        return fail(c, ROVER_E_STATE, "obs_occlusion: F - first = %lld columns, the distribution has Ns + Nd = %d", (long long)C, c->Ns + c->Nd);
+    if (empty) return ROVER_OK;
+    USE_DEVICE(c);
+    const OcclusionTables& t = c->occ;
+    OcclusionArgs a{};
+    a.h = c->hf;
+    a.tilemax = t.tilemax.get(); a.TN0 = t.TN0; a.TN1 = t.TN1;
+    a.body3 = t.body3.get(); a.order = t.order.get();
+    a.pos3 = d->pos3; a.quat4 = d->quat4;
+    a.clean = d->clean; a.clean_stride = d->clean_stride; a.in = d->in; a.in_stride = d->in_stride; a.out = d->out; a.out_stride = d->out_stride;
+    a.hidden = d->hidden_u8; a.hidden_stride = d->hidden_stride; a.target3 = d->target3;
+    a.M = d->M; a.F = d->F; a.first = d->first;
+    for (int i = 0; i < 3; ++i) a.camera[i] = t.cfg.camera[i];
+    a.step = t.cfg.step; a.clearance = t.cfg.clearance; a.miss = t.cfg.miss; a.drop_value = d->drop_value;
+    a.max_steps = t.cfg.max_steps; a.route = c->occlusion_route;
+    HIP_TRY(c, launch_obs_occlusion(a, (hipStream_t)stream));
     return ROVER_OK;
 }
 

@@ -352,6 +352,29 @@ struct ObsNoiseArgs {
 };
 hipError_t launch_obs_noise(const ObsNoiseArgs& a, hipStream_t s);
 
+// The line-of-sight occlusion of the heightmap columns (rover_obs_occlusion of the C ABI, validated; rover_occlusion.hip): the definition
+// is in include/rover_step.h.  body3, order and tilemax are rover_set_occlusion's tables.
+#define OCC_TILE 8                         // nodes per side of a tile of the tile-max table
+struct OcclusionArgs {
+    HeightDev h;
+    const float* tilemax;                  // [TN0][TN1]: max of hm * vscale over the tile's nodes, NaN ignored; -inf for a tile of NaNs
+    int32_t TN0, TN1;                      // ceil(N0 / OCC_TILE), ceil(N1 / OCC_TILE)
+    const float* body3;                    // [C][3] the columns' body points, f32
+    const int32_t* order;                  // [C] a permutation of the columns (route 1)
+    const float *pos3, *quat4;             // [M, 3], [M, 4]
+    const float* clean; int64_t clean_stride;
+    const float* in; int64_t in_stride;
+    float* out; int64_t out_stride;        // out == in (and the same stride): in place, the first columns are then left alone
+    uint8_t* hidden; int64_t hidden_stride;   // optional [M, C]
+    float* target3;                        // optional [M, C, 3]
+    int32_t M, F, first;
+    float camera[3], step, clearance, miss, drop_value;
+    int32_t max_steps;
+    int32_t route;                         // 0 plain march, 1 ordered columns + tile table
+};
+hipError_t launch_obs_occlusion(const OcclusionArgs& a, hipStream_t s);
+hipError_t launch_occlusion_tiles(const HeightDev& h, float* tilemax, int32_t TN0, int32_t TN1, hipStream_t s);
+
 // skrl's RunningStandardScaler (rover_scaler_update / rover_scaler_apply of the C ABI, validated; rover_scaler.hip).  The plan's numbers
 // come from rover_scaler_plan; `partials` points one double past the scratch's start (the header double keeps the count the call
 // started from): three planes [n_chunks][N] of count, mean, M2.

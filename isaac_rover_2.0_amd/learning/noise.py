@@ -13,6 +13,9 @@ under one seed): a value depends on (seed, call counter, global env, column) and
 shard that passes its ``env_offset`` reproduces its slice of the whole —, and no second window-sized tensor of random numbers exists.
 The two counters are device tensors at fixed addresses, advanced by torch ops enqueued after the launch: after one warm-up call,
 ``apply`` can be captured in a graph, and eager calls and replays continue one stream of draws.
+
+``HeightmapOcclusion`` is the scene-dependent stage behind it, ONE ``rover_obs_occlusion`` launch (``csrc/rover_occlusion.hip``): a column
+whose measured point a camera on the mast cannot see — the ground rises above the sight line — reads ``drop_value``.  It is stateless.
 """
 from __future__ import annotations
 
@@ -121,3 +124,77 @@ class HeightmapNoise:
                 cur.copy_(v)
             else:
                 setattr(self, name, torch.as_tensor(v).to(self.device).clone())
+
+
+OCCLUSION_PARAMS = ("camera", "step", "clearance", "max_steps", "miss", "drop_value")
+
+
+class HeightmapOcclusion:
+    def __init__(self, engine, task_or_info, camera=(0.0, 0.0, 0.7), step=0.05, clearance=0.03, max_steps=256, miss=5.0, drop_value=0.0):
+        """The line-of-sight stage: a heightmap column whose measured point a camera at ``camera`` (body frame: forward, left, up, in
+        metres) cannot see reads ``drop_value``.  ``step``: spacing of the samples along a sight line; ``clearance``: by how much the
+        ground must rise above the line to hide; ``max_steps``: the most intervals per line; ``miss``: |clean| at or beyond it is the
+        clipped sentinel and stays as it is.  ``task_or_info`` as for ``HeightmapNoise``.  With an engine the constructor calls
+        ``configure()``: the engine must hold its distribution and heightfield (a RoverTask's does).  ``engine`` None: a parameter
+        carrier whose ``apply`` raises.  The object is stateless: no counters, ``state_dict`` holds the parameters only."""
+        self.engine = engine
+        self.task = None if hasattr(task_or_info, "keys") else task_or_info
+        self.info = _info_of(task_or_info)
+        cam = tuple(float(v) for v in camera)
+        if len(cam) != 3:
+            raise ValueError(f"HeightmapOcclusion: camera = {camera} must have three components (forward, left, up)")
+        for name, v in (("camera", cam[0]), ("camera", cam[1]), ("camera", cam[2]), ("step", step), ("clearance", clearance), ("miss", miss),
+                        ("drop_value", drop_value)):
+            if not math.isfinite(float(v)):
+                raise ValueError(f"HeightmapOcclusion: {name} = {v} must be finite")
+        if not float(step) > 0.0:
+            raise ValueError(f"HeightmapOcclusion: step = {step} must be > 0")
+        if not float(miss) > 0.0:
+            raise ValueError(f"HeightmapOcclusion: miss = {miss} must be > 0")
+        if int(max_steps) != max_steps or not 2 <= int(max_steps) <= 4096:
+            raise ValueError(f"HeightmapOcclusion: max_steps = {max_steps} outside 2 .. 4096")
+        self.camera, self.step, self.clearance, self.max_steps = cam, float(step), float(clearance), int(max_steps)
+        self.miss, self.drop_value = float(miss), float(drop_value)
+        if engine is not None:
+            self.configure()
+
+    columns = HeightmapNoise.columns
+
+    def configure(self):
+        """rover_set_occlusion with this object's parameters: to be called again after the engine's distribution or heightfield was set
+        again (``apply`` then raises with a message that says so)."""
+        if self.engine is None:
+            raise RuntimeError("HeightmapOcclusion.configure needs an Engine (this object was made without one)")
+        self.engine.configure_occlusion(self.camera, self.step, self.clearance, self.max_steps, self.miss)
+
+    def apply(self, obs, noisy=None, out=None, pos=None, quat=None, hidden=None):
+        """obs [E, F], the task's CLEAN observation -> out [E, F]: ``noisy`` (None: ``obs``; usually ``HeightmapNoise.apply(obs)``) with
+        the hidden heightmap columns at ``drop_value``.  ``out`` None: a new tensor; it may be ``noisy`` itself, or a row view such as
+        ``x[:, t]`` of a [B, T, F] window, but never ``obs``.  ``pos`` [E, 3] / ``quat`` [E, 4]: the poses the observation was made
+        from; they default to the task's ``_rover.get_world_poses()``, which are those until the next sim step.  ``hidden``: optional
+        uint8 [E, sparse + dense] receiving the mask."""
+        if self.engine is None:
+            raise RuntimeError("HeightmapOcclusion.apply needs an Engine (this object was made without one)")
+        e, f = obs.shape
+        ex = self.columns
+        if f < ex:
+            raise ValueError(f"HeightmapOcclusion: obs has {f} columns, the heightmap alone has sparse + dense = {ex}")
+        if pos is None or quat is None:
+            if self.task is None:
+                raise ValueError("HeightmapOcclusion.apply: pos and quat must be given (this object was made from an info mapping, not a task)")
+            tp, tq = self.task._rover.get_world_poses()
+            pos, quat = tp if pos is None else pos, tq if quat is None else quat
+        return self.engine.obs_occlusion(obs, noisy, out, first=f - ex, pos=pos, quat=quat, drop_value=self.drop_value, hidden=hidden)
+
+    def state_dict(self):
+        return OrderedDict((k, getattr(self, k)) for k in OCCLUSION_PARAMS)
+
+    def load_state_dict(self, sd):
+        """The parameters from ``sd`` (a missing key is a KeyError naming it); with an engine, ``configure()`` again."""
+        for k in OCCLUSION_PARAMS:
+            if k not in sd:
+                raise KeyError(f"HeightmapOcclusion.load_state_dict: missing key '{k}'")
+        for k in OCCLUSION_PARAMS:
+            setattr(self, k, tuple(float(v) for v in sd[k]) if k == "camera" else type(getattr(self, k))(sd[k]))
+        if self.engine is not None:
+            self.configure()
