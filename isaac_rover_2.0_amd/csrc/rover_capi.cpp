@@ -1,11 +1,9 @@
-// rover_capi.cpp — C-ABI layer of librover_step.so (include/rover_step.h): context, library-owned device
-// tables, argument checks, kernel sequencing.  No torch, no exceptions across the boundary.
+// rover_capi.cpp — the env step's unit of the C-ABI layer of librover_step.so (include/rover_step.h): context, library-owned device tables,
+// planning and allocation, the knob table, kernel sequencing of the step and the ray cast, evaluation, resets, profiling.  It also defines
+// fail, which rover_ctx.h declares for every unit, and keeps the thread's no-ctx error string.  The other units: rover_capi_scene.cpp (scene
+// builders), rover_capi_learn.cpp (learning kernels), rover_capi_sim.cpp (sensor, motion, statistics).  No torch, no exceptions across the boundary.
 #include "../../include/rover_step.h"
-#include "rover_internal.h"
-#include "rover_bf16.h"
-#include "rover_philox.h"
-#include "rover_operands.h"
-#include "rover_plan.h"
+#include "rover_ctx.h"
 
 #include <algorithm>
 #include <cstdarg>
@@ -13,170 +11,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <new>
-#include <string>
-#include <vector>
-
-using namespace rover;
-
-// One hipMalloc allocation, owned: freed when the owner is reset, replaced or destroyed (on the ctx's device: every entry point that can
-// free holds a DeviceGuard).  Move-only.
-template <typename T>
-class DevBuf {
-  public:
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
-        return *this;
-    }
-    ~DevBuf() { reset(); }
-    // n elements in place of what the buffer held; on failure it holds nothing and the runtime's sticky error is cleared
-    hipError_t alloc(size_t n) {
-        reset();
-        const hipError_t e = hipMalloc((void**)&p_, n * sizeof(T));
-        if (e != hipSuccess) { (void)hipGetLastError(); p_ = nullptr; return e; }
-        n_ = n;
-        return e;
-    }
-    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }
-    T* get() const { return p_; }
-    uint64_t bytes() const { return (uint64_t)n_ * sizeof(T); }
-
-  private:
-    T* p_ = nullptr;
-    size_t n_ = 0;
-};
-
-// The tables of one map for one rejection proof: proof 0 is the f32 one (ray_precision 0 / 1), proof 1 the as-shipped fp16 arithmetic's
-// (ray_precision 2).  The culled ray cast (variant 3) reads ctab and far; the staged one (variant 4) lvl / lrec / lid, which are optional.
-struct ProofTables {
-    DevBuf<uint4> ctab;                 // [T_int] bounding-sphere centre + scaled unit normal per triangle (16 B)
-    DevBuf<float4> far;                 // [cell][2] far-pair bounds, then [cell] near-pair bounds
-    DevBuf<float4> lvl;                 // staged: [cell][lane_lvl_stride()] header, suffix bounds, the suffixes' cones
-    DevBuf<uint4> lrec;                 // staged: [cell][2][pp] pair records of tests (A) and (B) in group-bound order
-    DevBuf<uint2> lid;                  // staged: [cell][pp] the pairs' triangle ids
-    int64_t always = 0, nocone = 0;     // always-candidate triangles, cells without a cone (counted when the tables were built)
-    LaneTables view() const { return LaneTables{lvl.get(), lrec.get(), lid.get()}; }
-};
-
-// Everything rover_set_knn_map builds for one map; built whole, then moved into the ctx in one assignment
-struct MapTables {
-    DevBuf<uint16_t> table;             // re-packed map, per-cell contiguous fp16 block [X*Y][9][K8]
-    KnnDev knn{};                       // its geometry; knn.table = table.get()
-    DevBuf<int32_t> cull_idx;           // culled / staged ray cast: [cell][K8] the cell's triangles in the internal numbering (null: not built)
-    DevBuf<uint16_t> rtab;              // [T_int] the nine fp16 vertex components of a triangle (20 B)
-    ProofTables proof[2];
-    uint32_t lane_pp = 0;               // pairs per row of the staged kernel's records
-    bool lane_box = false;              // the f32 proof's staged records are boxes (one per pair), not two spheres
-    bool lane_pair_rows = false;        // the staged tables (both proofs) hold one row per two cells that neighbour in iy (lane_pp pairs: their union)
-    int64_t tris = 0, farok = 0, cells = 0;   // triangles; cells whose far bound can hold for a usual ray (far_build_kernel); cells
-    uint64_t bytes() const {
-        uint64_t b = table.bytes() + cull_idx.bytes() + rtab.bytes();
-        for (const ProofTables& p : proof) b += p.ctab.bytes() + p.far.bytes() + p.lvl.bytes() + p.lrec.bytes() + p.lid.bytes();
-        return b;
-    }
-};
-
-// The candidate queue of the culled / staged ray cast and its per-wave counters, with the two facts the steps check about them
-struct CullQueue {
-    DevBuf<uint2> entries;              // one region of 1 024 entries per wave of a launch
-    DevBuf<uint4> stats;                // per-wave counters of the last culled launch (rover_get_cull_info)
-    StepPlan sized_for{};               // the plan both were sized for (alloc_cull_queue)
-    StepPlan counters_written_under{};  // the plan the counters were last written under (run_raycast)
-};
-
-// One rover_optim_create: the ctx owns the chunk table, the partials and the record; the tensors and the state are the caller's
-struct OptimHandle {
-    bool live = false;
-    DevBuf<OptimChunk> chunks;          // [n_chunks] (optim_plan's chunks with their addresses)
-    DevBuf<double> partials;            // [n_chunks] sums of g*g
-    DevBuf<OptimRecord> record;         // [1] what the prepare launch leaves for the apply launch
-    uint32_t n_chunks = 0;
-    float *exp_avg = nullptr, *exp_avg_sq = nullptr;
-    int64_t* step = nullptr;
-    int32_t* stopped = nullptr;
-    std::vector<Span> spans;            // everything the step reads or writes through the handle (norm_out must stay clear of it)
-};
-
-// Everything rover_set_occlusion derives, under one validity key: the counters of rover_set_distribution and rover_set_heightfield it was
-// built under.  rover_obs_occlusion runs only while both still stand.
-struct OcclusionTables {
-    bool set = false;
-    rover_occlusion_cfg cfg{};
-    DevBuf<float> body3;                // [C][3] the columns' body points, f64 rounded to f32 once
-    DevBuf<int32_t> order;              // [C] rover_occlusion_order
-    DevBuf<float> tilemax;              // [TN0][TN1] maxima of the OCC_TILE x OCC_TILE-node tiles of the heightfield
-    int32_t TN0 = 0, TN1 = 0;
-    uint64_t dist_gen = 0, hf_gen = 0;  // the key
-};
-
-struct rover_ctx {
-    rover_cfg cfg{};
-    std::string err;
-    MapTables maps[2];                  // terrain, rocks
-    Knobs knobs{};                      // what rover_set_option / the ROVER_* environment set (the knob table below)
-    StepPlan plan{};                    // the step in force (replan): what runs and what the plan-dependent buffers are sized for
-    StepPlan ws_plan{};                 // the plan the ray workspace was produced with (cast_rays): the sorted list, rover_get_cull_info
-    CullQueue queue;
-    // distribution
-    DevBuf<double> d_dist;          // [P][3]
-    DevBuf<int32_t> d_obs_idx;      // [Ns+Nd]
-    int32_t P = 0, Ns = 0, Nd = 0;
-    bool have_dist = false;
-    // heightfield / stones (hf and sgrid: the kernels' views of the owners beside them)
-    DevBuf<float> d_hm;
-    HeightDev hf{};
-    bool have_hf = false;
-    DevBuf<float> d_stones;         // [S][7]
-    int32_t S = 0;
-    DevBuf<uint32_t> d_grid_start;
-    DevBuf<float4> d_grid_xyr;
-    StoneGridDev sgrid{};
-    bool have_stones = false;
-    uint64_t dist_gen = 0, hf_gen = 0;  // advanced by rover_set_distribution / rover_set_heightfield: the validity key of derived tables
-    OcclusionTables occ;                // rover_set_occlusion
-    int32_t occlusion_route = 1;        // option "occlusion_route": 0 plain march, 1 ordered columns + tile-max table (results do not depend on it)
-    // per-step workspace
-    DevBuf<RayRec> d_rays;
-    DevBuf<float> d_dist_out;       // [E*R8]
-    DevBuf<float> d_euler;          // [E,3]
-    DevBuf<float> d_heading;        // [E]
-    DevBuf<int64_t> d_ids_work;     // [E]
-    DevBuf<uint32_t> d_goal_work;   // [2][E] work lists of generate_goals
-    DevBuf<uint32_t> d_block_cnt;   // [ceil(E/256)] + a spare word
-    // ray binning (raycast variant 2)
-    DevBuf<uint32_t> d_bins;            // [E*R8] bin key per slot
-    DevBuf<uint32_t> d_bkt_table;       // [n_buckets * n_blocks] counts -> offsets
-    bool bkt_table_dirty = true;        // not known to be all zero (what prep_rays_kernel's fused histogram starts from): a step failed half way
-    DevBuf<uint2> d_pairs;              // [E*R8] (bin, slot) after the coarse partition
-    int precision = 0;                  // option "ray_precision": 0 fp32 mode, 1 fp16 sources, 2 as shipped (fp16 maths)
-    DevBuf<uint32_t> d_block_sums;      // [4096] bucket totals + [4097] bucket starts
-    DevBuf<uint32_t> d_sorted;          // [E*R8] ray slots sorted by (map, cell)
-    int32_t cell_rcp = 0;               // option "cell_index_mode": 0 cpu_div (x / 0.1), 1 cuda_rcp (x * (1 / 0.1))
-    int32_t lane_rebase = 1;            // option "lane_rebase": the staged kernel's level loop measures a ray from the point where its line crosses the row's height (bit 4 of LaneArgs::forms; results do not depend on it)
-    DevBuf<float> d_mlp_scratch;        // partial sums of the split-k small-batch encoder path (rover_mlp_chain_forward)
-    DevBuf<double> d_gae_partials;      // [GAE_MAX_BLOCKS][3] per-block (count, mean, M2) of rover_gae, sized once at rover_create
-    DevBuf<double> d_ppo_partials;      // [PPO_MAX_BLOCKS][3 + GAUSS_MAX_A] per-block sums of rover_ppo_loss, sized once at rover_create
-    std::vector<OptimHandle> optims;    // rover_optim_create's handles, by number (a destroyed one's slot is given out again)
-    uint64_t workspace_bytes = 0;
-    bool ws_ok = false, bins_ok = false;   // false after a failed (re)allocation: the step entry points refuse to run
-    bool rays_valid = false;            // the ray workspace holds a finished ray cast (rover_replay_raycast)
-    bool obs_valid = false;             // ... and euler / heading hold the state of a rover_get_observations (rover_calculate_metrics reads them)
-    // evaluation mode (rover_set_evaluation): per-env outcome code and the progress at which it latched
-    DevBuf<int64_t> d_eval_res;         // [E] 0 pending, 1 collided / out of area, 2 reached goal, 3 timed out
-    DevBuf<int64_t> d_eval_step;        // [E]
-    bool eval_on = false;
-    // in-situ ray-cast timing (rover_set_profiling)
-    bool profiling = false;
-    int32_t prof_every = 1;             // time every prof_every-th ray-cast launch (an event pair costs ~12 us of stream time)
-    int32_t prof_seen = 0;              // launches since profiling was switched on
-    std::vector<hipEvent_t> ev0, ev1;
-    int32_t prof_launches = 0;
-    double prof_ms = 0.0;
-    int32_t prof_pending = 0;
-};
 
 static const int kProfRing = 256;
 
@@ -194,7 +29,7 @@ static int prof_drain(rover_ctx* c) {
 
 static thread_local std::string g_create_err;
 
-static int fail(rover_ctx* c, int code, const char* fmt, ...) {
+int fail(rover_ctx* c, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -203,35 +38,6 @@ static int fail(rover_ctx* c, int code, const char* fmt, ...) {
     if (c) c->err = buf; else g_create_err = buf;
     return code;
 }
-
-#define HIP_TRY(c, expr)                                                                         \
-    do {                                                                                         \
-        hipError_t e__ = (expr);                                                                 \
-        if (e__ != hipSuccess) return fail((c), ROVER_E_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-
-// Makes the ctx's device current for the duration of one entry point and restores the caller's device afterwards
-// (the reference's task pins everything to one device, rover.py:90; a library must not change the caller's).
-struct DeviceGuard {
-    int prev = -1;
-    bool changed = false;
-    hipError_t err;
-    explicit DeviceGuard(int dev) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != dev) {
-            err = hipSetDevice(dev);
-            changed = err == hipSuccess;
-        }
-    }
-    ~DeviceGuard() { if (changed) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-
-#define USE_DEVICE(c)                                                                                          \
-    DeviceGuard device_guard__((c)->cfg.device);                                                               \
-    if (device_guard__.err != hipSuccess)                                                                      \
-        return fail((c), ROVER_E_HIP, "hipSetDevice(%d): %s", (c)->cfg.device, hipGetErrorString(device_guard__.err))
 
 static bool have_maps(const rover_ctx* c) { return c->maps[0].table.get() && c->maps[1].table.get(); }
 
@@ -640,8 +446,8 @@ int rover_create(const rover_cfg* cfg, rover_ctx** out) {
     if (e == hipSuccess) e = c->d_block_cnt.alloc((size_t)cfg->num_envs / 256 + 2);
     if (e == hipSuccess) e = c->d_goal_work.alloc(2 * (size_t)cfg->num_envs);
     if (e == hipSuccess) e = c->d_ids_work.alloc((size_t)cfg->num_envs);
-    if (e == hipSuccess) e = c->d_gae_partials.alloc(3 * (size_t)GAE_MAX_BLOCKS);
-    if (e == hipSuccess) e = c->d_ppo_partials.alloc((3 + (size_t)GAUSS_MAX_A) * PPO_MAX_BLOCKS);
+    if (e == hipSuccess) e = c->learn.gae_partials.alloc(3 * (size_t)GAE_MAX_BLOCKS);
+    if (e == hipSuccess) e = c->learn.ppo_partials.alloc((3 + (size_t)GAUSS_MAX_A) * PPO_MAX_BLOCKS);
     if (e != hipSuccess) { delete c; return fail(nullptr, ROVER_E_HIP, "rover_create: %s", hipGetErrorString(e)); }
     *out = c;
     return ROVER_OK;
@@ -1337,1378 +1143,6 @@ int rover_get_cull_info(rover_ctx* c, rover_cull_info* out) {
         out->lane_items += (v.w >> 8) & 0x3ffffu; out->lane_flushes += v.w >> 26;      // (zero in the words the culled kernel's waves write)
         out->max_pairs_per_run = v.x > out->max_pairs_per_run ? v.x : out->max_pairs_per_run;
     }
-    return ROVER_OK;
-}
-
-// IEEE binary16 <-> binary32 on the host (round to nearest even), for the reference-ranking coordinate tables
-static float half_bits_to_float(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, exp = (h >> 10) & 0x1fu, man = h & 0x3ffu;
-    uint32_t u;
-    if (exp == 0) {
-        if (man == 0) u = sign;
-        else { int e = -1; uint32_t m = man; do { ++e; m <<= 1; } while (!(m & 0x400u)); u = sign | ((uint32_t)(127 - 15 - e) << 23) | ((m & 0x3ffu) << 13); }
-    } else if (exp == 31) u = sign | 0x7f800000u | (man << 13);
-    else u = sign | ((exp + 112u) << 23) | (man << 13);
-    float f; memcpy(&f, &u, sizeof f); return f;
-}
-static uint16_t float_to_half_bits(float f) {
-    uint32_t u; memcpy(&u, &f, sizeof u);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    u &= 0x7fffffffu;
-    if (u >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (u > 0x7f800000u ? 0x200u : 0u));
-    if (u >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                        // rounds to infinity
-    if (u < 0x38800000u) {                                                         // subnormal half or zero
-        if (u < 0x33000000u) return (uint16_t)sign;
-        const int shift = 126 - (int)(u >> 23);                                    // 14 .. 24
-        const uint32_t m = (u & 0x7fffffu) | 0x800000u;
-        uint32_t r = m >> shift;
-        const uint32_t rem = m & ((1u << shift) - 1u), halfway = 1u << (shift - 1);
-        if (rem > halfway || (rem == halfway && (r & 1u))) ++r;
-        return (uint16_t)(sign | r);
-    }
-    uint32_t r = (u - 0x38000000u) >> 13;
-    const uint32_t rem = u & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (r & 1u))) ++r;
-    return (uint16_t)(sign | r);
-}
-
-static int build_knn_map_impl(rover_ctx* c, const float* vertices, int32_t V, const int32_t* triangles, int32_t T, int32_t X, int32_t Y,
-                              float res, int32_t K, int ref, const uint16_t* cell_x_f16, const uint16_t* cell_y_f16,
-                              int32_t* map_idx_out);
-
-int rover_build_knn_map(rover_ctx* c, const float* vertices, int32_t V, const int32_t* triangles, int32_t T, int32_t X, int32_t Y,
-                        float res, int32_t K, int32_t* map_idx_out) {
-    return build_knn_map_impl(c, vertices, V, triangles, T, X, Y, res, K, 0, nullptr, nullptr, map_idx_out);
-}
-
-int rover_build_knn_map_ref(rover_ctx* c, const float* vertices, int32_t V, const int32_t* triangles, int32_t T, int32_t X, int32_t Y,
-                            float res, int32_t K, const uint16_t* cell_x_f16, const uint16_t* cell_y_f16, int32_t* map_idx_out) {
-    return build_knn_map_impl(c, vertices, V, triangles, T, X, Y, res, K, 1, cell_x_f16, cell_y_f16, map_idx_out);
-}
-
-static int build_knn_map_impl(rover_ctx* c, const float* vertices, int32_t V, const int32_t* triangles, int32_t T, int32_t X, int32_t Y,
-                              float res, int32_t K, int ref, const uint16_t* cell_x_f16, const uint16_t* cell_y_f16,
-                              int32_t* map_idx_out) {
-    if (!c) return ROVER_E_INVALID;
-    if (!vertices || !triangles || !map_idx_out || V <= 0 || T <= 0 || X <= 0 || Y <= 0 || K <= 0 || !(res > 0.0f))
-        return fail(c, ROVER_E_INVALID, "build_knn_map: bad arguments");
-    if (T < K) return fail(c, ROVER_E_INVALID, "build_knn_map: the mesh has %d triangles, fewer than K=%d", T, K);
-    if (K > 4096) return fail(c, ROVER_E_INVALID, "build_knn_map: K=%d exceeds the builder's limit of 4096", K);
-    USE_DEVICE(c);
-    DevBuf<float> d_v, d_cx, d_cy, d_cell;
-    DevBuf<int32_t> d_t, d_over;
-    DevBuf<uint32_t> d_cur, d_items, d_bs, d_start;
-#define KNN_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess) return fail(c, ROVER_E_HIP, "build_knn_map: %s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-    KNN_TRY(d_v.alloc((size_t)V * 3));
-    KNN_TRY(d_t.alloc((size_t)T * 3));
-    KNN_TRY(d_cx.alloc(T));
-    KNN_TRY(d_cy.alloc(T));
-    KNN_TRY(d_items.alloc(T));
-    KNN_TRY(d_over.alloc(1));
-    KNN_TRY(d_bs.alloc(8192));
-    KNN_TRY(hipMemcpy(d_v.get(), vertices, d_v.bytes(), hipMemcpyDefault));
-    KNN_TRY(hipMemcpy(d_t.get(), triangles, d_t.bytes(), hipMemcpyDefault));
-    KNN_TRY(hipMemset(d_over.get(), 0, sizeof(int32_t)));
-    KNN_TRY(launch_knn_centroids(d_v.get(), d_t.get(), (uint32_t)T, (uint32_t)V, ref, d_cx.get(), d_cy.get(), nullptr));
-    if (ref) {
-        // cell coordinates as fp16 values: the caller's tables (what the reference's torch.arange(0, X res, res, dtype=float16)
-        // gave on the host that built the map), or fp16(float(i) * res) — ATen's CUDA arange kernel, the reference's own device
-        std::vector<float> cell((size_t)X + (size_t)Y);
-        std::vector<uint16_t> hx((size_t)X), hy((size_t)Y);
-        if (cell_x_f16) KNN_TRY(hipMemcpy(hx.data(), cell_x_f16, hx.size() * sizeof(uint16_t), hipMemcpyDefault));
-        if (cell_y_f16) KNN_TRY(hipMemcpy(hy.data(), cell_y_f16, hy.size() * sizeof(uint16_t), hipMemcpyDefault));
-        for (int32_t i = 0; i < X; ++i) cell[(size_t)i] = half_bits_to_float(cell_x_f16 ? hx[(size_t)i] : float_to_half_bits((float)i * res));
-        for (int32_t j = 0; j < Y; ++j) cell[(size_t)X + j] = half_bits_to_float(cell_y_f16 ? hy[(size_t)j] : float_to_half_bits((float)j * res));
-        KNN_TRY(d_cell.alloc(cell.size()));
-        KNN_TRY(hipMemcpy(d_cell.get(), cell.data(), d_cell.bytes(), hipMemcpyHostToDevice));
-    }
-    // bucket grid over the centroids' bounding box; bucket edge ~ the radius that holds K/4 centroids at mean density
-    std::vector<float> hx((size_t)T), hy((size_t)T);
-    KNN_TRY(hipMemcpy(hx.data(), d_cx.get(), d_cx.bytes(), hipMemcpyDeviceToHost));
-    KNN_TRY(hipMemcpy(hy.data(), d_cy.get(), d_cy.bytes(), hipMemcpyDeviceToHost));
-    // (NaN centroids are left out of the box, the first triangle's included: they all land in bucket 0 and rank last)
-    float x0 = 0.0f, x1 = 0.0f, y0 = 0.0f, y1 = 0.0f;
-    bool any_x = false, any_y = false;
-    for (int32_t t = 0; t < T; ++t) {
-        if (hx[t] == hx[t]) { x0 = (any_x && x0 < hx[t]) ? x0 : hx[t]; x1 = (any_x && x1 > hx[t]) ? x1 : hx[t]; any_x = true; }
-        if (hy[t] == hy[t]) { y0 = (any_y && y0 < hy[t]) ? y0 : hy[t]; y1 = (any_y && y1 > hy[t]) ? y1 : hy[t]; any_y = true; }
-    }
-    // the largest |coordinate - origin| of any centroid or cell point: knn_select_kernel's stop slack is absolute in it
-    const double cell_x1 = (double)((float)(X - 1) * res), cell_y1 = (double)((float)(Y - 1) * res);
-    const float span = (float)std::max({(double)x1 - x0, (double)y1 - y0, std::fabs((double)x0), std::fabs(cell_x1 - x0), std::fabs((double)y0),
-                                        std::fabs(cell_y1 - y0)});
-    const double area = ((double)x1 - x0 + 1e-6) * ((double)y1 - y0 + 1e-6);
-    // (an infinite centroid would make the bucket edge infinite or NaN, and the sizing below would never settle)
-    if (!std::isfinite(area)) return fail(c, ROVER_E_INVALID, "build_knn_map: the centroids' bounding box is not finite");
-    double gsz = std::sqrt(area * (double)K / (4.0 * (double)T));
-    if (gsz < (double)res) gsz = (double)res;
-    // A cell's search gathers whole rings of buckets into LDS (8192 candidates at most).  On a strongly non-uniform mesh (a
-    // decimated terrain: millimetre triangles on the rocks, metre-sized ones between them) a ring sized for the MEAN density can
-    // hold more than that next to a dense patch: the bucket edge is halved and the search repeated (same result: the ranking
-    // does not depend on the bucket size).
-    hipError_t e2 = hipSuccess;
-    int32_t over = 0;
-    for (int attempt = 0; attempt < 6; ++attempt, gsz *= 0.5) {
-        uint32_t nbx = (uint32_t)(((double)x1 - x0) / gsz) + 1, nby = (uint32_t)(((double)y1 - y0) / gsz) + 1;
-        while ((uint64_t)nbx * nby > (1u << 22)) { gsz *= 2.0; nbx = (uint32_t)(((double)x1 - x0) / gsz) + 1; nby = (uint32_t)(((double)y1 - y0) / gsz) + 1; attempt = 99; }
-        const float g = (float)gsz, inv_g = 1.0f / g;
-        const uint32_t nb = nbx * nby;
-        d_start.reset();
-        KNN_TRY(d_cur.alloc((size_t)nb + 1));
-        KNN_TRY(hipMemset(d_cur.get(), 0, d_cur.bytes()));
-        KNN_TRY(hipMemset(d_over.get(), 0, sizeof(int32_t)));
-        KNN_TRY(launch_knn_bucket(d_cx.get(), d_cy.get(), (uint32_t)T, x0, y0, inv_g, nbx, nby, d_cur.get(), d_items.get(), 1, nullptr));
-        KNN_TRY(launch_scan_exclusive(d_cur.get(), nb + 1, d_bs.get(), nullptr));
-        e2 = d_start.alloc((size_t)nb + 1);
-        if (e2 == hipSuccess) e2 = hipMemcpy(d_start.get(), d_cur.get(), d_cur.bytes(), hipMemcpyDeviceToDevice);
-        if (e2 == hipSuccess) e2 = launch_knn_bucket(d_cx.get(), d_cy.get(), (uint32_t)T, x0, y0, inv_g, nbx, nby, d_cur.get(), d_items.get(), 0, nullptr);
-        if (e2 == hipSuccess) e2 = launch_knn_select(d_cx.get(), d_cy.get(), d_start.get(), d_items.get(), x0, y0, g, span, nbx, nby, (uint32_t)X, (uint32_t)Y,
-                                                     res, (uint32_t)K, d_cell.get(), d_cell.get() ? d_cell.get() + X : nullptr, map_idx_out, d_over.get(), nullptr);
-        if (e2 == hipSuccess) e2 = hipDeviceSynchronize();
-        over = 0;
-        if (e2 == hipSuccess) e2 = hipMemcpy(&over, d_over.get(), sizeof over, hipMemcpyDeviceToHost);
-        if (e2 != hipSuccess || !over) break;
-    }
-#undef KNN_TRY
-    if (e2 != hipSuccess) return fail(c, ROVER_E_HIP, "build_knn_map: %s", hipGetErrorString(e2));
-    if (over) return fail(c, ROVER_E_INVALID, "build_knn_map: a search ring held more than 8192 candidate triangles (mesh too dense for K=%d)", K);
-    return ROVER_OK;
-}
-
-// Host only: the sizes that separate the rasteriser's routes
-int rover_heightfield_limits(int32_t out[4]) {
-    if (!out) return fail(nullptr, ROVER_E_INVALID, "heightfield_limits: null argument");
-    out[0] = RASTER_SMALL_NODES; out[1] = RASTER_TILE_I; out[2] = RASTER_TILE_J; out[3] = RASTER_GROUP;
-    return ROVER_OK;
-}
-
-// The arguments are validated before the ctx is looked at, as for rover_motion_step
-int rover_build_heightfield(rover_ctx* c, const float* vertices, int32_t V, const int32_t* triangles, int32_t T, int32_t N0, int32_t N1,
-                            float horizontal_scale, float shift_x, float shift_y, float fill, float* hm_out, int64_t stats[2]) {
-    if (N0 < 1 || N1 < 1 || N0 > RASTER_MAX_NODES || N1 > RASTER_MAX_NODES)
-        return fail(c, ROVER_E_INVALID, "build_heightfield: N0 = %d or N1 = %d is outside 1 .. %d", N0, N1, RASTER_MAX_NODES);
-    if (!std::isfinite(horizontal_scale) || !(horizontal_scale > 0.0f))
-        return fail(c, ROVER_E_INVALID, "build_heightfield: horizontal_scale = %g is not finite or not > 0", (double)horizontal_scale);
-    if (!std::isfinite(shift_x) || !std::isfinite(shift_y))
-        return fail(c, ROVER_E_INVALID, "build_heightfield: shift = (%g, %g) is not finite", (double)shift_x, (double)shift_y);
-    if (V < 0 || T < 0) return fail(c, ROVER_E_INVALID, "build_heightfield: V = %d or T = %d is negative", V, T);
-    if ((V > 0 && !vertices) || (T > 0 && !triangles) || !hm_out)
-        return fail(c, ROVER_E_INVALID, "build_heightfield: vertices, triangles and hm_out must be given");
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "build_heightfield: null ctx");
-    USE_DEVICE(c);
-#define HF_TRY(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e__ = (expr);                                                                              \
-        if (e__ != hipSuccess) return fail(c, ROVER_E_HIP, "build_heightfield: %s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-    DevBuf<float> d_v;
-    DevBuf<int32_t> d_t;
-    DevBuf<uint4> d_snap;
-    DevBuf<uint32_t> d_large, d_tiles;
-    DevBuf<unsigned long long> d_counts;            // {uncovered, skipped, length of the list}
-    DevBuf<uint64_t> d_start;
-    const size_t nv = V > 0 ? (size_t)V : 1, nt = T > 0 ? (size_t)T : 1;
-    const uint64_t nodes = (uint64_t)N0 * (uint64_t)N1;
-    HF_TRY(d_v.alloc(nv * 3));
-    HF_TRY(d_t.alloc(nt * 3));
-    HF_TRY(d_snap.alloc(nv));
-    HF_TRY(d_large.alloc(nt));
-    HF_TRY(d_tiles.alloc(nt));
-    HF_TRY(d_counts.alloc(3));
-    if (V > 0) HF_TRY(hipMemcpy(d_v.get(), vertices, (size_t)V * 3 * sizeof(float), hipMemcpyDefault));
-    if (T > 0) HF_TRY(hipMemcpy(d_t.get(), triangles, (size_t)T * 3 * sizeof(int32_t), hipMemcpyDefault));
-    HF_TRY(hipMemset(d_counts.get(), 0, d_counts.bytes()));
-    HF_TRY(hipMemset(hm_out, 0, nodes * sizeof(float)));                                  // key 0: never covered
-    RasterArgs a{};
-    a.snap = d_snap.get(); a.tris = d_t.get(); a.V = V; a.T = T; a.N0 = N0; a.N1 = N1;
-    a.keys = reinterpret_cast<uint32_t*>(hm_out);
-    a.n_large = reinterpret_cast<uint32_t*>(d_counts.get() + 2);
-    a.large_tri = d_large.get(); a.large_tiles = d_tiles.get(); a.stats = d_counts.get();
-    HF_TRY(launch_raster_snap(d_v.get(), (uint32_t)V, horizontal_scale, shift_x, shift_y, d_snap.get(), nullptr));
-    HF_TRY(launch_raster_small(a, nullptr));
-    unsigned long long counts[3] = {0, 0, 0};
-    HF_TRY(hipMemcpy(counts, d_counts.get(), sizeof counts, hipMemcpyDeviceToHost));      // (synchronises)
-    const uint32_t n_large = (uint32_t)(counts[2] & 0xffffffffull);
-    if (n_large > (uint32_t)T) return fail(c, ROVER_E_HIP, "build_heightfield: the list holds %u triangles of %d", n_large, T);
-    if (n_large) {
-        std::vector<uint32_t> tiles(n_large);
-        std::vector<uint64_t> start((size_t)n_large + 1);
-        HF_TRY(hipMemcpy(tiles.data(), d_tiles.get(), (size_t)n_large * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        start[0] = 0;
-        for (uint32_t i = 0; i < n_large; ++i) start[(size_t)i + 1] = start[i] + tiles[i];
-        HF_TRY(d_start.alloc(start.size()));
-        HF_TRY(hipMemcpy(d_start.get(), start.data(), d_start.bytes(), hipMemcpyHostToDevice));
-        HF_TRY(launch_raster_large(a, d_start.get(), n_large, start[n_large], nullptr));
-    }
-    HF_TRY(launch_raster_decode(a.keys, nodes, fill, d_counts.get(), nullptr));
-    HF_TRY(hipDeviceSynchronize());
-    HF_TRY(hipMemcpy(counts, d_counts.get(), sizeof counts, hipMemcpyDeviceToHost));
-#undef HF_TRY
-    if (stats) { stats[0] = (int64_t)counts[0]; stats[1] = (int64_t)counts[1]; }
-    return ROVER_OK;
-}
-
-// ---- Mars terrain generator ----
-static_assert(MARS_TILE == ROVER_MARS_TILE, "the kernel's tile is the ABI's");
-
-// shared by rover_mars_heightfield and rover_mars_tiles: true when the descriptor is acceptable, else *why says what is wrong.  This is
-// what keeps the kernel inside its buffers: a window or a kept stamp that fails here never reaches the device.
-static bool mars_desc_ok(const rover_mars_desc* d, std::string* why) {
-    char buf[256];
-    buf[0] = 0;
-#define MARS_REFUSE(...) do { snprintf(buf, sizeof buf, __VA_ARGS__); *why = buf; return false; } while (0)
-    if (!d) MARS_REFUSE("desc is NULL");
-    if (d->rows < 1 || d->cols < 1 || d->rows > ROVER_MARS_MAX_SIDE || d->cols > ROVER_MARS_MAX_SIDE)
-        MARS_REFUSE("rows = %d or cols = %d is outside 1 .. %d", d->rows, d->cols, ROVER_MARS_MAX_SIDE);
-    if (d->n_hills < 0) MARS_REFUSE("n_hills = %d is negative", d->n_hills);
-    if (d->n_classes < 0 || d->n_classes > ROVER_MARS_MAX_CLASSES) MARS_REFUSE("n_classes = %d is outside 0 .. %d", d->n_classes, ROVER_MARS_MAX_CLASSES);
-    if (d->n_stamps < 0) MARS_REFUSE("n_stamps = %d is negative", d->n_stamps);
-    if (d->g_len < 1 || !d->g) MARS_REFUSE("g is NULL or g_len = %d is below 1", d->g_len);
-    if (d->n_hills > 0 && (!d->hill_window || !d->hill_amp)) MARS_REFUSE("hill_window or hill_amp is NULL with n_hills = %d", d->n_hills);
-    if (d->n_classes > 0 && (!d->class_side || !d->class_tables)) MARS_REFUSE("class_side or class_tables is NULL with n_classes = %d", d->n_classes);
-    if (d->n_stamps > 0 && (!d->stamp_row || !d->stamp_col || !d->stamp_class || !d->stamp_factor || !d->stamp_kept))
-        MARS_REFUSE("a stamp array is NULL with n_stamps = %d", d->n_stamps);
-    for (int32_t k = 0; k < d->n_classes; ++k)
-        if (d->class_side[k] < 1 || d->class_side[k] > ROVER_MARS_MAX_TABLE)
-            MARS_REFUSE("class_side[%d] = %d is outside 1 .. %d", k, d->class_side[k], ROVER_MARS_MAX_TABLE);
-    for (int32_t i = 0; i < d->n_hills; ++i) {
-        const int32_t* w = d->hill_window + 6 * (size_t)i;
-        const int64_t r0 = w[0], r1 = w[1], c0 = w[2], c1 = w[3], a0 = w[4], b0 = w[5];
-        if (r0 < 0 || r1 < r0 || r1 > d->rows || c0 < 0 || c1 < c0 || c1 > d->cols)
-            MARS_REFUSE("hill_window[%d] = rows %d:%d, columns %d:%d is not inside the %d x %d field", i, w[0], w[1], w[2], w[3], d->rows, d->cols);
-        if (a0 < 0 || b0 < 0 || a0 + (r1 - r0) > d->g_len || b0 + (c1 - c0) > d->g_len)
-            MARS_REFUSE("hill_window[%d] reads g from %d and %d: outside its %d entries", i, w[4], w[5], d->g_len);
-        if (!std::isfinite(d->hill_amp[i])) MARS_REFUSE("hill_amp[%d] is not finite", i);
-    }
-    for (int32_t s = 0; s < d->n_stamps; ++s) {
-        if (!d->stamp_kept[s]) continue;
-        const int32_t k = d->stamp_class[s];
-        if (k < 0 || k >= d->n_classes) MARS_REFUSE("stamp_class[%d] = %d is outside 0 .. %d", s, k, d->n_classes - 1);
-        const int64_t side = d->class_side[k], r = d->stamp_row[s], c = d->stamp_col[s];
-        if (r < 0 || c < 0 || r + side > d->rows || c + side > d->cols)
-            MARS_REFUSE("stamp %d (stamp_row = %d, stamp_col = %d, side %d) is not inside the %d x %d field", s, d->stamp_row[s], d->stamp_col[s],
-                        (int)side, d->rows, d->cols);
-        if (!std::isfinite(d->stamp_factor[s])) MARS_REFUSE("stamp_factor[%d] is not finite", s);
-    }
-#undef MARS_REFUSE
-    return true;
-}
-
-static inline uint32_t mars_tiles_of(int32_t n) { return ((uint32_t)n + MARS_TILE - 1) / MARS_TILE; }
-
-// the total length of the tile lists of a descriptor that passed mars_desc_ok
-static int64_t mars_count_items(const rover_mars_desc& d) {
-    int64_t total = 0;
-    for (int32_t s = 0; s < d.n_stamps; ++s) {
-        if (!d.stamp_kept[s]) continue;
-        const int32_t side = d.class_side[d.stamp_class[s]], r = d.stamp_row[s], c = d.stamp_col[s];
-        total += (int64_t)((r + side - 1) / MARS_TILE - r / MARS_TILE + 1) * ((c + side - 1) / MARS_TILE - c / MARS_TILE + 1);
-    }
-    return total;
-}
-
-// start [tiles + 1], items [mars_count_items]: the stamps are visited in index order, so every tile's list is ascending
-static void mars_fill_lists(const rover_mars_desc& d, int32_t* start, int32_t* items) {
-    const uint32_t tiles_c = mars_tiles_of(d.cols);
-    const size_t tiles = (size_t)mars_tiles_of(d.rows) * tiles_c;
-    std::fill(start, start + tiles + 1, 0);
-    for (int pass = 0; pass < 2; ++pass) {
-        std::vector<int32_t> cursor;
-        if (pass == 1) {                                  // counts -> exclusive sum
-            int32_t sum = 0;
-            for (size_t t = 0; t <= tiles; ++t) { const int32_t n = start[t]; start[t] = sum; sum += n; }
-            cursor.assign(start, start + tiles);
-        }
-        for (int32_t s = 0; s < d.n_stamps; ++s) {
-            if (!d.stamp_kept[s]) continue;
-            const int32_t side = d.class_side[d.stamp_class[s]], r = d.stamp_row[s], c = d.stamp_col[s];
-            for (int32_t ti = r / MARS_TILE; ti <= (r + side - 1) / MARS_TILE; ++ti)
-                for (int32_t tj = c / MARS_TILE; tj <= (c + side - 1) / MARS_TILE; ++tj) {
-                    const size_t t = (size_t)ti * tiles_c + (size_t)tj;
-                    if (pass == 0) ++start[t]; else items[cursor[t]++] = s;
-                }
-        }
-    }
-}
-
-int rover_mars_tiles(const rover_mars_desc* d, int32_t* tile_start, int32_t* tile_items, int64_t capacity, int64_t* n_items) {
-    std::string why;
-    if (!mars_desc_ok(d, &why)) return fail(nullptr, ROVER_E_INVALID, "mars_tiles: %s", why.c_str());
-    if (!n_items) return fail(nullptr, ROVER_E_INVALID, "mars_tiles: n_items is NULL");
-    const int64_t n = mars_count_items(*d);
-    if (n > INT32_MAX) return fail(nullptr, ROVER_E_INVALID, "mars_tiles: the tile lists hold %lld items, more than 2^31 - 1", (long long)n);
-    const bool want = tile_start || tile_items;
-    if (want && (!tile_start || (!tile_items && n > 0))) return fail(nullptr, ROVER_E_INVALID, "mars_tiles: tile_start and tile_items go together");
-    if (capacity < 0 || (want && capacity < n))
-        return fail(nullptr, ROVER_E_INVALID, "mars_tiles: capacity %lld < %lld items", (long long)capacity, (long long)n);
-    if (want) mars_fill_lists(*d, tile_start, tile_items);
-    *n_items = n;
-    return ROVER_OK;
-}
-
-// The arguments are validated before the ctx is looked at, as for rover_build_heightfield
-int rover_mars_heightfield(rover_ctx* c, const rover_mars_desc* d, double* hf, uint8_t* rock_mask, void* stream) {
-    std::string why;
-    if (!mars_desc_ok(d, &why)) return fail(c, ROVER_E_INVALID, "mars_heightfield: %s", why.c_str());
-    if (!hf) return fail(c, ROVER_E_INVALID, "mars_heightfield: hf is NULL");
-    const int64_t n_items = mars_count_items(*d);
-    if (n_items > INT32_MAX) return fail(c, ROVER_E_INVALID, "mars_heightfield: the tile lists hold %lld items, more than 2^31 - 1", (long long)n_items);
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "mars_heightfield: null ctx");
-    USE_DEVICE(c);
-#define MARS_TRY(expr)                                                                                        \
-    do {                                                                                                      \
-        hipError_t e__ = (expr);                                                                              \
-        if (e__ != hipSuccess) return fail(c, ROVER_E_HIP, "mars_heightfield: %s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-    // host tables in the kernel's records
-    const uint32_t tiles_r = mars_tiles_of(d->rows), tiles_c = mars_tiles_of(d->cols);
-    const size_t tiles = (size_t)tiles_r * tiles_c;
-    std::vector<MarsHill> hills((size_t)d->n_hills);
-    for (int32_t i = 0; i < d->n_hills; ++i) {
-        const int32_t* w = d->hill_window + 6 * (size_t)i;
-        hills[i] = MarsHill{w[0], w[1], w[2], w[3], w[4], w[5], d->hill_amp[i]};
-    }
-    uint32_t table_at[ROVER_MARS_MAX_CLASSES + 1] = {0};
-    for (int32_t k = 0; k < d->n_classes; ++k) table_at[k + 1] = table_at[k] + (uint32_t)(d->class_side[k] * d->class_side[k]);
-    const size_t table_doubles = table_at[d->n_classes];
-    std::vector<MarsStamp> stamps((size_t)d->n_stamps, MarsStamp{0, 0, 0u, 0u, 0.0, 0.0});
-    for (int32_t s = 0; s < d->n_stamps; ++s)
-        if (d->stamp_kept[s]) {
-            const int32_t k = d->stamp_class[s];
-            stamps[s] = MarsStamp{d->stamp_row[s], d->stamp_col[s], (uint32_t)d->class_side[k], table_at[k], d->stamp_factor[s], 0.0};
-        }
-    std::vector<int32_t> start(tiles + 1), items((size_t)n_items);
-    mars_fill_lists(*d, start.data(), items.data());
-    DevBuf<MarsHill> d_hills;
-    DevBuf<MarsStamp> d_stamps;
-    DevBuf<double> d_g, d_tables;
-    DevBuf<int32_t> d_start, d_items;
-    MARS_TRY(d_hills.alloc(std::max<size_t>(hills.size(), 1)));
-    MARS_TRY(d_stamps.alloc(std::max<size_t>(stamps.size(), 1)));
-    MARS_TRY(d_g.alloc((size_t)d->g_len));
-    MARS_TRY(d_tables.alloc(std::max<size_t>(table_doubles, 1)));
-    MARS_TRY(d_start.alloc(start.size()));
-    MARS_TRY(d_items.alloc(std::max<size_t>(items.size(), 1)));
-    if (!hills.empty()) MARS_TRY(hipMemcpy(d_hills.get(), hills.data(), hills.size() * sizeof(MarsHill), hipMemcpyHostToDevice));
-    if (!stamps.empty()) MARS_TRY(hipMemcpy(d_stamps.get(), stamps.data(), stamps.size() * sizeof(MarsStamp), hipMemcpyHostToDevice));
-    MARS_TRY(hipMemcpy(d_g.get(), d->g, (size_t)d->g_len * sizeof(double), hipMemcpyHostToDevice));
-    if (table_doubles) MARS_TRY(hipMemcpy(d_tables.get(), d->class_tables, table_doubles * sizeof(double), hipMemcpyHostToDevice));
-    MARS_TRY(hipMemcpy(d_start.get(), start.data(), start.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (!items.empty()) MARS_TRY(hipMemcpy(d_items.get(), items.data(), items.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    MarsArgs a{};
-    a.hf = hf; a.mask = rock_mask; a.rows = d->rows; a.cols = d->cols; a.tiles_r = tiles_r; a.tiles_c = tiles_c;
-    a.hills = d_hills.get(); a.n_hills = d->n_hills; a.g = d_g.get(); a.tables = d_tables.get(); a.stamps = d_stamps.get();
-    a.tile_start = d_start.get(); a.tile_items = d_items.get();
-    MARS_TRY(launch_mars_heightfield(a, (hipStream_t)stream));
-    MARS_TRY(hipStreamSynchronize((hipStream_t)stream));          // the tables above are freed on return
-#undef MARS_TRY
-    return ROVER_OK;
-}
-
-// the f32 and the bf16 layer differ in the launch alone (launch_linear_act: rover_mlp.hip; launch_linear_bf16: rover_bf16_tile.hip)
-static int linear_forward_run(rover_ctx* c, const char* what, hipError_t (*launch)(const LinearArgs&, hipStream_t), const float* x, int64_t x_stride,
-                              int32_t M, int32_t K, const float* weight, const float* bias, int32_t N, int32_t activation, float* y, int64_t y_stride,
-                              void* stream) {
-    if (!c) return ROVER_E_INVALID;
-    // K = 0: a layer over an empty obs slice (model.py builds Encoder(0, ...) when a heightmap part is absent) = act(bias)
-    if ((K > 0 && (!x || !weight)) || !y || M < 0 || K < 0 || N <= 0 || N > 256 || x_stride < K || y_stride < N || activation < 0 || activation > 4)
-        return fail(c, ROVER_E_INVALID, "%s: bad arguments (M=%d K=%d N=%d act=%d)", what, M, K, N, activation);
-    if (M == 0) return ROVER_OK;
-    USE_DEVICE(c);
-    LinearArgs a{x, x_stride, weight, bias, y, y_stride, M, K, N, activation};
-    HIP_TRY(c, launch(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-int rover_linear_forward(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K, const float* weight, const float* bias,
-                         int32_t N, int32_t activation, float* y, int64_t y_stride, void* stream) {
-    return linear_forward_run(c, "linear_forward", launch_linear_act, x, x_stride, M, K, weight, bias, N, activation, y, y_stride, stream);
-}
-
-int rover_linear_forward_bf16(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K, const float* weight, const float* bias,
-                              int32_t N, int32_t activation, float* y, int64_t y_stride, void* stream) {
-    return linear_forward_run(c, "linear_forward_bf16", launch_linear_bf16, x, x_stride, M, K, weight, bias, N, activation, y, y_stride, stream);
-}
-
-// One chain, validated in one place.  The shape half: M, K0, the depth, every width and activation — all chain_route() reads, so all a route query looks at (no pointer of
-// the descriptor but widths / activations).  0 = fine, -1 = M / K0 / the depth / a null array, i + 1 = layer i's width or activation.
-// min_k0: 1 for the f32 chains; 0 for the bf16 ones, which also run a chain over an EMPTY obs slice (model.py builds Encoder(0, ...) when
-// a heightmap part is absent: its first layer is act(bias), as rover_linear_forward computes it for K = 0) — x is then not read.
-static int chain_shape_of(const rover_chain_desc& d, int32_t M, ChainArgs* a, int32_t min_k0 = 1) {
-    if (!d.widths || !d.activations || M < 0 || d.K0 < min_k0 || (d.n_layers != 2 && d.n_layers != 4)) return -1;
-    *a = ChainArgs{};
-    a->M = M; a->K0 = d.K0; a->n_layers = d.n_layers;
-    for (int i = 0; i < d.n_layers; ++i) {
-        if (d.widths[i] <= 0 || d.widths[i] > 256 || d.activations[i] < 0 || d.activations[i] > 4) return i + 1;
-        a->n[i] = d.widths[i]; a->act[i] = d.activations[i];
-    }
-    return 0;
-}
-// The whole of it, for a call that launches: the shapes, then the pointers and the row strides (0 = ok, else the error is recorded
-// under `what`, the entry point that was called)
-static int chain_args_of(rover_ctx* c, const rover_chain_desc& d, int32_t M, const char* what, ChainArgs* out, int32_t min_k0 = 1) {
-    ChainArgs a;
-    const int bad = chain_shape_of(d, M, &a, min_k0);
-    if (bad < 0 || (!d.x && d.K0 > 0) || !d.y || !d.weights || !d.biases || d.x_stride < d.K0)
-        return fail(c, ROVER_E_INVALID, "%s: bad arguments (M=%d K0=%d layers=%d)", what, M, d.K0, d.n_layers);
-    for (int i = 0; i < d.n_layers; ++i) {
-        if ((!d.weights[i] && (i > 0 || d.K0 > 0)) || bad == i + 1)
-            return fail(c, ROVER_E_INVALID, "%s: layer %d: width %d activation %d", what, i, d.widths[i], d.activations[i]);
-        a.w[i] = d.weights[i]; a.b[i] = d.biases[i];
-    }
-    if (d.y_stride < a.n[d.n_layers - 1]) return fail(c, ROVER_E_INVALID, "%s: y_stride %lld < width %d", what, (long long)d.y_stride, a.n[d.n_layers - 1]);
-    a.x = d.x; a.x_stride = d.x_stride; a.y = d.y; a.y_stride = d.y_stride;
-    *out = a;
-    return ROVER_OK;
-}
-
-// the split-k scratch buffer, grown when a larger batch comes (not inside a stream capture — size the first call before capturing)
-static int mlp_scratch_reserve(rover_ctx* c, size_t need, hipStream_t s) {
-    if (need * sizeof(float) <= c->d_mlp_scratch.bytes()) return ROVER_OK;
-    HIP_TRY(c, hipStreamSynchronize(s));          // kernels still reading the old buffer
-    HIP_TRY(c, c->d_mlp_scratch.alloc(need));
-    return ROVER_OK;
-}
-
-static int chain_refused(rover_ctx* c, const char* what) {
-    return fail(c, ROVER_E_INVALID, "%s: net outside the built tile shapes (<= 96 -> <= 64, or <= 256 -> <= 160 -> <= 128 -> <= 16 with hidden activations none / LeakyReLU / ReLU)", what);
-}
-
-// launches what chain_route() chose (never ChainKernel::None)
-static int chain_run(rover_ctx* c, const ChainArgs& a, const ChainRoute& r, hipStream_t s) {
-    if (r.kernel == ChainKernel::SplitK)
-        if (int e = mlp_scratch_reserve(c, chain_splitk_scratch_floats(a.M, a.K0, a.n[0]), s)) return e;
-    HIP_TRY(c, launch_chain(a, r, c->d_mlp_scratch.get(), s));
-    return ROVER_OK;
-}
-
-// the f32 and the bf16 entry points differ in the route function alone (chain_route / chain_route_bf16: rover_mlp.hip)
-typedef ChainRoute (*ChainRouteFn)(const ChainArgs&);
-static int32_t chain_min_k0(ChainRouteFn route) { return route == chain_route_bf16 ? 0 : 1; }
-
-static int chain_forward(rover_ctx* c, const rover_chain_desc& d, int32_t M, const char* what, ChainRouteFn route, void* stream) {
-    if (!c) return ROVER_E_INVALID;
-    ChainArgs a;
-    if (int r = chain_args_of(c, d, M, what, &a, chain_min_k0(route))) return r;
-    if (M == 0) return ROVER_OK;
-    const ChainRoute r = route(a);
-    if (r.kernel == ChainKernel::None) return chain_refused(c, what);
-    USE_DEVICE(c);
-    return chain_run(c, a, r, (hipStream_t)stream);
-}
-
-int rover_mlp_chain_forward(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers,
-                            const float* const* weights, const float* const* biases, const int32_t* widths, const int32_t* activations,
-                            float* y, int64_t y_stride, void* stream) {
-    const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
-    return chain_forward(c, d, M, "mlp_chain_forward", chain_route, stream);
-}
-
-int rover_mlp_chain_forward_bf16(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers,
-                                 const float* const* weights, const float* const* biases, const int32_t* widths, const int32_t* activations,
-                                 float* y, int64_t y_stride, void* stream) {
-    const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
-    return chain_forward(c, d, M, "mlp_chain_forward_bf16", chain_route_bf16, stream);
-}
-
-int rover_bf16_round(const float* in, int64_t n, float* out) {
-    if (n < 0 || (n > 0 && (!in || !out))) return fail(nullptr, ROVER_E_INVALID, "bf16_round: bad arguments (n=%lld)", (long long)n);
-    for (int64_t i = 0; i < n; ++i) out[i] = (float)bf16_rne(in[i]);
-    return ROVER_OK;
-}
-
-int rover_mlp_chain_pair_forward(rover_ctx* c, int32_t M, const rover_chain_desc* da, const rover_chain_desc* db, const float* copy_src,
-                                 int64_t copy_src_stride, float* copy_dst, int64_t copy_dst_stride, int32_t copy_cols, void* stream) {
-    if (!c) return ROVER_E_INVALID;
-    if (!da || !db || copy_cols < 0 || (copy_cols > 0 && (!copy_src || !copy_dst || copy_src_stride < copy_cols || copy_dst_stride < copy_cols)))
-        return fail(c, ROVER_E_INVALID, "mlp_chain_pair_forward: bad arguments (copy_cols=%d)", copy_cols);
-    ChainArgs a, b;
-    if (int r = chain_args_of(c, *da, M, "mlp_chain_pair_forward", &a)) return r;
-    if (int r = chain_args_of(c, *db, M, "mlp_chain_pair_forward", &b)) return r;
-    if (M == 0) return ROVER_OK;
-    const ChainRoute ra = chain_route(a), rb = chain_route(b);
-    if (ra.kernel == ChainKernel::None || rb.kernel == ChainKernel::None) return chain_refused(c, "mlp_chain_pair_forward");
-    USE_DEVICE(c);
-    hipStream_t s = (hipStream_t)stream;
-    if (chain_pair_side_by_side(ra, rb)) {
-        const size_t fa = chain_splitk_scratch_floats(a.M, a.K0, a.n[0]), fb = chain_splitk_scratch_floats(b.M, b.K0, b.n[0]);
-        if (int r = mlp_scratch_reserve(c, fa + fb, s)) return r;
-        HIP_TRY(c, launch_chain_splitk_pair(a, b, ra, c->d_mlp_scratch.get(), c->d_mlp_scratch.get() + fa, copy_src, copy_src_stride, copy_dst,
-                                            copy_dst_stride, copy_cols, s));
-        return ROVER_OK;
-    }
-    if (copy_cols > 0)
-        HIP_TRY(c, hipMemcpy2DAsync(copy_dst, (size_t)copy_dst_stride * sizeof(float), copy_src, (size_t)copy_src_stride * sizeof(float),
-                                    (size_t)copy_cols * sizeof(float), (size_t)M, hipMemcpyDeviceToDevice, s));
-    if (int r = chain_run(c, a, ra, s)) return r;
-    return chain_run(c, b, rb, s);
-}
-
-// ---- route queries: what the forward calls above would launch, from the shapes alone (host only) ----
-const char* rover_linear_route(int32_t M, int32_t K, int32_t N) {
-    const LinearRoute r = linear_route(M, N);
-    if (K < 0 || !r.nw) return nullptr;
-    return M == 0 ? "none" : linear_route_name(r);
-}
-
-const char* rover_linear_route_bf16(int32_t M, int32_t K, int32_t N) {
-    const char* name = linear_route_bf16_name(M, N);
-    if (K < 0 || !name) return nullptr;
-    return M == 0 ? "none" : name;
-}
-
-static const char* chain_route_query(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations, ChainRouteFn route) {
-    const rover_chain_desc d{nullptr, 0, K0, n_layers, nullptr, nullptr, widths, activations, nullptr, 0};      // a route query: shapes alone
-    ChainArgs a;
-    if (chain_shape_of(d, M, &a, chain_min_k0(route))) return nullptr;
-    return M == 0 ? "none" : chain_route_name(route(a));
-}
-const char* rover_mlp_chain_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations) {
-    return chain_route_query(M, K0, n_layers, widths, activations, chain_route);
-}
-const char* rover_mlp_chain_route_bf16(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations) {
-    return chain_route_query(M, K0, n_layers, widths, activations, chain_route_bf16);
-}
-
-const char* rover_mlp_chain_pair_route(int32_t M, const rover_chain_desc* da, const rover_chain_desc* db) {
-    ChainArgs a, b;
-    if (!da || !db || chain_shape_of(*da, M, &a) || chain_shape_of(*db, M, &b)) return nullptr;
-    if (M == 0) return "none";
-    const ChainRoute ra = chain_route(a), rb = chain_route(b);
-    if (ra.kernel == ChainKernel::None || rb.kernel == ChainKernel::None) return nullptr;
-    static thread_local char name[96];
-    char na[48];                                                     // (chain_route_name() may hand out one buffer twice)
-    snprintf(na, sizeof na, "%s", chain_route_name(ra));
-    if (chain_pair_side_by_side(ra, rb)) snprintf(name, sizeof name, "pair(%s)", na);
-    else snprintf(name, sizeof name, "seq(%s;%s)", na, chain_route_name(rb));
-    return name;
-}
-
-// ---- the Gaussian head ----
-// the validated descriptor (0 = ok, else the error is recorded with c, or for rover_last_error(NULL) when c is null); no pointer is read
-static int gauss_head_of(rover_ctx* c, const rover_gauss_head* g, int32_t M, bool given_mean, GaussHead* out) {
-    if (!g) return fail(c, ROVER_E_INVALID, "gauss_head: null descriptor");
-    if (g->A < 1 || g->A > GAUSS_MAX_A) return fail(c, ROVER_E_INVALID, "gauss_head: A = %d outside 1 .. %d", g->A, GAUSS_MAX_A);
-    if (g->clip_log_std && !(g->min_log_std <= g->max_log_std))
-        return fail(c, ROVER_E_INVALID, "gauss_head: min_log_std %g > max_log_std %g", (double)g->min_log_std, (double)g->max_log_std);
-    if (g->clip_actions && !(g->low <= g->high)) return fail(c, ROVER_E_INVALID, "gauss_head: low %g > high %g", (double)g->low, (double)g->high);
-    if (g->reduction < ROVER_REDUCE_SUM || g->reduction > ROVER_REDUCE_NONE) return fail(c, ROVER_E_INVALID, "gauss_head: unknown reduction %d", g->reduction);
-    if (!g->log_std || !g->actions || !g->log_prob) return fail(c, ROVER_E_INVALID, "gauss_head: log_std, actions and log_prob must be given");
-    const int lp_cols = g->reduction == ROVER_REDUCE_NONE ? g->A : 1;
-    if (g->actions_stride < g->A || g->log_prob_stride < lp_cols || (g->taken_actions && g->taken_stride < g->A))
-        return fail(c, ROVER_E_INVALID, "gauss_head: a row stride is shorter than its row (A = %d)", g->A);
-    if (given_mean && (!g->mean || g->mean_stride < g->A)) return fail(c, ROVER_E_INVALID, "gauss_head: mean [M, A] must be given");
-    if (M < 0 || g->row_offset < 0 || g->row_offset + (int64_t)M > (int64_t)1 << 32)
-        return fail(c, ROVER_E_INVALID, "gauss_head: rows %lld .. + %d outside [0, 2^32)", (long long)g->row_offset, M);
-    GaussHead h{};
-    h.log_std = g->log_std; h.A = g->A; h.clip_log_std = g->clip_log_std != 0; h.clip_actions = g->clip_actions != 0;
-    h.reduction = g->reduction; h.deterministic = g->deterministic != 0;
-    h.min_log_std = g->min_log_std; h.max_log_std = g->max_log_std; h.low = g->low; h.high = g->high;
-    h.seed = g->seed; h.step = g->step; h.step_dev = g->step_dev; h.row_offset = g->row_offset;
-    h.taken = g->taken_actions; h.taken_stride = g->taken_stride;
-    h.actions = g->actions; h.actions_stride = g->actions_stride; h.log_prob = g->log_prob; h.log_prob_stride = g->log_prob_stride;
-    *out = h;
-    return ROVER_OK;
-}
-
-static int chain_act(rover_ctx* c, const rover_chain_desc& d, int32_t M, const rover_gauss_head* head, const char* what, ChainRouteFn route,
-                     void* stream) {
-    if (!c) return ROVER_E_INVALID;
-    ChainArgs a; GaussHead h{};
-    if (int r = chain_args_of(c, d, M, what, &a, chain_min_k0(route))) return r;
-    if (int r = gauss_head_of(c, head, M, false, &h)) return r;
-    if (a.n[d.n_layers - 1] != h.A) return fail(c, ROVER_E_INVALID, "%s: the last layer is %d wide, the head has A = %d", what, a.n[d.n_layers - 1], h.A);
-    if (M == 0) return ROVER_OK;
-    const ChainRoute r = route(a);
-    if (r.kernel == ChainKernel::None) return chain_refused(c, what);
-    USE_DEVICE(c);
-    hipStream_t s = (hipStream_t)stream;
-    if (chain_head_fused(r, h.A)) {
-        HIP_TRY(c, launch_chain_head(a, r, h, s));
-        return ROVER_OK;
-    }
-    if (int e = chain_run(c, a, r, s)) return e;
-    HIP_TRY(c, launch_gaussian_head(a.y, a.y_stride, M, h, s));
-    return ROVER_OK;
-}
-
-int rover_mlp_chain_act(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers, const float* const* weights,
-                        const float* const* biases, const int32_t* widths, const int32_t* activations, float* y, int64_t y_stride,
-                        const rover_gauss_head* head, void* stream) {
-    const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
-    return chain_act(c, d, M, head, "mlp_chain_act", chain_route, stream);
-}
-
-int rover_mlp_chain_act_bf16(rover_ctx* c, const float* x, int64_t x_stride, int32_t M, int32_t K0, int32_t n_layers, const float* const* weights,
-                             const float* const* biases, const int32_t* widths, const int32_t* activations, float* y, int64_t y_stride,
-                             const rover_gauss_head* head, void* stream) {
-    const rover_chain_desc d{x, x_stride, K0, n_layers, weights, biases, widths, activations, y, y_stride};
-    return chain_act(c, d, M, head, "mlp_chain_act_bf16", chain_route_bf16, stream);
-}
-
-int rover_gaussian_head(rover_ctx* c, int32_t M, const rover_gauss_head* head, void* stream) {
-    if (!c) return ROVER_E_INVALID;
-    GaussHead h{};
-    if (int r = gauss_head_of(c, head, M, true, &h)) return r;
-    if (M == 0) return ROVER_OK;
-    USE_DEVICE(c);
-    HIP_TRY(c, launch_gaussian_head(head->mean, head->mean_stride, M, h, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-int rover_policy_noise(rover_ctx* c, uint64_t seed, uint64_t step, const uint64_t* step_dev, int64_t row_offset, int32_t M, int32_t A, float* eps,
-                       int64_t eps_stride, void* stream) {
-    if (!c) return ROVER_E_INVALID;
-    if (!eps || M < 0 || A < 1 || A > GAUSS_MAX_A || eps_stride < A || row_offset < 0 || row_offset + (int64_t)M > (int64_t)1 << 32)
-        return fail(c, ROVER_E_INVALID, "policy_noise: bad arguments (M=%d A=%d row_offset=%lld)", M, A, (long long)row_offset);
-    if (M == 0) return ROVER_OK;
-    USE_DEVICE(c);
-    HIP_TRY(c, launch_policy_noise(seed, step, step_dev, row_offset, M, A, eps, eps_stride, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-int rover_philox4x32(const uint32_t* counter, const uint32_t* key, uint32_t* out) {
-    if (!counter || !key || !out) return fail(nullptr, ROVER_E_INVALID, "philox4x32: null argument");
-    uint32_t w[4] = {counter[0], counter[1], counter[2], counter[3]};
-    philox4x32_10(w, key[0], key[1]);
-    for (int i = 0; i < 4; ++i) out[i] = w[i];
-    return ROVER_OK;
-}
-
-static const char* chain_act_route_query(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations,
-                                         const rover_gauss_head* head, ChainRouteFn route) {
-    const rover_chain_desc d{nullptr, 0, K0, n_layers, nullptr, nullptr, widths, activations, nullptr, 0};
-    ChainArgs a; GaussHead h{};
-    if (chain_shape_of(d, M, &a, chain_min_k0(route))) {
-        fail(nullptr, ROVER_E_INVALID, "mlp_chain_act_route: bad shapes (M=%d K0=%d layers=%d)", M, K0, n_layers);
-        return nullptr;
-    }
-    if (gauss_head_of(nullptr, head, M, false, &h)) return nullptr;
-    if (a.n[n_layers - 1] != h.A) {
-        fail(nullptr, ROVER_E_INVALID, "mlp_chain_act_route: the last layer is %d wide, the head has A = %d", a.n[n_layers - 1], h.A);
-        return nullptr;
-    }
-    if (M == 0) return "none";
-    const char* name = chain_act_route_name(route(a), h.A);
-    if (!name) fail(nullptr, ROVER_E_INVALID, "mlp_chain_act_route: net outside the built tile shapes");
-    return name;
-}
-const char* rover_mlp_chain_act_route(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations,
-                                      const rover_gauss_head* head) {
-    return chain_act_route_query(M, K0, n_layers, widths, activations, head, chain_route);
-}
-const char* rover_mlp_chain_act_route_bf16(int32_t M, int32_t K0, int32_t n_layers, const int32_t* widths, const int32_t* activations,
-                                           const rover_gauss_head* head) {
-    return chain_act_route_query(M, K0, n_layers, widths, activations, head, chain_route_bf16);
-}
-
-// ---- the learning entry points ----
-// Each lists its arrays as an operand table (rover_operands.h), which applies the operand rules of rover_step.h; the ctx is looked at last
-// (`need_ctx`: here), so every refusal is reached with a NULL ctx too and reports through rover_last_error(NULL).
-static int check_operands(rover_ctx* c, Operands& ops, bool need_ctx = true) {
-    char why[512];
-    if (ops.refused(why, sizeof why)) return fail(c, ROVER_E_INVALID, "%s", why);
-    return need_ctx && !c ? fail(nullptr, ROVER_E_INVALID, "%s: null ctx", ops.entry()) : ROVER_OK;
-}
-
-// ---- rollout: GAE ----
-int rover_gae(rover_ctx* c, const rover_gae_desc* d, void* stream) {
-    if (!d) return fail(c, ROVER_E_INVALID, "gae: null descriptor");
-    if (d->T < 1 || d->T > 4096 || d->E < 0 || (int64_t)d->T * d->E >= (int64_t)1 << 31)
-        return fail(c, ROVER_E_INVALID, "gae: T = %d outside 1 .. 4096, E = %d < 0, or T E >= 2^31", d->T, d->E);
-    if (d->normalize < ROVER_GAE_RAW || d->normalize > ROVER_GAE_NORMALIZE_GIVEN) return fail(c, ROVER_E_INVALID, "gae: unknown normalize %d", d->normalize);
-    if (d->E == 0) return ROVER_OK;            // nothing to read or write: no pointer is required
-    const int32_t T = d->T, E = d->E;
-    if (d->normalize == ROVER_GAE_NORMALIZE && (int64_t)T * E < 2)
-        return fail(c, ROVER_E_INVALID, "gae: ROVER_GAE_NORMALIZE needs T E >= 2 (the unbiased std of one element is NaN)");
-    Operands ops("gae");
-    ops.read("rewards", d->rewards, d->rewards_stride, T, E, 4).read("values", d->values, d->values_stride, T, E, 4)
-        .read("dones", d->dones, d->dones_stride, T, E, 1).read("last_values", d->last_values, E, 1, E, 4)
-        .written("returns", d->returns, d->returns_stride, T, E, 4).written("advantages", d->advantages, d->advantages_stride, T, E, 4)
-        .written("stats_out", d->stats_out, 3, 1, 3, 8, OP_OPTIONAL)
-        .same_array("returns", "values");
-    if (d->normalize == ROVER_GAE_NORMALIZE_GIVEN) ops.state("stats_in", d->stats_in, 3, 1, 3, 8);     // only read, but clear of every array
-    if (int e = check_operands(c, ops)) return e;
-    USE_DEVICE(c);
-    GaeArgs a{};
-    a.T = d->T; a.E = (uint32_t)d->E; a.gamma = d->gamma; a.lam = d->lam;
-    a.rewards = d->rewards; a.rewards_stride = d->rewards_stride; a.values = d->values; a.values_stride = d->values_stride;
-    a.dones = d->dones; a.dones_stride = d->dones_stride; a.last_values = d->last_values;
-    a.returns = d->returns; a.returns_stride = d->returns_stride; a.advantages = d->advantages; a.advantages_stride = d->advantages_stride;
-    a.normalize = d->normalize; a.stats_out = d->stats_out; a.stats_in = d->normalize == ROVER_GAE_NORMALIZE_GIVEN ? d->stats_in : nullptr;
-    a.partials = c->d_gae_partials.get();
-    HIP_TRY(c, launch_gae(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-int rover_combine_moments(const double* a, const double* b, double* out) {
-    if (!a || !b || !out) return fail(nullptr, ROVER_E_INVALID, "combine_moments: null argument");
-    gae_combine_moments(a, b, out);
-    return ROVER_OK;
-}
-
-// ---- training: the backward of one Layer, the PPO loss ----
-int rover_linear_backward(rover_ctx* c, const float* x, int64_t x_stride, const float* y, int64_t y_stride, const float* dy, int64_t dy_stride,
-                          int32_t M, int32_t K, const float* weight, int32_t N, int32_t activation, float* dx, int64_t dx_stride, float* dweight,
-                          float* dbias, void* stream) {
-    const LinearBwdRoute r = linear_backward_route(M, K, N, dx != nullptr);
-    if (!r.ok || activation < 0 || activation > 4)
-        return fail(c, ROVER_E_INVALID, "linear_backward: M=%d K=%d N=%d act=%d outside M >= 0, K >= 0 (<= 256 with dx), 1 <= N <= 256, act 0 .. 4", M, K, N, activation);
-    const bool need_x = dweight && K > 0, need_w = dx && K > 0;
-    Operands ops("linear_backward");        // M = 0: the [M, .] operands have no element and need no pointer, their strides are checked all the same
-    ops.read("dy", dy, dy_stride, M, N, 4);
-    if (activation) ops.read("y", y, y_stride, M, N, 4);
-    if (need_x) ops.read("x", x, x_stride, M, K, 4);
-    if (need_w) ops.read("weight", weight, K, M > 0 ? N : 0, K, 4).written("dx", dx, dx_stride, M, K, 4);
-    if (need_x) ops.written("dweight", dweight, K, M > 0 ? N : 0, K, 4);
-    ops.written("dbias", dbias, N, M > 0 ? 1 : 0, N, 4, OP_OPTIONAL);     // (M = 0 only zeroes dweight / dbias: they were never checked there)
-    if (int e = check_operands(c, ops)) return e;
-    USE_DEVICE(c);
-    hipStream_t s = (hipStream_t)stream;
-    LinearBwdArgs a{x, x_stride, y, y_stride, dy, dy_stride, weight, dx, dx_stride, dweight, dbias, M, K, N, activation};
-    if (M > 0 && (dweight || dbias))
-        if (int e = mlp_scratch_reserve(c, linear_backward_scratch_floats(r, K, N), s)) return e;
-    HIP_TRY(c, launch_linear_backward(a, r, c->d_mlp_scratch.get(), s));
-    return ROVER_OK;
-}
-
-const char* rover_linear_backward_route(int32_t M, int32_t K, int32_t N, int32_t want_dx) {
-    const LinearBwdRoute r = linear_backward_route(M, K, N, want_dx != 0);
-    if (!r.ok) return nullptr;
-    return M == 0 ? "zero" : linear_backward_route_name(r);
-}
-
-int rover_linear_dgrad(rover_ctx* c, const float* y, int64_t y_stride, const float* dy, int64_t dy_stride, int32_t M, int32_t K, const float* weight,
-                       int32_t N, int32_t activation, float* dx, int64_t dx_stride, void* stream) {
-    const LinearRoute r = linear_dgrad_route(M, N, K);
-    if (!r.nw || activation < 0 || activation > 4)
-        return fail(c, ROVER_E_INVALID, "linear_dgrad: M=%d K=%d N=%d act=%d outside M >= 0, 1 <= K <= %d, N >= 1, act 0 .. 4", M, K, N, activation, 32 * 65535);
-    if (M == 0) return ROVER_OK;
-    Operands ops("linear_dgrad");
-    ops.read("dy", dy, dy_stride, M, N, 4);
-    if (activation) ops.read("y", y, y_stride, M, N, 4);
-    ops.read("weight", weight, K, N, K, 4).written("dx", dx, dx_stride, M, K, 4);
-    if (int e = check_operands(c, ops)) return e;
-    USE_DEVICE(c);
-    LinearBwdArgs a{nullptr, 0, y, y_stride, dy, dy_stride, weight, dx, dx_stride, nullptr, nullptr, M, K, N, activation};
-    HIP_TRY(c, launch_linear_dgrad(a, r, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-const char* rover_linear_dgrad_route(int32_t M, int32_t K, int32_t N) {
-    const LinearRoute r = linear_dgrad_route(M, N, K);
-    if (!r.nw) return nullptr;
-    return M == 0 ? "none" : linear_dgrad_route_name(r);
-}
-
-int rover_ppo_loss(rover_ctx* c, const rover_ppo_loss_desc* d, void* stream) {
-    if (!d) return fail(c, ROVER_E_INVALID, "ppo_loss: null descriptor");
-    if (d->M < 0 || d->A < 1 || d->A > GAUSS_MAX_A) return fail(c, ROVER_E_INVALID, "ppo_loss: M = %d < 0 or A = %d outside 1 .. %d", d->M, d->A, GAUSS_MAX_A);
-    if (d->reduction != ROVER_REDUCE_SUM) return fail(c, ROVER_E_INVALID, "ppo_loss: the log-prob reduction must be ROVER_REDUCE_SUM (got %d)", d->reduction);
-    if (d->clip_log_std && !(d->min_log_std <= d->max_log_std))
-        return fail(c, ROVER_E_INVALID, "ppo_loss: min_log_std %g > max_log_std %g", (double)d->min_log_std, (double)d->max_log_std);
-    if (!(d->ratio_clip >= 0.0f) || (d->clip_predicted_values && !(d->value_clip >= 0.0f)))
-        return fail(c, ROVER_E_INVALID, "ppo_loss: ratio_clip %g and value_clip %g must be >= 0", (double)d->ratio_clip, (double)d->value_clip);
-    if (d->M == 0) return ROVER_OK;            // nothing to read or write: no pointer is required
-    const int32_t M = d->M, A = d->A;
-    Operands ops("ppo_loss");
-    ops.read("mean", d->mean, d->mean_stride, M, A, 4).read("log_std", d->log_std, A, 1, A, 4).read("actions", d->actions, d->actions_stride, M, A, 4)
-        .read("old_log_prob", d->old_log_prob, M, 1, M, 4).read("advantages", d->advantages, M, 1, M, 4).read("value", d->value, M, 1, M, 4)
-        .read("old_values", d->old_values, M, 1, M, 4).read("returns", d->returns, M, 1, M, 4)
-        .written("d_mean", d->d_mean, d->d_mean_stride, M, A, 4).written("d_value", d->d_value, M, 1, M, 4)
-        .written("d_log_std", d->d_log_std, A, 1, A, 4).written("stats", d->stats, 4, 1, 4, 8);
-    if (int e = check_operands(c, ops)) return e;
-    USE_DEVICE(c);
-    PpoArgs a{};
-    a.M = M; a.A = A; a.mean = d->mean; a.mean_stride = d->mean_stride; a.log_std = d->log_std; a.actions = d->actions; a.actions_stride = d->actions_stride;
-    a.old_log_prob = d->old_log_prob; a.advantages = d->advantages; a.value = d->value; a.old_values = d->old_values; a.returns = d->returns;
-    a.clip_log_std = d->clip_log_std != 0; a.min_log_std = d->min_log_std; a.max_log_std = d->max_log_std;
-    a.ratio_clip = d->ratio_clip; a.value_clip = d->value_clip; a.clip_predicted_values = d->clip_predicted_values != 0;
-    a.entropy_loss_scale = d->entropy_loss_scale; a.value_loss_scale = d->value_loss_scale;
-    a.d_mean = d->d_mean; a.d_mean_stride = d->d_mean_stride; a.d_value = d->d_value; a.d_log_std = d->d_log_std; a.stats = d->stats;
-    a.partials = c->d_ppo_partials.get();
-    HIP_TRY(c, launch_ppo_loss(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-// ---- training: gradient-norm clip + Adam ----
-// shared by rover_optim_plan and rover_optim_create: NULL when the sizes are acceptable, else what is wrong; *total = sum(numel)
-static const char* optim_sizes_refused(int32_t n_tensors, const int64_t* numel, int64_t* total) {
-    if (!numel) return "numel is NULL";
-    if (n_tensors < 1 || n_tensors > 256) return "n_tensors outside 1 .. 256";
-    int64_t sum = 0;
-    for (int32_t i = 0; i < n_tensors; ++i) {
-        if (numel[i] < 0) return "a negative numel";
-        if (numel[i] >= (int64_t)1 << 31 || (sum += numel[i]) >= (int64_t)1 << 31) return "total elements >= 2^31";
-    }
-    *total = sum;
-    return nullptr;
-}
-
-int rover_optim_plan(int32_t n_tensors, const int64_t* numel, rover_optim_chunk* chunks, int64_t capacity, int64_t* n_chunks) {
-    int64_t total = 0;
-    if (const char* why = optim_sizes_refused(n_tensors, numel, &total)) return fail(nullptr, ROVER_E_INVALID, "optim_plan: %s", why);
-    if (!n_chunks) return fail(nullptr, ROVER_E_INVALID, "optim_plan: n_chunks is NULL");
-    const int64_t n = optim_plan(n_tensors, numel, nullptr, 0);
-    if (capacity < 0 || (chunks && capacity < n)) return fail(nullptr, ROVER_E_INVALID, "optim_plan: capacity %lld < %lld chunks", (long long)capacity, (long long)n);
-    static_assert(sizeof(rover_optim_chunk) == sizeof(OptimChunkHost), "rover_optim_chunk is OptimChunkHost");
-    if (chunks) (void)optim_plan(n_tensors, numel, reinterpret_cast<OptimChunkHost*>(chunks), capacity);
-    *n_chunks = n;
-    return ROVER_OK;
-}
-
-int rover_optim_create(rover_ctx* c, const rover_optim_desc* d, int32_t* handle) {
-    if (!d || !handle || !d->params || !d->grads) return fail(c, ROVER_E_INVALID, "optim_create: null descriptor, handle, params or grads");
-    int64_t total = 0;
-    if (const char* why = optim_sizes_refused(d->n_tensors, d->numel, &total)) return fail(c, ROVER_E_INVALID, "optim_create: %s", why);
-    Operands st("optim_create");        // the state by the operand rules (total = 0: the moments have no element); the tensor lists by the loops below
-    st.state("step", d->step, 1, 1, 1, 8, 0, 8).state("stopped", d->stopped, 1, 1, 1, 4, 0, 4)
-        .state("exp_avg", d->exp_avg, total, 1, total, 4, 0, 4).state("exp_avg_sq", d->exp_avg_sq, total, 1, total, 4, 0, 4);
-    if (int e = check_operands(c, st, false)) return e;
-    const int32_t n = d->n_tensors;
-    std::vector<Span> ps, gs, state = {st.span(0), st.span(1)};         // the tensors with elements; the state with elements
-    if (total > 0) state.insert(state.end(), {st.span(2), st.span(3)});
-    for (int32_t i = 0; i < n; ++i) {
-        if (d->numel[i] == 0) continue;
-        if (!d->params[i] || !d->grads[i] || (uintptr_t)d->params[i] % 4 || (uintptr_t)d->grads[i] % 4)
-            return fail(c, ROVER_E_INVALID, "optim_create: params[%d] or grads[%d] is NULL or misaligned", i, i);
-        Span p, g;
-        if (!span_of(d->params[i], d->numel[i], 1, d->numel[i], 4, &p) || !span_of(d->grads[i], d->numel[i], 1, d->numel[i], 4, &g))
-            return fail(c, ROVER_E_INVALID, "optim_create: params[%d] or grads[%d]: extent too large", i, i);
-        ps.push_back(p);
-        gs.push_back(g);
-    }
-    for (size_t i = 0; i < ps.size(); ++i) {
-        for (const Span& s : state)
-            if (overlap(ps[i], s) || overlap(gs[i], s)) return fail(c, ROVER_E_INVALID, "optim_create: a parameter or a gradient overlaps the state");
-        for (size_t j = 0; j < ps.size(); ++j)
-            if (overlap(ps[i], gs[j]) || (j > i && overlap(ps[i], ps[j])))
-                return fail(c, ROVER_E_INVALID, "optim_create: a parameter overlaps a gradient or another parameter");
-    }
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "optim_create: null ctx");       // the ctx is only where the handle is kept
-    USE_DEVICE(c);
-    const int64_t n_chunks = optim_plan(n, d->numel, nullptr, 0);
-    std::vector<OptimChunkHost> plan((size_t)n_chunks);
-    (void)optim_plan(n, d->numel, plan.data(), n_chunks);
-    std::vector<int64_t> offset((size_t)n, 0);                 // of tensor i in the flat state
-    for (int32_t i = 1; i < n; ++i) offset[i] = offset[i - 1] + d->numel[i - 1];
-    const bool state_al = ((uintptr_t)d->exp_avg | (uintptr_t)d->exp_avg_sq) % 16 == 0;
-    std::vector<OptimChunk> table((size_t)n_chunks);
-    for (int64_t k = 0; k < n_chunks; ++k) {
-        const OptimChunkHost& h = plan[(size_t)k];
-        OptimChunk& o = table[(size_t)k];
-        o.p = d->params[h.tensor] + h.first;
-        o.g = d->grads[h.tensor] + h.first;
-        o.state = (uint32_t)(offset[h.tensor] + h.first);
-        o.len = (uint32_t)h.length;
-        o.flags = (((uintptr_t)d->params[h.tensor] | (uintptr_t)d->grads[h.tensor]) % 16 == 0 ? OPTIM_PG_ALIGNED : 0) |
-                  (state_al && offset[h.tensor] % 4 == 0 ? OPTIM_STATE_ALIGNED : 0);
-        o.pad = 0;
-    }
-    OptimHandle h;
-    hipError_t e = h.record.alloc(1);
-    if (e == hipSuccess && n_chunks > 0) e = h.chunks.alloc((size_t)n_chunks);
-    if (e == hipSuccess && n_chunks > 0) e = h.partials.alloc((size_t)n_chunks);
-    if (e == hipSuccess && n_chunks > 0) e = hipMemcpy(h.chunks.get(), table.data(), table.size() * sizeof(OptimChunk), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(h.record.get(), 0, sizeof(OptimRecord));
-    if (e != hipSuccess) return fail(c, ROVER_E_HIP, "optim_create: %s", hipGetErrorString(e));
-    h.live = true;
-    h.n_chunks = (uint32_t)n_chunks;
-    h.exp_avg = d->exp_avg; h.exp_avg_sq = d->exp_avg_sq; h.step = d->step; h.stopped = d->stopped;
-    h.spans = state;
-    h.spans.insert(h.spans.end(), ps.begin(), ps.end());
-    h.spans.insert(h.spans.end(), gs.begin(), gs.end());
-    size_t slot = 0;
-    while (slot < c->optims.size() && c->optims[slot].live) ++slot;
-    if (slot == c->optims.size()) c->optims.emplace_back();
-    c->optims[slot] = std::move(h);
-    *handle = (int32_t)slot;
-    return ROVER_OK;
-}
-
-static OptimHandle* optim_handle(rover_ctx* c, int32_t handle) {
-    return handle >= 0 && (size_t)handle < c->optims.size() && c->optims[(size_t)handle].live ? &c->optims[(size_t)handle] : nullptr;
-}
-
-int rover_optim_destroy(rover_ctx* c, int32_t handle) {
-    if (!c) return ROVER_E_INVALID;
-    OptimHandle* h = optim_handle(c, handle);
-    if (!h) return fail(c, ROVER_E_INVALID, "optim_destroy: handle %d is not live", handle);
-    USE_DEVICE(c);
-    *h = OptimHandle{};                 // (the owners free their device memory)
-    return ROVER_OK;
-}
-
-int rover_optim_step(rover_ctx* c, int32_t handle, const rover_optim_step_desc* d, void* stream) {
-    if (!d) return fail(c, ROVER_E_INVALID, "optim_step: null descriptor");
-    if (!(d->lr >= 0.0) || !std::isfinite(d->lr) || !(d->beta1 >= 0.0 && d->beta1 < 1.0) || !(d->beta2 >= 0.0 && d->beta2 < 1.0) ||
-        !(d->eps >= 0.0) || !std::isfinite(d->eps))
-        return fail(c, ROVER_E_INVALID, "optim_step: lr %g and eps %g must be finite and >= 0, beta1 %g and beta2 %g in [0, 1)", d->lr, d->eps, d->beta1, d->beta2);
-    if (std::isnan(d->grad_norm_clip) || std::isnan(d->gate_threshold)) return fail(c, ROVER_E_INVALID, "optim_step: grad_norm_clip or gate_threshold is NaN");
-    Operands ops("optim_step");
-    ops.read("gate", d->gate, 1, 1, 1, 8, OP_OPTIONAL, 8).written("norm_out", d->norm_out, 1, 1, 1, 8, OP_OPTIONAL, 8);
-    if (int e = check_operands(c, ops)) return e;
-    const OptimHandle* h = optim_handle(c, handle);
-    if (!h) return fail(c, ROVER_E_INVALID, "optim_step: handle %d is not live", handle);
-    Span out;
-    if (d->norm_out && span_of(d->norm_out, 1, 1, 1, 8, &out))
-        for (const Span& s : h->spans)
-            if (overlap(out, s)) return fail(c, ROVER_E_INVALID, "optim_step: norm_out overlaps a parameter, a gradient or the state");
-    USE_DEVICE(c);
-    OptimArgs a{};
-    a.chunks = h->chunks.get(); a.n_chunks = h->n_chunks; a.partials = h->partials.get(); a.record = h->record.get();
-    a.exp_avg = h->exp_avg; a.exp_avg_sq = h->exp_avg_sq; a.step = h->step; a.stopped = h->stopped;
-    a.lr = d->lr; a.beta1 = d->beta1; a.beta2 = d->beta2; a.eps = d->eps; a.clip = d->grad_norm_clip;
-    a.gate = d->gate; a.gate_threshold = d->gate_threshold; a.norm_out = d->norm_out;
-    HIP_TRY(c, launch_optim_step(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-// ---- the student policy's recurrent block (rover_gru.hip) ----
-static int gru_cell_run(rover_ctx* c, const char* what, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K,
-                        int32_t H, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
-                        int64_t h_out_stride, bool train, float* gates, int64_t gates_stride, void* stream,
-                        hipError_t (*launch)(const GruArgs&, hipStream_t) = launch_gru_cell) {
-    if (!gru_cell_route(M, K, H).nw) return fail(c, ROVER_E_INVALID, "%s: M=%d K=%d H=%d outside M >= 0, K >= 0, 1 <= H <= %d", what, M, K, H, 32 * 65535);
-    if (M == 0) return ROVER_OK;                   // nothing is read or written: no pointer is required
-    const int64_t G = (int64_t)3 * H;              // gate rows
-    Operands ops(what);
-    ops.read("h_in", h_in, h_in_stride, M, H, 4);  // (h_out may not even be h_in: a tile of h' needs whole rows of h that other workgroups still read)
-    if (K > 0) ops.read("x", x, x_stride, M, K, 4).read("w_ih", w_ih, K, G, K, 4);
-    ops.read("w_hh", w_hh, H, G, H, 4).read("b_ih", b_ih, G, 1, G, 4, OP_OPTIONAL).read("b_hh", b_hh, G, 1, G, 4, OP_OPTIONAL)
-        .read("reset_mask", reset_mask, M, 1, M, 1, OP_OPTIONAL).written("h_out", h_out, h_out_stride, M, H, 4);
-    if (train) ops.written("gates", gates, gates_stride, M, (int64_t)4 * H, 4);
-    if (int e = check_operands(c, ops)) return e;
-    USE_DEVICE(c);
-    GruArgs a{x, x_stride, h_in, h_in_stride, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, M, K, H, train ? gates : nullptr, gates_stride};
-    HIP_TRY(c, launch(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-int rover_gru_cell(rover_ctx* c, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K, int32_t H,
-                   const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
-                   int64_t h_out_stride, void* stream) {
-    return gru_cell_run(c, "gru_cell", x, x_stride, h_in, h_in_stride, M, K, H, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, false, nullptr, 0, stream);
-}
-
-int rover_gru_cell_bf16(rover_ctx* c, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K, int32_t H,
-                        const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
-                        int64_t h_out_stride, void* stream) {
-    return gru_cell_run(c, "gru_cell_bf16", x, x_stride, h_in, h_in_stride, M, K, H, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, false, nullptr, 0,
-                        stream, launch_gru_cell_bf16);
-}
-
-int rover_gru_cell_train(rover_ctx* c, const float* x, int64_t x_stride, const float* h_in, int64_t h_in_stride, int32_t M, int32_t K, int32_t H,
-                         const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const uint8_t* reset_mask, float* h_out,
-                         int64_t h_out_stride, float* gates, int64_t gates_stride, void* stream) {
-    return gru_cell_run(c, "gru_cell_train", x, x_stride, h_in, h_in_stride, M, K, H, w_ih, w_hh, b_ih, b_hh, reset_mask, h_out, h_out_stride, true, gates,
-                        gates_stride, stream);
-}
-
-int rover_gru_cell_backward(rover_ctx* c, const float* dh_above, int64_t dh_above_stride, const float* dh_next, int64_t dh_next_stride, const float* gates,
-                            int64_t gates_stride, const float* h_in, int64_t h_in_stride, const uint8_t* reset_mask, const float* w_hh, int32_t M, int32_t H,
-                            float* dgi, int64_t dgi_stride, float* dgh, int64_t dgh_stride, float* dh_in, int64_t dh_in_stride, void* stream) {
-    if (!gru_cell_backward_route(M, H).nw) return fail(c, ROVER_E_INVALID, "gru_cell_backward: M=%d H=%d outside M >= 0, 1 <= H <= %d", M, H, 32 * 65535);
-    if (M == 0) return ROVER_OK;
-    const int64_t G = (int64_t)3 * H;
-    Operands ops("gru_cell_backward");
-    ops.read("dh_above", dh_above, dh_above_stride, M, H, 4).read("dh_next", dh_next, dh_next_stride, M, H, 4, OP_OPTIONAL)
-        .read("gates", gates, gates_stride, M, (int64_t)4 * H, 4).read("h_in", h_in, h_in_stride, M, H, 4)
-        .read("reset_mask", reset_mask, M, 1, M, 1, OP_OPTIONAL).read("w_hh", w_hh, H, G, H, 4)
-        .written("dgi", dgi, dgi_stride, M, G, 4).written("dgh", dgh, dgh_stride, M, G, 4).written("dh_in", dh_in, dh_in_stride, M, H, 4);
-    if (int e = check_operands(c, ops)) return e;
-    USE_DEVICE(c);
-    GruBwdArgs a{dh_above, dh_above_stride, dh_next, dh_next_stride, gates, gates_stride, h_in, h_in_stride, reset_mask, w_hh,
-                 dgi, dgi_stride, dgh, dgh_stride, dh_in, dh_in_stride, M, H};
-    HIP_TRY(c, launch_gru_cell_backward(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-const char* rover_gru_cell_backward_route(int32_t M, int32_t H) {
-    const GruRoute r = gru_cell_backward_route(M, H);
-    if (!r.nw) return nullptr;
-    return M == 0 ? "none" : gru_cell_backward_route_name(r);
-}
-
-const char* rover_gru_cell_route(int32_t M, int32_t K, int32_t H) {
-    const GruRoute r = gru_cell_route(M, K, H);
-    if (!r.nw) return nullptr;
-    return M == 0 ? "none" : gru_cell_route_name(r);
-}
-
-const char* rover_gru_cell_route_bf16(int32_t M, int32_t K, int32_t H) {
-    const char* name = gru_cell_route_bf16_name(M, K, H);
-    if (!name) return nullptr;
-    return M == 0 ? "none" : name;
-}
-
-int rover_gated_sum(rover_ctx* c, const float* add, int64_t add_stride, const float* mul, int64_t mul_stride, const float* pre, int64_t pre_stride,
-                    int32_t M, int32_t N, float* out, int64_t out_stride, void* stream) {
-    if (M < 0 || N < 1 || (int64_t)M * N >= (int64_t)1 << 38) return fail(c, ROVER_E_INVALID, "gated_sum: M=%d N=%d outside M >= 0, N >= 1, M N < 2^38", M, N);
-    if (M == 0) return ROVER_OK;
-    Operands ops("gated_sum");
-    ops.read("add", add, add_stride, M, N, 4, OP_STRIDE0).read("mul", mul, mul_stride, M, N, 4, OP_STRIDE0).read("pre", pre, pre_stride, M, N, 4, OP_STRIDE0)
-        .written("out", out, out_stride, M, N, 4);
-    if (int e = check_operands(c, ops)) return e;
-    USE_DEVICE(c);
-    GatedSumArgs a{add, add_stride, mul, mul_stride, pre, pre_stride, out, out_stride, M, N};
-    HIP_TRY(c, launch_gated_sum(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-int rover_gated_sum_backward(rover_ctx* c, const float* d_out, int64_t d_out_stride, const float* mul, int64_t mul_stride, const float* pre,
-                             int64_t pre_stride, int32_t M, int32_t N, float* d_mul, int64_t d_mul_stride, float* d_pre, int64_t d_pre_stride, void* stream) {
-    if (M < 0 || N < 1 || (int64_t)M * N >= (int64_t)1 << 38)
-        return fail(c, ROVER_E_INVALID, "gated_sum_backward: M=%d N=%d outside M >= 0, N >= 1, M N < 2^38", M, N);
-    if (M == 0 || (!d_mul && !d_pre)) return ROVER_OK;
-    Operands ops("gated_sum_backward");
-    ops.read("d_out", d_out, d_out_stride, M, N, 4);
-    if (d_pre) ops.read("mul", mul, mul_stride, M, N, 4, OP_STRIDE0);
-    ops.read("pre", pre, pre_stride, M, N, 4, OP_STRIDE0).written("d_mul", d_mul, d_mul_stride, M, N, 4, OP_OPTIONAL)
-        .written("d_pre", d_pre, d_pre_stride, M, N, 4, OP_OPTIONAL);
-    if (int e = check_operands(c, ops)) return e;
-    USE_DEVICE(c);
-    GatedSumBwdArgs a{d_out, d_out_stride, mul, mul_stride, pre, pre_stride, d_mul, d_mul_stride, d_pre, d_pre_stride, M, N};
-    HIP_TRY(c, launch_gated_sum_backward(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-// Validates the whole descriptor before the ctx is looked at (a NULL ctx reports through rover_last_error(NULL)): the refusals can be
-// checked without a device.
-int rover_obs_noise(rover_ctx* c, const rover_obs_noise_desc* d, void* stream) {
-    if (!d) return fail(c, ROVER_E_INVALID, "obs_noise: null descriptor");
-    if (d->M < 0 || d->F < 0) return fail(c, ROVER_E_INVALID, "obs_noise: M = %d or F = %d is negative", d->M, d->F);
-    if (d->first < 0 || d->first > d->F) return fail(c, ROVER_E_INVALID, "obs_noise: first = %d outside 0 .. F = %d", d->first, d->F);
-    if (d->F - d->first > (1 << 21)) return fail(c, ROVER_E_INVALID, "obs_noise: %d heightmap columns, more than 2^21", d->F - d->first);
-    if (!(d->sigma_point >= 0.0f) || !std::isfinite(d->sigma_point) || !(d->sigma_offset >= 0.0f) || !std::isfinite(d->sigma_offset))
-        return fail(c, ROVER_E_INVALID, "obs_noise: sigma_point = %g or sigma_offset = %g is negative or not finite", (double)d->sigma_point, (double)d->sigma_offset);
-    if (!(d->dropout >= 0.0 && d->dropout <= 1.0)) return fail(c, ROVER_E_INVALID, "obs_noise: dropout = %g outside [0, 1]", d->dropout);
-    if (!std::isfinite(d->drop_value)) return fail(c, ROVER_E_INVALID, "obs_noise: drop_value is not finite");
-    if (d->row_offset < 0 || d->row_offset + (int64_t)d->M > (int64_t)1 << 32)
-        return fail(c, ROVER_E_INVALID, "obs_noise: row_offset = %lld is negative or row_offset + M passes 2^32", (long long)d->row_offset);
-    const bool empty = d->M == 0 || d->F == 0;
-    if (!empty) {
-        Operands ops("obs_noise");
-        ops.read("in", d->in, d->in_stride, d->M, d->F, 4).written("out", d->out, d->out_stride, d->M, d->F, 4)
-            .read("row_scale", d->row_scale, d->M, 1, d->M, 4, OP_OPTIONAL).read("episode", d->episode, d->M, 1, d->M, 8, OP_OPTIONAL)
-            .read("step_dev", d->step_dev, 1, 1, 1, 8, OP_OPTIONAL)
-            .same_array("out", "in");
-        if (int e = check_operands(c, ops, false)) return e;
-    }
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "obs_noise: null ctx");
-    if (empty) return ROVER_OK;
-    USE_DEVICE(c);
-    ObsNoiseArgs a{};
-    a.in = d->in; a.in_stride = d->in_stride; a.out = d->out; a.out_stride = d->out_stride;
-    a.M = d->M; a.F = d->F; a.first = d->first;
-    a.sigma_point = d->sigma_point; a.sigma_offset = d->sigma_offset; a.drop_value = d->drop_value;
-    (void)rover_obs_noise_threshold(d->dropout, &a.thr);
-    a.row_scale = d->row_scale; a.episode = d->episode;
-    a.seed = d->seed; a.step = d->step; a.step_dev = d->step_dev; a.row_offset = d->row_offset;
-    HIP_TRY(c, launch_obs_noise(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-// Host only: the dropout threshold rover_obs_noise compares a column's 24-bit word with
-int rover_obs_noise_threshold(double dropout, uint32_t* thr) {
-    if (!thr || !(dropout >= 0.0 && dropout <= 1.0)) return fail(nullptr, ROVER_E_INVALID, "obs_noise_threshold: null argument or dropout = %g outside [0, 1]", dropout);
-    *thr = (uint32_t)llrint(dropout * 16777216.0);
-    return ROVER_OK;
-}
-
-// Host only: the heightmap columns far first by the horizontal distance of their body point from the camera, ties in column order
-int rover_occlusion_order(const double* points, int32_t P, const int64_t* sparse_idx, int32_t Ns, const int64_t* dense_idx, int32_t Nd,
-                          const float camera[3], int32_t* order) {
-    if (!points || !order || !camera || P <= 0 || Ns < 0 || Nd < 0 || (Ns > 0 && !sparse_idx) || (Nd > 0 && !dense_idx))
-        return fail(nullptr, ROVER_E_INVALID, "occlusion_order: null argument or bad counts (P=%d Ns=%d Nd=%d)", P, Ns, Nd);
-    if (!std::isfinite(camera[0]) || !std::isfinite(camera[1]) || !std::isfinite(camera[2]))
-        return fail(nullptr, ROVER_E_INVALID, "occlusion_order: the camera is not finite");
-    const int32_t C = Ns + Nd;
-    std::vector<double> key((size_t)C);
-    for (int32_t c = 0; c < C; ++c) {
-        const int64_t j = c < Ns ? sparse_idx[c] : dense_idx[c - Ns];
-        if (j < 0 || j >= P) return fail(nullptr, ROVER_E_INVALID, "occlusion_order: index %lld outside [0,%d)", (long long)j, P);
-        const double ax = (double)(float)points[3 * j] - (double)camera[0], ay = (double)(float)points[3 * j + 1] - (double)camera[1];
-        const double k = ax * ax + ay * ay;
-        key[(size_t)c] = k == k ? k : -1.0;        // a NaN point goes last
-    }
-    for (int32_t c = 0; c < C; ++c) order[c] = c;
-    std::stable_sort(order, order + C, [&](int32_t a, int32_t b) { return key[(size_t)a] > key[(size_t)b]; });
-    return ROVER_OK;
-}
-
-// The cfg is validated before the ctx is looked at.  Builds the three derived tables whole, then moves them into the ctx in one assignment
-// (a failure half way leaves the previous configuration in force).
-int rover_set_occlusion(rover_ctx* c, const rover_occlusion_cfg* cfg) {
-    if (!cfg) return fail(c, ROVER_E_INVALID, "set_occlusion: null cfg");
-    if (!std::isfinite(cfg->camera[0]) || !std::isfinite(cfg->camera[1]) || !std::isfinite(cfg->camera[2]) || !std::isfinite(cfg->step) ||
-        !std::isfinite(cfg->clearance) || !std::isfinite(cfg->miss))
-        return fail(c, ROVER_E_INVALID, "set_occlusion: camera, step, clearance and miss must be finite");
-    if (!(cfg->step > 0.0f)) return fail(c, ROVER_E_INVALID, "set_occlusion: step = %g is not > 0", (double)cfg->step);
-    if (cfg->max_steps < 2 || cfg->max_steps > 4096) return fail(c, ROVER_E_INVALID, "set_occlusion: max_steps = %d outside 2 .. 4096", cfg->max_steps);
-    if (!(cfg->miss > 0.0f)) return fail(c, ROVER_E_INVALID, "set_occlusion: miss = %g is not > 0", (double)cfg->miss);
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "set_occlusion: null ctx");
-    if (!c->have_dist) return fail(c, ROVER_E_STATE, "set_occlusion: rover_set_distribution first");
-    if (!c->have_hf) return fail(c, ROVER_E_STATE, "set_occlusion: rover_set_heightfield first");
-    USE_DEVICE(c);
-    const int32_t C = c->Ns + c->Nd;
-    std::vector<double> pts((size_t)c->P * 3);
-    std::vector<int32_t> idx((size_t)C);
-    HIP_TRY(c, hipMemcpy(pts.data(), c->d_dist.get(), pts.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if (C) HIP_TRY(c, hipMemcpy(idx.data(), c->d_obs_idx.get(), idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    std::vector<int64_t> idx64(idx.begin(), idx.end());
-    std::vector<float> body((size_t)C * 3);
-    for (int32_t k = 0; k < C; ++k)
-        for (int i = 0; i < 3; ++i) body[(size_t)3 * k + i] = (float)pts[(size_t)3 * idx[(size_t)k] + i];
-    std::vector<int32_t> order((size_t)C);
-    if (int e = rover_occlusion_order(pts.data(), c->P, idx64.data(), c->Ns, idx64.data() + c->Ns, c->Nd, cfg->camera, order.data()))
-        return fail(c, e, "set_occlusion: %s", g_create_err.c_str());
-    OcclusionTables t;
-    t.cfg = *cfg;
-    t.TN0 = (c->hf.N0 + OCC_TILE - 1) / OCC_TILE; t.TN1 = (c->hf.N1 + OCC_TILE - 1) / OCC_TILE;
-    HIP_TRY(c, t.body3.alloc(body.size() + 1));
-    HIP_TRY(c, t.order.alloc(order.size() + 1));
-    HIP_TRY(c, t.tilemax.alloc((size_t)t.TN0 * t.TN1));
-    if (C) HIP_TRY(c, hipMemcpy(t.body3.get(), body.data(), body.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (C) HIP_TRY(c, hipMemcpy(t.order.get(), order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, launch_occlusion_tiles(c->hf, t.tilemax.get(), t.TN0, t.TN1, nullptr));
-    HIP_TRY(c, hipStreamSynchronize(nullptr));
-    t.dist_gen = c->dist_gen; t.hf_gen = c->hf_gen;
-    t.set = true;
-    c->occ = std::move(t);
-    return ROVER_OK;
-}
-
-// The descriptor is validated before the ctx is looked at, as for rover_obs_noise
-int rover_obs_occlusion(rover_ctx* c, const rover_obs_occlusion_desc* d, void* stream) {
-    if (!d) return fail(c, ROVER_E_INVALID, "obs_occlusion: null descriptor");
-    if (d->M < 0 || d->F < 0) return fail(c, ROVER_E_INVALID, "obs_occlusion: M = %d or F = %d is negative", d->M, d->F);
-    if (d->first < 0 || d->first > d->F) return fail(c, ROVER_E_INVALID, "obs_occlusion: first = %d outside 0 .. F = %d", d->first, d->F);
-    if (!std::isfinite(d->drop_value)) return fail(c, ROVER_E_INVALID, "obs_occlusion: drop_value is not finite");
-    const bool empty = d->M == 0 || d->F == 0;
-    const int64_t C = (int64_t)d->F - d->first;
-    if (!empty) {
-        Operands ops("obs_occlusion");
-        ops.read("pos3", d->pos3, 3, d->M, 3, 4).read("quat4", d->quat4, 4, d->M, 4, 4)
-            .read("clean", d->clean, d->clean_stride, d->M, d->F, 4).read("in", d->in, d->in_stride, d->M, d->F, 4)
-            .written("out", d->out, d->out_stride, d->M, d->F, 4)
-            .written("hidden_u8", d->hidden_u8, d->hidden_stride, d->M, C, 1, OP_OPTIONAL).written("target3", d->target3, 3 * C, d->M, 3 * C, 4, OP_OPTIONAL)
-            .same_array("out", "in");
-        if (int e = check_operands(c, ops, false)) return e;
-    }
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "obs_occlusion: null ctx");
-    if (!c->have_dist) return fail(c, ROVER_E_STATE, "obs_occlusion: rover_set_distribution first");
-    if (!c->have_hf) return fail(c, ROVER_E_STATE, "obs_occlusion: rover_set_heightfield first");
-    if (!c->occ.set) return fail(c, ROVER_E_STATE, "obs_occlusion: rover_set_occlusion first");
-    if (c->occ.dist_gen != c->dist_gen || c->occ.hf_gen != c->hf_gen)
-        return fail(c, ROVER_E_STATE, "obs_occlusion: the %s was set again after rover_set_occlusion: call rover_set_occlusion again",
-                    c->occ.dist_gen != c->dist_gen ? "distribution" : "heightfield");
-    if (C != (int64_t)c->Ns + c->Nd)
-        return fail(c, ROVER_E_STATE, "obs_occlusion: F - first = %lld columns, the distribution has Ns + Nd = %d", (long long)C, c->Ns + c->Nd);
-    if (empty) return ROVER_OK;
-    USE_DEVICE(c);
-    const OcclusionTables& t = c->occ;
-    OcclusionArgs a{};
-    a.h = c->hf;
-    a.tilemax = t.tilemax.get(); a.TN0 = t.TN0; a.TN1 = t.TN1;
-    a.body3 = t.body3.get(); a.order = t.order.get();
-    a.pos3 = d->pos3; a.quat4 = d->quat4;
-    a.clean = d->clean; a.clean_stride = d->clean_stride; a.in = d->in; a.in_stride = d->in_stride; a.out = d->out; a.out_stride = d->out_stride;
-    a.hidden = d->hidden_u8; a.hidden_stride = d->hidden_stride; a.target3 = d->target3;
-    a.M = d->M; a.F = d->F; a.first = d->first;
-    for (int i = 0; i < 3; ++i) a.camera[i] = t.cfg.camera[i];
-    a.step = t.cfg.step; a.clearance = t.cfg.clearance; a.miss = t.cfg.miss; a.drop_value = d->drop_value;
-    a.max_steps = t.cfg.max_steps; a.route = c->occlusion_route;
-    HIP_TRY(c, launch_obs_occlusion(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-// Host only, a pure function of (M, N): the route, the chunking and the scratch of rover_scaler_update
-int rover_scaler_plan(int32_t M, int32_t N, rover_scaler_plan_desc* plan) {
-    if (!plan) return fail(nullptr, ROVER_E_INVALID, "scaler_plan: null plan");
-    if (N < 1 || N > 4096) return fail(nullptr, ROVER_E_INVALID, "scaler_plan: N = %d outside 1 .. 4096", N);
-    if (M < 0 || (int64_t)M * N >= (int64_t)1 << 31) return fail(nullptr, ROVER_E_INVALID, "scaler_plan: M = %d is negative or M N >= 2^31", M);
-    const bool narrow = (uint32_t)N <= SCALER_NARROW_MAX_N;
-    plan->route = narrow ? ROVER_SCALER_NARROW : ROVER_SCALER_WIDE;
-    plan->rows_per_chunk = narrow ? 16384 : (M <= 8192 ? 32 : 128);
-    plan->n_chunks = (int32_t)(((int64_t)M + plan->rows_per_chunk - 1) / plan->rows_per_chunk);
-    plan->scratch_bytes = 8 + (int64_t)24 * plan->n_chunks * N;
-    return ROVER_OK;
-}
-
-// The descriptor is validated before the ctx is looked at, as for rover_obs_noise
-int rover_scaler_update(rover_ctx* c, const rover_scaler_update_desc* d, void* stream) {
-    if (!d) return fail(c, ROVER_E_INVALID, "scaler_update: null descriptor");
-    rover_scaler_plan_desc plan;
-    if (d->N < 1 || d->N > 4096) return fail(c, ROVER_E_INVALID, "scaler_update: N = %d outside 1 .. 4096", d->N);
-    if (d->M < 0 || (int64_t)d->M * d->N >= (int64_t)1 << 31) return fail(c, ROVER_E_INVALID, "scaler_update: M = %d is negative or M N >= 2^31", d->M);
-    if (d->M < 2) return fail(c, ROVER_E_INVALID, "scaler_update: M = %d rows, a train call needs at least 2 (the unbiased variance of one row is undefined)", d->M);
-    (void)rover_scaler_plan(d->M, d->N, &plan);
-    if (d->scratch_bytes < plan.scratch_bytes)
-        return fail(c, ROVER_E_INVALID, "scaler_update: scratch of %lld bytes, the plan needs %lld", (long long)d->scratch_bytes, (long long)plan.scratch_bytes);
-    Operands ops("scaler_update");
-    ops.read("x", d->x, d->x_stride, d->M, d->N, 4).written("scratch", d->scratch, 0, 1, d->scratch_bytes, 1, OP_BYTES, 8)
-        .state("mean", d->mean, d->N, 1, d->N, 8, 0, 8).state("var", d->var, d->N, 1, d->N, 8, 0, 8).state("count", d->count, 1, 1, 1, 8, 0, 8)
-        .read("skip_if", d->skip_if, 1, 1, 1, 4, OP_OPTIONAL, 4);
-    if (int e = check_operands(c, ops)) return e;
-    USE_DEVICE(c);
-    ScalerUpdateArgs a{};
-    a.x = d->x; a.x_stride = d->x_stride;
-    a.M = (uint32_t)d->M; a.N = (uint32_t)d->N; a.rows_per_chunk = (uint32_t)plan.rows_per_chunk; a.n_chunks = (uint32_t)plan.n_chunks;
-    a.partials = (double*)d->scratch + 1;
-    a.mean = d->mean; a.var = d->var; a.count = d->count; a.skip_if = d->skip_if;
-    HIP_TRY(c, launch_scaler_update(a, plan.route == ROVER_SCALER_NARROW ? SCALER_ROUTE_NARROW : SCALER_ROUTE_WIDE, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-int rover_scaler_apply(rover_ctx* c, const rover_scaler_apply_desc* d, void* stream) {
-    if (!d) return fail(c, ROVER_E_INVALID, "scaler_apply: null descriptor");
-    if (d->N < 1 || d->N > 4096) return fail(c, ROVER_E_INVALID, "scaler_apply: N = %d outside 1 .. 4096", d->N);
-    if (d->M < 0 || (int64_t)d->M * d->N >= (int64_t)1 << 31) return fail(c, ROVER_E_INVALID, "scaler_apply: M = %d is negative or M N >= 2^31", d->M);
-    if (!(d->epsilon >= 0.0) || !std::isfinite(d->epsilon) || !(d->clip >= 0.0) || !std::isfinite(d->clip))
-        return fail(c, ROVER_E_INVALID, "scaler_apply: epsilon = %g or clip = %g is negative or not finite", d->epsilon, d->clip);
-    Operands ops("scaler_apply");
-    if (d->M > 0) ops.read("x", d->x, d->x_stride, d->M, d->N, 4).written("y", d->y, d->y_stride, d->M, d->N, 4).same_array("y", "x");
-    ops.state("mean", d->mean, d->N, 1, d->N, 8, 0, 8).state("var", d->var, d->N, 1, d->N, 8, 0, 8);      // only read here, but clear of x and y too
-    if (int e = check_operands(c, ops)) return e;
-    if (d->M == 0) return ROVER_OK;
-    USE_DEVICE(c);
-    ScalerApplyArgs a{d->x, d->x_stride, d->y, d->y_stride, (uint32_t)d->M, (uint32_t)d->N, d->mean, d->var, (float)d->epsilon, (float)d->clip};
-    HIP_TRY(c, launch_scaler_apply(a, d->inverse != 0, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-// The checks that rover_motion_step and rover_motion_step_bogie share, in two parts: the descriptor's own, which need no ctx ...
-static int motion_check_desc(rover_ctx* c, const rover_motion_desc* d, const char* what) {
-    if (!d) return fail(c, ROVER_E_INVALID, "%s: null descriptor", what);
-    if (d->E < 0 || d->substeps < 1 || d->cmd_stride < 1)
-        return fail(c, ROVER_E_INVALID, "%s: E = %d is negative, substeps = %d or cmd_stride = %d is below 1", what, d->E, d->substeps, d->cmd_stride);
-    if (!std::isfinite(d->dt) || !(d->dt > 0.0f)) return fail(c, ROVER_E_INVALID, "%s: dt = %g is not finite or not > 0", what, (double)d->dt);
-    if (d->E > 0 && (!d->pos3 || !d->quat4 || !d->lin || !d->ang)) return fail(c, ROVER_E_INVALID, "%s: pos3, quat4, lin and ang must be given", what);
-    const int n_joint = (d->joint_pos_targets13 != nullptr) + (d->joint_vel_targets13 != nullptr) + (d->joint_pos13 != nullptr) + (d->joint_vel13 != nullptr);
-    if (n_joint != 0 && n_joint != 4)
-        return fail(c, ROVER_E_INVALID, "%s: joint_pos_targets13, joint_vel_targets13, joint_pos13 and joint_vel13 go together (%d of 4 given)", what, n_joint);
-    return ROVER_OK;
-}
-
-// ... and the ctx's, after which the kernel's arguments are filled in
-static int motion_check_ctx(rover_ctx* c, const rover_motion_desc* d, const char* what, MotionArgs& a) {
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "%s: null ctx", what);
-    if (!c->have_hf) return fail(c, ROVER_E_STATE, "%s: rover_set_heightfield first", what);
-    a.h = c->hf;
-    a.pos3 = d->pos3; a.quat4 = d->quat4; a.lin = d->lin; a.ang = d->ang;
-    a.cmd_stride = d->cmd_stride; a.E = (uint32_t)d->E; a.substeps = d->substeps;
-    a.dt = d->dt; a.max_lin = d->max_lin; a.max_ang = d->max_ang; a.ride_height = d->ride_height;
-    a.joint_pos_targets13 = d->joint_pos_targets13; a.joint_vel_targets13 = d->joint_vel_targets13;
-    a.joint_pos13 = d->joint_pos13; a.joint_vel13 = d->joint_vel13;
-    return ROVER_OK;
-}
-
-// The descriptor is validated before the ctx is looked at, as for rover_obs_noise
-int rover_motion_step(rover_ctx* c, const rover_motion_desc* d, void* stream) {
-    const char* what = "motion_step";
-    if (int e = motion_check_desc(c, d, what)) return e;
-    MotionArgs a{};
-    if (int e = motion_check_ctx(c, d, what, a)) return e;
-    if (d->E == 0) return ROVER_OK;
-    USE_DEVICE(c);
-    motion_plane_fit(a.fit);
-    HIP_TRY(c, launch_motion(a, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-// The rocker-bogie posture mode: rover_motion_step's refusals and the two parameters', all before the ctx is looked at
-int rover_motion_step_bogie(rover_ctx* c, const rover_motion_desc* d, const rover_bogie_params* p, void* stream) {
-    const char* what = "motion_step_bogie";
-    if (int e = motion_check_desc(c, d, what)) return e;
-    if (!p) return fail(c, ROVER_E_INVALID, "%s: null parameters", what);
-    if (p->iters < 1 || p->iters > ROVER_BOGIE_MAX_ITERS)
-        return fail(c, ROVER_E_INVALID, "%s: iters = %d is outside 1 .. %d", what, p->iters, ROVER_BOGIE_MAX_ITERS);
-    if (!std::isfinite(p->max_bogie) || !(p->max_bogie > 0.0f))
-        return fail(c, ROVER_E_INVALID, "%s: max_bogie = %g is not finite or not > 0", what, (double)p->max_bogie);
-    MotionArgs a{};
-    if (int e = motion_check_ctx(c, d, what, a)) return e;
-    if (d->E == 0) return ROVER_OK;
-    USE_DEVICE(c);
-    HIP_TRY(c, launch_motion_bogie(a, p->iters, p->max_bogie, (hipStream_t)stream));
-    return ROVER_OK;
-}
-
-// Host only: the constant of the posture solve
-int rover_motion_bogie_fit(float out[36]) {
-    if (!out) return fail(nullptr, ROVER_E_INVALID, "motion_bogie_fit: null argument");
-    float inv[MOTION_WHEELS][MOTION_WHEELS];
-    motion_bogie_fit(inv);
-    memcpy(out, inv, sizeof inv);
-    return ROVER_OK;
-}
-
-// Host only: the constant of the motion model's plane fit
-int rover_motion_plane_fit(float out[18]) {
-    if (!out) return fail(nullptr, ROVER_E_INVALID, "motion_plane_fit: null argument");
-    float fit[3][MOTION_WHEELS];
-    motion_plane_fit(fit);
-    memcpy(out, fit, sizeof fit);
-    return ROVER_OK;
-}
-
-static bool track_shape_ok(int32_t E, int32_t W, int32_t K) {
-    return E >= 0 && W >= 1 && W <= ROVER_TRACK_MAX_WINDOW && K >= 0 && K <= ROVER_TRACK_MAX_COMPONENTS;
-}
-
-// Host only: what the descriptor's scratch must cover
-int rover_track_sizes(int32_t E, int32_t W, int32_t K, rover_track_sizes_out* out) {
-    if (!out) return fail(nullptr, ROVER_E_INVALID, "track_sizes: null argument");
-    if (!track_shape_ok(E, W, K))
-        return fail(nullptr, ROVER_E_INVALID, "track_sizes: E = %d is negative, W = %d is outside 1 .. %d or K = %d is outside 0 .. %d", E, W,
-                    ROVER_TRACK_MAX_WINDOW, K, ROVER_TRACK_MAX_COMPONENTS);
-    out->workgroup = TRACK_BLOCK;
-    out->n_partials = (int32_t)track_partials((uint32_t)E);
-    out->partial_bytes = (int64_t)track_partial_bytes();
-    out->finished_slots = (int64_t)out->n_partials * TRACK_BLOCK;
-    out->scratch_bytes = (int64_t)track_scratch_bytes((uint32_t)E);
-    return ROVER_OK;
-}
-
-// The descriptor is validated before the ctx is looked at, as for rover_motion_step
-int rover_episode_track(rover_ctx* c, const rover_track_desc* d, void* stream) {
-    if (!d) return fail(c, ROVER_E_INVALID, "episode_track: null descriptor");
-    if (!track_shape_ok(d->E, d->W, d->K))
-        return fail(c, ROVER_E_INVALID, "episode_track: E = %d is negative, W = %d is outside 1 .. %d or K = %d is outside 0 .. %d", d->E, d->W,
-                    ROVER_TRACK_MAX_WINDOW, d->K, ROVER_TRACK_MAX_COMPONENTS);
-    if (d->done_size != 1 && d->done_size != 8) return fail(c, ROVER_E_INVALID, "episode_track: done_size = %d is neither 1 nor 8", d->done_size);
-    for (int32_t k = 0; k < d->K; ++k)
-        if (d->comp_kind[k] != ROVER_TRACK_F32 && d->comp_kind[k] != ROVER_TRACK_I64)
-            return fail(c, ROVER_E_INVALID, "episode_track: comp_kind[%d] = %d is neither ROVER_TRACK_F32 nor ROVER_TRACK_I64", k, d->comp_kind[k]);
-    if (!d->ring_ret || !d->ring_len || !d->ring_count || !d->record)
-        return fail(c, ROVER_E_INVALID, "episode_track: ring_ret, ring_len, ring_count and record must be given");
-    if (d->E > 0) {
-        if (!d->rewards || !d->done || !d->cum_reward || !d->cum_steps || !d->scratch)
-            return fail(c, ROVER_E_INVALID, "episode_track: rewards, done, cum_reward, cum_steps and scratch must be given");
-        for (int32_t k = 0; k < d->K; ++k)
-            if (!d->comp[k]) return fail(c, ROVER_E_INVALID, "episode_track: comp[%d] is NULL (K = %d)", k, d->K);
-        if (((uintptr_t)d->scratch & 7u) != 0) return fail(c, ROVER_E_INVALID, "episode_track: scratch is not 8-byte aligned");
-        if (d->scratch_bytes < (int64_t)track_scratch_bytes((uint32_t)d->E))
-            return fail(c, ROVER_E_INVALID, "episode_track: scratch_bytes = %lld is below the %llu of rover_track_sizes", (long long)d->scratch_bytes,
-                        (unsigned long long)track_scratch_bytes((uint32_t)d->E));
-    }
-    if (!c) return fail(nullptr, ROVER_E_INVALID, "episode_track: null ctx");
-    USE_DEVICE(c);
-    TrackArgs a{};
-    a.rewards = d->rewards; a.done = d->done; a.done8 = d->done_size == 8;
-    a.E = (uint32_t)d->E; a.W = (uint32_t)d->W; a.K = (uint32_t)d->K;
-    for (int32_t k = 0; k < d->K; ++k) {
-        a.comp[k] = d->comp[k];
-        if (d->comp_kind[k] == ROVER_TRACK_I64) a.comp_i64 |= 1u << k;
-    }
-    a.cum_reward = d->cum_reward; a.cum_steps = d->cum_steps;
-    a.ring_ret = d->ring_ret; a.ring_len = d->ring_len; a.ring_count = d->ring_count;
-    a.record = d->record; a.scratch = d->scratch;
-    HIP_TRY(c, launch_track(a, (hipStream_t)stream));
     return ROVER_OK;
 }
 

@@ -1,4 +1,4 @@
-// rover_internal.h — structs shared by the kernels (rover_kernels.hip) and the C-ABI layer (rover_capi.cpp).
+// rover_internal.h — structs shared by the kernels (rover_kernels.hip) and the C-ABI layer (rover_capi*.cpp, through rover_ctx.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -4,7 +4,7 @@
 // A gather: one workgroup per MARS_TILE x MARS_TILE nodes (256 threads, one node each; neighbouring lanes on neighbouring columns).
 // A node starts at 0.0, adds every hill that covers it in index order — a loop over ALL hills with wave-uniform bounds, a hill whose
 // window misses the tile is skipped by the whole workgroup, g comes through L2 — and then every kept stamp that covers it in ascending
-// stamp order: the host lists the tile's stamps (mars_fill_lists in rover_capi.cpp, the code rover_mars_tiles runs), the workgroup stages
+// stamp order: the host lists the tile's stamps (mars_fill_lists in rover_capi_scene.cpp, the code rover_mars_tiles runs), the workgroup stages
 // MARS_CHUNK records at a time in LDS and every thread walks them in order (all lanes read the same record: an LDS broadcast).  Nothing
 // is scattered, so there are no atomics and the bits do not depend on the launch order.
 //

@@ -1,4 +1,4 @@
-"""numpy definitions of what the KNN map builder (rover_build_knn_map: csrc/rover_kernels.hip `knn_*_kernel`, csrc/rover_capi.cpp
+"""numpy definitions of what the KNN map builder (rover_build_knn_map: csrc/rover_kernels.hip `knn_*_kernel`, csrc/rover_capi_scene.cpp
 `build_knn_map_impl`) has to compute, every operation rounded to float32 as the kernels round it (the library is built with
 -ffp-contract=off, so a product and the sum it feeds round separately).
 
