@@ -182,7 +182,9 @@ ROVER_API int rover_compact_resets(rover_ctx *ctx, const int64_t *reset, int64_t
 ROVER_API int rover_quat_to_euler(rover_ctx *ctx, const float *quat, float *euler, int32_t n, void *stream);
 
 /* ---- reset / spawn / goal validation (rover.py:533-564, 588-608, 649-661) ---------------------------- */
-/* nearest_rock = min_s(|p - stone_s| - r_s)  (rover.py:536-538,655-658); xy [n][2] -> out [n] */
+/* nearest_rock = min_s(|p - stone_s| - r_s)  (rover.py:536-538,655-658); xy [n][2] -> out [n].  The minimum is torch.min's: +inf
+ * without stones, and NaN for every query as soon as one stone holds a NaN in x, y or r (the decisions made on it — spawn shift, goal
+ * validation, the step's stone mask — then find no collision anywhere, as `NaN <= thr` does in the reference). */
 ROVER_API int rover_clearance(rover_ctx *ctx, const float *xy, int32_t n, float *out, void *stream);
 /* avoid_pos_rock_collision rover.py:649-661: per env, x += 0.05 while clearance <= 1.4; pos [n][3] in place */
 ROVER_API int rover_shift_spawns(rover_ctx *ctx, float *pos3, int32_t n, int32_t max_iter, void *stream);

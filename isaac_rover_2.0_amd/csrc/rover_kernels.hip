@@ -821,7 +821,7 @@ __device__ __forceinline__ float clearance_tiles(const float* __restrict__ info7
             for (uint32_t i = 0; i < cnt; ++i) {
                 float dx = x - sx[i], dy = y - sy[i];
                 float d = sqrtf(dx * dx + dy * dy) - sr[i];                 // rover.py:536-537 / :655-656
-                best = (d < best) ? d : best;
+                best = (d < best || d != d) ? d : best;                    // torch.min (:538): a NaN stone makes the minimum NaN
             }
         }
     }
