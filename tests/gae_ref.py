@@ -155,6 +155,43 @@ def make_case(T, E, pattern="random", scale=1.0, seed=0, rate=0.02):
     return r, v, d, lv
 
 
+def nonfinite_case(T, E, seed=0):
+    """make_case("random") with two poisoned columns (T >= 5, E >= 8) -> (r, v, d, lv, cols).  Column cols["inf"]: a +Inf reward at
+    t = 3 whose done is set (g = 0 times a finite bootstrap: A = +Inf there), no done at t = 2 (A stays +Inf), a done at t = 1
+    (0 * Inf = NaN from there down), none at t = 0 and t = 4.  Column cols["nan"]: a NaN value at t = 2 and no done at all (A is NaN at
+    t = 2, where the value is subtracted, and below, where it is the bootstrap)."""
+    assert T >= 5 and E >= 8
+    r, v, d, lv = make_case(T, E, "random", seed=seed)
+    cols = {"inf": E // 3, "nan": E - 1}                                # the last env: at E = 131 073 the one lane of the scan's second trip
+    d[:, cols["inf"]] = False
+    d[[1, 3], cols["inf"]] = True
+    r[3, cols["inf"]] = np.inf
+    d[:, cols["nan"]] = False
+    v[2, cols["nan"]] = np.nan
+    return r, v, d, lv, cols
+
+
+def cleaned(r, v, d, lv, cols):
+    """The same rollout with the two non-finite entries of nonfinite_case made finite; every other element unchanged."""
+    r, v = r.copy(), v.copy()
+    r[3, cols["inf"]] = 1.0
+    v[2, cols["nan"]] = 0.5
+    return r, v, d, lv, cols
+
+
+def reference_nonfinite(rewards, values, dones, last_values, gamma=0.99, lam=0.95):
+    """reference() on inputs that hold Inf / NaN: IEEE arithmetic says where A and returns are +-Inf or NaN (0 * Inf = NaN); the
+    bounds of those columns mean nothing."""
+    with np.errstate(all="ignore"):
+        return reference(rewards, values, dones, last_values, gamma, lam)
+
+
+def nonfinite_pattern(a):
+    """0 finite, 1 +Inf, 2 -Inf, 3 NaN per element."""
+    a = (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(np.float64)
+    return np.select([np.isnan(a), a == np.inf, a == -np.inf], [3, 1, 2], 0)
+
+
 class Guarded:
     """A [T, E] array of ``dtype`` on ``device`` inside a trap-filled allocation with guard rows before and after and a time stride of
     ``E + pad`` elements (the pad columns hold the trap too).  layout "plain": .t is [T, E]; "skrl": .t is [T, E, 1] (pad must be 0 — the

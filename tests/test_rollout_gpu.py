@@ -1,10 +1,12 @@
 """rover_gae / Engine.gae / RolloutMemory / compute_gae on the GPU against the float64 reference and its derived bound (tests/gae_ref.py):
 every (T, E) of the list in all three normalize modes, contiguous / padded / [T, E, 1] layouts and five done patterns, inside trap-filled
-buffers; the moments, the sharding identity, determinism, aliasing, graph replay, argument errors and one end-to-end rollout."""
+buffers; the moments, the sharding identity, determinism, aliasing, graph replay, argument errors and one end-to-end rollout; env counts
+past the scan's grid cap (its tile loop's second and third trip), non-finite columns, a one-element and an all-zero rollout."""
 import ctypes as C
 import os
 import subprocess
 import sys
+import warnings
 
 import numpy as np
 import pytest
@@ -30,17 +32,17 @@ def eng():
 class Case:
     """One rollout on the device: NaN-trapped inputs, CANARY-trapped outputs, the float64 reference."""
 
-    def __init__(self, T, E, pattern="random", layout="plain", pad=0, seed=0, scale=1.0):
+    def __init__(self, T, E, pattern="random", layout="plain", pad=0, seed=0, scale=1.0, data=None):
         dev = "cuda:0"
         self.T, self.E = T, E
-        self.np_in = r, v, d, lv = G.make_case(T, E, pattern, scale=scale, seed=seed)
+        self.np_in = r, v, d, lv = G.make_case(T, E, pattern, scale=scale, seed=seed) if data is None else data
         mk = lambda data, dtype=torch.float32, fill=NAN: G.Guarded(T, E, dev, dtype, pad, layout, fill, data)
         self.rew, self.val, self.don = mk(r), mk(v), mk(d, torch.bool)
         lvb = torch.full((E + 64,), NAN, device=dev)
         lvb[:E] = torch.from_numpy(lv).to(dev)
         self.lv = lvb[:E]
         self.ret, self.adv = mk(None, fill=G.CANARY), mk(None, fill=G.CANARY)
-        self.ref = G.reference(r, v, d, lv)
+        self.ref = G.reference(r, v, d, lv) if data is None else G.reference_nonfinite(r, v, d, lv)
 
     def run(self, eng, **kw):
         eng.gae(self.rew.t, self.val.t, self.don.t, self.lv, self.ret.t, self.adv.t, **kw)
@@ -98,6 +100,92 @@ def test_kernel_against_reference(eng, T, E):
 @pytest.mark.parametrize("scale", [1e-3, 1e3])
 def test_kernel_against_reference_scaled(eng, scale):
     _all_modes(eng, Case(60, 512, "random", seed=5, scale=scale), f"scale {scale}")
+
+
+# GAE_BLOCK (csrc/rover_rollout.hip) and GAE_MAX_BLOCKS (csrc/rover_internal.h) as they stand in the source: the env counts below are
+# placed round their product.  A change of either constant must move the sizes with it.
+GAE_BLOCK, GAE_MAX_BLOCKS = 64, 2048
+GAE_CAP_ENVS = GAE_BLOCK * GAE_MAX_BLOCKS                             # 131 072 envs: the most one trip of the scan's tile loop covers
+
+
+@pytest.mark.parametrize("T", [1, 4, 5])                               # head only, one whole chunk only, head + chunk
+@pytest.mark.parametrize("E", [GAE_CAP_ENVS, GAE_CAP_ENVS + 1, 2 * GAE_CAP_ENVS + 65])
+def test_kernel_past_the_grid_cap(eng, T, E):
+    """The scan's tile loop at its cap, one env past it (block 0 takes a second tile of one lane), and three trips with a ragged tail."""
+    tiles = -(-E // GAE_BLOCK)
+    blocks = min(tiles, GAE_MAX_BLOCKS)
+    print(f"gae T={T} E={E}: {tiles} tiles on {blocks} blocks = {blocks} partials, {-(-tiles // blocks)} trip(s) of the tile loop, "
+          f"{-(-blocks // 256)} trip(s) of the finishing kernel's partial loop")
+    for layout, pad in LAYOUTS[:2]:
+        _all_modes(eng, Case(T, E, "random", layout, pad, seed=7 * T + E + pad), f"T={T} E={E} {layout}+{pad} random")
+
+
+def _ibits(t):
+    return t.contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize("E", [130, GAE_CAP_ENVS + 1])
+def test_nonfinite_columns_stay_in_their_columns(eng, E):
+    """A +Inf reward under a done flag in one column and a NaN value in another: every other column's returns and raw A are the bits of
+    a run on cleaned copies (the sharding identity rests on that); the two columns are +Inf / NaN exactly where the float64 recurrence
+    says (0 * Inf = NaN at the next done); the moments are NaN with the full count."""
+    T = 5
+    data = G.nonfinite_case(T, E, seed=E)
+    cols = data[4]
+    bad, clean = Case(T, E, pad=3, data=data[:4]), Case(T, E, pad=3, data=G.cleaned(*data)[:4])
+    s_bad, s_clean = _stats(), _stats()
+    ret_b, raw_b = bad.run(eng, normalize=False, stats_out=s_bad)
+    ret_c, raw_c = clean.run(eng, normalize=False, stats_out=s_clean)
+    G.check(ret_c, clean.ref["returns"], clean.ref["b_returns"], f"E={E} cleaned returns")
+    G.check(raw_c, clean.ref["A"], clean.ref["bA"], f"E={E} cleaned A")
+    other = torch.ones(E, dtype=torch.bool, device="cuda:0")
+    other[[cols["inf"], cols["nan"]]] = False
+    assert torch.equal(_ibits(ret_b[:, other]), _ibits(ret_c[:, other])), "a non-finite column changed another column's returns"
+    assert torch.equal(_ibits(raw_b[:, other]), _ibits(raw_c[:, other])), "a non-finite column changed another column's raw A"
+    for name, got, want in (("returns", ret_b, bad.ref["returns"]), ("A", raw_b, bad.ref["A"])):
+        pg, pw = G.nonfinite_pattern(got), G.nonfinite_pattern(want)
+        print(f"E={E} {name}: column {cols['inf']} (+Inf reward, done) {pg[:, cols['inf']].tolist()}, column {cols['nan']} (NaN value) "
+              f"{pg[:, cols['nan']].tolist()} (0 finite, 1 +Inf, 2 -Inf, 3 NaN; t = 0 .. {T - 1}); {int((pg != 0).sum())} non-finite of {pg.size}")
+        assert np.array_equal(pg, pw), f"{name}: non-finite elements are not where the float64 recurrence has them"
+    assert G.nonfinite_pattern(raw_b)[:, cols["inf"]].tolist() == [3, 3, 1, 1, 0] and G.nonfinite_pattern(raw_b)[:, cols["nan"]].tolist() == [3, 3, 3, 0, 0]
+    sb, sc = s_bad.cpu().numpy(), s_clean.cpu().numpy()
+    print(f"E={E}: stats_out {sb.tolist()}, cleaned {sc.tolist()}")
+    assert sb[0] == T * E and np.isnan(sb[1]) and np.isnan(sb[2]) and np.isfinite(sc).all() and sc[0] == T * E
+
+
+def test_one_element_rollout(eng):
+    """T = E = 1: returns and the raw A are right, the moments are (1, A, 0).  The unbiased std of one element is 0 / 0: NORMALIZE refuses
+    it (include/rover_step.h), and NORMALIZE_GIVEN with those moments — the one way to ask for it — gives NaN, as torch.std does."""
+    from isaac_rover_amd._lib import RoverError
+    c = Case(1, 1, "none", seed=2)
+    s = _stats()
+    ret, raw = c.run(eng, normalize=False, stats_out=s)
+    G.check(ret, c.ref["returns"], c.ref["b_returns"], "T=E=1 returns")
+    G.check(raw, c.ref["A"], c.ref["bA"], "T=E=1 A")
+    assert s.tolist() == [1.0, float(raw), 0.0]
+    with pytest.raises(RoverError, match=r"rover_gae failed \(-1\)"):
+        c.run(eng, normalize=True)
+    ret_g, adv_g = c.run(eng, normalize=True, stats_in=s)
+    print(f"T=E=1: returns {float(ret_g)}, A {float(raw)}, advantage normalised with (1, A, 0): {float(adv_g)}")
+    assert torch.equal(ret_g, ret) and bool(torch.isfinite(ret_g).all()) and bool(torch.isnan(adv_g).all())
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                             # torch warns about the degrees of freedom, and returns NaN too
+        assert bool(torch.isnan(torch.std(raw.reshape(-1).cpu())))
+
+
+def test_all_zero_rollout_normalizes_to_zero(eng):
+    """rewards = values = last_values = 0: the raw A is identically 0, std = 0, and (0 - 0) / (0 + 1e-8) is exactly 0, not NaN."""
+    T, E = 5, 130
+    _, _, d, _ = G.make_case(T, E, "random", seed=1, rate=0.2)
+    z = np.zeros((T, E), dtype=np.float32)
+    c = Case(T, E, pad=3, data=(z, z.copy(), d, np.zeros(E, dtype=np.float32)))
+    s = _stats()
+    ret, adv = c.run(eng, normalize=True, stats_out=s)
+    assert s.tolist() == [float(T * E), 0.0, 0.0]
+    assert bool((ret == 0).all()) and bool((adv == 0).all())
+    ret_g, adv_g = c.run(eng, normalize=True, stats_in=s)
+    assert bool((ret_g == 0).all()) and bool((adv_g == 0).all())
+    print(f"all-zero rollout T={T} E={E}: {int((adv == 0).sum())} of {adv.numel()} advantages are 0 (NORMALIZE), {int((adv_g == 0).sum())} (NORMALIZE_GIVEN)")
 
 
 @pytest.mark.parametrize("T,E", [(60, 512), (60, 130), (7, 65536)])
