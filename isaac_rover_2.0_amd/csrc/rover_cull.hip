@@ -5,7 +5,7 @@
 //            tasks/utils/camera/ray_casting.py:31-59 (the (ray, triangle) test), rock_detect.py:52-149 (same on the rocks map).
 //
 // The reference evaluates all K = 200 triangles of a ray's cell and takes the min of k-or-11.0; a ray meets 1-3 of them.
-// raycast_binned_kernel (rover_kernels.hip) evaluates them all too (134 VALU instructions per ray).  This kernel splits the
+// raycast_binned_kernel (rover_rays.hip) evaluates them all too (134 VALU instructions per ray).  This kernel splits the
 // work: PHASE 1 proves, per (ray, triangle), with 11-15 packed instructions per pair of triangles, that ray_casting.py:59
 // rejects the triangle (it then contributes the 11.0 sentinel and nothing else); PHASE 2 runs the exact arithmetic of
 // rover_raymath.h — the same code the other kernels run — on the few (ray, lane-pair) candidates phase 1 could not

@@ -1,5 +1,5 @@
 // rover_height.h — the heightfield lookup of get_pos_height (rover.py:588-608) as one device function, shared by the kernels that read
-// terrain heights: goals, sample_height and the ray preparation (rover_kernels.hip), the motion model (rover_motion.hip).
+// terrain heights: goals and sample_height (rover_reset.hip), the ray preparation (rover_rays.hip), the motion model (rover_motion.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

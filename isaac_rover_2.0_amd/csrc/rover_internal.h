@@ -1,4 +1,4 @@
-// rover_internal.h — structs shared by the kernels (rover_kernels.hip) and the C-ABI layer (rover_capi*.cpp, through rover_ctx.h).
+// rover_internal.h — structs shared by the kernels (rover_*.hip) and the C-ABI layer (rover_capi*.cpp, through rover_ctx.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -580,17 +580,53 @@ hipError_t launch_optim_step(const OptimArgs& a, hipStream_t s);          // two
 // blocks of bs threads (or items) that cover n: the launchers' grid sizes
 static inline uint32_t blocks_for(uint64_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
 
+// rover_rays.hip
 hipError_t launch_repack(const int32_t* map_idx, const int32_t* tris, const uint16_t* verts, uint64_t n_cells, uint32_t K,
                          uint32_t K8, uint32_t T, uint32_t V, uint16_t* table, hipStream_t s);
 hipError_t launch_prep(const PrepArgs& a, hipStream_t s);
 hipError_t launch_raycast(const RayRec* rays, uint32_t n_rays, const uint16_t* tab0, const uint16_t* tab1, uint32_t kp0,
                           uint32_t kp1, float* out, hipStream_t s);
-// packed: one-dword sort entries (bin_entries_packed(n_slots, low_bits): the plan's sort_entry_dwords == 1)
-hipError_t launch_bin_rays(const uint32_t* bins, uint32_t n_slots, uint32_t n_valid, uint32_t n_bins, uint32_t low_bits, bool packed,
-                           uint32_t* table, uint2* pairs, uint32_t* block_sums, uint32_t* sorted, bool hist_done, hipStream_t s);
 hipError_t launch_raycast_binned(const RayRec* rays, const uint32_t* sorted, uint32_t n_sorted, const uint16_t* tab0,
                                  const uint16_t* tab1, uint32_t kp0, uint32_t kp1, uint32_t run, bool fp16_math, uint32_t early_out, float* out,
                                  hipStream_t s);
+hipError_t launch_export_dist(const float* dist, const RayRec* rays, uint32_t E, uint32_t R8, uint32_t P, int precision, float* ray_dist,
+                              float* wheel, float* body, float* ray_src, float* hit_pt, hipStream_t s);
+hipError_t launch_export_rays(const RayRec* rays, const float* dist, uint32_t E, uint32_t R8, uint32_t P, float* src, float* dir, int32_t* cell,
+                              float* out_dist, hipStream_t s);
+hipError_t launch_import_rays(const float* src, const float* dir, uint32_t E, uint32_t R8, uint32_t P, const KnnDev& terrain, const KnnDev& rocks,
+                              uint32_t rocks_bin_offset, int precision, int cell_rcp, RayRec* rays, uint32_t* bin_out, hipStream_t s,
+                              uint32_t* not_unit = nullptr /* optional: counts the finite directions whose length is not 1 */);
+// rover_sort.hip
+// packed: one-dword sort entries (bin_entries_packed(n_slots, low_bits): the plan's sort_entry_dwords == 1)
+hipError_t launch_bin_rays(const uint32_t* bins, uint32_t n_slots, uint32_t n_valid, uint32_t n_bins, uint32_t low_bits, bool packed,
+                           uint32_t* table, uint2* pairs, uint32_t* block_sums, uint32_t* sorted, bool hist_done, hipStream_t s);
+hipError_t launch_scan_exclusive(uint32_t* data, uint32_t n, uint32_t* block_sums, hipStream_t s);
+// rover_obs.hip
+hipError_t launch_assemble_obs(const ObsArgs& a, hipStream_t s);
+hipError_t launch_obs_metrics(const ObsArgs& o, const MetricsArgs& m, hipStream_t s);     // both in one launch (rover_step)
+hipError_t launch_metrics_done(const MetricsArgs& a, hipStream_t s);
+hipError_t launch_compact(const int64_t* reset, uint32_t n, int64_t offset, uint32_t* block_cnt, bool counted, int64_t* ids,
+                          int32_t* count, hipStream_t s);
+hipError_t launch_eval_summary(const int64_t* eval_res, const int64_t* eval_step, uint32_t E, int64_t* summary8, hipStream_t s);
+hipError_t launch_eval_clear(int64_t* eval_res, int64_t* eval_step, uint32_t E, const int64_t* ids, uint32_t n, hipStream_t s);
+// rover_reset.hip
+hipError_t launch_quat_to_euler(const float* q, float* eul, uint32_t n, hipStream_t s);
+hipError_t launch_clearance(const float* info7, uint32_t S, const float* xy, uint32_t n, float* out, hipStream_t s);
+hipError_t launch_shift_spawns(const StoneGridDev& g, const float* info7, float* pos3, uint32_t n, int32_t max_iter, hipStream_t s);
+hipError_t launch_sample_height(const HeightDev& h, const float* xy, uint32_t n, float* out, hipStream_t s);
+hipError_t launch_generate_goals(const GoalArgs& a, uint32_t n_max, hipStream_t s);
+hipError_t launch_reset_envs(const ResetArgs& a, uint32_t n_max, hipStream_t s);
+hipError_t launch_pre_physics(const PrePhysicsArgs& a, hipStream_t s);
+hipError_t launch_ackermann(const float* lin, const float* ang, uint32_t n, float* steer, float* vel, hipStream_t s);
+// rover_knn.hip
+hipError_t launch_knn_centroids(const float* verts, const int32_t* tris, uint32_t T, uint32_t V, int ref, float* cx, float* cy,
+                                hipStream_t s);
+hipError_t launch_knn_bucket(const float* cx, const float* cy, uint32_t T, float ox, float oy, float inv_g, uint32_t nbx, uint32_t nby,
+                             uint32_t* cursor, uint32_t* items, int count, hipStream_t s);
+hipError_t launch_knn_select(const float* cx, const float* cy, const uint32_t* bucket_start, const uint32_t* items, float ox, float oy,
+                             float g, float span, uint32_t nbx, uint32_t nby, uint32_t X, uint32_t Y, float res, uint32_t K,
+                             const float* cell_x, const float* cell_y, int32_t* out, int32_t* overflow, hipStream_t s);
+// rover_cull.hip
 hipError_t launch_tri_centroids(const int32_t* tris, const uint16_t* verts, uint32_t T, uint32_t V, float2* out, hipStream_t s);
 // the tables of the culled and staged ray casts for one map (launch_cull_build, rover_cull.hip)
 struct CullBuildArgs {
@@ -627,35 +663,5 @@ hipError_t launch_lane_union(const CullBuildArgs& a, uint2* upair, hipStream_t s
 hipError_t launch_lane_pair_rows(const CullBuildArgs& a, const uint2* upair, uint32_t pp, int box, hipStream_t s);
 float cull_far_k2(int half, CullProofH ph);
 hipError_t launch_raycast_culled(CullArgs a, hipStream_t s);
-hipError_t launch_knn_centroids(const float* verts, const int32_t* tris, uint32_t T, uint32_t V, int ref, float* cx, float* cy,
-                                hipStream_t s);
-hipError_t launch_knn_bucket(const float* cx, const float* cy, uint32_t T, float ox, float oy, float inv_g, uint32_t nbx, uint32_t nby,
-                             uint32_t* cursor, uint32_t* items, int count, hipStream_t s);
-hipError_t launch_scan_exclusive(uint32_t* data, uint32_t n, uint32_t* block_sums, hipStream_t s);
-hipError_t launch_knn_select(const float* cx, const float* cy, const uint32_t* bucket_start, const uint32_t* items, float ox, float oy,
-                             float g, float span, uint32_t nbx, uint32_t nby, uint32_t X, uint32_t Y, float res, uint32_t K,
-                             const float* cell_x, const float* cell_y, int32_t* out, int32_t* overflow, hipStream_t s);
-hipError_t launch_assemble_obs(const ObsArgs& a, hipStream_t s);
-hipError_t launch_export_dist(const float* dist, const RayRec* rays, uint32_t E, uint32_t R8, uint32_t P, int precision, float* ray_dist,
-                              float* wheel, float* body, float* ray_src, float* hit_pt, hipStream_t s);
-hipError_t launch_export_rays(const RayRec* rays, const float* dist, uint32_t E, uint32_t R8, uint32_t P, float* src, float* dir, int32_t* cell,
-                              float* out_dist, hipStream_t s);
-hipError_t launch_import_rays(const float* src, const float* dir, uint32_t E, uint32_t R8, uint32_t P, const KnnDev& terrain, const KnnDev& rocks,
-                              uint32_t rocks_bin_offset, int precision, int cell_rcp, RayRec* rays, uint32_t* bin_out, hipStream_t s,
-                              uint32_t* not_unit = nullptr /* optional: counts the finite directions whose length is not 1 */);
-hipError_t launch_obs_metrics(const ObsArgs& o, const MetricsArgs& m, hipStream_t s);     // both in one launch (rover_step)
-hipError_t launch_metrics_done(const MetricsArgs& a, hipStream_t s);
-hipError_t launch_compact(const int64_t* reset, uint32_t n, int64_t offset, uint32_t* block_cnt, bool counted, int64_t* ids,
-                          int32_t* count, hipStream_t s);
-hipError_t launch_eval_summary(const int64_t* eval_res, const int64_t* eval_step, uint32_t E, int64_t* summary8, hipStream_t s);
-hipError_t launch_eval_clear(int64_t* eval_res, int64_t* eval_step, uint32_t E, const int64_t* ids, uint32_t n, hipStream_t s);
-hipError_t launch_quat_to_euler(const float* q, float* eul, uint32_t n, hipStream_t s);
-hipError_t launch_clearance(const float* info7, uint32_t S, const float* xy, uint32_t n, float* out, hipStream_t s);
-hipError_t launch_shift_spawns(const StoneGridDev& g, const float* info7, float* pos3, uint32_t n, int32_t max_iter, hipStream_t s);
-hipError_t launch_sample_height(const HeightDev& h, const float* xy, uint32_t n, float* out, hipStream_t s);
-hipError_t launch_generate_goals(const GoalArgs& a, uint32_t n_max, hipStream_t s);
-hipError_t launch_reset_envs(const ResetArgs& a, uint32_t n_max, hipStream_t s);
-hipError_t launch_pre_physics(const PrePhysicsArgs& a, hipStream_t s);
-hipError_t launch_ackermann(const float* lin, const float* ang, uint32_t n, float* steer, float* vel, hipStream_t s);
 
 }  // namespace rover

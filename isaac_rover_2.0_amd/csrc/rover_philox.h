@@ -1,5 +1,5 @@
 // rover_philox.h — Philox4x32-10 (Salmon et al. 2011, Random123's philox4x32 with 10 rounds): the ONE copy of the round function.
-// Users: the goal / reset-yaw draws (rover_kernels.hip, counter word 3 = 0), the policy's action noise (rover_mlp.hip, counter word
+// Users: the goal / reset-yaw draws (rover_reset.hip, counter word 3 = 0), the policy's action noise (rover_mlp.hip, counter word
 // 3 = 0x50000000 | component pair), the exteroception noise (rover_noise.hip, 0x60000000 | column pair and 0x70000000) and the host
 // entry rover_philox4x32 (rover_capi_learn.cpp), which pins the generator on the CPU.
 #pragma once

@@ -6,7 +6,7 @@
 
 namespace rover {
 
-// Integer helpers that depend on kernel constants: defined next to their kernels (rover_kernels.hip, rover_cull.hip), called by plan_step.
+// Integer helpers that depend on kernel constants: defined next to their kernels (rover_sort.hip, rover_cull.hip), called by plan_step.
 // true when launch_bin_rays sorts one-dword entries (low bin bits | slot id) for this many slots, false for (bin, slot) pairs
 bool bin_entries_packed(uint32_t n_slots, uint32_t low_bits);
 // true when prep_rays_kernel can count the sort's coarse buckets itself (PrepArgs::hist): a 64-env block's keys lie inside one tile of the sort

@@ -1,5 +1,5 @@
 // rover_raymath.h — the (ray, triangle) arithmetic of ray_casting.py:31-59 shared by the binned ray-cast kernels
-// (rover_kernels.hip) and the culled ray cast (rover_cull.hip).  One definition, so that every kernel produces the same bits.
+// (rover_rays.hip) and the culled ray cast (rover_cull.hip).  One definition, so that every kernel produces the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

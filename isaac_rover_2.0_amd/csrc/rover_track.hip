@@ -4,7 +4,7 @@
 // Two launches per env step, no atomics, no host read:
 //   track_update_kernel   ceil(E / 256) workgroups, one thread per env: step 1 of the definition; the workgroup's finished (return,
 //                         length) pairs are compacted in env order into its own 256 scratch slots (ballot + popcount, as the done
-//                         compaction in rover_kernels.hip), and its minima, maxima and sums go into one TrackPartial — xor butterflies
+//                         compaction in rover_obs.hip), and its minima, maxima and sums go into one TrackPartial — xor butterflies
 //                         inside a wave, then the four waves in wave order: a fixed tree
 //   track_merge_kernel    one workgroup: folds the partials (the f64 columns by 8 slices of workgroups in workgroup order, then the 8
 //                         slices in a fixed tree), scans the per-workgroup counts in chunks of 256 workgroups, copies the last

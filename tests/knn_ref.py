@@ -1,4 +1,4 @@
-"""numpy definitions of what the KNN map builder (rover_build_knn_map: csrc/rover_kernels.hip `knn_*_kernel`, csrc/rover_capi_scene.cpp
+"""numpy definitions of what the KNN map builder (rover_build_knn_map: csrc/rover_knn.hip `knn_*_kernel`, csrc/rover_capi_scene.cpp
 `build_knn_map_impl`) has to compute, every operation rounded to float32 as the kernels round it (the library is built with
 -ffp-contract=off, so a product and the sum it feeds round separately).
 
@@ -15,7 +15,7 @@ f32 = np.float32
 KNN_CAP = 8192                    # knn_select_kernel: keys a cell's search can hold
 SCAN_TILE = 2048                  # launch_scan_exclusive: counts per workgroup
 
-# The stop slack of the exact_f32 ranking — `KNN_STOP_SLACK` in csrc/rover_kernels.hip (knn_select_kernel, "lim = reach - (reach + span) *
+# The stop slack of the exact_f32 ranking — `KNN_STOP_SLACK` in csrc/rover_knn.hip (knn_select_kernel, "lim = reach - (reach + span) *
 # KNN_STOP_SLACK"), the one place besides this line where the value is written.  Derivation: DESIGN.md §4.6.
 STOP_SLACK = 2.0 ** -20
 

@@ -1,6 +1,6 @@
 """Float64 restatement of the reset path (rover.py:533-564, 649-661) and seeded case builders for its tests.  numpy only, no GPU.
 
-The restatement decides in float64 what the kernels of csrc/rover_kernels.hip decide in float32, so a case is only usable where the two
+The restatement decides in float64 what the kernels of csrc/rover_reset.hip decide in float32, so a case is only usable where the two
 cannot disagree: every builder rerolls an input whose decision margin |clearance - threshold| is below MARGIN.  MARGIN is 1e-3 m, a
 thousand times the ~1e-6 m that one ulp of the device's cosf / sinf moves a goal at radius 8 (and far above the f32 rounding of the
 clearance itself, ~1e-6 m at 10 m): after the reroll every compared decision is exact and no case has to be skipped."""

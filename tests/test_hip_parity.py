@@ -539,7 +539,7 @@ def _ray_sort_layouts(n):
 
 def test_fused_sort_histogram_survives_option_and_shape_changes():
     """With 37 + 26 rays prep_rays_kernel counts the sort's coarse buckets itself into a table that has to be all zero when a step starts
-    (bucket_sort_kernel clears it again; bin_hist_fused, rover_kernels.hip).  One engine through everything that changes the table's
+    (bucket_sort_kernel clears it again; bin_hist_fused, rover_sort.hip).  One engine through everything that changes the table's
     layout or who fills it — other poses every step, the sorted variants and the env-order one in turn, bin_low_bits 12 / 8 / default
     (other bucket counts in the same allocation), a ray set that keeps bucket_hist_kernel (120 + 26: R8 = 152) and back — against a fresh
     env-order engine each time."""

@@ -1,5 +1,5 @@
 """rover_build_knn_map against brute force (knn_ref.brute_force) at the edges of its bucketed ring search and of the three-level scan
-behind it: csrc/rover_kernels.hip `knn_*_kernel`, `launch_scan_exclusive`; csrc/rover_capi_scene.cpp `build_knn_map_impl`; DESIGN.md §4.6.
+behind it: csrc/rover_knn.hip `knn_*_kernel`, csrc/rover_sort.hip `launch_scan_exclusive`; csrc/rover_capi_scene.cpp `build_knn_map_impl`; DESIGN.md §4.6.
 
 Every case compares the whole [X, Y, K] map with assert_array_equal.  A wrong list is otherwise silent: the step and the oracle are fed
 the same built map.  Large meshes go with long thin maps, so that the brute force stays small.

@@ -1,4 +1,4 @@
-"""Property test (CPU, numpy) of the KNN map builder's ring search — `knn_select_kernel` in csrc/rover_kernels.hip, DESIGN.md §4.6.
+"""Property test (CPU, numpy) of the KNN map builder's ring search — `knn_select_kernel` in csrc/rover_knn.hip, DESIGN.md §4.6.
 
 The search of a cell stops at ring r when its K-th key is within a bound that no centroid outside ring r can undercut.  "Outside ring r"
 is decided by `knn_bucket` in float32 — a subtraction, a product with fl(1 / g), a floor — so a centroid can sit a few ulps NEARER than

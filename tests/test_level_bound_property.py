@@ -221,7 +221,7 @@ def test_test_a_on_cell_relative_fp16_records_implies_the_proofs_premise():
 
 # ---------------------------------------------------------------------------------------------------
 # Test (B) for a whole set (last sentence): the ray record carries qm = CONE_TAU |d_z| + |d_xy| (+ 2e-5, rounded UP to 16
-# bits: ray_cone_bound, rover_kernels.hip), a cell or a suffix q = min |N_z| / |N| over its triangles (rounded DOWN to 16 bits:
+# bits: ray_cone_bound, rover_rays.hip), a cell or a suffix q = min |N_z| / |N| over its triangles (rounded DOWN to 16 bits:
 # lane_build_kernel / idx4_build_kernel).  q16 >= rq must give |N . d| > (CONE_TAU - 1e-4) |N| for every triangle of the set (CONE_TAU for an exactly unit
 # d) — more than the 3e-3 that (B) with the stored normal's 1e-3 error needs.
 # ---------------------------------------------------------------------------------------------------

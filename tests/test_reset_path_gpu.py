@@ -1,4 +1,4 @@
-"""GPU: the reset path of csrc/rover_kernels.hip (clearance_kernel, collides_grid, shift_spawns_kernel, goals_draw_kernel,
+"""GPU: the reset path of csrc/rover_reset.hip (clearance_kernel, collides_grid of csrc/rover_stones.h, shift_spawns_kernel, goals_draw_kernel,
 goals_env0_kernel, reset_envs_kernel and the stone grid of rover_set_stones) at its own dispatch edges, against the float64 restatement
 and the seeded, decided cases of tests/reset_ref.py (checked on the CPU by tests/test_reset_path_host.py), the C oracle and the host
 Philox.  Two tolerances: the derived float32 bound of one clearance evaluation, and the project's 1e-5 (goal xy) / 1e-6 (yaw quaternion);
