@@ -16,6 +16,7 @@ values, rewards and terminated every step, and every N steps `compute_gae` (one 
 obs as `last_values`.
 """
 import argparse
+import math
 import os
 import sys
 import time
@@ -57,6 +58,18 @@ def main():
     ap.add_argument("--suspension", choices=("plane", "bogie"), default="plane",
                     help="with --sim terrain: plane fits a plane through the six wheel contacts; bogie solves the rocker-bogie posture, which keeps "
                          "all six wheels down and writes the three passive joints (uprightness penalty, wheel-ray origins)")
+    ap.add_argument("--drive", choices=("command", "wheels"), default="command",
+                    help="with --sim terrain: command moves the body by the policy's command itself; wheels (rover_motion_step_drive) lets the "
+                         "steering and drive joints follow Ackermann's targets at a limited rate and moves the body the way its six wheels roll")
+    ap.add_argument("--wheel-radius", type=float, default=0.2,
+                    help="--drive wheels: metres per radian of wheel turn; 0.2 is the length the reference's Ackermann divides by (the command's "
+                         "speed), 0.1 the asset's physical radius, which halves every speed as the reference's rover in PhysX does")
+    ap.add_argument("--steer-rate", type=float, default=math.inf,
+                    help="--drive wheels: the steering joints' speed limit in rad/s; inf = ideal.  The repository holds no actuator limits for "
+                         "the asset: a finite value such as 1.5 is this project's choice")
+    ap.add_argument("--wheel-accel", type=float, default=math.inf,
+                    help="--drive wheels: the drive joints' acceleration limit in rad/s^2; inf = ideal.  A finite value such as 20 is this "
+                         "project's choice")
     ap.add_argument("--track-interval", type=int, default=0,
                     help="every N steps print the episode statistics kept on the device (learning/tracking.py:EpisodeTracker, one "
                          "rover_episode_track call per step, one read per N steps): skrl's nine Reward / Episode tags, the interval's exact "
@@ -69,6 +82,8 @@ def main():
     args = ap.parse_args()
     if args.suspension != "plane" and args.sim != "terrain":
         ap.error("--suspension bogie needs --sim terrain")
+    if args.drive != "command" and args.sim != "terrain":
+        ap.error("--drive wheels needs --sim terrain")
     if args.track_interval < 0 or not 1 <= args.track_window <= 1024:
         ap.error("--track-interval N needs N >= 0, --track-window W needs W in 1 .. 1024")
     noisy = bool(args.obs_noise or args.obs_offset or args.obs_dropout)
@@ -81,7 +96,8 @@ def main():
 
     scene = assets.load_reference_assets(args.assets) if args.assets else assets.example_scene(args.scene, args.scene_seed)
     cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
-    env = vec_env.VecEnv(headless=True, sim=args.sim, suspension=args.suspension)
+    env = vec_env.VecEnv(headless=True, sim=args.sim, suspension=args.suspension, drive=args.drive, wheel_radius=args.wheel_radius,
+                         steer_rate=args.steer_rate, wheel_accel=args.wheel_accel)
     extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size
     g = torch.Generator().manual_seed(0)
     spawn = torch.zeros(args.envs, 3)
@@ -172,7 +188,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{args.steps} steps x {args.envs} envs in {dt:.2f} s = {args.steps * args.envs / dt:,.0f} env-steps/s "
-          f"(incl. {args.policy} policy + {'toy pose feeder' if args.sim == 'kinematic' else 'terrain-following motion model' + (', rocker-bogie posture' if args.suspension == 'bogie' else '')}); episodes finished: {episodes}; mean return {float(ret.mean()):.4f}")
+          f"(incl. {args.policy} policy + {'toy pose feeder' if args.sim == 'kinematic' else 'terrain-following motion model' + (', rocker-bogie posture' if args.suspension == 'bogie' else '') + (', wheel-level drive' if args.drive == 'wheels' else '')}); episodes finished: {episodes}; mean return {float(ret.mean()):.4f}")
     if hidden is not None:
         print(f"occlusion: {100.0 * float(hidden.float().mean()):.2f} % of the heightmap columns hidden at the last step")
     env.close()

@@ -14,6 +14,7 @@ update trains both scalers.  `--lr-scheduler kl` steps skrl's KLAdaptiveRL once 
 state_preprocessor, value_preprocessor}` after the last step (the scalers' entries under skrl's three keys), `--load PATH` resumes from it.
 """
 import argparse
+import math
 import os
 import sys
 import time
@@ -53,6 +54,18 @@ def main():
     ap.add_argument("--suspension", choices=("plane", "bogie"), default="plane",
                     help="with --sim terrain: plane fits a plane through the six wheel contacts; bogie solves the rocker-bogie posture, which keeps "
                          "all six wheels down and writes the three passive joints (uprightness penalty, wheel-ray origins)")
+    ap.add_argument("--drive", choices=("command", "wheels"), default="command",
+                    help="with --sim terrain: command moves the body by the policy's command itself; wheels (rover_motion_step_drive) lets the "
+                         "steering and drive joints follow Ackermann's targets at a limited rate and moves the body the way its six wheels roll")
+    ap.add_argument("--wheel-radius", type=float, default=0.2,
+                    help="--drive wheels: metres per radian of wheel turn; 0.2 is the length the reference's Ackermann divides by (the command's "
+                         "speed), 0.1 the asset's physical radius, which halves every speed as the reference's rover in PhysX does")
+    ap.add_argument("--steer-rate", type=float, default=math.inf,
+                    help="--drive wheels: the steering joints' speed limit in rad/s; inf = ideal.  The repository holds no actuator limits for "
+                         "the asset: a finite value such as 1.5 is this project's choice")
+    ap.add_argument("--wheel-accel", type=float, default=math.inf,
+                    help="--drive wheels: the drive joints' acceleration limit in rad/s^2; inf = ideal.  A finite value such as 20 is this "
+                         "project's choice")
     ap.add_argument("--track-interval", type=int, default=0,
                     help="every N steps print the episode statistics kept on the device (learning/tracking.py:EpisodeTracker, one "
                          "rover_episode_track call per step, one read per N steps): skrl's nine Reward / Episode tags, the interval's exact "
@@ -65,6 +78,8 @@ def main():
     args = ap.parse_args()
     if args.suspension != "plane" and args.sim != "terrain":
         ap.error("--suspension bogie needs --sim terrain")
+    if args.drive != "command" and args.sim != "terrain":
+        ap.error("--drive wheels needs --sim terrain")
     if args.track_interval < 0 or not 1 <= args.track_window <= 1024:
         ap.error("--track-interval N needs N >= 0, --track-window W needs W in 1 .. 1024")
     if args.rollouts < 1:
@@ -72,7 +87,8 @@ def main():
 
     scene = assets.load_reference_assets(args.assets) if args.assets else assets.example_scene(args.scene, args.scene_seed)
     cfg = config.SimConfig(num_envs=args.envs, device="cuda:0")
-    env = vec_env.VecEnv(headless=True, sim=args.sim, suspension=args.suspension)
+    env = vec_env.VecEnv(headless=True, sim=args.sim, suspension=args.suspension, drive=args.drive, wheel_radius=args.wheel_radius,
+                         steer_rate=args.steer_rate, wheel_accel=args.wheel_accel)
     extent = scene.terrain.map_indices.shape[0] * scene.terrain.cell_size
     g = torch.Generator().manual_seed(0)
     spawn = torch.zeros(args.envs, 3)

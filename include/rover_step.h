@@ -1180,6 +1180,57 @@ ROVER_API int rover_motion_step_bogie(rover_ctx *ctx, const rover_motion_desc *d
 /* Host only (no ctx, no device): the 36 floats of D, row-major (z_c's row, roll's, pitch's, j0's, j1's, j2's). */
 ROVER_API int rover_motion_bogie_fit(float out[36]);
 
+/* ---- wheel-level drive: the motion model's opt-in third mode (TerrainSim(drive="wheels")); composes with both postures ---------------- */
+/* The two modes above move the body by the policy's command itself and copy the joint targets into the joint state.  This mode closes
+ * the chain the reference closes in PhysX — action -> Ackermann (rover_pre_physics_step) -> joint drives -> wheels on the ground -> body
+ * motion — kinematically: the actuated joints follow their targets at a limited rate, and the body moves by the rigid motion that fits
+ * the six wheels' velocity vectors best.  lin, ang, cmd_stride, max_lin and max_ang of the descriptor are NOT read (NULL / 0 are fine):
+ * the joint targets are the command.  Again this project's own definition: f32, one rounding per written operation, one thread per env.
+ * Wheel layout and order as in rover_motion_step (FL FR ML MR RL RR; a_i = f_i forward, b_i = -r_i left).  Joint columns, as
+ * pre_physics_step writes them:   steering angle d_i: FL 4, FR 6, RL 7, RR 8 (ML, MR do not steer: d = 0);   wheel speed o_i: FL 9, FR 10,
+ * ML 3, MR 5, RL 11, RR 12.  Steering angles are taken in Ackermann's own convention, counter-clockwise from body forward, exactly as
+ * written into the targets — no sign flips.  (rock_detect.py:248 reads RL as -j7 when it places the wheel rays; that is the rays'
+ * business and stays as it is.)
+ * Each of `substeps` sub-steps of length dt:
+ *   1. actuators.  step_s = steer_rate dt and step_w = wheel_accel dt, each computed once.  Every steered column, with D = target - d:
+ *      d <- |D| > step_s ? d + copysign(step_s, D) : target;   every drive column the same with step_w on the joint velocity.  A state
+ *      lands on its target exactly and never passes it (|D| > step and rounding is monotone); +inf rates are ideal actuators; a NaN
+ *      target fails the comparison and is taken as it is, so it reaches that env's pose and no other's.  The state is the caller's
+ *      joint_pos13 / joint_vel13: there is no hidden state, the call is stateless.
+ *   2. wheel velocity vectors:  s_i = wheel_radius o_i;   t_2i = s_i cos d_i,  t_2i+1 = s_i sin d_i for the four steered wheels,
+ *      t_2i = s_i,  t_2i+1 = 0 for ML and MR.
+ *   3. body twist.  A rigid motion (vx, vy, w) gives wheel i the velocity u_i = (vx - w b_i, vy + w a_i); minimising sum |u_i - t_i|^2 is
+ *      linear:  (vx, vy, w) = P t,  P [3][12] = pinv(M),  M's rows (1, 0, -b_i), (0, 1, a_i)  (condition number 1.87), computed in double
+ *      on the host, each entry rounded to f32 once (rover_motion_drive_fit); each row is summed from column 0 upwards, all 12 columns.
+ *   4. slip (optional output slip [E]), of the LAST sub-step:  q_i = (u_ix - t_2i)^2 + (u_iy - t_2i+1)^2 with u_ix = vx + w r_i and
+ *      u_iy = vy + w f_i,  slip = sqrt((q_0 + q_1 + ... + q_5) / 6) in m/s: 0 when the wheels agree with one rigid motion, positive while
+ *      the steering lags.  Slip is reported only; it does not change the motion.
+ *   5. yaw0 as step 2 of rover_motion_step;   yaw1 = yaw0 + w dt,  c = cos(yaw1),  s = sin(yaw1);
+ *      x1 = x + ((vx c) - (vy s)) dt,   y1 = y + ((vx s) + (vy c)) dt.   No turn-on-the-spot rule here: Ackermann applied it to the targets.
+ *   6. posture: steps 4-7 of rover_motion_step (bogie params NULL) or steps 4-7 of rover_motion_step_bogie, by the same device functions:
+ *      the same (x1, y1, yaw1) gives the bits those modes give.
+ * After the last sub-step the steered columns of joint_pos13 and the drive columns of joint_vel13 hold the new states; every other column
+ * follows the posture mode's rule (the targets' copy; with the bogie, columns 0-2 of joint_pos13 are the last solve's clamped angles).
+ * `substeps` = n gives the bits of n calls with `substeps` = 1.  A reset needs nothing new: rover_reset_envs zeroes a reset env's joint
+ * state, so a respawned rover starts at rest and ramps up.
+ * wheel_radius is the length that turns rad/s into m/s.  kinematics.py:18,61 divides the ground speed by wheel_diameter = 0.2, so 0.2 (the
+ * binding's default) moves the rover as far as the command modes do; the asset's physical radius is 0.1, which halves every speed, as
+ * the reference's rover in PhysX does.  The repository holds no actuator limits for the asset: the binding's rates default to +inf.
+ * One launch of ceil(E / 256) workgroups (csrc/rover_motion.hip); a workgroup stages its rows of the four joint arrays in LDS (53 248
+ * bytes), no atomics.  Enqueues only, allocates nothing, capturable.  E = 0: ROVER_OK, no launch.  ROVER_E_INVALID before any launch, all
+ * decided before the ctx is looked at: a NULL descriptor; E < 0; substeps < 1; dt not finite or not > 0; a NULL pos3 or quat4 with
+ * E > 0; a joint quadruple given only in part, or not at all with E > 0; NULL drive params; wheel_radius not finite or not > 0; steer_rate
+ * or wheel_accel NaN or not > 0 (+inf is valid); bogie params given with iters outside 1 .. ROVER_BOGIE_MAX_ITERS or max_bogie not finite
+ * or not > 0.  ROVER_E_STATE: no heightfield.  The two modes above and their structs are unchanged by this one. */
+typedef struct {
+    float wheel_radius, steer_rate, wheel_accel;   /* m (finite, > 0), rad/s and rad/s^2 (> 0, +inf: ideal)                         */
+    float *slip;                                   /* optional [E]: the last sub-step's slip, m/s                                  */
+} rover_drive_params;
+ROVER_API int rover_motion_step_drive(rover_ctx *ctx, const rover_motion_desc *d, const rover_drive_params *p,
+                                      const rover_bogie_params *bogie /* NULL: the plane's posture */, void *stream);
+/* Host only (no ctx, no device): the 36 floats of P, row-major (vx's row, vy's, w's); column 2i is wheel i's x component, 2i+1 its y. */
+ROVER_API int rover_motion_drive_fit(float out[36]);
+
 /* ---- episode statistics on the device (learning/tracking.py:EpisodeTracker) ----------------------------------------------------------- */
 /* What skrl's agent writes every write_interval steps (instantaneous reward, total reward and length of the episodes in a deque of the
  * last W, each as max / min / mean), the exact totals of a reporting interval and the sums of up to 16 reward components, kept on the

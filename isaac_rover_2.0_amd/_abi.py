@@ -159,7 +159,12 @@ class BogieParams(C.Structure):
     _fields_ = [("iters", C.c_int32), ("max_bogie", C.c_float)]
 
 
+class DriveParams(C.Structure):
+    _fields_ = [("wheel_radius", C.c_float), ("steer_rate", C.c_float), ("wheel_accel", C.c_float), ("slip", C.c_void_p)]
+
+
 SUSPENSIONS = ("plane", "bogie")
+DRIVES = ("command", "wheels")
 MARS_MAX_SIDE, MARS_MAX_CLASSES, MARS_MAX_TABLE, MARS_TILE = 131072, 16, 129, 16
 
 
@@ -216,7 +221,8 @@ TYPEDEFS = {
     "rover_gae_desc": GaeDesc, "rover_ppo_loss_desc": PpoLossDesc, "rover_optim_chunk": OptimChunk, "rover_optim_desc": OptimDesc,
     "rover_optim_step_desc": OptimStepDesc, "rover_obs_noise_desc": ObsNoiseDesc, "rover_occlusion_cfg": OcclusionCfg,
     "rover_obs_occlusion_desc": ObsOcclusionDesc, "rover_scaler_plan_desc": ScalerPlanDesc, "rover_scaler_update_desc": ScalerUpdateDesc,
-    "rover_scaler_apply_desc": ScalerApplyDesc, "rover_motion_desc": MotionDesc, "rover_bogie_params": BogieParams, "rover_mars_desc": MarsDesc,
+    "rover_scaler_apply_desc": ScalerApplyDesc, "rover_motion_desc": MotionDesc, "rover_bogie_params": BogieParams,
+    "rover_drive_params": DriveParams, "rover_mars_desc": MarsDesc,
     "rover_track_record": TrackRecord, "rover_track_desc": TrackDesc, "rover_track_sizes_out": TrackSizes, "rover_reset_io": ResetIO,
     "rover_profile": Profile,
 }
@@ -314,6 +320,8 @@ SYMBOLS = {
     "rover_motion_plane_fit": (C.c_int, [_P]),
     "rover_motion_step_bogie": (C.c_int, [_P, C.POINTER(MotionDesc), C.POINTER(BogieParams), _P]),
     "rover_motion_bogie_fit": (C.c_int, [_P]),
+    "rover_motion_step_drive": (C.c_int, [_P, C.POINTER(MotionDesc), C.POINTER(DriveParams), C.POINTER(BogieParams), _P]),
+    "rover_motion_drive_fit": (C.c_int, [_P]),
     "rover_episode_track": (C.c_int, [_P, C.POINTER(TrackDesc), _P]),
     "rover_track_sizes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(TrackSizes)]),
     "rover_set_evaluation": (C.c_int, [_P, C.c_int32]),

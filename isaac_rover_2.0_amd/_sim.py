@@ -1,11 +1,12 @@
 """The entry points of rover_capi_sim.cpp: observation noise, line-of-sight occlusion, the running scalers, the motion model and the
 episode statistics."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
 
-from ._abi import (_FAKE, SUSPENSIONS, TRACK_F32, TRACK_I64, TRACK_MAX_COMPONENTS, TRACK_MAX_WINDOW, BogieParams, EngineBase, MotionDesc,
+from ._abi import (_FAKE, DRIVES, SUSPENSIONS, TRACK_F32, TRACK_I64, TRACK_MAX_COMPONENTS, TRACK_MAX_WINDOW, BogieParams, DriveParams, EngineBase, MotionDesc,
                    ObsNoiseDesc, ObsOcclusionDesc, OcclusionCfg, RoverError, ScalerApplyDesc, ScalerPlanDesc, ScalerUpdateDesc, TrackDesc,
                    TrackRecord, TrackSizes, _host, _rows, as_dict, host_call)
 
@@ -101,6 +102,14 @@ def motion_bogie_fit():
     wheel-origin heights by (z_c, roll, pitch, j0, j1, j2) -> a float32 array.  Host only."""
     out = np.empty((6, 6), dtype=np.float32)
     host_call("rover_motion_bogie_fit", out.ctypes.data)
+    return out
+
+
+def motion_drive_fit():
+    """rover_motion_drive_fit: the constant P [3, 12] of the wheel-level drive mode, (vx, vy, w) = P t over the six wheels' velocity
+    vectors (FL, FR, ML, MR, RL, RR; column 2i is wheel i's body-x component, 2i + 1 its body-y) -> a float32 array.  Host only."""
+    out = np.empty((3, 12), dtype=np.float32)
+    host_call("rover_motion_drive_fit", out.ctypes.data)
     return out
 
 
@@ -249,7 +258,8 @@ class SimEngine(EngineBase):
         return out
 
     def motion_step(self, pos, quat, lin, ang, *, dt, substeps=1, max_lin=1.0, max_ang=1.0, ride_height=0.3, joints=None,
-                    suspension="plane", iters=4, max_bogie=0.6):
+                    suspension="plane", iters=4, max_bogie=0.6, drive="command", wheel_radius=0.2, steer_rate=math.inf, wheel_accel=math.inf,
+                    slip=None):
         """``substeps`` sub-steps of length ``dt`` of the terrain-following motion model on ``pos`` [e, 3] and ``quat`` [e, 4] (w, x, y, z),
         IN PLACE (rover_motion_step, one launch; needs set_heightfield): the commands ``lin`` / ``ang`` [e] scaled by ``max_lin`` /
         ``max_ang`` move the body, the six wheel contacts' terrain heights give z, roll and pitch.  ``lin`` and ``ang`` may be one column
@@ -257,21 +267,34 @@ class SimEngine(EngineBase):
         joint_pos, joint_vel), each [e, 13] — after the last sub-step the state becomes the targets.
         ``suspension="bogie"`` (rover_motion_step_bogie) solves the rocker-bogie posture instead of fitting a plane: ``iters`` chord
         iterations put all six wheels on the ground, and the three passive joint angles, clamped to +-``max_bogie`` rad, go to columns
-        0-2 of joint_pos.  ``iters`` and ``max_bogie`` are not read with ``suspension="plane"``."""
+        0-2 of joint_pos.  ``iters`` and ``max_bogie`` are not read with ``suspension="plane"``.
+        ``drive="wheels"`` (rover_motion_step_drive; either suspension) moves the body by its wheels instead of by the command: the
+        steering angles and wheel speeds of joint_pos / joint_vel follow their targets by at most ``steer_rate`` rad/s and ``wheel_accel``
+        rad/s^2 (``inf``, the default: at once), and the body takes the rigid motion that fits the six wheel velocity vectors, rolling on
+        ``wheel_radius`` m, best.  ``joints`` must be given; ``lin``, ``ang``, ``max_lin`` and ``max_ang`` are not read and ``lin`` / ``ang``
+        may be None.  ``slip``: None, or a float32 vector [e] that receives the last sub-step's wheel slip in m/s.  ``wheel_radius`` = 0.2
+        is the length the reference's Ackermann divides by, so a forward command covers the distance it covers with ``drive="command"``;
+        0.1 is the asset's physical radius and halves every speed, as the reference's rover in PhysX does.  ``drive="command"``, the
+        default, is the behaviour without these arguments, which it does not read."""
         what = "motion_step"
         if suspension not in SUSPENSIONS:
             raise RoverError(f"{what}: suspension must be one of {SUSPENSIONS}, not {suspension!r}")
+        if drive not in DRIVES:
+            raise RoverError(f"{what}: drive must be one of {DRIVES}, not {drive!r}")
+        wheels = drive == "wheels"
         e = pos.shape[0] if pos is not None and pos.dim() == 2 else -1
         self._chk(pos, (e, 3), torch.float32, "pos")
         self._chk(quat, (e, 4), torch.float32, "quat")
         if pos is None or quat is None or e < 0:
             raise RoverError(f"{what}: pos [e, 3] and quat [e, 4] must be given")
-        for t, name in ((lin, "lin"), (ang, "ang")):
-            if t is None or not t.is_cuda or t.device != self.device or t.dtype != torch.float32 or tuple(t.shape) != (e,):
-                raise RoverError(f"{what}: {name} must be a float32 vector [{e}] on {self.device}")
-        stride = 1 if e <= 1 else lin.stride(0)
-        if e > 1 and (stride < 1 or ang.stride(0) != stride):
-            raise RoverError(f"{what}: lin and ang must have the same positive stride (got {lin.stride(0)} and {ang.stride(0)})")
+        stride = 1
+        if not wheels:
+            for t, name in ((lin, "lin"), (ang, "ang")):
+                if t is None or not t.is_cuda or t.device != self.device or t.dtype != torch.float32 or tuple(t.shape) != (e,):
+                    raise RoverError(f"{what}: {name} must be a float32 vector [{e}] on {self.device}")
+            stride = 1 if e <= 1 else lin.stride(0)
+            if e > 1 and (stride < 1 or ang.stride(0) != stride):
+                raise RoverError(f"{what}: lin and ang must have the same positive stride (got {lin.stride(0)} and {ang.stride(0)})")
         jp = [None] * 4
         if joints is not None:
             if len(joints) != 4:
@@ -281,6 +304,16 @@ class SimEngine(EngineBase):
                     raise RoverError(f"{what}: {name} is missing")
                 self._chk(t, (e, 13), torch.float32, name)
             jp = [t.data_ptr() for t in joints]
+        bogie = BogieParams(int(iters), float(max_bogie)) if suspension == "bogie" else None
+        if wheels:
+            if joints is None:
+                raise RoverError(f"{what}: drive='wheels' needs joints: the joint state is what it drives")
+            if slip is not None:
+                self._chk(slip, (e,), torch.float32, "slip")
+            desc = motion_desc(e, pos.data_ptr(), quat.data_ptr(), None, None, 0, substeps, dt, 0.0, 0.0, ride_height, *jp)
+            params = DriveParams(float(wheel_radius), float(steer_rate), float(wheel_accel), None if slip is None else slip.data_ptr())
+            self._call("rover_motion_step_drive", C.byref(desc), C.byref(params), None if bogie is None else C.byref(bogie))
+            return
         desc = motion_desc(e, pos.data_ptr(), quat.data_ptr(), lin.data_ptr(), ang.data_ptr(), stride, substeps, dt, max_lin, max_ang, ride_height, *jp)
         if suspension == "bogie":
             self._call("rover_motion_step_bogie", C.byref(desc), C.byref(BogieParams(int(iters), float(max_bogie))))

@@ -215,13 +215,22 @@ int rover_scaler_apply(rover_ctx* c, const rover_scaler_apply_desc* d, void* str
     return ROVER_OK;
 }
 
-// The checks that rover_motion_step and rover_motion_step_bogie share, in two parts: the descriptor's own, which need no ctx ...
-static int motion_check_desc(rover_ctx* c, const rover_motion_desc* d, const char* what) {
+// The checks that the three motion entry points share, in two parts: the descriptor's own, which need no ctx ...  `commands`: the mode
+// reads lin, ang and cmd_stride (rover_motion_step_drive does not)
+static int motion_check_desc(rover_ctx* c, const rover_motion_desc* d, const char* what, bool commands = true) {
     if (!d) return fail(c, ROVER_E_INVALID, "%s: null descriptor", what);
-    if (d->E < 0 || d->substeps < 1 || d->cmd_stride < 1)
-        return fail(c, ROVER_E_INVALID, "%s: E = %d is negative, substeps = %d or cmd_stride = %d is below 1", what, d->E, d->substeps, d->cmd_stride);
+    if (commands) {
+        if (d->E < 0 || d->substeps < 1 || d->cmd_stride < 1)
+            return fail(c, ROVER_E_INVALID, "%s: E = %d is negative, substeps = %d or cmd_stride = %d is below 1", what, d->E, d->substeps, d->cmd_stride);
+    } else if (d->E < 0 || d->substeps < 1) {
+        return fail(c, ROVER_E_INVALID, "%s: E = %d is negative or substeps = %d is below 1", what, d->E, d->substeps);
+    }
     if (!std::isfinite(d->dt) || !(d->dt > 0.0f)) return fail(c, ROVER_E_INVALID, "%s: dt = %g is not finite or not > 0", what, (double)d->dt);
-    if (d->E > 0 && (!d->pos3 || !d->quat4 || !d->lin || !d->ang)) return fail(c, ROVER_E_INVALID, "%s: pos3, quat4, lin and ang must be given", what);
+    if (commands) {
+        if (d->E > 0 && (!d->pos3 || !d->quat4 || !d->lin || !d->ang)) return fail(c, ROVER_E_INVALID, "%s: pos3, quat4, lin and ang must be given", what);
+    } else if (d->E > 0 && (!d->pos3 || !d->quat4)) {
+        return fail(c, ROVER_E_INVALID, "%s: pos3 and quat4 must be given", what);
+    }
     const int n_joint = (d->joint_pos_targets13 != nullptr) + (d->joint_vel_targets13 != nullptr) + (d->joint_pos13 != nullptr) + (d->joint_vel13 != nullptr);
     if (n_joint != 0 && n_joint != 4)
         return fail(c, ROVER_E_INVALID, "%s: joint_pos_targets13, joint_vel_targets13, joint_pos13 and joint_vel13 go together (%d of 4 given)", what, n_joint);
@@ -254,20 +263,58 @@ int rover_motion_step(rover_ctx* c, const rover_motion_desc* d, void* stream) {
     return ROVER_OK;
 }
 
+static int bogie_check_params(rover_ctx* c, const rover_bogie_params* p, const char* what) {
+    if (p->iters < 1 || p->iters > ROVER_BOGIE_MAX_ITERS)
+        return fail(c, ROVER_E_INVALID, "%s: iters = %d is outside 1 .. %d", what, p->iters, ROVER_BOGIE_MAX_ITERS);
+    if (!std::isfinite(p->max_bogie) || !(p->max_bogie > 0.0f))
+        return fail(c, ROVER_E_INVALID, "%s: max_bogie = %g is not finite or not > 0", what, (double)p->max_bogie);
+    return ROVER_OK;
+}
+
 // The rocker-bogie posture mode: rover_motion_step's refusals and the two parameters', all before the ctx is looked at
 int rover_motion_step_bogie(rover_ctx* c, const rover_motion_desc* d, const rover_bogie_params* p, void* stream) {
     const char* what = "motion_step_bogie";
     if (int e = motion_check_desc(c, d, what)) return e;
     if (!p) return fail(c, ROVER_E_INVALID, "%s: null parameters", what);
-    if (p->iters < 1 || p->iters > ROVER_BOGIE_MAX_ITERS)
-        return fail(c, ROVER_E_INVALID, "%s: iters = %d is outside 1 .. %d", what, p->iters, ROVER_BOGIE_MAX_ITERS);
-    if (!std::isfinite(p->max_bogie) || !(p->max_bogie > 0.0f))
-        return fail(c, ROVER_E_INVALID, "%s: max_bogie = %g is not finite or not > 0", what, (double)p->max_bogie);
+    if (int e = bogie_check_params(c, p, what)) return e;
     MotionArgs a{};
     if (int e = motion_check_ctx(c, d, what, a)) return e;
     if (d->E == 0) return ROVER_OK;
     USE_DEVICE(c);
     HIP_TRY(c, launch_motion_bogie(a, p->iters, p->max_bogie, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+// The wheel-level drive mode: the refusals of the other two modes that still apply (the commands are not read), the drive parameters'
+// and, where given, the bogie parameters', all before the ctx is looked at
+int rover_motion_step_drive(rover_ctx* c, const rover_motion_desc* d, const rover_drive_params* p, const rover_bogie_params* b, void* stream) {
+    const char* what = "motion_step_drive";
+    if (int e = motion_check_desc(c, d, what, false)) return e;
+    if (d->E > 0 && !d->joint_pos13)           // given in part is refused above
+        return fail(c, ROVER_E_INVALID, "%s: joint_pos_targets13, joint_vel_targets13, joint_pos13 and joint_vel13 must be given", what);
+    if (!p) return fail(c, ROVER_E_INVALID, "%s: null parameters", what);
+    if (!std::isfinite(p->wheel_radius) || !(p->wheel_radius > 0.0f))
+        return fail(c, ROVER_E_INVALID, "%s: wheel_radius = %g is not finite or not > 0", what, (double)p->wheel_radius);
+    if (!(p->steer_rate > 0.0f) || !(p->wheel_accel > 0.0f))
+        return fail(c, ROVER_E_INVALID, "%s: steer_rate = %g or wheel_accel = %g is NaN or not > 0", what, (double)p->steer_rate, (double)p->wheel_accel);
+    if (b)
+        if (int e = bogie_check_params(c, b, what)) return e;
+    MotionArgs a{};
+    if (int e = motion_check_ctx(c, d, what, a)) return e;
+    if (d->E == 0) return ROVER_OK;
+    USE_DEVICE(c);
+    DriveArgs g{p->wheel_radius, p->steer_rate, p->wheel_accel, p->slip, b != nullptr, b ? b->iters : 0, b ? b->max_bogie : 0.0f};
+    if (!b) motion_plane_fit(a.fit);
+    HIP_TRY(c, launch_motion_drive(a, g, (hipStream_t)stream));
+    return ROVER_OK;
+}
+
+// Host only: the constant of the drive mode's twist fit
+int rover_motion_drive_fit(float out[36]) {
+    if (!out) return fail(nullptr, ROVER_E_INVALID, "motion_drive_fit: null argument");
+    float fit[3][2 * MOTION_WHEELS];
+    motion_drive_fit(fit);
+    memcpy(out, fit, sizeof fit);
     return ROVER_OK;
 }
 

@@ -419,6 +419,18 @@ hipError_t launch_motion(const MotionArgs& a, hipStream_t s);
 // the constant inverse of the Jacobian at rest, the joint angles clamped to +-max_bogie into columns 0-2 of joint_pos13.
 void motion_bogie_fit(float out[MOTION_WHEELS][MOTION_WHEELS]);      // host, double arithmetic rounded to f32 once: inv(dF/du at u = 0)
 hipError_t launch_motion_bogie(const MotionArgs& a, int32_t iters, float max_bogie, hipStream_t s);
+// The wheel-level drive mode (rover_motion_step_drive, validated): the same arguments — the commands and their scales are not read, the
+// joint quadruple is always given —, rate-limited actuators on the joint state, the body twist fitted to the six wheel velocity vectors,
+// and the posture of the plane (bogie = false: fit is read) or of the bogie solve (iters, max_bogie as above).
+struct DriveArgs {
+    float wheel_radius, steer_rate, wheel_accel;
+    float* slip;                           // [E] or NULL
+    bool bogie;
+    int32_t iters;
+    float max_bogie;
+};
+void motion_drive_fit(float out[3][2 * MOTION_WHEELS]);   // host, double arithmetic rounded to f32 once: pinv of the rigid-motion matrix
+hipError_t launch_motion_drive(const MotionArgs& a, const DriveArgs& d, hipStream_t s);
 
 // Episode statistics (rover_episode_track of the C ABI, validated; rover_track.hip): one env step's rewards, done flags and component
 // columns folded into the per-env state, the window ring and the interval record; the definition is in include/rover_step.h.

@@ -10,6 +10,8 @@ PhysX is replaced by ``KinematicSim``: a toy unicycle integrator that moves each
 which also tilts the body with the ground under its six wheels, obeys Ackermann's turn-on-the-spot rule and writes the joint state.
 ``VecEnv(sim="terrain", suspension="bogie")`` runs its rocker-bogie posture mode: all six wheels on the ground, the three
 passive suspension joints in the joint state, where the uprightness penalty and the wheel rays read them.
+``VecEnv(sim="terrain", drive="wheels")`` runs its wheel-level drive mode, with either suspension: the steering and
+drive joints follow Ackermann's targets at a limited rate, and the body moves the way its six wheels roll.
 """
 from __future__ import annotations
 
@@ -47,14 +49,23 @@ class TerrainSim:
     on the task's engine and heightfield, and the joint state follows the joint targets (ideal actuators).  ``advance(n)`` folds ``n``
     sub-steps of length ``dt`` into one launch; ``step`` is ``advance(1)``.  ``suspension="bogie"`` solves the rocker-bogie posture
     (``iters`` chord iterations, joints clamped to +-``max_bogie`` rad) and writes the passive joints into columns 0-2 of the joint
-    positions; ``"plane"``, the default, fits a plane and leaves them at the targets' 0."""
+    positions; ``"plane"``, the default, fits a plane and leaves them at the targets' 0.  ``drive="wheels"`` moves the body by the
+    wheels instead of by the command: the steering angles and wheel speeds of the joint state follow their targets by at most
+    ``steer_rate`` rad/s and ``wheel_accel`` rad/s^2 (``inf``: ideal actuators), and the body takes the rigid motion that fits the six
+    wheels, rolling on ``wheel_radius`` m, best (0.2 is the length the reference's Ackermann divides by; 0.1, the asset's physical
+    radius, halves every speed); ``last_slip`` then holds the wheel slip of the last sub-step in m/s.  ``"command"`` is the default."""
 
     def __init__(self, task, dt: float = 0.05, max_lin: float = 1.0, max_ang: float = 1.0, ride_height: float = 0.3,
-                 suspension: str = "plane", iters: int = 4, max_bogie: float = 0.6):
+                 suspension: str = "plane", iters: int = 4, max_bogie: float = 0.6, drive: str = "command", wheel_radius: float = 0.2,
+                 steer_rate: float = math.inf, wheel_accel: float = math.inf):
         if suspension not in SUSPENSIONS:
             raise ValueError(f"suspension must be one of {SUSPENSIONS}, not {suspension!r}")
+        if drive not in DRIVES:
+            raise ValueError(f"drive must be one of {DRIVES}, not {drive!r}")
         self.task, self.dt, self.max_lin, self.max_ang, self.ride_height = task, dt, max_lin, max_ang, ride_height
         self.suspension, self.iters, self.max_bogie = suspension, iters, max_bogie
+        self.drive, self.wheel_radius, self.steer_rate, self.wheel_accel = drive, wheel_radius, steer_rate, wheel_accel
+        self.last_slip = None
         self._playing = True
 
     def is_playing(self):
@@ -67,25 +78,37 @@ class TerrainSim:
         t = self.task
         r = t._rover
         pos, quat = r.get_world_poses()
+        kw = {}
+        if self.drive == "wheels":
+            if self.last_slip is None or self.last_slip.shape[0] != pos.shape[0]:
+                self.last_slip = torch.zeros(pos.shape[0], dtype=torch.float32, device=pos.device)
+            kw = dict(drive="wheels", wheel_radius=self.wheel_radius, steer_rate=self.steer_rate, wheel_accel=self.wheel_accel, slip=self.last_slip)
         t._engine.motion_step(pos, quat, t.linear_velocity.get_state(0), t.angular_velocity.get_state(0), dt=self.dt, substeps=n,
                               max_lin=self.max_lin, max_ang=self.max_ang, ride_height=self.ride_height,
                               joints=(r._joint_pos_targets, r._joint_vel_targets, r.get_joint_positions(), r.get_joint_velocities()),
-                              suspension=self.suspension, iters=self.iters, max_bogie=self.max_bogie)
+                              suspension=self.suspension, iters=self.iters, max_bogie=self.max_bogie, **kw)
 
 
 SUSPENSIONS = ("plane", "bogie")
+DRIVES = ("command", "wheels")
 SIMS = {"kinematic": KinematicSim, "terrain": TerrainSim}
 
 
 class VecEnv:
-    def __init__(self, headless: bool = True, sim_device: int = 0, sim: str = "kinematic", suspension: str = "plane"):
+    def __init__(self, headless: bool = True, sim_device: int = 0, sim: str = "kinematic", suspension: str = "plane", drive: str = "command",
+                 wheel_radius: float = 0.2, steer_rate: float = math.inf, wheel_accel: float = math.inf):
         if sim not in SIMS:
             raise ValueError(f"sim must be one of {tuple(SIMS)}, not {sim!r}")
         if suspension not in SUSPENSIONS:
             raise ValueError(f"suspension must be one of {SUSPENSIONS}, not {suspension!r}")
         if suspension != "plane" and sim != "terrain":
             raise ValueError(f"suspension={suspension!r} needs sim='terrain': KinematicSim writes no joint state")
+        if drive not in DRIVES:
+            raise ValueError(f"drive must be one of {DRIVES}, not {drive!r}")
+        if drive != "command" and sim != "terrain":
+            raise ValueError(f"drive={drive!r} needs sim='terrain': KinematicSim drives no joints")
         self._sim, self._suspension = sim, suspension
+        self._drive = {} if drive == "command" else dict(drive=drive, wheel_radius=wheel_radius, steer_rate=steer_rate, wheel_accel=wheel_accel)
         self._render = not headless
         self._task = None
         self._world = None
@@ -93,7 +116,7 @@ class VecEnv:
     def set_task(self, task, backend="torch", sim_params=None, init_sim=True, spawn_positions=None) -> None:
         self._task = task
         task._env = self
-        kw = {"suspension": self._suspension} if self._sim == "terrain" else {}
+        kw = dict(self._drive, suspension=self._suspension) if self._sim == "terrain" else {}
         self._world = SIMS[self._sim](task, dt=(sim_params or {}).get("dt", 0.05), **kw)
         task.set_up_scene(spawn_positions=spawn_positions)
         task.post_reset()

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Times the pose feeders of vec_env on the GPU: TerrainSim.advance(1) (one rover_motion_step launch) against KinematicSim.step()
 (about fifteen torch ops and a height lookup), both as VecEnv's world object would call them, on the same task (EXPERIMENTS.md §22),
-and "bogie", TerrainSim(suspension="bogie").advance(1) (one rover_motion_step_bogie launch; EXPERIMENTS.md §29).
+and "bogie", TerrainSim(suspension="bogie").advance(1) (one rover_motion_step_bogie launch; EXPERIMENTS.md §29); "wheels" and
+"wheels_bogie" are the same two with drive="wheels" (one rover_motion_step_drive launch; EXPERIMENTS.md §35), with ideal actuators
+unless --steer-rate / --wheel-accel say otherwise.
 
-    python tools/motion_timing.py [--envs 512 4096 65536] [--reps 30] [--feeders kinematic terrain bogie] [--json out.json]
+    python tools/motion_timing.py [--envs 512 4096 65536] [--reps 30] [--feeders kinematic terrain bogie wheels wheels_bogie] [--json out.json]
 
 Per size one task is built (synthetic scene, 37-ray distribution), stepped a few times with random actions so that the histories, the
 joint targets and the poses are those of a rollout, and then each feeder is called in windows of --inner calls between two device
@@ -14,6 +16,7 @@ call, with no enqueue cost.  --feeders kinematic alone runs on a tree without Te
 bogie mode.  Needs a GPU; there is no fallback."""
 import argparse
 import json
+import math
 import os
 import statistics
 import sys
@@ -42,7 +45,10 @@ def main():
     ap.add_argument("--envs", type=int, nargs="+", default=[512, 4096, 65536])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=200, help="calls per window")
-    ap.add_argument("--feeders", nargs="+", choices=("kinematic", "terrain", "bogie"), default=["kinematic", "terrain", "bogie"])
+    ap.add_argument("--feeders", nargs="+", choices=("kinematic", "terrain", "bogie", "wheels", "wheels_bogie"),
+                    default=["kinematic", "terrain", "bogie", "wheels", "wheels_bogie"])
+    ap.add_argument("--steer-rate", type=float, default=math.inf, help="wheels: rad/s")
+    ap.add_argument("--wheel-accel", type=float, default=math.inf, help="wheels: rad/s^2")
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -61,15 +67,19 @@ def main():
         for _ in range(5):
             env.step(2 * torch.rand(e, 2, device=task.device) - 1)
         worlds = {"kinematic": lambda: vec_env.KinematicSim(task, dt=0.05), "terrain": lambda: vec_env.TerrainSim(task, dt=0.05),
-                  "bogie": lambda: vec_env.TerrainSim(task, dt=0.05, suspension="bogie")}
+                  "bogie": lambda: vec_env.TerrainSim(task, dt=0.05, suspension="bogie"),
+                  "wheels": lambda: vec_env.TerrainSim(task, dt=0.05, drive="wheels", steer_rate=args.steer_rate, wheel_accel=args.wheel_accel),
+                  "wheels_bogie": lambda: vec_env.TerrainSim(task, dt=0.05, suspension="bogie", drive="wheels", steer_rate=args.steer_rate,
+                                                             wheel_accel=args.wheel_accel)}
         calls = {}
         for name in args.feeders:
             w = worlds[name]()
             calls[name] = (lambda w=w: w.step(render=False)) if name == "kinematic" else (lambda w=w: w.advance(1))
         pos, quat = task._rover.get_world_poses()
-        start = (pos.clone(), quat.clone())
+        jpos, jvel = task._rover.get_joint_positions(), task._rover.get_joint_velocities()
+        start = (pos.clone(), quat.clone(), jpos.clone(), jvel.clone())
         graphs = {}
-        for name in ("terrain", "bogie"):
+        for name in ("terrain", "bogie", "wheels", "wheels_bogie"):
             if name not in calls:
                 continue
             for _ in range(3):
@@ -86,11 +96,11 @@ def main():
         torch.cuda.synchronize()
         for _ in range(args.reps):
             for name, fn in calls.items():
-                pos.copy_(start[0]), quat.copy_(start[1])            # every window starts from the same poses
+                pos.copy_(start[0]), quat.copy_(start[1]), jpos.copy_(start[2]), jvel.copy_(start[3])      # every window starts from the same state
                 torch.cuda.synchronize()
                 samples[name].append(window(fn, args.inner))
             for name, graph in graphs.items():
-                pos.copy_(start[0]), quat.copy_(start[1])
+                pos.copy_(start[0]), quat.copy_(start[1]), jpos.copy_(start[2]), jvel.copy_(start[3])
                 torch.cuda.synchronize()
                 samples.setdefault(name + "_graph", []).append(window(graph.replay, 1) / args.inner)
         rec = {name: (statistics.median(v), min(v), max(v)) for name, v in samples.items()}
